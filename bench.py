@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""Headline benchmark: train windows/s of the CnnGruAttentionModel step on MI355X, the full 15-fold
-LOSO wall-clock and its mean accuracy (BASELINE.json's metric).
+"""Headline benchmark: train windows/s of the CnnGruAttentionModel step on MI355X; with --full also the full
+15-fold LOSO wall-clock and its mean accuracy (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N=1 default)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]          (N=1 default)
+
+A plain run sets up, warms up, times the K headline steps and prints the line; everything else it can measure
+(`long_run`, `roofline` / `kernels`, `b64`, `loso`, `cpu_baseline`) runs only with --full.  --dump-outputs DIR writes what the
+last timed step computed (rank 0's loss, logits, state_dict and Adam moments) as DIR/<name>.npy; the inputs are seeded, so two
+builds given the same arguments can be compared output for output.
 
 With N > 1 and no torch.distributed environment, bench.py starts the N ranks ITSELF (a
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` child, before anything touches
@@ -16,7 +21,7 @@ Every rank trains an independent replica on its own GPU (the LOSO folds share no
 SURVEY.md §8e), so the aggregate is weak scaling.
 
 Rank 0 prints ONE JSON line; see DESIGN.md §Measurement for every field.  Besides the contract's
-fields: `roofline` (dominant contraction kernel), `cpu_baseline`, `kernels` (named as rocprofv3 names
+fields, with --full: `roofline` (dominant contraction kernel), `cpu_baseline`, `kernels` (named as rocprofv3 names
 them), `b64` (the same step at the reference's B = 64; `b64.fold_batch`: fifteen such models in one set of launches) and `loso` (synthetic 15-fold LOSO with the
 reference's hyper-parameters, folds sharded over the ranks: wall_s, mean_acc, epochs_total).
 """
@@ -131,11 +136,36 @@ def src_sha16():
     return h.hexdigest()[:16]
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, eng, B, K):
+    """What a caller of the train step holds after the last timed step: its loss and logits, the model's state_dict (weights and
+    BatchNorm running statistics) and Adam's two moments, as float32 (float64 for the integer step counters).  Only the logits
+    grow with B: 8 bytes a window at K = 2, far below the budget at any batch that fits in HBM."""
+    import numpy as np
+    arrays = {"loss": eng.region("LOSS")[:1], "logits": eng.region("LOGITS", shape=(B, K)), "exp_avg": eng.exp_avg, "exp_avg_sq": eng.exp_avg_sq}
+    arrays.update({f"state.{k}": v for k, v in model.state_dict().items()})
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BYTES >> 20} MB")
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed steps of the headline leg (100 x 8 ms: box-to-box noise is +-3 %%)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps, run the blocks the options below configure: long_run, per-kernel roofline, b64, "
+                         "LOSO (emulated ranks, ablation) and the CPU baseline")
     ap.add_argument("--long-steps", type=int, default=100, help="rank 0: a second, longer timed run reported as `long_run` when --steps is shorter (0 disables)")
     ap.add_argument("--batch", type=int, default=8192, help="windows per step per GPU (64 = the reference's training batch)")
     ap.add_argument("--channels", type=int, default=6)
@@ -158,6 +188,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing rehearsal without a GPU: spawns/joins the ranks and prints the line with value null (tests only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- rank launch: before anything touches the GPU (a process that has initialised HIP must not exec/fork workers) ----
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -267,8 +299,10 @@ def main():
     dt, step_ms = timed(args.steps)
     elapsed = max_over_ranks(dt)
     loss_last = float(eng.region("LOSS")[0])
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, model, eng, B, K)
     long_run = None
-    if rank == 0 and 0 < args.steps < args.long_steps:
+    if args.full and rank == 0 and 0 < args.steps < args.long_steps:
         # the contract's K steps can be a 0.17 s region (K = 20): kernel changes of 1-3 % drown in it, so rank 0 times a longer one too
         dtl, perl = timed(args.long_steps, collective=False)
         long_run = {"steps": args.long_steps, "value_per_gpu": round(B * args.long_steps / dtl, 1), "ms_per_step": round(1e3 * dtl / args.long_steps, 3),
@@ -277,7 +311,7 @@ def main():
     # ---- per-kernel HIP-event timing (own pass: the events add bubbles) --------------------
     roofline, kernels = None, {}
     macs, fwd_macs = kernel_macs_per_window(C, T)
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         L.profile_enable(True)
         for _ in range(args.profile_steps):
             n += 1
@@ -323,7 +357,7 @@ def main():
 
     # ---- the same step at the reference's batch size (main.py:63 BATCH_SIZE = 64): latency-bound regime of configs[1..3] ----
     b64 = None
-    if args.b64_steps > 0 and rank == 0:
+    if args.full and args.b64_steps > 0 and rank == 0:
         xs, ys = x[:64].contiguous(), y[:64].contiguous()
         for i in range(30):
             step(n + i + 1, xs, ys)
@@ -347,7 +381,7 @@ def main():
 
     # ---- synthetic 15-fold LOSO with the reference's hyper-parameters (main.py:48-67), folds sharded over the ranks ----
     loso = None
-    if args.loso:
+    if args.full and args.loso:
         del x, y
         eng.drop_workspaces()
         torch.cuda.empty_cache()
@@ -435,7 +469,7 @@ def main():
                 loso["ablation"] = loso_abl
 
     cpu = None
-    if rank == 0 and args.cpu_budget > 0:          # every N: rank 0, after the GPU sections (the other ranks wait at the last barrier)
+    if args.full and rank == 0 and args.cpu_budget > 0:          # every N: rank 0, after the GPU sections (the other ranks wait at the last barrier)
         from oracle.cpu_model import time_train_steps      # reported baseline only; never the product path
         r = time_train_steps(batch=64, C=C, T=T, K=K, budget_s=args.cpu_budget)
         r256 = time_train_steps(batch=256, C=C, T=T, K=K, budget_s=6.0, min_steps=4, threads=r["threads"])      # ~10 steps of 0.6 s (round 3: two)
@@ -480,7 +514,7 @@ def main():
                                      "convolutions and the head on fp32 MFMA"},
             "step_mfma_frac": round(value / n_seen * train_flop / (PEAK_F32_MFMA_TFLOPS * 1e12), 4),
             "train_mflop_per_window": round(train_flop / 1e6, 2),
-            "loss_last": round(loss_last, 5), "lib_sha16": lib_sha16(), "src_sha16": src_sha16(),
+            "loss_last": round(loss_last, 5), "lib_sha16": lib_sha16(), "src_sha16": src_sha16(), "full": args.full,
             "roofline": roofline, "cpu_baseline": cpu, "b64": b64, "loso": loso, "kernels": kernels,
         }
         print(json.dumps(out), flush=True)

@@ -7,7 +7,6 @@ Fixture: tests/golden/loso_parity_ref.json (tests/golden/make_parity_fixture.py;
 container).  The synthetic dataset is regenerated here from the generator arguments the fixture records."""
 import json
 import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -24,7 +23,7 @@ def test_loso_accuracy_matches_reference_over_seeds(tmp_path_factory):
     import loso_parity as LP
     fx = json.loads((GOLDEN / "loso_parity_ref.json").read_text())
     ds, tr = fx["dataset"], fx["training"]
-    data = Path("/tmp") / f"msig_parity_w{ds['windows_per_subject']}_t{ds['T']}_d{ds['difficulty']}"
+    data = tmp_path_factory.getbasetemp() / f"msig_parity_w{ds['windows_per_subject']}_t{ds['T']}_d{ds['difficulty']}"
     LP.ensure_data(data, ds["windows_per_subject"], ds["T"], ds["difficulty"])
     out = tmp_path_factory.mktemp("parity")
     folds = list(fx["runs"][0]["folds"])
@@ -55,7 +54,7 @@ def test_loso_accuracy_matches_reference_over_seeds(tmp_path_factory):
 
 
 @pytest.mark.timeout(900)
-def test_deterministic_loso_matches_reference_fold_by_fold(tmp_path):
+def test_deterministic_loso_matches_reference_fold_by_fold(tmp_path, tmp_path_factory):
     """per-fold accuracy AND weighted F1 of the SHIPPED LOSO path — `run_experiments`, LockstepTrainer, default
     fold grouping, pinned kernel forms — against the reference's own CPU run (fixture: tests/golden/loso_parity_det_ref.json, made by
     tests/golden/make_parity_fixture.py --deterministic from the imported reference) in the deterministic setting: dropout 0,
@@ -67,7 +66,7 @@ def test_deterministic_loso_matches_reference_fold_by_fold(tmp_path):
     from multimodalsignal_amd.synth import ALL_SUBJECTS, CHANNELS6, make_synthetic_wesad
     fx = json.loads((GOLDEN / "loso_parity_det_ref.json").read_text())
     ds, tr = fx["dataset"], fx["training"]
-    data = Path("/tmp") / f"msig_parity_w{ds['windows_per_subject']}_t{ds['T']}_d{ds['difficulty']}"
+    data = tmp_path_factory.getbasetemp() / f"msig_parity_w{ds['windows_per_subject']}_t{ds['T']}_d{ds['difficulty']}"
     if not (data / "_channel_names.txt").exists():
         make_synthetic_wesad(data, windows_per_subject=ds["windows_per_subject"], T=ds["T"], difficulty=ds["difficulty"])
     names = (data / "_channel_names.txt").read_text().split()
@@ -143,7 +142,7 @@ BENCH_VAL_CAP = 5e-2              # ... up to the distance two fp32 runs of one 
 
 
 @pytest.mark.timeout(900)
-def test_bench_setting_early_stopping_matches_reference(tmp_path):
+def test_bench_setting_early_stopping_matches_reference(tmp_path, tmp_path_factory):
     """The regime the bench's LOSO block runs in — 270 +- 20 windows per subject, difficulty 2, B = 64, patience 20, epoch budget 100,
     where the reference's inverted early stopping FIRES — in the deterministic setting, through the shipped path (run_experiments,
     lockstep fold batch), for three folds of the 15-fold split: S3 (the HIP path stops it at the earliest possible epoch, 21), S7 and S5
@@ -160,7 +159,7 @@ def test_bench_setting_early_stopping_matches_reference(tmp_path):
     from multimodalsignal_amd.trainer import EarlyStopping
     fx = json.loads((GOLDEN / "loso_parity_bench_ref.json").read_text())
     ds, tr = fx["dataset"], fx["training"]
-    data = Path("/tmp") / f"msig_parity_w{ds['windows_per_subject']}_s{ds['window_spread']}_t{ds['T']}_d{ds['difficulty']}"
+    data = tmp_path_factory.getbasetemp() / f"msig_parity_w{ds['windows_per_subject']}_s{ds['window_spread']}_t{ds['T']}_d{ds['difficulty']}"
     if not (data / "_channel_names.txt").exists():
         make_synthetic_wesad(data, windows_per_subject=ds["windows_per_subject"], T=ds["T"], difficulty=ds["difficulty"], window_spread=ds["window_spread"])
     names = (data / "_channel_names.txt").read_text().split()

@@ -45,7 +45,7 @@ def test_world_size_mismatch_is_an_error():
 def test_gpus2_on_one_gpu_gloo_rehearsal():
     """GPU tier: two real ranks (sharing the box's one GPU, gloo in place of RCCL) through the whole bench line, the sharded
     LOSO block included: each rank runs its own SubjectStore, LockstepTrainer fold batches and the metric gather."""
-    r = _run(["--gpus", "2", "--batch", "256", "--samples", "256", "--steps", "2", "--warmup", "1", "--cpu-budget", "0.5", "--b64-steps", "20",
+    r = _run(["--gpus", "2", "--full", "--batch", "256", "--samples", "256", "--steps", "2", "--warmup", "1", "--cpu-budget", "0.5", "--b64-steps", "20",
               "--loso", "1", "--loso-windows", "24", "--loso-spread", "3", "--loso-epochs", "3", "--profile-steps", "1", "--long-steps", "4"],
              {"MSIG_DIST_BACKEND": "gloo"}, timeout=800)
     assert r.returncode == 0, "\n".join([ln for ln in r.stderr.splitlines() if "[rank0]" in ln][-60:]) + "\n" + r.stderr[-3000:]
@@ -55,3 +55,28 @@ def test_gpus2_on_one_gpu_gloo_rehearsal():
     assert j["loso"]["folds"] == 15 and j["loso"]["folds_per_rank"] == [8, 7] and 0.0 < j["loso"]["mean_acc"] <= 1.0
     assert j["cpu_baseline"] is not None and j["cpu_baseline"]["value"] > 0          # reported at every N, not only N = 1
     assert j["long_run"]["steps"] == 4 and j["ms_per_step_spread"]["min"] <= j["ms_per_step_spread"]["max"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_headline_only_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries the headline step alone; --dump-outputs writes the last timed step's outputs, and two runs
+    with the same arguments write the same ones (seeded inputs and weights, no float atomics)."""
+    import numpy as np
+    args = ["--gpus", "1", "--batch", "256", "--samples", "256", "--steps", "3", "--warmup", "1"]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run(args + ["--dump-outputs", str(d)], timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _json_line(r.stdout)
+        assert j["steps"] == 3 and j["value"] > 0 and j["ms_per_step"] > 0 and j["full"] is False
+        assert j["roofline"] is None and j["b64"] is None and j["loso"] is None and j["cpu_baseline"] is None and j["long_run"] is None
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.name: np.load(f) for f in files})
+    a, b = dumps
+    assert {"loss.npy", "logits.npy", "exp_avg.npy", "exp_avg_sq.npy", "state.classifier.3.weight.npy"} <= set(a)
+    assert a["logits.npy"].shape == (256, 2) and np.isfinite(a["loss.npy"]).all()
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
