@@ -27,9 +27,10 @@
 extern "C" {
 #endif
 
-#define MSIG_ABI_VERSION 4      /* 2: msig_multi.form_folds, msig_struct_bytes, kernel forms; 3: msig_multi.step (per-fold Adam step);
+#define MSIG_ABI_VERSION 5      /* 2: msig_multi.form_folds, msig_struct_bytes, kernel forms; 3: msig_multi.step (per-fold Adam step);
                                    4: kernel forms are per call (msig_batch.fwd_form / bwd_form; msig_set_kernel_form is gone),
-                                      MSIG_E_FORM, the two-vector stash only inside the fused train-step calls, msig_batch.loss_acc */
+                                      MSIG_E_FORM, the two-vector stash only inside the fused train-step calls, msig_batch.loss_acc;
+                                   5: msig_batch.keep_for_backward (backward through an eval-mode forward), msig_batch.dx (input gradient) */
 
 #define MSIG_E_NULL      (-1)  /* a required pointer is NULL                         */
 #define MSIG_E_SHAPE     (-2)  /* B/C/T/K outside the supported range                */
@@ -114,12 +115,12 @@ enum msig_ws {
   MSIG_WS_BNB_STAT,      /* c1,c2 per channel (2 x 32)                         */
   MSIG_WS_GRAD_PART,     /* per-workgroup partial weight gradients             */
   MSIG_WS_GI,            /* layer-1 input projections (small batches only: < 192 batch tiles) */
-  MSIG_WS_POOLC1,        /* (B,P1,4) bytes: MaxPool-1 decisions, 2 bits per channel (training only)      */
+  MSIG_WS_POOLC1,        /* (B,P1,4) bytes: MaxPool-1 decisions, 2 bits per channel (kept for a backward) */
   MSIG_WS_POOLC2,        /* (B,TP,8) bytes: MaxPool-2 decisions                                          */
   MSIG_WS_G1W,           /* (B, S, 2, 16, 16*ceil(7C/16)) per-window pieces of conv1's weight-gradient correlation, [sum dz x][sum xhat x]: the
-                            BatchNorm-1 backward is applied to them by linearity (training only).  S = 1 from B = 256 on; smaller
+                            BatchNorm-1 backward is applied to them by linearity (backward only).  S = 1 from B = 256 on; smaller
                             batches cut a window into up to 8 segments, one record each (room for 8 is reserved)        */
-  MSIG_WS_GATE_EO,       /* (B, C, 2)  sums of the even- / odd-indexed samples of a channel (training only)              */
+  MSIG_WS_GATE_EO,       /* (B, C, 2)  sums of the even- / odd-indexed samples of a channel (kept for a backward)       */
   MSIG_NWS
 };
 
@@ -134,14 +135,16 @@ typedef struct msig_shape {
 int msig_stage_lengths(int T, int32_t* out /* host, [4] = L1,P1,L2,TP */);
 
 /* Byte offset of every workspace region (256-byte aligned); offsets[MSIG_NWS] is
- * the total.  `training`=0 omits stashes and gradient scratch. */
+ * the total.  `training`=0 omits stashes and gradient scratch.  An eval-mode forward that keeps what a backward needs
+ * (msig_batch.keep_for_backward = 1) uses the training layout: pass training || keep_for_backward. */
 int msig_workspace_layout(const msig_shape* s, int training, int64_t* offsets /* host, [MSIG_NWS+1] */);
 int64_t msig_workspace_bytes(const msig_shape* s, int training);
 
 /* One mini-batch of work: everything trainer.py:140-149 touches. */
 typedef struct msig_batch {
   msig_shape shape;
-  int32_t  training;      /* 1 = model.train(): batch-stat BN, dropout, stashes; 0 = model.eval() */
+  int32_t  training;      /* 1 = model.train(): batch-stat BN (running statistics updated), dropout, stashes; 0 = model.eval():
+                             running-stat BN, no dropout, nothing kept for a backward unless keep_for_backward = 1 */
   float    bn_momentum;   /* 0.1   (nn.BatchNorm1d default)                    */
   float    bn_eps;        /* 1e-5                                              */
   int32_t  dropout_thr;   /* round(p*256): element kept iff hash byte >= thr; 0 disables */
@@ -168,6 +171,16 @@ typedef struct msig_batch {
                              loss_acc[1] += correctly classified windows.  One thread adds, in stream order (deterministic); the caller
                              zeroes them when a pass starts and reads them when it ends — the per-step accumulation launch and host op of
                              trainer.py:152-153 disappear.  In a fold batch fold s's pair sits s * stride_bytes further on, like every buffer */
+  int32_t  keep_for_backward; /* ABI 5.  With training = 0: 1 = the forward keeps what a backward needs (pooling decisions, conv outputs,
+                             GRU stashes, the head's activations) while it still runs in eval mode — running-stat BatchNorm, running
+                             statistics and num_batches_tracked untouched, no dropout — and the *_bwd calls then accept the descriptor
+                             (BatchNorm backward in its eval form: dy = gamma * invstd_running * dz).  The workspace is sized as for
+                             training.  0 = an eval forward as before (the *_bwd calls return MSIG_E_SHAPE).  Ignored when training = 1.
+                             The logits do not depend on it */
+  float*   dx;            /* ABI 5.  NULL = not wanted.  Otherwise the front end's backward (msig_frontend_bwd, and so msig_backward) also
+                             writes dL/dx, (B,C,T) fp32, 16-byte aligned, through ChannelAttention's gate and its mean over T: one
+                             launch more, every other output unchanged.  Only the single-model calls take it: the fused train step and
+                             the fold batches (and a descriptor with training = keep_for_backward = 0) return MSIG_E_SHAPE */
 } msig_batch;
 
 /* ChannelAttention + cnn_encoder forward (models.py:75-76): x -> WS_P2. */

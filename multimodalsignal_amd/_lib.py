@@ -55,11 +55,12 @@ class Batch(C.Structure):
         ("bn_state", C.c_void_p), ("bn_count", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
         ("gru_layers", C.c_int32), ("fwd_form", C.c_int16), ("bwd_form", C.c_int16),
         ("loss_acc", C.c_void_p),
+        ("keep_for_backward", C.c_int32), ("dx", C.c_void_p),          # ABI 5
     ]
 
 
 MAX_FOLDS = 16
-ABI_VERSION = 4       # include/msig.h MSIG_ABI_VERSION
+ABI_VERSION = 5       # include/msig.h MSIG_ABI_VERSION
 
 
 class Multi(C.Structure):

@@ -203,13 +203,14 @@ static int make_ctx(const msig_batch* b, Ctx& c, bool need_grads) {
   if (rc) return rc;
   if (!b->x || !b->params || !b->bn_state || !b->bn_count || !b->ws) return MSIG_E_NULL;
   if (need_grads && !b->grads) return MSIG_E_NULL;
-  if (((uintptr_t)b->x | (uintptr_t)b->params | (uintptr_t)b->ws | (uintptr_t)b->grads) & 15) return MSIG_E_ALIGN;
+  if (((uintptr_t)b->x | (uintptr_t)b->params | (uintptr_t)b->ws | (uintptr_t)b->grads | (uintptr_t)b->dx) & 15) return MSIG_E_ALIGN;
   if (b->dropout_thr < 0 || b->dropout_thr > 256) return MSIG_E_SHAPE;
   if ((uintptr_t)b->loss_acc & 7) return MSIG_E_ALIGN;
+  if (b->dx && !msig_keeps(b)) return MSIG_E_SHAPE;         // an input gradient needs a forward that kept for a backward
   if (b->gru_layers < 0 || b->gru_layers > 2) return MSIG_E_SHAPE;
   if ((rc = msig_check_forms(b))) return rc;
   c.d = make_dims(b->shape);
-  rc = msig_workspace_layout(&b->shape, b->training, c.w.off);
+  rc = msig_workspace_layout(&b->shape, msig_keeps(b), c.w.off);      // an eval forward kept for a backward has the training layout
   if (rc) return rc;
   if (b->ws_bytes < c.w.off[MSIG_NWS]) return MSIG_E_WORKSPACE;
   c.w.base = (char*)b->ws;
@@ -230,27 +231,28 @@ extern "C" int msig_head_ce_fwd(const msig_batch* b, void* stream) {
 }
 extern "C" int msig_head_ce_bwd(const msig_batch* b, const float* dlogits, void* stream) {
   Ctx c; int rc = make_ctx(b, c, true); if (rc) return rc;
-  if (!b->training) return MSIG_E_SHAPE;
+  if (!msig_keeps(b)) return MSIG_E_SHAPE;
   ColsumPlan plan;
   if ((rc = launch_head_bwd(b, dlogits, c.d, c.w, c.po, plan, single_fold(b), (hipStream_t)stream))) return rc;
   return launch_colsum_plan(plan, single_fold(b), (hipStream_t)stream);
 }
 extern "C" int msig_gru_bwd(const msig_batch* b, void* stream) {
   Ctx c; int rc = make_ctx(b, c, true); if (rc) return rc;
-  if (!b->training) return MSIG_E_SHAPE;
+  if (!msig_keeps(b)) return MSIG_E_SHAPE;
   ColsumPlan plan;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, single_fold(b), (hipStream_t)stream))) return rc;
   return launch_colsum_plan(plan, single_fold(b), (hipStream_t)stream);
 }
 extern "C" int msig_frontend_bwd(const msig_batch* b, void* stream) {
   Ctx c; int rc = make_ctx(b, c, true); if (rc) return rc;
-  if (!b->training) return MSIG_E_SHAPE;
+  if (!msig_keeps(b)) return MSIG_E_SHAPE;
   ColsumPlan plan;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, single_fold(b), (hipStream_t)stream))) return rc;
   return launch_colsum_plan(plan, single_fold(b), (hipStream_t)stream);
 }
 
 static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true) {
+  if (b->dx && fc.stride != 0) return MSIG_E_SHAPE;          // no input gradients in fold batches
   Ctx c; int rc = make_ctx(b, c, false); if (rc) return rc;
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;      // nothing has been launched: no model state has changed
   if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
@@ -264,7 +266,7 @@ extern "C" int msig_forward(const msig_batch* b, void* stream) {
 
 extern "C" int msig_backward(const msig_batch* b, const float* dlogits, void* stream) {
   Ctx c; int rc = make_ctx(b, c, true); if (rc) return rc;
-  if (!b->training) return MSIG_E_SHAPE;
+  if (!msig_keeps(b)) return MSIG_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const FoldCtx fc = single_fold(b);
   ColsumPlan plan;      // every weight-gradient reduction of the pass, done by one launch at the end
@@ -287,6 +289,7 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
                          float beta2, float eps, float weight_decay, int64_t step, hipStream_t st) {
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
+  if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
   if (!exp_avg || !exp_avg_sq) return MSIG_E_NULL;
   if (step < 1) return MSIG_E_SHAPE;
   if (steps)

@@ -641,18 +641,20 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_pass1(const float* __restrict
   }
 }
 
-// sums -> c1 = mean(dz), c2 = mean(dz*xhat); also d(gamma), d(beta)
+// sums -> c1 = mean(dz), c2 = mean(dz*xhat); also d(gamma), d(beta).  After an eval-mode forward (batch_stats = 0) the normalisation
+// used constants (the running statistics), not functions of the batch: BatchNorm's backward is then dy = scale * dz, i.e. c1 = c2 = 0
+// in the consumers' scale * (dz - c1 - xhat * c2); d(gamma) = sum dz * xhat and d(beta) = sum dz as in training.
 __global__ __launch_bounds__(FIN_THREADS) void bn_bwd_finalize_kernel(const float* __restrict__ part, int nrows, int CH, double count,
                                                               float* __restrict__ cstat, float* __restrict__ dgamma,
-                                                              float* __restrict__ dbeta, const FoldCtx fc) {
+                                                              float* __restrict__ dbeta, int batch_stats, const FoldCtx fc) {
   FOLD_BEGIN; FS(part); FS(cstat); FS(dgamma); FS(dbeta);
   __shared__ double red[FIN_THREADS];
   const int tid = threadIdx.x, ncol = 2 * CH;
   fin_colsums(part, nrows, ncol, red);
   if (tid < ncol) {
     const double s = red[tid];
-    if (tid < CH) { dbeta[tid] = (float)s; cstat[tid] = (float)(s / count); }
-    else { dgamma[tid - CH] = (float)s; cstat[tid] = (float)(s / count); }
+    if (tid < CH) dbeta[tid] = (float)s; else dgamma[tid - CH] = (float)s;
+    cstat[tid] = batch_stats ? (float)(s / count) : 0.f;
   }
 }
 
@@ -808,6 +810,58 @@ __global__ __launch_bounds__(256) void conv2_bwd_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------
+// Stage 1's backward staging by QUADS of positions tq .. tq + 3 (tq % 4 == 0) x channels 4 sc4 .. +3, shared by conv1_bwd and
+// conv1_bwd_dx.  Needs L1 % 4 == 0 (then P1 = L1 / 2): a quad is wholly inside or wholly outside the window.  quad_load issues
+// three dP1 vectors, three decision bytes and four y1 vectors from two base addresses with immediate offsets (the software
+// pipelines issue it an item ahead); quad_dz_xhat routes dP1 to dz = dL/d(bn1 output) through the decisions, each decoded once,
+// and forms xhat = (y1 - mean) * invstd.  Both are zero for a quad past the window's end.
+// ------------------------------------------------------------------------------------
+struct QuadRaw { float4 g[3], y[4]; unsigned c[3]; };
+__device__ __forceinline__ void quad_load(QuadRaw& r, const float* __restrict__ dp1, const uint8_t* __restrict__ code1,
+                                          const float* __restrict__ y1, int b, int tq, int L1, int P1, int sc4) {
+  const int tqc = tq < L1 - 4 ? tq : L1 - 4;       // a quad is wholly inside or wholly outside the window
+  const int ph = tqc >> 1, ph2 = ph + 2 < P1 ? ph + 2 : P1 - 1;
+  const float* dpb = dp1 + (size_t)b * P1 * 16;
+  const uint8_t* cb = code1 + (size_t)b * P1 * 4;
+  const float* yb = y1 + (size_t)b * L1 * 16;
+  const unsigned o = (unsigned)(ph * 16 + sc4 * 4), oc = (unsigned)(ph * 4 + sc4), oy = (unsigned)(tqc * 16 + sc4 * 4);
+  r.g[0] = *(const float4*)(dpb + o); r.g[1] = *(const float4*)(dpb + o + 16); r.g[2] = *(const float4*)(dpb + (unsigned)(ph2 * 16 + sc4 * 4));
+  r.c[0] = cb[oc]; r.c[1] = cb[oc + 4]; r.c[2] = cb[(unsigned)(ph2 * 4 + sc4)];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r.y[j] = *(const float4*)(yb + oy + 16 * j);
+}
+// the quad's four positions t = tq .. tq + 3 (tq even): window ph = tq / 2 is centred on tq, ph + 1 on tq + 2;
+//   dz[tq]     = [c(ph) == centre] g(ph)
+//   dz[tq + 1] = [c(ph) == right] g(ph)     + [c(ph+1) == left] g(ph+1)
+//   dz[tq + 2] = [c(ph+1) == centre] g(ph+1)
+//   dz[tq + 3] = [c(ph+1) == right] g(ph+1) + [c(ph+2) == left] g(ph+2)        (no window ph + 2 at the end of the sequence)
+__device__ __forceinline__ void quad_dz_xhat(const QuadRaw& r, int tq, int L1, int P1, const float* bn_mean, const float* bn_inv,
+                                             float4 dz[4], float4 xh[4]) {
+  const bool inside = tq < L1, has2 = (tq >> 1) + 2 < P1;
+  const float g0[4] = {r.g[0].x, r.g[0].y, r.g[0].z, r.g[0].w}, g1[4] = {r.g[1].x, r.g[1].y, r.g[1].z, r.g[1].w},
+              g2[4] = {r.g[2].x, r.g[2].y, r.g[2].z, r.g[2].w};
+  float d[4][4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned c0 = (r.c[0] >> (2 * e)) & 3u, c1 = (r.c[1] >> (2 * e)) & 3u, c2 = has2 ? (r.c[2] >> (2 * e)) & 3u : 3u;
+    d[0][e] = c0 == 1u ? g0[e] : 0.f;
+    d[1][e] = (c0 == 2u ? g0[e] : 0.f) + (c1 == 0u ? g1[e] : 0.f);
+    d[2][e] = c1 == 1u ? g1[e] : 0.f;
+    d[3][e] = (c1 == 2u ? g1[e] : 0.f) + (c2 == 0u ? g2[e] : 0.f);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float4 dq = make_float4(d[j][0], d[j][1], d[j][2], d[j][3]), h;
+    h.x = (r.y[j].x - bn_mean[0]) * bn_inv[0];
+    h.y = (r.y[j].y - bn_mean[1]) * bn_inv[1];
+    h.z = (r.y[j].z - bn_mean[2]) * bn_inv[2];
+    h.w = (r.y[j].w - bn_mean[3]) * bn_inv[3];
+    if (!inside) { dq = make_float4(0.f, 0.f, 0.f, 0.f); h = dq; }
+    dz[j] = dq; xh[j] = h;
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // conv1 backward: per window G[o][c,kk] = sum_t dy1[t][o] x[c][2t+kk-3]; then
 //   dW1[o][c][kk] += s[b,c] * G      and      ds[b,c] = sum_{o,kk} w1[o][c][kk] * G
 // ------------------------------------------------------------------------------------
@@ -837,7 +891,7 @@ __device__ __forceinline__ int g1_row(int r) { return (r >> 2) * G1_QS + (r & 3)
 // sums dz and dz * xhat per channel on the side (-> the partials bn_bwd_finalize turns into c1, c2, d gamma, d beta) and stores the
 // window's Gdz and Gxh (6 KB per window at C = 6).  conv1_bwd_fin then combines them with c1, c2 and Sx (which is a sum of samples of
 // one parity less a few at the window's edges: the gate kernel leaves the two parity sums) and forms dW1 and ds.
-// Neither dy1 nor dz1 ever exists in HBM.
+// Neither dy1 nor dz1 ever exists in HBM (conv1_bwd_dx, run only when an input gradient is wanted, rebuilds dy1 in LDS from the same pieces).
 // fp32 MFMA shares its pipe with the VALU, so every VALU instruction here costs matrix time (the first version of this kernel
 // issued 450 per chunk and wave for staging — 24 separately addressed loads, 2-bit decisions decoded per position — and 14 per MFMA
 // k-step).  Now a thread stages a QUAD of positions (4 t x 4 channels): three dP1 vectors, three decision bytes and four y1 vectors
@@ -886,8 +940,8 @@ __global__ __launch_bounds__(256, CONV1_BWD_WGS) void conv1_bwd_kernel(const flo
   const bool pipe = PIPE_OK && (T & 7) == 0 && 2 * P1 == L1 && L1 >= 8;
   constexpr int NX4 = PIPE_OK ? (CT * (C1_XW / 4) + 255) / 256 : 1;
   const int sq = tid >> 2, sc4 = tid & 3;    // staging role: quad sq of the chunk, channels 4 sc4 .. +3
-  float4 xr[NX4], yq[4], gq[3];
-  unsigned cq[3];
+  float4 xr[NX4];
+  QuadRaw qr;
   auto prefetch = [&](int b, int ch) {
     const int t0 = ch * G1_TCH, g_base = 2 * t0 - 4;
     const float* xb = x + (size_t)b * C * T;
@@ -898,16 +952,7 @@ __global__ __launch_bounds__(256, CONV1_BWD_WGS) void conv1_bwd_kernel(const flo
       const int gc = g0 < 0 ? 0 : (g0 > T - 4 ? T - 4 : g0);          // unconditional, clamped load
       xr[j] = *(const float4*)(xb + (unsigned)(c * T + gc));
     }
-    const int tq = t0 + 4 * sq, tqc = tq < L1 - 4 ? tq : L1 - 4;       // a quad is wholly inside or wholly outside the window
-    const int ph = tqc >> 1, ph2 = ph + 2 < P1 ? ph + 2 : P1 - 1;
-    const float* dpb = dp1 + (size_t)b * P1 * 16;
-    const uint8_t* cb = code1 + (size_t)b * P1 * 4;
-    const float* yb = y1 + (size_t)b * L1 * 16;
-    const unsigned o = (unsigned)(ph * 16 + sc4 * 4), oc = (unsigned)(ph * 4 + sc4), oy = (unsigned)(tqc * 16 + sc4 * 4);
-    gq[0] = *(const float4*)(dpb + o); gq[1] = *(const float4*)(dpb + o + 16); gq[2] = *(const float4*)(dpb + (unsigned)(ph2 * 16 + sc4 * 4));
-    cq[0] = cb[oc]; cq[1] = cb[oc + 4]; cq[2] = cb[(unsigned)(ph2 * 4 + sc4)];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) yq[j] = *(const float4*)(yb + oy + 16 * j);
+    quad_load(qr, dp1, code1, y1, b, t0 + 4 * sq, L1, P1, sc4);
   };
   const int CPS = conv1_bwd_cps(B, nchunk), SEG = conv1_bwd_segs(B, nchunk), nitems = B * SEG;
   if (pipe && (int)blockIdx.x < nitems) prefetch(blockIdx.x / SEG, (blockIdx.x % SEG) * CPS);
@@ -932,33 +977,12 @@ __global__ __launch_bounds__(256, CONV1_BWD_WGS) void conv1_bwd_kernel(const flo
             *(float4*)&xs[c * G1_XS + 4 * i4] = q;
           }
         }
-        // the quad's four positions t = tq .. tq + 3 (tq even): window ph = tq / 2 is centred on tq, ph + 1 on tq + 2;
-        //   dz[tq]     = [c(ph) == centre] g(ph)
-        //   dz[tq + 1] = [c(ph) == right] g(ph)     + [c(ph+1) == left] g(ph+1)
-        //   dz[tq + 2] = [c(ph+1) == centre] g(ph+1)
-        //   dz[tq + 3] = [c(ph+1) == right] g(ph+1) + [c(ph+2) == left] g(ph+2)        (no window ph + 2 at the end of the sequence)
-        const int tq = t0 + 4 * sq;
-        const bool inside = tq < L1, has2 = (tq >> 1) + 2 < P1;
-        const float g0[4] = {gq[0].x, gq[0].y, gq[0].z, gq[0].w}, g1[4] = {gq[1].x, gq[1].y, gq[1].z, gq[1].w}, g2[4] = {gq[2].x, gq[2].y, gq[2].z, gq[2].w};
-        float d[4][4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const unsigned c0 = (cq[0] >> (2 * e)) & 3u, c1 = (cq[1] >> (2 * e)) & 3u, c2 = has2 ? (cq[2] >> (2 * e)) & 3u : 3u;
-          d[0][e] = c0 == 1u ? g0[e] : 0.f;
-          d[1][e] = (c0 == 2u ? g0[e] : 0.f) + (c1 == 0u ? g1[e] : 0.f);
-          d[2][e] = c1 == 1u ? g1[e] : 0.f;
-          d[3][e] = (c1 == 2u ? g1[e] : 0.f) + (c2 == 0u ? g2[e] : 0.f);
-        }
+        float4 dq[4], h[4];
+        quad_dz_xhat(qr, t0 + 4 * sq, L1, P1, bn_mean, bn_inv, dq, h);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          float4 dq = make_float4(d[j][0], d[j][1], d[j][2], d[j][3]), h;
-          h.x = (yq[j].x - bn_mean[0]) * bn_inv[0];
-          h.y = (yq[j].y - bn_mean[1]) * bn_inv[1];
-          h.z = (yq[j].z - bn_mean[2]) * bn_inv[2];
-          h.w = (yq[j].w - bn_mean[3]) * bn_inv[3];
-          if (!inside) { dq = make_float4(0.f, 0.f, 0.f, 0.f); h = dq; }
-          *(float4*)&dzs[sq * G1_QS + j * 16 + sc4 * 4] = dq;
-          *(float4*)&xhs[sq * G1_QS + j * 16 + sc4 * 4] = h;
+          *(float4*)&dzs[sq * G1_QS + j * 16 + sc4 * 4] = dq[j];
+          *(float4*)&xhs[sq * G1_QS + j * 16 + sc4 * 4] = h[j];
         }
       } else {
         stage_x_chunk<false>(xs, xb, C, T, t0, tid, G1_XS);
@@ -1110,6 +1134,124 @@ __global__ __launch_bounds__(256) void conv1_bwd_fin_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------
+// Input gradient (msig_batch.dx, ABI 5): conv1's backward with respect to its input plus the gate's, per window b:
+//   dy1[t'][o] = scale[o] * (dz[t'][o] - c1[o] - xhat[t'][o] * c2[o])               (c1 = c2 = 0 after an eval-mode forward)
+//   du[c][t]   = sum_o sum_{kk : t + 3 - kk even, t' = (t + 3 - kk) / 2 in [0, L1)} w1[o][c][kk] * dy1[t'][o]
+//   dmean[c]   = sum_j W1[j][c] [pre[j] > 0] sum_c' W2[c'][j] ds[c'] s(1 - s)[c']    (0 for C < 4: the hidden layer is empty)
+//   dx[c][t]   = s[c] * du[c][t] + dmean[c] / T
+// A thread owns one u and the output pair t = 2u (taps kk = 1, 3, 5 <-> t' = u + 1, u, u - 1) and t = 2u + 1 (kk = 0, 2, 4, 6 <->
+// t' = u + 2 .. u - 1): it reads the four dy1 rows u - 1 .. u + 2 from LDS and contracts them with conv1's weights, which are the
+// same for every lane (scalar loads).  An item (one workgroup) is 256 u of one window; it stages dy1 rows u0 - 4 .. u0 + 259 from dP1,
+// the pooling decisions and y1 — by quads, as conv1_bwd does, with BatchNorm-1's backward applied on the way into LDS — and rows
+// outside [0, L1) are zero, which is the convolution's zero padding at both edges of the window.  Planned as HBM-bound: y1, dP1 and
+// the decisions are read once (+ 3 % halo) and dx is written once, at ~56 FMA per output element; measured at 2.6 TB/s (DESIGN.md
+// section 11: a workgroup's load, contraction and store phases follow one another and four workgroups per CU do not hide it).  LDS rows are DX_PS = 20 floats
+// apart: the four ds_read_b128 lane groups (16 consecutive-ish u each) then hit 16 distinct 16-byte slots of the 64 banks (20 = 4 x 5,
+// 5 odd), and the staging stores of 8 neighbouring lanes cover the 32 store banks once — no bank conflicts (the im2col layouts of the
+// conv kernels have 38-46 %).  ds (conv1_bwd_fin) is read, never written, here: its own launch, after that one.
+// ------------------------------------------------------------------------------------
+#define DX_UCH 256              // u (output pairs) per item: one per thread
+#define DX_ROWS (DX_UCH + 8)    // staged dy1 rows t' = u0 - 4 .. u0 + DX_UCH + 3: whole quads, the halo rows u0 - 1 and u0 + 256, u0 + 257 included
+#define DX_PS 20                // LDS row stride (floats) of a 16-channel dy1 row
+__global__ __launch_bounds__(256) void conv1_bwd_dx_kernel(const float* __restrict__ dp1, const uint8_t* __restrict__ code1,
+                                                           const float* __restrict__ y1, const float* __restrict__ stat,
+                                                           const float* __restrict__ cstat, const float* __restrict__ w1,
+                                                           const float* __restrict__ gate_s, const float* __restrict__ pre,
+                                                           const float* __restrict__ gw1, const float* __restrict__ gw2,
+                                                           const float* __restrict__ ds, float* __restrict__ dx, int C, int Cr, int T,
+                                                           int L1, int P1, const FoldCtx fc) {
+  FOLD_BEGIN; FS(dp1); FS(code1); FS(y1); FS(stat); FS(cstat); FS(w1); FS(gate_s); FS(pre); FS(gw1); FS(gw2); FS(ds); FS(dx);
+  __shared__ __attribute__((aligned(16))) float dys[DX_ROWS * DX_PS];     // row i <-> t' = u0 - 4 + i
+  __shared__ float s_s[MSIG_MAX_C], s_dm[MSIG_MAX_C];
+  const int tid = threadIdx.x;
+  const int nchunk = (L1 + DX_UCH - 1) / DX_UCH;
+  const int b = blockIdx.x / nchunk, u0 = (blockIdx.x - b * nchunk) * DX_UCH;
+  // the gate: dmean / T and s of this window (gate_bwd's expression for dL/d(fc.0 output))
+  if (tid < C) {
+    float a = 0.f;
+    for (int j = 0; j < Cr; ++j)
+      if (pre[(size_t)b * Cr + j] > 0.f) {
+        float da = 0.f;
+        for (int cc = 0; cc < C; ++cc) {
+          const float sv = gate_s[(size_t)b * C + cc];
+          da += gw2[cc * Cr + j] * ds[(size_t)b * C + cc] * sv * (1.f - sv);
+        }
+        a += gw1[j * C + tid] * da;
+      }
+    s_s[tid] = gate_s[(size_t)b * C + tid];
+    s_dm[tid] = a / (float)T;
+  }
+  // staging: unit i = quad i >> 2 (rows 4 (i >> 2) .. +3) x channels 4 c4 .. +3, c4 = i & 3 = tid & 3 for every unit of a thread
+  const int c4 = tid & 3;
+  float bn_mean[4], bn_inv[4], bn_sc[4], bn_c1[4], bn_c2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int ch = c4 * 4 + e;
+    bn_mean[e] = stat[ch]; bn_inv[e] = stat[16 + ch]; bn_sc[e] = stat[32 + ch]; bn_c1[e] = cstat[ch]; bn_c2[e] = cstat[16 + ch];
+  }
+  const bool quads = (L1 & 3) == 0;
+  for (int i = tid; i < DX_ROWS; i += 256) {
+    const int q = i >> 2, tq = u0 - 4 + 4 * q;
+    float4 dz[4], xh[4];
+    if (quads) {
+      QuadRaw r;
+      quad_load(r, dp1, code1, y1, b, tq < 0 ? 0 : tq, L1, P1, c4);
+      quad_dz_xhat(r, tq, L1, P1, bn_mean, bn_inv, dz, xh);
+    } else {                                  // L1 % 4 != 0: position by position through the routed loads
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int t = tq + j, tc = t < 0 ? 0 : (t > L1 - 1 ? L1 - 1 : t);
+        const RoutedRaw rr = routed_load<16>(dp1, code1, b, tc, P1, c4);
+        const float4 yv = *(const float4*)(y1 + ((size_t)b * L1 + tc) * 16 + c4 * 4);
+        dz[j] = routed_dz(rr, tc, P1);
+        xh[j] = make_float4((yv.x - bn_mean[0]) * bn_inv[0], (yv.y - bn_mean[1]) * bn_inv[1], (yv.z - bn_mean[2]) * bn_inv[2],
+                            (yv.w - bn_mean[3]) * bn_inv[3]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = tq + j;
+      float4 v = make_float4(bn_sc[0] * (dz[j].x - bn_c1[0] - xh[j].x * bn_c2[0]), bn_sc[1] * (dz[j].y - bn_c1[1] - xh[j].y * bn_c2[1]),
+                             bn_sc[2] * (dz[j].z - bn_c1[2] - xh[j].z * bn_c2[2]), bn_sc[3] * (dz[j].w - bn_c1[3] - xh[j].w * bn_c2[3]));
+      if (t < 0 || t >= L1) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      *(float4*)&dys[(4 * q + j) * DX_PS + c4 * 4] = v;
+    }
+  }
+  __syncthreads();
+  const int u = u0 + tid;
+  if (u >= L1) return;
+  // channel by channel, eight dy1 channels o per loop iteration: its 56 weights are scalar operands (all 112 of a channel, or every
+  // channel's at once, overflow the SGPRs and spill)
+  const float* row = &dys[(tid + 3) * DX_PS];              // t' = u - 1
+  float* dxb = dx + (size_t)b * C * T;
+  const int t = 2 * u;
+#pragma unroll 1
+  for (int c = 0; c < C; ++c) {
+    float ae = 0.f, ao = 0.f;
+#pragma unroll 2
+    for (int q = 0; q < 4; ++q) {                          // o = 4 q .. 4 q + 3
+      const float4 m1 = *(const float4*)(row + 4 * q), z0 = *(const float4*)(row + DX_PS + 4 * q),
+                   p1 = *(const float4*)(row + 2 * DX_PS + 4 * q), p2 = *(const float4*)(row + 3 * DX_PS + 4 * q);
+      const float vm1[4] = {m1.x, m1.y, m1.z, m1.w}, v0[4] = {z0.x, z0.y, z0.z, z0.w}, vp1[4] = {p1.x, p1.y, p1.z, p1.w},
+                  vp2[4] = {p2.x, p2.y, p2.z, p2.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float* wr = w1 + ((4 * q + e) * C + c) * 7;
+        ae = fmaf(wr[5], vm1[e], fmaf(wr[3], v0[e], fmaf(wr[1], vp1[e], ae)));
+        ao = fmaf(wr[6], vm1[e], fmaf(wr[4], v0[e], fmaf(wr[2], vp1[e], fmaf(wr[0], vp2[e], ao))));
+      }
+    }
+    const float ev = fmaf(s_s[c], ae, s_dm[c]), od = fmaf(s_s[c], ao, s_dm[c]);
+    if ((T & 1) == 0) {
+      *(float2*)(dxb + (size_t)c * T + t) = make_float2(ev, od);          // T even: 2u + 1 < T for every u < L1 = T / 2
+    } else {
+      dxb[(size_t)c * T + t] = ev;
+      if (t + 1 < T) dxb[(size_t)c * T + t + 1] = od;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // Gate MLP backward (tiny): one workgroup per output weight, block-reduced over the batch
 //   dz2[b,c] = ds[b,c] s(1-s);  dW2[c][j] = sum_b dz2[b,c] relu(a1[b,j])
 //   da1[b,j] = (a1>0) sum_c W2[c][j] dz2[b,c];  dW1[j][c] = sum_b da1[b,j] mean[b,c]
@@ -1162,7 +1304,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
   {
     MSIG_K("gate", st);
 #define GATE(CT) gate_kernel<CT><<<dim3(d.B, 1, fc.n), 256, 0, st>>>(b->x, P + po[MSIG_P_GATE_W1], P + po[MSIG_P_GATE_W2], mean, pre, gs, \
-                                                           b->training ? w.p<float>(MSIG_WS_GATE_EO) : nullptr, d.C, d.T, d.Cr, fc)
+                                                           msig_keeps(b) ? w.p<float>(MSIG_WS_GATE_EO) : nullptr, d.C, d.T, d.Cr, fc)
     switch (d.C) {
       case 1: GATE(1); break; case 2: GATE(2); break; case 3: GATE(3); break; case 4: GATE(4); break;
       case 5: GATE(5); break; case 6: GATE(6); break; case 7: GATE(7); break; case 8: GATE(8); break;
@@ -1171,7 +1313,8 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
 #undef GATE
   }
   MSIG_LAUNCH_CHECK();
-  const int tr = b->training;
+  const int tr = b->training;                // batch statistics and the running-statistic update
+  const bool keep = msig_keeps(b);            // the pooling decisions the backward routes through (training, or an eval forward kept for one)
   // ---- stage 1
   {
     const int nchunk = (d.L1 + C1_CHUNK - 1) / C1_CHUNK;
@@ -1201,7 +1344,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     const int nchunk = (d.L2 + C2_CHUNK - 1) / C2_CHUNK;
     const int grid = clampi((int64_t)d.B * nchunk, MSIG_PERSIST_WG);
     { MSIG_K("pool1_conv2_fwd", st); pool1_conv2_fwd_kernel<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_Y1), w.p<float>(MSIG_WS_BN1_STAT), w.p<float>(MSIG_WS_P1),
-                                            tr ? w.p<uint8_t>(MSIG_WS_POOLC1) : nullptr, P + po[MSIG_P_CONV2_W], w.p<float>(MSIG_WS_Y2),
+                                            keep ? w.p<uint8_t>(MSIG_WS_POOLC1) : nullptr, P + po[MSIG_P_CONV2_W], w.p<float>(MSIG_WS_Y2),
                                             w.p<float>(MSIG_WS_BN2_PART), d.B, d.L1, d.P1, d.L2, tr, fc); }
     MSIG_LAUNCH_CHECK();
     { MSIG_K("bn_finalize", st); bn_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(w.p<float>(MSIG_WS_BN2_PART), grid, 32, (double)d.B * d.L2, P + po[MSIG_P_BN2_G],
@@ -1210,7 +1353,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     MSIG_LAUNCH_CHECK();
     const int64_t n = (int64_t)d.B * d.TP * 8;
     { MSIG_K("bn_relu_pool_32", st); bn_relu_pool_kernel<32><<<dim3(clampi((n + 255) / 256, 8192), 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_Y2), w.p<float>(MSIG_WS_BN2_STAT),
-                                                                          w.p<float>(MSIG_WS_P2), tr ? w.p<uint8_t>(MSIG_WS_POOLC2) : nullptr, d.B, d.L2, d.TP, fc); }
+                                                                          w.p<float>(MSIG_WS_P2), keep ? w.p<uint8_t>(MSIG_WS_POOLC2) : nullptr, d.B, d.L2, d.TP, fc); }
     MSIG_LAUNCH_CHECK();
   }
   return 0;
@@ -1232,7 +1375,7 @@ int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     { MSIG_K("pool_bn_bwd_pass1_32", st); pool_bn_bwd_pass1<32><<<dim3(grid, 1, fc.n), 256, 0, st>>>(dxa, dxb, w.p<uint8_t>(MSIG_WS_POOLC2), w.p<float>(MSIG_WS_Y2),
                                                 w.p<float>(MSIG_WS_BN2_STAT), w.p<float>(MSIG_WS_DY2), bpart, d.B, d.L2, d.TP, fc); }
     MSIG_LAUNCH_CHECK();
-    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 32, (double)d.B * d.L2, cstat, G + po[MSIG_P_BN2_G], G + po[MSIG_P_BN2_B], fc); }
+    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 32, (double)d.B * d.L2, cstat, G + po[MSIG_P_BN2_G], G + po[MSIG_P_BN2_B], b->training, fc); }
     MSIG_LAUNCH_CHECK();
     // (pass 2 of this stage is fused into the staging of conv2_bwd: WS_DY2 keeps dL/d(bn2 output))
   }
@@ -1266,12 +1409,19 @@ int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
 #undef C1B
     }
     MSIG_LAUNCH_CHECK();
-    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 16, (double)d.B * d.L1, cstat, G + po[MSIG_P_BN1_G], G + po[MSIG_P_BN1_B], fc); }
+    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 16, (double)d.B * d.L1, cstat, G + po[MSIG_P_BN1_G], G + po[MSIG_P_BN1_B], b->training, fc); }
     MSIG_LAUNCH_CHECK();
     { MSIG_K("conv1_bwd_fin", st); conv1_bwd_fin_kernel<<<dim3(grid_fin, 1, fc.n), 256, 0, st>>>(g1w, w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], w.p<float>(MSIG_WS_GATE_S),
                                                                                          w.p<float>(MSIG_WS_GATE_EO), b->x, part1, w.p<float>(MSIG_WS_DS), d.B, d.C, d.T, d.L1, seg, fc); }
     MSIG_LAUNCH_CHECK();
     if (!plan.add(part1, grid_fin, 16 * K, 0, 16 * K, G + po[MSIG_P_CONV1_W])) return MSIG_E_SHAPE;
+    if (b->dx) {          // dL/dx: after conv1_bwd_fin (it reads ds), a launch of its own
+      const int nchunk_dx = (d.L1 + DX_UCH - 1) / DX_UCH;
+      { MSIG_K("conv1_bwd_dx", st); conv1_bwd_dx_kernel<<<dim3(d.B * nchunk_dx, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_DP1), w.p<uint8_t>(MSIG_WS_POOLC1),
+          w.p<float>(MSIG_WS_Y1), w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], w.p<float>(MSIG_WS_GATE_S), w.p<float>(MSIG_WS_GATE_PRE),
+          P + po[MSIG_P_GATE_W1], P + po[MSIG_P_GATE_W2], w.p<float>(MSIG_WS_DS), b->dx, d.C, d.Cr, d.T, d.L1, d.P1, fc); }
+      MSIG_LAUNCH_CHECK();
+    }
     if (d.Cr > 0) {
       { MSIG_K("gate_bwd", st); gate_bwd_kernel<<<dim3(2 * d.C * d.Cr, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_DS), w.p<float>(MSIG_WS_GATE_S), w.p<float>(MSIG_WS_GATE_PRE),
                                                         w.p<float>(MSIG_WS_GATE_MEAN), P + po[MSIG_P_GATE_W2], G + po[MSIG_P_GATE_W1],

@@ -12,7 +12,7 @@
 //     lane (li,lq), k-step m  <->  W[row = gate*64 + w*16 + li][col = lq*(Kdim/4) + m].
 //
 //   gru_fwd_seq<I>  input projection fused with the recurrence (no gi tensor in HBM);
-//                   writes h_t, and in training the gate stash (r,z,n,W_hn h+b_hn).
+//                   writes h_t, and in training (or an eval forward kept for a backward) the gate stash (r,z,n,W_hn h+b_hn).
 //   gru_bwd_seq4    BPTT recurrence: dh_{t-1} = dh_t*z + W_hh^T dgh_t (gru_bwd4.hip); overwrites the
 //                   stash in place with (dr_pre, dz_pre, dn_pre, dhn_pre).
 //   gru_bwd_dx<I>   dx_t = W_ih^T dgi_t  (bulk over all (row, t)).
@@ -1787,7 +1787,7 @@ static void setup_layer0(GruArgs& a, const msig_batch* b, const StageDims& d, co
     g.t_start = dir ? d.TP - 1 : 0; g.t_sign = dir ? -1 : 1; g.n_steps = d.TP;
     g.h = w.p<float>(MSIG_WS_H0); g.h_bs = (int64_t)d.TP * 128; g.h_ts = 128; g.h_col = dir * 64;
     g.h_last = nullptr; g.hl_bs = 0; g.hl_col = 0;
-    g.stash = b->training ? w.p<float4>(MSIG_WS_STASH0) + dir * stash_dir : nullptr;
+    g.stash = msig_keeps(b) ? w.p<float4>(MSIG_WS_STASH0) + dir * stash_dir : nullptr;
   }
 }
 
@@ -1802,7 +1802,7 @@ static void setup_layer1(GruArgs& a, const msig_batch* b, const StageDims& d, co
     g.t_start = 0; g.t_sign = 1; g.n_steps = d.TP;
     g.h = w.p<float>(MSIG_WS_H1); g.h_bs = (int64_t)d.TP * 64; g.h_ts = 64; g.h_col = 0;
     g.h_last = w.p<float>(MSIG_WS_FEAT); g.hl_bs = 128; g.hl_col = 0;
-    g.stash = b->training ? w.p<float4>(MSIG_WS_STASH1) : nullptr;
+    g.stash = msig_keeps(b) ? w.p<float4>(MSIG_WS_STASH1) : nullptr;
   }
   {  // reverse direction: only its first step (t = T'-1) reaches outputs[:, -1, :]
     GruDir& g = a.dir[1];
@@ -1810,7 +1810,7 @@ static void setup_layer1(GruArgs& a, const msig_batch* b, const StageDims& d, co
     g.t_start = d.TP - 1; g.t_sign = -1; g.n_steps = 1;
     g.h = w.p<float>(MSIG_WS_FEAT); g.h_bs = 128; g.h_ts = 0; g.h_col = 64;
     g.h_last = nullptr; g.hl_bs = 0; g.hl_col = 0;
-    g.stash = b->training ? w.p<float4>(MSIG_WS_STASH1R) : nullptr;
+    g.stash = msig_keeps(b) ? w.p<float4>(MSIG_WS_STASH1R) : nullptr;
   }
 }
 
@@ -1984,23 +1984,23 @@ int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
     { MSIG_K("gru_fwd_proj_l0", st); gru_fwd_proj<32><<<dim3(bulk_grid(units, 256, fc.n, 2), 2, fc.n), 256, 0, st>>>(a, d.NT, fc); }
     MSIG_LAUNCH_CHECK();
     MSIG_K("gru_fwd_rec_l0", st);
-    if (b->training) gru_fwd_rec<true><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
+    if (msig_keeps(b)) gru_fwd_rec<true><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
     else gru_fwd_rec<false><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
   } else if (fp32) {
     MSIG_K("gru_fwd_seq_l0", st);
-    if (b->training) gru_fwd_seq<32, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
+    if (msig_keeps(b)) gru_fwd_seq<32, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
     else gru_fwd_seq<32, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
   } else if (ws0 && folds) {
     MSIG_K("gru_fwd_ws_l0", st);
-    if (b->training) gru_fwd_ws<32, true, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
+    if (msig_keeps(b)) gru_fwd_ws<32, true, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
     else gru_fwd_ws<32, false, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
   } else if (ws0 && MSIG_WS_LAYER0) {
     MSIG_K("gru_fwd_ws_l0", st);
-    if (b->training) gru_fwd_ws<32, true, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
+    if (msig_keeps(b)) gru_fwd_ws<32, true, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
     else gru_fwd_ws<32, false, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
   } else {
     MSIG_K("gru_fwd_b3_l0", st);
-    if (b->training) gru_fwd_b3<32, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
+    if (msig_keeps(b)) gru_fwd_b3<32, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
     else gru_fwd_b3<32, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
   }
   MSIG_LAUNCH_CHECK();
@@ -2029,24 +2029,24 @@ int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
     MSIG_LAUNCH_CHECK();
     {
       MSIG_K("gru_fwd_rec_l1", st);
-      if (b->training) gru_fwd_rec<true><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
+      if (msig_keeps(b)) gru_fwd_rec<true><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
       else gru_fwd_rec<false><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
     }
   } else if (fp32) {
     MSIG_K("gru_fwd_seq_l1", st);
-    if (b->training) gru_fwd_seq<128, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
+    if (msig_keeps(b)) gru_fwd_seq<128, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
     else gru_fwd_seq<128, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
   } else if (ws1 && folds) {
     MSIG_K("gru_fwd_ws_l1", st);
-    if (b->training) gru_fwd_ws<128, true, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
+    if (msig_keeps(b)) gru_fwd_ws<128, true, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
     else gru_fwd_ws<128, false, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
   } else if (ws1) {
     MSIG_K("gru_fwd_ws_l1", st);
-    if (b->training) gru_fwd_ws<128, true, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
+    if (msig_keeps(b)) gru_fwd_ws<128, true, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
     else gru_fwd_ws<128, false, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
   } else {
     MSIG_K("gru_fwd_b3_l1", st);
-    if (b->training) gru_fwd_b3<128, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
+    if (msig_keeps(b)) gru_fwd_b3<128, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
     else gru_fwd_b3<128, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
   }
   MSIG_LAUNCH_CHECK();

@@ -667,7 +667,7 @@ int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, co
   if (b->labels) {
     MSIG_K("ce", st);
     ce_kernel<<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                 b->training ? w.p<float>(MSIG_WS_DLOGITS) : nullptr, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K, fc);
+                                 msig_keeps(b) ? w.p<float>(MSIG_WS_DLOGITS) : nullptr, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K, fc);
   } else {
     MSIG_K("softmax", st);
     softmax_kernel<<<dim3((d.B + 255) / 256, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED), d.B, d.K, fc);

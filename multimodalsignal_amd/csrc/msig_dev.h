@@ -233,6 +233,11 @@ struct FoldCtx {
 __device__ __forceinline__ const void* msig_fold_addr(const void* p, int64_t off) { return p ? (const void*)((const char*)p + off) : p; }
 #define FOLD_BEGIN const int64_t foff_ = (int64_t)fc.slot[blockIdx.z] * fc.stride
 #define FS(p) p = (decltype(p))msig_fold_addr((const void*)(p), foff_)
+// The forward keeps what a backward reads (pooling decisions, the gate's parity sums, GRU stashes, dL/dlogits of a call with labels):
+// in training, and in an eval-mode forward that asked for it (msig_batch.keep_for_backward, ABI 5).  Batch statistics, the running-
+// statistic update and dropout stay with `training` alone.
+inline bool msig_keeps(const msig_batch* b) { return b->training || b->keep_for_backward; }
+
 inline FoldCtx single_fold(const msig_batch* b) {
   FoldCtx fc{};
   fc.n = 1; fc.stride = 0; fc.form_folds = 1;

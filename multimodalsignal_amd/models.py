@@ -16,6 +16,7 @@ import math
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 from .runtime import EmbeddedEngine, Engine
@@ -83,31 +84,40 @@ class _GruParams(nn.Module):
 
 
 class _MsigFunction(torch.autograd.Function):
-    """model(inputs) with autograd: forward = msig_forward, backward = msig_backward."""
+    """model(inputs) with autograd: forward = msig_forward, backward = msig_backward (input gradient through msig_batch.dx).  An
+    eval-mode forward keeps what the backward reads (msig_batch.keep_for_backward) only when autograd may ask for it: grad mode on
+    and the input or a parameter requiring grad.  Its logits are the same bits either way."""
 
     @staticmethod
-    def forward(ctx, model, x, *params):
+    def forward(ctx, model, keep, x, *params):
         eng = model._engine
         training = model.training
         step = model._bump_step() if training else 0
-        b = eng.forward(x, None, training=training, dropout_p=model.dropout_p, seed=model._seed, step=step)
-        ctx.model, ctx.batch, ctx.token, ctx.training = model, b, model._bump_token(), training
+        keep = bool(keep) and not training
+        b = eng.forward(x, None, training=training, dropout_p=model.dropout_p, seed=model._seed, step=step, keep_for_backward=keep)
+        ctx.model, ctx.batch, ctx.token, ctx.training, ctx.kept = model, b, model._bump_token(), training, training or keep
         return eng.region("LOGITS", torch.float32, (x.shape[0], model.num_classes)).clone()
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dlogits):
         model = ctx.model
-        if not ctx.training:
-            raise RuntimeError("backward through a model.eval() forward is not supported (no stash is kept)")
+        if not ctx.kept:
+            raise RuntimeError("backward through a model.eval() forward that kept nothing for it: it ran with autograd disabled or "
+                               "with neither the input nor any parameter requiring grad")
         if ctx.token != model._token:
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the same model")
         eng = model._engine
-        eng.backward(ctx.batch, dlogits)
+        dx = None
+        if ctx.needs_input_grad[2]:
+            B, T = ctx.batch.shape.B, ctx.batch.shape.T
+            dx = torch.empty((B, model.in_channels, T), dtype=torch.float32, device=dlogits.device)
+        eng.backward(ctx.batch, dlogits, dx=dx)
         if model.embedded:
             grads = [g.clone() for g in eng.gather_grads().values()]
         else:
             grads = [eng.param_view(i, eng.grads).clone() for i in range(L.NPARAM)]
-        return (None, None, *grads)
+        return (None, None, dx, *grads)
 
 
 class CnnGruAttentionModel(nn.Module):
@@ -197,4 +207,9 @@ class CnnGruAttentionModel(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("CnnGruAttentionModel.forward needs a GPU tensor: the MI355X path has no CPU fallback")
         self.engine()
-        return _MsigFunction.apply(self, x, *self._named())
+        params = self._named()
+        # an eval-mode forward keeps what a backward reads only when autograd may ask for one (decided here: inside
+        # Function.forward grad mode is always off)
+        keep = (not self.training and torch.is_grad_enabled()
+                and (x.requires_grad or any(p.requires_grad for p in params)))
+        return _MsigFunction.apply(self, keep, x, *params)

@@ -56,9 +56,9 @@ class Engine:
         self.bn_state[16:32] = 1.0
         self.bn_state[64:96] = 1.0
         self.gru_layers = 2                     # msig_batch.gru_layers: EmbeddedEngine (the one-layer, 32-unit model) sets 1
-        self._ws: Dict[Tuple[int, int, bool], Tuple[torch.Tensor, list]] = {}
-        self._ws_pool: Dict[bool, torch.Tensor] = {}
-        self._last: Optional[Tuple[int, int, bool]] = None
+        self._ws: Dict[Tuple[int, int, object], Tuple[torch.Tensor, list]] = {}
+        self._ws_pool: Dict[object, torch.Tensor] = {}
+        self._last: Optional[Tuple[int, int, object]] = None
         self._keep = None
 
     # ---- views -----------------------------------------------------------------
@@ -92,10 +92,18 @@ class Engine:
             dst.copy_(torch.as_tensor(v).to(dst.dtype).reshape(dst.shape))
 
     # ---- workspace ---------------------------------------------------------------
-    def workspace(self, B: int, T: int, training: bool):
-        key = (B, T, bool(training))
+    EVAL_KEEP = "eval+keep"       # workspace mode of an eval forward kept for a backward (msig_batch.keep_for_backward)
+
+    @classmethod
+    def _mode(cls, training: bool, keep_for_backward: bool = False):
+        """Workspace mode: True (training), False (evaluation) or EVAL_KEEP (evaluation kept for a backward: the training layout)."""
+        return bool(training) or (cls.EVAL_KEEP if keep_for_backward else False)
+
+    def workspace(self, B: int, T: int, training: bool, keep_for_backward: bool = False):
+        mode = self._mode(training, keep_for_backward)
+        key = (B, T, mode)
         if key not in self._ws:
-            off = L.workspace_layout(B, self.C, T, self.K, training)
+            off = L.workspace_layout(B, self.C, T, self.K, mode is not False)
             if self._ws_region is not None:          # arena mode: every shape shares the arena's one workspace region
                 if off[-1] > self._ws_region.numel():
                     raise RuntimeError(f"fold arena workspace too small for B={B}, T={T}")
@@ -104,16 +112,17 @@ class Engine:
                 # One allocation per mode, sized for the largest shape seen: the ragged last batch of an epoch lays its regions
                 # out in the full batch's buffer instead of allocating a second one (13.6 GB each at B = 8192).  Training and
                 # evaluation keep separate buffers — an evaluation between a training forward and its backward (autograd path)
-                # must not overwrite the stash.  Growing frees the smaller buffer: layouts cached for it are dropped, and a
-                # HIP graph captured on it must be re-captured (a graph holds raw pointers).
-                pool = self._ws_pool.get(bool(training))
+                # must not overwrite the stash — and so does an evaluation kept for a backward (a third buffer, neither a pending
+                # training forward's nor a plain evaluation's).  Growing frees the smaller buffer: layouts cached for it are dropped,
+                # and a HIP graph captured on it must be re-captured (a graph holds raw pointers).
+                pool = self._ws_pool.get(mode)
                 if pool is None or pool.numel() < off[-1]:
-                    for k in [k for k in self._ws if k[2] == bool(training)]:
+                    for k in [k for k in self._ws if k[2] == mode]:
                         del self._ws[k]
-                    if self._last is not None and self._last[2] == bool(training):
+                    if self._last is not None and self._last[2] == mode:
                         self._last, self._keep = None, None      # region() must not resolve to a purged layout
                     pool = None
-                    self._ws_pool[bool(training)] = pool = torch.empty(off[-1], dtype=torch.uint8, device=self.device)
+                    self._ws_pool[mode] = pool = torch.empty(off[-1], dtype=torch.uint8, device=self.device)
                 buf = pool[:off[-1]]
             lo = off[L.WS["LOSS"]]
             buf[lo:lo + 16].zero_()
@@ -140,7 +149,7 @@ class Engine:
 
     # ---- descriptor ----------------------------------------------------------------
     def _batch(self, x: torch.Tensor, labels: Optional[torch.Tensor], training: bool, dropout_p: float,
-               seed: int, step: int) -> L.Batch:
+               seed: int, step: int, keep_for_backward: bool = False) -> L.Batch:
         _require_gpu(x, "input batch")
         if x.dtype != torch.float32 or x.dim() != 3 or x.shape[1] != self.C:
             raise ValueError(f"expected float32 (B,{self.C},T) input, got {x.dtype} {tuple(x.shape)}")
@@ -149,11 +158,13 @@ class Engine:
         if labels is not None:
             _require_gpu(labels, "labels")
             labels = labels.to(torch.int64).contiguous()
-        buf, off = self.workspace(B, T, training)
+        keep = bool(keep_for_backward) and not training
+        buf, off = self.workspace(B, T, training, keep)
         thr = L.dropout_threshold(dropout_p) if training else 0
         b = L.Batch()
         b.shape = L.Shape(B, self.C, T, self.K)
         b.training = int(training)
+        b.keep_for_backward = int(keep)
         b.bn_momentum, b.bn_eps = 0.1, 1e-5
         b.dropout_thr = thr
         b.key_gru = L.dropout_key(seed, step, 1) if thr else 0
@@ -169,7 +180,7 @@ class Engine:
         b.gru_layers = self.gru_layers
         b.loss_acc = self.loss_acc.data_ptr()
         L.apply_forms(b)
-        self._last = (B, T, bool(training))
+        self._last = (B, T, self._mode(training, keep))
         self._keep = (x, labels)
         return b
 
@@ -177,19 +188,28 @@ class Engine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- calls -------------------------------------------------------------------------
-    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0) -> L.Batch:
+    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False) -> L.Batch:
         """model(inputs) [+ criterion]: logits land in region('LOGITS'); returns the descriptor
-        that a following backward() must be given."""
-        b = self._batch(x, labels, training, dropout_p, seed, step)
+        that a following backward() must be given.  An eval-mode forward (training=False) takes a backward only with
+        keep_for_backward=True: it then keeps the stashes in a workspace of its own, with the same logits."""
+        b = self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward)
         L.check(L.lib().msig_forward(C.byref(b), self._stream()), "msig_forward")
         return b
 
-    def backward(self, b: L.Batch, dlogits: Optional[torch.Tensor] = None):
+    def backward(self, b: L.Batch, dlogits: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None):
+        """loss.backward() of the forward that returned `b`: parameter gradients into `grads`; with `dx` — a contiguous float32
+        (B, C, T) tensor on this device — also dL/dx (msig_batch.dx)."""
         ptr = None
         if dlogits is not None:
             _require_gpu(dlogits, "dlogits")
             dlogits = dlogits.to(torch.float32).contiguous()
             ptr = dlogits.data_ptr()
+        if dx is not None:
+            _require_gpu(dx, "dx")
+            if dx.dtype != torch.float32 or not dx.is_contiguous() or tuple(dx.shape) != (b.shape.B, self.C, b.shape.T):
+                raise ValueError(f"dx must be a contiguous float32 ({b.shape.B}, {self.C}, {b.shape.T}) tensor, got {dx.dtype} {tuple(dx.shape)}")
+            b = L.Batch.from_buffer_copy(b)          # the caller's descriptor stays as its forward left it
+            b.dx = dx.data_ptr()
         L.check(L.lib().msig_backward(C.byref(b), ptr, self._stream()), "msig_backward")
 
     def ensure_adam_state(self):
@@ -290,9 +310,9 @@ class EmbeddedEngine(Engine):
         return self.small_views(self.small_grads)
 
     # ---- the library calls, with the embedding maintained around them ----
-    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0):
+    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False):
         self.scatter()
-        return super().forward(x, labels, training, dropout_p, seed, step)
+        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward)
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0):
         self.scatter()
