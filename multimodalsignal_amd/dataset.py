@@ -165,6 +165,31 @@ class SubjectStore:
         self.labels_host = torch.cat(ys).numpy()
         self.y = torch.from_numpy(self.labels_host).to(self.device)
 
+    @classmethod
+    def from_wesad(cls, data_path: Path, subjects: list, channels_to_use: list, all_channel_names: list,
+                   classification_mode="stress_binary", device="cuda", cache: Optional[dict] = None) -> "SubjectStore":
+        """A store of any classification mode, amusement_binary included, built from WesadDataset's per-subject arrays (its
+        `cache` shared): every window is the float64 -> fp32 cast of WesadDataset.device_tensors, so a StoreView of it feeds the
+        same bits as a WesadDataset of those subjects.  A subject with no window of the mode keeps an empty range."""
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+        xs, ys, self.ranges, start = [], [], {}, 0
+        for sid in subjects:
+            if not ((Path(data_path) / f"{sid}_X.npy").exists() and (Path(data_path) / f"{sid}_y.npy").exists()):
+                print(f"Warning: Skipping subject {sid} for data, file not found.")
+                continue
+            ds = WesadDataset(data_path, [sid], channels_to_use, all_channel_names, classification_mode=classification_mode, cache=cache)
+            xs.append(torch.from_numpy(np.ascontiguousarray(ds.data.transpose(0, 2, 1), dtype=np.float32)))
+            ys.append(torch.from_numpy(ds.labels.astype(np.int64)))
+            self.ranges[sid] = (start, start + len(ds))
+            start += len(ds)
+        if not xs:
+            raise ValueError(f"No data loaded for subjects: {subjects}. Check paths and data existence.")
+        self.x = torch.cat(xs, dim=0).contiguous().to(self.device)
+        self.labels_host = torch.cat(ys).numpy()
+        self.y = torch.from_numpy(self.labels_host).to(self.device)
+        return self
+
     def view(self, subjects: list) -> "StoreView":
         return StoreView(self, subjects)
 

@@ -25,6 +25,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from . import _lib as L
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel
@@ -61,6 +62,19 @@ EVAL_BATCH_SIZE = 1024
 # training at once: four fold batches per configuration (+ a side stream for finished folds' short test passes), one per configuration
 # in a sweep, and at most four single-fold streams with --no-lockstep (round 4 ran fifteen there).
 MAX_TRAIN_STREAMS = 4
+
+
+def cap_waves(waves, cap=MAX_TRAIN_STREAMS):
+    """Splits every wave (a list of fold batches that run concurrently, one stream each) into waves of at most `cap` fold batches,
+    in order: what does not fit spills into the next wave."""
+    return [wv[i:i + cap] for wv in waves for i in range(0, len(wv), cap)]
+
+
+def chunk_schedule(chunk_preps):
+    """(epoch budget, smallest patience) of a fold batch, from its own folds' trainer configurations (prepare_fold): a sweep's
+    configurations need not share cfg0's.  The folds of one batch share one budget (LockstepTrainer checks it)."""
+    tcs = [p["config"]["trainer"] for p in chunk_preps]
+    return max(int(t["epochs"]) for t in tcs), min(int(t["early_stopping"]["patience"]) for t in tcs)
 
 
 def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
@@ -211,11 +225,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
             # A sweep (channel ablation: 4 configurations x 15 folds): the configurations' fold batches run CONCURRENTLY, one
             # stream each, at most MAX_TRAIN_STREAMS at a time — round 4 ran them as sequential waves of three streams, each wave
             # ending in a multi-second tail with one or two folds left on an otherwise idle GPU.
-            for c0 in range(0, len(glist), MAX_TRAIN_STREAMS):
-                wave = []
-                for g in glist[c0:c0 + MAX_TRAIN_STREAMS]:
-                    wave += [g[i:i + 16] for i in range(0, len(g), 16)]
-                waves.append(wave)
+            waves.append([g[i:i + 16] for g in glist for i in range(0, len(g), 16)])
         else:
             for g in glist:
                 for w0 in range(0, len(g), conc):
@@ -223,6 +233,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
                     k = min(ng, max(1, len(gw) // 2), MAX_TRAIN_STREAMS)
                     parts = [gw[i::k] for i in range(k)]
                     waves.append([part[i:i + 16] for part in parts for i in range(0, len(part), 16)])
+        waves = cap_waves(waves)                         # never more than MAX_TRAIN_STREAMS training streams at once
         chunk_preps = [[[(u, preps[u]) for u in ch] for ch in wv] for wv in waves]
         if all(lockstep_compatible([p for _, p in ch]) for wv in chunk_preps for ch in wv):
             torch.cuda.synchronize(device)
@@ -237,17 +248,22 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
                     streams[pos_] = torch.cuda.Stream(device)
                 with torch.cuda.stream(streams[pos_]):
                     lt = LockstepTrainer([p for _, p in ch], device, adaptive_forms=adaptive)
-                    done, alive = lt.run(epoch0=epoch0, max_epochs=n_ep, t_start=t_lock0)
+                    if n_ep > 0:
+                        done, alive = lt.run(epoch0=epoch0, max_epochs=n_ep, t_start=t_lock0)
+                    else:                                  # a budget of 0 epochs: every fold goes straight to its test pass
+                        done, alive = dict(enumerate(lt.run(t_start=t_lock0))), []
                     torch.cuda.current_stream(device).synchronize()
                 return ch, done, alive, lt
 
             from concurrent.futures import ThreadPoolExecutor
 
             def run_round(chunks, epoch0, n_ep):
-                """One round: every chunk (fold batch) trains epochs epoch0 .. epoch0 + n_ep - 1 on its own stream.  Returns the units
-                still training (with their preps, which now carry their Trainer) — and keeps the finished batches' arenas alive
-                until the survivors have been re-dealt (their state is copied out of them)."""
-                jobs = [(ch, epoch0, n_ep, i) for i, ch in enumerate(chunks)]
+                """One round: every chunk (fold batch) trains epochs epoch0 .. epoch0 + n_ep - 1 on its own stream (`n_ep` one
+                count for all chunks, or one per chunk).  Returns the units still training (with their preps, which now carry their
+                Trainer) — and keeps the finished batches' arenas alive until the survivors have been re-dealt (their state is
+                copied out of them)."""
+                n_eps = list(n_ep) if isinstance(n_ep, (list, tuple)) else [n_ep] * len(chunks)
+                jobs = [(ch, epoch0, n_eps[i], i) for i, ch in enumerate(chunks)]
                 if len(jobs) == 1:
                     res = [work(jobs[0])]
                 else:
@@ -260,9 +276,6 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
                     alive_units += [ch[pos] for pos in alive]
                 return sorted(alive_units, key=lambda up: up[0]), res
 
-            budget = int(cfg0["epochs"])
-            pats = cfg0["patience"] if isinstance(cfg0["patience"], (list, tuple)) else [cfg0["patience"]]
-            first_round = min(int(p_) for p_ in pats) + 1            # no fold can stop before patience + 1 epochs
             # Re-dealing the surviving folds evenly over the fold batches between rounds — after the first patience + 1 epochs (0) or every n
             # epochs (n) — is BUILT AND OFF (-1, the default): measured on the bench's LOSO (same 558 fold-epochs, same box, profiles/
             # r05_loso_redeal.log) never: 7.30 / 7.23 s, once: 7.41 / 7.37 s, every 16 / 8 epochs: 7.47 / 7.5-7.7 s.  The run is bound by its
@@ -270,9 +283,13 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
             # round boundaries (the batches wait for each other, arenas are rebuilt) cost more than the balance returns.
             redeal = int(cfg0.get("redeal_every", -1))
             for wv in chunk_preps:
+                sched = [chunk_schedule([p for _, p in ch]) for ch in wv]     # each fold batch's budget from its own trainers
                 if redeal < 0 or len(names) > 1:
-                    run_round(wv, 0, budget)                          # sweeps: one fold batch per configuration, run to the end
+                    alive_units, _ = run_round(wv, 0, [b_ for b_, _ in sched])   # sweeps: one fold batch per configuration, run to the end
+                    assert not alive_units, "a fold batch ended its epoch budget with folds still training"
                     continue
+                budget = max(b_ for b_, _ in sched)
+                first_round = min(p_ for _, p_ in sched) + 1              # no fold can stop before patience + 1 epochs
                 # Rounds.  Early stopping thins the fold batches unevenly — the batch that happens to hold the long folds bounds
                 # the run (round 4 / first half of round 5: 6.67 s against 6.08 s for its neighbour) — so after the first
                 # patience + 1 epochs, and then every `redeal_every`, the folds still training are dealt evenly over the batches
@@ -358,13 +375,17 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
     three-class decision `2 if M1 says stress else M2's class` on the test subject.  The reference cannot run this function (its
     dataset.py raises for 'amusement_binary'): the label map is defined in dataset.map_labels, and the
     summary the reference stops short of (overall three-class accuracy / weighted F1, per-fold M1 accuracy) is written to
-    hierarchical_summary.txt.  Folds are dealt to the ranks like the simple experiment's; each fold's two models train one after
-    the other on the rank's GPU.  Returns (per-fold dicts in subject order, wall seconds)."""
+    hierarchical_summary.txt.  Folds are dealt to the ranks like the simple experiment's, so a fold's M1 and M2 stay on one rank.
+    By default the rank's work units — (fold, model) pairs — train as fold batches (multifold.LockstepTrainer): the M1s over the
+    stress_binary store, the M2s over the amusement_binary store, concurrently on their own streams; each fold's decision runs
+    once both its models have finished.  cfg["concurrent_folds"] = 1 (or lockstep False) trains each fold's two models one after
+    the other, as the reference does; both give the same bits.  Returns (per-fold dicts in subject order, wall seconds)."""
     from .trainer import accuracy_and_weighted_f1
     cfg = dict(cfg or default_cfg())
     m1_ch, m2_ch = list(cfg.get("m1_channels", M1_CHANNELS_TO_USE)), list(cfg.get("m2_channels", M2_CHANNELS_TO_USE))
     m1_par, m2_par = dict(cfg.get("m1_params", M1_MODEL_PARAMS)), dict(cfg.get("m2_params", M2_MODEL_PARAMS))
     subjects, t0, cache = list(cfg["subjects"]), time.time(), {}
+    models = (("m1", m1_ch, m1_par, "stress_binary"), ("m2", m2_ch, m2_par, "amusement_binary"))
 
     def tcfg_for(k):
         pat = cfg["patience"]
@@ -377,25 +398,10 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
     bs = cfg["batch_size"]
     ebs = int(cfg.get("eval_batch_size") or bs)              # validation / test passes (per-window results do not depend on it)
     local, rows = {}, {}
-    for k in folds_for_rank(len(subjects), world, rank):
-        sid = subjects[k]
-        fold_dir = Path(run_output_dir) / f"fold_test_on_{sid}"
-        fold_dir.mkdir(parents=True, exist_ok=True)
-        train_subjects, val_subjects = split_train_val(subjects, sid, cfg["seed"])
-        trainers = {}
-        for tag, ch, par, mode in (("m1", m1_ch, m1_par, "stress_binary"), ("m2", m2_ch, m2_par, "amusement_binary")):
-            torch.manual_seed(cfg["seed"] + 2 * k + (tag == "m2"))
-            tr_ds, va_ds = mk(train_subjects, ch, mode), mk(val_subjects, ch, mode)
-            if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
-                print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
-                break
-            model = CnnGruAttentionModel(in_channels=len(ch), num_classes=2, **par)
-            model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
-            t = Trainer(model, fold_dir / f"model_{tag}", tcfg_for(k))
-            t.train(DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device))
-            trainers[tag] = t
-        if len(trainers) < 2:
-            continue
+    mine = folds_for_rank(len(subjects), world, rank)
+
+    def decide(k, sid, fold_dir, trainers):
+        """M1's test pass and the three-class decision of fold k (main.py:203-247), once both its models have trained."""
         _, m1_acc, m1_f1 = trainers["m1"].evaluate(DeviceLoader(mk([sid], m1_ch, "stress_binary"), ebs, False, device), is_test=True)   # main.py:203-207
         eval_ch = list(dict.fromkeys(m1_ch + m2_ch))              # main.py:211 (a set there: the order is immaterial, the indices follow it)
         tern = mk([sid], eval_ch, "ternary")
@@ -414,6 +420,30 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
         (fold_dir / "fold_result.json").write_text(json.dumps(rows[k]))
         local[k] = (m1_acc, acc3)
         print(f"[rank {rank}] fold {k} ({sid}): M1 acc {m1_acc:.4f} | three-class acc {acc3:.4f} f1 {f13:.4f}", flush=True)
+
+    if int(cfg.get("concurrent_folds", 1)) > 1 and cfg.get("lockstep", True) and mine:
+        _hierarchical_fold_batches(cfg, mine, subjects, models, tcfg_for, Path(run_output_dir), device, all_channel_names, cache, decide)
+    else:
+        for k in mine:
+            sid = subjects[k]
+            fold_dir = Path(run_output_dir) / f"fold_test_on_{sid}"
+            fold_dir.mkdir(parents=True, exist_ok=True)
+            train_subjects, val_subjects = split_train_val(subjects, sid, cfg["seed"])
+            trainers = {}
+            for tag, ch, par, mode in models:
+                torch.manual_seed(cfg["seed"] + 2 * k + (tag == "m2"))
+                tr_ds, va_ds = mk(train_subjects, ch, mode), mk(val_subjects, ch, mode)
+                if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
+                    print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
+                    break
+                model = CnnGruAttentionModel(in_channels=len(ch), num_classes=2, **par)
+                model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
+                t = Trainer(model, fold_dir / f"model_{tag}", tcfg_for(k))
+                t.train(DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device))
+                trainers[tag] = t
+            if len(trainers) < 2:
+                continue
+            decide(k, sid, fold_dir, trainers)
     allm = gather_fold_metrics(local, len(subjects), world, cfg.get("gather_device", device))
     wall = time.time() - t0
     results = [dict(subject=subjects[k], m1_accuracy=allm[k][0], ternary_accuracy=allm[k][1]) for k in sorted(allm)]
@@ -429,6 +459,74 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
             f.write(f"\nwall-clock: {wall:.1f} s on {world} GPU(s)\n")
         print(f"分层分类汇总结果已保存至: {path}")
     return results, wall
+
+
+def _hierarchical_fold_batches(cfg, mine, subjects, models, tcfg_for, run_output_dir, device, all_channel_names, cache, decide):
+    """The hierarchical experiment's work units — (fold, model) pairs of this rank's folds — as fold batches.  Seeds, models,
+    loaders and trainer configurations are made in the sequential driver's order and with its values; the datasets are views of
+    one store per model (SubjectStore.from_wesad: the same windows, bit for bit).  The M1s of a wave form fold batches over the
+    stress_binary store, its M2s (the one-layer model: runtime.FoldArena's padded form) over the amusement_binary store — at most
+    MAX_FOLDS folds and `lockstep_groups` batches per model, all of a wave's batches concurrently, one stream each, never more than
+    MAX_TRAIN_STREAMS at once.  M2's training sets are smaller; folds of unequal size share launches as in the simple experiment.
+    The backward kernel form is pinned per fold (FoldArena.multi), so every fold's bits are those of its sequential run."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .multifold import LockstepTrainer, lockstep_compatible
+    bs = cfg["batch_size"]
+    ebs = int(cfg.get("eval_batch_size") or bs)
+    stores = {tag: SubjectStore.from_wesad(cfg["data_path"], subjects, ch, all_channel_names, mode, device, cache)
+              for tag, ch, _, mode in models}
+    units, fold_dirs = {}, {}                       # (k, tag) -> prep
+    for k in mine:                                  # sequential: seeding / initialisation order as in the sequential driver
+        sid = subjects[k]
+        fold_dir = fold_dirs[k] = run_output_dir / f"fold_test_on_{sid}"
+        fold_dir.mkdir(parents=True, exist_ok=True)
+        train_subjects, val_subjects = split_train_val(subjects, sid, cfg["seed"])
+        for tag, ch, par, mode in models:
+            torch.manual_seed(cfg["seed"] + 2 * k + (tag == "m2"))
+            tr_ds, va_ds = stores[tag].view(train_subjects), stores[tag].view(val_subjects)
+            if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
+                print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
+                break
+            model = CnnGruAttentionModel(in_channels=len(ch), num_classes=2, **par)
+            model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
+            loaders = (DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device),
+                       DeviceLoader(stores[tag].view([sid]), ebs, False, device))
+            # test_pass False: the fold's M1 test pass and three-class decision run in `decide`, as in the sequential driver
+            units[(k, tag)] = dict(fold=k, subject=sid, fold_dir=fold_dir / f"model_{tag}", loaders=loaders, model=model,
+                                   config=tcfg_for(k), test_pass=False)
+    conc = max(1, int(cfg.get("concurrent_folds", 15)))
+    ng = max(1, min(int(cfg.get("lockstep_groups", 4)), MAX_TRAIN_STREAMS // len(models)))
+    waves = []
+    for w0 in range(0, len(mine), conc):            # at most `concurrent_folds` folds (both their models) resident at a time
+        wave = []
+        for tag, *_ in models:
+            g = [u for u in units if u[0] in mine[w0:w0 + conc] and u[1] == tag]
+            k_ = min(ng, max(1, len(g) // 2))
+            wave += [part[i:i + L.MAX_FOLDS] for part in (g[j::k_] for j in range(k_)) for i in range(0, len(part), L.MAX_FOLDS) if part]
+        waves.append(wave)
+    waves = cap_waves(waves)
+    for wv in waves:
+        if not all(lockstep_compatible([units[u] for u in ch]) for ch in wv):
+            raise RuntimeError("hierarchical fold batch: folds of one model do not share a store / batch size")
+    adaptive = bool(cfg.get("adaptive_forms", False))
+    torch.cuda.synchronize(device)                  # uploads were issued on this thread's stream
+    t_start = time.time()
+
+    def work(ch):
+        torch.cuda.set_device(device)
+        with torch.cuda.stream(torch.cuda.Stream(device)):
+            lt = LockstepTrainer([units[u] for u in ch], device, adaptive_forms=adaptive)
+            lt.run(t_start=t_start)                 # every fold of the batch to its early stop (or budget), then its checkpoint restored
+            torch.cuda.current_stream(device).synchronize()
+
+    finished = set()
+    for wv in waves:
+        with ThreadPoolExecutor(max_workers=len(wv)) as ex:
+            list(ex.map(work, wv))
+        finished.update(u for ch in wv for u in ch)
+        for k in mine:                              # a fold decides as soon as both its models have finished
+            if k in fold_dirs and all((k, tag) in finished for tag, *_ in models):
+                decide(k, subjects[k], fold_dirs.pop(k), {tag: units[(k, tag)]["trainer"] for tag, *_ in models})
 
 
 def ablation_sets(all_channel_names):

@@ -30,16 +30,24 @@ from .runtime import FoldArena
 from .trainer import Trainer, accuracy_and_weighted_f1
 
 
+def _depth(model):
+    """(gru_hidden_size, gru_num_layers) of a model: the arena form it takes (runtime.FoldArena)."""
+    return int(getattr(model, "gru_hidden_size", 64)), int(getattr(model, "gru_num_layers", 2))
+
+
 def lockstep_compatible(preps) -> bool:
     """Folds can share launches when they draw from one SubjectStore with one model configuration and one batch size.  Their
     train / val sets may differ in size (WESAD subjects differ by a few windows, dataset.py:17-27): full batches run as one fold
-    batch, the folds' ragged last batches as launches over the folds whose batch sizes agree (`launch_plan`)."""
+    batch, the folds' ragged last batches as launches over the folds whose batch sizes agree (`launch_plan`).  The one-layer
+    32-unit model has an arena form (padded, as runtime.EmbeddedEngine); a batch is uniform in depth — msig_batch.gru_layers is
+    one value per launch."""
     if not (1 <= len(preps) <= L.MAX_FOLDS):       # a batch of ONE fold is a fold batch too (it can be re-dealt with others later)
         return False
     tr0, va0, _ = preps[0]["loaders"]
+    d0 = _depth(preps[0]["model"])
     for p in preps:
         tr, va, _ = p["loaders"]
-        if (getattr(p["model"], "embedded", False)          # the one-layer 32-unit model keeps its own embedded engine (no arena form)
+        if (_depth(p["model"]) != d0
                 or tr.batch_size != tr0.batch_size or va.batch_size != va0.batch_size or tr.store.data_ptr() != tr0.store.data_ptr()
                 or p["model"].in_channels != preps[0]["model"].in_channels or p["model"].num_classes != preps[0]["model"].num_classes
                 or p["model"].dropout_p != preps[0]["model"].dropout_p):
@@ -72,8 +80,12 @@ class LockstepTrainer:
         m0 = preps[0]["model"]
         self.n = len(preps)
         self.C, self.K, self.T = m0.in_channels, m0.num_classes, int(tr0.store.shape[2])
+        hidden, layers = _depth(m0)
+        if any(_depth(p["model"]) != (hidden, layers) for p in preps):
+            raise ValueError("a fold batch is uniform in depth: msig_batch.gru_layers is one value per launch")
+        self.embedded = layers == 1
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
-                               adaptive_forms=adaptive_forms)
+                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers)
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
@@ -84,10 +96,14 @@ class LockstepTrainer:
                 # rounds): its Adam moments move with it; model.engine() below moves the parameters and the BatchNorm state
                 new.exp_avg.copy_(old.exp_avg)
                 new.exp_avg_sq.copy_(old.exp_avg_sq)
+                if self.embedded:
+                    old.gather()                               # the one-layer model's reference-shaped parameters from its old arena
             model._engine = new                                # the model's parameters become views into arena `slot`
             t = p.get("trainer") or Trainer(model, p["fold_dir"], p["config"])
             p["trainer"] = t
             model.engine()
+            if self.embedded:
+                new.scatter()                                  # into the padded layout, once: the steps train it in place
             self.trainers.append(t)
         h0 = self.trainers[0].optimizer.hyper
         for t in self.trainers:
@@ -226,13 +242,17 @@ class LockstepTrainer:
             lockstep loop's critical path (a stopped fold's arena is no longer touched by the batch)."""
             t, p = self.trainers[f], self.preps[f]
             torch.cuda.set_device(dev)
+            test = p.get("test_pass", True)       # False: the caller evaluates the model itself (main.run_hierarchical_experiment)
             with torch.cuda.stream(torch.cuda.Stream(dev)):
+                if self.embedded:
+                    t.model._engine.gather()       # the trained padded layout -> the model's reference-shaped parameters
                 t._finish_training()
-                _, acc, f1 = t.evaluate(p["loaders"][2], is_test=True)
+                acc, f1 = t.evaluate(p["loaders"][2], is_test=True)[1:] if test else (None, None)
                 torch.cuda.current_stream(dev).synchronize()
             info = dict(subject=p["subject"], accuracy=acc, f1_score=f1, seconds=getattr(t, "finished_at", time.time() - t_start),
                         epochs=len(t.history), train_windows_per_s=t.train_windows / max(t.train_seconds, 1e-9), history=t.history)
-            (p["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
+            if test:
+                (p["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
             return info
 
         active = list(range(self.n))
@@ -251,6 +271,8 @@ class LockstepTrainer:
                 still = []
                 for (vl, va, vf), f in zip(vals, active):
                     t = self.trainers[f]
+                    if self.embedded:
+                        t.model._engine.gather()   # once per epoch, for the checkpoint early stopping may write (best_model.pt)
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
                     if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf):

@@ -242,6 +242,37 @@ class Engine:
             L.check(fn(C.byref(b), self._stream()), name)
 
 
+def embedding_index(in_channels: int, num_classes: int, hidden: int = 32):
+    """The one-layer model's embedding in the padded 64-unit flat layout (EmbeddedEngine): ([(state_dict key, reference shape)]
+    in flat-buffer order, int64 CPU index) — element i of the concatenated reference-shaped parameters lives at flat[index[i]]."""
+    layout, shapes = L.param_layout(in_channels, num_classes), L.param_shapes(in_channels, num_classes)
+    H = hidden
+    small_shapes, idx = [], []
+    gate_rows = torch.cat([torch.arange(g * 64, g * 64 + H) for g in range(3)])            # rows of the real units
+    for i, k in enumerate(L.PARAM_KEYS):
+        o, shape = layout[i], shapes[i]
+        if k.startswith("gru."):
+            if "_l1" in k:
+                continue                                            # no second layer in the embedded model
+            if k.startswith("gru.weight_ih"):
+                sm = (3 * H, shape[1]); ii = o + gate_rows[:, None] * shape[1] + torch.arange(shape[1])[None, :]
+            elif k.startswith("gru.weight_hh"):
+                sm = (3 * H, H); ii = o + gate_rows[:, None] * shape[1] + torch.arange(H)[None, :]
+            else:
+                sm = (3 * H,); ii = o + gate_rows
+        elif k == "classifier.0.weight":                            # (64, 128): real features at columns 0..31 (forward) and 64..95 (reverse)
+            cols = torch.cat([torch.arange(0, H), torch.arange(64, 64 + H)])
+            sm = (shape[0], 2 * H); ii = o + torch.arange(shape[0])[:, None] * shape[1] + cols[None, :]
+        else:
+            n = 1
+            for d in shape:
+                n *= d
+            sm, ii = tuple(shape), o + torch.arange(n)
+        small_shapes.append((k, sm))
+        idx.append(ii.reshape(-1).to(torch.int64))
+    return small_shapes, torch.cat(idx)
+
+
 class EmbeddedEngine(Engine):
     """The hierarchical experiment's second model (main.py:35-40: gru_hidden_size = 32, gru_num_layers = 1) on the kernels of the
     reference configuration.  Its GRU is embedded in layer 0 of the 64-unit layout: unit u of gate g sits at row g * 64 + u of the
@@ -252,37 +283,23 @@ class EmbeddedEngine(Engine):
     2 x 32 real features at columns 0..31 and 64..95 (classifier.0.weight is embedded the same way).
 
     The model's nn.Parameters are views of ONE contiguous buffer `small` (reference shapes, reference order); `index` maps its
-    elements into the padded flat buffer.  scatter() / gather() move values between the two around every library call."""
+    elements into the padded flat buffer.  scatter() / gather() move values between the two around every library call of a
+    stand-alone model; in a fold batch's arena (FoldArena) only when a model enters, is checkpointed or is handed back."""
 
-    def __init__(self, in_channels: int, num_classes: int, device: torch.device, hidden: int):
-        super().__init__(in_channels, num_classes, device)
+    def __init__(self, in_channels: int, num_classes: int, device: torch.device, hidden: int, storage: Optional[dict] = None):
+        """`storage`: the padded buffers of one arena of a fold batch (FoldArena.engine).  The library then trains the padded layout
+        in place; `small` is brought up to date (gather) and written back (scatter) only when the model's parameters are needed or
+        replaced — checkpoints, evaluation, re-dealing — never per step."""
+        super().__init__(in_channels, num_classes, device, storage)
         if hidden != 32:
             raise NotImplementedError("embedded GRU: hidden size 32 (main.py:38)")
         self.gru_layers = 1
         self.hidden = hidden
-        H, dev = hidden, self.device
-        self.small_shapes, idx = [], []
-        keys = L.PARAM_KEYS
-        gate_rows = torch.cat([torch.arange(g * 64, g * 64 + H) for g in range(3)])            # rows of the real units
-        for i, k in enumerate(keys):
-            o, shape = self.layout[i], self.shapes[i]
-            if k.startswith("gru."):
-                if "_l1" in k:
-                    continue                                            # no second layer in the embedded model
-                if k.startswith("gru.weight_ih"):
-                    sm = (3 * H, shape[1]); ii = o + gate_rows[:, None] * shape[1] + torch.arange(shape[1])[None, :]
-                elif k.startswith("gru.weight_hh"):
-                    sm = (3 * H, H); ii = o + gate_rows[:, None] * shape[1] + torch.arange(H)[None, :]
-                else:
-                    sm = (3 * H,); ii = o + gate_rows
-            elif k == "classifier.0.weight":                            # (64, 128): real features at columns 0..31 (forward) and 64..95 (reverse)
-                cols = torch.cat([torch.arange(0, H), torch.arange(64, 64 + H)])
-                sm = (shape[0], 2 * H); ii = o + torch.arange(shape[0])[:, None] * shape[1] + cols[None, :]
-            else:
-                sm, ii = tuple(shape), o + torch.arange(self._numel(i))
-            self.small_shapes.append((k, sm))
-            idx.append(ii.reshape(-1).to(torch.int64))
-        self.index = torch.cat(idx).to(dev)
+        dev = self.device
+        self.small_shapes, index = embedding_index(in_channels, num_classes, hidden)
+        self.index = index.to(dev)
+        self.padding = torch.ones(self.n_flat, dtype=torch.bool, device=dev)   # entries of the flat buffer no model parameter maps to
+        self.padding[self.index] = False
         self.small = torch.zeros(int(self.index.numel()), dtype=torch.float32, device=dev)
         self.small_grads = torch.zeros_like(self.small)
 
@@ -334,9 +351,15 @@ class FoldArena:
     same offsets — which is all msig_*_multi needs to run the same step for several folds in one set of launches."""
 
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
-                 adaptive_forms: bool = False):
+                 adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2):
+        """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
+        grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
+        launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth)."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
+        if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
+            raise NotImplementedError(f"fold arenas hold (gru_hidden, gru_layers) = (64, 2) or (32, 1), got {(gru_hidden, gru_layers)}")
+        self.gru_hidden, self.gru_layers = int(gru_hidden), int(gru_layers)
         eval_batch = int(eval_batch) or int(train_batch)
         self.C, self.K, self.n, self.T = in_channels, num_classes, n, T
         self.max_batch = max(int(train_batch), eval_batch)
@@ -384,6 +407,8 @@ class FoldArena:
         st["bn_count"] = self.view(slot, "bn_count", torch.int64)
         st["acc"] = self.view(slot, "acc", torch.float64)
         st["ws"] = self.view(slot, "ws")
+        if self.gru_layers == 1:
+            return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st)
         return Engine(self.C, self.K, self.device, storage=st)
 
     def ptr(self, name: str) -> int:
@@ -404,7 +429,7 @@ class FoldArena:
         b.bn_state, b.bn_count = self.ptr("bn_state"), self.ptr("bn_count")
         b.ws, b.ws_bytes = self.ptr("ws"), self.ws_bytes
         b.loss_acc = self.ptr("acc")
-        b.gru_layers = 2
+        b.gru_layers = self.gru_layers
         L.apply_forms(b)
         return b
 
