@@ -61,6 +61,7 @@ class Batch(C.Structure):
 
 MAX_FOLDS = 16
 ABI_VERSION = 5       # include/msig.h MSIG_ABI_VERSION
+CW_ABI_VERSION = 1    # include/msig_cw.h MSIG_CW_ABI_VERSION (class-weighted CrossEntropy)
 
 
 class Multi(C.Structure):
@@ -147,6 +148,15 @@ def lib() -> C.CDLL:
         L.msig_gather_windows_multi.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int64, vp, vp, C.POINTER(Multi), vp]
         L.msig_profile_report.argtypes = [C.c_char_p, C.c_int64]
         L.msig_profile_report.restype = C.c_int64
+        # include/msig_cw.h, exported by the same library: the forward / train-step calls with a class-weight vector
+        L.msig_cw_abi_version.restype = C.c_int
+        if L.msig_cw_abi_version() != CW_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_cw.h ABI {L.msig_cw_abi_version()}; this binding is {CW_ABI_VERSION}: rebuild the library")
+        f32, i64 = C.c_float, C.c_int64
+        L.msig_cw_forward.argtypes = [C.POINTER(Batch), vp, vp]
+        L.msig_cw_train_step.argtypes = [C.POINTER(Batch), vp, vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_cw_forward_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp]
+        L.msig_cw_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp, vp, f32, f32, f32, f32, i64, vp]
         _lib = L
     return _lib
 
@@ -213,6 +223,21 @@ def dropout_keys(seed: int, steps, stream_id: int):
 
 def dropout_threshold(p: float) -> int:
     return int(round(float(p) * 256.0))
+
+
+def check_class_weight(values, K: int):
+    """The host-side checks of a class-weight vector (include/msig_cw.h), made before anything is launched: exactly K finite,
+    non-negative numbers.  Returns them as a float64 numpy array; raises ValueError otherwise."""
+    import numpy as np
+    try:
+        w = np.asarray(values, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"class weights must be {K} numbers: {e}") from None
+    if w.ndim != 1 or w.size != K:
+        raise ValueError(f"class weights must be {K} numbers (one per class), got shape {tuple(w.shape)}")
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError(f"class weights must be finite and non-negative, got {w.tolist()}")
+    return w
 
 
 FORM_AUTO = -1

@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h and include/msig_cw.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "msig_dev.h"
+#include "../../include/msig_cw.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -251,13 +252,14 @@ extern "C" int msig_frontend_bwd(const msig_batch* b, void* stream) {
   return launch_colsum_plan(plan, single_fold(b), (hipStream_t)stream);
 }
 
-static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true) {
+// cw: class weights of include/msig_cw.h (NULL = the msig.h call)
+static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true, const float* cw = nullptr) {
   if (b->dx && fc.stride != 0) return MSIG_E_SHAPE;          // no input gradients in fold batches
   Ctx c; int rc = make_ctx(b, c, false); if (rc) return rc;
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;      // nothing has been launched: no model state has changed
   if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
   if ((rc = launch_gru_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
-  return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st) : 0;
+  return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st, cw) : 0;
 }
 extern "C" int msig_forward(const msig_batch* b, void* stream) {
   if (!b) return MSIG_E_NULL;
@@ -286,7 +288,7 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
 
 // fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch)
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
-                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st) {
+                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr) {
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
   if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
@@ -302,11 +304,11 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
   const bool head_step = head_step_applies(b, c.d);
-  if ((rc = forward_fc(b, fc, st, !head_step))) return rc;
+  if ((rc = forward_fc(b, fc, st, !head_step, cw))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
-  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
+  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, cw) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
@@ -353,6 +355,34 @@ extern "C" int msig_train_step_multi(const msig_batch* b, const msig_multi* m, f
                                      float eps, float weight_decay, int64_t step, void* stream) {
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+
+// ---- class-weighted CrossEntropy (include/msig_cw.h): the same calls with the weight vector passed down to the loss kernels ----
+extern "C" int msig_cw_abi_version(void) { return MSIG_CW_ABI_VERSION; }
+static inline bool cw_misaligned(const float* cw) { return ((uintptr_t)cw & 3) != 0; }
+
+extern "C" int msig_cw_forward(const msig_batch* b, const float* class_weight, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (!b) return MSIG_E_NULL;
+  return forward_fc(b, single_fold(b), (hipStream_t)stream, true, class_weight);
+}
+extern "C" int msig_cw_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (!b) return MSIG_E_NULL;
+  return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
+                       class_weight);
+}
+extern "C" int msig_cw_forward_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return forward_fc(b, fc, (hipStream_t)stream, true, class_weight);
+}
+extern "C" int msig_cw_train_step_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, float* exp_avg, float* exp_avg_sq,
+                                        float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight);
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {

@@ -78,34 +78,66 @@ __device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
   return mx + logf(se);
 }
 
+// Class-weighted CrossEntropy (include/msig_cw.h): W = sum_b w[y_b], the normaliser of the weighted mean, summed in fp64 in ONE
+// fixed order whatever the workgroup's size — lane j of the first 256 threads adds rows j, j + 256, ... in turn, each wave reduces
+// its lanes, the four wave sums are added in wave order — so that ce_kernel (1024 threads), every workgroup of head_step_kernel and
+// the loss finalizer (256 each) hold the identical value.  Every thread of the workgroup must call it (it synchronises); red4 is
+// shared memory of its own.
+__device__ __forceinline__ double cw_total(const float* __restrict__ cw, const int64_t* __restrict__ labels, int B, double* red4) {
+  const int tid = threadIdx.x;
+  if (tid < 256) {
+    double s = 0.0;
+    for (int row = tid; row < B; row += 256) s += (double)cw[labels[row]];
+    s = wave_sum_d(s);
+    if ((tid & 63) == 0) red4[tid >> 6] = s;
+  }
+  __syncthreads();
+  return (red4[0] + red4[1]) + (red4[2] + red4[3]);
+}
+
 // ------------------------------------------------------------------------------------
 // CrossEntropy (mean), dlogits, softmax probabilities, argmax, accuracy counter.
 // Single workgroup (one deterministic sum) of CE_THREADS threads — with 256 the 32 rows per thread of a B = 8192 batch took 62 us,
 // all of it exp / log latency.  lossbuf[0] = mean loss of this batch;
 // lossbuf[1] = summed loss of this batch (loss.item() * B, trainer.py:152,221); lossbuf[2] = #correct of this batch — plain
 // stores, no running sums: layouts of different batch sizes alias one pooled workspace, and the epoch sums live with the caller.
+// CW = class weights w (K floats, include/msig_cw.h; torch's CrossEntropyLoss(weight=w)): row b's terms carry w[y_b], the mean
+// divides by W = sum_b w[y_b] (cw_total) instead of B, and lossbuf[1] / loss_acc[0] get B times that mean.  Arranged so that w = 1
+// reproduces the unweighted instantiation's bits: W = B exactly, w_y * v = v, ls * (B / W) = ls.
 // ------------------------------------------------------------------------------------
 #define CE_THREADS 1024
+template <bool CW>
 __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                  float* __restrict__ probs, int* __restrict__ pred,
-                                                 float* __restrict__ dlogits, float* __restrict__ lossbuf, double* __restrict__ lacc, int B, int K, const FoldCtx fc) {
+                                                 float* __restrict__ dlogits, float* __restrict__ lossbuf, double* __restrict__ lacc,
+                                                 const float* __restrict__ cw, int B, int K, const FoldCtx fc) {
   FOLD_BEGIN; FS(logits); FS(labels); FS(probs); FS(pred); FS(dlogits); FS(lossbuf); FS(lacc);
   __shared__ double red[2][CE_THREADS / 64];
   const int tid = threadIdx.x;
   double lsum = 0.0, correct = 0.0;
-  const float invB = 1.0f / (float)B;
+  float invB = 1.0f / (float)B;
+  double W = 0.0;
+  if constexpr (CW) {
+    __shared__ double wred[4];
+    FS(cw);
+    W = cw_total(cw, labels, B, wred);
+    invB = 1.0f / (float)W;
+  }
   for (int row = tid; row < B; row += CE_THREADS) {
     const float* lg = logits + (size_t)row * K;
     int am;
     const float lse = ce_row_lse(lg, K, am);
     const int y = (int)labels[row];
-    lsum += (double)(lse - lg[y]);
+    const float wy = CW ? cw[y] : 1.f;
+    if constexpr (CW) lsum += (double)wy * (double)(lse - lg[y]);
+    else lsum += (double)(lse - lg[y]);
     correct += (am == y) ? 1.0 : 0.0;
     pred[row] = am;
     for (int c = 0; c < K; ++c) {
       const float p = expf(lg[c] - lse);
       probs[(size_t)row * K + c] = p;
-      if (dlogits) dlogits[(size_t)row * K + c] = (p - (c == y ? 1.f : 0.f)) * invB;
+      if constexpr (CW) { if (dlogits) dlogits[(size_t)row * K + c] = (wy * (p - (c == y ? 1.f : 0.f))) * invB; }
+      else { if (dlogits) dlogits[(size_t)row * K + c] = (p - (c == y ? 1.f : 0.f)) * invB; }
     }
   }
   lsum = wave_sum_d(lsum); correct = wave_sum_d(correct);
@@ -114,19 +146,30 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict_
   if (tid == 0) {
     double ls = 0.0, cs = 0.0;
     for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
-    lossbuf[0] = (float)(ls / (double)B);
-    lossbuf[1] = (float)ls;
-    lossbuf[2] = (float)cs;
-    if (lacc) { lacc[0] += ls; lacc[1] += cs; }      // msig_batch.loss_acc: the caller's running sums of a pass (one thread, stream order)
+    if constexpr (CW) {
+      const double sum = ls * ((double)B / W);
+      lossbuf[0] = (float)(ls / W);
+      lossbuf[1] = (float)sum;
+      lossbuf[2] = (float)cs;
+      if (lacc) { lacc[0] += sum; lacc[1] += cs; }
+    } else {
+      lossbuf[0] = (float)(ls / (double)B);
+      lossbuf[1] = (float)ls;
+      lossbuf[2] = (float)cs;
+      if (lacc) { lacc[0] += ls; lacc[1] += cs; }      // msig_batch.loss_acc: the caller's running sums of a pass (one thread, stream order)
+    }
   }
 }
 
 // The reduction half of ce_kernel for the fused head (head_step_kernel wrote pred / probs / dlogits; the loss and the accuracy
 // counter are sums over the whole batch): one workgroup of 256 threads plays ce_kernel's 1024 — virtual thread q * 256 + tid sums
 // the rows ce_kernel's thread of that index sums, each real wave reduces four virtual waves, thread 0 adds the sixteen wave sums in
-// ce_kernel's order.  Same values, same order: the loss is ce_kernel's, bit for bit.
-__device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[CE_THREADS / 64]) {
+// ce_kernel's order.  Same values, same order: the loss is ce_kernel's, bit for bit (CW: with cw_total's W, as ce_kernel<true>).
+template <bool CW>
+__device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[CE_THREADS / 64], double* wred) {
   const int tid = threadIdx.x;
+  double W = 0.0;
+  if constexpr (CW) W = cw_total(lf.cw, lf.labels, lf.B, wred);
 #pragma unroll 1
   for (int q = 0; q < CE_THREADS / 256; ++q) {
     double lsum = 0.0, correct = 0.0;
@@ -135,7 +178,8 @@ __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[C
       int am;
       const float lse = ce_row_lse(lg, lf.K, am);
       const int y = (int)lf.labels[row];
-      lsum += (double)(lse - lg[y]);
+      if constexpr (CW) lsum += (double)lf.cw[y] * (double)(lse - lg[y]);
+      else lsum += (double)(lse - lg[y]);
       correct += (am == y) ? 1.0 : 0.0;
     }
     lsum = wave_sum_d(lsum); correct = wave_sum_d(correct);
@@ -145,10 +189,18 @@ __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[C
   if (tid == 0) {
     double ls = 0.0, cs = 0.0;
     for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
-    lf.lossbuf[0] = (float)(ls / (double)lf.B);
-    lf.lossbuf[1] = (float)ls;
-    lf.lossbuf[2] = (float)cs;
-    if (lf.lacc) { lf.lacc[0] += ls; lf.lacc[1] += cs; }
+    if constexpr (CW) {
+      const double sum = ls * ((double)lf.B / W);
+      lf.lossbuf[0] = (float)(ls / W);
+      lf.lossbuf[1] = (float)sum;
+      lf.lossbuf[2] = (float)cs;
+      if (lf.lacc) { lf.lacc[0] += sum; lf.lacc[1] += cs; }
+    } else {
+      lf.lossbuf[0] = (float)(ls / (double)lf.B);
+      lf.lossbuf[1] = (float)ls;
+      lf.lossbuf[2] = (float)cs;
+      if (lf.lacc) { lf.lacc[0] += ls; lf.lacc[1] += cs; }
+    }
   }
 }
 
@@ -260,12 +312,15 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // loss and the accuracy counter — is summed by loss_finalize in the step's last launch.  Every statement is the corresponding one
 // of head_fwd_kernel / ce_kernel / head_bwd_kernel: the step's bits are those of the three launches
 // (tests/test_parity_gpu.py::test_fused_step_equals_separate_calls_bit_for_bit).  grid = (B + 15) / 16 <= HEAD_WG workgroups, each
-// writing one partial row, as head_bwd_kernel does at that size.
+// writing one partial row, as head_bwd_kernel does at that size.  CW: class-weighted CrossEntropy (ce_kernel<true>) — a row's dlogits
+// need the whole batch's W, which every workgroup sums itself over all B <= 2048 labels in cw_total's one order (no extra launch).
 // ------------------------------------------------------------------------------------
+template <bool CW>
 __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict__ feat, const float* __restrict__ W0, const float* __restrict__ b0,
                                                         const float* __restrict__ W3, const float* __restrict__ b3, const int64_t* __restrict__ labels,
                                                         float* __restrict__ hid, float* __restrict__ logits, float* __restrict__ probs, int* __restrict__ pred,
                                                         float* __restrict__ dlogits, float* __restrict__ dfeat, float* __restrict__ part,
+                                                        const float* __restrict__ cw,
                                                         int B, int K, int drop_thr, uint32_t drop_key, float dscale, float dscale_bwd, const FoldCtx fc) {
   FOLD_BEGIN; FS(feat); FS(W0); FS(b0); FS(W3); FS(b3); FS(labels); FS(hid); FS(logits); FS(probs); FS(pred); FS(dlogits); FS(dfeat); FS(part);
   drop_key = fc.key_head[blockIdx.z];
@@ -290,6 +345,12 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
   for (int i = tid; i < HEAD_ROWS * 128; i += 256) {
     const int row = r0 + (i >> 7);
     fs[i] = row < B ? feat[(size_t)row * 128 + (i & 127)] : 0.f;
+  }
+  float invW = 0.f;
+  if constexpr (CW) {
+    __shared__ double wred[4];
+    FS(cw);
+    invW = 1.0f / (float)cw_total(cw, labels, B, wred);
   }
   __syncthreads();
   // ---- head_fwd_kernel ----
@@ -331,10 +392,13 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
       const float lse = ce_row_lse(lg, K, am);
       const int y = (int)labels[row];
       pred[row] = am;
+      const float wy = CW ? cw[y] : 1.f;
       for (int c = 0; c < K; ++c) {
         const float p = expf(lg[c] - lse);
         probs[(size_t)row * K + c] = p;
-        const float dl = (p - (c == y ? 1.f : 0.f)) * invB;
+        float dl;
+        if constexpr (CW) dl = (wy * (p - (c == y ? 1.f : 0.f))) * invW;
+        else dl = (p - (c == y ? 1.f : 0.f)) * invB;
         dlogits[(size_t)row * K + c] = dl;
         dls[tid * MSIG_MAX_K + c] = dl;
       }
@@ -455,14 +519,17 @@ __global__ __launch_bounds__(256) void colsum_plan_kernel(const ColsumJobs jobs,
   if (ry == 0 && c < jb.ncols) jb.out[c] = (float)colsum_fold(red, cx);
 }
 
+template <bool CW>
 __global__ __launch_bounds__(256) void colsum_adam_kernel(const ColsumJobs jobs, const AdamArgs ad_in, const LossFin loss_in, const FoldCtx fc) {
   __shared__ double red[CS_LANES][CS_COLS];
   if ((int)blockIdx.x == jobs.blk0[MSIG_MAX_JOBS]) {          // one workgroup past the column blocks: the fused head's loss (launched only then)
     __shared__ double lred[2][CE_THREADS / 64];
+    __shared__ double wred[4];
     LossFin lf = loss_in;
     const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
     FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
-    loss_finalize(lf, lred);
+    if constexpr (CW) FS(lf.cw);
+    loss_finalize<CW>(lf, lred, wred);
     return;
   }
   const int ji = colsum_find_job(jobs, blockIdx.x);
@@ -499,7 +566,12 @@ int launch_colsum_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const Fo
   ColsumJobs a;
   const int nblk = colsum_fill(plan, a);
   if (nblk <= 0) return 0;
-  { MSIG_K("colsum_adam", st); colsum_adam_kernel<<<dim3(nblk + (plan.loss.logits ? 1 : 0), fc.n), 256, 0, st>>>(a, ad, plan.loss, fc); }
+  {
+    MSIG_K("colsum_adam", st);
+    const dim3 grid(nblk + (plan.loss.logits ? 1 : 0), fc.n);
+    if (plan.loss.cw) colsum_adam_kernel<true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc);
+    else colsum_adam_kernel<false><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc);
+  }
   MSIG_LAUNCH_CHECK();
   return 0;
 }
@@ -655,7 +727,8 @@ int launch_normalise(const double* raw, int64_t N, int T, int C_all, const int* 
 // ------------------------------------------------------------------------------------
 // Host launchers
 // ------------------------------------------------------------------------------------
-int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st) {
+int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
+                    const float* cw) {
   const float* P = b->params;
   const int thr = b->training ? b->dropout_thr : 0;
   const int ngroups = (d.B + HEAD_ROWS - 1) / HEAD_ROWS;
@@ -666,8 +739,13 @@ int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, co
   MSIG_LAUNCH_CHECK();
   if (b->labels) {
     MSIG_K("ce", st);
-    ce_kernel<<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                 msig_keeps(b) ? w.p<float>(MSIG_WS_DLOGITS) : nullptr, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K, fc);
+    float* dl = msig_keeps(b) ? w.p<float>(MSIG_WS_DLOGITS) : nullptr;
+    if (cw)
+      ce_kernel<true><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
+                                                             dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B, d.K, fc);
+    else
+      ce_kernel<false><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
+                                                              dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, nullptr, d.B, d.K, fc);
   } else {
     MSIG_K("softmax", st);
     softmax_kernel<<<dim3((d.B + 255) / 256, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED), d.B, d.K, fc);
@@ -699,19 +777,24 @@ int launch_head_bwd(const msig_batch* b, const float* dlogits, const StageDims& 
 bool head_step_applies(const msig_batch* b, const StageDims& d) {
   return b->training && b->labels && (d.B + HEAD_ROWS - 1) / HEAD_ROWS <= HEAD_WG;
 }
-int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st) {
+int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
+                     const float* cw) {
   const float* P = b->params;
   float* G = b->grads;
   const int thr = b->dropout_thr;
   const int grid = (d.B + HEAD_ROWS - 1) / HEAD_ROWS;
   float* part = w.p<float>(MSIG_WS_GRAD_PART) + part_offsets(d).head;
   const int PS = 64 * 128 + 64 + d.K * 64 + d.K;
-  { MSIG_K("head_step", st); head_step_kernel<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
-                                         P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                         w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, d.B, d.K, thr, b->key_head, drop_scale(thr),
-                                         thr > 0 ? drop_scale(thr) : 1.0f, fc); }
+  {
+    MSIG_K("head_step", st);
+    auto* kern = cw ? head_step_kernel<true> : head_step_kernel<false>;
+    kern<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
+                                              P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS),
+                                              w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr,
+                                              b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc);
+  }
   MSIG_LAUNCH_CHECK();
-  plan.loss = LossFin{w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K};
+  plan.loss = LossFin{w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K, cw};
   const bool ok = plan.add(part, grid, PS, 0, 64 * 128, G + po[MSIG_P_CLS0_W]) && plan.add(part, grid, PS, 64 * 128, 64, G + po[MSIG_P_CLS0_B]) &&
                   plan.add(part, grid, PS, 64 * 128 + 64, d.K * 64, G + po[MSIG_P_CLS3_W]) &&
                   plan.add(part, grid, PS, 64 * 128 + 64 + d.K * 64, d.K, G + po[MSIG_P_CLS3_B]);

@@ -62,6 +62,15 @@ EVAL_BATCH_SIZE = 1024
 # training at once: four fold batches per configuration (+ a side stream for finished folds' short test passes), one per configuration
 # in a sweep, and at most four single-fold streams with --no-lockstep (round 4 ran fifteen there).
 MAX_TRAIN_STREAMS = 4
+# Class-weighted CrossEntropyLoss (include/msig_cw.h): "none" (the reference's effective criterion — its use_class_weights branch
+# cannot run, trainer.py:81) or "balanced" (compute_class_weight('balanced') over each model's own training labels, trainer.py:85-89).
+CLASS_WEIGHTS = "none"
+
+
+def trainer_class_weights(cfg):
+    """cfg["class_weights"] as config['trainer']['class_weights']: None for "none"."""
+    v = cfg.get("class_weights", CLASS_WEIGHTS)
+    return None if v is None or (isinstance(v, str) and v == "none") else v
 
 
 def cap_waves(waves, cap=MAX_TRAIN_STREAMS):
@@ -106,6 +115,8 @@ def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_
     config_dict = {"trainer": {"epochs": cfg["epochs"], "learning_rate": cfg["lr"],
                                "early_stopping": {"enabled": True, "patience": pat, "delta": 0},
                                "weight_decay": cfg["weight_decay"], "verbose": cfg["verbose"]}}
+    if trainer_class_weights(cfg) is not None:
+        config_dict["trainer"]["class_weights"] = trainer_class_weights(cfg)
     return dict(fold=fold_idx, subject=subject_to_test, fold_dir=fold_dir, loaders=loaders, model=model, config=config_dict)
 
 
@@ -139,6 +150,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
                      ("NUM_WORKERS", NUM_WORKERS), ("PATIENCE", cfg["patience"]), ("NUM_CLASSES", cfg["num_classes"]),
                      ("MODEL_PARAMS", {MODEL_TO_USE: cfg["model_params"]})):
             f.write(f"{k}: {v}\n")
+        if trainer_class_weights(cfg) is not None:                  # named only when set: summaries of unweighted runs are unchanged
+            f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -391,9 +404,12 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
         pat = cfg["patience"]
         if isinstance(pat, (list, tuple)):       # a per-fold cycle of patiences, as in prepare_fold
             pat = int(pat[k % len(pat)])
-        return {"trainer": {"epochs": cfg["epochs"], "learning_rate": cfg["lr"],
-                            "early_stopping": {"enabled": True, "patience": pat, "delta": 0},
-                            "weight_decay": cfg["weight_decay"], "verbose": cfg.get("verbose", False)}}
+        tc = {"trainer": {"epochs": cfg["epochs"], "learning_rate": cfg["lr"],
+                          "early_stopping": {"enabled": True, "patience": pat, "delta": 0},
+                          "weight_decay": cfg["weight_decay"], "verbose": cfg.get("verbose", False)}}
+        if trainer_class_weights(cfg) is not None:      # M1's from its stress_binary, M2's from its amusement_binary training labels
+            tc["trainer"]["class_weights"] = trainer_class_weights(cfg)
+        return tc
     mk = lambda subj, ch, mode: WesadDataset(cfg["data_path"], subj, ch, all_channel_names, classification_mode=mode, cache=cache)
     bs = cfg["batch_size"]
     ebs = int(cfg.get("eval_batch_size") or bs)              # validation / test passes (per-window results do not depend on it)
@@ -450,7 +466,10 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
     if rank == 0:
         path = Path(run_output_dir) / "hierarchical_summary.txt"
         with open(path, "w", encoding="utf-8") as f:
-            f.write(f"M1 {m1_ch} {m1_par}\nM2 {m2_ch} {m2_par}\n\n")
+            f.write(f"M1 {m1_ch} {m1_par}\nM2 {m2_ch} {m2_par}\n")
+            if trainer_class_weights(cfg) is not None:
+                f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
+            f.write("\n")
             for r in results:
                 f.write(f"  - 测试 {r['subject']}: M1 Accuracy = {r['m1_accuracy']:.4f}, 三分类 Accuracy = {r['ternary_accuracy']:.4f}\n")
             if results:
@@ -542,7 +561,7 @@ def default_cfg():
     return dict(data_path=EARLY_DATA_PATH, channels=list(CHANNELS_TO_USE), mode=CLASSIFICATION_MODE, num_classes=NUM_CLASSES,
                 model_params=dict(MODEL_PARAMS[MODEL_TO_USE]), seed=SEED, epochs=EPOCHS, batch_size=BATCH_SIZE, lr=LEARNING_RATE,
                 patience=PATIENCE, weight_decay=WEIGHTS_DECAY, subjects=list(ALL_SUBJECTS), verbose=False, concurrent_folds=15,
-                eval_batch_size=EVAL_BATCH_SIZE)
+                eval_batch_size=EVAL_BATCH_SIZE, class_weights=CLASS_WEIGHTS)
 
 
 def main(argv=None):
@@ -577,6 +596,9 @@ def main(argv=None):
                     help="train concurrent folds on one HIP stream each instead of as one fold batch (msig_*_multi)")
     ap.add_argument("--difficulty", type=float, default=1.0, help="noise scale of the synthetic dataset")
     ap.add_argument("--normalise", choices=["host", "device"], default="host", help="where the per-subject z-score runs")
+    ap.add_argument("--class-weights", choices=["none", "balanced"], default=CLASS_WEIGHTS,
+                    help="class-weighted CrossEntropyLoss for training, validation and test losses: 'balanced' = N / (K * count_c) over "
+                         "each model's own training labels (M1 and M2 separately in --hierarchical)")
     args = ap.parse_args(argv)
 
     # Concurrent folds need their own hardware queues: with the runtime's default of 4, fifteen streams share four
@@ -599,7 +621,8 @@ def main(argv=None):
     cfg.update(epochs=args.epochs, patience=args.patience[0] if len(args.patience) == 1 else list(args.patience), batch_size=args.batch_size,
                verbose=args.verbose,
                concurrent_folds=args.concurrent_folds, normalise=args.normalise, eval_batch_size=args.eval_batch_size,
-               lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms)
+               lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms,
+               class_weights=args.class_weights)
     if args.synthetic is not None:
         from .synth import CHANNELS6, make_synthetic_wesad
         if rank == 0 and not (args.synthetic / "_channel_names.txt").exists():

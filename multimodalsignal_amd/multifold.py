@@ -105,6 +105,14 @@ class LockstepTrainer:
             if self.embedded:
                 new.scatter()                                  # into the padded layout, once: the steps train it in place
             self.trainers.append(t)
+        # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
+        # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
+        cws = [t.prepare_class_weights(p["loaders"][0]) for t, p in zip(self.trainers, preps)]
+        self.cw = None
+        if any(w is not None for w in cws):
+            for slot, w in enumerate(cws):
+                self.arena.set_class_weight(slot, np.ones(self.K) if w is None else w)
+            self.cw = self.arena.ptr("cw")
         h0 = self.trainers[0].optimizer.hyper
         for t in self.trainers:
             h = t.optimizer.hyper
@@ -184,7 +192,8 @@ class LockstepTrainer:
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
             self._gather(loaders[0], order, r0, i, b, m)
             _, desc = self._layout(b, True)
-            L.check(lib.msig_train_step_multi(C.byref(desc), C.byref(m), ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_train_step_multi")
+            L.check(lib.msig_cw_train_step_multi(C.byref(desc), C.byref(m), self.cw, ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
+                    "msig_cw_train_step_multi")           # self.cw None: exactly msig_train_step_multi
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
         return self.acc[:, 0].cpu().numpy()                   # the epoch's only sync
@@ -211,7 +220,7 @@ class LockstepTrainer:
             m = multis[(r0, nr)]
             self._gather(loaders[0], order, r0, i, b, m)
             off, desc = self._layout(b, False)
-            L.check(lib.msig_forward_multi(C.byref(desc), C.byref(m), st), "msig_forward_multi")
+            L.check(lib.msig_cw_forward_multi(C.byref(desc), C.byref(m), self.cw, st), "msig_cw_forward_multi")
             got = arena.across("ws", off[L.WS["PRED"]], torch.int32, b)[act[r0:r0 + nr]]      # (folds of the launch, b) copy
             for j in range(nr):
                 preds[r0 + j].append(got[j])

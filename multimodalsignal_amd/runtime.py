@@ -8,6 +8,7 @@ stream.  It holds no arithmetic of its own.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -60,6 +61,7 @@ class Engine:
         self._ws_pool: Dict[object, torch.Tensor] = {}
         self._last: Optional[Tuple[int, int, object]] = None
         self._keep = None
+        self._cw_checked = None                 # (weakref, version) of the last class-weight tensor whose values passed the checks
 
     # ---- views -----------------------------------------------------------------
     def _numel(self, i):
@@ -187,13 +189,35 @@ class Engine:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _class_weight(self, w: Optional[torch.Tensor]) -> Optional[int]:
+        """Device pointer of a class-weight vector (include/msig_cw.h) after the host-side checks — a contiguous (K,) float32 tensor
+        on a GPU holding finite, non-negative values, else ValueError before anything is launched.  The values are read back once
+        per tensor and version (an in-place change is seen), not once per step."""
+        if w is None:
+            return None
+        _require_gpu(w, "class_weight")
+        if w.dtype != torch.float32 or w.dim() != 1 or w.numel() != self.K or not w.is_contiguous():
+            raise ValueError(f"class_weight must be a contiguous float32 ({self.K},) tensor, got {w.dtype} {tuple(w.shape)}")
+        seen = self._cw_checked
+        if seen is None or seen[0]() is not w or seen[1] != w._version:
+            L.check_class_weight(w.detach().cpu().numpy(), self.K)
+            self._cw_checked = (weakref.ref(w), w._version)
+        return w.data_ptr()
+
     # ---- calls -------------------------------------------------------------------------
-    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False) -> L.Batch:
+    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False,
+                class_weight: Optional[torch.Tensor] = None) -> L.Batch:
         """model(inputs) [+ criterion]: logits land in region('LOGITS'); returns the descriptor
         that a following backward() must be given.  An eval-mode forward (training=False) takes a backward only with
-        keep_for_backward=True: it then keeps the stashes in a workspace of its own, with the same logits."""
+        keep_for_backward=True: it then keeps the stashes in a workspace of its own, with the same logits.  class_weight: a (K,)
+        float32 device tensor = CrossEntropyLoss(weight=class_weight) for the loss and, kept for a backward, WS_DLOGITS
+        (msig_cw_forward); None = the unweighted criterion."""
+        cw = self._class_weight(class_weight)
         b = self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward)
-        L.check(L.lib().msig_forward(C.byref(b), self._stream()), "msig_forward")
+        if cw is None:
+            L.check(L.lib().msig_forward(C.byref(b), self._stream()), "msig_forward")
+        else:
+            L.check(L.lib().msig_cw_forward(C.byref(b), cw, self._stream()), "msig_cw_forward")
         return b
 
     def backward(self, b: L.Batch, dlogits: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None):
@@ -224,14 +248,20 @@ class Engine:
                                        weight_decay, step, self._stream()), "msig_adam_step")
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
-                   dropout_p=0.0, seed=0) -> None:
+                   dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
-        to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts."""
+        to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
+        class_weight: (K,) float32 device tensor = criterion CrossEntropyLoss(weight=class_weight) (msig_cw_train_step)."""
+        cw = self._class_weight(class_weight)
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
-        L.check(L.lib().msig_train_step(C.byref(b), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                        betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_train_step")
+        if cw is None:
+            L.check(L.lib().msig_train_step(C.byref(b), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
+                                            betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_train_step")
+        else:
+            L.check(L.lib().msig_cw_train_step(C.byref(b), cw, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
+                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_cw_train_step")
 
     def stage(self, name: str, b: L.Batch):
         """Runs a single stage launcher by name (tests / profiling)."""
@@ -327,13 +357,15 @@ class EmbeddedEngine(Engine):
         return self.small_views(self.small_grads)
 
     # ---- the library calls, with the embedding maintained around them ----
-    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False):
+    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False, class_weight=None):
+        self._class_weight(class_weight)                    # the checks before the scatter: nothing runs on a bad vector
         self.scatter()
-        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward)
+        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight)
 
-    def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0):
+    def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None):
+        self._class_weight(class_weight)
         self.scatter()
-        super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed)
+        super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight)
         self.gather()
 
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1):
@@ -368,9 +400,10 @@ class FoldArena:
         self.device = torch.device(device)
         self.n_flat = L.param_layout(in_channels, num_classes)[-1]
         self.ws_bytes = self.workspace_bytes(train_batch, eval_batch, in_channels, T, num_classes)
+        # "cw": the fold's class-weight vector (include/msig_cw.h msig_cw_*_multi), written when a fold enters (set_class_weight)
         sizes = [("params", self.n_flat * 4), ("grads", self.n_flat * 4), ("exp_avg", self.n_flat * 4), ("exp_avg_sq", self.n_flat * 4),
                  ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16), ("acc", 16), ("x", self.max_batch * in_channels * T * 4), ("y", self.max_batch * 8),
-                 ("ws", self.ws_bytes)]
+                 ("ws", self.ws_bytes), ("cw", num_classes * 4)]
         self.off, at = {}, 0
         for name, nbytes in sizes:
             self.off[name] = (at, nbytes)
@@ -413,6 +446,13 @@ class FoldArena:
 
     def ptr(self, name: str) -> int:
         return self.mem.data_ptr() + self.off[name][0]                  # arena 0's buffer
+
+    def set_class_weight(self, slot: int, values) -> None:
+        """Writes the class-weight vector of the fold in arena `slot` (K values, checked on the host: ValueError before anything is
+        written).  msig_cw_*_multi, given ptr("cw"), read fold z's vector in arena m.slot[z]; all ones = the unweighted criterion,
+        bit for bit, so an unweighted fold can share launches with weighted ones."""
+        w = L.check_class_weight(values, self.K)
+        self.view(slot, "cw", torch.float32).copy_(torch.as_tensor(w, dtype=torch.float32))
 
     def batch(self, B: int, training: bool, dropout_p: float, with_labels: bool = True) -> L.Batch:
         """msig_batch describing arena 0 (the *_multi calls shift every pointer by slot * stride)."""

@@ -15,6 +15,8 @@ epoch — and evaluation reads predictions back once per call.
 Reference behaviours reproduced on purpose: EarlyStopping treats a
 HIGHER monitored value as better although it is fed the validation loss; the class-weight
 option is accepted and ignored (the reference's branch is unreachable, trainer.py:81).
+The class-weighted loss that branch would build is opted into through a key of this repo's
+own, ``config['trainer']['class_weights']`` (include/msig_cw.h).
 """
 from __future__ import annotations
 
@@ -110,6 +112,26 @@ def accuracy_and_weighted_f1(y_true: np.ndarray, y_pred: np.ndarray):
     return acc, float(f1)
 
 
+def balanced_class_weights(labels, num_classes: int) -> np.ndarray:
+    """sklearn's compute_class_weight('balanced', classes=range(K), y=labels) (trainer.py:85-89): N / (K * count_c), float64.
+    A class of [0, K) with no window in `labels` has no such weight: ValueError naming it."""
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    counts = np.bincount(y, minlength=num_classes)[:num_classes] if y.size else np.zeros(num_classes, np.int64)
+    missing = [c for c in range(num_classes) if counts[c] == 0]
+    if missing:
+        raise ValueError(f"class_weights='balanced': class(es) {missing} of [0, {num_classes}) are absent from the training set")
+    return y.size / (num_classes * counts.astype(np.float64))
+
+
+def class_weight_setting(value, num_classes: int):
+    """config['trainer']['class_weights']: None (the unweighted criterion), 'balanced', or K numbers (checked: ValueError)."""
+    if value is None or (isinstance(value, str) and value == "balanced"):
+        return value
+    if isinstance(value, str):
+        raise ValueError(f"class_weights must be None, 'balanced' or {num_classes} numbers, got {value!r}")
+    return L.check_class_weight(value, num_classes)
+
+
 class Trainer:
     def __init__(self, model, fold_output_dir: Path, config):
         self.model, self.fold_dir, self.config = model, Path(fold_output_dir), config
@@ -125,6 +147,10 @@ class Trainer:
         self.epochs, self.learning_rate = cfg["epochs"], cfg["learning_rate"]
         self.patience, self.weight_decay = cfg["early_stopping"]["patience"], cfg["weight_decay"]
         self.use_class_weights = cfg.get("use_class_weights", False)      # accepted, inert (trainer.py:81)
+        # CrossEntropyLoss(weight=...) of the train steps and of the validation / test losses (trainer.py:96-97): None, 'balanced'
+        # (from the training loader's labels, when training starts) or K numbers.  class_weight: the (K,) fp32 device vector once set
+        self.class_weights = class_weight_setting(cfg.get("class_weights"), self.model.num_classes)
+        self.class_weight = None
         self.verbose = cfg.get("verbose", True)
         self.optimizer = MsigAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)   # trainer.py:68
         self.scheduler = ReduceLROnPlateau(self.optimizer, mode="min", factor=0.1, patience=3)         # trainer.py:72-77
@@ -163,11 +189,29 @@ class Trainer:
                              f"[0, {self.model.num_classes}): dataset labels do not match the model's num_classes")
         self._labels_ok.add(id(ds))
 
+    def prepare_class_weights(self, train_loader):
+        """Resolves config['trainer']['class_weights'] once (trainer.py:80-97): 'balanced' from the training loader's dataset labels.
+        Logs the vector as the reference does.  Returns the host values (float32) or None."""
+        if self.class_weights is None:
+            return None
+        if self.class_weight is None:
+            if isinstance(self.class_weights, str):
+                labels = getattr(getattr(train_loader, "dataset", None), "labels", None)
+                if labels is None:
+                    raise ValueError("class_weights='balanced' needs a training dataset with a `labels` array")
+                w = balanced_class_weights(labels, self.model.num_classes)
+            else:
+                w = self.class_weights
+            self.class_weight = torch.tensor(np.asarray(w, dtype=np.float32), device=self.device)
+            self._log(f"已启用类别加权损失，权重为: {np.asarray(w, dtype=np.float32)}")
+        return self.class_weight.cpu().numpy()
+
     # ---- trainer.py:119-191 -------------------------------------------------------------------
     def train(self, train_loader, val_loader):
         eng = self.model.engine()
         self._check_labels(train_loader)
         self._check_labels(val_loader)
+        self.prepare_class_weights(train_loader)
         n_train = len(train_loader.dataset)
         for epoch in range(self.epochs):
             t0 = time.time()
@@ -178,7 +222,8 @@ class Trainer:
                 h = self.optimizer.hyper
                 self.optimizer.step_count += 1
                 eng.train_step(x, y, lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
-                               step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed)
+                               step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
+                               class_weight=self.class_weight)
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
             train_loss = float(eng.loss_acc[0].item()) / n_train                        # the epoch's only sync
             dt = time.time() - t0
@@ -218,7 +263,7 @@ class Trainer:
         preds, labs = [], []
         for inputs, labels in data_loader:
             x, y = self._to_device(inputs, labels)
-            eng.forward(x, y, training=False)              # the loss kernel adds loss * batch to eng.loss_acc (trainer.py:221)
+            eng.forward(x, y, training=False, class_weight=self.class_weight)   # the loss kernel adds loss * batch to eng.loss_acc (trainer.py:221)
             preds.append(eng.region("PRED", torch.int32, (y.shape[0],)).clone())
             labs.append(y.clone())          # DeviceLoader reuses its batch buffers
         all_preds = torch.cat(preds).cpu().numpy().astype(np.int64)
