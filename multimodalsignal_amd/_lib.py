@@ -1,4 +1,4 @@
-"""ctypes binding of libmsig_hip.so (include/msig.h).
+"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -38,6 +38,23 @@ PARAM_KEYS = (
 )
 assert len(PARAM_KEYS) == NPARAM
 
+# Model kinds (main.py --model).  "cnn_gru" is the baseline without ChannelAttention (include/msig_cg.h): the same tensors minus
+# the gate's two, which have zero size in its flat layout.
+MODEL_KINDS = ("cnn_gru_attention", "cnn_gru")
+GATE_KEYS = ("channel_attention.fc.0.weight", "channel_attention.fc.2.weight")
+
+
+def check_kind(kind: str) -> str:
+    if kind not in MODEL_KINDS:
+        raise ValueError(f"model kind must be one of {MODEL_KINDS}, got {kind!r}")
+    return kind
+
+
+def param_keys(kind: str = "cnn_gru_attention"):
+    """(msig_param index, state_dict key) of every parameter tensor the model kind has, in flat-buffer order."""
+    check_kind(kind)
+    return [(i, k) for i, k in enumerate(PARAM_KEYS) if kind == "cnn_gru_attention" or k not in GATE_KEYS]
+
 ERRORS = {-1: "MSIG_E_NULL (required pointer is NULL)", -2: "MSIG_E_SHAPE (unsupported B/C/T/K or mode)",
           -3: "MSIG_E_ALIGN (buffer not 16-byte aligned)", -4: "MSIG_E_WORKSPACE (workspace too small)",
           -5: "MSIG_E_FORM (fwd_form / bwd_form is not a kernel form this call can run)"}
@@ -62,6 +79,7 @@ class Batch(C.Structure):
 MAX_FOLDS = 16
 ABI_VERSION = 5       # include/msig.h MSIG_ABI_VERSION
 CW_ABI_VERSION = 1    # include/msig_cw.h MSIG_CW_ABI_VERSION (class-weighted CrossEntropy)
+CG_ABI_VERSION = 1    # include/msig_cg.h MSIG_CG_ABI_VERSION (the cnn_gru baseline)
 
 
 class Multi(C.Structure):
@@ -157,6 +175,16 @@ def lib() -> C.CDLL:
         L.msig_cw_train_step.argtypes = [C.POINTER(Batch), vp, vp, vp, f32, f32, f32, f32, f32, i64, vp]
         L.msig_cw_forward_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp]
         L.msig_cw_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp, vp, f32, f32, f32, f32, i64, vp]
+        # include/msig_cg.h, exported by the same library: the cnn_gru baseline (no ChannelAttention)
+        L.msig_cg_abi_version.restype = C.c_int
+        if L.msig_cg_abi_version() != CG_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_cg.h ABI {L.msig_cg_abi_version()}; this binding is {CG_ABI_VERSION}: rebuild the library")
+        L.msig_cg_param_layout.argtypes = [C.c_int, C.c_int, i64p]
+        L.msig_cg_forward.argtypes = [C.POINTER(Batch), vp, vp]
+        L.msig_cg_backward.argtypes = [C.POINTER(Batch), vp, vp]
+        L.msig_cg_train_step.argtypes = [C.POINTER(Batch), vp, vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_cg_forward_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp]
+        L.msig_cg_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp, vp, f32, f32, f32, f32, i64, vp]
         _lib = L
     return _lib
 
@@ -173,16 +201,21 @@ def stage_lengths(T: int):
     return tuple(int(v) for v in out)
 
 
-def param_layout(Cin: int, K: int):
-    """Offsets (floats) of the NPARAM tensors in the flat buffer; last entry = total."""
+def param_layout(Cin: int, K: int, kind: str = "cnn_gru_attention"):
+    """Offsets (floats) of the NPARAM tensors in the flat buffer; last entry = total.  kind "cnn_gru": msig_cg_param_layout (the
+    gate's two tensors have zero size)."""
     off = (C.c_int64 * (NPARAM + 1))()
-    check(lib().msig_param_layout(Cin, K, off), "msig_param_layout")
+    if check_kind(kind) == "cnn_gru":
+        check(lib().msig_cg_param_layout(Cin, K, off), "msig_cg_param_layout")
+    else:
+        check(lib().msig_param_layout(Cin, K, off), "msig_param_layout")
     return [int(v) for v in off]
 
 
-def param_shapes(Cin: int, K: int):
+def param_shapes(Cin: int, K: int, kind: str = "cnn_gru_attention"):
     G, H = 192, 64
-    shapes = [(Cin // 4, Cin), (Cin, Cin // 4), (16, Cin, 7), (16,), (16,), (32, 16, 5), (32,), (32,)]
+    Cr = Cin // 4 if check_kind(kind) == "cnn_gru_attention" else 0
+    shapes = [(Cr, Cin), (Cin, Cr), (16, Cin, 7), (16,), (16,), (32, 16, 5), (32,), (32,)]
     for layer in (0, 1):
         for _ in range(2):
             shapes += [(G, 128 if layer else 32), (G, H), (G,), (G,)]

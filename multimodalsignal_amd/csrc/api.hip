@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h and include/msig_cw.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, include/msig_cw.h and include/msig_cg.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -9,6 +9,7 @@
 #include <vector>
 #include "msig_dev.h"
 #include "../../include/msig_cw.h"
+#include "../../include/msig_cg.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -103,11 +104,12 @@ extern "C" int msig_stage_lengths(int T, int32_t* out) {
   return 0;
 }
 
-extern "C" int msig_param_layout(int C, int K, int64_t* off) {
+// gated = false: CnnGruModel's layout (include/msig_cg.h), the gate's two tensors with zero size
+static int param_layout(int C, int K, int64_t* off, bool gated) {
   if (!off) return MSIG_E_NULL;
   if (C < 1 || C > MSIG_MAX_C || K < 2 || K > MSIG_MAX_K) return MSIG_E_SHAPE;
   int64_t n[MSIG_NPARAM];
-  const int Cr = C / 4;
+  const int Cr = gated ? C / 4 : 0;
   n[MSIG_P_GATE_W1] = (int64_t)Cr * C;
   n[MSIG_P_GATE_W2] = (int64_t)C * Cr;
   n[MSIG_P_CONV1_W] = 16 * C * 7;
@@ -128,6 +130,7 @@ extern "C" int msig_param_layout(int C, int K, int64_t* off) {
   off[MSIG_NPARAM] = o;
   return 0;
 }
+extern "C" int msig_param_layout(int C, int K, int64_t* off) { return param_layout(C, K, off, true); }
 
 static inline int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
 static inline int64_t imax(int64_t a, int64_t b) { return a > b ? a : b; }
@@ -198,7 +201,8 @@ struct Ctx {
   int64_t po[MSIG_NPARAM + 1];
 };
 
-static int make_ctx(const msig_batch* b, Ctx& c, bool need_grads) {
+// cg: CnnGruModel (include/msig_cg.h), whose parameter layout has no gate tensors
+static int make_ctx(const msig_batch* b, Ctx& c, bool need_grads, bool cg = false) {
   if (!b) return MSIG_E_NULL;
   int rc = check_shape(&b->shape);
   if (rc) return rc;
@@ -215,7 +219,7 @@ static int make_ctx(const msig_batch* b, Ctx& c, bool need_grads) {
   if (rc) return rc;
   if (b->ws_bytes < c.w.off[MSIG_NWS]) return MSIG_E_WORKSPACE;
   c.w.base = (char*)b->ws;
-  return msig_param_layout(b->shape.C, b->shape.K, c.po);
+  return param_layout(b->shape.C, b->shape.K, c.po, !cg);
 }
 
 extern "C" int msig_frontend_fwd(const msig_batch* b, void* stream) {
@@ -252,12 +256,13 @@ extern "C" int msig_frontend_bwd(const msig_batch* b, void* stream) {
   return launch_colsum_plan(plan, single_fold(b), (hipStream_t)stream);
 }
 
-// cw: class weights of include/msig_cw.h (NULL = the msig.h call)
-static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true, const float* cw = nullptr) {
+// cw: class weights of include/msig_cw.h (NULL = the msig.h call); cg: CnnGruModel (include/msig_cg.h)
+static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true, const float* cw = nullptr,
+                      bool cg = false) {
   if (b->dx && fc.stride != 0) return MSIG_E_SHAPE;          // no input gradients in fold batches
-  Ctx c; int rc = make_ctx(b, c, false); if (rc) return rc;
+  Ctx c; int rc = make_ctx(b, c, false, cg); if (rc) return rc;
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;      // nothing has been launched: no model state has changed
-  if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
+  if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st, !cg))) return rc;
   if ((rc = launch_gru_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
   return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st, cw) : 0;
 }
@@ -266,16 +271,18 @@ extern "C" int msig_forward(const msig_batch* b, void* stream) {
   return forward_fc(b, single_fold(b), (hipStream_t)stream);
 }
 
-extern "C" int msig_backward(const msig_batch* b, const float* dlogits, void* stream) {
-  Ctx c; int rc = make_ctx(b, c, true); if (rc) return rc;
+static int backward_fc(const msig_batch* b, const float* dlogits, hipStream_t st, bool cg) {
+  Ctx c; int rc = make_ctx(b, c, true, cg); if (rc) return rc;
   if (!msig_keeps(b)) return MSIG_E_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
   const FoldCtx fc = single_fold(b);
   ColsumPlan plan;      // every weight-gradient reduction of the pass, done by one launch at the end
   if ((rc = launch_head_bwd(b, dlogits, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
-  if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
+  if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
   return launch_colsum_plan(plan, fc, st);
+}
+extern "C" int msig_backward(const msig_batch* b, const float* dlogits, void* stream) {
+  return backward_fc(b, dlogits, (hipStream_t)stream, false);
 }
 
 extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -288,7 +295,7 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
 
 // fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch)
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
-                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr) {
+                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr, bool cg = false) {
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
   if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
@@ -299,18 +306,18 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   if (((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return MSIG_E_ALIGN;
   int rc;
   Ctx c;
-  if ((rc = make_ctx(b, c, true))) return rc;          // every argument check of the step before its first launch
+  if ((rc = make_ctx(b, c, true, cg))) return rc;          // every argument check of the step before its first launch
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
   const bool head_step = head_step_applies(b, c.d);
-  if ((rc = forward_fc(b, fc, st, !head_step, cw))) return rc;
+  if ((rc = forward_fc(b, fc, st, !head_step, cw, cg))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
   if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, cw) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
-  if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
+  if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
   for (int i = 0; i < 6; ++i) {
     const int t = in_place[i];
@@ -383,6 +390,38 @@ extern "C" int msig_cw_train_step_multi(const msig_batch* b, const msig_multi* m
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight);
+}
+
+// ---- CnnGruModel, the baseline without ChannelAttention (include/msig_cg.h): the same steps on the gate-free front end ----------
+extern "C" int msig_cg_abi_version(void) { return MSIG_CG_ABI_VERSION; }
+extern "C" int msig_cg_param_layout(int C, int K, int64_t* off) { return param_layout(C, K, off, false); }
+
+extern "C" int msig_cg_forward(const msig_batch* b, const float* class_weight, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (!b) return MSIG_E_NULL;
+  return forward_fc(b, single_fold(b), (hipStream_t)stream, true, class_weight, true);
+}
+extern "C" int msig_cg_backward(const msig_batch* b, const float* dlogits, void* stream) {
+  return backward_fc(b, dlogits, (hipStream_t)stream, true);
+}
+extern "C" int msig_cg_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (!b) return MSIG_E_NULL;
+  return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
+                       class_weight, true);
+}
+extern "C" int msig_cg_forward_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return forward_fc(b, fc, (hipStream_t)stream, true, class_weight, true);
+}
+extern "C" int msig_cg_train_step_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, float* exp_avg, float* exp_avg_sq,
+                                        float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight,
+                       true);
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {

@@ -23,7 +23,9 @@
 // interleave — one channel after the other the kernel was C dependent round trips to memory (14.5 us at the reference's 64
 // windows, where a workgroup's 92 KB are the whole job of its CU).  Per channel the sums run over the same samples in the same
 // order either way.
-template <int CT>
+// EO_ONLY (CnnGruModel, which has no gate): only the even / odd sample sums conv1's backward needs, in the same order as the full
+// form — no mean, no MLP, no s.
+template <int CT, bool EO_ONLY = false>
 __global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ x, const float* __restrict__ W1,
                                                    const float* __restrict__ W2, float* __restrict__ mean_out,
                                                    float* __restrict__ pre_out, float* __restrict__ s_out,
@@ -55,15 +57,17 @@ __global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ x, 
         if (i0 + 256 * u < T4) {
 #pragma unroll
           for (int c = 0; c < CN; ++c) {
-            acc[c] += (q[u][c].x + q[u][c].y) + (q[u][c].z + q[u][c].w);
+            if (!EO_ONLY) acc[c] += (q[u][c].x + q[u][c].y) + (q[u][c].z + q[u][c].w);
             ev[c] += q[u][c].x + q[u][c].z; od[c] += q[u][c].y + q[u][c].w;
           }
         }
     }
 #pragma unroll
     for (int c = 0; c < CN; ++c) {
-      const float a = wave_sum(acc[c]);
-      if (lane == 0) red[w][c] = a;
+      if (!EO_ONLY) {
+        const float a = wave_sum(acc[c]);
+        if (lane == 0) red[w][c] = a;
+      }
       if (eo_out) {                                  // uniform
         const float e = wave_sum(ev[c]), o = wave_sum(od[c]);
         if (lane == 0) { red_eo[w][2 * c] = e; red_eo[w][2 * c + 1] = o; }
@@ -77,20 +81,26 @@ __global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ x, 
       const float4* x4 = (const float4*)xc;
       for (int i = tid; i < T / 4; i += 256) {
         const float4 q = x4[i];
-        acc += (q.x + q.y) + (q.z + q.w);
+        if (!EO_ONLY) acc += (q.x + q.y) + (q.z + q.w);
         ev += q.x + q.z; od += q.y + q.w;
       }
     } else {
-      for (int i = tid; i < T; i += 256) { const float v = xc[i]; acc += v; if (i & 1) od += v; else ev += v; }
+      for (int i = tid; i < T; i += 256) { const float v = xc[i]; if (!EO_ONLY) acc += v; if (i & 1) od += v; else ev += v; }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) red[w][c] = acc;
+    if (!EO_ONLY) {
+      acc = wave_sum(acc);
+      if (lane == 0) red[w][c] = acc;
+    }
     if (eo_out) {                                  // uniform
       ev = wave_sum(ev); od = wave_sum(od);
       if (lane == 0) { red_eo[w][2 * c] = ev; red_eo[w][2 * c + 1] = od; }
     }
   }
   __syncthreads();
+  if (EO_ONLY) {
+    if (tid < 2 * C) eo_out[(size_t)b * 2 * C + tid] = (red_eo[0][tid] + red_eo[1][tid]) + (red_eo[2][tid] + red_eo[3][tid]);
+    return;
+  }
   if (tid < C) {
     const float m = (red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]) / (float)T;
     mean_s[tid] = m;
@@ -182,7 +192,9 @@ __device__ __forceinline__ void stage_x_chunk(float* xs, const float* __restrict
 
 // CT > 0: channel count known at compile time (straight-line MFMA stream, no per-MFMA guards);
 // CT == 0: generic fallback for C > 8 with wave-uniform guards.
-template <int CT>
+// GATED = false (CnnGruModel, no gate; gate_s is not read): the taps are conv1's raw weights, the same for every item — loaded into the
+// A-operand registers once per workgroup, with no per-item gate prefetch, staging or multiply.
+template <int CT, bool GATED = true>
 __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w1,
                                                         const float* __restrict__ gate_s, float* __restrict__ y1,
                                                         float* __restrict__ part, int B, int Crt, int T, int L1,
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
   const bool pipe = PIPE && (T & 3) == 0;
   float4 xr[NX4];
   float wfix[NWS], gr[NWS];
-  if (pipe) {
+  if (GATED && pipe) {
 #pragma unroll
     for (int j = 0; j < NWS; ++j) {      // the weight itself never changes: only the window's gate does
       const int i = tid + 256 * j, k = i >> 4, o = i & 15;
@@ -232,12 +244,22 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
       const int gc = g0 < 0 ? 0 : (g0 > T - 4 ? T - 4 : g0);              // unconditional, clamped load
       xr[j] = *(const float4*)(xb + (size_t)c * T + gc);
     }
+    if (GATED) {
 #pragma unroll
-    for (int j = 0; j < NWS; ++j) {
-      const int i = tid + 256 * j, k = i >> 4, kc = (i < 4 * KM * 16 && k < K) ? k : 0;
-      gr[j] = gate_s[(size_t)b * C + kc / 7];
+      for (int j = 0; j < NWS; ++j) {
+        const int i = tid + 256 * j, k = i >> 4, kc = (i < 4 * KM * 16 && k < K) ? k : 0;
+        gr[j] = gate_s[(size_t)b * C + kc / 7];
+      }
     }
   };
+  float wa[KMC];                          // A operands: k = 4 m + lq, o = li
+  if (!GATED) {
+#pragma unroll
+    for (int m = 0; m < KMC; ++m) {
+      const int k = 4 * m + lq;
+      wa[m] = ((CT > 0 || m < KM) && k < K) ? w1[li * K + k] : 0.f;
+    }
+  }
   if (pipe && (int)blockIdx.x < nitems) prefetch(blockIdx.x);
   for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
     const int b = item / nchunk, t0 = (item - b * nchunk) * C1_CHUNK;
@@ -255,26 +277,31 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
           *(float2*)&xs[(2 * c + 1) * C1_XP + 2 * i4] = make_float2(q.y, q.w);
         }
       }
+      if (GATED) {
 #pragma unroll
-      for (int j = 0; j < NWS; ++j) {
-        const int i = tid + 256 * j;
-        if (i < 4 * KM * 16) ws[i] = wfix[j] * gr[j];
+        for (int j = 0; j < NWS; ++j) {
+          const int i = tid + 256 * j;
+          if (i < 4 * KM * 16) ws[i] = wfix[j] * gr[j];
+        }
       }
     } else {
       stage_x_chunk<true>(xs, x + (size_t)b * C * T, C, T, t0, tid);
-      for (int i = tid; i < 4 * KM * 16; i += 256) {
-        const int k = i >> 4, o = i & 15, kc = k < K ? k : 0;
-        const float v = w1[o * K + kc] * gate_s[(size_t)b * C + kc / 7];
-        ws[i] = (k < K) ? v : 0.f;
+      if (GATED) {
+        for (int i = tid; i < 4 * KM * 16; i += 256) {
+          const int k = i >> 4, o = i & 15, kc = k < K ? k : 0;
+          const float v = w1[o * K + kc] * gate_s[(size_t)b * C + kc / 7];
+          ws[i] = (k < K) ? v : 0.f;
+        }
       }
     }
     __syncthreads();
     if (pipe && item + (int)gridDim.x < nitems) prefetch(item + gridDim.x);
     // the A operands (this window's gate-scaled weights) are the same for the wave's four position blocks: read
     // them once per item (a DS instruction costs a wave ~12 cycles; this removes 33 of the 88 per item)
-    float wa[KMC];
+    if (GATED) {
 #pragma unroll
-    for (int m = 0; m < KMC; ++m) wa[m] = (CT > 0 || m < KM) ? ws[(4 * m + lq) * 16 + li] : 0.f;
+      for (int m = 0; m < KMC; ++m) wa[m] = (CT > 0 || m < KM) ? ws[(4 * m + lq) * 16 + li] : 0.f;
+    }
 #pragma unroll
     for (int pbi = 0; pbi < 4; ++pbi) {
       const int pl = (w * 4 + pbi) * 16 + li;      // position within the chunk
@@ -1053,6 +1080,8 @@ __global__ __launch_bounds__(256, CONV1_BWD_WGS) void conv1_bwd_kernel(const flo
 //   G = scale * (Gdz - c1 * Sx - c2 * Gxh);   dW1 += s[b,c] * G (one partial row per workgroup);   ds[b,c] = sum_{o,kk} w1[o][c][kk] * G.
 // Sx[c][kk] = sum_{0 <= t < L1} x[c][2t + kk - 3] (zero padding) = the sum of all samples of the parity of kk - 3 (eo, from the gate
 // kernel) less the few at the window's edges that no t reaches.
+// GATED = false (CnnGruModel): the factor s[b,c] is 1, no ds is formed (gate_s and ds_out are not touched).
+template <bool GATED = true>
 __global__ __launch_bounds__(256) void conv1_bwd_fin_kernel(const float* __restrict__ g1w, const float* __restrict__ stat,
                                                             const float* __restrict__ cstat, const float* __restrict__ w1,
                                                             const float* __restrict__ gate_s, const float* __restrict__ eo,
@@ -1077,7 +1106,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_fin_kernel(const float* __restr
   }
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const float* gw = g1w + (size_t)b * SEG * 32 * NB16;
-    if (tid < C) ss[tid] = gate_s[(size_t)b * C + tid];
+    if (GATED && tid < C) ss[tid] = gate_s[(size_t)b * C + tid];
     if (tid >= 64 && tid < 64 + K) {
       const int col = tid - 64, c = col / 7, d = col - 7 * c - 3, par = d & 1;
       const float* xc = x + ((size_t)b * C + c) * T;
@@ -1107,11 +1136,12 @@ __global__ __launch_bounds__(256) void conv1_bwd_fin_kernel(const float* __restr
               if (s0 + u < SEG) { gdz += a8[u]; gxh += b8[u]; }
           }
           g = sc[j] * (gdz - k1[j] * sxs[col_[j]] - gxh * k2[j]);
-          dwacc[j] += ss[col_[j] / 7] * g;
+          dwacc[j] += GATED ? ss[col_[j] / 7] * g : g;
         }
-        prod[idx] = wv[j] * g;
+        if (GATED) prod[idx] = wv[j] * g;
       }
     __syncthreads();
+    if (!GATED) continue;
     if (tid < 16 * C) {
       const int o = tid / C, c = tid - o * C;
       float a = 0.f;
@@ -1153,6 +1183,8 @@ __global__ __launch_bounds__(256) void conv1_bwd_fin_kernel(const float* __restr
 #define DX_UCH 256              // u (output pairs) per item: one per thread
 #define DX_ROWS (DX_UCH + 8)    // staged dy1 rows t' = u0 - 4 .. u0 + DX_UCH + 3: whole quads, the halo rows u0 - 1 and u0 + 256, u0 + 257 included
 #define DX_PS 20                // LDS row stride (floats) of a 16-channel dy1 row
+// GATED = false (CnnGruModel): no gate term and no s factor, dx = du (gate_s, pre, gw1, gw2 and ds are not read).
+template <bool GATED = true>
 __global__ __launch_bounds__(256) void conv1_bwd_dx_kernel(const float* __restrict__ dp1, const uint8_t* __restrict__ code1,
                                                            const float* __restrict__ y1, const float* __restrict__ stat,
                                                            const float* __restrict__ cstat, const float* __restrict__ w1,
@@ -1167,7 +1199,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_dx_kernel(const float* __restri
   const int nchunk = (L1 + DX_UCH - 1) / DX_UCH;
   const int b = blockIdx.x / nchunk, u0 = (blockIdx.x - b * nchunk) * DX_UCH;
   // the gate: dmean / T and s of this window (gate_bwd's expression for dL/d(fc.0 output))
-  if (tid < C) {
+  if (GATED && tid < C) {
     float a = 0.f;
     for (int j = 0; j < Cr; ++j)
       if (pre[(size_t)b * Cr + j] > 0.f) {
@@ -1241,7 +1273,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_dx_kernel(const float* __restri
         ao = fmaf(wr[6], vm1[e], fmaf(wr[4], v0[e], fmaf(wr[2], vp1[e], fmaf(wr[0], vp2[e], ao))));
       }
     }
-    const float ev = fmaf(s_s[c], ae, s_dm[c]), od = fmaf(s_s[c], ao, s_dm[c]);
+    const float ev = GATED ? fmaf(s_s[c], ae, s_dm[c]) : ae, od = GATED ? fmaf(s_s[c], ao, s_dm[c]) : ao;
     if ((T & 1) == 0) {
       *(float2*)(dxb + (size_t)c * T + t) = make_float2(ev, od);          // T even: 2u + 1 < T for every u < L1 = T / 2
     } else {
@@ -1296,12 +1328,27 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------
 static inline int clampi(int64_t v, int hi) { return (int)(v < hi ? (v < 1 ? 1 : v) : hi); }
 
-int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st) {
+int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
+                        bool gated) {
   const float* P = b->params;
   float* mean = w.p<float>(MSIG_WS_GATE_MEAN);
   float* pre = w.p<float>(MSIG_WS_GATE_PRE);
-  float* gs = w.p<float>(MSIG_WS_GATE_S);
-  {
+  float* gs = gated ? w.p<float>(MSIG_WS_GATE_S) : nullptr;
+  if (!gated) {
+    // no gate: only the parity sums conv1's backward needs, and only when a backward may follow
+    if (msig_keeps(b)) {
+      MSIG_K("gate_eo", st);
+#define GATE_EO(CT) gate_kernel<CT, true><<<dim3(d.B, 1, fc.n), 256, 0, st>>>(b->x, nullptr, nullptr, nullptr, nullptr, nullptr, \
+                                                                   w.p<float>(MSIG_WS_GATE_EO), d.C, d.T, 0, fc)
+      switch (d.C) {
+        case 1: GATE_EO(1); break; case 2: GATE_EO(2); break; case 3: GATE_EO(3); break; case 4: GATE_EO(4); break;
+        case 5: GATE_EO(5); break; case 6: GATE_EO(6); break; case 7: GATE_EO(7); break; case 8: GATE_EO(8); break;
+        default: GATE_EO(0); break;
+      }
+#undef GATE_EO
+      MSIG_LAUNCH_CHECK();
+    }
+  } else {
     MSIG_K("gate", st);
 #define GATE(CT) gate_kernel<CT><<<dim3(d.B, 1, fc.n), 256, 0, st>>>(b->x, P + po[MSIG_P_GATE_W1], P + po[MSIG_P_GATE_W2], mean, pre, gs, \
                                                            msig_keeps(b) ? w.p<float>(MSIG_WS_GATE_EO) : nullptr, d.C, d.T, d.Cr, fc)
@@ -1311,8 +1358,8 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
       default: GATE(0); break;
     }
 #undef GATE
+    MSIG_LAUNCH_CHECK();
   }
-  MSIG_LAUNCH_CHECK();
   const int tr = b->training;                // batch statistics and the running-statistic update
   const bool keep = msig_keeps(b);            // the pooling decisions the backward routes through (training, or an eval forward kept for one)
   // ---- stage 1
@@ -1324,13 +1371,14 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     if (smem < 4 * 32 * sizeof(float)) smem = 4 * 32 * sizeof(float);
     {
       MSIG_K("conv1_fwd", st);
-#define C1F(CT) conv1_fwd_kernel<CT><<<dim3(grid, 1, fc.n), 256, smem, st>>>(b->x, P + po[MSIG_P_CONV1_W], gs, w.p<float>(MSIG_WS_Y1), \
+#define C1F(CT, G) conv1_fwd_kernel<CT, G><<<dim3(grid, 1, fc.n), 256, smem, st>>>(b->x, P + po[MSIG_P_CONV1_W], gs, w.p<float>(MSIG_WS_Y1), \
                                                              w.p<float>(MSIG_WS_BN1_PART), d.B, d.C, d.T, d.L1, tr, fc)
-      switch (d.C) {
-        case 1: C1F(1); break; case 2: C1F(2); break; case 3: C1F(3); break; case 4: C1F(4); break;
-        case 5: C1F(5); break; case 6: C1F(6); break; case 7: C1F(7); break; case 8: C1F(8); break;
-        default: C1F(0); break;
-      }
+#define C1F_ALL(G) switch (d.C) { \
+        case 1: C1F(1, G); break; case 2: C1F(2, G); break; case 3: C1F(3, G); break; case 4: C1F(4, G); break; \
+        case 5: C1F(5, G); break; case 6: C1F(6, G); break; case 7: C1F(7, G); break; case 8: C1F(8, G); break; \
+        default: C1F(0, G); break; }
+      if (gated) { C1F_ALL(true) } else { C1F_ALL(false) }
+#undef C1F_ALL
 #undef C1F
     }
     MSIG_LAUNCH_CHECK();
@@ -1359,7 +1407,8 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
   return 0;
 }
 
-int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st) {
+int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
+                        bool gated) {
   const float* P = b->params;
   float* G = b->grads;
   const PartOffsets pof = part_offsets(d);
@@ -1411,18 +1460,33 @@ int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     MSIG_LAUNCH_CHECK();
     { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 16, (double)d.B * d.L1, cstat, G + po[MSIG_P_BN1_G], G + po[MSIG_P_BN1_B], b->training, fc); }
     MSIG_LAUNCH_CHECK();
-    { MSIG_K("conv1_bwd_fin", st); conv1_bwd_fin_kernel<<<dim3(grid_fin, 1, fc.n), 256, 0, st>>>(g1w, w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], w.p<float>(MSIG_WS_GATE_S),
-                                                                                         w.p<float>(MSIG_WS_GATE_EO), b->x, part1, w.p<float>(MSIG_WS_DS), d.B, d.C, d.T, d.L1, seg, fc); }
+    {
+      MSIG_K("conv1_bwd_fin", st);
+      if (gated)
+        conv1_bwd_fin_kernel<true><<<dim3(grid_fin, 1, fc.n), 256, 0, st>>>(g1w, w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], w.p<float>(MSIG_WS_GATE_S),
+                                                                            w.p<float>(MSIG_WS_GATE_EO), b->x, part1, w.p<float>(MSIG_WS_DS), d.B, d.C, d.T, d.L1, seg, fc);
+      else
+        conv1_bwd_fin_kernel<false><<<dim3(grid_fin, 1, fc.n), 256, 0, st>>>(g1w, w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], nullptr,
+                                                                             w.p<float>(MSIG_WS_GATE_EO), b->x, part1, nullptr, d.B, d.C, d.T, d.L1, seg, fc);
+    }
     MSIG_LAUNCH_CHECK();
     if (!plan.add(part1, grid_fin, 16 * K, 0, 16 * K, G + po[MSIG_P_CONV1_W])) return MSIG_E_SHAPE;
     if (b->dx) {          // dL/dx: after conv1_bwd_fin (it reads ds), a launch of its own
       const int nchunk_dx = (d.L1 + DX_UCH - 1) / DX_UCH;
-      { MSIG_K("conv1_bwd_dx", st); conv1_bwd_dx_kernel<<<dim3(d.B * nchunk_dx, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_DP1), w.p<uint8_t>(MSIG_WS_POOLC1),
-          w.p<float>(MSIG_WS_Y1), w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], w.p<float>(MSIG_WS_GATE_S), w.p<float>(MSIG_WS_GATE_PRE),
-          P + po[MSIG_P_GATE_W1], P + po[MSIG_P_GATE_W2], w.p<float>(MSIG_WS_DS), b->dx, d.C, d.Cr, d.T, d.L1, d.P1, fc); }
+      {
+        MSIG_K("conv1_bwd_dx", st);
+        if (gated)
+          conv1_bwd_dx_kernel<true><<<dim3(d.B * nchunk_dx, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_DP1), w.p<uint8_t>(MSIG_WS_POOLC1),
+              w.p<float>(MSIG_WS_Y1), w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], w.p<float>(MSIG_WS_GATE_S), w.p<float>(MSIG_WS_GATE_PRE),
+              P + po[MSIG_P_GATE_W1], P + po[MSIG_P_GATE_W2], w.p<float>(MSIG_WS_DS), b->dx, d.C, d.Cr, d.T, d.L1, d.P1, fc);
+        else
+          conv1_bwd_dx_kernel<false><<<dim3(d.B * nchunk_dx, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_DP1), w.p<uint8_t>(MSIG_WS_POOLC1),
+              w.p<float>(MSIG_WS_Y1), w.p<float>(MSIG_WS_BN1_STAT), cstat, P + po[MSIG_P_CONV1_W], nullptr, nullptr, nullptr, nullptr, nullptr,
+              b->dx, d.C, 0, d.T, d.L1, d.P1, fc);
+      }
       MSIG_LAUNCH_CHECK();
     }
-    if (d.Cr > 0) {
+    if (gated && d.Cr > 0) {
       { MSIG_K("gate_bwd", st); gate_bwd_kernel<<<dim3(2 * d.C * d.Cr, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_DS), w.p<float>(MSIG_WS_GATE_S), w.p<float>(MSIG_WS_GATE_PRE),
                                                         w.p<float>(MSIG_WS_GATE_MEAN), P + po[MSIG_P_GATE_W2], G + po[MSIG_P_GATE_W1],
                                                         G + po[MSIG_P_GATE_W2], d.B, d.C, d.Cr, fc); }

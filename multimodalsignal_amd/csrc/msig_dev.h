@@ -281,9 +281,12 @@ struct WsPtrs {
   template <typename T> __host__ T* p(int region) const { return (T*)(base + off[region]); }
 };
 
-int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st);
+// gated = false: CnnGruModel's front end (include/msig_cg.h): conv1 on raw taps, no gate, no gate_bwd, no ds
+int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
+                        bool gated = true);
 struct ColsumPlan;
-int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st);
+int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
+                        bool gated = true);
 int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st);
 int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st);
 // cw: class weights (include/msig_cw.h), K device floats of fold slot 0 (shifted per fold like every buffer); NULL = unweighted

@@ -28,7 +28,7 @@ import torch
 from . import _lib as L
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
-from .models import CnnGruAttentionModel
+from .models import CnnGruAttentionModel, CnnGruModel
 from .trainer import Trainer
 
 warnings.filterwarnings("ignore", message="Initializing zero-element tensors is a no-op")
@@ -39,7 +39,10 @@ CLASSIFICATION_MODE = "stress_binary"
 NUM_CLASSES = 2
 MODEL_TO_USE = "cnn_gru_attention"
 CHANNELS_TO_USE = ["chest_ECG", "chest_EDA", "chest_Resp"]
-MODEL_PARAMS = {"cnn_gru_attention": {"cnn_out_channels": 32, "gru_hidden_size": 64, "gru_num_layers": 2, "dropout": 0.5}}
+# 'cnn_gru': the baseline the reference's README names (README.md:13,81) and its models.py never defines (models.CnnGruModel)
+MODEL_PARAMS = {"cnn_gru_attention": {"cnn_out_channels": 32, "gru_hidden_size": 64, "gru_num_layers": 2, "dropout": 0.5},
+                "cnn_gru": {"cnn_out_channels": 32, "gru_hidden_size": 64, "gru_num_layers": 2, "dropout": 0.5}}
+MODEL_CLASSES = {"cnn_gru_attention": CnnGruAttentionModel, "cnn_gru": CnnGruModel}
 PROCESSED_DATA_PATH = Path("./data")
 EARLY_DATA_PATH = PROCESSED_DATA_PATH / "chest_raw"
 SEED = 42
@@ -65,6 +68,15 @@ MAX_TRAIN_STREAMS = 4
 # Class-weighted CrossEntropyLoss (include/msig_cw.h): "none" (the reference's effective criterion — its use_class_weights branch
 # cannot run, trainer.py:81) or "balanced" (compute_class_weight('balanced') over each model's own training labels, trainer.py:85-89).
 CLASS_WEIGHTS = "none"
+
+
+def model_kind(cfg):
+    """cfg["model"]: the model kind of a configuration ("cnn_gru_attention" when absent)."""
+    return cfg.get("model", MODEL_TO_USE)
+
+
+def make_model(cfg, in_channels, num_classes, params):
+    return MODEL_CLASSES[model_kind(cfg)](in_channels=in_channels, num_classes=num_classes, **params)
 
 
 def trainer_class_weights(cfg):
@@ -107,7 +119,7 @@ def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_
     # setting tests/test_accuracy_parity_gpu.py compares fold by fold with the reference's CPU run); default as main.py:112
     loaders = (DeviceLoader(train_ds, cfg["batch_size"], bool(cfg.get("shuffle", True)), device, seed=fold_seed),
                DeviceLoader(val_ds, ebs, False, device), DeviceLoader(test_ds, ebs, False, device))
-    model = CnnGruAttentionModel(in_channels=len(cfg["channels"]), num_classes=cfg["num_classes"], **cfg["model_params"])
+    model = make_model(cfg, len(cfg["channels"]), cfg["num_classes"], cfg["model_params"])
     model.set_dropout_seed(fold_seed * 0x9E3779B97F4A7C15 + 12345)
     pat = cfg["patience"]
     if isinstance(pat, (list, tuple)):       # a per-fold cycle of patiences (tests: folds that stop at different epochs); an int as in main.py:66
@@ -145,10 +157,11 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
     path = Path(run_output_dir) / "cv_summary.txt"
     with open(path, "w", encoding="utf-8") as f:
         f.write("实验配置:\n")
-        for k, v in (("MODEL_TO_USE", MODEL_TO_USE), ("RUN_NAME", RUN_NAME), ("SEED", cfg["seed"]), ("CHANNELS_TO_USE", cfg["channels"]),
+        kind = model_kind(cfg)
+        for k, v in (("MODEL_TO_USE", kind), ("RUN_NAME", RUN_NAME), ("SEED", cfg["seed"]), ("CHANNELS_TO_USE", cfg["channels"]),
                      ("EPOCHS", cfg["epochs"]), ("BATCH_SIZE", cfg["batch_size"]), ("LEARNING_RATE", cfg["lr"]),
                      ("NUM_WORKERS", NUM_WORKERS), ("PATIENCE", cfg["patience"]), ("NUM_CLASSES", cfg["num_classes"]),
-                     ("MODEL_PARAMS", {MODEL_TO_USE: cfg["model_params"]})):
+                     ("MODEL_PARAMS", {kind: cfg["model_params"]})):
             f.write(f"{k}: {v}\n")
         if trainer_class_weights(cfg) is not None:                  # named only when set: summaries of unweighted runs are unchanged
             f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
@@ -185,8 +198,14 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
             pass
     warm = threading.Thread(target=_warm_imports, daemon=True)
     warm.start()
-    stores = {n: SubjectStore(c["data_path"], c["subjects"], c["channels"], all_channel_names, classification_mode=c["mode"],
-                              device=device, normalise=c.get("normalise", "host")) for n, c in cfgs.items()}
+    # one store per distinct data set: the model kinds of a comparison run read the same windows
+    stores, by_data = {}, {}
+    for n, c in cfgs.items():
+        dkey = (str(c["data_path"]), tuple(c["subjects"]), tuple(c["channels"]), c["mode"], c.get("normalise", "host"))
+        if dkey not in by_data:
+            by_data[dkey] = SubjectStore(c["data_path"], c["subjects"], c["channels"], all_channel_names, classification_mode=c["mode"],
+                                         device=device, normalise=c.get("normalise", "host"))
+        stores[n] = by_data[dkey]
     t_data = time.time() - t0
     # unit u = (fold-major, configuration-minor): neighbouring units of one fold index go to different ranks
     units = [(n, k) for k in range(max(len(c["subjects"]) for c in cfgs.values())) for n in names if k < len(cfgs[n]["subjects"])]
@@ -369,6 +388,67 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     return results, wall
 
 
+def comparison(results, kinds, channels):
+    """Attention model vs baseline, fold by fold.  results: {set name: {kind: [per-fold dicts with subject, accuracy, f1_score]}};
+    channels: {set name: channel list}.  Folds are paired by test subject (the kinds share splits, seeds and loader order).  The
+    paired difference is cnn_gru_attention - cnn_gru and the win counts are the attention model's, the baseline's and the ties,
+    whatever the order of `kinds`; std is the population std (np.std, as cv_summary.txt).  Returns a JSON-ready dict."""
+    a, b = sorted(kinds, key=list(MODEL_PARAMS).index)          # (cnn_gru_attention, cnn_gru)
+    out = {"kinds": [a, b], "difference": f"{a} - {b}", "sets": {}}
+    for name, per_kind in results.items():
+        ra = {r["subject"]: r for r in per_kind[a]}
+        rb = {r["subject"]: r for r in per_kind[b]}
+        folds = []
+        for subj in [r["subject"] for r in per_kind[a] if r["subject"] in rb]:
+            row = {"subject": subj}
+            for kind, rr in ((a, ra), (b, rb)):
+                row[kind] = {"accuracy": float(rr[subj]["accuracy"]), "f1_score": float(rr[subj]["f1_score"])}
+            row["difference"] = {m: row[a][m] - row[b][m] for m in ("accuracy", "f1_score")}
+            folds.append(row)
+        summary = {}
+        for key in (a, b, "difference"):
+            summary[key] = {}
+            for m in ("accuracy", "f1_score"):
+                v = np.array([f[key][m] for f in folds], dtype=np.float64)
+                summary[key][m] = {"mean": float(v.mean()) if v.size else float("nan"), "std": float(v.std()) if v.size else float("nan")}
+        ch = list(channels[name])
+        out["sets"][name] = {
+            "channels": ch, "gate_hidden_width": len(ch) // 4, "folds": folds, "summary": summary,
+            "attention_wins": {m: int(sum(f["difference"][m] > 0 for f in folds)) for m in ("accuracy", "f1_score")},
+            "baseline_wins": {m: int(sum(f["difference"][m] < 0 for f in folds)) for m in ("accuracy", "f1_score")},
+            "ties": {m: int(sum(f["difference"][m] == 0 for f in folds)) for m in ("accuracy", "f1_score")},
+            "n_folds": len(folds)}
+    return out
+
+
+def write_comparison(run_output_dir, cmp):
+    """comparison.json (the dict of `comparison`) and comparison.txt beside the configurations' directories."""
+    run_output_dir = Path(run_output_dir)
+    (run_output_dir / "comparison.json").write_text(json.dumps(cmp, indent=1))
+    a, b = cmp["kinds"]
+    lines = [f"模型对比 (paired LOSO folds): {a} vs {b}; difference = {cmp['difference']}", ""]
+    for name, st in cmp["sets"].items():
+        gw = st["gate_hidden_width"]
+        lines.append(f"channel set {name or 'default'}: {st['channels']} (C = {len(st['channels'])}), gate hidden width C // 4 = {gw}"
+                     + ("  -> the gate is the constant 0.5: the models differ only by that scale before BatchNorm-1" if gw == 0 else ""))
+        lines.append(f"  {'subject':<10} {a + ' acc':>24} {b + ' acc':>14} {'diff':>9}   {a + ' F1':>23} {b + ' F1':>13} {'diff':>9}")
+        for f in st["folds"]:
+            lines.append(f"  {f['subject']:<10} {f[a]['accuracy']:>24.4f} {f[b]['accuracy']:>14.4f} {f['difference']['accuracy']:>+9.4f}   "
+                         f"{f[a]['f1_score']:>23.4f} {f[b]['f1_score']:>13.4f} {f['difference']['f1_score']:>+9.4f}")
+        sm = st["summary"]
+        for key in (a, b, "difference"):
+            sg = "+" if key == "difference" else ""
+            lines.append(f"  {key:<18} accuracy {sm[key]['accuracy']['mean']:{sg}.4f} ± {sm[key]['accuracy']['std']:.4f}   "
+                         f"weighted F1 {sm[key]['f1_score']['mean']:{sg}.4f} ± {sm[key]['f1_score']['std']:.4f}")
+        for m, label in (("accuracy", "accuracy"), ("f1_score", "weighted F1")):
+            lines.append(f"  {label}: {a} wins {st['attention_wins'][m]} of {st['n_folds']} folds, {b} wins {st['baseline_wins'][m]}, "
+                         f"ties {st['ties'][m]}")
+        lines.append("")
+    path = run_output_dir / "comparison.txt"
+    path.write_text("\n".join(lines), encoding="utf-8")
+    return path
+
+
 def run_simple_experiment(run_output_dir, device, all_channel_names, cfg=None, rank=0, world=1):
     """The reference's entry point (main.py:91): one configuration, 15 folds."""
     results, wall = run_experiments(run_output_dir, device, all_channel_names, {"": cfg or default_cfg()}, rank, world)
@@ -452,7 +532,7 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
                     print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
                     break
-                model = CnnGruAttentionModel(in_channels=len(ch), num_classes=2, **par)
+                model = make_model(cfg, len(ch), 2, par)
                 model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
                 t = Trainer(model, fold_dir / f"model_{tag}", tcfg_for(k))
                 t.train(DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device))
@@ -467,6 +547,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
         path = Path(run_output_dir) / "hierarchical_summary.txt"
         with open(path, "w", encoding="utf-8") as f:
             f.write(f"M1 {m1_ch} {m1_par}\nM2 {m2_ch} {m2_par}\n")
+            if model_kind(cfg) != MODEL_TO_USE:                      # named only when not the reference's model, like CLASS_WEIGHTS
+                f.write(f"MODEL_TO_USE: {model_kind(cfg)}\n")
             if trainer_class_weights(cfg) is not None:
                 f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
             f.write("\n")
@@ -506,7 +588,7 @@ def _hierarchical_fold_batches(cfg, mine, subjects, models, tcfg_for, run_output
             if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
                 print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
                 break
-            model = CnnGruAttentionModel(in_channels=len(ch), num_classes=2, **par)
+            model = make_model(cfg, len(ch), 2, par)
             model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
             loaders = (DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device),
                        DeviceLoader(stores[tag].view([sid]), ebs, False, device))
@@ -599,7 +681,14 @@ def main(argv=None):
     ap.add_argument("--class-weights", choices=["none", "balanced"], default=CLASS_WEIGHTS,
                     help="class-weighted CrossEntropyLoss for training, validation and test losses: 'balanced' = N / (K * count_c) over "
                          "each model's own training labels (M1 and M2 separately in --hierarchical)")
+    ap.add_argument("--model", nargs="+", choices=list(MODEL_PARAMS), default=[MODEL_TO_USE],
+                    help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
+                         "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
+                         "comparison.txt / comparison.json")
     args = ap.parse_args(argv)
+    kinds = [k for k in MODEL_PARAMS if k in args.model]          # attention model first, whatever the order given
+    if len(kinds) > 1 and args.hierarchical:
+        ap.error("--hierarchical takes one --model kind (M1 and M2 are both of that kind); run the kinds as separate jobs")
 
     # Concurrent folds need their own hardware queues: with the runtime's default of 4, fifteen streams share four
     # queues and serialise (1649 -> 2914 train steps/s at 15 folds with 16 queues, tools/concurrency_probe.py).
@@ -622,7 +711,7 @@ def main(argv=None):
                verbose=args.verbose,
                concurrent_folds=args.concurrent_folds, normalise=args.normalise, eval_batch_size=args.eval_batch_size,
                lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms,
-               class_weights=args.class_weights)
+               class_weights=args.class_weights, model=kinds[0], model_params=dict(MODEL_PARAMS[kinds[0]]))
     if args.synthetic is not None:
         from .synth import CHANNELS6, make_synthetic_wesad
         if rank == 0 and not (args.synthetic / "_channel_names.txt").exists():
@@ -663,6 +752,19 @@ def main(argv=None):
             sets[name] = chans.split(",")
     if args.hierarchical:
         results, wall = run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg, rank, world)
+    elif len(kinds) > 1:
+        # one job: every (kind, set) is a configuration of its own — own fold batches and streams, shared splits and seeds
+        sets_ = sets or {"": list(cfg["channels"])}
+        for n, ch in sets_.items():
+            if len(ch) > 16:
+                ap.error(f"channel set {n!r} has {len(ch)} channels; the HIP path supports at most 16")
+        cfgs = {(f"{kd}/{n}" if n else kd): dict(cfg, channels=list(ch), model=kd, model_params=dict(MODEL_PARAMS[kd]))
+                for n, ch in sets_.items() for kd in kinds}
+        results, wall = run_experiments(run_output_dir, device, all_channel_names, cfgs, rank, world)
+        if rank == 0:
+            paired = {n: {kd: results[f"{kd}/{n}" if n else kd] for kd in kinds} for n in sets_}
+            path = write_comparison(run_output_dir, comparison(paired, kinds, sets_))
+            print(f"模型对比已保存至: {path}")
     elif sets:
         for n, ch in sets.items():
             if len(ch) > 16:

@@ -8,6 +8,10 @@ initialisers (drawn in the same order, so the same ``torch.manual_seed`` gives t
 same initial weights).  The sub-modules are parameter CONTAINERS only: all arithmetic
 runs in libmsig_hip.so on the flat parameter buffer the parameters are views of.
 There is no CPU fallback — a CPU input raises.
+
+``CnnGruModel`` is the ``cnn_gru`` baseline the reference's README compares against but
+never defines: ``CnnGruAttentionModel`` without ``channel_attention`` (include/msig_cg.h,
+DESIGN.md section 13).
 """
 from __future__ import annotations
 
@@ -116,12 +120,17 @@ class _MsigFunction(torch.autograd.Function):
         if model.embedded:
             grads = [g.clone() for g in eng.gather_grads().values()]
         else:
-            grads = [eng.param_view(i, eng.grads).clone() for i in range(L.NPARAM)]
+            grads = [g.clone() for g in eng.named_param_views(eng.grads).values()]       # the kind's tensors, in _named()'s order
         return (None, None, dx, *grads)
 
 
-class CnnGruAttentionModel(nn.Module):
+class _MsigModel(nn.Module):
+    """What CnnGruAttentionModel and CnnGruModel share: the containers, the binding to an Engine of the model's kind, autograd."""
+    kind = None
+
     def __init__(self, in_channels, num_classes, cnn_out_channels=32, gru_hidden_size=64, gru_num_layers=2, dropout=0.5):
+        if self.kind not in L.MODEL_KINDS:
+            raise TypeError(f"{type(self).__name__} has no model kind: instantiate CnnGruAttentionModel or CnnGruModel")
         super().__init__()
         if (cnn_out_channels, gru_hidden_size, gru_num_layers) not in ((32, 64, 2), (32, 32, 1)):
             raise NotImplementedError(
@@ -134,8 +143,9 @@ class CnnGruAttentionModel(nn.Module):
         if not (1 <= in_channels <= L.MAX_C and 2 <= num_classes <= L.MAX_K):
             raise ValueError(f"in_channels must be 1..{L.MAX_C} and num_classes 2..{L.MAX_K}")
         self.in_channels, self.num_classes, self.dropout_p = in_channels, num_classes, float(dropout)
-        # containers, created in the reference's order (models.py:43-71) so that the RNG stream matches
-        self.channel_attention = ChannelAttention(in_channels)
+        # containers, created in the reference's order (models.py:43-71) so that the RNG stream matches; the baseline has no gate
+        if self.kind == "cnn_gru_attention":
+            self.channel_attention = ChannelAttention(in_channels)
         self.cnn_encoder = nn.Sequential(
             nn.Conv1d(in_channels, 16, kernel_size=7, stride=2, padding=3, bias=False), nn.BatchNorm1d(16), nn.ReLU(),
             nn.MaxPool1d(kernel_size=3, stride=2, padding=1),
@@ -158,21 +168,22 @@ class CnnGruAttentionModel(nn.Module):
         eng = self._engine
         if self.embedded:
             return list(eng.small_views(eng.small_grads).values())
-        return [eng.param_view(i, eng.grads) for i in range(L.NPARAM)]
+        return list(eng.named_param_views(eng.grads).values())
 
     def engine(self) -> Engine:
         """Returns the Engine whose flat buffers the parameters are views of (re-binding after
         .to(), load_state_dict(assign=True) or anything else that replaced a parameter's storage)."""
-        plist = self._named()
+        sd_params = dict(self.named_parameters())
         dev = self.classifier[0].weight.device
         if dev.type != "cuda":
             raise RuntimeError(f"model is on {dev}: move it to the GPU (model.to('cuda')); there is no CPU fallback")
         if self._engine is None or self._engine.device != dev:
-            self._engine = (EmbeddedEngine(self.in_channels, self.num_classes, dev, self.gru_hidden_size) if self.embedded
-                            else Engine(self.in_channels, self.num_classes, dev))
+            self._engine = (EmbeddedEngine(self.in_channels, self.num_classes, dev, self.gru_hidden_size, kind=self.kind) if self.embedded
+                            else Engine(self.in_channels, self.num_classes, dev, kind=self.kind))
         eng = self._engine
-        views = list(eng.small_views().values()) if self.embedded else [eng.param_view(i) for i in range(len(plist))]
-        for p, view in zip(plist, views):
+        views = eng.small_views() if self.embedded else eng.named_param_views()
+        for k, view in views.items():                      # by key: the baseline's positions differ from the attention model's
+            p = sd_params[k]
             if p.numel() and (p.data_ptr() != view.data_ptr() or p.device != dev):
                 view.copy_(p.data)
                 p.data = view
@@ -205,7 +216,7 @@ class CnnGruAttentionModel(nn.Module):
             raise TypeError("this model takes one (B, C, T) tensor (trainer.py:135-140's list branch is for a dataset "
                             "the reference no longer ships)")
         if not x.is_cuda:
-            raise RuntimeError("CnnGruAttentionModel.forward needs a GPU tensor: the MI355X path has no CPU fallback")
+            raise RuntimeError(f"{type(self).__name__}.forward needs a GPU tensor: the MI355X path has no CPU fallback")
         self.engine()
         params = self._named()
         # an eval-mode forward keeps what a backward reads only when autograd may ask for one (decided here: inside
@@ -213,3 +224,21 @@ class CnnGruAttentionModel(nn.Module):
         keep = (not self.training and torch.is_grad_enabled()
                 and (x.requires_grad or any(p.requires_grad for p in params)))
         return _MsigFunction.apply(self, keep, x, *params)
+
+
+class CnnGruAttentionModel(_MsigModel):
+    """The reference's model (models.py:34-81): ChannelAttention -> cnn_encoder -> 2-layer bidirectional GRU -> classifier."""
+    kind = "cnn_gru_attention"
+
+
+class CnnGruModel(_MsigModel):
+    """The ``cnn_gru`` baseline of the reference's README (README.md:13,81: MODEL_TO_USE = 'cnn_gru'), which its models.py never
+    defines.  Our reading: CnnGruAttentionModel with ``channel_attention`` removed —
+
+        cnn_encoder -> permute -> GRU -> outputs[:, -1, :] -> classifier
+
+    with the same layers, configurations ((32, 64, 2) and the embedded (32, 32, 1); others raise NotImplementedError), reference
+    quirks and initialisers, drawn in the attention model's order minus the gate's two Linear layers.  Its state_dict is the
+    attention model's minus ``channel_attention.fc.0.weight`` and ``channel_attention.fc.2.weight``.  Any C in 1..16.  It runs on
+    include/msig_cg.h: conv1 on the raw taps, no gate launch, no gate backward."""
+    kind = "cnn_gru"

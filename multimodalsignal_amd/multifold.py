@@ -35,19 +35,24 @@ def _depth(model):
     return int(getattr(model, "gru_hidden_size", 64)), int(getattr(model, "gru_num_layers", 2))
 
 
+def _kind(model):
+    """Model kind of a fold: "cnn_gru_attention" or "cnn_gru" (runtime.Engine)."""
+    return getattr(model, "kind", None) or "cnn_gru_attention"
+
+
 def lockstep_compatible(preps) -> bool:
-    """Folds can share launches when they draw from one SubjectStore with one model configuration and one batch size.  Their
+    """Folds can share launches when they draw from one SubjectStore with one model kind and configuration and one batch size.  Their
     train / val sets may differ in size (WESAD subjects differ by a few windows, dataset.py:17-27): full batches run as one fold
     batch, the folds' ragged last batches as launches over the folds whose batch sizes agree (`launch_plan`).  The one-layer
     32-unit model has an arena form (padded, as runtime.EmbeddedEngine); a batch is uniform in depth — msig_batch.gru_layers is
-    one value per launch."""
+    one value per launch, and so is the kind (msig_multi has no per-slot flag: a launch runs msig_cg_*_multi or the msig_* calls)."""
     if not (1 <= len(preps) <= L.MAX_FOLDS):       # a batch of ONE fold is a fold batch too (it can be re-dealt with others later)
         return False
     tr0, va0, _ = preps[0]["loaders"]
-    d0 = _depth(preps[0]["model"])
+    d0, k0 = _depth(preps[0]["model"]), _kind(preps[0]["model"])
     for p in preps:
         tr, va, _ = p["loaders"]
-        if (_depth(p["model"]) != d0
+        if (_depth(p["model"]) != d0 or _kind(p["model"]) != k0
                 or tr.batch_size != tr0.batch_size or va.batch_size != va0.batch_size or tr.store.data_ptr() != tr0.store.data_ptr()
                 or p["model"].in_channels != preps[0]["model"].in_channels or p["model"].num_classes != preps[0]["model"].num_classes
                 or p["model"].dropout_p != preps[0]["model"].dropout_p):
@@ -83,9 +88,12 @@ class LockstepTrainer:
         hidden, layers = _depth(m0)
         if any(_depth(p["model"]) != (hidden, layers) for p in preps):
             raise ValueError("a fold batch is uniform in depth: msig_batch.gru_layers is one value per launch")
+        self.kind = _kind(m0)
+        if any(_kind(p["model"]) != self.kind for p in preps):
+            raise ValueError("a fold batch is uniform in model kind: msig_multi has no per-slot kind")
         self.embedded = layers == 1
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
-                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers)
+                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind)
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
@@ -164,6 +172,7 @@ class LockstepTrainer:
         launch are consecutive rows of the order matrix (`launch_plan`); which folds share a launch has no influence on any
         fold's numbers.  Returns per-arena loss sums (indexed by slot) — the epoch's only sync."""
         arena, lib = self.arena, L.lib()
+        train_multi = lib.msig_cg_train_step_multi if self.kind == "cnn_gru" else lib.msig_cw_train_step_multi
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][0].dataset))
         trs = [self.trainers[f] for f in act]
         loaders = [self.preps[f]["loaders"][0] for f in act]
@@ -192,8 +201,8 @@ class LockstepTrainer:
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
             self._gather(loaders[0], order, r0, i, b, m)
             _, desc = self._layout(b, True)
-            L.check(lib.msig_cw_train_step_multi(C.byref(desc), C.byref(m), self.cw, ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
-                    "msig_cw_train_step_multi")           # self.cw None: exactly msig_train_step_multi
+            L.check(train_multi(C.byref(desc), C.byref(m), self.cw, ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
+                    train_multi.__name__)           # self.cw None: exactly msig_train_step_multi (msig_cg_*: the baseline)
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
         return self.acc[:, 0].cpu().numpy()                   # the epoch's only sync
@@ -201,6 +210,7 @@ class LockstepTrainer:
     def _evaluate(self, active, which):
         """Validation pass of every active fold (loader index `which`): per fold (loss, acc, f1), in the order of `active`."""
         arena, lib = self.arena, L.lib()
+        fwd_multi = lib.msig_cg_forward_multi if self.kind == "cnn_gru" else lib.msig_cw_forward_multi
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][which].dataset))
         loaders = [self.preps[f]["loaders"][which] for f in act]
         for f in act:
@@ -220,7 +230,7 @@ class LockstepTrainer:
             m = multis[(r0, nr)]
             self._gather(loaders[0], order, r0, i, b, m)
             off, desc = self._layout(b, False)
-            L.check(lib.msig_cw_forward_multi(C.byref(desc), C.byref(m), self.cw, st), "msig_cw_forward_multi")
+            L.check(fwd_multi(C.byref(desc), C.byref(m), self.cw, st), fwd_multi.__name__)
             got = arena.across("ws", off[L.WS["PRED"]], torch.int32, b)[act[r0:r0 + nr]]      # (folds of the launch, b) copy
             for j in range(nr):
                 preds[r0 + j].append(got[j])

@@ -24,18 +24,23 @@ def _require_gpu(t: torch.Tensor, what: str):
 
 
 class Engine:
-    def __init__(self, in_channels: int, num_classes: int, device: torch.device, storage: Optional[dict] = None):
+    def __init__(self, in_channels: int, num_classes: int, device: torch.device, storage: Optional[dict] = None,
+                 kind: str = "cnn_gru_attention"):
         """`storage` (FoldArena.engine): pre-allocated flat tensors "params", "grads", "exp_avg", "exp_avg_sq", "bn_state",
-        "bn_count" and a "ws" byte region to use instead of allocating — the buffers of one arena of a fold batch."""
+        "bn_count" and a "ws" byte region to use instead of allocating — the buffers of one arena of a fold batch.  `kind`:
+        "cnn_gru_attention" (include/msig.h, msig_cw.h) or "cnn_gru", the baseline without ChannelAttention (include/msig_cg.h:
+        its layout and its calls)."""
         if not (1 <= in_channels <= L.MAX_C) or not (2 <= num_classes <= L.MAX_K):
             raise ValueError(f"unsupported in_channels={in_channels} / num_classes={num_classes}")
+        self.kind = L.check_kind(kind)
         self.C, self.K = in_channels, num_classes
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Engine needs a cuda (HIP) device")
         L.lib()
-        self.layout = L.param_layout(self.C, self.K)
-        self.shapes = L.param_shapes(self.C, self.K)
+        self.layout = L.param_layout(self.C, self.K, kind)
+        self.shapes = L.param_shapes(self.C, self.K, kind)
+        self.keys = L.param_keys(kind)          # (msig_param index, state_dict key) of the tensors this kind has
         self.n_flat = self.layout[-1]
         self._ws_region = None
         if storage is None:
@@ -76,7 +81,8 @@ class Engine:
         return flat[o:o + self._numel(i)].view(self.shapes[i])
 
     def named_param_views(self, flat: Optional[torch.Tensor] = None):
-        return {k: self.param_view(i, flat) for i, k in enumerate(L.PARAM_KEYS)}
+        """{state_dict key: view} of every parameter tensor of the model kind, in flat-buffer order."""
+        return {k: self.param_view(i, flat) for i, k in self.keys}
 
     def bn_views(self):
         s = self.bn_state
@@ -214,7 +220,9 @@ class Engine:
         (msig_cw_forward); None = the unweighted criterion."""
         cw = self._class_weight(class_weight)
         b = self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward)
-        if cw is None:
+        if self.kind == "cnn_gru":
+            L.check(L.lib().msig_cg_forward(C.byref(b), cw, self._stream()), "msig_cg_forward")
+        elif cw is None:
             L.check(L.lib().msig_forward(C.byref(b), self._stream()), "msig_forward")
         else:
             L.check(L.lib().msig_cw_forward(C.byref(b), cw, self._stream()), "msig_cw_forward")
@@ -234,7 +242,10 @@ class Engine:
                 raise ValueError(f"dx must be a contiguous float32 ({b.shape.B}, {self.C}, {b.shape.T}) tensor, got {dx.dtype} {tuple(dx.shape)}")
             b = L.Batch.from_buffer_copy(b)          # the caller's descriptor stays as its forward left it
             b.dx = dx.data_ptr()
-        L.check(L.lib().msig_backward(C.byref(b), ptr, self._stream()), "msig_backward")
+        if self.kind == "cnn_gru":
+            L.check(L.lib().msig_cg_backward(C.byref(b), ptr, self._stream()), "msig_cg_backward")
+        else:
+            L.check(L.lib().msig_backward(C.byref(b), ptr, self._stream()), "msig_backward")
 
     def ensure_adam_state(self):
         if self.exp_avg is None:
@@ -256,7 +267,10 @@ class Engine:
         cw = self._class_weight(class_weight)
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
-        if cw is None:
+        if self.kind == "cnn_gru":
+            L.check(L.lib().msig_cg_train_step(C.byref(b), cw, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
+                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_cg_train_step")
+        elif cw is None:
             L.check(L.lib().msig_train_step(C.byref(b), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
                                             betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_train_step")
         else:
@@ -272,14 +286,14 @@ class Engine:
             L.check(fn(C.byref(b), self._stream()), name)
 
 
-def embedding_index(in_channels: int, num_classes: int, hidden: int = 32):
+def embedding_index(in_channels: int, num_classes: int, hidden: int = 32, kind: str = "cnn_gru_attention"):
     """The one-layer model's embedding in the padded 64-unit flat layout (EmbeddedEngine): ([(state_dict key, reference shape)]
     in flat-buffer order, int64 CPU index) — element i of the concatenated reference-shaped parameters lives at flat[index[i]]."""
-    layout, shapes = L.param_layout(in_channels, num_classes), L.param_shapes(in_channels, num_classes)
+    layout, shapes = L.param_layout(in_channels, num_classes, kind), L.param_shapes(in_channels, num_classes, kind)
     H = hidden
     small_shapes, idx = [], []
     gate_rows = torch.cat([torch.arange(g * 64, g * 64 + H) for g in range(3)])            # rows of the real units
-    for i, k in enumerate(L.PARAM_KEYS):
+    for i, k in L.param_keys(kind):
         o, shape = layout[i], shapes[i]
         if k.startswith("gru."):
             if "_l1" in k:
@@ -316,17 +330,18 @@ class EmbeddedEngine(Engine):
     elements into the padded flat buffer.  scatter() / gather() move values between the two around every library call of a
     stand-alone model; in a fold batch's arena (FoldArena) only when a model enters, is checkpointed or is handed back."""
 
-    def __init__(self, in_channels: int, num_classes: int, device: torch.device, hidden: int, storage: Optional[dict] = None):
+    def __init__(self, in_channels: int, num_classes: int, device: torch.device, hidden: int, storage: Optional[dict] = None,
+                 kind: str = "cnn_gru_attention"):
         """`storage`: the padded buffers of one arena of a fold batch (FoldArena.engine).  The library then trains the padded layout
         in place; `small` is brought up to date (gather) and written back (scatter) only when the model's parameters are needed or
         replaced — checkpoints, evaluation, re-dealing — never per step."""
-        super().__init__(in_channels, num_classes, device, storage)
+        super().__init__(in_channels, num_classes, device, storage, kind)
         if hidden != 32:
             raise NotImplementedError("embedded GRU: hidden size 32 (main.py:38)")
         self.gru_layers = 1
         self.hidden = hidden
         dev = self.device
-        self.small_shapes, index = embedding_index(in_channels, num_classes, hidden)
+        self.small_shapes, index = embedding_index(in_channels, num_classes, hidden, kind)
         self.index = index.to(dev)
         self.padding = torch.ones(self.n_flat, dtype=torch.bool, device=dev)   # entries of the flat buffer no model parameter maps to
         self.padding[self.index] = False
@@ -383,22 +398,24 @@ class FoldArena:
     same offsets — which is all msig_*_multi needs to run the same step for several folds in one set of launches."""
 
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
-                 adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2):
+                 adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention"):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
-        launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth)."""
+        launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
+        `kind`: the model kind of every fold (Engine); it sizes the arenas from its layout.  A fold batch is uniform in kind too."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
             raise NotImplementedError(f"fold arenas hold (gru_hidden, gru_layers) = (64, 2) or (32, 1), got {(gru_hidden, gru_layers)}")
         self.gru_hidden, self.gru_layers = int(gru_hidden), int(gru_layers)
+        self.kind = L.check_kind(kind)
         eval_batch = int(eval_batch) or int(train_batch)
         self.C, self.K, self.n, self.T = in_channels, num_classes, n, T
         self.max_batch = max(int(train_batch), eval_batch)
         self.max_train_batch = int(train_batch)
         self.adaptive_forms = bool(adaptive_forms)
         self.device = torch.device(device)
-        self.n_flat = L.param_layout(in_channels, num_classes)[-1]
+        self.n_flat = L.param_layout(in_channels, num_classes, kind)[-1]
         self.ws_bytes = self.workspace_bytes(train_batch, eval_batch, in_channels, T, num_classes)
         # "cw": the fold's class-weight vector (include/msig_cw.h msig_cw_*_multi), written when a fold enters (set_class_weight)
         sizes = [("params", self.n_flat * 4), ("grads", self.n_flat * 4), ("exp_avg", self.n_flat * 4), ("exp_avg_sq", self.n_flat * 4),
@@ -441,8 +458,8 @@ class FoldArena:
         st["acc"] = self.view(slot, "acc", torch.float64)
         st["ws"] = self.view(slot, "ws")
         if self.gru_layers == 1:
-            return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st)
-        return Engine(self.C, self.K, self.device, storage=st)
+            return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st, kind=self.kind)
+        return Engine(self.C, self.K, self.device, storage=st, kind=self.kind)
 
     def ptr(self, name: str) -> int:
         return self.mem.data_ptr() + self.off[name][0]                  # arena 0's buffer
