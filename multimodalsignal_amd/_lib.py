@@ -1,4 +1,4 @@
-"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h).
+"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -80,6 +80,9 @@ MAX_FOLDS = 16
 ABI_VERSION = 5       # include/msig.h MSIG_ABI_VERSION
 CW_ABI_VERSION = 1    # include/msig_cw.h MSIG_CW_ABI_VERSION (class-weighted CrossEntropy)
 CG_ABI_VERSION = 1    # include/msig_cg.h MSIG_CG_ABI_VERSION (the cnn_gru baseline)
+FT_ABI_VERSION = 1    # include/msig_ft.h MSIG_FT_ABI_VERSION (window embeddings, classifier-only head epochs)
+FT_MAX_BATCH, FT_MAX_N = 256, 1 << 24
+FT_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_FT_KIND_*
 
 
 class Multi(C.Structure):
@@ -87,6 +90,23 @@ class Multi(C.Structure):
     _fields_ = [("n", C.c_int32), ("slot", C.c_int32 * MAX_FOLDS), ("stride_bytes", C.c_int64),
                 ("key_gru", C.c_uint32 * MAX_FOLDS), ("key_head", C.c_uint32 * MAX_FOLDS), ("lr", C.c_float * MAX_FOLDS),
                 ("form_folds", C.c_int32), ("step", C.c_int64 * MAX_FOLDS)]
+
+
+class FtHead(C.Structure):
+    """msig_ft_head (include/msig_ft.h): consecutive classifier-only train steps on cached features, one launch."""
+    _fields_ = [("K", C.c_int32), ("N", C.c_int32), ("n_order", C.c_int32), ("batch", C.c_int32), ("first_step", C.c_int32),
+                ("n_steps", C.c_int32), ("dropout_thr", C.c_int32), ("reserved", C.c_int32), ("cls_offset", C.c_int64),
+                ("step0", C.c_int64), ("seed", C.c_uint64), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("weight_decay", C.c_float), ("reserved_f", C.c_float),
+                ("feat", C.c_void_p), ("labels", C.c_void_p), ("order", C.c_void_p), ("params", C.c_void_p), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p), ("class_weight", C.c_void_p), ("loss_acc", C.c_void_p)]
+
+
+class FtMulti(C.Structure):
+    """msig_ft_multi (include/msig_ft.h): the folds of one head-epoch launch — arenas `stride_bytes` apart, per-fold learning rate,
+    first optimiser step count and dropout seed."""
+    _fields_ = [("n", C.c_int32), ("slot", C.c_int32 * MAX_FOLDS), ("reserved", C.c_int32), ("stride_bytes", C.c_int64),
+                ("lr", C.c_float * MAX_FOLDS), ("step0", C.c_int64 * MAX_FOLDS), ("seed", C.c_uint64 * MAX_FOLDS)]
 
 
 _lib = None
@@ -185,6 +205,19 @@ def lib() -> C.CDLL:
         L.msig_cg_train_step.argtypes = [C.POINTER(Batch), vp, vp, vp, f32, f32, f32, f32, f32, i64, vp]
         L.msig_cg_forward_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp]
         L.msig_cg_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), vp, vp, vp, f32, f32, f32, f32, i64, vp]
+        # include/msig_ft.h, exported by the same library: window embeddings and the classifier-only head epoch
+        L.msig_ft_abi_version.restype = C.c_int
+        L.msig_ft_struct_bytes.argtypes = [C.c_int32]
+        L.msig_ft_struct_bytes.restype = C.c_int64
+        if (L.msig_ft_abi_version() != FT_ABI_VERSION or L.msig_ft_struct_bytes(0) != C.sizeof(FtHead)
+                or L.msig_ft_struct_bytes(1) != C.sizeof(FtMulti)):
+            raise RuntimeError(f"{LIB_PATH} has msig_ft.h ABI {L.msig_ft_abi_version()} with msig_ft_head / msig_ft_multi of "
+                               f"{L.msig_ft_struct_bytes(0)} / {L.msig_ft_struct_bytes(1)} bytes; this binding is {FT_ABI_VERSION} with "
+                               f"{C.sizeof(FtHead)} / {C.sizeof(FtMulti)}: rebuild the library")
+        L.msig_ft_features.argtypes = [C.POINTER(Batch), C.c_int, vp, vp]
+        L.msig_ft_features_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.c_int, vp, C.c_int64, vp]
+        L.msig_ft_head_epoch.argtypes = [C.POINTER(FtHead), vp]
+        L.msig_ft_head_epoch_multi.argtypes = [C.POINTER(FtHead), C.POINTER(FtMulti), vp]
         _lib = L
     return _lib
 

@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, include/msig_cw.h and include/msig_cg.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, include/msig_cw.h, include/msig_cg.h and include/msig_ft.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -10,6 +10,7 @@
 #include "msig_dev.h"
 #include "../../include/msig_cw.h"
 #include "../../include/msig_cg.h"
+#include "finetune.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -422,6 +423,71 @@ extern "C" int msig_cg_train_step_multi(const msig_batch* b, const msig_multi* m
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight,
                        true);
+}
+
+// ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------
+extern "C" int msig_ft_abi_version(void) { return MSIG_FT_ABI_VERSION; }
+extern "C" int64_t msig_ft_struct_bytes(int32_t which) {
+  return which == 0 ? (int64_t)sizeof(msig_ft_head) : which == 1 ? (int64_t)sizeof(msig_ft_multi) : -1;
+}
+
+// the front end and the GRU of an eval-mode forward, no head launch, then MSIG_WS_FEAT of every fold copied out
+static int features_fc(const msig_batch* b, const FoldCtx& fc, int kind, float* out, int64_t out_stride_bytes, hipStream_t st) {
+  if (!out) return MSIG_E_NULL;
+  if (kind != MSIG_FT_KIND_ATTENTION && kind != MSIG_FT_KIND_CNN_GRU) return MSIG_E_SHAPE;
+  if (b->training) return MSIG_E_SHAPE;
+  if ((uintptr_t)out & 15) return MSIG_E_ALIGN;
+  if (fc.n > 1 && (out_stride_bytes < (int64_t)b->shape.B * 512 || (out_stride_bytes & 15))) return MSIG_E_SHAPE;
+  const bool cg = kind == MSIG_FT_KIND_CNN_GRU;
+  int rc = forward_fc(b, fc, st, false, nullptr, cg);         // every argument check of the forward before its first launch
+  if (rc) return rc;
+  Ctx c;
+  if ((rc = make_ctx(b, c, false, cg))) return rc;
+  return launch_ft_feat_copy(c.w.p<float>(MSIG_WS_FEAT), out, out_stride_bytes, c.d.B, fc, st);
+}
+extern "C" int msig_ft_features(const msig_batch* b, int kind, float* out, void* stream) {
+  if (!b) return MSIG_E_NULL;
+  return features_fc(b, single_fold(b), kind, out, 0, (hipStream_t)stream);
+}
+extern "C" int msig_ft_features_multi(const msig_batch* b, const msig_multi* m, int kind, float* out, int64_t out_stride_bytes, void* stream) {
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return features_fc(b, fc, kind, out, out_stride_bytes, (hipStream_t)stream);
+}
+
+static int check_ft_head(const msig_ft_head* h) {
+  if (!h) return MSIG_E_NULL;
+  if (!h->feat || !h->labels || !h->order || !h->params || !h->exp_avg || !h->exp_avg_sq) return MSIG_E_NULL;
+  if (h->K < 2 || h->K > MSIG_MAX_K || h->batch < 1 || h->batch > MSIG_FT_MAX_BATCH) return MSIG_E_SHAPE;
+  if (h->N < 1 || h->N > MSIG_FT_MAX_N || h->n_order < 1 || h->n_order > h->N) return MSIG_E_SHAPE;
+  if (h->first_step < 0 || h->n_steps < 1) return MSIG_E_SHAPE;
+  if ((int64_t)h->first_step + h->n_steps > ((int64_t)h->n_order + h->batch - 1) / h->batch) return MSIG_E_SHAPE;
+  if (h->dropout_thr < 0 || h->dropout_thr > 256) return MSIG_E_SHAPE;
+  if (h->cls_offset < 0 || (h->cls_offset & 3)) return MSIG_E_SHAPE;
+  if (((uintptr_t)h->feat | (uintptr_t)h->params | (uintptr_t)h->exp_avg | (uintptr_t)h->exp_avg_sq) & 15) return MSIG_E_ALIGN;
+  if (((uintptr_t)h->labels | (uintptr_t)h->loss_acc) & 7) return MSIG_E_ALIGN;
+  if (((uintptr_t)h->order | (uintptr_t)h->class_weight) & 3) return MSIG_E_ALIGN;
+  return 0;
+}
+extern "C" int msig_ft_head_epoch(const msig_ft_head* h, void* stream) {
+  int rc = check_ft_head(h); if (rc) return rc;
+  if (h->step0 < 1) return MSIG_E_SHAPE;
+  FtFolds ff{};
+  ff.n = 1; ff.lr[0] = h->lr; ff.step0[0] = h->step0; ff.seed[0] = h->seed;
+  return launch_head_epoch(*h, ff, (hipStream_t)stream);
+}
+extern "C" int msig_ft_head_epoch_multi(const msig_ft_head* h, const msig_ft_multi* m, void* stream) {
+  if (!m) return MSIG_E_NULL;
+  int rc = check_ft_head(h); if (rc) return rc;
+  if (m->n < 1 || m->n > MSIG_MAX_FOLDS) return MSIG_E_SHAPE;
+  if (m->stride_bytes <= 0 || (m->stride_bytes & 255)) return MSIG_E_ALIGN;
+  FtFolds ff{};
+  ff.n = m->n; ff.stride = m->stride_bytes;
+  for (int i = 0; i < m->n; ++i) {
+    if (m->slot[i] < 0 || m->step0[i] < 1) return MSIG_E_SHAPE;
+    for (int j = 0; j < i; ++j) if (m->slot[j] == m->slot[i]) return MSIG_E_SHAPE;        // two workgroups in one arena would race
+    ff.slot[i] = m->slot[i]; ff.lr[i] = m->lr[i]; ff.step0[i] = m->step0[i]; ff.seed[i] = m->seed[i];
+  }
+  return launch_head_epoch(*h, ff, (hipStream_t)stream);
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {

@@ -1,0 +1,303 @@
+// include/msig_ft.h: window embeddings (the copy of MSIG_WS_FEAT; the forward itself is api.hip's) and the head epoch —
+// consecutive classifier-only train steps on cached features in ONE launch (few-shot subject calibration).
+#include "msig_dev.h"
+#include "finetune.h"
+
+// ------------------------------------------------------------------------------------
+// MSIG_WS_FEAT (B,128) of fold z -> out + z * out_stride
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ft_feat_copy_kernel(const float* __restrict__ feat, float* __restrict__ out, int64_t out_stride_bytes,
+                                                           int n4, const FoldCtx fc) {
+  FOLD_BEGIN; FS(feat);
+  float4* o = (float4*)((char*)out + (int64_t)blockIdx.z * out_stride_bytes);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) o[i] = ((const float4*)feat)[i];
+}
+
+int launch_ft_feat_copy(const float* feat, float* out, int64_t out_stride_bytes, int B, const FoldCtx& fc, hipStream_t st) {
+  const int n4 = B * 32;
+  const int grid = (n4 + 255) / 256 < 256 ? (n4 + 255) / 256 : 256;
+  { MSIG_K("ft_feat_copy", st); ft_feat_copy_kernel<<<dim3(grid, 1, fc.n), 256, 0, st>>>(feat, out, out_stride_bytes, n4, fc); }
+  MSIG_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// Head epoch.  One workgroup of 256 threads per fold keeps the classifier (9.3 k floats) in LDS and both Adam moments in
+// REGISTERS for the whole call — every element of W0 / b0 / W3 / b3 has ONE owner thread, which accumulates its gradient,
+// applies Adam and writes the new value where the next step's forward reads it — so a step is barriers and LDS traffic, with no
+// global round trip but the gather of its rows:
+//   W0 (64,128): thread (kcol = tid & 127, half = tid >> 7) owns rows half * 32 + j, j < 32, of column kcol (head_bwd_kernel's
+//                accumulator map); kept TRANSPOSED in LDS, W0t[k * 65 + v], which the forward (lane = v) and the owners
+//                (lane = k, stride 65) both reach without a bank conflict;
+//   W3 (K,64)  : thread tid owns elements tid + 256 * j, j < 4;   b0: tid < 64;   b3: tid < K.
+// A step's rows run through the statements of head_fwd_kernel / ce_kernel / head_bwd_kernel in chunks of 16 rows, in batch order:
+// a weight-gradient element is the chain  acc += dps[row] * feat[row]  over the step's rows 0, 1, 2, ... — one fixed order.  The
+// loss and the class-weight total are fp64 sums in ce_kernel's / cw_total's order for a batch of <= 256 rows (lane = row, wave
+// reduction, the four wave sums in wave order).  Nothing depends on the number of steps, on the position of a step inside the
+// call or on the folds beside it.  Plain fp32 FMA, no MFMA: a step's contractions are 2 x 131 k multiply-adds per 16 rows — about
+// a microsecond on four waves — beside six barriers; the matrix pipes would shorten only that microsecond, at the price of
+// fragment shuffles through LDS for operands that are already there in the layout the VALU wants.
+// ------------------------------------------------------------------------------------
+#define FT_ROWS 16
+#define FT_W0S 65
+
+__device__ __forceinline__ double ft_powi(double b, int64_t e) {      // b^e by squaring: a function of (b, e) alone
+  double r = 1.0;
+  while (e > 0) { if (e & 1) r *= b; b *= b; e >>= 1; }
+  return r;
+}
+__device__ __forceinline__ uint32_t ft_dropout_key(uint64_t seed, uint64_t step) {      // msig_dropout_key(seed, step, 2) (api.hip)
+  const uint32_t lo = (uint32_t)(seed & 0xFFFFFFFFu), hi = (uint32_t)(seed >> 32);
+  const uint32_t a = (uint32_t)((step * 0x9E3779B9ull) & 0xFFFFFFFFull);
+  const uint32_t b = (uint32_t)((2ull * 0x7F4A7C15ull) & 0xFFFFFFFFull);
+  return fmix32(lo ^ fmix32(a + b + hi));
+}
+// torch.optim.Adam with L2-in-gradient weight decay — the arithmetic of adam_kernel (head.hip), element by element
+__device__ __forceinline__ float ft_adam(float p, float g, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
+                                         float eps, float wd) {
+  const float gr = g + wd * p;
+  m = b1 * m + (1.f - b1) * gr;
+  v = b2 * v + (1.f - b2) * gr * gr;
+  const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
+  return p - lr_over_bc1 * (m / denom);
+}
+
+template <bool CW>
+__global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, const FtFolds ff) {
+  const int fold = blockIdx.x;
+  const int64_t foff_ = (int64_t)ff.slot[fold] * ff.stride;
+  const float* feat = h.feat; const int64_t* labels = h.labels; const int32_t* order = h.order;
+  float* params = h.params; float* ea = h.exp_avg; float* eas = h.exp_avg_sq;
+  const float* cw = h.class_weight; double* lacc = h.loss_acc;
+  FS(feat); FS(labels); FS(order); FS(params); FS(ea); FS(eas); FS(cw); FS(lacc);
+  const int K = h.K;
+  float* W0 = params + h.cls_offset;
+  float* b0 = W0 + 64 * 128;
+  float* W3 = b0 + 64;
+  float* b3 = W3 + (K * 64 + 3) / 4 * 4;
+  const int64_t om = W0 - params;      // the moments' tensors sit at the same offsets
+
+  __shared__ float W0t[128 * FT_W0S];
+  __shared__ float W3s[MSIG_MAX_K * 64];
+  __shared__ float b0s[64];
+  __shared__ float b3s[MSIG_MAX_K];
+  __shared__ float cws[MSIG_MAX_K];
+  __shared__ __attribute__((aligned(16))) float fs[FT_ROWS * 128];
+  __shared__ float hs[FT_ROWS * 64];
+  __shared__ float dps[FT_ROWS * 64];
+  __shared__ float dls[FT_ROWS * MSIG_MAX_K];
+  __shared__ float lgs[FT_ROWS * MSIG_MAX_K];
+  __shared__ int idxs[MSIG_FT_MAX_BATCH];
+  __shared__ int ys[MSIG_FT_MAX_BATCH];
+  __shared__ double rowloss[MSIG_FT_MAX_BATCH];
+  __shared__ float rowok[MSIG_FT_MAX_BATCH];
+  __shared__ double red[3][4];
+
+  const int tid = threadIdx.x;
+  const int v = tid & 63, rg = tid >> 6, kcol = tid & 127, half = tid >> 7;
+  // ---- the head and its moments: global -> LDS / registers, once ----
+  float m0[32], v0[32], m3[4], v3[4];
+  float mb0 = 0.f, vb0 = 0.f, mb3 = 0.f, vb3 = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int i = (half * 32 + j) * 128 + kcol;
+    W0t[kcol * FT_W0S + half * 32 + j] = W0[i];
+    m0[j] = ea[om + i]; v0[j] = eas[om + i];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = tid + 256 * j;
+    m3[j] = 0.f; v3[j] = 0.f;
+    if (i < K * 64) { W3s[i] = W3[i]; m3[j] = (ea + om + (W3 - W0))[i]; v3[j] = (eas + om + (W3 - W0))[i]; }
+  }
+  if (tid < 64) { b0s[tid] = b0[tid]; mb0 = (ea + om + (b0 - W0))[tid]; vb0 = (eas + om + (b0 - W0))[tid]; }
+  if (tid < K) { b3s[tid] = b3[tid]; mb3 = (ea + om + (b3 - W0))[tid]; vb3 = (eas + om + (b3 - W0))[tid]; }
+  if (tid < MSIG_MAX_K) cws[tid] = (CW && tid < K) ? cw[tid] : 1.f;
+  double acc_loss = 0.0, acc_ok = 0.0;          // thread 0: loss_acc, continued in step order
+  if (tid == 0 && lacc) { acc_loss = lacc[0]; acc_ok = lacc[1]; }
+  const int thr = h.dropout_thr;
+  const float dscale = drop_scale(thr), dscale_bwd = thr > 0 ? drop_scale(thr) : 1.0f;
+  const float lr = ff.lr[fold];
+  __syncthreads();
+
+#pragma unroll 1
+  for (int s = 0; s < h.n_steps; ++s) {
+    const int pos0 = (h.first_step + s) * h.batch;
+    const int nb = min(h.batch, h.n_order - pos0);
+    const int64_t t = ff.step0[fold] + s;
+    const uint32_t key = ft_dropout_key(ff.seed[fold], (uint64_t)t);
+    // ---- the step's rows and labels; W = sum_b w[y_b] in cw_total's order ----
+    if (tid < nb) {
+      const int r = min(max(order[pos0 + tid], 0), h.N - 1);
+      idxs[tid] = r;
+      const int64_t y = labels[r];
+      ys[tid] = y < 0 ? 0 : (y > K - 1 ? K - 1 : (int)y);
+    }
+    float inv = 1.0f / (float)nb;
+    double Wt = 0.0;
+    if constexpr (CW) {
+      double sw = tid < nb ? (double)cws[ys[tid]] : 0.0;
+      sw = wave_sum_d(sw);
+      if ((tid & 63) == 0) red[2][tid >> 6] = sw;
+      __syncthreads();
+      Wt = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+      inv = 1.0f / (float)Wt;
+    }
+    // Adam's bias corrections of step t, as train_step_fc forms them on the host
+    const double bc1 = 1.0 - ft_powi((double)h.beta1, t), bc2 = 1.0 - ft_powi((double)h.beta2, t);
+    const float lr_over_bc1 = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+
+    float dW0acc[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) dW0acc[j] = 0.f;
+    float dW3acc[4] = {0.f, 0.f, 0.f, 0.f};
+    float db0acc = 0.f, db3acc = 0.f;
+    __syncthreads();                     // idxs / ys are written; the previous step's parameter update is visible
+
+#pragma unroll 1
+    for (int r0 = 0; r0 < nb; r0 += FT_ROWS) {
+      // ---- gather 16 rows of features ----
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int i4 = tid + 256 * q, rl = i4 >> 5, c4 = i4 & 31, row = r0 + rl;
+        float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row < nb) val = ((const float4*)(feat + (size_t)idxs[row] * 128))[c4];
+        ((float4*)fs)[i4] = val;
+      }
+      __syncthreads();
+      // ---- head_fwd_kernel ----
+      {
+        const float bv = b0s[v];
+        float acc[4] = {bv, bv, bv, bv};
+        for (int k = 0; k < 128; ++k) {
+          const float wv = W0t[k * FT_W0S + v];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[r] += wv * fs[(rg * 4 + r) * 128 + k];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + rg * 4 + r;
+          float hv = acc[r] > 0.f ? acc[r] : 0.f;
+          if (thr > 0) {
+            const uint32_t e = (uint32_t)row * 64u + (uint32_t)v;
+            hv *= drop_mul(drop_word(e, key), e & 3, thr, dscale);
+          }
+          hs[(rg * 4 + r) * 64 + v] = row < nb ? hv : 0.f;       // head_bwd_kernel reads hid as 0 for the rows past the batch
+        }
+      }
+      __syncthreads();
+      for (int i = tid; i < FT_ROWS * K; i += 256) {
+        const int rl = i / K, c = i - rl * K;
+        float a = b3s[c];
+        for (int vv = 0; vv < 64; ++vv) a += W3s[c * 64 + vv] * hs[rl * 64 + vv];
+        lgs[rl * MSIG_MAX_K + c] = a;
+      }
+      __syncthreads();
+      // ---- ce_kernel, the rows of this chunk ----
+      if (tid < FT_ROWS) {
+        const int row = r0 + tid;
+        if (row < nb) {
+          const float* lg = &lgs[tid * MSIG_MAX_K];
+          int am;
+          const float lse = ce_row_lse(lg, K, am);
+          const int y = ys[row];
+          const float wy = cws[y];
+          if constexpr (CW) rowloss[row] = (double)wy * (double)(lse - lg[y]);
+          else rowloss[row] = (double)(lse - lg[y]);
+          rowok[row] = (am == y) ? 1.f : 0.f;
+          for (int c = 0; c < K; ++c) {
+            const float p = expf(lg[c] - lse);
+            float dl;
+            if constexpr (CW) dl = (wy * (p - (c == y ? 1.f : 0.f))) * inv;
+            else dl = (p - (c == y ? 1.f : 0.f)) * inv;
+            dls[tid * MSIG_MAX_K + c] = dl;
+          }
+        } else {
+          for (int c = 0; c < K; ++c) dls[tid * MSIG_MAX_K + c] = 0.f;
+        }
+      }
+      __syncthreads();
+      // ---- head_bwd_kernel, without dfeat (the extractor is frozen) ----
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rl = rg * 4 + r;
+        float a = 0.f;
+        for (int c = 0; c < K; ++c) a += W3s[c * 64 + v] * dls[rl * MSIG_MAX_K + c];
+        dps[rl * 64 + v] = hs[rl * 64 + v] > 0.f ? a * dscale_bwd : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int idx = tid + 256 * j;
+        if (idx < K * 64) {
+          const int c = idx >> 6, vv = idx & 63;
+          float a = 0.f;
+#pragma unroll 4
+          for (int rl = 0; rl < FT_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + c] * hs[rl * 64 + vv];
+          dW3acc[j] += a;
+        }
+      }
+      if (tid < K) { float a = 0.f; for (int rl = 0; rl < FT_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + tid]; db3acc += a; }
+      if (tid < 64) { float a = 0.f; for (int rl = 0; rl < FT_ROWS; ++rl) a += dps[rl * 64 + tid]; db0acc += a; }
+#pragma unroll 1
+      for (int rl = 0; rl < FT_ROWS; ++rl) {
+        const float fv = fs[rl * 128 + kcol];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) dW0acc[j] += dps[rl * 64 + half * 32 + j] * fv;
+      }
+      __syncthreads();                   // the next chunk overwrites fs / hs / dps / dls
+    }
+
+    // ---- the step's loss and accuracy counter: ce_kernel's sums for a batch of <= 256 rows ----
+    {
+      double ls = tid < nb ? rowloss[tid] : 0.0, cs = tid < nb ? (double)rowok[tid] : 0.0;
+      ls = wave_sum_d(ls); cs = wave_sum_d(cs);
+      if ((tid & 63) == 0) { red[0][tid >> 6] = ls; red[1][tid >> 6] = cs; }
+    }
+    // ---- Adam, every element by its owner ----
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      float* p = &W0t[kcol * FT_W0S + half * 32 + j];
+      *p = ft_adam(*p, dW0acc[j], m0[j], v0[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int idx = tid + 256 * j;
+      if (idx < K * 64) W3s[idx] = ft_adam(W3s[idx], dW3acc[j], m3[j], v3[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+    }
+    if (tid < 64) b0s[tid] = ft_adam(b0s[tid], db0acc, mb0, vb0, lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+    if (tid < K) b3s[tid] = ft_adam(b3s[tid], db3acc, mb3, vb3, lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+    __syncthreads();
+    if (tid == 0) {
+      double ls = 0.0, cs = 0.0;
+      for (int i = 0; i < 4; ++i) { ls += red[0][i]; cs += red[1][i]; }
+      if constexpr (CW) acc_loss += ls * ((double)nb / Wt);
+      else acc_loss += ls;
+      acc_ok += cs;
+    }
+  }
+
+  // ---- write the head and its moments back, once ----
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int i = (half * 32 + j) * 128 + kcol;
+    W0[i] = W0t[kcol * FT_W0S + half * 32 + j];
+    ea[om + i] = m0[j]; eas[om + i] = v0[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = tid + 256 * j;
+    if (i < K * 64) { W3[i] = W3s[i]; (ea + om + (W3 - W0))[i] = m3[j]; (eas + om + (W3 - W0))[i] = v3[j]; }
+  }
+  if (tid < 64) { b0[tid] = b0s[tid]; (ea + om + (b0 - W0))[tid] = mb0; (eas + om + (b0 - W0))[tid] = vb0; }
+  if (tid < K) { b3[tid] = b3s[tid]; (ea + om + (b3 - W0))[tid] = mb3; (eas + om + (b3 - W0))[tid] = vb3; }
+  if (tid == 0 && lacc) { lacc[0] = acc_loss; lacc[1] = acc_ok; }
+}
+
+int launch_head_epoch(const msig_ft_head& h, const FtFolds& ff, hipStream_t st) {
+  MSIG_K("head_epoch", st);
+  if (h.class_weight) head_epoch_kernel<true><<<dim3(ff.n), 256, 0, st>>>(h, ff);
+  else head_epoch_kernel<false><<<dim3(ff.n), 256, 0, st>>>(h, ff);
+  MSIG_LAUNCH_CHECK();
+  return 0;
+}

@@ -68,16 +68,6 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   }
 }
 
-// One row of CrossEntropy: argmax and log-sum-exp of its K logits — shared by ce_kernel, head_step_kernel and the loss finalizer of
-// the fused step (colsum_adam_kernel), which must agree in every bit.
-__device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
-  float mx = lg[0]; am = 0;
-  for (int c = 1; c < K; ++c) if (lg[c] > mx) { mx = lg[c]; am = c; }
-  float se = 0.f;
-  for (int c = 0; c < K; ++c) se += expf(lg[c] - mx);
-  return mx + logf(se);
-}
-
 // Class-weighted CrossEntropy (include/msig_cw.h): W = sum_b w[y_b], the normaliser of the weighted mean, summed in fp64 in ONE
 // fixed order whatever the workgroup's size — lane j of the first 256 threads adds rows j, j + 256, ... in turn, each wave reduces
 // its lanes, the four wave sums are added in wave order — so that ce_kernel (1024 threads), every workgroup of head_step_kernel and

@@ -213,6 +213,16 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// One row of CrossEntropy: argmax and log-sum-exp of its K logits — shared by ce_kernel, head_step_kernel, the loss finalizer of
+// the fused step (colsum_adam_kernel) — which must agree in every bit — and the head epoch (finetune.hip).
+__device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
+  float mx = lg[0]; am = 0;
+  for (int c = 1; c < K; ++c) if (lg[c] > mx) { mx = lg[c]; am = c; }
+  float se = 0.f;
+  for (int c = 0; c < K; ++c) se += expf(lg[c] - mx);
+  return mx + logf(se);
+}
+
 // ---- fold batching (msig_*_multi): one launch covers several independent models ("folds" of the LOSO loop) -------------
 // Every buffer of fold f (parameters, gradients, Adam moments, BN state, workspace, input batch, labels) lives at the SAME
 // offset inside a per-fold arena, arenas are `stride` bytes apart, and blockIdx.z selects the fold: every pointer a kernel

@@ -136,6 +136,7 @@ def train_fold(prep, device):
     """The reference's per-fold body (main.py:116-125) on the current HIP stream."""
     train_loader, val_loader, test_loader = prep["loaders"]
     trainer = Trainer(prep["model"], prep["fold_dir"], prep["config"])
+    prep["trainer"] = trainer
     t0 = time.time()
     trainer.train(train_loader, val_loader)
     _, test_acc, test_f1 = trainer.evaluate(test_loader, is_test=True)
@@ -173,6 +174,63 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
         f.write(f"平均 F1 分数 (Weighted F1-score): {np.mean(f1s):.4f} ± {np.std(f1s):.4f}\n")
         f.write(f"\nLOSO wall-clock: {wall_s:.1f} s on {world} GPU(s)\n")
     return path
+
+
+def calibration_settings(cfg):
+    """The calibration settings of a configuration (--calibrate ...), as calibration.txt / calibration.json name them."""
+    from .calibrate import DEFAULT_EPOCHS, DEFAULT_GAP
+    lr = cfg.get("calibration_lr")
+    return {"windows_per_class": int(cfg.get("calibrate") or 0), "gap": int(cfg.get("calibration_gap", DEFAULT_GAP)),
+            "epochs": int(cfg.get("calibration_epochs", DEFAULT_EPOCHS)), "lr": float(cfg["lr"] if lr is None else lr),
+            "batch_size": int(cfg["batch_size"]), "weight_decay": float(cfg["weight_decay"])}
+
+
+def calibrate_units(kept, units, cfgs, device, rank=0):
+    """Few-shot subject calibration of the rank's finished folds (calibrate.HeadCalibrator): per fold the first --calibrate windows
+    per class of the TEST subject re-fit the classifier of the fold's model (the one its test pass evaluated) on frozen features; the
+    LOSO model and the calibrated head are then evaluated on the same remainder.  All folds of a configuration calibrate as one
+    fold batch — one launch per epoch (cfg["calibration_batched"] False: one launch per fold and epoch, the same bits).  The models,
+    best_model.pt, fold_result.json and the LOSO summary are untouched; each fold directory gets calibration_result.json.
+    Returns {unit: ((acc, f1) before, (acc, f1) after, (n_cal, n_eval))}."""
+    from .calibrate import HeadCalibrator, calibration_split
+    out, by_cfg = {}, {}
+    for u in sorted(kept):
+        by_cfg.setdefault(units[u][0], []).append(u)
+    for n, us in by_cfg.items():
+        cfg = cfgs[n]
+        st = calibration_settings(cfg)
+        for c0 in range(0, len(us), L.MAX_FOLDS):
+            chunk, jobs = us[c0:c0 + L.MAX_FOLDS], []
+            for u in chunk:
+                p = kept[u]
+                loader, model = p["loaders"][2], p["model"]
+                labels = np.asarray(loader.dataset.labels).astype(np.int64)
+                try:
+                    cal_idx, eval_idx = calibration_split(labels, st["windows_per_class"], st["gap"])
+                except ValueError as e:
+                    raise ValueError(f"--calibrate {st['windows_per_class']}: test subject {p['subject']}: {e}") from None
+                pos = loader.index if loader.index is not None else torch.arange(len(labels), device=device)
+                take = lambda idx: (loader.store.index_select(0, pos[torch.as_tensor(idx, device=device)]),
+                                    loader.store_y.index_select(0, pos[torch.as_tensor(idx, device=device)]))
+                (xc, yc), (xe, ye) = take(cal_idx), take(eval_idx)
+                cw = p["trainer"].class_weight if p.get("trainer") is not None else None
+                fold_seed = cfg["seed"] + p["fold"]
+                jobs.append(dict(model=model, x_cal=xc, y_cal=yc, x_eval=xe, y_eval=ye, lr=st["lr"],
+                                 seed=(model._seed ^ 0xCA11B8A7E) % (1 << 64), shuffle_seed=fold_seed + 7919,
+                                 class_weight=None if cw is None else cw.cpu().numpy()))
+            cal = HeadCalibrator(jobs, epochs=st["epochs"], batch_size=st["batch_size"], weight_decay=st["weight_decay"],
+                                 batched=bool(cfg.get("calibration_batched", True)), eval_batch=kept[chunk[0]]["loaders"][2].batch_size)
+            for u, r in zip(chunk, cal.run()):
+                p = kept[u]
+                r = dict(subject=p["subject"], settings=st, **r)
+                (p["fold_dir"] / "calibration_result.json").write_text(json.dumps(r))
+                tag = f"{n}/" if n else ""
+                print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) calibration on {r['n_cal']} windows, remainder {r['n_eval']}: "
+                      f"acc {r['before']['accuracy']:.4f} -> {r['after']['accuracy']:.4f}  f1 {r['before']['f1_score']:.4f} -> "
+                      f"{r['after']['f1_score']:.4f}", flush=True)
+                out[u] = ((r["before"]["accuracy"], r["before"]["f1_score"]), (r["after"]["accuracy"], r["after"]["f1_score"]),
+                          (float(r["n_cal"]), float(r["n_eval"])))
+    return out
 
 
 def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, world=1):
@@ -224,9 +282,15 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         print(f"[rank {rank}] {tag}fold {k} ({cfgs[n]['subjects'][k]}): acc {info['accuracy']:.4f} f1 {info['f1_score']:.4f} "
               f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
 
+    n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off, nothing below runs
+    kept = {}                                        # unit -> its prep (model, loaders), kept for the calibration after the folds
+
     def prep(u):
         n, k = units[u]
-        return prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
+        p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
+        if n_cal:
+            kept[u] = p
+        return p
 
     lockstep_done = False
     if conc > 1 and mine and cfg0.get("lockstep", True):
@@ -365,6 +429,9 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         with ThreadPoolExecutor(max_workers=min(conc, MAX_TRAIN_STREAMS)) as ex:      # beyond four streams the device falls off a cliff
             for u, info in ex.map(work, preps):
                 report(u, info)
+    cal_local = {}
+    if n_cal and kept:
+        cal_local = calibrate_units(kept, units, cfgs, device, rank)
     if cfg0.get("emulate_rank"):
         # bench.py --emulate-ranks: this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what that rank
         # executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
@@ -372,6 +439,14 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     else:
         allm = gather_fold_metrics(local, len(units), world, cfg0.get("gather_device", device))
     wall = time.time() - t0
+    cal_all = None
+    if n_cal:                 # after the LOSO wall-clock is taken: the summary's timing line is the LOSO's
+        if cfg0.get("emulate_rank"):
+            cal_all = dict(cal_local)
+        else:
+            gdev = cfg0.get("gather_device", device)
+            parts = [gather_fold_metrics({u: v[i] for u, v in cal_local.items()}, len(units), world, gdev) for i in range(3)]
+            cal_all = {u: (parts[0][u], parts[1][u], parts[2][u]) for u in parts[0]}
     warm.join()            # long done in a real run; a tiny one must not leave an import running at interpreter exit
     results = {n: [] for n in names}
     for u in sorted(allm):
@@ -385,6 +460,14 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
             print(f"交叉验证汇总结果已保存至: {path}")
             print(f"{(n + ': ') if n else ''}平均准确率 (Accuracy): {np.mean(accs):.4f} ± {np.std(accs):.4f}"
                   f" | LOSO wall-clock {wall:.1f}s on {world} GPU(s) ({len(units)} folds in this job; load + normalise + upload {t_data:.1f}s)")
+            if cal_all is not None:
+                from .calibrate import write_calibration
+                folds = [{"subject": cfgs[n]["subjects"][units[u][1]], "n_cal": int(cal_all[u][2][0]), "n_eval": int(cal_all[u][2][1]),
+                          "before": {"accuracy": cal_all[u][0][0], "f1_score": cal_all[u][0][1]},
+                          "after": {"accuracy": cal_all[u][1][0], "f1_score": cal_all[u][1][1]}}
+                         for u in sorted(cal_all) if units[u][0] == n]
+                path = write_calibration(out_dir[n], folds, calibration_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"校准结果已保存至: {path}")
     return results, wall
 
 
@@ -646,7 +729,24 @@ def default_cfg():
                 eval_batch_size=EVAL_BATCH_SIZE, class_weights=CLASS_WEIGHTS)
 
 
-def main(argv=None):
+def parse_args(ap, argv=None):
+    """parse_args plus the checks between flags that need no GPU."""
+    args = ap.parse_args(argv)
+    if args.calibrate < 0:
+        ap.error("--calibrate takes a number of windows per class (>= 1; 0 = off)")
+    if args.calibrate and (args.hierarchical or args.ablation or args.sweep):
+        ap.error("--calibrate runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
+    if not args.calibrate and (args.calibration_sequential
+                               or any(v is not None for v in (args.calibration_gap, args.calibration_epochs, args.calibration_lr))):
+        ap.error("--calibration-gap / --calibration-epochs / --calibration-lr / --calibration-sequential need --calibrate N")
+    if (args.calibration_gap is not None and args.calibration_gap < 0) or (args.calibration_epochs is not None and args.calibration_epochs < 0):
+        ap.error("--calibration-gap and --calibration-epochs must be >= 0")
+    if args.calibration_lr is not None and not args.calibration_lr > 0:
+        ap.error("--calibration-lr must be > 0")
+    return args
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", type=Path, default=None, help="directory with {sid}_X.npy/_y.npy and _channel_names.txt")
     ap.add_argument("--synthetic", type=Path, default=None, help="generate (if missing) and use a synthetic dataset here")
@@ -685,7 +785,22 @@ def main(argv=None):
                     help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
                          "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
                          "comparison.txt / comparison.json")
-    args = ap.parse_args(argv)
+    ap.add_argument("--calibrate", type=int, default=0, metavar="N",
+                    help="after each fold's test pass, few-shot subject calibration: re-fit the classifier (frozen CNN + GRU) on the first N "
+                         "windows per class of the test subject and evaluate the LOSO model and the calibrated head on the remaining "
+                         "windows; writes calibration.txt / calibration.json (0 = off; standard LOSO and --model comparison runs)")
+    ap.add_argument("--calibration-gap", type=int, default=None,
+                    help="windows dropped on either side of a calibration window (overlapping windows; default 5)")
+    ap.add_argument("--calibration-epochs", type=int, default=None, help="head epochs of the calibration (default 30)")
+    ap.add_argument("--calibration-lr", type=float, default=None, help="learning rate of the calibration (default: the run's LEARNING_RATE)")
+    ap.add_argument("--calibration-sequential", action="store_true",
+                    help="calibrate with one launch per fold and epoch instead of one per epoch for all folds of a rank (the same bits)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = parse_args(ap, argv)
     kinds = [k for k in MODEL_PARAMS if k in args.model]          # attention model first, whatever the order given
     if len(kinds) > 1 and args.hierarchical:
         ap.error("--hierarchical takes one --model kind (M1 and M2 are both of that kind); run the kinds as separate jobs")
@@ -712,6 +827,12 @@ def main(argv=None):
                concurrent_folds=args.concurrent_folds, normalise=args.normalise, eval_batch_size=args.eval_batch_size,
                lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms,
                class_weights=args.class_weights, model=kinds[0], model_params=dict(MODEL_PARAMS[kinds[0]]))
+    if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
+        cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
+        for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),
+                         ("calibration_lr", args.calibration_lr)):
+            if val is not None:
+                cfg[key] = val
     if args.synthetic is not None:
         from .synth import CHANNELS6, make_synthetic_wesad
         if rank == 0 and not (args.synthetic / "_channel_names.txt").exists():

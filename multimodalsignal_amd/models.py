@@ -211,6 +211,16 @@ class _MsigModel(nn.Module):
         self._token += 1
         return self._token
 
+    @torch.no_grad()
+    def embed(self, x):
+        """Window embeddings: the (B, 2 * gru_hidden_size) vector the classifier sees, ``outputs[:, -1, :]`` (models.py:79), of an
+        EVAL-mode forward whatever ``self.training`` is — running-statistics BatchNorm, no dropout.  No autograd graph; parameters,
+        BatchNorm buffers, the dropout step counter and ``self.training`` are untouched (msig_ft_features: front end and GRU, no
+        head launch).  What few-shot calibration caches (calibrate.HeadCalibrator) and what PCA / t-SNE plots take."""
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.embed needs a GPU tensor: the MI355X path has no CPU fallback")
+        return self.engine().features(x)
+
     def forward(self, x):
         if isinstance(x, (list, tuple)):
             raise TypeError("this model takes one (B, C, T) tensor (trainer.py:135-140's list branch is for a dataset "

@@ -277,6 +277,19 @@ class Engine:
             L.check(L.lib().msig_cw_train_step(C.byref(b), cw, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
                                                betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_cw_train_step")
 
+    def features(self, x: torch.Tensor, padded: bool = False) -> torch.Tensor:
+        """The (B, 128) vector the classifier sees, outputs[:, -1, :], of an EVAL-mode forward (running-statistics BatchNorm, no
+        dropout, BatchNorm state untouched; msig_ft_features): front end and GRU, no head launch.  The rows are the bits an eval-mode
+        forward() leaves in region('FEAT').  Leaves region() pointing at the call it pointed at before.  `padded` matters only to
+        EmbeddedEngine."""
+        last, keep = self._last, self._keep
+        b = self._batch(x, None, False, 0.0, 0, 0)
+        out = torch.empty((b.shape.B, 128), dtype=torch.float32, device=self.device)
+        L.check(L.lib().msig_ft_features(C.byref(b), L.FT_KINDS[self.kind], out.data_ptr(), self._stream()), "msig_ft_features")
+        if last is not None:
+            self._last, self._keep = last, keep
+        return out
+
     def stage(self, name: str, b: L.Batch):
         """Runs a single stage launcher by name (tests / profiling)."""
         fn = getattr(L.lib(), f"msig_{name}")
@@ -382,6 +395,15 @@ class EmbeddedEngine(Engine):
         self.scatter()
         super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight)
         self.gather()
+
+    def features(self, x, padded: bool = False):
+        """The one-layer model's real (B, 64) features: columns 0..31 (forward direction) and 64..95 (reverse) of the padded row;
+        padded=True: the (B, 128) row itself, as the padded classifier.0.weight reads it (the other columns are exactly zero)."""
+        self.scatter()
+        f = super().features(x)
+        if padded:
+            return f
+        return torch.cat([f[:, :self.hidden], f[:, 64:64 + self.hidden]], dim=1)
 
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1):
         """Un-fused use: the caller has put the model's gradients into `small_grads` (MsigAdam.step)."""
@@ -489,6 +511,19 @@ class FoldArena:
         b.gru_layers = self.gru_layers
         L.apply_forms(b)
         return b
+
+    def features(self, slots, B: int) -> torch.Tensor:
+        """Eval-mode features (msig_ft_features_multi) of the B windows that sit in the "x" buffer of every arena in `slots`, in one
+        set of launches: (len(slots), B, 128), or (len(slots), B, 64) — the real columns — for the one-layer model.  Fold z's rows are
+        the bits Engine.features gives for the same model and windows."""
+        out = torch.empty((len(slots), B, 128), dtype=torch.float32, device=self.device)
+        b, m = self.batch(B, False, 0.0, with_labels=False), self.multi(slots)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().msig_ft_features_multi(C.byref(b), C.byref(m), L.FT_KINDS[self.kind], out.data_ptr(), B * 512, st),
+                "msig_ft_features_multi")
+        if self.gru_layers == 1:
+            return torch.cat([out[:, :, :self.gru_hidden], out[:, :, 64:64 + self.gru_hidden]], dim=2)
+        return out
 
     def multi(self, slots, key_gru=None, key_head=None, lr=None, steps=None) -> L.Multi:
         m = L.Multi()
