@@ -17,9 +17,11 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import threading
 import time
 import warnings
 from datetime import datetime
+from operator import itemgetter
 from pathlib import Path
 
 import numpy as np
@@ -29,7 +31,9 @@ from . import _lib as L
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
+from .multifold import fold_result, lockstep_compatible
 from .trainer import Trainer
+from .waves import MAX_TRAIN_STREAMS, cap_waves, chunk_schedule, deal, on_streams, run_wave  # noqa: F401  (the first three: importable from here)
 
 warnings.filterwarnings("ignore", message="Initializing zero-element tensors is a no-op")
 
@@ -58,13 +62,6 @@ ALL_SUBJECTS = [f"S{i}" for i in range(2, 18) if i != 12]
 # are the same whatever the batching; only the summation order of the reported loss changes (~1e-7 relative).  One launch sequence
 # over a subject's ~270 windows instead of five is what the latency-bound B = 64 regime wants (0 = BATCH_SIZE, the reference's loaders).
 EVAL_BATCH_SIZE = 1024
-# Concurrent HIP streams per GPU.  Measured (profiles/r05_stream_sweep.log: G single-fold step loops on G streams, GPU_MAX_HW_QUEUES
-# 4 / 8 / 16 / 24): 1.04 / 1.12 / 1.19 / 1.26 ms per step with 1 / 2 / 3 / 4 streams, then 1.9-2.3 ms with FIVE whatever the queue
-# count — the command processor's four pipes each work on one queue at a time, and a stream whose next launch waits behind a
-# 200-us recurrence of another stream on the same pipe waits for all of it.  Nothing in this driver runs more than four streams of
-# training at once: four fold batches per configuration (+ a side stream for finished folds' short test passes), one per configuration
-# in a sweep, and at most four single-fold streams with --no-lockstep (round 4 ran fifteen there).
-MAX_TRAIN_STREAMS = 4
 # Class-weighted CrossEntropyLoss (include/msig_cw.h): "none" (the reference's effective criterion — its use_class_weights branch
 # cannot run, trainer.py:81) or "balanced" (compute_class_weight('balanced') over each model's own training labels, trainer.py:85-89).
 CLASS_WEIGHTS = "none"
@@ -85,66 +82,69 @@ def trainer_class_weights(cfg):
     return None if v is None or (isinstance(v, str) and v == "none") else v
 
 
-def cap_waves(waves, cap=MAX_TRAIN_STREAMS):
-    """Splits every wave (a list of fold batches that run concurrently, one stream each) into waves of at most `cap` fold batches,
-    in order: what does not fit spills into the next wave."""
-    return [wv[i:i + cap] for wv in waves for i in range(0, len(wv), cap)]
-
-
-def chunk_schedule(chunk_preps):
-    """(epoch budget, smallest patience) of a fold batch, from its own folds' trainer configurations (prepare_fold): a sweep's
-    configurations need not share cfg0's.  The folds of one batch share one budget (LockstepTrainer checks it)."""
-    tcs = [p["config"]["trainer"] for p in chunk_preps]
-    return max(int(t["epochs"]) for t in tcs), min(int(t["early_stopping"]["patience"]) for t in tcs)
-
-
-def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
-    """Everything of one fold that touches global state (RNG seeding, model initialisation, host data):
-    done sequentially in the main thread so that concurrent folds stay deterministic."""
-    fold_dir = Path(run_output_dir) / f"fold_test_on_{subject_to_test}"
-    fold_dir.mkdir(parents=True, exist_ok=True)
-    train_subjects, val_subjects = split_train_val(cfg["subjects"], subject_to_test, cfg["seed"])
-    if isinstance(cache, SubjectStore):       # one HBM-resident store for the whole run: datasets are index subsets
-        mk = cache.view
-    else:
-        mk = lambda subj: WesadDataset(cfg["data_path"], subj, cfg["channels"], all_channel_names,
-                                       classification_mode=cfg["mode"], cache=cache)
-    train_ds, val_ds, test_ds = mk(train_subjects), mk(val_subjects), mk([subject_to_test])
-    fold_seed = cfg["seed"] + fold_idx
-    torch.manual_seed(fold_seed)
-    # Evaluation runs in eval mode (running BN statistics, no dropout), so its predictions do not depend on how the
-    # windows are batched; only the summation order of the reported loss does (~1e-7 relative).
-    ebs = int(cfg.get("eval_batch_size") or cfg["batch_size"])
-    # cfg["shuffle"] = False: training batches in dataset order (with dropout 0 the run is deterministic up to rounding — the
-    # setting tests/test_accuracy_parity_gpu.py compares fold by fold with the reference's CPU run); default as main.py:112
-    loaders = (DeviceLoader(train_ds, cfg["batch_size"], bool(cfg.get("shuffle", True)), device, seed=fold_seed),
-               DeviceLoader(val_ds, ebs, False, device), DeviceLoader(test_ds, ebs, False, device))
-    model = make_model(cfg, len(cfg["channels"]), cfg["num_classes"], cfg["model_params"])
-    model.set_dropout_seed(fold_seed * 0x9E3779B97F4A7C15 + 12345)
+def trainer_config(cfg, fold_idx):
+    """config['trainer'] of the Trainer of fold `fold_idx` (main.py:60-67), every experiment's."""
     pat = cfg["patience"]
     if isinstance(pat, (list, tuple)):       # a per-fold cycle of patiences (tests: folds that stop at different epochs); an int as in main.py:66
         pat = int(pat[fold_idx % len(pat)])
-    config_dict = {"trainer": {"epochs": cfg["epochs"], "learning_rate": cfg["lr"],
-                               "early_stopping": {"enabled": True, "patience": pat, "delta": 0},
-                               "weight_decay": cfg["weight_decay"], "verbose": cfg["verbose"]}}
-    if trainer_class_weights(cfg) is not None:
-        config_dict["trainer"]["class_weights"] = trainer_class_weights(cfg)
-    return dict(fold=fold_idx, subject=subject_to_test, fold_dir=fold_dir, loaders=loaders, model=model, config=config_dict)
+    tc = {"trainer": {"epochs": cfg["epochs"], "learning_rate": cfg["lr"],
+                      "early_stopping": {"enabled": True, "patience": pat, "delta": 0},
+                      "weight_decay": cfg["weight_decay"], "verbose": cfg.get("verbose", False)}}
+    if trainer_class_weights(cfg) is not None:      # each model's from its own training labels (M1's stress_binary, M2's amusement_binary)
+        tc["trainer"]["class_weights"] = trainer_class_weights(cfg)
+    return tc
+
+
+def host_datasets(cfg, all_channel_names, cache, channels, mode):
+    """The dataset factory over host arrays: subjects -> WesadDataset (`cache`: one dict shared by the datasets of a run)."""
+    return lambda subjects: WesadDataset(cfg["data_path"], subjects, channels, all_channel_names, classification_mode=mode, cache=cache)
+
+
+def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, params, seed, cfg, device, shuffle=True, test_pass=True,
+              skip_empty=False):
+    """One training unit — a fold's model with its loaders and trainer configuration — as the `prep` dict train_fold and
+    multifold.LockstepTrainer consume.  Everything of a unit that touches global state (RNG seeding, model initialisation, host
+    data) happens here: the drivers call it sequentially, in the main thread, so that concurrent units stay deterministic.
+    `datasets(subjects)` is the dataset factory (host_datasets, or SubjectStore.view: index subsets of one HBM-resident store);
+    `seed` seeds torch for the model's initialisation, the model's dropout stream and the training loader's shuffler.
+    test_pass False: whoever trains the unit leaves the test subject to the caller.  skip_empty: None for a unit whose training
+    or validation set is empty (main.py:187-189)."""
+    train_subjects, val_subjects = split_train_val(cfg["subjects"], subject, cfg["seed"])
+    train_ds, val_ds = datasets(train_subjects), datasets(val_subjects)
+    if skip_empty and (len(train_ds) == 0 or len(val_ds) == 0):
+        return None
+    fold_dir.mkdir(parents=True, exist_ok=True)
+    torch.manual_seed(seed)
+    # Evaluation runs in eval mode (running BN statistics, no dropout), so its predictions do not depend on how the
+    # windows are batched; only the summation order of the reported loss does (~1e-7 relative).
+    ebs = int(cfg.get("eval_batch_size") or cfg["batch_size"])
+    loaders = (DeviceLoader(train_ds, cfg["batch_size"], shuffle, device, seed=seed),
+               DeviceLoader(val_ds, ebs, False, device), DeviceLoader(datasets([subject]), ebs, False, device))
+    model = make_model(cfg, in_channels, num_classes, params)
+    model.set_dropout_seed(seed * 0x9E3779B97F4A7C15 + 12345)
+    return dict(fold=fold_idx, subject=subject, fold_dir=fold_dir, loaders=loaders, model=model, config=trainer_config(cfg, fold_idx),
+                test_pass=test_pass)
+
+
+def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
+    """The unit of fold `fold_idx` of the simple experiment (make_unit): seed SEED + fold index, `cache` a SubjectStore (one
+    HBM-resident store for the whole run) or the host cache of WesadDataset."""
+    datasets = cache.view if isinstance(cache, SubjectStore) else host_datasets(cfg, all_channel_names, cache, cfg["channels"], cfg["mode"])
+    # cfg["shuffle"] = False: training batches in dataset order (with dropout 0 the run is deterministic up to rounding — the
+    # setting tests/test_accuracy_parity_gpu.py compares fold by fold with the reference's CPU run); default as main.py:112
+    return make_unit(fold_idx, subject_to_test, Path(run_output_dir) / f"fold_test_on_{subject_to_test}", datasets, len(cfg["channels"]),
+                     cfg["num_classes"], cfg["model_params"], cfg["seed"] + fold_idx, cfg, device, shuffle=bool(cfg.get("shuffle", True)))
 
 
 def train_fold(prep, device):
-    """The reference's per-fold body (main.py:116-125) on the current HIP stream."""
+    """The reference's per-fold body (main.py:116-125) on the current HIP stream.  prep["test_pass"] False: no test pass — the
+    caller evaluates the trained model itself (run_hierarchical_experiment)."""
     train_loader, val_loader, test_loader = prep["loaders"]
-    trainer = Trainer(prep["model"], prep["fold_dir"], prep["config"])
-    prep["trainer"] = trainer
+    trainer = prep["trainer"] = Trainer(prep["model"], prep["fold_dir"], prep["config"])
     t0 = time.time()
     trainer.train(train_loader, val_loader)
-    _, test_acc, test_f1 = trainer.evaluate(test_loader, is_test=True)
-    info = dict(subject=prep["subject"], accuracy=test_acc, f1_score=test_f1, seconds=time.time() - t0,
-                epochs=len(trainer.history), train_windows_per_s=trainer.train_windows / max(trainer.train_seconds, 1e-9),
-                history=trainer.history)
-    (prep["fold_dir"] / "fold_result.json").write_text(json.dumps(info))      # survives a crash of another fold
-    return info
+    acc, f1 = trainer.evaluate(test_loader, is_test=True)[1:] if prep.get("test_pass", True) else (None, None)
+    return fold_result(prep, trainer, acc, f1, time.time() - t0)
 
 
 def run_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
@@ -233,30 +233,17 @@ def calibrate_units(kept, units, cfgs, device, rank=0):
     return out
 
 
-def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, world=1):
-    """Runs the LOSO loop of every configuration in `cfgs` ({name: cfg}) as ONE sharded job: the work units
-    are (configuration, fold) pairs — 15 for a plain run, 4 x 15 = 60 for the channel-ablation sweep — dealt
-    round-robin to the ranks and trained concurrently within a rank.  A configuration named "" writes into
-    `run_output_dir` itself, any other into `run_output_dir/<name>`.  Returns {name: results}, wall seconds."""
-    names = list(cfgs)
-    cfg0 = cfgs[names[0]]
-    t0 = time.time()
-    # matplotlib (the confusion-matrix plots) costs ~0.4 s of interpreter time the first time it is imported: started here on a
-    # thread, it runs while this thread reads and normalises the subjects' files (numpy, mostly outside the interpreter lock)
-    # instead of in front of the first fold's test pass.  (Round 3 also warmed torch._dynamo here, which torch.optim's first
-    # Optimizer pulled in — 0.9 s that still ended up in front of the first train step; trainer.MsigAdam no longer triggers it.)
-    import threading
+def _warm_imports():
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot  # noqa: F401
+    except Exception:
+        pass
 
-    def _warm_imports():
-        try:
-            import matplotlib
-            matplotlib.use("Agg")
-            import matplotlib.pyplot  # noqa: F401
-        except Exception:
-            pass
-    warm = threading.Thread(target=_warm_imports, daemon=True)
-    warm.start()
-    # one store per distinct data set: the model kinds of a comparison run read the same windows
+
+def subject_stores(cfgs, all_channel_names, device):
+    """{configuration name: SubjectStore}, one store per distinct data set: the model kinds of a comparison run read the same windows."""
     stores, by_data = {}, {}
     for n, c in cfgs.items():
         dkey = (str(c["data_path"]), tuple(c["subjects"]), tuple(c["channels"]), c["mode"], c.get("normalise", "host"))
@@ -264,210 +251,125 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
             by_data[dkey] = SubjectStore(c["data_path"], c["subjects"], c["channels"], all_channel_names, classification_mode=c["mode"],
                                          device=device, normalise=c.get("normalise", "host"))
         stores[n] = by_data[dkey]
-    t_data = time.time() - t0
-    # unit u = (fold-major, configuration-minor): neighbouring units of one fold index go to different ranks
+    return stores
+
+
+def rank_units(cfgs, world, rank):
+    """The work units of a job — (configuration, fold) pairs, numbered fold-major, configuration-minor, so that neighbouring units of
+    one fold index go to different ranks — with this rank's share of them (unit numbers, dealt round-robin) and that share grouped
+    by configuration (in order of first appearance).  Returns units, mine, groups."""
+    names, cfg0 = list(cfgs), next(iter(cfgs.values()))
     units = [(n, k) for k in range(max(len(c["subjects"]) for c in cfgs.values())) for n in names if k < len(cfgs[n]["subjects"])]
     mine = folds_for_rank(len(units), world, rank)
     if cfg0.get("only_subjects"):       # a subset of the LOSO's folds (tests: the splits stay those of the full subject list)
         keep = set(cfg0["only_subjects"])
         mine = [u for u in mine if cfgs[units[u][0]]["subjects"][units[u][1]] in keep]
+    groups = {}
+    for u in mine:
+        groups.setdefault(units[u][0], []).append(u)
+    return units, mine, list(groups.values())
+
+
+def train_units(mine, groups, make, cfg0, device):
+    """Trains the units `mine` of a rank (`groups`: the same units by configuration; make(unit): its prep, see prepare_fold) in
+    one of three modes and yields (unit, result dict): sequentially (concurrent_folds 1; a unit is yielded when it finishes), as
+    fold batches (the units of a wave when the wave has finished, in batch order then position order), or — with --no-lockstep, or
+    for units that cannot share launches — as single folds on concurrent streams (all units, in order, when the last has finished)."""
     conc = max(1, min(int(cfg0.get("concurrent_folds", 1)), len(mine)))
-    out_dir = {n: (Path(run_output_dir) / n if n else Path(run_output_dir)) for n in names}
-    local = {}
+    if conc == 1:
+        for u in mine:                                   # a unit is made immediately before it trains: one unit's loaders at a time
+            yield u, train_fold(make(u), device)
+        return
+    preps = {u: make(u) for u in mine}                   # sequential: seeding / initialisation order as in every other mode
+    torch.cuda.synchronize(device)                       # uploads were issued on this thread's stream
+    # Folds of one configuration advance in LOCKSTEP as one fold batch: every launch of the step covers all of them
+    # (multifold.LockstepTrainer, msig_*_multi) — at B = 64 fifteen streams are bound by the command processor, one set of
+    # launches is not.  The folds' splits may differ in size (real WESAD): full batches share launches, ragged last batches
+    # run over the folds whose batch sizes agree.  At most `concurrent_folds` folds are resident at a time (waves.deal).
+    waves = deal(groups, mine, conc, cfg0.get("lockstep_groups", 4), sweep=len(groups) > 1) if cfg0.get("lockstep", True) else []
+    if waves and all(lockstep_compatible([preps[u] for u in ch]) for wv in waves for ch in wv):
+        t_start = time.time()
+        for wv in waves:
+            yield from run_wave(wv, preps, device, bool(cfg0.get("adaptive_forms", False)), t_start)
+        return
+    # At the reference's batch size (64) one fold keeps ~2 % of an MI355X busy (4 batch tiles of a strictly
+    # sequential recurrence), so the rank's units run concurrently, each on its own HIP stream.  Seeding,
+    # model initialisation and host-side data preparation stay sequential (deterministic); only the
+    # training loops overlap (libmsig_hip.so is re-entrant across streams; ctypes releases the GIL).
+    # Beyond four streams the device falls off a cliff (MAX_TRAIN_STREAMS).
+    yield from zip(mine, on_streams(lambda u: train_fold(preps[u], device), mine, device, workers=min(conc, MAX_TRAIN_STREAMS)))
 
-    def report(u, info):
-        n, k = units[u]
-        local[u] = (info["accuracy"], info["f1_score"])
-        tag = f"{n}/" if n else ""
-        print(f"[rank {rank}] {tag}fold {k} ({cfgs[n]['subjects'][k]}): acc {info['accuracy']:.4f} f1 {info['f1_score']:.4f} "
-              f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
 
-    n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off, nothing below runs
-    kept = {}                                        # unit -> its prep (model, loaders), kept for the calibration after the folds
+def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data):
+    """cv_summary.txt — and calibration.txt / calibration.json after --calibrate — of every configuration of a job."""
+    for n in cfgs:
+        out_dir[n].mkdir(parents=True, exist_ok=True)
+        path = write_summary(out_dir[n], results[n], cfgs[n], wall, world)
+        accs = [r["accuracy"] for r in results[n]]
+        print(f"交叉验证汇总结果已保存至: {path}")
+        print(f"{(n + ': ') if n else ''}平均准确率 (Accuracy): {np.mean(accs):.4f} ± {np.std(accs):.4f}"
+              f" | LOSO wall-clock {wall:.1f}s on {world} GPU(s) ({len(units)} folds in this job; load + normalise + upload {t_data:.1f}s)")
+        if cal_all is not None:
+            from .calibrate import write_calibration
+            folds = [{"subject": cfgs[n]["subjects"][units[u][1]], "n_cal": int(cal_all[u][2][0]), "n_eval": int(cal_all[u][2][1]),
+                      "before": {"accuracy": cal_all[u][0][0], "f1_score": cal_all[u][0][1]},
+                      "after": {"accuracy": cal_all[u][1][0], "f1_score": cal_all[u][1][1]}}
+                     for u in sorted(cal_all) if units[u][0] == n]
+            path = write_calibration(out_dir[n], folds, calibration_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
+            print(f"校准结果已保存至: {path}")
 
-    def prep(u):
+
+def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, world=1):
+    """Runs the LOSO loop of every configuration in `cfgs` ({name: cfg}) as ONE sharded job: the work units
+    are (configuration, fold) pairs — 15 for a plain run, 4 x 15 = 60 for the channel-ablation sweep — dealt
+    round-robin to the ranks and trained concurrently within a rank.  A configuration named "" writes into
+    `run_output_dir` itself, any other into `run_output_dir/<name>`.  Returns {name: results}, wall seconds."""
+    cfg0 = next(iter(cfgs.values()))
+    t0 = time.time()
+    # matplotlib (the confusion-matrix plots) costs ~0.4 s of interpreter time the first time it is imported: started here on a
+    # thread, it runs while this thread reads and normalises the subjects' files (numpy, mostly outside the interpreter lock)
+    # instead of in front of the first fold's test pass.  (Round 3 also warmed torch._dynamo here, which torch.optim's first
+    # Optimizer pulled in — 0.9 s that still ended up in front of the first train step; trainer.MsigAdam no longer triggers it.)
+    warm = threading.Thread(target=_warm_imports, daemon=True)
+    warm.start()
+    stores = subject_stores(cfgs, all_channel_names, device)
+    t_data = time.time() - t0
+    units, mine, groups = rank_units(cfgs, world, rank)
+    out_dir = {n: (Path(run_output_dir) / n if n else Path(run_output_dir)) for n in cfgs}
+    n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off
+    kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration after the folds; -> its metrics
+
+    def make(u):
         n, k = units[u]
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
         if n_cal:
             kept[u] = p
         return p
 
-    lockstep_done = False
-    if conc > 1 and mine and cfg0.get("lockstep", True):
-        # Folds of one configuration advance in LOCKSTEP as one fold batch: every launch of the step covers all of them
-        # (multifold.LockstepTrainer, msig_*_multi) — at B = 64 fifteen streams are bound by the command processor, one set of
-        # launches is not.  The folds' splits may differ in size (real WESAD): full batches share launches, ragged last batches
-        # run over the folds whose batch sizes agree.  At most `concurrent_folds` folds are resident at a time.
-        from .multifold import LockstepTrainer, lockstep_compatible
-        groups = {}
-        for u in mine:
-            groups.setdefault(units[u][0], []).append(u)
-        # Each configuration's folds are dealt round-robin into `lockstep_groups` fold batches (default 4), each advancing in
-        # lockstep on its own HIP stream: one batch of 15 is bound by the latency of its ~30 dependent launches per step
-        # (2.1 ms at 15 folds, 0.96 ms at one) and runs as many epochs as its slowest fold; several smaller batches overlap
-        # each other's latency (and each other's per-epoch host work and sync), let early finishers free their share sooner and
-        # — what decides the wall-clock — keep the few folds that train longest in SMALL batches: a step costs 0.96 + 0.11 ms per
-        # further fold of its batch, and which folds stop late is not known when they are dealt.  As many batches as the command
-        # processor has pipes (MAX_TRAIN_STREAMS = 4).  Round 5, bench LOSO, the same 558 fold-epochs: 7.44 s with 1 batch, 7.03 with
-        # 2, 7.06-7.12 with 3 (round 2-4's default: its deal puts the folds of 76, 70 and 59 epochs into one batch), 6.59-6.69 with 4
-        # (profiles/r05_loso_groups.log) — the short test pass of a finished fold on the side stream is a fifth stream for a few
-        # milliseconds and is inside those numbers.
-        ng = max(1, int(cfg0.get("lockstep_groups", 4)))
-        adaptive = bool(cfg0.get("adaptive_forms", False))
-        preps = {u: prep(u) for u in mine}               # sequential: seeding / initialisation order as in every other mode
-        waves = []                                       # lists of chunks; the chunks of a wave run concurrently, waves one after another
-        glist = list(groups.values())
-        if len(glist) > 1:
-            # A sweep (channel ablation: 4 configurations x 15 folds): the configurations' fold batches run CONCURRENTLY, one
-            # stream each, at most MAX_TRAIN_STREAMS at a time — round 4 ran them as sequential waves of three streams, each wave
-            # ending in a multi-second tail with one or two folds left on an otherwise idle GPU.
-            waves.append([g[i:i + 16] for g in glist for i in range(0, len(g), 16)])
-        else:
-            for g in glist:
-                for w0 in range(0, len(g), conc):
-                    gw = g[w0:w0 + conc]
-                    k = min(ng, max(1, len(gw) // 2), MAX_TRAIN_STREAMS)
-                    parts = [gw[i::k] for i in range(k)]
-                    waves.append([part[i:i + 16] for part in parts for i in range(0, len(part), 16)])
-        waves = cap_waves(waves)                         # never more than MAX_TRAIN_STREAMS training streams at once
-        chunk_preps = [[[(u, preps[u]) for u in ch] for ch in wv] for wv in waves]
-        if all(lockstep_compatible([p for _, p in ch]) for wv in chunk_preps for ch in wv):
-            torch.cuda.synchronize(device)
-            t_lock0 = time.time()
-
-            streams = {}                                          # one HIP stream per fold-batch position, reused across rounds
-
-            def work(args):
-                ch, epoch0, n_ep, pos_ = args
-                torch.cuda.set_device(device)
-                if pos_ not in streams:
-                    streams[pos_] = torch.cuda.Stream(device)
-                with torch.cuda.stream(streams[pos_]):
-                    lt = LockstepTrainer([p for _, p in ch], device, adaptive_forms=adaptive)
-                    if n_ep > 0:
-                        done, alive = lt.run(epoch0=epoch0, max_epochs=n_ep, t_start=t_lock0)
-                    else:                                  # a budget of 0 epochs: every fold goes straight to its test pass
-                        done, alive = dict(enumerate(lt.run(t_start=t_lock0))), []
-                    torch.cuda.current_stream(device).synchronize()
-                return ch, done, alive, lt
-
-            from concurrent.futures import ThreadPoolExecutor
-
-            def run_round(chunks, epoch0, n_ep):
-                """One round: every chunk (fold batch) trains epochs epoch0 .. epoch0 + n_ep - 1 on its own stream (`n_ep` one
-                count for all chunks, or one per chunk).  Returns the units still training (with their preps, which now carry their
-                Trainer) — and keeps the finished batches' arenas alive until the survivors have been re-dealt (their state is
-                copied out of them)."""
-                n_eps = list(n_ep) if isinstance(n_ep, (list, tuple)) else [n_ep] * len(chunks)
-                jobs = [(ch, epoch0, n_eps[i], i) for i, ch in enumerate(chunks)]
-                if len(jobs) == 1:
-                    res = [work(jobs[0])]
-                else:
-                    with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
-                        res = list(ex.map(work, jobs))
-                alive_units = []
-                for ch, done, alive, lt in res:
-                    for pos, info in done.items():
-                        report(ch[pos][0], info)
-                    alive_units += [ch[pos] for pos in alive]
-                return sorted(alive_units, key=lambda up: up[0]), res
-
-            # Re-dealing the surviving folds evenly over the fold batches between rounds — after the first patience + 1 epochs (0) or every n
-            # epochs (n) — is BUILT AND OFF (-1, the default): measured on the bench's LOSO (same 558 fold-epochs, same box, profiles/
-            # r05_loso_redeal.log) never: 7.30 / 7.23 s, once: 7.41 / 7.37 s, every 16 / 8 epochs: 7.47 / 7.5-7.7 s.  The run is bound by its
-            # longest fold's serial chain wherever that fold sits; evening out the batches slows the short folds' batches down and the
-            # round boundaries (the batches wait for each other, arenas are rebuilt) cost more than the balance returns.
-            redeal = int(cfg0.get("redeal_every", -1))
-            for wv in chunk_preps:
-                sched = [chunk_schedule([p for _, p in ch]) for ch in wv]     # each fold batch's budget from its own trainers
-                if redeal < 0 or len(names) > 1:
-                    alive_units, _ = run_round(wv, 0, [b_ for b_, _ in sched])   # sweeps: one fold batch per configuration, run to the end
-                    assert not alive_units, "a fold batch ended its epoch budget with folds still training"
-                    continue
-                budget = max(b_ for b_, _ in sched)
-                first_round = min(p_ for _, p_ in sched) + 1              # no fold can stop before patience + 1 epochs
-                # Rounds.  Early stopping thins the fold batches unevenly — the batch that happens to hold the long folds bounds
-                # the run (round 4 / first half of round 5: 6.67 s against 6.08 s for its neighbour) — so after the first
-                # patience + 1 epochs, and then every `redeal_every`, the folds still training are dealt evenly over the batches
-                # again (at most `lockstep_groups`, never more than one batch per fold).  A fold's numbers do not depend on its
-                # companions, so this changes nothing but the wall-clock.
-                alive_units, keep = run_round(wv, 0, min(first_round, budget))
-                epoch0 = min(first_round, budget)
-                while alive_units and epoch0 < budget:
-                    k = max(1, min(ng, len(alive_units), MAX_TRAIN_STREAMS))
-                    chunks = [alive_units[i::k] for i in range(k)]
-                    n_ep = min(redeal, budget - epoch0) if redeal > 0 else budget - epoch0
-                    alive_units, keep2 = run_round(chunks, epoch0, n_ep)
-                    epoch0 += n_ep
-                    keep = keep2                                      # the previous round's arenas may go now
-                del keep
-            lockstep_done = True
-        else:
-            del preps, chunk_preps
-    if lockstep_done:
-        pass
-    elif conc == 1:
-        for u in mine:
-            report(u, train_fold(prep(u), device))
-    elif mine:
-        # At the reference's batch size (64) one fold keeps ~2 % of an MI355X busy (4 batch tiles of a strictly
-        # sequential recurrence), so the rank's units run concurrently, each on its own HIP stream.  Seeding,
-        # model initialisation and host-side data preparation stay sequential (deterministic); only the
-        # training loops overlap (libmsig_hip.so is re-entrant across streams; ctypes releases the GIL).
-        from concurrent.futures import ThreadPoolExecutor
-        preps = [(u, prep(u)) for u in mine]
-        torch.cuda.synchronize(device)      # uploads were issued on this thread's stream
-
-        def work(item):
-            u, p = item
-            torch.cuda.set_device(device)
-            with torch.cuda.stream(torch.cuda.Stream(device)):
-                info = train_fold(p, device)
-                torch.cuda.current_stream(device).synchronize()
-            return u, info
-
-        with ThreadPoolExecutor(max_workers=min(conc, MAX_TRAIN_STREAMS)) as ex:      # beyond four streams the device falls off a cliff
-            for u, info in ex.map(work, preps):
-                report(u, info)
-    cal_local = {}
-    if n_cal and kept:
-        cal_local = calibrate_units(kept, units, cfgs, device, rank)
-    if cfg0.get("emulate_rank"):
-        # bench.py --emulate-ranks: this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what that rank
-        # executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
-        allm = dict(local)
-    else:
-        allm = gather_fold_metrics(local, len(units), world, cfg0.get("gather_device", device))
+    for u, info in train_units(mine, groups, make, cfg0, device):
+        n, k = units[u]
+        local[u] = (info["accuracy"], info["f1_score"])
+        print(f"[rank {rank}] {n + '/' if n else ''}fold {k} ({cfgs[n]['subjects'][k]}): acc {info['accuracy']:.4f} f1 {info['f1_score']:.4f} "
+              f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
+    cal_local = calibrate_units(kept, units, cfgs, device, rank) if n_cal and kept else {}
+    # emulate_rank (bench.py --emulate-ranks): this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what
+    # that rank executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
+    emulate, gdev = cfg0.get("emulate_rank"), cfg0.get("gather_device", device)
+    allm = dict(local) if emulate else gather_fold_metrics(local, len(units), world, gdev)
     wall = time.time() - t0
     cal_all = None
-    if n_cal:                 # after the LOSO wall-clock is taken: the summary's timing line is the LOSO's
-        if cfg0.get("emulate_rank"):
-            cal_all = dict(cal_local)
-        else:
-            gdev = cfg0.get("gather_device", device)
-            parts = [gather_fold_metrics({u: v[i] for u, v in cal_local.items()}, len(units), world, gdev) for i in range(3)]
-            cal_all = {u: (parts[0][u], parts[1][u], parts[2][u]) for u in parts[0]}
+    if n_cal and emulate:     # after the LOSO wall-clock is taken: the summary's timing line is the LOSO's
+        cal_all = dict(cal_local)
+    elif n_cal:
+        parts = [gather_fold_metrics({u: v[i] for u, v in cal_local.items()}, len(units), world, gdev) for i in range(3)]
+        cal_all = {u: (parts[0][u], parts[1][u], parts[2][u]) for u in parts[0]}
     warm.join()            # long done in a real run; a tiny one must not leave an import running at interpreter exit
-    results = {n: [] for n in names}
+    results = {n: [] for n in cfgs}
     for u in sorted(allm):
         n, k = units[u]
         results[n].append({"subject": cfgs[n]["subjects"][k], "accuracy": allm[u][0], "f1_score": allm[u][1]})
-    if rank == 0 or cfg0.get("emulate_rank"):
-        for n in names:
-            out_dir[n].mkdir(parents=True, exist_ok=True)
-            path = write_summary(out_dir[n], results[n], cfgs[n], wall, world)
-            accs = [r["accuracy"] for r in results[n]]
-            print(f"交叉验证汇总结果已保存至: {path}")
-            print(f"{(n + ': ') if n else ''}平均准确率 (Accuracy): {np.mean(accs):.4f} ± {np.std(accs):.4f}"
-                  f" | LOSO wall-clock {wall:.1f}s on {world} GPU(s) ({len(units)} folds in this job; load + normalise + upload {t_data:.1f}s)")
-            if cal_all is not None:
-                from .calibrate import write_calibration
-                folds = [{"subject": cfgs[n]["subjects"][units[u][1]], "n_cal": int(cal_all[u][2][0]), "n_eval": int(cal_all[u][2][1]),
-                          "before": {"accuracy": cal_all[u][0][0], "f1_score": cal_all[u][0][1]},
-                          "after": {"accuracy": cal_all[u][1][0], "f1_score": cal_all[u][1][1]}}
-                         for u in sorted(cal_all) if units[u][0] == n]
-                path = write_calibration(out_dir[n], folds, calibration_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
-                print(f"校准结果已保存至: {path}")
+    if rank == 0 or emulate:
+        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data)
     return results, wall
 
 
@@ -545,6 +447,24 @@ M2_CHANNELS_TO_USE = ["chest_ECG", "chest_EDA", "chest_Resp"]
 M2_MODEL_PARAMS = {"cnn_out_channels": 32, "gru_hidden_size": 32, "gru_num_layers": 1, "dropout": 0.5}
 
 
+def hierarchical_units(k, cfg, models, datasets, run_output_dir, device):
+    """The (fold, model) units of fold k of the hierarchical experiment, as (tag, prep) pairs — M1, then M2, each made when it is
+    asked for (make_unit; seed SEED + 2 k + (M2), loaders that always shuffle, no test pass: the fold's M1 test pass and its
+    three-class decision are the driver's `decide`).  `datasets`: {tag: dataset factory}.  Ends, with the reference's warning, at
+    the first model whose training or validation set is empty (main.py:187-189): a fold that loses its M2 this way has trained
+    its M1 and never decides."""
+    sid = cfg["subjects"][k]
+    fold_dir = Path(run_output_dir) / f"fold_test_on_{sid}"
+    fold_dir.mkdir(parents=True, exist_ok=True)
+    for tag, ch, par, mode in models:
+        p = make_unit(k, sid, fold_dir / f"model_{tag}", datasets[tag], len(ch), 2, par, cfg["seed"] + 2 * k + (tag == "m2"), cfg, device,
+                      test_pass=False, skip_empty=True)
+        if p is None:
+            print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
+            return
+        yield tag, p
+
+
 def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=None, rank=0, world=1):
     """The reference's run_hierarchical_experiment (main.py:159-247): per LOSO fold a stress-vs-rest model M1 (the reference
     configuration) and an amusement-vs-baseline model M2 (gru_hidden_size 32, gru_num_layers 1: runtime.EmbeddedEngine), then the
@@ -553,37 +473,30 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
     summary the reference stops short of (overall three-class accuracy / weighted F1, per-fold M1 accuracy) is written to
     hierarchical_summary.txt.  Folds are dealt to the ranks like the simple experiment's, so a fold's M1 and M2 stay on one rank.
     By default the rank's work units — (fold, model) pairs — train as fold batches (multifold.LockstepTrainer): the M1s over the
-    stress_binary store, the M2s over the amusement_binary store, concurrently on their own streams; each fold's decision runs
-    once both its models have finished.  cfg["concurrent_folds"] = 1 (or lockstep False) trains each fold's two models one after
-    the other, as the reference does; both give the same bits.  Returns (per-fold dicts in subject order, wall seconds)."""
+    stress_binary store, the M2s (the one-layer model: runtime.FoldArena's padded form) over the amusement_binary store — views of one
+    store per model (SubjectStore.from_wesad: the same windows, bit for bit) — dealt and run like the simple experiment's
+    (waves.deal, waves.run_wave), the two models being the groups that train side by side; each fold's decision runs once both
+    its models have finished.  M2's training sets are smaller; folds of unequal size share launches as in the simple experiment,
+    and the backward kernel form is pinned per fold (FoldArena.multi), so every fold's bits are those of its sequential run.
+    cfg["concurrent_folds"] = 1 (or lockstep False) trains each fold's two models one after the other (train_fold), as the
+    reference does; both give the same bits.  Returns (per-fold dicts in subject order, wall seconds)."""
     from .trainer import accuracy_and_weighted_f1
     cfg = dict(cfg or default_cfg())
     m1_ch, m2_ch = list(cfg.get("m1_channels", M1_CHANNELS_TO_USE)), list(cfg.get("m2_channels", M2_CHANNELS_TO_USE))
     m1_par, m2_par = dict(cfg.get("m1_params", M1_MODEL_PARAMS)), dict(cfg.get("m2_params", M2_MODEL_PARAMS))
     subjects, t0, cache = list(cfg["subjects"]), time.time(), {}
     models = (("m1", m1_ch, m1_par, "stress_binary"), ("m2", m2_ch, m2_par, "amusement_binary"))
-
-    def tcfg_for(k):
-        pat = cfg["patience"]
-        if isinstance(pat, (list, tuple)):       # a per-fold cycle of patiences, as in prepare_fold
-            pat = int(pat[k % len(pat)])
-        tc = {"trainer": {"epochs": cfg["epochs"], "learning_rate": cfg["lr"],
-                          "early_stopping": {"enabled": True, "patience": pat, "delta": 0},
-                          "weight_decay": cfg["weight_decay"], "verbose": cfg.get("verbose", False)}}
-        if trainer_class_weights(cfg) is not None:      # M1's from its stress_binary, M2's from its amusement_binary training labels
-            tc["trainer"]["class_weights"] = trainer_class_weights(cfg)
-        return tc
-    mk = lambda subj, ch, mode: WesadDataset(cfg["data_path"], subj, ch, all_channel_names, classification_mode=mode, cache=cache)
-    bs = cfg["batch_size"]
-    ebs = int(cfg.get("eval_batch_size") or bs)              # validation / test passes (per-window results do not depend on it)
+    ebs = int(cfg.get("eval_batch_size") or cfg["batch_size"])     # validation / test passes (per-window results do not depend on it)
     local, rows = {}, {}
     mine = folds_for_rank(len(subjects), world, rank)
 
-    def decide(k, sid, fold_dir, trainers):
+    def decide(k, trainers):
         """M1's test pass and the three-class decision of fold k (main.py:203-247), once both its models have trained."""
-        _, m1_acc, m1_f1 = trainers["m1"].evaluate(DeviceLoader(mk([sid], m1_ch, "stress_binary"), ebs, False, device), is_test=True)   # main.py:203-207
+        sid = subjects[k]
+        m1_test = host_datasets(cfg, all_channel_names, cache, m1_ch, "stress_binary")([sid])
+        _, m1_acc, m1_f1 = trainers["m1"].evaluate(DeviceLoader(m1_test, ebs, False, device), is_test=True)   # main.py:203-207
         eval_ch = list(dict.fromkeys(m1_ch + m2_ch))              # main.py:211 (a set there: the order is immaterial, the indices follow it)
-        tern = mk([sid], eval_ch, "ternary")
+        tern = host_datasets(cfg, all_channel_names, cache, eval_ch, "ternary")([sid])
         i1, i2 = [eval_ch.index(c) for c in m1_ch], [eval_ch.index(c) for c in m2_ch]
         m1, m2 = trainers["m1"].model.eval(), trainers["m2"].model.eval()
         preds = []
@@ -596,33 +509,35 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
         acc3, f13 = accuracy_and_weighted_f1(np.asarray(tern.labels), pred)
         rows[k] = dict(subject=sid, m1_accuracy=m1_acc, m1_f1=m1_f1, ternary_accuracy=acc3, ternary_f1=f13, n=int(len(pred)),
                        correct=int((pred == np.asarray(tern.labels)).sum()))
-        (fold_dir / "fold_result.json").write_text(json.dumps(rows[k]))
+        (Path(run_output_dir) / f"fold_test_on_{sid}" / "fold_result.json").write_text(json.dumps(rows[k]))
         local[k] = (m1_acc, acc3)
         print(f"[rank {rank}] fold {k} ({sid}): M1 acc {m1_acc:.4f} | three-class acc {acc3:.4f} f1 {f13:.4f}", flush=True)
 
     if int(cfg.get("concurrent_folds", 1)) > 1 and cfg.get("lockstep", True) and mine:
-        _hierarchical_fold_batches(cfg, mine, subjects, models, tcfg_for, Path(run_output_dir), device, all_channel_names, cache, decide)
+        stores = {tag: SubjectStore.from_wesad(cfg["data_path"], subjects, ch, all_channel_names, mode, device, cache) for tag, ch, _, mode in models}
+        datasets = {tag: stores[tag].view for tag in stores}
+        # sequential: seeding / initialisation order as in the sequential driver
+        units = {(k, tag): p for k in mine for tag, p in hierarchical_units(k, cfg, models, datasets, run_output_dir, device)}
+        waves = deal([[u for u in units if u[1] == tag] for tag in stores], mine, cfg.get("concurrent_folds", 15), cfg.get("lockstep_groups", 4),
+                     fold_of=itemgetter(0))
+        if not all(lockstep_compatible([units[u] for u in ch]) for wv in waves for ch in wv):
+            raise RuntimeError("hierarchical fold batch: folds of one model do not share a store / batch size")
+        torch.cuda.synchronize(device)                  # uploads were issued on this thread's stream
+        t_start, finished, undecided = time.time(), set(), list(mine)
+        for wv in waves:
+            finished.update(u for u, _ in run_wave(wv, units, device, bool(cfg.get("adaptive_forms", False)), t_start))
+            for k in [k for k in undecided if all((k, tag) in finished for tag in stores)]:      # both its models have finished
+                undecided.remove(k)
+                decide(k, {tag: units[(k, tag)]["trainer"] for tag in stores})
     else:
+        datasets = {tag: host_datasets(cfg, all_channel_names, cache, ch, mode) for tag, ch, _, mode in models}
         for k in mine:
-            sid = subjects[k]
-            fold_dir = Path(run_output_dir) / f"fold_test_on_{sid}"
-            fold_dir.mkdir(parents=True, exist_ok=True)
-            train_subjects, val_subjects = split_train_val(subjects, sid, cfg["seed"])
             trainers = {}
-            for tag, ch, par, mode in models:
-                torch.manual_seed(cfg["seed"] + 2 * k + (tag == "m2"))
-                tr_ds, va_ds = mk(train_subjects, ch, mode), mk(val_subjects, ch, mode)
-                if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
-                    print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
-                    break
-                model = make_model(cfg, len(ch), 2, par)
-                model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
-                t = Trainer(model, fold_dir / f"model_{tag}", tcfg_for(k))
-                t.train(DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device))
-                trainers[tag] = t
-            if len(trainers) < 2:
-                continue
-            decide(k, sid, fold_dir, trainers)
+            for tag, p in hierarchical_units(k, cfg, models, datasets, run_output_dir, device):     # made immediately before it trains
+                train_fold(p, device)
+                trainers[tag] = p["trainer"]
+            if len(trainers) == len(models):
+                decide(k, trainers)
     allm = gather_fold_metrics(local, len(subjects), world, cfg.get("gather_device", device))
     wall = time.time() - t0
     results = [dict(subject=subjects[k], m1_accuracy=allm[k][0], ternary_accuracy=allm[k][1]) for k in sorted(allm)]
@@ -643,74 +558,6 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
             f.write(f"\nwall-clock: {wall:.1f} s on {world} GPU(s)\n")
         print(f"分层分类汇总结果已保存至: {path}")
     return results, wall
-
-
-def _hierarchical_fold_batches(cfg, mine, subjects, models, tcfg_for, run_output_dir, device, all_channel_names, cache, decide):
-    """The hierarchical experiment's work units — (fold, model) pairs of this rank's folds — as fold batches.  Seeds, models,
-    loaders and trainer configurations are made in the sequential driver's order and with its values; the datasets are views of
-    one store per model (SubjectStore.from_wesad: the same windows, bit for bit).  The M1s of a wave form fold batches over the
-    stress_binary store, its M2s (the one-layer model: runtime.FoldArena's padded form) over the amusement_binary store — at most
-    MAX_FOLDS folds and `lockstep_groups` batches per model, all of a wave's batches concurrently, one stream each, never more than
-    MAX_TRAIN_STREAMS at once.  M2's training sets are smaller; folds of unequal size share launches as in the simple experiment.
-    The backward kernel form is pinned per fold (FoldArena.multi), so every fold's bits are those of its sequential run."""
-    from concurrent.futures import ThreadPoolExecutor
-    from .multifold import LockstepTrainer, lockstep_compatible
-    bs = cfg["batch_size"]
-    ebs = int(cfg.get("eval_batch_size") or bs)
-    stores = {tag: SubjectStore.from_wesad(cfg["data_path"], subjects, ch, all_channel_names, mode, device, cache)
-              for tag, ch, _, mode in models}
-    units, fold_dirs = {}, {}                       # (k, tag) -> prep
-    for k in mine:                                  # sequential: seeding / initialisation order as in the sequential driver
-        sid = subjects[k]
-        fold_dir = fold_dirs[k] = run_output_dir / f"fold_test_on_{sid}"
-        fold_dir.mkdir(parents=True, exist_ok=True)
-        train_subjects, val_subjects = split_train_val(subjects, sid, cfg["seed"])
-        for tag, ch, par, mode in models:
-            torch.manual_seed(cfg["seed"] + 2 * k + (tag == "m2"))
-            tr_ds, va_ds = stores[tag].view(train_subjects), stores[tag].view(val_subjects)
-            if len(tr_ds) == 0 or len(va_ds) == 0:                # main.py:187-189
-                print(f"警告: 训练集或验证集在 {mode} 模式下没有数据，跳过此折叠。")
-                break
-            model = make_model(cfg, len(ch), 2, par)
-            model.set_dropout_seed((cfg["seed"] + 2 * k + (tag == "m2")) * 0x9E3779B97F4A7C15 + 12345)
-            loaders = (DeviceLoader(tr_ds, bs, True, device, seed=cfg["seed"] + 2 * k + (tag == "m2")), DeviceLoader(va_ds, ebs, False, device),
-                       DeviceLoader(stores[tag].view([sid]), ebs, False, device))
-            # test_pass False: the fold's M1 test pass and three-class decision run in `decide`, as in the sequential driver
-            units[(k, tag)] = dict(fold=k, subject=sid, fold_dir=fold_dir / f"model_{tag}", loaders=loaders, model=model,
-                                   config=tcfg_for(k), test_pass=False)
-    conc = max(1, int(cfg.get("concurrent_folds", 15)))
-    ng = max(1, min(int(cfg.get("lockstep_groups", 4)), MAX_TRAIN_STREAMS // len(models)))
-    waves = []
-    for w0 in range(0, len(mine), conc):            # at most `concurrent_folds` folds (both their models) resident at a time
-        wave = []
-        for tag, *_ in models:
-            g = [u for u in units if u[0] in mine[w0:w0 + conc] and u[1] == tag]
-            k_ = min(ng, max(1, len(g) // 2))
-            wave += [part[i:i + L.MAX_FOLDS] for part in (g[j::k_] for j in range(k_)) for i in range(0, len(part), L.MAX_FOLDS) if part]
-        waves.append(wave)
-    waves = cap_waves(waves)
-    for wv in waves:
-        if not all(lockstep_compatible([units[u] for u in ch]) for ch in wv):
-            raise RuntimeError("hierarchical fold batch: folds of one model do not share a store / batch size")
-    adaptive = bool(cfg.get("adaptive_forms", False))
-    torch.cuda.synchronize(device)                  # uploads were issued on this thread's stream
-    t_start = time.time()
-
-    def work(ch):
-        torch.cuda.set_device(device)
-        with torch.cuda.stream(torch.cuda.Stream(device)):
-            lt = LockstepTrainer([units[u] for u in ch], device, adaptive_forms=adaptive)
-            lt.run(t_start=t_start)                 # every fold of the batch to its early stop (or budget), then its checkpoint restored
-            torch.cuda.current_stream(device).synchronize()
-
-    finished = set()
-    for wv in waves:
-        with ThreadPoolExecutor(max_workers=len(wv)) as ex:
-            list(ex.map(work, wv))
-        finished.update(u for ch in wv for u in ch)
-        for k in mine:                              # a fold decides as soon as both its models have finished
-            if k in fold_dirs and all((k, tag) in finished for tag, *_ in models):
-                decide(k, subjects[k], fold_dirs.pop(k), {tag: units[(k, tag)]["trainer"] for tag, *_ in models})
 
 
 def ablation_sets(all_channel_names):

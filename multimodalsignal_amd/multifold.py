@@ -19,6 +19,7 @@ stop early leave the batch.
 from __future__ import annotations
 
 import ctypes as C
+import json
 import time
 from typing import List
 
@@ -40,13 +41,23 @@ def _kind(model):
     return getattr(model, "kind", None) or "cnn_gru_attention"
 
 
+def fold_result(prep, trainer, accuracy, f1_score, seconds):
+    """The result dict of one trained fold, whichever mode trained it (main.train_fold, LockstepTrainer.run); a fold with a test
+    pass of its own leaves it in fold_result.json as soon as it has finished (it survives a crash of another fold)."""
+    info = dict(subject=prep["subject"], accuracy=accuracy, f1_score=f1_score, seconds=seconds, epochs=len(trainer.history),
+                train_windows_per_s=trainer.train_windows / max(trainer.train_seconds, 1e-9), history=trainer.history)
+    if prep.get("test_pass", True):
+        (prep["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
+    return info
+
+
 def lockstep_compatible(preps) -> bool:
     """Folds can share launches when they draw from one SubjectStore with one model kind and configuration and one batch size.  Their
     train / val sets may differ in size (WESAD subjects differ by a few windows, dataset.py:17-27): full batches run as one fold
     batch, the folds' ragged last batches as launches over the folds whose batch sizes agree (`launch_plan`).  The one-layer
     32-unit model has an arena form (padded, as runtime.EmbeddedEngine); a batch is uniform in depth — msig_batch.gru_layers is
     one value per launch, and so is the kind (msig_multi has no per-slot flag: a launch runs msig_cg_*_multi or the msig_* calls)."""
-    if not (1 <= len(preps) <= L.MAX_FOLDS):       # a batch of ONE fold is a fold batch too (it can be re-dealt with others later)
+    if not (1 <= len(preps) <= L.MAX_FOLDS):       # a batch of ONE fold is a fold batch too (a window's last fold, a rank's only one)
         return False
     tr0, va0, _ = preps[0]["loaders"]
     d0, k0 = _depth(preps[0]["model"]), _kind(preps[0]["model"])
@@ -97,21 +108,11 @@ class LockstepTrainer:
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
-            old = model._engine
-            new = self.arena.engine(slot)                      # zeroed storage of arena `slot`
-            if p.get("trainer") is not None and old is not None:
-                # a fold that has already trained in ANOTHER fold batch (main.run_experiments re-deals the surviving folds between
-                # rounds): its Adam moments move with it; model.engine() below moves the parameters and the BatchNorm state
-                new.exp_avg.copy_(old.exp_avg)
-                new.exp_avg_sq.copy_(old.exp_avg_sq)
-                if self.embedded:
-                    old.gather()                               # the one-layer model's reference-shaped parameters from its old arena
-            model._engine = new                                # the model's parameters become views into arena `slot`
-            t = p.get("trainer") or Trainer(model, p["fold_dir"], p["config"])
-            p["trainer"] = t
+            model._engine = self.arena.engine(slot)            # zeroed storage of arena `slot`: the model's parameters become views into it
+            t = p["trainer"] = Trainer(model, p["fold_dir"], p["config"])
             model.engine()
             if self.embedded:
-                new.scatter()                                  # into the padded layout, once: the steps train it in place
+                model._engine.scatter()                        # into the padded layout, once: the steps train it in place
             self.trainers.append(t)
         # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
         # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
@@ -243,12 +244,9 @@ class LockstepTrainer:
             out[f] = (float(sums[f]) / len(ds), acc, f1)
         return [out[f] for f in active]
 
-    def run(self, epoch0: int = 0, max_epochs: int = 0, t_start: float = None):
-        """Trains every fold to its early stop, then evaluates each on its test subject; returns main.train_fold's dicts.
-        With `max_epochs` > 0 it trains epochs epoch0 .. epoch0 + max_epochs - 1 only and returns (infos of the folds that finished, in
-        a dict by position, positions of the folds still training): main.run_experiments runs a rank's folds in ROUNDS and re-deals
-        the survivors evenly over the fold batches between rounds (which folds share a batch has no influence on any fold's numbers)."""
-        import json
+    def run(self, t_start: float = None):
+        """Trains every fold to its early stop (or the epoch budget), then evaluates each on its test subject; returns the folds'
+        `fold_result` dicts in position order.  A budget of 0 epochs takes every fold straight to its test pass."""
         from concurrent.futures import ThreadPoolExecutor
         for t, p in zip(self.trainers, self.preps):
             for ld in p["loaders"]:
@@ -268,19 +266,13 @@ class LockstepTrainer:
                 t._finish_training()
                 acc, f1 = t.evaluate(p["loaders"][2], is_test=True)[1:] if test else (None, None)
                 torch.cuda.current_stream(dev).synchronize()
-            info = dict(subject=p["subject"], accuracy=acc, f1_score=f1, seconds=getattr(t, "finished_at", time.time() - t_start),
-                        epochs=len(t.history), train_windows_per_s=t.train_windows / max(t.train_seconds, 1e-9), history=t.history)
-            if test:
-                (p["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
-            return info
+            return fold_result(p, t, acc, f1, getattr(t, "finished_at", time.time() - t_start))
 
         active = list(range(self.n))
         n_train = [len(p["loaders"][0].dataset) for p in self.preps]
         pending = {}
-        budget = self.trainers[0].epochs
-        last = min(budget, epoch0 + max_epochs) if max_epochs > 0 else budget
         with ThreadPoolExecutor(max_workers=2) as side:
-            for epoch in range(epoch0, last):
+            for epoch in range(self.trainers[0].epochs):               # the batch's budget: its folds share it (__init__)
                 if not active:
                     break
                 t0 = time.time()
@@ -302,10 +294,6 @@ class LockstepTrainer:
                         pending[f] = side.submit(finish, f)
                 active = still
             torch.cuda.current_stream(dev).synchronize()
-            if last >= budget:
-                for f in active:                                           # ran out of epochs without an early stop
-                    pending[f] = side.submit(finish, f)
-                active = []
-            if max_epochs > 0:
-                return {f: fut.result() for f, fut in pending.items()}, active
+            for f in active:                                               # ran out of epochs without an early stop
+                pending[f] = side.submit(finish, f)
             return [pending[f].result() for f in range(self.n)]
