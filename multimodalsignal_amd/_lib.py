@@ -1,4 +1,4 @@
-"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h).
+"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -81,6 +81,7 @@ ABI_VERSION = 5       # include/msig.h MSIG_ABI_VERSION
 CW_ABI_VERSION = 1    # include/msig_cw.h MSIG_CW_ABI_VERSION (class-weighted CrossEntropy)
 CG_ABI_VERSION = 1    # include/msig_cg.h MSIG_CG_ABI_VERSION (the cnn_gru baseline)
 FT_ABI_VERSION = 1    # include/msig_ft.h MSIG_FT_ABI_VERSION (window embeddings, classifier-only head epochs)
+GC_ABI_VERSION = 1    # include/msig_gc.h MSIG_GC_ABI_VERSION (gradient-norm clipping inside the fused train steps)
 FT_MAX_BATCH, FT_MAX_N = 256, 1 << 24
 FT_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_FT_KIND_*
 
@@ -107,6 +108,17 @@ class FtMulti(C.Structure):
     first optimiser step count and dropout seed."""
     _fields_ = [("n", C.c_int32), ("slot", C.c_int32 * MAX_FOLDS), ("reserved", C.c_int32), ("stride_bytes", C.c_int64),
                 ("lr", C.c_float * MAX_FOLDS), ("step0", C.c_int64 * MAX_FOLDS), ("seed", C.c_uint64 * MAX_FOLDS)]
+
+
+GC_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_GC_KIND_*
+GC_SUM, GC_MAX, GC_CLIPPED, GC_LAST, GC_NSTAT = range(5)      # msig_gc.h: the statistics at the head of a model's clip state
+
+
+class GcClip(C.Structure):
+    """msig_gc_clip (include/msig_gc.h): the clip of a train step — model kind, optional class weights, the caller-owned clip state
+    and max_norm per fold of the launch."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("class_weight", C.c_void_p), ("state", C.c_void_p),
+                ("state_bytes", C.c_int64), ("max_norm", C.c_double * MAX_FOLDS)]
 
 
 _lib = None
@@ -218,6 +230,16 @@ def lib() -> C.CDLL:
         L.msig_ft_features_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.c_int, vp, C.c_int64, vp]
         L.msig_ft_head_epoch.argtypes = [C.POINTER(FtHead), vp]
         L.msig_ft_head_epoch_multi.argtypes = [C.POINTER(FtHead), C.POINTER(FtMulti), vp]
+        # include/msig_gc.h, exported by the same library: the train steps with gradient-norm clipping
+        L.msig_gc_abi_version.restype = C.c_int
+        L.msig_gc_struct_bytes.restype = C.c_int64
+        if L.msig_gc_abi_version() != GC_ABI_VERSION or L.msig_gc_struct_bytes() != C.sizeof(GcClip):
+            raise RuntimeError(f"{LIB_PATH} has msig_gc.h ABI {L.msig_gc_abi_version()} with msig_gc_clip of {L.msig_gc_struct_bytes()} bytes; "
+                               f"this binding is {GC_ABI_VERSION} with {C.sizeof(GcClip)}: rebuild the library")
+        L.msig_gc_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.msig_gc_state_bytes.restype = C.c_int64
+        L.msig_gc_train_step.argtypes = [C.POINTER(Batch), C.POINTER(GcClip), vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_gc_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(GcClip), vp, vp, f32, f32, f32, f32, i64, vp]
         _lib = L
     return _lib
 
@@ -304,6 +326,27 @@ def check_class_weight(values, K: int):
     if not np.isfinite(w).all() or (w < 0).any():
         raise ValueError(f"class weights must be finite and non-negative, got {w.tolist()}")
     return w
+
+
+def gc_state_bytes(Cin: int, K: int, kind: str = "cnn_gru_attention") -> int:
+    """Bytes of one model's clip state (include/msig_gc.h msig_gc_state_bytes)."""
+    n = int(lib().msig_gc_state_bytes(Cin, K, GC_KINDS[check_kind(kind)]))
+    if n < 0:
+        check(n, "msig_gc_state_bytes")
+    return n
+
+
+def check_max_grad_norm(value) -> float:
+    """The host-side check of a max_norm (include/msig_gc.h): a number > 0, +infinity allowed (no clipping).  ValueError otherwise."""
+    if isinstance(value, (str, bytes, bool)):          # float("1") would pass: a string is not a number here
+        raise ValueError(f"max_grad_norm must be a positive number, got {value!r}")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_grad_norm must be a positive number, got {value!r}") from None
+    if not v > 0.0:
+        raise ValueError(f"max_grad_norm must be a positive number, got {value!r}")
+    return v
 
 
 FORM_AUTO = -1

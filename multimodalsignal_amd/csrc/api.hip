@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, include/msig_cw.h, include/msig_cg.h and include/msig_ft.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h and msig_gc.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -296,7 +296,8 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
 
 // fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch)
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
-                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr, bool cg = false) {
+                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr, bool cg = false,
+                         const ClipArgs* clip = nullptr) {
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
   if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
@@ -331,7 +332,8 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
     fc.inv_sqrt_bc2[i] = (float)(1.0 / sqrt(bc2));
   }
   const AdamArgs ad{(float*)b->params, b->grads, exp_avg, exp_avg_sq, fc.lr_over_bc1[0], fc.inv_sqrt_bc2[0], beta1, beta2, eps, weight_decay};
-  return launch_colsum_adam_plan(plan, ad, fc, st);
+  // clip: the norm of the whole gradient has to be known between the reduction and the update — two launches (include/msig_gc.h)
+  return clip ? launch_colsum_clip_adam_plan(plan, ad, fc, *clip, st) : launch_colsum_adam_plan(plan, ad, fc, st);
 }
 
 extern "C" int msig_train_step(const msig_batch* b, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
@@ -423,6 +425,55 @@ extern "C" int msig_cg_train_step_multi(const msig_batch* b, const msig_multi* m
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight,
                        true);
+}
+
+// ---- gradient-norm clipping (include/msig_gc.h): the train steps with the clip between the reduction and the Adam update ---------
+extern "C" int msig_gc_abi_version(void) { return MSIG_GC_ABI_VERSION; }
+extern "C" int64_t msig_gc_struct_bytes(void) { return (int64_t)sizeof(msig_gc_clip); }
+
+// Column blocks of a train step's reduction plan, bounded from the layout alone: the plan's jobs cover every parameter element once,
+// a job of n columns has ceil(n / 32) blocks, and there are at most MSIG_MAX_JOBS jobs.
+static int64_t gc_partials(int C, int K, int kind) {
+  int64_t po[MSIG_NPARAM + 1];
+  const int rc = param_layout(C, K, po, kind == MSIG_GC_KIND_ATTENTION);
+  if (rc) return rc;
+  return po[MSIG_NPARAM] / 32 + MSIG_MAX_JOBS;
+}
+extern "C" int64_t msig_gc_state_bytes(int C, int K, int kind) {
+  if (kind != MSIG_GC_KIND_ATTENTION && kind != MSIG_GC_KIND_CNN_GRU) return MSIG_E_SHAPE;
+  const int64_t n = gc_partials(C, K, kind);
+  return n < 0 ? n : (MSIG_GC_NSTAT + n) * (int64_t)sizeof(double);
+}
+// every check of msig_gc.h's own arguments, before the counterpart's and before any launch; n = folds of the launch
+static int make_clip(const msig_batch* b, const msig_gc_clip* g, int n, ClipArgs& cl) {
+  if (!g || !b) return MSIG_E_NULL;
+  if (g->kind != MSIG_GC_KIND_ATTENTION && g->kind != MSIG_GC_KIND_CNN_GRU) return MSIG_E_SHAPE;
+  for (int i = 0; i < n; ++i)
+    if (!(g->max_norm[i] > 0.0)) return MSIG_E_SHAPE;                   // NaN included
+  if (!g->state) return MSIG_E_NULL;
+  if ((uintptr_t)g->state & 7) return MSIG_E_ALIGN;
+  if (cw_misaligned(g->class_weight)) return MSIG_E_ALIGN;
+  const int64_t cap = gc_partials(b->shape.C, b->shape.K, g->kind);
+  if (cap < 0) return (int)cap;
+  if (g->state_bytes < (MSIG_GC_NSTAT + cap) * (int64_t)sizeof(double)) return MSIG_E_WORKSPACE;
+  cl = ClipArgs{};
+  cl.state = (double*)g->state;
+  cl.cap = (int)cap;
+  for (int i = 0; i < n; ++i) cl.max_norm[i] = g->max_norm[i];
+  return 0;
+}
+extern "C" int msig_gc_train_step(const msig_batch* b, const msig_gc_clip* g, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  ClipArgs cl; int rc = make_clip(b, g, 1, cl); if (rc) return rc;
+  return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
+                       g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl);
+}
+extern "C" int msig_gc_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_gc_clip* g, float* exp_avg, float* exp_avg_sq,
+                                        float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  ClipArgs cl; if ((rc = make_clip(b, g, fc.n, cl))) return rc;
+  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
+                       g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

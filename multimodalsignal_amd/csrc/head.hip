@@ -566,6 +566,152 @@ int launch_colsum_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const Fo
   return 0;
 }
 
+// ------------------------------------------------------------------------------------
+// Gradient-norm clipping (include/msig_gc.h): colsum_adam's launch as two.  The global norm has to be known between
+// the reduction and the Adam update of every element, and a hand-over between workgroups inside one kernel costs a kernel boundary
+// on this part — so the boundary is a launch.
+//   colsum_sq_kernel  colsum_adam's reduction half on the same grid: writes g, and each workgroup the fp64 sum of its 32 columns'
+//                     squares to partial[blockIdx.x] of its fold's clip state (in-place jobs only read and square).  Which
+//                     columns a workgroup owns follows from the plan, i.e. from the model's shape: the partials and the order
+//                     they are added in do not depend on the folds of the launch.  The fused head's loss workgroup rides along.
+//   clip_adam_kernel  a few fat workgroups per fold (the ~4 000 partials are 32 KB: re-read by every workgroup of the launch, so
+//                     there are at most a few hundred of those, not thousands): each sums the partials in ONE order (thread t adds
+//                     t, t + 256, ..., each wave reduces its lanes, the four wave sums are added in wave order), forms coef, and
+//                     walks its share of the column blocks: g' = g * coef stored, then colsum_adam_kernel's Adam statements.
+// With coef = 1 the step's bits are the unclipped step's: see the note at the arithmetic of clip_adam_kernel.
+// ------------------------------------------------------------------------------------
+template <bool CW>
+__global__ __launch_bounds__(256) void colsum_sq_kernel(const ColsumJobs jobs, double* __restrict__ state, const LossFin loss_in, const FoldCtx fc) {
+  __shared__ double red[CS_LANES][CS_COLS];
+  if ((int)blockIdx.x == jobs.blk0[MSIG_MAX_JOBS]) {          // the fused head's loss, as in colsum_adam_kernel
+    __shared__ double lred[2][CE_THREADS / 64];
+    __shared__ double wred[4];
+    LossFin lf = loss_in;
+    const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
+    FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
+    if constexpr (CW) FS(lf.cw);
+    loss_finalize<CW>(lf, lred, wred);
+    return;
+  }
+  const int ji = colsum_find_job(jobs, blockIdx.x);
+  ColsumJob jb = jobs.j[ji];
+  const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
+  FS(jb.part); FS(jb.out); FS(state);
+  const int cx = threadIdx.x & (CS_COLS - 1), ry = threadIdx.x / CS_COLS;
+  const int c = ((int)blockIdx.x - jobs.blk0[ji]) * CS_COLS + cx;
+  if (jb.nrows > 0) {
+    red[ry][cx] = c < jb.ncols ? colsum_lane(jb.part + jb.col0 + c, jb.nrows, (size_t)jb.row_stride, ry) : 0.0;
+    __syncthreads();
+  }
+  if (threadIdx.x < 64) {                                     // wave 0: lanes 0..31 own the columns, lanes 32..63 add zeros
+    double sq = 0.0;
+    if (ry == 0 && c < jb.ncols) {
+      float gsum;
+      if (jb.nrows > 0) { gsum = (float)colsum_fold(red, cx); jb.out[c] = gsum; }
+      else gsum = jb.out[c];
+      sq = (double)gsum * (double)gsum;
+    }
+    sq = wave_sum_d(sq);
+    if (threadIdx.x == 0) state[MSIG_GC_NSTAT + blockIdx.x] = sq;
+  }
+}
+
+#define CLIP_SUB (256 / CS_COLS)      // column blocks a workgroup covers at once
+#define CLIP_U 4                      // of those per thread, their loads in flight together
+#define CLIP_MIN_WG 16
+__global__ __launch_bounds__(256) void clip_adam_kernel(const ColsumJobs jobs, const AdamArgs ad_in, const ClipArgs cl, const FoldCtx fc) {
+  __shared__ double wsum[4];
+  AdamArgs ad = ad_in;
+  double* state = cl.state;
+  const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
+  FS(state); FS(ad.p); FS(ad.g); FS(ad.m); FS(ad.v);
+  ad.lr_over_bc1 = fc.lr_over_bc1[blockIdx.y];
+  ad.inv_sqrt_bc2 = fc.inv_sqrt_bc2[blockIdx.y];
+  const int nblk = jobs.blk0[MSIG_MAX_JOBS];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int i = tid; i < nblk; i += 256) s += state[MSIG_GC_NSTAT + i];
+  s = wave_sum_d(s);
+  if ((tid & 63) == 0) wsum[tid >> 6] = s;
+  __syncthreads();
+  const double N = sqrt((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
+  const double max_norm = cl.max_norm[blockIdx.y];
+  const double q = max_norm / (N + 1e-6);
+  const float coef = (float)(q > 1.0 ? 1.0 : q);             // torch's clamp(max=1): a NaN quotient stays NaN
+  if (blockIdx.x == 0 && tid == 0) {                          // the fold's running statistics: one thread, stream order
+    state[MSIG_GC_SUM] += N;
+    state[MSIG_GC_MAX] = N > state[MSIG_GC_MAX] ? N : state[MSIG_GC_MAX];
+    state[MSIG_GC_CLIPPED] += N > max_norm ? 1.0 : 0.0;
+    state[MSIG_GC_LAST] = N;
+  }
+  const int cx = tid & (CS_COLS - 1), sub = tid / CS_COLS;
+  for (int b0 = (int)blockIdx.x * (CLIP_SUB * CLIP_U); b0 < nblk; b0 += (int)gridDim.x * (CLIP_SUB * CLIP_U)) {
+    int64_t idx[CLIP_U];
+    float g[CLIP_U], p[CLIP_U], m[CLIP_U], v[CLIP_U];
+#pragma unroll
+    for (int u = 0; u < CLIP_U; ++u) {
+      const int blk = b0 + u * CLIP_SUB + sub;
+      idx[u] = -1;
+      g[u] = p[u] = m[u] = v[u] = 0.f;
+      if (blk < nblk) {
+        int ji = 0;
+        for (int j = 1; j < jobs.n; ++j) ji += blk >= jobs.blk0[j] ? 1 : 0;      // colsum_find_job with a uniform trip count
+        const int c = (blk - jobs.blk0[ji]) * CS_COLS + cx;
+        if (c < jobs.j[ji].ncols) idx[u] = (jobs.j[ji].out - ad_in.g) + c;       // both are fold 0's pointers
+      }
+      if (idx[u] >= 0) { g[u] = ad.g[idx[u]]; p[u] = ad.p[idx[u]]; m[u] = ad.m[idx[u]]; v[u] = ad.v[idx[u]]; }
+    }
+#pragma unroll
+    for (int u = 0; u < CLIP_U; ++u) {
+      if (idx[u] < 0) continue;
+      const int64_t i = idx[u];
+      {
+        // Every rounding spelled out, nothing left to contraction: the clip is a multiplication of its own, and the Adam statements
+        // are colsum_adam_kernel's AS COMPILED — there hipcc fuses wd * p, b1 * m, sqrt(vv) * inv_sqrt_bc2 and lr * (mm / denom)
+        // into FMAs and leaves (1 - b1) * gr, b2 * v and ((1 - b2) * gr) * gr as products.  Left to itself it pairs the statements
+        // of this loop into packed instructions and picks the other product of mm for the FMA: one ulp off the unclipped step.
+        // tests/test_grad_clip_gpu.py (max_norm = inf against the unclipped step, bit for bit) holds the two kernels together.
+#pragma clang fp contract(off)
+        const float gsum = g[u] * coef;
+        ad.g[i] = gsum;
+        const float gr = __builtin_fmaf(ad.wd, p[u], gsum);
+        const float mm = __builtin_fmaf(ad.b1, m[u], (1.f - ad.b1) * gr);
+        const float vv = ad.b2 * v[u] + ((1.f - ad.b2) * gr) * gr;
+        const float denom = __builtin_fmaf(sqrtf(vv), ad.inv_sqrt_bc2, ad.eps);
+        ad.p[i] = __builtin_fmaf(-ad.lr_over_bc1, mm / denom, p[u]);
+        ad.m[i] = mm;
+        ad.v[i] = vv;
+      }
+    }
+  }
+}
+
+int launch_colsum_clip_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const FoldCtx& fc, const ClipArgs& cl, hipStream_t st) {
+  if (plan.n <= 0) return 0;
+  ColsumJobs a;
+  const int nblk = colsum_fill(plan, a);
+  if (nblk <= 0) return 0;
+  if (nblk > cl.cap) return MSIG_E_WORKSPACE;      // msig_gc_state_bytes bounds the plan's column blocks: not reached
+  {
+    MSIG_K("colsum_sq", st);
+    const dim3 grid(nblk + (plan.loss.logits ? 1 : 0), fc.n);
+    if (plan.loss.cw) colsum_sq_kernel<true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc);
+    else colsum_sq_kernel<false><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc);
+  }
+  MSIG_LAUNCH_CHECK();
+  {
+    MSIG_K("clip_adam", st);
+    // about one workgroup per CU over the whole launch, never fewer than CLIP_MIN_WG per fold; the bits do not depend on the count
+    const int per_pass = CLIP_SUB * CLIP_U;
+    int wg = 256 / fc.n;
+    if (wg < CLIP_MIN_WG) wg = CLIP_MIN_WG;
+    if (wg > (nblk + per_pass - 1) / per_pass) wg = (nblk + per_pass - 1) / per_pass;
+    clip_adam_kernel<<<dim3(wg, fc.n), 256, 0, st>>>(a, ad, cl, fc);
+  }
+  MSIG_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_colsum_plan(const ColsumPlan& plan, const FoldCtx& fc, hipStream_t st) {
   if (plan.n <= 0) return 0;
   ColsumJobs a;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/msig.h"
+#include "../../include/msig_gc.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -338,6 +339,11 @@ int launch_colsum_plan(const ColsumPlan& plan, const FoldCtx& fc, hipStream_t st
 // last two launches in one).  Jobs with nrows == 0 are "gradient already in place" ranges (BN affine, gate weights).
 struct AdamArgs { float *p, *g, *m, *v; float lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, wd; };
 int launch_colsum_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const FoldCtx& fc, hipStream_t st);
+// The same with gradient-norm clipping between the reduction and the update (include/msig_gc.h; head.hip colsum_sq_kernel +
+// clip_adam_kernel).  state: fold slot 0's clip state (MSIG_GC_NSTAT doubles of statistics, then `cap` doubles for the
+// per-workgroup sums of squares), shifted per fold like every buffer; max_norm per fold of the launch.
+struct ClipArgs { double* state; int cap; double max_norm[MSIG_MAX_FOLDS]; };
+int launch_colsum_clip_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const FoldCtx& fc, const ClipArgs& cl, hipStream_t st);
 // sub-regions of MSIG_WS_GRAD_PART, in floats
 struct PartOffsets { int64_t head, l1, l0, conv2, conv1, total; int gru_rows; };
 PartOffsets part_offsets(const StageDims& d);

@@ -32,7 +32,7 @@ from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
 from .multifold import fold_result, lockstep_compatible
-from .trainer import Trainer
+from .trainer import Trainer, grad_clip_setting
 from .waves import MAX_TRAIN_STREAMS, cap_waves, chunk_schedule, deal, on_streams, run_wave  # noqa: F401  (the first three: importable from here)
 
 warnings.filterwarnings("ignore", message="Initializing zero-element tensors is a no-op")
@@ -92,6 +92,8 @@ def trainer_config(cfg, fold_idx):
                       "weight_decay": cfg["weight_decay"], "verbose": cfg.get("verbose", False)}}
     if trainer_class_weights(cfg) is not None:      # each model's from its own training labels (M1's stress_binary, M2's amusement_binary)
         tc["trainer"]["class_weights"] = trainer_class_weights(cfg)
+    if cfg.get("max_grad_norm") is not None:        # clip_grad_norm_ inside the fused step (include/msig_gc.h); absent = the unclipped step
+        tc["trainer"]["max_grad_norm"] = grad_clip_setting(cfg["max_grad_norm"])
     return tc
 
 
@@ -166,6 +168,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(f"{k}: {v}\n")
         if trainer_class_weights(cfg) is not None:                  # named only when set: summaries of unweighted runs are unchanged
             f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
+        if cfg.get("max_grad_norm") is not None:                    # likewise
+            f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -549,6 +553,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(f"MODEL_TO_USE: {model_kind(cfg)}\n")
             if trainer_class_weights(cfg) is not None:
                 f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
+            if cfg.get("max_grad_norm") is not None:
+                f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
             f.write("\n")
             for r in results:
                 f.write(f"  - 测试 {r['subject']}: M1 Accuracy = {r['m1_accuracy']:.4f}, 三分类 Accuracy = {r['ternary_accuracy']:.4f}\n")
@@ -590,6 +596,10 @@ def parse_args(ap, argv=None):
         ap.error("--calibration-gap and --calibration-epochs must be >= 0")
     if args.calibration_lr is not None and not args.calibration_lr > 0:
         ap.error("--calibration-lr must be > 0")
+    try:
+        args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
+    except ValueError as e:
+        ap.error(f"--max-grad-norm: {e}")
     return args
 
 
@@ -628,6 +638,9 @@ def build_parser():
     ap.add_argument("--class-weights", choices=["none", "balanced"], default=CLASS_WEIGHTS,
                     help="class-weighted CrossEntropyLoss for training, validation and test losses: 'balanced' = N / (K * count_c) over "
                          "each model's own training labels (M1 and M2 separately in --hierarchical)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="torch.nn.utils.clip_grad_norm_(model.parameters(), X) between backward and Adam inside the fused train step "
+                         "(every mode: LOSO, --ablation, --hierarchical, --model, sequential); logs each epoch's gradient norms")
     ap.add_argument("--model", nargs="+", choices=list(MODEL_PARAMS), default=[MODEL_TO_USE],
                     help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
                          "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
@@ -674,6 +687,8 @@ def main(argv=None):
                concurrent_folds=args.concurrent_folds, normalise=args.normalise, eval_batch_size=args.eval_batch_size,
                lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms,
                class_weights=args.class_weights, model=kinds[0], model_params=dict(MODEL_PARAMS[kinds[0]]))
+    if args.max_grad_norm is not None:      # without the flag the configuration has no such key
+        cfg["max_grad_norm"] = args.max_grad_norm
     if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
         cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
         for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib as L
 from .runtime import FoldArena
-from .trainer import Trainer, accuracy_and_weighted_f1
+from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary
 
 
 def _depth(model):
@@ -103,8 +103,16 @@ class LockstepTrainer:
         if any(_kind(p["model"]) != self.kind for p in preps):
             raise ValueError("a fold batch is uniform in model kind: msig_multi has no per-slot kind")
         self.embedded = layers == 1
+        # gradient-norm clipping (config['trainer']['max_grad_norm'], include/msig_gc.h): the arenas get a clip state only when a
+        # fold asks for it; a fold of such a batch that does not is run with max_norm = inf, which is the unclipped step bit for bit
+        norms = [grad_clip_setting(p["config"]["trainer"].get("max_grad_norm")) for p in preps]
+        self.clip = any(v is not None for v in norms)
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
-                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind)
+                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip)
+        if self.clip:
+            for slot, v in enumerate(norms):
+                self.arena.set_max_norm(slot, float("inf") if v is None else v)
+        self.grad_stats = {}
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
@@ -174,6 +182,8 @@ class LockstepTrainer:
         fold's numbers.  Returns per-arena loss sums (indexed by slot) — the epoch's only sync."""
         arena, lib = self.arena, L.lib()
         train_multi = lib.msig_cg_train_step_multi if self.kind == "cnn_gru" else lib.msig_cw_train_step_multi
+        if self.clip:
+            arena.zero_grad_stats(sorted(active))
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][0].dataset))
         trs = [self.trainers[f] for f in act]
         loaders = [self.preps[f]["loaders"][0] for f in act]
@@ -202,11 +212,25 @@ class LockstepTrainer:
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
             self._gather(loaders[0], order, r0, i, b, m)
             _, desc = self._layout(b, True)
+            if self.clip:
+                if (r0, nr, "gc") not in multis:
+                    multis[(r0, nr, "gc")] = arena.clip(act[r0:r0 + nr], self.cw)
+                L.check(lib.msig_gc_train_step_multi(C.byref(desc), C.byref(m), C.byref(multis[(r0, nr, "gc")]), ea, eas, b1, b2, eps, wd,
+                                                     int(steps[r0][k]), st), "msig_gc_train_step_multi")
+                continue
             L.check(train_multi(C.byref(desc), C.byref(m), self.cw, ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
                     train_multi.__name__)           # self.cw None: exactly msig_train_step_multi (msig_cg_*: the baseline)
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
-        return self.acc[:, 0].cpu().numpy()                   # the epoch's only sync
+        if not self.clip:
+            return self.acc[:, 0].cpu().numpy()               # the epoch's only sync
+        # the same sync: the loss sums and the folds' gradient-norm statistics in one read-back
+        both = torch.cat([self.acc[:, :1], arena.across("gc", 0, torch.float64, L.GC_NSTAT)], dim=1).cpu().numpy()
+        sums, st4 = both[:, 0], both[:, 1:]
+        self.grad_stats = {f: grad_norm_summary(dict(sum=float(st4[f, L.GC_SUM]), max=float(st4[f, L.GC_MAX]),
+                                                     clipped=int(st4[f, L.GC_CLIPPED])), ns)
+                           for f, ns in zip(act, n_steps) if self.trainers[f].max_grad_norm is not None}
+        return sums
 
     def _evaluate(self, active, which):
         """Validation pass of every active fold (loader index `which`): per fold (loss, acc, f1), in the order of `active`."""
@@ -286,7 +310,7 @@ class LockstepTrainer:
                         t.model._engine.gather()   # once per epoch, for the checkpoint early stopping may write (best_model.pt)
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
-                    if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf):
+                    if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f)):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start

@@ -27,7 +27,8 @@ class Engine:
     def __init__(self, in_channels: int, num_classes: int, device: torch.device, storage: Optional[dict] = None,
                  kind: str = "cnn_gru_attention"):
         """`storage` (FoldArena.engine): pre-allocated flat tensors "params", "grads", "exp_avg", "exp_avg_sq", "bn_state",
-        "bn_count" and a "ws" byte region to use instead of allocating — the buffers of one arena of a fold batch.  `kind`:
+        "bn_count" and a "ws" byte region to use instead of allocating — the buffers of one arena of a fold batch (plus "gc", the
+        arena's clip state, when the arena was built for gradient clipping).  `kind`:
         "cnn_gru_attention" (include/msig.h, msig_cw.h) or "cnn_gru", the baseline without ChannelAttention (include/msig_cg.h:
         its layout and its calls)."""
         if not (1 <= in_channels <= L.MAX_C) or not (2 <= num_classes <= L.MAX_K):
@@ -51,12 +52,16 @@ class Engine:
             self.exp_avg: Optional[torch.Tensor] = None
             self.exp_avg_sq: Optional[torch.Tensor] = None
             self.loss_acc = torch.zeros(2, dtype=torch.float64, device=self.device)      # msig_batch.loss_acc: [sum of CE, #correct] of a pass
+            self.gc_state: Optional[torch.Tensor] = None      # include/msig_gc.h clip state (float64), made by the first clipped step
         else:
             self.params, self.grads = storage["params"], storage["grads"]
             self.bn_state, self.bn_count = storage["bn_state"], storage["bn_count"]
             self.exp_avg, self.exp_avg_sq = storage["exp_avg"], storage["exp_avg_sq"]
             self._ws_region = storage["ws"]
             self.loss_acc = storage["acc"]
+            self.gc_state = storage.get("gc")
+            if self.gc_state is not None:
+                self.gc_state.zero_()
             for t in (self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.bn_state, self.bn_count, self.loss_acc):
                 t.zero_()
         self.bn_state[16:32] = 1.0
@@ -258,15 +263,53 @@ class Engine:
                                        self.exp_avg_sq.data_ptr(), self.n_flat, lr, betas[0], betas[1], eps,
                                        weight_decay, step, self._stream()), "msig_adam_step")
 
+    def ensure_gc_state(self) -> torch.Tensor:
+        """The model's clip state (include/msig_gc.h): four float64 statistics, then the step's scratch."""
+        if self.gc_state is None:
+            self.gc_state = torch.zeros(L.gc_state_bytes(self.C, self.K, self.kind) // 8, dtype=torch.float64, device=self.device)
+        return self.gc_state
+
+    def zero_grad_stats(self):
+        if self.gc_state is not None:
+            self.gc_state[:L.GC_NSTAT].zero_()
+
+    def grad_stats(self) -> Optional[dict]:
+        """Gradient-norm statistics of the clipped steps since zero_grad_stats() (one read-back: a sync): sum, max and last of the
+        norms before the clip, the number of steps and how many of them exceeded max_norm.  None before the first clipped step."""
+        if self.gc_state is None:
+            return None
+        return self._stats(self.gc_state[:L.GC_NSTAT].cpu().tolist())
+
+    @staticmethod
+    def _stats(s) -> dict:
+        return dict(sum=s[L.GC_SUM], max=s[L.GC_MAX], clipped=int(s[L.GC_CLIPPED]), last=s[L.GC_LAST])
+
+    def loss_and_grad_stats(self):
+        """(loss_acc as a list, grad_stats()) in ONE device-to-host copy: what a trainer reads at the end of a clipped epoch."""
+        v = torch.cat([self.loss_acc, self.ensure_gc_state()[:L.GC_NSTAT]]).cpu().tolist()
+        return v[:2], self._stats(v[2:])
+
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
-                   dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None) -> None:
+                   dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
-        class_weight: (K,) float32 device tensor = criterion CrossEntropyLoss(weight=class_weight) (msig_cw_train_step)."""
+        class_weight: (K,) float32 device tensor = criterion CrossEntropyLoss(weight=class_weight) (msig_cw_train_step).
+        max_grad_norm: torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) between loss.backward() and
+        optimizer.step() (msig_gc_train_step, DESIGN.md §15): `grads` then holds the clipped gradient and grad_stats() the norms;
+        float('inf') measures without clipping; None = the calls above, unchanged."""
         cw = self._class_weight(class_weight)
+        max_norm = None if max_grad_norm is None else L.check_max_grad_norm(max_grad_norm)
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
+        if max_norm is not None:
+            state = self.ensure_gc_state()
+            g = L.GcClip()
+            g.kind, g.class_weight, g.state, g.state_bytes = L.GC_KINDS[self.kind], cw, state.data_ptr(), state.numel() * 8
+            g.max_norm[0] = max_norm
+            L.check(L.lib().msig_gc_train_step(C.byref(b), C.byref(g), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
+                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_gc_train_step")
+            return
         if self.kind == "cnn_gru":
             L.check(L.lib().msig_cg_train_step(C.byref(b), cw, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
                                                betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_cg_train_step")
@@ -390,10 +433,13 @@ class EmbeddedEngine(Engine):
         self.scatter()
         return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight)
 
-    def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None):
+    def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
+                   max_grad_norm=None):
         self._class_weight(class_weight)
+        if max_grad_norm is not None:
+            L.check_max_grad_norm(max_grad_norm)
         self.scatter()
-        super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight)
+        super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -420,11 +466,14 @@ class FoldArena:
     same offsets — which is all msig_*_multi needs to run the same step for several folds in one set of launches."""
 
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
-                 adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention"):
+                 adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
+                 grad_clip: bool = False):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
-        `kind`: the model kind of every fold (Engine); it sizes the arenas from its layout.  A fold batch is uniform in kind too."""
+        `kind`: the model kind of every fold (Engine); it sizes the arenas from its layout.  A fold batch is uniform in kind too.
+        `grad_clip`: the arenas also hold a "gc" region, each fold's clip state (include/msig_gc.h), after every other region —
+        without it the arenas and their stride are what they are without this argument."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -443,6 +492,10 @@ class FoldArena:
         sizes = [("params", self.n_flat * 4), ("grads", self.n_flat * 4), ("exp_avg", self.n_flat * 4), ("exp_avg_sq", self.n_flat * 4),
                  ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16), ("acc", 16), ("x", self.max_batch * in_channels * T * 4), ("y", self.max_batch * 8),
                  ("ws", self.ws_bytes), ("cw", num_classes * 4)]
+        self.grad_clip = bool(grad_clip)
+        if self.grad_clip:
+            sizes.append(("gc", L.gc_state_bytes(in_channels, num_classes, kind)))
+        self.max_norm = [float("inf")] * n              # per arena: max_norm of the fold in it (set_max_norm); inf = measured, not clipped
         self.off, at = {}, 0
         for name, nbytes in sizes:
             self.off[name] = (at, nbytes)
@@ -479,6 +532,8 @@ class FoldArena:
         st["bn_count"] = self.view(slot, "bn_count", torch.int64)
         st["acc"] = self.view(slot, "acc", torch.float64)
         st["ws"] = self.view(slot, "ws")
+        if self.grad_clip:
+            st["gc"] = self.view(slot, "gc", torch.float64)
         if self.gru_layers == 1:
             return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st, kind=self.kind)
         return Engine(self.C, self.K, self.device, storage=st, kind=self.kind)
@@ -492,6 +547,34 @@ class FoldArena:
         bit for bit, so an unweighted fold can share launches with weighted ones."""
         w = L.check_class_weight(values, self.K)
         self.view(slot, "cw", torch.float32).copy_(torch.as_tensor(w, dtype=torch.float32))
+
+    def set_max_norm(self, slot: int, value) -> None:
+        """max_norm of the fold in arena `slot` (checked on the host: ValueError); float('inf') = its norms are measured, nothing is clipped."""
+        if not self.grad_clip:
+            raise RuntimeError("this FoldArena was built without grad_clip=True: it has no clip state")
+        self.max_norm[slot] = L.check_max_grad_norm(value)
+
+    def clip(self, slots, class_weight: Optional[int] = None) -> L.GcClip:
+        """msig_gc_clip of a launch over `slots` (msig_gc_train_step_multi): arena 0's clip state, every fold's own max_norm."""
+        if not self.grad_clip:
+            raise RuntimeError("this FoldArena was built without grad_clip=True: it has no clip state")
+        g = L.GcClip()
+        g.kind, g.class_weight, g.state, g.state_bytes = L.GC_KINDS[self.kind], class_weight, self.ptr("gc"), self.off["gc"][1]
+        for i, s in enumerate(slots):
+            g.max_norm[i] = self.max_norm[int(s)]
+        return g
+
+    def zero_grad_stats(self, slots=None) -> None:
+        st = self.across("gc", 0, torch.float64, L.GC_NSTAT)
+        if slots is None:
+            st.zero_()
+        else:
+            st.index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
+
+    def grad_stats(self, slot: int) -> dict:
+        """Gradient-norm statistics of the fold in arena `slot` since zero_grad_stats (Engine.grad_stats; one read-back)."""
+        s = self.view(slot, "gc", torch.float64)[:L.GC_NSTAT].cpu().tolist()
+        return dict(sum=s[L.GC_SUM], max=s[L.GC_MAX], clipped=int(s[L.GC_CLIPPED]), last=s[L.GC_LAST])
 
     def batch(self, B: int, training: bool, dropout_p: float, with_labels: bool = True) -> L.Batch:
         """msig_batch describing arena 0 (the *_multi calls shift every pointer by slot * stride)."""

@@ -17,6 +17,9 @@ HIGHER monitored value as better although it is fed the validation loss; the cla
 option is accepted and ignored (the reference's branch is unreachable, trainer.py:81).
 The class-weighted loss that branch would build is opted into through a key of this repo's
 own, ``config['trainer']['class_weights']`` (include/msig_cw.h).
+``config['trainer']['max_grad_norm']``, another key of this repo's own, puts
+``torch.nn.utils.clip_grad_norm_`` between the backward pass and Adam inside the fused step
+(include/msig_gc.h) and adds the epoch's gradient norms to ``history`` and the log.
 """
 from __future__ import annotations
 
@@ -132,6 +135,22 @@ def class_weight_setting(value, num_classes: int):
     return L.check_class_weight(value, num_classes)
 
 
+def grad_clip_setting(value):
+    """config['trainer']['max_grad_norm']: None (no clipping: the unclipped train step) or a positive finite number (ValueError
+    otherwise), returned as a float."""
+    if value is None:
+        return None
+    v = L.check_max_grad_norm(value)          # a number > 0; the binding also takes inf ("measure, do not clip"), a configuration does not
+    if v == float("inf"):
+        raise ValueError(f"max_grad_norm must be None or a positive finite number, got {value!r}")
+    return v
+
+
+def grad_norm_summary(stats, steps: int) -> dict:
+    """The history entries of an epoch's gradient norms from a clip state's statistics (runtime.Engine.grad_stats) over `steps` steps."""
+    return dict(grad_norm_mean=stats["sum"] / max(steps, 1), grad_norm_max=stats["max"], clipped_steps=int(stats["clipped"]))
+
+
 class Trainer:
     def __init__(self, model, fold_output_dir: Path, config):
         self.model, self.fold_dir, self.config = model, Path(fold_output_dir), config
@@ -151,6 +170,8 @@ class Trainer:
         # (from the training loader's labels, when training starts) or K numbers.  class_weight: the (K,) fp32 device vector once set
         self.class_weights = class_weight_setting(cfg.get("class_weights"), self.model.num_classes)
         self.class_weight = None
+        # clip_grad_norm_(model.parameters(), max_grad_norm) inside the fused step (include/msig_gc.h); None: the unclipped step
+        self.max_grad_norm = grad_clip_setting(cfg.get("max_grad_norm"))
         self.verbose = cfg.get("verbose", True)
         self.optimizer = MsigAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)   # trainer.py:68
         self.scheduler = ReduceLROnPlateau(self.optimizer, mode="min", factor=0.1, patience=3)         # trainer.py:72-77
@@ -217,30 +238,44 @@ class Trainer:
             t0 = time.time()
             self.model.train()
             eng.loss_acc.zero_()
+            if self.max_grad_norm is not None:
+                eng.zero_grad_stats()
+            n_steps = 0
             for inputs, labels in train_loader:
+                n_steps += 1
                 x, y = self._to_device(inputs, labels)
                 h = self.optimizer.hyper
                 self.optimizer.step_count += 1
                 eng.train_step(x, y, lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
                                step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
-                               class_weight=self.class_weight)
+                               class_weight=self.class_weight, max_grad_norm=self.max_grad_norm)
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
-            train_loss = float(eng.loss_acc[0].item()) / n_train                        # the epoch's only sync
+            if self.max_grad_norm is None:
+                train_loss, grad = float(eng.loss_acc[0].item()) / n_train, None         # the epoch's only sync
+            else:                                                                        # the same sync: one read-back for both
+                acc, stats = eng.loss_and_grad_stats()
+                train_loss, grad = acc[0] / n_train, grad_norm_summary(stats, n_steps)
             dt = time.time() - t0
             self.train_windows += n_train
             self.train_seconds += dt
             val_loss, val_acc, val_f1, _, _ = self.evaluate(val_loader, is_val=True)
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1):
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad):
                 break
         self._finish_training()
 
-    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1) -> bool:
-        """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training."""
+    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None) -> bool:
+        """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
+        the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
+        suffix = ""
+        if grad is not None:
+            self.history[-1].update(grad)
+            suffix = (f" | 梯度范数: {grad['grad_norm_mean']:.4f} (max {grad['grad_norm_max']:.4f}) | "
+                      f"裁剪步数: {grad['clipped_steps']} (max_grad_norm={self.max_grad_norm:g})")
         self._log(f"Epoch {epoch + 1}/{self.epochs} | 耗时: {dt:.2f}s | 训练损失: {train_loss:.4f} | 验证损失: {val_loss:.4f} | "
-                  f"验证Acc: {val_acc:.4f} | 验证F1: {val_f1:.4f} | {n_train / max(dt, 1e-9):.0f} windows/s")
+                  f"验证Acc: {val_acc:.4f} | 验证F1: {val_f1:.4f} | {n_train / max(dt, 1e-9):.0f} windows/s" + suffix)
         if self.early_stopping:
             self.early_stopping(val_loss, self.model)
             if self.early_stopping.early_stop:
