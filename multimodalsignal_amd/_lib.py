@@ -1,4 +1,5 @@
-"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h).
+"""ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
+include/msig_aug.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -82,6 +83,8 @@ CW_ABI_VERSION = 1    # include/msig_cw.h MSIG_CW_ABI_VERSION (class-weighted Cr
 CG_ABI_VERSION = 1    # include/msig_cg.h MSIG_CG_ABI_VERSION (the cnn_gru baseline)
 FT_ABI_VERSION = 1    # include/msig_ft.h MSIG_FT_ABI_VERSION (window embeddings, classifier-only head epochs)
 GC_ABI_VERSION = 1    # include/msig_gc.h MSIG_GC_ABI_VERSION (gradient-norm clipping inside the fused train steps)
+AUG_ABI_VERSION = 1   # include/msig_aug.h MSIG_AUG_ABI_VERSION (window augmentation inside the training gather)
+AUG_STREAM_ID = 3     # msig_aug.h MSIG_AUG_STREAM_ID: msig_dropout_key's stream of the augmentation keys (1, 2: GRU and head dropout)
 FT_MAX_BATCH, FT_MAX_N = 256, 1 << 24
 FT_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_FT_KIND_*
 
@@ -119,6 +122,12 @@ class GcClip(C.Structure):
     and max_norm per fold of the launch."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("class_weight", C.c_void_p), ("state", C.c_void_p),
                 ("state_bytes", C.c_int64), ("max_norm", C.c_double * MAX_FOLDS)]
+
+
+class Aug(C.Structure):
+    """msig_aug (include/msig_aug.h): the augmentation of a gather launch — the four transforms' parameters and a key per fold."""
+    _fields_ = [("scale_sigma", C.c_float), ("jitter_sigma", C.c_float), ("mask_prob", C.c_float), ("chan_drop_prob", C.c_float),
+                ("mask_max", C.c_int32), ("reserved", C.c_int32), ("key", C.c_uint32 * MAX_FOLDS)]
 
 
 _lib = None
@@ -240,6 +249,15 @@ def lib() -> C.CDLL:
         L.msig_gc_state_bytes.restype = C.c_int64
         L.msig_gc_train_step.argtypes = [C.POINTER(Batch), C.POINTER(GcClip), vp, vp, f32, f32, f32, f32, f32, i64, vp]
         L.msig_gc_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(GcClip), vp, vp, f32, f32, f32, f32, i64, vp]
+        # include/msig_aug.h, exported by the same library: the gathers with on-device window augmentation
+        L.msig_aug_abi_version.restype = C.c_int
+        L.msig_aug_struct_bytes.restype = C.c_int64
+        if L.msig_aug_abi_version() != AUG_ABI_VERSION or L.msig_aug_struct_bytes() != C.sizeof(Aug):
+            raise RuntimeError(f"{LIB_PATH} has msig_aug.h ABI {L.msig_aug_abi_version()} with msig_aug of {L.msig_aug_struct_bytes()} bytes; "
+                               f"this binding is {AUG_ABI_VERSION} with {C.sizeof(Aug)}: rebuild the library")
+        i32 = C.c_int32
+        L.msig_aug_gather_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(Aug), vp]
+        L.msig_aug_gather_windows_multi.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, C.POINTER(Multi), C.POINTER(Aug), vp]
         _lib = L
     return _lib
 

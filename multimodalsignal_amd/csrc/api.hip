@@ -357,6 +357,11 @@ static int make_fold_ctx(const msig_batch* b, const msig_multi* m, FoldCtx& fc) 
   }
   return 0;
 }
+// msig_multi's own checks for a call that has no msig_batch (augment.hip)
+int msig_multi_fold_ctx(const msig_multi* m, FoldCtx& fc) {
+  msig_batch dummy{};
+  return make_fold_ctx(&dummy, m, fc);
+}
 extern "C" int msig_forward_multi(const msig_batch* b, const msig_multi* m, void* stream) {
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return forward_fc(b, fc, (hipStream_t)stream);

@@ -246,9 +246,13 @@ class StoreView:
 
 class DeviceLoader:
     """Iterates (x, y) device batches of a WesadDataset without touching the host per step.
-    Same iteration contract as ``DataLoader(ds, batch_size, shuffle)`` (no drop_last)."""
+    Same iteration contract as ``DataLoader(ds, batch_size, shuffle)`` (no drop_last).
 
-    def __init__(self, dataset: WesadDataset, batch_size: int, shuffle: bool, device, seed: Optional[int] = None):
+    `augment` (an ``augment.Augment``; training loaders only): every batch is one ``msig_aug_gather_windows`` launch instead, keyed
+    by (`aug_seed` = the loader's seed, `aug_step` = the batches this loader has served so far, counted from 1) — the same windows
+    are augmented differently in every epoch, and two loaders with one seed serve the same batches.  None: the plain gather."""
+
+    def __init__(self, dataset: WesadDataset, batch_size: int, shuffle: bool, device, seed: Optional[int] = None, augment=None):
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.device = torch.device(device)
         self.store, self.store_y = dataset.device_tensors(self.device)
@@ -256,6 +260,10 @@ class DeviceLoader:
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(torch.initial_seed() if seed is None else seed)
         self._bufs = {}
+        self.augment = None if augment is None or augment.off else augment       # all transforms at 0 is the plain gather: take it
+        self.aug_seed, self.aug_step = int(torch.initial_seed() if seed is None else seed), 0
+        if self.augment is not None:
+            self.augment.check_window(int(self.store.shape[2]))
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
@@ -280,6 +288,14 @@ class DeviceLoader:
                 self._bufs[b] = [(torch.empty((b,) + tuple(self.store.shape[1:]), device=self.device),
                                   torch.empty(b, dtype=torch.int64, device=self.device)) for _ in range(2)]
             ox, oy = self._bufs[b][(i // self.batch_size) & 1]
+            if self.augment is not None:
+                self.aug_step += 1
+                a = self.augment.struct([L.dropout_key(self.aug_seed, self.aug_step, L.AUG_STREAM_ID)])
+                L.check(L.lib().msig_aug_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, self.store.shape[1],
+                                                        self.store.shape[2], ox.data_ptr(), oy.data_ptr(), C.byref(a), st),
+                        "msig_aug_gather_windows")
+                yield ox, oy
+                continue
             L.check(L.lib().msig_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, wfl,
                                                 ox.data_ptr(), oy.data_ptr(), st), "msig_gather_windows")
             yield ox, oy

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .augment import Augment
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
@@ -120,7 +121,8 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
     # Evaluation runs in eval mode (running BN statistics, no dropout), so its predictions do not depend on how the
     # windows are batched; only the summation order of the reported loss does (~1e-7 relative).
     ebs = int(cfg.get("eval_batch_size") or cfg["batch_size"])
-    loaders = (DeviceLoader(train_ds, cfg["batch_size"], shuffle, device, seed=seed),
+    # cfg["augment"] (--augment SPEC, include/msig_aug.h): the TRAINING loader's gather augments; validation and test never do
+    loaders = (DeviceLoader(train_ds, cfg["batch_size"], shuffle, device, seed=seed, augment=Augment.coerce(cfg.get("augment"))),
                DeviceLoader(val_ds, ebs, False, device), DeviceLoader(datasets([subject]), ebs, False, device))
     model = make_model(cfg, in_channels, num_classes, params)
     model.set_dropout_seed(seed * 0x9E3779B97F4A7C15 + 12345)
@@ -170,6 +172,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
         if cfg.get("max_grad_norm") is not None:                    # likewise
             f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
+        if cfg.get("augment") is not None:                          # likewise
+            f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -555,6 +559,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
             if cfg.get("max_grad_norm") is not None:
                 f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
+            if cfg.get("augment") is not None:
+                f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
             f.write("\n")
             for r in results:
                 f.write(f"  - 测试 {r['subject']}: M1 Accuracy = {r['m1_accuracy']:.4f}, 三分类 Accuracy = {r['ternary_accuracy']:.4f}\n")
@@ -600,6 +606,13 @@ def parse_args(ap, argv=None):
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
         ap.error(f"--max-grad-norm: {e}")
+    if args.augment is not None:
+        try:
+            args.augment = Augment.parse(args.augment)
+            if args.synthetic is not None:          # its window length is known here; a data directory's when the loaders are made
+                args.augment.check_window(args.samples)
+        except ValueError as e:
+            ap.error(f"--augment: {e}")
     return args
 
 
@@ -641,6 +654,11 @@ def build_parser():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="torch.nn.utils.clip_grad_norm_(model.parameters(), X) between backward and Adam inside the fused train step "
                          "(every mode: LOSO, --ablation, --hierarchical, --model, sequential); logs each epoch's gradient norms")
+    ap.add_argument("--augment", default=None, metavar="SPEC",
+                    help="augment every training batch inside its gather launch, e.g. scale=0.1,jitter=0.05,mask=0.5:320,chandrop=0.1: "
+                         "per-channel gain 1 + scale * g, additive noise jitter * g per sample, with probability mask=P one zeroed span of "
+                         "1..N samples per window, each channel zeroed with probability chandrop (every mode: LOSO, --ablation, "
+                         "--hierarchical, --model, sequential; validation, test and --calibrate never augment)")
     ap.add_argument("--model", nargs="+", choices=list(MODEL_PARAMS), default=[MODEL_TO_USE],
                     help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
                          "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
@@ -656,6 +674,28 @@ def build_parser():
     ap.add_argument("--calibration-sequential", action="store_true",
                     help="calibrate with one launch per fold and epoch instead of one per epoch for all folds of a rank (the same bits)")
     return ap
+
+
+def build_cfg(args, kinds):
+    """The configuration of the parsed command line, before the data set is known (no GPU needed); keys of optional features
+    (max_grad_norm, augment, calibrate ...) exist only when their flag was given."""
+    cfg = default_cfg()
+    cfg.update(epochs=args.epochs, patience=args.patience[0] if len(args.patience) == 1 else list(args.patience), batch_size=args.batch_size,
+               verbose=args.verbose,
+               concurrent_folds=args.concurrent_folds, normalise=args.normalise, eval_batch_size=args.eval_batch_size,
+               lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms,
+               class_weights=args.class_weights, model=kinds[0], model_params=dict(MODEL_PARAMS[kinds[0]]))
+    if args.max_grad_norm is not None:      # without the flag the configuration has no such key
+        cfg["max_grad_norm"] = args.max_grad_norm
+    if args.augment is not None:            # likewise
+        cfg["augment"] = args.augment
+    if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
+        cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
+        for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),
+                         ("calibration_lr", args.calibration_lr)):
+            if val is not None:
+                cfg[key] = val
+    return cfg
 
 
 def main(argv=None):
@@ -681,20 +721,7 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=device)
         else:
             dist.init_process_group(backend)
-    cfg = default_cfg()
-    cfg.update(epochs=args.epochs, patience=args.patience[0] if len(args.patience) == 1 else list(args.patience), batch_size=args.batch_size,
-               verbose=args.verbose,
-               concurrent_folds=args.concurrent_folds, normalise=args.normalise, eval_batch_size=args.eval_batch_size,
-               lockstep=not args.no_lockstep, lockstep_groups=args.lockstep_groups, adaptive_forms=args.adaptive_forms,
-               class_weights=args.class_weights, model=kinds[0], model_params=dict(MODEL_PARAMS[kinds[0]]))
-    if args.max_grad_norm is not None:      # without the flag the configuration has no such key
-        cfg["max_grad_norm"] = args.max_grad_norm
-    if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
-        cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
-        for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),
-                         ("calibration_lr", args.calibration_lr)):
-            if val is not None:
-                cfg[key] = val
+    cfg = build_cfg(args, kinds)
     if args.synthetic is not None:
         from .synth import CHANNELS6, make_synthetic_wesad
         if rank == 0 and not (args.synthetic / "_channel_names.txt").exists():

@@ -113,6 +113,12 @@ class LockstepTrainer:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
         self.grad_stats = {}
+        # window augmentation inside the gather (include/msig_aug.h): the training loaders carry it; a launch has ONE set of
+        # parameters, so the folds of a batch must agree on them — their keys are per fold (each loader's own seed and batch count)
+        augs = [getattr(p["loaders"][0], "augment", None) for p in preps]
+        if any(a != augs[0] for a in augs):
+            raise ValueError(f"lockstep folds must share one augmentation, got {sorted({repr(a) for a in augs})}")
+        self.augment = augs[0]
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
@@ -151,8 +157,16 @@ class LockstepTrainer:
             self._layouts[key] = (off, self.arena.batch(B, training, self.trainers[0].model.dropout_p if training else 0.0))
         return self._layouts[key]
 
-    def _gather(self, loader, order_mat, row0, i, b, m):
-        """order_mat: (folds, n_max) int64 store positions of the pass; gathers columns i .. i+b of rows row0 .. row0+m.n."""
+    def _gather(self, loader, order_mat, row0, i, b, m, aug=None):
+        """order_mat: (folds, n_max) int64 store positions of the pass; gathers columns i .. i+b of rows row0 .. row0+m.n.
+        aug: the msig_aug of a training launch whose loaders augment (its keys filled for the folds of `m`)."""
+        if aug is not None:
+            L.check(L.lib().msig_aug_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
+                                                          order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b,
+                                                          loader.store.shape[1], loader.store.shape[2], self.arena.ptr("x"), self.arena.ptr("y"),
+                                                          C.byref(m), C.byref(aug), self._stream()),
+                    "msig_aug_gather_windows_multi")
+            return
         wfl = loader.store.shape[1] * loader.store.shape[2]
         L.check(L.lib().msig_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
                                                   order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b, wfl,
@@ -197,6 +211,10 @@ class LockstepTrainer:
         steps = [np.arange(s0 + 1, s0 + 1 + ns) for s0, ns in zip(step0, n_steps)]
         kg = [L.dropout_keys(t.model._seed, st, 1) if thr else np.zeros(len(st), np.uint32) for t, st in zip(trs, steps)]
         kh = [L.dropout_keys(t.model._seed, st, 2) if thr else np.zeros(len(st), np.uint32) for t, st in zip(trs, steps)]
+        # augmentation keys: per fold from its own loader's (seed, batches served so far), as its sequential iteration draws them
+        aug = self.augment.struct() if self.augment is not None else None
+        ka = [L.dropout_keys(ld.aug_seed, np.arange(ld.aug_step + 1, ld.aug_step + 1 + ns), L.AUG_STREAM_ID)
+              for ld, ns in zip(loaders, n_steps)] if aug is not None else None
         lrs = [t.optimizer.hyper["lr"] for t in trs]
         h0 = trs[0].optimizer.hyper
         b1, b2, eps, wd = h0["betas"][0], h0["betas"][1], h0["eps"], h0["weight_decay"]
@@ -210,7 +228,10 @@ class LockstepTrainer:
             m = multis[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
-            self._gather(loaders[0], order, r0, i, b, m)
+            if aug is not None:
+                for j in range(nr):
+                    aug.key[j] = int(ka[r0 + j][k])
+            self._gather(loaders[0], order, r0, i, b, m, aug)
             _, desc = self._layout(b, True)
             if self.clip:
                 if (r0, nr, "gc") not in multis:
@@ -222,6 +243,9 @@ class LockstepTrainer:
                     train_multi.__name__)           # self.cw None: exactly msig_train_step_multi (msig_cg_*: the baseline)
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
+        if aug is not None:
+            for ld, ns in zip(loaders, n_steps):
+                ld.aug_step += ns
         if not self.clip:
             return self.acc[:, 0].cpu().numpy()               # the epoch's only sync
         # the same sync: the loss sums and the folds' gradient-norm statistics in one read-back
