@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h).
+include/msig_aug.h, include/msig_st.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -85,6 +85,8 @@ FT_ABI_VERSION = 1    # include/msig_ft.h MSIG_FT_ABI_VERSION (window embeddings
 GC_ABI_VERSION = 1    # include/msig_gc.h MSIG_GC_ABI_VERSION (gradient-norm clipping inside the fused train steps)
 AUG_ABI_VERSION = 1   # include/msig_aug.h MSIG_AUG_ABI_VERSION (window augmentation inside the training gather)
 AUG_STREAM_ID = 3     # msig_aug.h MSIG_AUG_STREAM_ID: msig_dropout_key's stream of the augmentation keys (1, 2: GRU and head dropout)
+ST_ABI_VERSION = 1    # include/msig_st.h MSIG_ST_ABI_VERSION (label smoothing and mixup in the criterion and the training gather)
+ST_STREAM_ID = 4      # msig_st.h MSIG_ST_STREAM_ID: msig_dropout_key's stream of the mixup draws
 FT_MAX_BATCH, FT_MAX_N = 256, 1 << 24
 FT_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_FT_KIND_*
 
@@ -128,6 +130,24 @@ class Aug(C.Structure):
     """msig_aug (include/msig_aug.h): the augmentation of a gather launch — the four transforms' parameters and a key per fold."""
     _fields_ = [("scale_sigma", C.c_float), ("jitter_sigma", C.c_float), ("mask_prob", C.c_float), ("chan_drop_prob", C.c_float),
                 ("mask_max", C.c_int32), ("reserved", C.c_int32), ("key", C.c_uint32 * MAX_FOLDS)]
+
+
+class St(C.Structure):
+    """msig_st (include/msig_st.h): the soft targets of a launch — model kind, label smoothing, optional class weights, an optional
+    msig_gc_clip (by address: `make_st` keeps it alive) and the mixup weight of every fold."""
+    _fields_ = [("kind", C.c_int32), ("smoothing", C.c_float), ("class_weight", C.c_void_p), ("clip", C.c_void_p),
+                ("lam", C.c_float * MAX_FOLDS)]
+
+
+def make_st(kind: str, smoothing: float, class_weight=None, clip: "GcClip" = None, lams=(1.0,)) -> St:
+    """msig_st of model kind `kind` with the given smoothing, class-weight device pointer, clip and per-fold lam."""
+    s = St()
+    s.kind, s.smoothing, s.class_weight = GC_KINDS[check_kind(kind)], float(smoothing), class_weight
+    s._clip = clip                      # the struct holds only its address
+    s.clip = C.addressof(clip) if clip is not None else None
+    for i in range(MAX_FOLDS):
+        s.lam[i] = float(lams[i]) if i < len(lams) else 1.0
+    return s
 
 
 _lib = None
@@ -258,6 +278,18 @@ def lib() -> C.CDLL:
         i32 = C.c_int32
         L.msig_aug_gather_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(Aug), vp]
         L.msig_aug_gather_windows_multi.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, C.POINTER(Multi), C.POINTER(Aug), vp]
+        # include/msig_st.h, exported by the same library: soft targets (label smoothing, mixup)
+        L.msig_st_abi_version.restype = C.c_int
+        L.msig_st_struct_bytes.restype = C.c_int64
+        if L.msig_st_abi_version() != ST_ABI_VERSION or L.msig_st_struct_bytes() != C.sizeof(St):
+            raise RuntimeError(f"{LIB_PATH} has msig_st.h ABI {L.msig_st_abi_version()} with msig_st of {L.msig_st_struct_bytes()} bytes; "
+                               f"this binding is {ST_ABI_VERSION} with {C.sizeof(St)}: rebuild the library")
+        L.msig_st_forward.argtypes = [C.POINTER(Batch), C.POINTER(St), vp]
+        L.msig_st_forward_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), vp]
+        L.msig_st_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_st_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), vp, vp, f32, f32, f32, f32, i64, vp]
+        L.msig_st_gather_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(Aug), C.POINTER(f32), vp]
+        L.msig_st_gather_windows_multi.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, C.POINTER(Multi), C.POINTER(Aug), C.POINTER(f32), vp]
         _lib = L
     return _lib
 
@@ -365,6 +397,37 @@ def check_max_grad_norm(value) -> float:
     if not v > 0.0:
         raise ValueError(f"max_grad_norm must be a positive number, got {value!r}")
     return v
+
+
+def check_label_smoothing(value) -> float:
+    """The host-side check of a label smoothing (include/msig_st.h): None or a number with 0 <= eps < 1 as the C calls see it (fp32).
+    Returns the float (0.0 for None); ValueError otherwise."""
+    if value is None:
+        return 0.0
+    if isinstance(value, (str, bytes, bool)):
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {value!r}")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {value!r}") from None
+    if not 0.0 <= v < 1.0 or C.c_float(v).value >= 1.0:
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {value!r}")
+    return v
+
+
+def check_mix_lambda(value) -> float:
+    """The host-side check of a mixup weight (include/msig_st.h): None (1.0, no mixing) or a number in [0, 1].  ValueError otherwise."""
+    if value is None:
+        return 1.0
+    if isinstance(value, (str, bytes, bool)):
+        raise ValueError(f"mix_lambda must be a number in [0, 1], got {value!r}")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"mix_lambda must be a number in [0, 1], got {value!r}") from None
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"mix_lambda must be a number in [0, 1], got {value!r}")
+    return C.c_float(v).value
 
 
 FORM_AUTO = -1

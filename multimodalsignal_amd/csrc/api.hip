@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h and msig_gc.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h and msig_st.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -10,6 +10,7 @@
 #include "msig_dev.h"
 #include "../../include/msig_cw.h"
 #include "../../include/msig_cg.h"
+#include "../../include/msig_st.h"
 #include "finetune.h"
 
 // ---- profiling aid --------------------------------------------------------------
@@ -258,14 +259,15 @@ extern "C" int msig_frontend_bwd(const msig_batch* b, void* stream) {
 }
 
 // cw: class weights of include/msig_cw.h (NULL = the msig.h call); cg: CnnGruModel (include/msig_cg.h)
+// soft: soft targets of include/msig_st.h (NULL = the plain criterion's kernels)
 static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true, const float* cw = nullptr,
-                      bool cg = false) {
+                      bool cg = false, const SoftArgs* soft = nullptr) {
   if (b->dx && fc.stride != 0) return MSIG_E_SHAPE;          // no input gradients in fold batches
   Ctx c; int rc = make_ctx(b, c, false, cg); if (rc) return rc;
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;      // nothing has been launched: no model state has changed
   if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st, !cg))) return rc;
   if ((rc = launch_gru_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
-  return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st, cw) : 0;
+  return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st, cw, soft) : 0;
 }
 extern "C" int msig_forward(const msig_batch* b, void* stream) {
   if (!b) return MSIG_E_NULL;
@@ -297,7 +299,7 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
 // fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch)
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
                          float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr, bool cg = false,
-                         const ClipArgs* clip = nullptr) {
+                         const ClipArgs* clip = nullptr, const SoftArgs* soft = nullptr) {
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
   if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
@@ -313,11 +315,11 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
   const bool head_step = head_step_applies(b, c.d);
-  if ((rc = forward_fc(b, fc, st, !head_step, cw, cg))) return rc;
+  if ((rc = forward_fc(b, fc, st, !head_step, cw, cg, soft))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
-  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, cw) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
+  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, cw, soft) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
@@ -479,6 +481,64 @@ extern "C" int msig_gc_train_step_multi(const msig_batch* b, const msig_multi* m
   ClipArgs cl; if ((rc = make_clip(b, g, fc.n, cl))) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
                        g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl);
+}
+
+// ---- soft targets (include/msig_st.h): label smoothing and mixup in the criterion of the same calls ------------------------------
+extern "C" int msig_st_abi_version(void) { return MSIG_ST_ABI_VERSION; }
+extern "C" int64_t msig_st_struct_bytes(void) { return (int64_t)sizeof(msig_st); }
+
+// every check of msig_st.h's own arguments, before the counterpart's and before any launch; n = folds of the launch.  use = false:
+// smoothing 0 and every lam 1 — the call is its counterpart (soft stays unused: the same launches).
+static int make_soft(const msig_st* s, int n, SoftArgs& soft, bool& use) {
+  if (!s) return MSIG_E_NULL;
+  if (s->kind != MSIG_GC_KIND_ATTENTION && s->kind != MSIG_GC_KIND_CNN_GRU) return MSIG_E_SHAPE;
+  if (!(s->smoothing >= 0.f && s->smoothing < 1.f)) return MSIG_E_SHAPE;                 // NaN included
+  soft = SoftArgs{};
+  soft.eps = s->smoothing;
+  use = s->smoothing != 0.f;
+  for (int i = 0; i < n; ++i) {
+    if (!(s->lam[i] >= 0.f && s->lam[i] <= 1.f)) return MSIG_E_SHAPE;
+    soft.lam[i] = s->lam[i];
+    use = use || s->lam[i] != 1.f;
+  }
+  for (int i = n; i < MSIG_MAX_FOLDS; ++i) soft.lam[i] = 1.f;
+  if (cw_misaligned(s->class_weight)) return MSIG_E_ALIGN;
+  return 0;
+}
+static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, hipStream_t st) {
+  SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
+  if (!b) return MSIG_E_NULL;
+  return forward_fc(b, fc, st, true, s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, use ? &soft : nullptr);
+}
+static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
+                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st) {
+  SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
+  if (!b) return MSIG_E_NULL;
+  ClipArgs cl;
+  if (s->clip) {
+    if (s->clip->kind != s->kind) return MSIG_E_SHAPE;
+    if ((rc = make_clip(b, s->clip, fc.n, cl))) return rc;
+  }
+  return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st, s->class_weight,
+                       s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr);
+}
+extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
+  return st_forward(b, single_fold(b), s, (hipStream_t)stream);
+}
+extern "C" int msig_st_forward_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return st_forward(b, fc, s, (hipStream_t)stream);
+}
+extern "C" int msig_st_train_step(const msig_batch* b, const msig_st* s, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int64_t step, void* stream) {
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+extern "C" int msig_st_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, float* exp_avg, float* exp_avg_sq,
+                                        float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

@@ -5,6 +5,7 @@
 #include <math.h>
 #include "msig_dev.h"
 #include "../../include/msig_aug.h"
+#include "../../include/msig_st.h"
 
 int launch_gather(const float* store, const int64_t* sy, const int64_t* idx, int64_t idx_row_stride, int B, int64_t wfloats, float* ox, int64_t* oy,
                   const FoldCtx& fc, hipStream_t st);                                        // head.hip: the plain gather
@@ -93,6 +94,87 @@ __global__ __launch_bounds__(256) void aug_gather_kernel(const float* __restrict
   }
 }
 
+// ---- the gather with mixup (include/msig_st.h): out[b] = lam * A_b + mu * A_{B-1-b}, A_r the window of batch
+// row r after that row's own transforms above ("augment the batch, then mix it"); with every transform off A_r is the plain window.
+// AugRowChan is what aug_gather_kernel draws per (row, channel), aug_vec4 one float4 of A_r: the same statements in the same order,
+// every fp32 operation one rounding (contraction is off), so A_r has aug_gather_kernel's bits.  A fold whose lam is 1 — uniform,
+// blockIdx.z — stores A_b itself: the plain or augmented gather's bits, not a + 0 * b (which turns -0.0 into +0.0).
+struct MixLam { float lam[MSIG_MAX_FOLDS]; };
+struct AugRowChan { const float4* s4; uint32_t ck; int m0, m1; float gain; bool zero, scale; };
+
+__device__ __forceinline__ AugRowChan aug_row_chan(const float* __restrict__ store, int64_t src, int row, int c, int C, int T4, const AugArgs& a,
+                                                   uint32_t key) {
+  AugRowChan r;
+  r.s4 = (const float4*)(store) + (src * C + c) * T4;
+  const uint32_t rk = aug_row_key(key, (uint32_t)row);
+  r.ck = aug_chan_key(rk, (uint32_t)c);
+  r.zero = false; r.m0 = 0; r.m1 = 0;
+  if (a.cdrop_on && fmix32(r.ck ^ AUG_TAG_CDROP) <= a.cdrop_thr) {
+    bool all = true;
+    for (int cc = 0; cc < C; ++cc) all = all && fmix32(aug_chan_key(rk, (uint32_t)cc) ^ AUG_TAG_CDROP) <= a.cdrop_thr;
+    r.zero = !(all && (int)aug_mulhi(fmix32(rk ^ AUG_TAG_KEEP), (uint32_t)C) == c);
+  }
+  if (a.mask_on && fmix32(rk ^ AUG_TAG_MASK) <= a.mask_thr) {
+    const int len = 1 + (int)aug_mulhi(fmix32(rk ^ AUG_TAG_MLEN), (uint32_t)a.mask_max);
+    r.m0 = (int)aug_mulhi(fmix32(rk ^ AUG_TAG_MT0), (uint32_t)(a.T - len + 1));
+    r.m1 = r.m0 + len;
+  }
+  r.scale = a.scale_sigma != 0.f;
+  r.gain = r.scale ? aug_fadd(1.f, aug_fmul(a.scale_sigma, aug_noise(fmix32(r.ck ^ AUG_TAG_SCALE)))) : 1.f;
+  return r;
+}
+template <bool JITTER>
+__device__ __forceinline__ void aug_vec4(const AugRowChan& r, int j, const AugArgs& a, float (&y)[4]) {
+  if (r.zero) { y[0] = y[1] = y[2] = y[3] = 0.f; return; }       // channel dropout: +0.0, nothing is read
+  const float4 v = r.s4[j];
+  y[0] = v.x; y[1] = v.y; y[2] = v.z; y[3] = v.w;
+  const int t = 4 * j;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (r.scale) y[e] = aug_fmul(y[e], r.gain);
+    if (JITTER) y[e] = aug_fadd(y[e], aug_fmul(a.jitter_sigma, aug_noise(fmix32(r.ck ^ (uint32_t)(t + e)))));
+    if (t + e >= r.m0 && t + e < r.m1) y[e] = 0.f;
+  }
+}
+
+// aug_gather_kernel's grid: x = channel * chunks + chunk, y = row of the batch (B = gridDim.y), z = fold
+template <bool JITTER>
+__global__ __launch_bounds__(256) void mix_gather_kernel(const float* __restrict__ store, const int64_t* __restrict__ store_y,
+                                                         const int64_t* __restrict__ idx, int64_t idx_row_stride, int C, int chunks,
+                                                         float* __restrict__ ox, int64_t* __restrict__ oy, const AugArgs a,
+                                                         const AugKeys keys, const MixLam ml, const FoldCtx fc) {
+  FOLD_BEGIN; FS(ox); FS(oy);
+  const int B = gridDim.y;
+  const int row = blockIdx.y, prow = B - 1 - row, c = blockIdx.x / chunks, chunk = blockIdx.x - c * chunks;
+  const int T4 = a.T >> 2;
+  const int64_t* ix = idx + (int64_t)blockIdx.z * idx_row_stride;
+  const int64_t src = ix[row];
+  float4* d4 = (float4*)(ox) + ((int64_t)row * C + c) * T4;
+  if (oy && store_y && blockIdx.x == 0 && threadIdx.x == 0) oy[row] = store_y[src];      // the row's own label
+  const uint32_t key = keys.key[blockIdx.z];
+  const float lam = ml.lam[blockIdx.z];
+  const int stride = chunks * blockDim.x;
+  const AugRowChan ra = aug_row_chan(store, src, row, c, C, T4, a, key);
+  if (lam == 1.f) {
+    for (int j = chunk * blockDim.x + threadIdx.x; j < T4; j += stride) {
+      float y[4];
+      aug_vec4<JITTER>(ra, j, a, y);
+      d4[j] = make_float4(y[0], y[1], y[2], y[3]);
+    }
+    return;
+  }
+  const float mu = aug_fadd(1.f, -lam);
+  const AugRowChan rb = aug_row_chan(store, ix[prow], prow, c, C, T4, a, key);
+  for (int j = chunk * blockDim.x + threadIdx.x; j < T4; j += stride) {
+    float y[4], p[4];
+    aug_vec4<JITTER>(ra, j, a, y);
+    aug_vec4<JITTER>(rb, j, a, p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = aug_fadd(aug_fmul(lam, y[e]), aug_fmul(mu, p[e]));
+    d4[j] = make_float4(y[0], y[1], y[2], y[3]);
+  }
+}
+
 // ceil(p * 2^32) - 1 for 0 < p <= 1: the event `word <= thr` has probability ceil(p 2^32) / 2^32
 static uint32_t aug_threshold(float p) {
   const double v = ceil((double)p * 4294967296.0) - 1.0;
@@ -107,9 +189,10 @@ static int aug_check(const msig_aug* a, int64_t B, int C, int T) {
   return 0;
 }
 
+// lam: NULL, or the folds' mixup weights (include/msig_st.h) of which at least one is not 1 — then mix_gather_kernel runs instead
 static int launch_aug_gather(const float* store, const int64_t* sy, const int64_t* idx, int64_t idx_row_stride, int B, int C, int T, float* ox,
-                             int64_t* oy, const msig_aug* a, const FoldCtx& fc, hipStream_t st) {
-  if (a->scale_sigma == 0.f && a->jitter_sigma == 0.f && a->mask_prob == 0.f && a->chan_drop_prob == 0.f)
+                             int64_t* oy, const msig_aug* a, const FoldCtx& fc, hipStream_t st, const float* lam = nullptr) {
+  if (!lam && a->scale_sigma == 0.f && a->jitter_sigma == 0.f && a->mask_prob == 0.f && a->chan_drop_prob == 0.f)
     return launch_gather(store, sy, idx, idx_row_stride, B, (int64_t)C * T, ox, oy, fc, st);   // switched off: the plain gather itself
   AugArgs g{};
   g.scale_sigma = a->scale_sigma; g.jitter_sigma = a->jitter_sigma; g.T = T;
@@ -124,6 +207,17 @@ static int launch_aug_gather(const float* store, const int64_t* sy, const int64_
   int chunks = (T4 + threads - 1) / threads;
   if (chunks > 8) chunks = 8;
   const dim3 grid((unsigned)(C * chunks), (unsigned)B, (unsigned)fc.n);
+  if (lam) {
+    MixLam ml{};
+    for (int z = 0; z < fc.n; ++z) ml.lam[z] = lam[z];
+    {
+      MSIG_K("mix_gather", st);
+      if (g.jitter_sigma != 0.f) mix_gather_kernel<true><<<grid, threads, 0, st>>>(store, sy, idx, idx_row_stride, C, chunks, ox, oy, g, keys, ml, fc);
+      else mix_gather_kernel<false><<<grid, threads, 0, st>>>(store, sy, idx, idx_row_stride, C, chunks, ox, oy, g, keys, ml, fc);
+    }
+    MSIG_LAUNCH_CHECK();
+    return 0;
+  }
   {
     MSIG_K("aug_gather", st);
     if (g.jitter_sigma != 0.f) aug_gather_kernel<true><<<grid, threads, 0, st>>>(store, sy, idx, idx_row_stride, C, chunks, ox, oy, g, keys, fc);
@@ -153,4 +247,39 @@ extern "C" int msig_aug_gather_windows_multi(const float* store, const int64_t* 
   if (idx_row_stride < B) return MSIG_E_SHAPE;
   if (((uintptr_t)store | (uintptr_t)out_x) & 15) return MSIG_E_ALIGN;
   return launch_aug_gather(store, store_labels, idx, idx_row_stride, B, C, T, out_x, out_y, a, fc, (hipStream_t)stream);
+}
+
+// ---- include/msig_st.h: the gathers with the mixup blend ------------------------------------------------------------------------
+// the checks of the lam array (host values, n folds): 0 = every lam is 1 (no blend), 1 = blend, else MSIG_E_*
+static int mix_check(const float* lam, int n) {
+  int any = 0;
+  for (int z = 0; z < n; ++z) {
+    if (!(lam[z] >= 0.f && lam[z] <= 1.f)) return MSIG_E_SHAPE;          // NaN included
+    if (lam[z] != 1.f) any = 1;
+  }
+  return any;
+}
+static const msig_aug kAugOff{};
+
+extern "C" int msig_st_gather_windows(const float* store, const int64_t* store_labels, const int64_t* idx, int32_t B, int32_t C, int32_t T,
+                                      float* out_x, int64_t* out_y, const msig_aug* a, const float* lam, void* stream) {
+  if (!lam || !store || !idx || !out_x) return MSIG_E_NULL;
+  if (!a) a = &kAugOff;
+  const int mix = mix_check(lam, 1); if (mix < 0) return mix;
+  const int rc = aug_check(a, B, C, T); if (rc) return rc;
+  if (((uintptr_t)store | (uintptr_t)out_x) & 15) return MSIG_E_ALIGN;
+  return launch_aug_gather(store, store_labels, idx, B, B, C, T, out_x, out_y, a, single_fold(nullptr), (hipStream_t)stream, mix ? lam : nullptr);
+}
+
+extern "C" int msig_st_gather_windows_multi(const float* store, const int64_t* store_labels, const int64_t* idx, int64_t idx_row_stride,
+                                            int32_t B, int32_t C, int32_t T, float* out_x, int64_t* out_y, const msig_multi* m,
+                                            const msig_aug* a, const float* lam, void* stream) {
+  if (!lam || !store || !idx || !out_x || !m) return MSIG_E_NULL;
+  if (!a) a = &kAugOff;
+  FoldCtx fc; int rc = msig_multi_fold_ctx(m, fc); if (rc) return rc;
+  const int mix = mix_check(lam, fc.n); if (mix < 0) return mix;
+  rc = aug_check(a, B, C, T); if (rc) return rc;
+  if (idx_row_stride < B) return MSIG_E_SHAPE;
+  if (((uintptr_t)store | (uintptr_t)out_x) & 15) return MSIG_E_ALIGN;
+  return launch_aug_gather(store, store_labels, idx, idx_row_stride, B, C, T, out_x, out_y, a, fc, (hipStream_t)stream, mix ? lam : nullptr);
 }

@@ -85,6 +85,48 @@ __device__ __forceinline__ double cw_total(const float* __restrict__ cw, const i
   return (red4[0] + red4[1]) + (red4[2] + red4[3]);
 }
 
+// Soft targets (include/msig_st.h): label smoothing eps of the launch and the mixup weight lam of each fold, the
+// partner of row b being row B-1-b.  ST is one more flag beside CW on ce_kernel / head_step_kernel / loss_finalize (and on the two
+// kernels the finalizer rides in); the ST = false instantiations take an empty SoftT and are what they were.  A fold with eps = 0
+// and lam = 1 (`plain`, uniform per fold) runs the plain statements, so its bits are the plain kernel's whatever its companions
+// use.  Every operation of the soft statements is one rounding (contraction off): ce_kernel and head_step_kernel + loss_finalize
+// agree in every bit because they share these functions, not because the compiler happens to fuse alike.
+template <bool ST> struct SoftT {};
+template <> struct SoftT<true> { SoftArgs a; };
+struct SoftCoef { bool plain; float a1, a2, ek, wsum; double d1, d2, dk; };
+template <bool CW>
+__device__ __forceinline__ SoftCoef soft_coef(float eps, float lam, const float* __restrict__ cw, int K) {
+#pragma clang fp contract(off)
+  SoftCoef s;
+  s.plain = eps == 0.f && lam == 1.f;
+  const float om = 1.f - eps;
+  s.a1 = om * lam; s.a2 = om * (1.f - lam); s.ek = eps / (float)K;
+  const double de = (double)eps, dl = (double)lam, dom = 1.0 - de;
+  s.d1 = dom * dl; s.d2 = dom * (1.0 - dl); s.dk = de / (double)K;
+  s.wsum = (float)K;
+  if constexpr (CW) { float t = 0.f; for (int c = 0; c < K; ++c) t = t + cw[c]; s.wsum = t; }
+  return s;
+}
+// one row's term of the loss sum, fp64: (1-eps)(lam w[y] l(y) + (1-lam) w[y'] l(y')) + (eps/K) sum_c w_c l(c), l(c) = lse - lg[c]
+template <bool CW>
+__device__ __forceinline__ double soft_row_loss(const SoftCoef& s, const float* lg, float lse, int y, int y2, const float* __restrict__ cw, int K) {
+#pragma clang fp contract(off)
+  const double wy = CW ? (double)cw[y] : 1.0, wy2 = CW ? (double)cw[y2] : 1.0;
+  double all = 0.0;
+  for (int c = 0; c < K; ++c) all = all + (CW ? (double)cw[c] : 1.0) * (double)(lse - lg[c]);
+  const double own = (s.d1 * wy) * (double)(lse - lg[y]);
+  const double par = (s.d2 * wy2) * (double)(lse - lg[y2]);
+  return (own + par) + s.dk * all;
+}
+// dL/dz[b][c] of the same, fp32
+__device__ __forceinline__ float soft_dlogit(const SoftCoef& s, float p, int c, int y, int y2, float wy, float wy2, float wc, float invW) {
+#pragma clang fp contract(off)
+  const float own = (s.a1 * wy) * (p - (c == y ? 1.f : 0.f));
+  const float par = (s.a2 * wy2) * (p - (c == y2 ? 1.f : 0.f));
+  const float sm = s.ek * (p * s.wsum - wc);
+  return ((own + par) + sm) * invW;
+}
+
 // ------------------------------------------------------------------------------------
 // CrossEntropy (mean), dlogits, softmax probabilities, argmax, accuracy counter.
 // Single workgroup (one deterministic sum) of CE_THREADS threads — with 256 the 32 rows per thread of a B = 8192 batch took 62 us,
@@ -96,11 +138,11 @@ __device__ __forceinline__ double cw_total(const float* __restrict__ cw, const i
 // reproduces the unweighted instantiation's bits: W = B exactly, w_y * v = v, ls * (B / W) = ls.
 // ------------------------------------------------------------------------------------
 #define CE_THREADS 1024
-template <bool CW>
+template <bool CW, bool ST = false>
 __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                  float* __restrict__ probs, int* __restrict__ pred,
                                                  float* __restrict__ dlogits, float* __restrict__ lossbuf, double* __restrict__ lacc,
-                                                 const float* __restrict__ cw, int B, int K, const FoldCtx fc) {
+                                                 const float* __restrict__ cw, int B, int K, const FoldCtx fc, const SoftT<ST> sa) {
   FOLD_BEGIN; FS(logits); FS(labels); FS(probs); FS(pred); FS(dlogits); FS(lossbuf); FS(lacc);
   __shared__ double red[2][CE_THREADS / 64];
   const int tid = threadIdx.x;
@@ -113,12 +155,34 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict_
     W = cw_total(cw, labels, B, wred);
     invB = 1.0f / (float)W;
   }
+  SoftCoef sc{};
+  bool soft = false;
+  if constexpr (ST) {
+    sc = soft_coef<CW>(sa.a.eps, sa.a.lam[blockIdx.z], cw, K);
+    soft = !sc.plain;
+    if constexpr (!CW) W = (double)B;
+  }
   for (int row = tid; row < B; row += CE_THREADS) {
     const float* lg = logits + (size_t)row * K;
     int am;
     const float lse = ce_row_lse(lg, K, am);
     const int y = (int)labels[row];
     const float wy = CW ? cw[y] : 1.f;
+    if constexpr (ST) {
+      if (soft) {                                 // uniform per fold: the soft-target statements of this row, then the next row
+        const int y2 = (int)labels[B - 1 - row];
+        const float wy2 = CW ? cw[y2] : 1.f;
+        lsum += soft_row_loss<CW>(sc, lg, lse, y, y2, cw, K);
+        correct += (am == y) ? 1.0 : 0.0;
+        pred[row] = am;
+        for (int c = 0; c < K; ++c) {
+          const float p = expf(lg[c] - lse);
+          probs[(size_t)row * K + c] = p;
+          if (dlogits) dlogits[(size_t)row * K + c] = soft_dlogit(sc, p, c, y, y2, wy, wy2, CW ? cw[c] : 1.f, invB);
+        }
+        continue;
+      }
+    }
     if constexpr (CW) lsum += (double)wy * (double)(lse - lg[y]);
     else lsum += (double)(lse - lg[y]);
     correct += (am == y) ? 1.0 : 0.0;
@@ -136,7 +200,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict_
   if (tid == 0) {
     double ls = 0.0, cs = 0.0;
     for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
-    if constexpr (CW) {
+    if constexpr (CW || ST) {
       const double sum = ls * ((double)B / W);
       lossbuf[0] = (float)(ls / W);
       lossbuf[1] = (float)sum;
@@ -155,11 +219,18 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict_
 // counter are sums over the whole batch): one workgroup of 256 threads plays ce_kernel's 1024 — virtual thread q * 256 + tid sums
 // the rows ce_kernel's thread of that index sums, each real wave reduces four virtual waves, thread 0 adds the sixteen wave sums in
 // ce_kernel's order.  Same values, same order: the loss is ce_kernel's, bit for bit (CW: with cw_total's W, as ce_kernel<true>).
-template <bool CW>
-__device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[CE_THREADS / 64], double* wred) {
+template <bool CW, bool ST = false>
+__device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[CE_THREADS / 64], double* wred, const SoftT<ST>& sa, int fold) {
   const int tid = threadIdx.x;
   double W = 0.0;
   if constexpr (CW) W = cw_total(lf.cw, lf.labels, lf.B, wred);
+  SoftCoef sc{};
+  bool soft = false;
+  if constexpr (ST) {
+    sc = soft_coef<CW>(sa.a.eps, sa.a.lam[fold], lf.cw, lf.K);
+    soft = !sc.plain;
+    if constexpr (!CW) W = (double)lf.B;
+  }
 #pragma unroll 1
   for (int q = 0; q < CE_THREADS / 256; ++q) {
     double lsum = 0.0, correct = 0.0;
@@ -168,7 +239,8 @@ __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[C
       int am;
       const float lse = ce_row_lse(lg, lf.K, am);
       const int y = (int)lf.labels[row];
-      if constexpr (CW) lsum += (double)lf.cw[y] * (double)(lse - lg[y]);
+      if (ST && soft) lsum += soft_row_loss<CW>(sc, lg, lse, y, (int)lf.labels[lf.B - 1 - row], lf.cw, lf.K);
+      else if constexpr (CW) lsum += (double)lf.cw[y] * (double)(lse - lg[y]);
       else lsum += (double)(lse - lg[y]);
       correct += (am == y) ? 1.0 : 0.0;
     }
@@ -179,7 +251,7 @@ __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[C
   if (tid == 0) {
     double ls = 0.0, cs = 0.0;
     for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
-    if constexpr (CW) {
+    if constexpr (CW || ST) {
       const double sum = ls * ((double)lf.B / W);
       lf.lossbuf[0] = (float)(ls / W);
       lf.lossbuf[1] = (float)sum;
@@ -305,13 +377,14 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // writing one partial row, as head_bwd_kernel does at that size.  CW: class-weighted CrossEntropy (ce_kernel<true>) — a row's dlogits
 // need the whole batch's W, which every workgroup sums itself over all B <= 2048 labels in cw_total's one order (no extra launch).
 // ------------------------------------------------------------------------------------
-template <bool CW>
+template <bool CW, bool ST = false>
 __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict__ feat, const float* __restrict__ W0, const float* __restrict__ b0,
                                                         const float* __restrict__ W3, const float* __restrict__ b3, const int64_t* __restrict__ labels,
                                                         float* __restrict__ hid, float* __restrict__ logits, float* __restrict__ probs, int* __restrict__ pred,
                                                         float* __restrict__ dlogits, float* __restrict__ dfeat, float* __restrict__ part,
                                                         const float* __restrict__ cw,
-                                                        int B, int K, int drop_thr, uint32_t drop_key, float dscale, float dscale_bwd, const FoldCtx fc) {
+                                                        int B, int K, int drop_thr, uint32_t drop_key, float dscale, float dscale_bwd, const FoldCtx fc,
+                                                        const SoftT<ST> sa) {
   FOLD_BEGIN; FS(feat); FS(W0); FS(b0); FS(W3); FS(b3); FS(labels); FS(hid); FS(logits); FS(probs); FS(pred); FS(dlogits); FS(dfeat); FS(part);
   drop_key = fc.key_head[blockIdx.z];
   __shared__ float W0t[128 * W0T_S];
@@ -383,11 +456,21 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
       const int y = (int)labels[row];
       pred[row] = am;
       const float wy = CW ? cw[y] : 1.f;
+      SoftCoef sc{};
+      bool soft = false;
+      int y2 = y;
+      float wy2 = wy;
+      if constexpr (ST) {
+        sc = soft_coef<CW>(sa.a.eps, sa.a.lam[blockIdx.z], cw, K);
+        soft = !sc.plain;
+        if (soft) { y2 = (int)labels[B - 1 - row]; wy2 = CW ? cw[y2] : 1.f; }
+      }
       for (int c = 0; c < K; ++c) {
         const float p = expf(lg[c] - lse);
         probs[(size_t)row * K + c] = p;
         float dl;
-        if constexpr (CW) dl = (wy * (p - (c == y ? 1.f : 0.f))) * invW;
+        if (ST && soft) dl = soft_dlogit(sc, p, c, y, y2, wy, wy2, CW ? cw[c] : 1.f, CW ? invW : invB);
+        else if constexpr (CW) dl = (wy * (p - (c == y ? 1.f : 0.f))) * invW;
         else dl = (p - (c == y ? 1.f : 0.f)) * invB;
         dlogits[(size_t)row * K + c] = dl;
         dls[tid * MSIG_MAX_K + c] = dl;
@@ -509,8 +592,9 @@ __global__ __launch_bounds__(256) void colsum_plan_kernel(const ColsumJobs jobs,
   if (ry == 0 && c < jb.ncols) jb.out[c] = (float)colsum_fold(red, cx);
 }
 
-template <bool CW>
-__global__ __launch_bounds__(256) void colsum_adam_kernel(const ColsumJobs jobs, const AdamArgs ad_in, const LossFin loss_in, const FoldCtx fc) {
+template <bool CW, bool ST = false>
+__global__ __launch_bounds__(256) void colsum_adam_kernel(const ColsumJobs jobs, const AdamArgs ad_in, const LossFin loss_in, const FoldCtx fc,
+                                                          const SoftT<ST> sa) {
   __shared__ double red[CS_LANES][CS_COLS];
   if ((int)blockIdx.x == jobs.blk0[MSIG_MAX_JOBS]) {          // one workgroup past the column blocks: the fused head's loss (launched only then)
     __shared__ double lred[2][CE_THREADS / 64];
@@ -519,7 +603,7 @@ __global__ __launch_bounds__(256) void colsum_adam_kernel(const ColsumJobs jobs,
     const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
     FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
     if constexpr (CW) FS(lf.cw);
-    loss_finalize<CW>(lf, lred, wred);
+    loss_finalize<CW, ST>(lf, lred, wred, sa, (int)blockIdx.y);
     return;
   }
   const int ji = colsum_find_job(jobs, blockIdx.x);
@@ -559,8 +643,13 @@ int launch_colsum_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const Fo
   {
     MSIG_K("colsum_adam", st);
     const dim3 grid(nblk + (plan.loss.logits ? 1 : 0), fc.n);
-    if (plan.loss.cw) colsum_adam_kernel<true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc);
-    else colsum_adam_kernel<false><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc);
+    if (plan.soft && plan.loss.logits) {
+      const SoftT<true> sa{*plan.soft};
+      if (plan.loss.cw) colsum_adam_kernel<true, true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, sa);
+      else colsum_adam_kernel<false, true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, sa);
+    }
+    else if (plan.loss.cw) colsum_adam_kernel<true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, SoftT<false>{});
+    else colsum_adam_kernel<false><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, SoftT<false>{});
   }
   MSIG_LAUNCH_CHECK();
   return 0;
@@ -580,8 +669,9 @@ int launch_colsum_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const Fo
 //                     walks its share of the column blocks: g' = g * coef stored, then colsum_adam_kernel's Adam statements.
 // With coef = 1 the step's bits are the unclipped step's: see the note at the arithmetic of clip_adam_kernel.
 // ------------------------------------------------------------------------------------
-template <bool CW>
-__global__ __launch_bounds__(256) void colsum_sq_kernel(const ColsumJobs jobs, double* __restrict__ state, const LossFin loss_in, const FoldCtx fc) {
+template <bool CW, bool ST = false>
+__global__ __launch_bounds__(256) void colsum_sq_kernel(const ColsumJobs jobs, double* __restrict__ state, const LossFin loss_in, const FoldCtx fc,
+                                                        const SoftT<ST> sa) {
   __shared__ double red[CS_LANES][CS_COLS];
   if ((int)blockIdx.x == jobs.blk0[MSIG_MAX_JOBS]) {          // the fused head's loss, as in colsum_adam_kernel
     __shared__ double lred[2][CE_THREADS / 64];
@@ -590,7 +680,7 @@ __global__ __launch_bounds__(256) void colsum_sq_kernel(const ColsumJobs jobs, d
     const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
     FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
     if constexpr (CW) FS(lf.cw);
-    loss_finalize<CW>(lf, lred, wred);
+    loss_finalize<CW, ST>(lf, lred, wred, sa, (int)blockIdx.y);
     return;
   }
   const int ji = colsum_find_job(jobs, blockIdx.x);
@@ -695,8 +785,13 @@ int launch_colsum_clip_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, con
   {
     MSIG_K("colsum_sq", st);
     const dim3 grid(nblk + (plan.loss.logits ? 1 : 0), fc.n);
-    if (plan.loss.cw) colsum_sq_kernel<true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc);
-    else colsum_sq_kernel<false><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc);
+    if (plan.soft && plan.loss.logits) {
+      const SoftT<true> sa{*plan.soft};
+      if (plan.loss.cw) colsum_sq_kernel<true, true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, sa);
+      else colsum_sq_kernel<false, true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, sa);
+    }
+    else if (plan.loss.cw) colsum_sq_kernel<true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, SoftT<false>{});
+    else colsum_sq_kernel<false><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, SoftT<false>{});
   }
   MSIG_LAUNCH_CHECK();
   {
@@ -864,7 +959,7 @@ int launch_normalise(const double* raw, int64_t N, int T, int C_all, const int* 
 // Host launchers
 // ------------------------------------------------------------------------------------
 int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                    const float* cw) {
+                    const float* cw, const SoftArgs* soft) {
   const float* P = b->params;
   const int thr = b->training ? b->dropout_thr : 0;
   const int ngroups = (d.B + HEAD_ROWS - 1) / HEAD_ROWS;
@@ -876,12 +971,18 @@ int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, co
   if (b->labels) {
     MSIG_K("ce", st);
     float* dl = msig_keeps(b) ? w.p<float>(MSIG_WS_DLOGITS) : nullptr;
-    if (cw)
+    if (soft) {
+      const SoftT<true> sa{*soft};
+      auto* kern = cw ? ce_kernel<true, true> : ce_kernel<false, true>;
+      kern<<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
+                                                    dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B, d.K, fc, sa);
+    }
+    else if (cw)
       ce_kernel<true><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                                             dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B, d.K, fc);
+                                                             dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B, d.K, fc, SoftT<false>{});
     else
       ce_kernel<false><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                                              dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, nullptr, d.B, d.K, fc);
+                                                              dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, nullptr, d.B, d.K, fc, SoftT<false>{});
   } else {
     MSIG_K("softmax", st);
     softmax_kernel<<<dim3((d.B + 255) / 256, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED), d.B, d.K, fc);
@@ -914,7 +1015,7 @@ bool head_step_applies(const msig_batch* b, const StageDims& d) {
   return b->training && b->labels && (d.B + HEAD_ROWS - 1) / HEAD_ROWS <= HEAD_WG;
 }
 int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
-                     const float* cw) {
+                     const float* cw, const SoftArgs* soft) {
   const float* P = b->params;
   float* G = b->grads;
   const int thr = b->dropout_thr;
@@ -923,14 +1024,24 @@ int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, c
   const int PS = 64 * 128 + 64 + d.K * 64 + d.K;
   {
     MSIG_K("head_step", st);
-    auto* kern = cw ? head_step_kernel<true> : head_step_kernel<false>;
-    kern<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
-                                              P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS),
-                                              w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr,
-                                              b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc);
+    if (soft) {
+      const SoftT<true> sa{*soft};
+      auto* kern = cw ? head_step_kernel<true, true> : head_step_kernel<false, true>;
+      kern<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
+                                                P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS),
+                                                w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr,
+                                                b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc, sa);
+    } else {
+      auto* kern = cw ? head_step_kernel<true> : head_step_kernel<false>;
+      kern<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
+                                                P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS),
+                                                w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr,
+                                                b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc, SoftT<false>{});
+    }
   }
   MSIG_LAUNCH_CHECK();
   plan.loss = LossFin{w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K, cw};
+  plan.soft = soft;
   const bool ok = plan.add(part, grid, PS, 0, 64 * 128, G + po[MSIG_P_CLS0_W]) && plan.add(part, grid, PS, 64 * 128, 64, G + po[MSIG_P_CLS0_B]) &&
                   plan.add(part, grid, PS, 64 * 128 + 64, d.K * 64, G + po[MSIG_P_CLS3_W]) &&
                   plan.add(part, grid, PS, 64 * 128 + 64 + d.K * 64, d.K, G + po[MSIG_P_CLS3_B]);

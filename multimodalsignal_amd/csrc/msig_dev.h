@@ -300,15 +300,18 @@ int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
                         bool gated = true);
 int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st);
 int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st);
+// Soft targets (include/msig_st.h): the launch's label smoothing and every fold's mixup weight; NULL wherever it is
+// taken = the plain criterion's kernels.
+struct SoftArgs { float eps; float lam[MSIG_MAX_FOLDS]; };
 // cw: class weights (include/msig_cw.h), K device floats of fold slot 0 (shifted per fold like every buffer); NULL = unweighted
 int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                    const float* cw = nullptr);
+                    const float* cw = nullptr, const SoftArgs* soft = nullptr);
 int launch_head_bwd(const msig_batch* b, const float* dlogits, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan,
                     const FoldCtx& fc, hipStream_t st);
 // head forward + CrossEntropy + head backward of a fused train step in one launch (few windows: see head.hip); false = not applicable
 bool head_step_applies(const msig_batch* b, const StageDims& d);
 int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
-                     const float* cw = nullptr);
+                     const float* cw = nullptr, const SoftArgs* soft = nullptr);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch
@@ -323,6 +326,7 @@ struct ColsumPlan {
   ColsumJob job[MSIG_MAX_JOBS];
   int n = 0;
   LossFin loss{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
+  const SoftArgs* soft = nullptr;      // of `loss` (host side; the launch passes it by value): soft targets, include/msig_st.h
   bool add(const float* part, int nrows, int row_stride, int col0, int ncols, float* out) {
     if (n >= MSIG_MAX_JOBS) return false;
     if (ncols > 0 && nrows > 0) job[n++] = ColsumJob{part, nrows, row_stride, col0, ncols, out};

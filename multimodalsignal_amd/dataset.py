@@ -250,9 +250,14 @@ class DeviceLoader:
 
     `augment` (an ``augment.Augment``; training loaders only): every batch is one ``msig_aug_gather_windows`` launch instead, keyed
     by (`aug_seed` = the loader's seed, `aug_step` = the batches this loader has served so far, counted from 1) — the same windows
-    are augmented differently in every epoch, and two loaders with one seed serve the same batches.  None: the plain gather."""
+    are augmented differently in every epoch, and two loaders with one seed serve the same batches.  None: the plain gather.
 
-    def __init__(self, dataset: WesadDataset, batch_size: int, shuffle: bool, device, seed: Optional[int] = None, augment=None):
+    `mixup` (a ``mixup.Mixup``; training loaders only, composes with `augment`: the batch is augmented, then mixed): every batch is
+    one ``msig_st_gather_windows`` launch that blends row b with row B-1-b, lam drawn from the same (`aug_seed`, `aug_step`) on a
+    stream of its own.  `last_lam` is the lam of the batch just served — the criterion needs it (Engine.train_step(mix_lambda=))."""
+
+    def __init__(self, dataset: WesadDataset, batch_size: int, shuffle: bool, device, seed: Optional[int] = None, augment=None,
+                 mixup=None):
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.device = torch.device(device)
         self.store, self.store_y = dataset.device_tensors(self.device)
@@ -264,6 +269,9 @@ class DeviceLoader:
         self.aug_seed, self.aug_step = int(torch.initial_seed() if seed is None else seed), 0
         if self.augment is not None:
             self.augment.check_window(int(self.store.shape[2]))
+        self.mixup, self.last_lam = mixup, None
+        if mixup is not None and (int(self.store.shape[2]) < 4 or int(self.store.shape[2]) % 4):
+            raise ValueError(f"mixup: the window length must be a multiple of 4, got {int(self.store.shape[2])}")
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
@@ -288,6 +296,16 @@ class DeviceLoader:
                 self._bufs[b] = [(torch.empty((b,) + tuple(self.store.shape[1:]), device=self.device),
                                   torch.empty(b, dtype=torch.int64, device=self.device)) for _ in range(2)]
             ox, oy = self._bufs[b][(i // self.batch_size) & 1]
+            if self.mixup is not None:
+                self.aug_step += 1
+                self.last_lam = self.mixup.lam(self.aug_seed, self.aug_step)
+                a = (C.byref(self.augment.struct([L.dropout_key(self.aug_seed, self.aug_step, L.AUG_STREAM_ID)]))
+                     if self.augment is not None else None)
+                L.check(L.lib().msig_st_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, self.store.shape[1],
+                                                       self.store.shape[2], ox.data_ptr(), oy.data_ptr(), a, (C.c_float * 1)(self.last_lam), st),
+                        "msig_st_gather_windows")
+                yield ox, oy
+                continue
             if self.augment is not None:
                 self.aug_step += 1
                 a = self.augment.struct([L.dropout_key(self.aug_seed, self.aug_step, L.AUG_STREAM_ID)])

@@ -29,11 +29,12 @@ import torch
 
 from . import _lib as L
 from .augment import Augment
+from .mixup import Mixup
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
 from .multifold import fold_result, lockstep_compatible
-from .trainer import Trainer, grad_clip_setting
+from .trainer import Trainer, grad_clip_setting, label_smoothing_setting
 from .waves import MAX_TRAIN_STREAMS, cap_waves, chunk_schedule, deal, on_streams, run_wave  # noqa: F401  (the first three: importable from here)
 
 warnings.filterwarnings("ignore", message="Initializing zero-element tensors is a no-op")
@@ -95,7 +96,18 @@ def trainer_config(cfg, fold_idx):
         tc["trainer"]["class_weights"] = trainer_class_weights(cfg)
     if cfg.get("max_grad_norm") is not None:        # clip_grad_norm_ inside the fused step (include/msig_gc.h); absent = the unclipped step
         tc["trainer"]["max_grad_norm"] = grad_clip_setting(cfg["max_grad_norm"])
+    if cfg.get("label_smoothing") is not None:      # CrossEntropyLoss(label_smoothing=) of every loss (include/msig_st.h); absent = hard labels
+        tc["trainer"]["label_smoothing"] = label_smoothing_setting(cfg["label_smoothing"])
     return tc
+
+
+def soft_targets_line(cfg):
+    """The SOFT TARGETS line of a summary, or None when neither label smoothing nor mixup is set."""
+    ls, mix = cfg.get("label_smoothing"), Mixup.coerce(cfg.get("mixup"))
+    if ls is None and mix is None:
+        return None
+    parts = ([f"label_smoothing={ls:g}"] if ls is not None else []) + ([f"mixup_alpha={mix.alpha:g}"] if mix is not None else [])
+    return "SOFT TARGETS: " + " ".join(parts) + "\n"
 
 
 def host_datasets(cfg, all_channel_names, cache, channels, mode):
@@ -122,7 +134,9 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
     # windows are batched; only the summation order of the reported loss does (~1e-7 relative).
     ebs = int(cfg.get("eval_batch_size") or cfg["batch_size"])
     # cfg["augment"] (--augment SPEC, include/msig_aug.h): the TRAINING loader's gather augments; validation and test never do
-    loaders = (DeviceLoader(train_ds, cfg["batch_size"], shuffle, device, seed=seed, augment=Augment.coerce(cfg.get("augment"))),
+    # cfg["mixup"] (--mixup ALPHA, include/msig_st.h): likewise the training loader's gather alone mixes
+    loaders = (DeviceLoader(train_ds, cfg["batch_size"], shuffle, device, seed=seed, augment=Augment.coerce(cfg.get("augment")),
+                            mixup=Mixup.coerce(cfg.get("mixup"))),
                DeviceLoader(val_ds, ebs, False, device), DeviceLoader(datasets([subject]), ebs, False, device))
     model = make_model(cfg, in_channels, num_classes, params)
     model.set_dropout_seed(seed * 0x9E3779B97F4A7C15 + 12345)
@@ -174,6 +188,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
         if cfg.get("augment") is not None:                          # likewise
             f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
+        if soft_targets_line(cfg) is not None:                      # likewise
+            f.write(soft_targets_line(cfg))
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -561,6 +577,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
             if cfg.get("augment") is not None:
                 f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
+            if soft_targets_line(cfg) is not None:
+                f.write(soft_targets_line(cfg))
             f.write("\n")
             for r in results:
                 f.write(f"  - 测试 {r['subject']}: M1 Accuracy = {r['m1_accuracy']:.4f}, 三分类 Accuracy = {r['ternary_accuracy']:.4f}\n")
@@ -613,6 +631,17 @@ def parse_args(ap, argv=None):
                 args.augment.check_window(args.samples)
         except ValueError as e:
             ap.error(f"--augment: {e}")
+    try:
+        args.label_smoothing = label_smoothing_setting(args.label_smoothing)
+    except ValueError as e:
+        ap.error(f"--label-smoothing: {e}")
+    if args.mixup is not None:
+        try:
+            args.mixup = Mixup(args.mixup)
+        except ValueError as e:
+            ap.error(f"--mixup: {e}")
+        if args.synthetic is not None and (args.samples < 4 or args.samples % 4):
+            ap.error(f"--mixup: the window length must be a multiple of 4, got {args.samples}")
     return args
 
 
@@ -659,6 +688,13 @@ def build_parser():
                          "per-channel gain 1 + scale * g, additive noise jitter * g per sample, with probability mask=P one zeroed span of "
                          "1..N samples per window, each channel zeroed with probability chandrop (every mode: LOSO, --ablation, "
                          "--hierarchical, --model, sequential; validation, test and --calibrate never augment)")
+    ap.add_argument("--label-smoothing", type=float, default=None, metavar="E",
+                    help="CrossEntropyLoss(label_smoothing=E), 0 <= E < 1, inside the fused step; like the criterion it is, it applies to "
+                         "training, validation and test losses (every mode: LOSO, --ablation, --hierarchical, --model, sequential)")
+    ap.add_argument("--mixup", type=float, default=None, metavar="ALPHA",
+                    help="mixup of every training batch inside its gather launch: row b is blended with row B-1-b, lam ~ Beta(ALPHA, ALPHA) "
+                         "per batch and fold, and the loss is taken against both labels (every mode; composes with --augment: augment, "
+                         "then mix; validation, test and --calibrate never mix)")
     ap.add_argument("--model", nargs="+", choices=list(MODEL_PARAMS), default=[MODEL_TO_USE],
                     help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
                          "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
@@ -689,6 +725,10 @@ def build_cfg(args, kinds):
         cfg["max_grad_norm"] = args.max_grad_norm
     if args.augment is not None:            # likewise
         cfg["augment"] = args.augment
+    if args.label_smoothing is not None:    # likewise
+        cfg["label_smoothing"] = args.label_smoothing
+    if args.mixup is not None:              # likewise
+        cfg["mixup"] = args.mixup
     if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
         cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
         for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib as L
 from .runtime import FoldArena
-from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary
+from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary, label_smoothing_setting
 
 
 def _depth(model):
@@ -119,6 +119,16 @@ class LockstepTrainer:
         if any(a != augs[0] for a in augs):
             raise ValueError(f"lockstep folds must share one augmentation, got {sorted({repr(a) for a in augs})}")
         self.augment = augs[0]
+        # soft targets (include/msig_st.h): label smoothing is the launch's and mixup's alpha decides how every fold's lam is drawn,
+        # so the folds of a batch must agree on both; lam itself is per fold, from each loader's own seed and batch count
+        mixes = [getattr(p["loaders"][0], "mixup", None) for p in preps]
+        if any(m != mixes[0] for m in mixes):
+            raise ValueError(f"lockstep folds must share one mixup alpha, got {sorted({repr(m) for m in mixes})}")
+        self.mixup = mixes[0]
+        smooths = [label_smoothing_setting(p["config"]["trainer"].get("label_smoothing")) or 0.0 for p in preps]
+        if any(v != smooths[0] for v in smooths):
+            raise ValueError(f"lockstep folds must share one label_smoothing, got {sorted(set(smooths))}")
+        self.smoothing = smooths[0]
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
@@ -157,9 +167,17 @@ class LockstepTrainer:
             self._layouts[key] = (off, self.arena.batch(B, training, self.trainers[0].model.dropout_p if training else 0.0))
         return self._layouts[key]
 
-    def _gather(self, loader, order_mat, row0, i, b, m, aug=None):
+    def _gather(self, loader, order_mat, row0, i, b, m, aug=None, lam=None):
         """order_mat: (folds, n_max) int64 store positions of the pass; gathers columns i .. i+b of rows row0 .. row0+m.n.
-        aug: the msig_aug of a training launch whose loaders augment (its keys filled for the folds of `m`)."""
+        aug: the msig_aug of a training launch whose loaders augment (its keys filled for the folds of `m`).
+        lam: the folds' mixup weights of a training launch whose loaders mix (a C float array; include/msig_st.h)."""
+        if lam is not None:
+            L.check(L.lib().msig_st_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
+                                                         order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b,
+                                                         loader.store.shape[1], loader.store.shape[2], self.arena.ptr("x"), self.arena.ptr("y"),
+                                                         C.byref(m), C.byref(aug) if aug is not None else None, lam, self._stream()),
+                    "msig_st_gather_windows_multi")
+            return
         if aug is not None:
             L.check(L.lib().msig_aug_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
                                                           order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b,
@@ -215,6 +233,11 @@ class LockstepTrainer:
         aug = self.augment.struct() if self.augment is not None else None
         ka = [L.dropout_keys(ld.aug_seed, np.arange(ld.aug_step + 1, ld.aug_step + 1 + ns), L.AUG_STREAM_ID)
               for ld, ns in zip(loaders, n_steps)] if aug is not None else None
+        # mixup weights: every fold's lam of every step of the epoch at once, keyed like the augmentation (the same counter)
+        mix = self.mixup
+        la = [mix.lams(ld.aug_seed, range(ld.aug_step + 1, ld.aug_step + 1 + ns)) for ld, ns in zip(loaders, n_steps)] if mix is not None else None
+        soft = mix is not None or self.smoothing != 0.0
+        lam_arr = (C.c_float * L.MAX_FOLDS)() if mix is not None else None
         lrs = [t.optimizer.hyper["lr"] for t in trs]
         h0 = trs[0].optimizer.hyper
         b1, b2, eps, wd = h0["betas"][0], h0["betas"][1], h0["eps"], h0["weight_decay"]
@@ -231,8 +254,21 @@ class LockstepTrainer:
             if aug is not None:
                 for j in range(nr):
                     aug.key[j] = int(ka[r0 + j][k])
-            self._gather(loaders[0], order, r0, i, b, m, aug)
+            if mix is not None:
+                for j in range(nr):
+                    lam_arr[j] = la[r0 + j][k]
+            self._gather(loaders[0], order, r0, i, b, m, aug, lam_arr)
             _, desc = self._layout(b, True)
+            if soft:                       # msig_st_train_step_multi: either kind, with or without class weights and clip
+                if (r0, nr, "st") not in multis:
+                    multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw,
+                                                        arena.clip(act[r0:r0 + nr], self.cw) if self.clip else None)
+                s = multis[(r0, nr, "st")]
+                for j in range(nr):
+                    s.lam[j] = lam_arr[j] if mix is not None else 1.0
+                L.check(lib.msig_st_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
+                        "msig_st_train_step_multi")
+                continue
             if self.clip:
                 if (r0, nr, "gc") not in multis:
                     multis[(r0, nr, "gc")] = arena.clip(act[r0:r0 + nr], self.cw)
@@ -243,7 +279,7 @@ class LockstepTrainer:
                     train_multi.__name__)           # self.cw None: exactly msig_train_step_multi (msig_cg_*: the baseline)
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
-        if aug is not None:
+        if aug is not None or mix is not None:
             for ld, ns in zip(loaders, n_steps):
                 ld.aug_step += ns
         if not self.clip:
@@ -279,7 +315,12 @@ class LockstepTrainer:
             m = multis[(r0, nr)]
             self._gather(loaders[0], order, r0, i, b, m)
             off, desc = self._layout(b, False)
-            L.check(fwd_multi(C.byref(desc), C.byref(m), self.cw, st), fwd_multi.__name__)
+            if self.smoothing != 0.0:          # the criterion's label smoothing applies to validation losses too; evaluation never mixes
+                if (r0, nr, "st") not in multis:
+                    multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw)
+                L.check(lib.msig_st_forward_multi(C.byref(desc), C.byref(m), C.byref(multis[(r0, nr, "st")]), st), "msig_st_forward_multi")
+            else:
+                L.check(fwd_multi(C.byref(desc), C.byref(m), self.cw, st), fwd_multi.__name__)
             got = arena.across("ws", off[L.WS["PRED"]], torch.int32, b)[act[r0:r0 + nr]]      # (folds of the launch, b) copy
             for j in range(nr):
                 preds[r0 + j].append(got[j])

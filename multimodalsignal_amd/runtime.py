@@ -217,14 +217,22 @@ class Engine:
 
     # ---- calls -------------------------------------------------------------------------
     def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False,
-                class_weight: Optional[torch.Tensor] = None) -> L.Batch:
+                class_weight: Optional[torch.Tensor] = None, label_smoothing=0.0, mix_lambda=None) -> L.Batch:
         """model(inputs) [+ criterion]: logits land in region('LOGITS'); returns the descriptor
         that a following backward() must be given.  An eval-mode forward (training=False) takes a backward only with
         keep_for_backward=True: it then keeps the stashes in a workspace of its own, with the same logits.  class_weight: a (K,)
         float32 device tensor = CrossEntropyLoss(weight=class_weight) for the loss and, kept for a backward, WS_DLOGITS
-        (msig_cw_forward); None = the unweighted criterion."""
+        (msig_cw_forward); None = the unweighted criterion.  label_smoothing / mix_lambda: the soft-target criterion of
+        include/msig_st.h (msig_st_forward) — CrossEntropyLoss(label_smoothing=eps), and with mix_lambda = lam the loss against the
+        row's own label (weight lam) and its partner's, row B-1-b (weight 1 - lam), for an `x` that was mixed the same way
+        (mixup.Mixup.apply, DeviceLoader(mixup=)); 0.0 and None (or 1) = the calls above, unchanged."""
         cw = self._class_weight(class_weight)
+        eps, lam = L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
         b = self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward)
+        if eps != 0.0 or lam != 1.0:
+            s = L.make_st(self.kind, eps, cw, None, [lam])
+            L.check(L.lib().msig_st_forward(C.byref(b), C.byref(s), self._stream()), "msig_st_forward")
+            return b
         if self.kind == "cnn_gru":
             L.check(L.lib().msig_cg_forward(C.byref(b), cw, self._stream()), "msig_cg_forward")
         elif cw is None:
@@ -290,23 +298,34 @@ class Engine:
         return v[:2], self._stats(v[2:])
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
-                   dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None) -> None:
+                   dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
+                   label_smoothing=0.0, mix_lambda=None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
         class_weight: (K,) float32 device tensor = criterion CrossEntropyLoss(weight=class_weight) (msig_cw_train_step).
         max_grad_norm: torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) between loss.backward() and
         optimizer.step() (msig_gc_train_step, DESIGN.md §15): `grads` then holds the clipped gradient and grad_stats() the norms;
-        float('inf') measures without clipping; None = the calls above, unchanged."""
+        float('inf') measures without clipping; None = the calls above, unchanged.
+        label_smoothing / mix_lambda: the soft-target criterion (msig_st_train_step; see forward()), with or without
+        class weights and clip; 0.0 and None (or 1) = the calls above, unchanged."""
         cw = self._class_weight(class_weight)
         max_norm = None if max_grad_norm is None else L.check_max_grad_norm(max_grad_norm)
+        smooth, lam = L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
+        g = None
         if max_norm is not None:
             state = self.ensure_gc_state()
             g = L.GcClip()
             g.kind, g.class_weight, g.state, g.state_bytes = L.GC_KINDS[self.kind], cw, state.data_ptr(), state.numel() * 8
             g.max_norm[0] = max_norm
+        if smooth != 0.0 or lam != 1.0:
+            s = L.make_st(self.kind, smooth, cw, g, [lam])
+            L.check(L.lib().msig_st_train_step(C.byref(b), C.byref(s), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
+                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_st_train_step")
+            return
+        if max_norm is not None:
             L.check(L.lib().msig_gc_train_step(C.byref(b), C.byref(g), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
                                                betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_gc_train_step")
             return
@@ -428,18 +447,22 @@ class EmbeddedEngine(Engine):
         return self.small_views(self.small_grads)
 
     # ---- the library calls, with the embedding maintained around them ----
-    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False, class_weight=None):
+    def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False, class_weight=None,
+                label_smoothing=0.0, mix_lambda=None):
         self._class_weight(class_weight)                    # the checks before the scatter: nothing runs on a bad vector
+        L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
         self.scatter()
-        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight)
+        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight, label_smoothing, mix_lambda)
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
-                   max_grad_norm=None):
+                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None):
         self._class_weight(class_weight)
         if max_grad_norm is not None:
             L.check_max_grad_norm(max_grad_norm)
+        L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
         self.scatter()
-        super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm)
+        super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm, label_smoothing,
+                           mix_lambda)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -563,6 +586,15 @@ class FoldArena:
         for i, s in enumerate(slots):
             g.max_norm[i] = self.max_norm[int(s)]
         return g
+
+    def soft(self, slots, smoothing: float, lams=None, class_weight: Optional[int] = None, clip: Optional[L.GcClip] = None) -> L.St:
+        """msig_st of a launch over `slots` (msig_st_*_multi, include/msig_st.h): the launch's label smoothing, lam per fold of the
+        launch (None: 1 everywhere — evaluation never mixes), ptr("cw") or None, and the launch's clip (`clip(slots)`) or None.
+        Checked on the host: ValueError before anything is launched."""
+        lams = [1.0] * len(slots) if lams is None else [L.check_mix_lambda(v) for v in lams]
+        if len(lams) != len(slots):
+            raise ValueError(f"{len(slots)} folds need {len(slots)} mixup weights, got {len(lams)}")
+        return L.make_st(self.kind, L.check_label_smoothing(smoothing), class_weight, clip, lams)
 
     def zero_grad_stats(self, slots=None) -> None:
         st = self.across("gc", 0, torch.float64, L.GC_NSTAT)

@@ -20,6 +20,8 @@ own, ``config['trainer']['class_weights']`` (include/msig_cw.h).
 ``config['trainer']['max_grad_norm']``, another key of this repo's own, puts
 ``torch.nn.utils.clip_grad_norm_`` between the backward pass and Adam inside the fused step
 (include/msig_gc.h) and adds the epoch's gradient norms to ``history`` and the log.
+``config['trainer']['label_smoothing']`` is ``CrossEntropyLoss(label_smoothing=...)`` of the training, validation and test
+losses alike (include/msig_st.h); a training loader built with ``mixup=`` has its batches' lam passed on to the step.
 """
 from __future__ import annotations
 
@@ -146,6 +148,11 @@ def grad_clip_setting(value):
     return v
 
 
+def label_smoothing_setting(value):
+    """config['trainer']['label_smoothing']: None (the hard-label criterion) or a number with 0 <= eps < 1 (ValueError otherwise)."""
+    return None if value is None else L.check_label_smoothing(value)
+
+
 def grad_norm_summary(stats, steps: int) -> dict:
     """The history entries of an epoch's gradient norms from a clip state's statistics (runtime.Engine.grad_stats) over `steps` steps."""
     return dict(grad_norm_mean=stats["sum"] / max(steps, 1), grad_norm_max=stats["max"], clipped_steps=int(stats["clipped"]))
@@ -172,6 +179,8 @@ class Trainer:
         self.class_weight = None
         # clip_grad_norm_(model.parameters(), max_grad_norm) inside the fused step (include/msig_gc.h); None: the unclipped step
         self.max_grad_norm = grad_clip_setting(cfg.get("max_grad_norm"))
+        # CrossEntropyLoss(label_smoothing=eps) of every loss this trainer takes (include/msig_st.h); None / 0: the hard-label calls
+        self.label_smoothing = label_smoothing_setting(cfg.get("label_smoothing")) or 0.0
         self.verbose = cfg.get("verbose", True)
         self.optimizer = MsigAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)   # trainer.py:68
         self.scheduler = ReduceLROnPlateau(self.optimizer, mode="min", factor=0.1, patience=3)         # trainer.py:72-77
@@ -248,7 +257,8 @@ class Trainer:
                 self.optimizer.step_count += 1
                 eng.train_step(x, y, lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
                                step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
-                               class_weight=self.class_weight, max_grad_norm=self.max_grad_norm)
+                               class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
+                               mix_lambda=getattr(train_loader, "last_lam", None))      # the lam of the batch a mixup loader just served
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
             if self.max_grad_norm is None:
                 train_loss, grad = float(eng.loss_acc[0].item()) / n_train, None         # the epoch's only sync
@@ -298,7 +308,7 @@ class Trainer:
         preds, labs = [], []
         for inputs, labels in data_loader:
             x, y = self._to_device(inputs, labels)
-            eng.forward(x, y, training=False, class_weight=self.class_weight)   # the loss kernel adds loss * batch to eng.loss_acc (trainer.py:221)
+            eng.forward(x, y, training=False, class_weight=self.class_weight, label_smoothing=self.label_smoothing)   # the loss kernel adds loss * batch to eng.loss_acc (trainer.py:221)
             preds.append(eng.region("PRED", torch.int32, (y.shape[0],)).clone())
             labs.append(y.clone())          # DeviceLoader reuses its batch buffers
         all_preds = torch.cat(preds).cpu().numpy().astype(np.int64)
