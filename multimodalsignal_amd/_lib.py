@@ -89,6 +89,9 @@ ST_ABI_VERSION = 1    # include/msig_st.h MSIG_ST_ABI_VERSION (label smoothing a
 ST_STREAM_ID = 4      # msig_st.h MSIG_ST_STREAM_ID: msig_dropout_key's stream of the mixup draws
 FT_MAX_BATCH, FT_MAX_N = 256, 1 << 24
 FT_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_FT_KIND_*
+AB_ABI_VERSION = 1    # include/msig_ab.h MSIG_AB_ABI_VERSION (label-free BatchNorm adaptation)
+AB_ACC_DOUBLES = 98   # msig_ab.h MSIG_AB_ACC_DOUBLES: fp64 values of one model's accumulator
+AB_N1, AB_N2, AB_SUM1, AB_SQ1, AB_SUM2, AB_SQ2 = 0, 1, 2, 18, 34, 66      # msig_ab.h MSIG_AB_*: the accumulator's slots
 
 
 class Multi(C.Structure):
@@ -259,6 +262,14 @@ def lib() -> C.CDLL:
         L.msig_ft_features_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.c_int, vp, C.c_int64, vp]
         L.msig_ft_head_epoch.argtypes = [C.POINTER(FtHead), vp]
         L.msig_ft_head_epoch_multi.argtypes = [C.POINTER(FtHead), C.POINTER(FtMulti), vp]
+        # include/msig_ab.h, exported by the same library: label-free BatchNorm adaptation (kind: FT_KINDS)
+        L.msig_ab_abi_version.restype = C.c_int
+        if L.msig_ab_abi_version() != AB_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_ab.h ABI {L.msig_ab_abi_version()}; this binding is {AB_ABI_VERSION}: rebuild the library")
+        L.msig_ab_accumulate.argtypes = [C.POINTER(Batch), C.c_int, C.c_int, vp, vp]
+        L.msig_ab_accumulate_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.c_int, C.c_int, vp, vp]
+        L.msig_ab_commit.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp]
+        L.msig_ab_commit_multi.argtypes = [vp, C.c_int, C.c_float, vp, vp, C.POINTER(Multi), vp]
         # include/msig_gc.h, exported by the same library: the train steps with gradient-norm clipping
         L.msig_gc_abi_version.restype = C.c_int
         L.msig_gc_struct_bytes.restype = C.c_int64

@@ -12,6 +12,7 @@
 #include "../../include/msig_cg.h"
 #include "../../include/msig_st.h"
 #include "finetune.h"
+#include "../../include/msig_ab.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -604,6 +605,49 @@ extern "C" int msig_ft_head_epoch_multi(const msig_ft_head* h, const msig_ft_mul
     ff.slot[i] = m->slot[i]; ff.lr[i] = m->lr[i]; ff.step0[i] = m->step0[i]; ff.seed[i] = m->seed[i];
   }
   return launch_head_epoch(*h, ff, (hipStream_t)stream);
+}
+
+// ---- label-free BatchNorm adaptation (include/msig_ab.h; kernels: adapt_bn.hip) ---------------------------------------------------
+extern "C" int msig_ab_abi_version(void) { return MSIG_AB_ABI_VERSION; }
+
+// one batch into stage `stage` of every fold's accumulator: the front end up to that stage's convolution with its partial sums on
+// (launch_frontend_fwd's stats_stage), then the merge.  Every argument check before the first launch.
+static int ab_accumulate_fc(const msig_batch* b, const FoldCtx& fc, int kind, int stage, double* acc, hipStream_t st) {
+  if (!b || !acc) return MSIG_E_NULL;
+  if (kind != MSIG_FT_KIND_ATTENTION && kind != MSIG_FT_KIND_CNN_GRU) return MSIG_E_SHAPE;
+  if (stage != 1 && stage != 2) return MSIG_E_SHAPE;
+  if (b->training) return MSIG_E_SHAPE;
+  if ((uintptr_t)acc & 7) return MSIG_E_ALIGN;
+  const bool cg = kind == MSIG_FT_KIND_CNN_GRU;
+  Ctx c; int rc = make_ctx(b, c, false, cg); if (rc) return rc;
+  int rows = 0;
+  if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st, !cg, stage, &rows))) return rc;
+  const bool s1 = stage == 1;
+  return launch_ab_merge(c.w.p<float>(s1 ? MSIG_WS_BN1_PART : MSIG_WS_BN2_PART), rows, stage, (double)c.d.B * (s1 ? c.d.L1 : c.d.L2), acc, fc, st);
+}
+extern "C" int msig_ab_accumulate(const msig_batch* b, int kind, int stage, double* acc, void* stream) {
+  if (!b) return MSIG_E_NULL;
+  return ab_accumulate_fc(b, single_fold(b), kind, stage, acc, (hipStream_t)stream);
+}
+extern "C" int msig_ab_accumulate_multi(const msig_batch* b, const msig_multi* m, int kind, int stage, double* acc, void* stream) {
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return ab_accumulate_fc(b, fc, kind, stage, acc, (hipStream_t)stream);
+}
+
+static int ab_commit_fc(const double* acc, int stage, float alpha, const float* bn_src, float* bn_dst, const FoldCtx& fc, hipStream_t st) {
+  if (!acc || !bn_src || !bn_dst) return MSIG_E_NULL;
+  if (stage != 1 && stage != 2) return MSIG_E_SHAPE;
+  if (!(alpha >= 0.0f && alpha <= 1.0f)) return MSIG_E_SHAPE;          // NaN fails both comparisons
+  if ((uintptr_t)acc & 7) return MSIG_E_ALIGN;
+  if (((uintptr_t)bn_src | (uintptr_t)bn_dst) & 3) return MSIG_E_ALIGN;
+  return launch_ab_commit(acc, stage, alpha, bn_src, bn_dst, fc, st);
+}
+extern "C" int msig_ab_commit(const double* acc, int stage, float alpha, const float* bn_src, float* bn_dst, void* stream) {
+  return ab_commit_fc(acc, stage, alpha, bn_src, bn_dst, single_fold(nullptr), (hipStream_t)stream);
+}
+extern "C" int msig_ab_commit_multi(const double* acc, int stage, float alpha, const float* bn_src, float* bn_dst, const msig_multi* m, void* stream) {
+  FoldCtx fc; int rc = msig_multi_fold_ctx(m, fc); if (rc) return rc;
+  return ab_commit_fc(acc, stage, alpha, bn_src, bn_dst, fc, (hipStream_t)stream);
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {

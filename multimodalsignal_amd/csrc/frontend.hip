@@ -468,35 +468,7 @@ __global__ __launch_bounds__(256, 2) void pool1_conv2_fwd_kernel(const float* __
   }
 }
 
-// Column sums of part[nrows][ncol] (ncol <= 64) by one 1024-thread workgroup into red[0..ncol): 1024/ncol
-// row-lanes, 8 loads in flight per lane, fixed combination order (deterministic for a given nrows).
-#define FIN_THREADS 1024
-__device__ __forceinline__ void fin_colsums(const float* __restrict__ part, int nrows, int ncol, double* red) {
-  const int tid = threadIdx.x;
-  const int col = tid % ncol, grp = tid / ncol, ngrp = FIN_THREADS / ncol;
-  double a[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = 0.0;
-  if (grp < ngrp) {
-    int r = grp;
-    for (; r + 7 * ngrp < nrows; r += 8 * ngrp) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = part[(size_t)(r + j * ngrp) * ncol + col];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] += (double)v[j];
-    }
-    for (; r < nrows; r += ngrp) a[0] += (double)part[(size_t)r * ncol + col];
-  }
-  red[tid] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  __syncthreads();
-  double s = 0.0;
-  if (tid < ncol)
-    for (int g = 0; g < ngrp; ++g) s += red[g * ncol + tid];
-  __syncthreads();
-  if (tid < ncol) red[tid] = s;
-  __syncthreads();
-}
+// fin_colsums (the column sums of a partial buffer by one FIN_THREADS workgroup) lives in msig_dev.h: adapt_bn.hip reduces in the same order.
 
 // ------------------------------------------------------------------------------------
 // BatchNorm statistics -> (mean, invstd, scale, shift); running-stat update
@@ -523,8 +495,10 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
       stat[2 * CH + tid] = sc;
       stat[3 * CH + tid] = beta[tid] - (float)mean * sc;
       const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      run_mean[tid] = (1.0f - momentum) * run_mean[tid] + momentum * (float)mean;
-      run_var[tid] = (1.0f - momentum) * run_var[tid] + momentum * (float)unbiased;
+      float new_mean, new_var;
+      bn_running_update(momentum, (float)mean, (float)unbiased, run_mean[tid], run_var[tid], new_mean, new_var);
+      run_mean[tid] = new_mean;
+      run_var[tid] = new_var;
     }
     if (tid == 0) nbt[0] += 1;
   } else if (tid < CH) {
@@ -1328,8 +1302,12 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------
 static inline int clampi(int64_t v, int hi) { return (int)(v < hi ? (v < 1 ? 1 : v) : hi); }
 
+// stats_stage (include/msig_ab.h; 0 = the whole front end): an EVAL descriptor's front end up to and including the convolution of
+// stage 1 or 2 with that convolution's per-workgroup partial sums ON, nothing after it; *stats_rows = the partial rows it wrote.
+// Stage 2 passes through BatchNorm-1's eval-form constants (bn_finalize with training = 0: reads the running statistics, writes
+// only WS_BN1_STAT).
 int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                        bool gated) {
+                        bool gated, int stats_stage, int* stats_rows) {
   const float* P = b->params;
   float* mean = w.p<float>(MSIG_WS_GATE_MEAN);
   float* pre = w.p<float>(MSIG_WS_GATE_PRE);
@@ -1361,6 +1339,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     MSIG_LAUNCH_CHECK();
   }
   const int tr = b->training;                // batch statistics and the running-statistic update
+  const int want1 = tr || stats_stage == 1, want2 = tr || stats_stage == 2;      // partial sums of the stage's convolution
   const bool keep = msig_keeps(b);            // the pooling decisions the backward routes through (training, or an eval forward kept for one)
   // ---- stage 1
   {
@@ -1372,7 +1351,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     {
       MSIG_K("conv1_fwd", st);
 #define C1F(CT, G) conv1_fwd_kernel<CT, G><<<dim3(grid, 1, fc.n), 256, smem, st>>>(b->x, P + po[MSIG_P_CONV1_W], gs, w.p<float>(MSIG_WS_Y1), \
-                                                             w.p<float>(MSIG_WS_BN1_PART), d.B, d.C, d.T, d.L1, tr, fc)
+                                                             w.p<float>(MSIG_WS_BN1_PART), d.B, d.C, d.T, d.L1, want1, fc)
 #define C1F_ALL(G) switch (d.C) { \
         case 1: C1F(1, G); break; case 2: C1F(2, G); break; case 3: C1F(3, G); break; case 4: C1F(4, G); break; \
         case 5: C1F(5, G); break; case 6: C1F(6, G); break; case 7: C1F(7, G); break; case 8: C1F(8, G); break; \
@@ -1382,6 +1361,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
 #undef C1F
     }
     MSIG_LAUNCH_CHECK();
+    if (stats_stage == 1) { *stats_rows = grid; return 0; }
     { MSIG_K("bn_finalize", st); bn_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(w.p<float>(MSIG_WS_BN1_PART), grid, 16, (double)d.B * d.L1, P + po[MSIG_P_BN1_G],
                                           P + po[MSIG_P_BN1_B], b->bn_state, b->bn_state + 16, b->bn_count, b->bn_momentum,
                                           b->bn_eps, tr, w.p<float>(MSIG_WS_BN1_STAT), fc); }
@@ -1393,8 +1373,9 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     const int grid = clampi((int64_t)d.B * nchunk, MSIG_PERSIST_WG);
     { MSIG_K("pool1_conv2_fwd", st); pool1_conv2_fwd_kernel<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_Y1), w.p<float>(MSIG_WS_BN1_STAT), w.p<float>(MSIG_WS_P1),
                                             keep ? w.p<uint8_t>(MSIG_WS_POOLC1) : nullptr, P + po[MSIG_P_CONV2_W], w.p<float>(MSIG_WS_Y2),
-                                            w.p<float>(MSIG_WS_BN2_PART), d.B, d.L1, d.P1, d.L2, tr, fc); }
+                                            w.p<float>(MSIG_WS_BN2_PART), d.B, d.L1, d.P1, d.L2, want2, fc); }
     MSIG_LAUNCH_CHECK();
+    if (stats_stage == 2) { *stats_rows = grid; return 0; }
     { MSIG_K("bn_finalize", st); bn_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(w.p<float>(MSIG_WS_BN2_PART), grid, 32, (double)d.B * d.L2, P + po[MSIG_P_BN2_G],
                                           P + po[MSIG_P_BN2_B], b->bn_state + 32, b->bn_state + 64, b->bn_count + 1,
                                           b->bn_momentum, b->bn_eps, tr, w.p<float>(MSIG_WS_BN2_STAT), fc); }

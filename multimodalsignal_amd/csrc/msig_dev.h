@@ -224,6 +224,47 @@ __device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
   return mx + logf(se);
 }
 
+// Column sums of part[nrows][ncol] (ncol <= 64) by one 1024-thread workgroup into red[0..ncol): 1024/ncol
+// row-lanes, 8 loads in flight per lane, fixed combination order (deterministic for a given nrows).
+#define FIN_THREADS 1024
+__device__ __forceinline__ void fin_colsums(const float* __restrict__ part, int nrows, int ncol, double* red) {
+  const int tid = threadIdx.x;
+  const int col = tid % ncol, grp = tid / ncol, ngrp = FIN_THREADS / ncol;
+  double a[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a[j] = 0.0;
+  if (grp < ngrp) {
+    int r = grp;
+    for (; r + 7 * ngrp < nrows; r += 8 * ngrp) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = part[(size_t)(r + j * ngrp) * ncol + col];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] += (double)v[j];
+    }
+    for (; r < nrows; r += ngrp) a[0] += (double)part[(size_t)r * ncol + col];
+  }
+  red[tid] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  __syncthreads();
+  double s = 0.0;
+  if (tid < ncol)
+    for (int g = 0; g < ngrp; ++g) s += red[g * ncol + tid];
+  __syncthreads();
+  if (tid < ncol) red[tid] = s;
+  __syncthreads();
+}
+
+// BatchNorm's running-statistic update  new = (1 - momentum) * old + momentum * batch  with its roundings PINNED: the mean as two
+// rounded products and their sum, the variance as one rounded product and a fused multiply-add.  That is what bn_finalize_kernel
+// has always computed (the compiler's contraction of the plain expressions); written out so that adapt_bn.hip's commit, which
+// must give the same bits from the same sums, does not depend on how another kernel's expressions happen to be contracted.
+__device__ __forceinline__ void bn_running_update(float momentum, float mean, float unbiased, float old_mean, float old_var, float& new_mean,
+                                                  float& new_var) {
+#pragma clang fp contract(off)
+  new_mean = (1.0f - momentum) * old_mean + momentum * mean;
+  new_var = __builtin_fmaf(momentum, unbiased, (1.0f - momentum) * old_var);
+}
+
 // ---- fold batching (msig_*_multi): one launch covers several independent models ("folds" of the LOSO loop) -------------
 // Every buffer of fold f (parameters, gradients, Adam moments, BN state, workspace, input batch, labels) lives at the SAME
 // offset inside a per-fold arena, arenas are `stride` bytes apart, and blockIdx.z selects the fold: every pointer a kernel
@@ -293,12 +334,17 @@ struct WsPtrs {
 };
 
 // gated = false: CnnGruModel's front end (include/msig_cg.h): conv1 on raw taps, no gate, no gate_bwd, no ds
+// stats_stage 1 / 2 (include/msig_ab.h): stop after that stage's convolution, its partial sums on; *stats_rows = rows written
 int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                        bool gated = true);
+                        bool gated = true, int stats_stage = 0, int* stats_rows = nullptr);
 struct ColsumPlan;
 int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
                         bool gated = true);
 int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st);
+// adapt_bn.hip (include/msig_ab.h): part[nrows][2 * CH] of every fold of the launch -> += into the stage's slots of its accumulator;
+// the stage's slices of the BatchNorm state from the accumulator
+int launch_ab_merge(const float* part, int nrows, int stage, double count, double* acc, const FoldCtx& fc, hipStream_t st);
+int launch_ab_commit(const double* acc, int stage, float alpha, const float* bn_src, float* bn_dst, const FoldCtx& fc, hipStream_t st);
 int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st);
 // Soft targets (include/msig_st.h): the launch's label smoothing and every fold's mixup weight; NULL wherever it is
 // taken = the plain criterion's kernels.

@@ -257,6 +257,46 @@ def calibrate_units(kept, units, cfgs, device, rank=0):
     return out
 
 
+def adaptation_settings(cfg):
+    """The adaptation settings of a configuration (--adapt-bn ...), as adaptation.txt / adaptation.json name them."""
+    return {"alpha": float(cfg.get("adapt_bn", 1.0))}
+
+
+def adapt_units(kept, units, cfgs, device, rank=0):
+    """Label-free BatchNorm adaptation of the rank's finished folds (adapt.BnAdapter): per fold the running statistics of the fold's
+    model (the one its test pass evaluated) are re-estimated on the TEST subject's windows, labels unread, and the LOSO model and the
+    adapted one are evaluated on those same windows.  All folds of a configuration adapt as one fold batch
+    (cfg["adapt_bn_batched"] False: single calls, the same bits).  The models, best_model.pt, fold_result.json and the LOSO summary
+    are untouched; each fold directory gets adaptation_result.json.
+    Returns {unit: ((acc, f1) before, (acc, f1) after, (n, 0.0))}."""
+    from .adapt import BnAdapter
+    out, by_cfg = {}, {}
+    for u in sorted(kept):
+        by_cfg.setdefault(units[u][0], []).append(u)
+    for n, us in by_cfg.items():
+        cfg = cfgs[n]
+        st = adaptation_settings(cfg)
+        for c0 in range(0, len(us), L.MAX_FOLDS):
+            chunk, jobs = us[c0:c0 + L.MAX_FOLDS], []
+            for u in chunk:
+                loader = kept[u]["loaders"][2]
+                pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=device)
+                jobs.append(dict(model=kept[u]["model"], x=loader.store.index_select(0, pos), y=loader.store_y.index_select(0, pos)))
+            ad = BnAdapter(jobs, alpha=st["alpha"], batched=bool(cfg.get("adapt_bn_batched", True)),
+                           eval_batch=kept[chunk[0]]["loaders"][2].batch_size)
+            for u, r in zip(chunk, ad.run()):
+                p = kept[u]
+                r = dict(subject=p["subject"], settings=st, **r)
+                (p["fold_dir"] / "adaptation_result.json").write_text(json.dumps(r))
+                tag = f"{n}/" if n else ""
+                print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) BatchNorm adaptation on {r['n']} unlabelled windows: "
+                      f"acc {r['before']['accuracy']:.4f} -> {r['after']['accuracy']:.4f}  f1 {r['before']['f1_score']:.4f} -> "
+                      f"{r['after']['f1_score']:.4f}", flush=True)
+                out[u] = ((r["before"]["accuracy"], r["before"]["f1_score"]), (r["after"]["accuracy"], r["after"]["f1_score"]),
+                          (float(r["n"]), 0.0))
+    return out
+
+
 def _warm_imports():
     try:
         import matplotlib
@@ -324,8 +364,9 @@ def train_units(mine, groups, make, cfg0, device):
     yield from zip(mine, on_streams(lambda u: train_fold(preps[u], device), mine, device, workers=min(conc, MAX_TRAIN_STREAMS)))
 
 
-def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data):
-    """cv_summary.txt — and calibration.txt / calibration.json after --calibrate — of every configuration of a job."""
+def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None):
+    """cv_summary.txt — and calibration.txt / calibration.json after --calibrate, adaptation.txt / adaptation.json after --adapt-bn —
+    of every configuration of a job."""
     for n in cfgs:
         out_dir[n].mkdir(parents=True, exist_ok=True)
         path = write_summary(out_dir[n], results[n], cfgs[n], wall, world)
@@ -341,6 +382,14 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data)
                      for u in sorted(cal_all) if units[u][0] == n]
             path = write_calibration(out_dir[n], folds, calibration_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
             print(f"校准结果已保存至: {path}")
+        if ad_all is not None:
+            from .adapt import write_adaptation
+            folds = [{"subject": cfgs[n]["subjects"][units[u][1]], "n": int(ad_all[u][2][0]),
+                      "before": {"accuracy": ad_all[u][0][0], "f1_score": ad_all[u][0][1]},
+                      "after": {"accuracy": ad_all[u][1][0], "f1_score": ad_all[u][1][1]}}
+                     for u in sorted(ad_all) if units[u][0] == n]
+            path = write_adaptation(out_dir[n], folds, adaptation_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
+            print(f"BatchNorm adaptation table written to: {path}")
 
 
 def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, world=1):
@@ -361,12 +410,13 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     units, mine, groups = rank_units(cfgs, world, rank)
     out_dir = {n: (Path(run_output_dir) / n if n else Path(run_output_dir)) for n in cfgs}
     n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off
-    kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration after the folds; -> its metrics
+    adapt = cfg0.get("adapt_bn") is not None         # --adapt-bn: label-free BatchNorm adaptation to the test subject; absent = off
+    kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration / adaptation after the folds; -> its metrics
 
     def make(u):
         n, k = units[u]
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
-        if n_cal:
+        if n_cal or adapt:
             kept[u] = p
         return p
 
@@ -376,6 +426,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         print(f"[rank {rank}] {n + '/' if n else ''}fold {k} ({cfgs[n]['subjects'][k]}): acc {info['accuracy']:.4f} f1 {info['f1_score']:.4f} "
               f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
     cal_local = calibrate_units(kept, units, cfgs, device, rank) if n_cal and kept else {}
+    ad_local = adapt_units(kept, units, cfgs, device, rank) if adapt and kept else {}      # on its own: the LOSO model, not the calibrated one
     # emulate_rank (bench.py --emulate-ranks): this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what
     # that rank executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
     emulate, gdev = cfg0.get("emulate_rank"), cfg0.get("gather_device", device)
@@ -387,13 +438,19 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     elif n_cal:
         parts = [gather_fold_metrics({u: v[i] for u, v in cal_local.items()}, len(units), world, gdev) for i in range(3)]
         cal_all = {u: (parts[0][u], parts[1][u], parts[2][u]) for u in parts[0]}
+    ad_all = None
+    if adapt and emulate:
+        ad_all = dict(ad_local)
+    elif adapt:
+        parts = [gather_fold_metrics({u: v[i] for u, v in ad_local.items()}, len(units), world, gdev) for i in range(3)]
+        ad_all = {u: (parts[0][u], parts[1][u], parts[2][u]) for u in parts[0]}
     warm.join()            # long done in a real run; a tiny one must not leave an import running at interpreter exit
     results = {n: [] for n in cfgs}
     for u in sorted(allm):
         n, k = units[u]
         results[n].append({"subject": cfgs[n]["subjects"][k], "accuracy": allm[u][0], "f1_score": allm[u][1]})
     if rank == 0 or emulate:
-        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data)
+        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all)
     return results, wall
 
 
@@ -620,6 +677,16 @@ def parse_args(ap, argv=None):
         ap.error("--calibration-gap and --calibration-epochs must be >= 0")
     if args.calibration_lr is not None and not args.calibration_lr > 0:
         ap.error("--calibration-lr must be > 0")
+    if args.adapt_bn is not None:
+        from .adapt import check_alpha
+        try:
+            args.adapt_bn = check_alpha(args.adapt_bn)
+        except ValueError as e:
+            ap.error(f"--adapt-bn: {e}")
+        if args.hierarchical or args.ablation or args.sweep:
+            ap.error("--adapt-bn runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
+    elif args.adapt_bn_sequential:
+        ap.error("--adapt-bn-sequential needs --adapt-bn")
     try:
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
@@ -709,6 +776,14 @@ def build_parser():
     ap.add_argument("--calibration-lr", type=float, default=None, help="learning rate of the calibration (default: the run's LEARNING_RATE)")
     ap.add_argument("--calibration-sequential", action="store_true",
                     help="calibrate with one launch per fold and epoch instead of one per epoch for all folds of a rank (the same bits)")
+    ap.add_argument("--adapt-bn", type=float, nargs="?", const=1.0, default=None, metavar="ALPHA",
+                    help="after each fold's test pass, label-free BatchNorm adaptation (AdaBN): every weight as trained, the BatchNorm "
+                         "running statistics re-estimated on the test subject's unlabelled windows and blended as (1 - ALPHA) * trained + "
+                         "ALPHA * subject (bare flag: 1.0); evaluates the LOSO model and the adapted one on the same windows and writes "
+                         "adaptation.txt / adaptation.json (standard LOSO and --model comparison runs; may be combined with --calibrate, "
+                         "each on its own against the LOSO model)")
+    ap.add_argument("--adapt-bn-sequential", action="store_true",
+                    help="adapt with single calls per fold instead of one fold batch for all folds of a rank (the same bits)")
     return ap
 
 
@@ -735,6 +810,8 @@ def build_cfg(args, kinds):
                          ("calibration_lr", args.calibration_lr)):
             if val is not None:
                 cfg[key] = val
+    if args.adapt_bn is not None:      # likewise: without the flag there is no such key
+        cfg.update(adapt_bn=args.adapt_bn, synthetic=args.synthetic is not None, adapt_bn_batched=not args.adapt_bn_sequential)
     return cfg
 
 

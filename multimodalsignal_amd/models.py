@@ -221,6 +221,21 @@ class _MsigModel(nn.Module):
             raise RuntimeError(f"{type(self).__name__}.embed needs a GPU tensor: the MI355X path has no CPU fallback")
         return self.engine().features(x)
 
+    @torch.no_grad()
+    def adapt_bn(self, x, alpha=1.0, inplace=False):
+        """Label-free BatchNorm adaptation (AdaBN, adapt.BnAdapter, include/msig_ab.h): the four ``cnn_encoder.{1,5}.running_{mean,var}``
+        tensors this model would have with the statistics of the unlabelled windows ``x`` (N, C, T) — stage 1 over the whole set,
+        then stage 2 under the adapted stage 1 in its eval form — blended as ``(1 - alpha) * current + alpha * new``.  Every weight,
+        ``num_batches_tracked`` and ``self.training`` are untouched; with ``inplace=False`` so are the running statistics, and
+        ``inplace=True`` loads the returned tensors into the model."""
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.adapt_bn needs a GPU tensor: the MI355X path has no CPU fallback")
+        from .adapt import BnAdapter
+        bufs = BnAdapter([dict(model=self, x=x)], alpha=alpha).adapted_buffers(0)
+        if inplace:
+            self.engine().load_named(bufs)
+        return bufs
+
     def forward(self, x):
         if isinstance(x, (list, tuple)):
             raise TypeError("this model takes one (B, C, T) tensor (trainer.py:135-140's list branch is for a dataset "
