@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -92,6 +92,9 @@ FT_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_FT_KIND_*
 AB_ABI_VERSION = 1    # include/msig_ab.h MSIG_AB_ABI_VERSION (label-free BatchNorm adaptation)
 AB_ACC_DOUBLES = 98   # msig_ab.h MSIG_AB_ACC_DOUBLES: fp64 values of one model's accumulator
 AB_N1, AB_N2, AB_SUM1, AB_SQ1, AB_SUM2, AB_SQ2 = 0, 1, 2, 18, 34, 66      # msig_ab.h MSIG_AB_*: the accumulator's slots
+AT_ABI_VERSION = 1    # include/msig_at.h MSIG_AT_ABI_VERSION (integrated-gradients attribution: path points and their reduction)
+AT_MAX_POINTS = 256   # msig_at.h MSIG_AT_MAX_POINTS: path points per window
+AT_BASE_ZERO, AT_BASE_CHANNEL, AT_BASE_SHARED, AT_BASE_OWN = range(4)      # msig_at.h MSIG_AT_BASE_*: what the baseline pointer holds
 
 
 class Multi(C.Structure):
@@ -270,6 +273,12 @@ def lib() -> C.CDLL:
         L.msig_ab_accumulate_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.c_int, C.c_int, vp, vp]
         L.msig_ab_commit.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp]
         L.msig_ab_commit_multi.argtypes = [vp, C.c_int, C.c_float, vp, vp, C.POINTER(Multi), vp]
+        # include/msig_at.h, exported by the same library: the path points of integrated gradients and the reduction of their gradients
+        L.msig_at_abi_version.restype = C.c_int
+        if L.msig_at_abi_version() != AT_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_at.h ABI {L.msig_at_abi_version()}; this binding is {AT_ABI_VERSION}: rebuild the library")
+        L.msig_at_path.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+        L.msig_at_reduce.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
         # include/msig_gc.h, exported by the same library: the train steps with gradient-norm clipping
         L.msig_gc_abi_version.restype = C.c_int
         L.msig_gc_struct_bytes.restype = C.c_int64

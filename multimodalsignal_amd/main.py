@@ -297,6 +297,44 @@ def adapt_units(kept, units, cfgs, device, rank=0):
     return out
 
 
+def attribution_settings(cfg):
+    """The attribution settings of a configuration (--attribute ...), as attribution.txt / attribution.json name them; the bin is
+    the flag's, else one second of a 60-second window of T samples (None while T is not known)."""
+    out = {"steps": int(cfg["attribute"]), "baseline": "zero", "target": "predicted"}
+    if cfg.get("attribute_bin") is not None:
+        out["bin"] = int(cfg["attribute_bin"])
+    return out
+
+
+def attribute_units(kept, units, cfgs, device, rank=0):
+    """Integrated-gradients attribution of the rank's finished folds (attribute.fold_attribution): per fold, from the model the fold
+    trained (the one its test pass evaluated) and the TEST subject's windows — which channels and which seconds of the window the
+    predicted class rests on, the gate's values and the forward-only channel-occlusion drops.  One model at a time: a path batch
+    fills the chip on its own.  The models, best_model.pt, fold_result.json and the LOSO summary are untouched; each fold directory
+    gets attribution_result.json.  Returns the units attributed."""
+    from .attribute import fold_attribution
+    from .runtime import Engine
+    done = []
+    for u in sorted(kept):
+        n, _ = units[u]
+        cfg, p = cfgs[n], kept[u]
+        loader, model = p["loaders"][2], p["model"]
+        pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=device)
+        x, y = loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+        r = fold_attribution(model, x, y, steps=int(cfg["attribute"]), bin=cfg.get("attribute_bin"), channels=cfg["channels"],
+                             num_classes=cfg["num_classes"])
+        model.engine().drop_workspaces(Engine.EVAL_KEEP)           # the kept-evaluation workspace of a path batch: not needed again
+        r = dict(subject=p["subject"], **r)
+        (p["fold_dir"] / "attribution_result.json").write_text(json.dumps(r))
+        order = np.argsort(-np.asarray(r["share"]), kind="stable")
+        tag = f"{n}/" if n else ""
+        print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) attribution over {r['n']} windows, {r['steps']} path points: "
+              + ", ".join(f"{r['channels'][i]} {r['share'][i]:.3f}" for i in order)
+              + f" | completeness gap mean {r['gap_rel_mean']:.2e} max {r['gap_rel_max']:.2e}", flush=True)
+        done.append(u)
+    return done
+
+
 def _warm_imports():
     try:
         import matplotlib
@@ -364,9 +402,10 @@ def train_units(mine, groups, make, cfg0, device):
     yield from zip(mine, on_streams(lambda u: train_fold(preps[u], device), mine, device, workers=min(conc, MAX_TRAIN_STREAMS)))
 
 
-def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None):
-    """cv_summary.txt — and calibration.txt / calibration.json after --calibrate, adaptation.txt / adaptation.json after --adapt-bn —
-    of every configuration of a job."""
+def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None, attributed=False):
+    """cv_summary.txt — and calibration.txt / calibration.json after --calibrate, adaptation.txt / adaptation.json after --adapt-bn,
+    attribution.txt / attribution.json after --attribute (from the folds' attribution_result.json, which every rank has written
+    before the fold metrics were gathered) — of every configuration of a job."""
     for n in cfgs:
         out_dir[n].mkdir(parents=True, exist_ok=True)
         path = write_summary(out_dir[n], results[n], cfgs[n], wall, world)
@@ -390,6 +429,13 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
                      for u in sorted(ad_all) if units[u][0] == n]
             path = write_adaptation(out_dir[n], folds, adaptation_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
             print(f"BatchNorm adaptation table written to: {path}")
+        if attributed:
+            from .attribute import write_attribution
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "attribution_result.json" for r in results[n]]
+            folds = [json.loads(f.read_text()) for f in files if f.exists()]
+            if folds:
+                path = write_attribution(out_dir[n], folds, attribution_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Attribution table written to: {path}")
 
 
 def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, world=1):
@@ -411,12 +457,13 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     out_dir = {n: (Path(run_output_dir) / n if n else Path(run_output_dir)) for n in cfgs}
     n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off
     adapt = cfg0.get("adapt_bn") is not None         # --adapt-bn: label-free BatchNorm adaptation to the test subject; absent = off
+    attr = cfg0.get("attribute") is not None         # --attribute: integrated-gradients attribution on the test subject; absent = off
     kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration / adaptation after the folds; -> its metrics
 
     def make(u):
         n, k = units[u]
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
-        if n_cal or adapt:
+        if n_cal or adapt or attr:
             kept[u] = p
         return p
 
@@ -427,6 +474,8 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
               f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
     cal_local = calibrate_units(kept, units, cfgs, device, rank) if n_cal and kept else {}
     ad_local = adapt_units(kept, units, cfgs, device, rank) if adapt and kept else {}      # on its own: the LOSO model, not the calibrated one
+    if attr and kept:                                # likewise the LOSO model; its records go to the fold directories
+        attribute_units(kept, units, cfgs, device, rank)
     # emulate_rank (bench.py --emulate-ranks): this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what
     # that rank executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
     emulate, gdev = cfg0.get("emulate_rank"), cfg0.get("gather_device", device)
@@ -450,7 +499,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         n, k = units[u]
         results[n].append({"subject": cfgs[n]["subjects"][k], "accuracy": allm[u][0], "f1_score": allm[u][1]})
     if rank == 0 or emulate:
-        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all)
+        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr)
     return results, wall
 
 
@@ -687,6 +736,17 @@ def parse_args(ap, argv=None):
             ap.error("--adapt-bn runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
     elif args.adapt_bn_sequential:
         ap.error("--adapt-bn-sequential needs --adapt-bn")
+    if args.attribute is not None:
+        from .attribute import check_bin, check_steps
+        try:
+            args.attribute = check_steps(args.attribute)
+            args.attribute_bin = check_bin(args.attribute_bin)
+        except ValueError as e:
+            ap.error(f"--attribute: {e}")
+        if args.hierarchical or args.ablation or args.sweep:
+            ap.error("--attribute runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
+    elif args.attribute_bin is not None:
+        ap.error("--attribute-bin needs --attribute")
     try:
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
@@ -784,6 +844,14 @@ def build_parser():
                          "each on its own against the LOSO model)")
     ap.add_argument("--adapt-bn-sequential", action="store_true",
                     help="adapt with single calls per fold instead of one fold batch for all folds of a rank (the same bits)")
+    ap.add_argument("--attribute", type=int, nargs="?", const=32, default=None, metavar="STEPS",
+                    help="after each fold's test pass, integrated-gradients attribution of the fold's model on the test subject's windows "
+                         "(zero baseline, each window's predicted class, STEPS midpoints of the path, 1..256; bare flag: 32): which channels "
+                         "and which seconds the decision rests on, the gate's values and a forward-only channel-occlusion column; writes "
+                         "attribution.txt / attribution.json (standard LOSO and --model comparison runs; may be combined with --calibrate "
+                         "and --adapt-bn, each on its own against the LOSO model)")
+    ap.add_argument("--attribute-bin", type=int, default=None, metavar="SAMPLES",
+                    help="samples per time bin of the attribution's time profile (default max(1, T // 60): one-second bins of 60-second windows)")
     return ap
 
 
@@ -812,6 +880,10 @@ def build_cfg(args, kinds):
                 cfg[key] = val
     if args.adapt_bn is not None:      # likewise: without the flag there is no such key
         cfg.update(adapt_bn=args.adapt_bn, synthetic=args.synthetic is not None, adapt_bn_batched=not args.adapt_bn_sequential)
+    if args.attribute is not None:     # likewise
+        cfg.update(attribute=args.attribute, synthetic=args.synthetic is not None)
+        if args.attribute_bin is not None:
+            cfg["attribute_bin"] = args.attribute_bin
     return cfg
 
 

@@ -236,6 +236,21 @@ class _MsigModel(nn.Module):
             self.engine().load_named(bufs)
         return bufs
 
+    def attribute(self, x, target="predicted", steps=32, baseline=None, bin=None, return_map=True):
+        """Integrated-gradients attribution (attribute.Attributor, include/msig_at.h) of the windows ``x`` (N, C, T) in EVAL mode
+        whatever ``self.training`` is: ``(x - baseline) * mean_p df/dx`` at ``steps`` midpoints of the straight path from the
+        baseline (None: zero; (C,), (C, T) or (N, C, T)) to x, with f = the target's combination of the logits (a class index,
+        "predicted" or a (K,) / (N, K) vector).  Returns an ``attribute.Attribution``: the map, its sums per time bin of ``bin``
+        samples (None: T // 60), per channel and per window, f(x), f(baseline) and the completeness gap.  Parameters, BatchNorm
+        buffers, every ``.grad``, the dropout step counter and ``self.training`` are untouched."""
+        from .attribute import Attributor
+        return Attributor(self, steps=steps, baseline=baseline, bin=bin).attribute(x, target, return_map)
+
+    def channel_occlusion(self, x, target="predicted", baseline=None):
+        """(N, C): f(x) - f(x with channel c set to its baseline), eval-mode forwards only (attribute.Attributor.channel_occlusion)."""
+        from .attribute import Attributor
+        return Attributor(self, baseline=baseline).channel_occlusion(x, target)
+
     def forward(self, x):
         if isinstance(x, (list, tuple)):
             raise TypeError("this model takes one (B, C, T) tensor (trainer.py:135-140's list branch is for a dataset "

@@ -142,7 +142,15 @@ class Engine:
             self._ws[key] = (buf, off)
         return self._ws[key]
 
-    def drop_workspaces(self):
+    def drop_workspaces(self, mode=None):
+        """Frees every workspace, or with `mode` (True, False or EVAL_KEEP) that mode's alone."""
+        if mode is not None:
+            for k in [k for k in self._ws if k[2] == mode]:
+                del self._ws[k]
+            self._ws_pool.pop(mode, None)
+            if self._last is not None and self._last[2] == mode:
+                self._last, self._keep = None, None
+            return
         self._ws.clear()
         self._ws_pool.clear()
         self._last = None
