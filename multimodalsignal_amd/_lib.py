@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -95,6 +95,9 @@ AB_N1, AB_N2, AB_SUM1, AB_SQ1, AB_SUM2, AB_SQ2 = 0, 1, 2, 18, 34, 66      # msig
 AT_ABI_VERSION = 1    # include/msig_at.h MSIG_AT_ABI_VERSION (integrated-gradients attribution: path points and their reduction)
 AT_MAX_POINTS = 256   # msig_at.h MSIG_AT_MAX_POINTS: path points per window
 AT_BASE_ZERO, AT_BASE_CHANNEL, AT_BASE_SHARED, AT_BASE_OWN = range(4)      # msig_at.h MSIG_AT_BASE_*: what the baseline pointer holds
+MC_ABI_VERSION = 1    # include/msig_mc.h MSIG_MC_ABI_VERSION (Monte-Carlo dropout: trunk, expand, tail, reduce)
+MC_MAX_SAMPLES = 256  # msig_mc.h MSIG_MC_MAX_SAMPLES: stochastic passes per window
+MC_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_MC_KIND_*
 
 
 class Multi(C.Structure):
@@ -279,6 +282,14 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} has msig_at.h ABI {L.msig_at_abi_version()}; this binding is {AT_ABI_VERSION}: rebuild the library")
         L.msig_at_path.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
         L.msig_at_reduce.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+        # include/msig_mc.h, exported by the same library: Monte-Carlo dropout (an eval forward cut at the first dropout site)
+        L.msig_mc_abi_version.restype = C.c_int
+        if L.msig_mc_abi_version() != MC_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_mc.h ABI {L.msig_mc_abi_version()}; this binding is {MC_ABI_VERSION}: rebuild the library")
+        L.msig_mc_trunk.argtypes = [C.POINTER(Batch), C.c_int32, vp]
+        L.msig_mc_tail.argtypes = [C.POINTER(Batch), C.c_int32, vp]
+        L.msig_mc_expand.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp]
+        L.msig_mc_reduce.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         # include/msig_gc.h, exported by the same library: the train steps with gradient-norm clipping
         L.msig_gc_abi_version.restype = C.c_int
         L.msig_gc_struct_bytes.restype = C.c_int64

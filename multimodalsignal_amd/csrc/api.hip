@@ -13,6 +13,7 @@
 #include "../../include/msig_st.h"
 #include "finetune.h"
 #include "../../include/msig_ab.h"
+#include "../../include/msig_mc.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -648,6 +649,41 @@ extern "C" int msig_ab_commit(const double* acc, int stage, float alpha, const f
 extern "C" int msig_ab_commit_multi(const double* acc, int stage, float alpha, const float* bn_src, float* bn_dst, const msig_multi* m, void* stream) {
   FoldCtx fc; int rc = msig_multi_fold_ctx(m, fc); if (rc) return rc;
   return ab_commit_fc(acc, stage, alpha, bn_src, bn_dst, fc, (hipStream_t)stream);
+}
+
+// ---- Monte-Carlo dropout (include/msig_mc.h; kernels of its own: mc.hip) ------------------------------------------------------------
+// An eval forward cut at the first dropout site.  Both halves are launch orders of the forward's own kernels (launch_gru_fwd's
+// `part`, launch_head_fwd's `mc_tail`); every argument check before the first launch.
+static int mc_check(const msig_batch* b, int32_t kind) {
+  if (!b) return MSIG_E_NULL;
+  if (kind != MSIG_MC_KIND_ATTENTION && kind != MSIG_MC_KIND_CNN_GRU) return MSIG_E_SHAPE;
+  if (b->training || b->keep_for_backward || b->dx) return MSIG_E_SHAPE;
+  return 0;
+}
+extern "C" int msig_mc_trunk(const msig_batch* b, int32_t kind, void* stream) {
+  int rc = mc_check(b, kind); if (rc) return rc;
+  const bool cg = kind == MSIG_MC_KIND_CNN_GRU;
+  const FoldCtx fc = single_fold(b);
+  hipStream_t st = (hipStream_t)stream;
+  Ctx c; if ((rc = make_ctx(b, c, false, cg))) return rc;
+  if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;
+  if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st, !cg))) return rc;
+  return launch_gru_fwd(b, c.d, c.w, c.po, fc, st, GRU_PART_L0);
+}
+extern "C" int msig_mc_tail(const msig_batch* b, int32_t kind, void* stream) {
+  int rc = mc_check(b, kind); if (rc) return rc;
+  if ((rc = check_shape(&b->shape))) return rc;
+  if ((int64_t)b->shape.B * make_dims(b->shape).TP * 128 > (int64_t)1 << 31) return MSIG_E_SHAPE;      // the mask index is 32-bit
+  msig_batch t = *b;
+  if (!t.x) t.x = t.params;                  // the tail reads no input: x may be NULL (params: any checked pointer, never read as x)
+  t.labels = nullptr;
+  const bool cg = kind == MSIG_MC_KIND_CNN_GRU;
+  const FoldCtx fc = single_fold(&t);
+  hipStream_t st = (hipStream_t)stream;
+  Ctx c; if ((rc = make_ctx(&t, c, false, cg))) return rc;
+  if ((rc = msig_check_call_forms(&t, c.d.NT, fc))) return rc;
+  if ((rc = launch_gru_fwd(&t, c.d, c.w, c.po, fc, st, GRU_PART_L1, true))) return rc;
+  return launch_head_fwd(&t, c.d, c.w, c.po, fc, st, nullptr, nullptr, true);
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {

@@ -1791,11 +1791,11 @@ static void setup_layer0(GruArgs& a, const msig_batch* b, const StageDims& d, co
   }
 }
 
-static void setup_layer1(GruArgs& a, const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po) {
+static void setup_layer1(GruArgs& a, const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, bool force_drop = false) {
   a = GruArgs{};
   a.x = w.p<float>(MSIG_WS_H0); a.x_bs = (int64_t)d.TP * 128; a.x_ts = 128;
   a.B = d.B;
-  a.drop_thr = b->training ? b->dropout_thr : 0; a.drop_key = b->key_gru; a.drop_scale = drop_scale(a.drop_thr);
+  a.drop_thr = (b->training || force_drop) ? b->dropout_thr : 0; a.drop_key = b->key_gru; a.drop_scale = drop_scale(a.drop_thr);
   {  // forward direction: all T' steps
     GruDir& g = a.dir[0];
     fill_dir(g, b->params, po, 1, 0);
@@ -1952,7 +1952,8 @@ int msig_check_call_forms(const msig_batch* b, int n_tiles, const FoldCtx& fc) {
   if (fc.stride != 0 && form != MSIG_FWD_LATENCY && form != MSIG_FWD_WS && form != FWD_MIXED) return MSIG_E_FORM;
   return 0;
 }
-int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st) {
+int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
+                   int part, bool force_drop) {
   GruArgs a;
   { const int rc = msig_check_forms(b); if (rc) return rc; }
   const int form = fwd_form(b, d.NT);
@@ -1977,7 +1978,9 @@ int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
 #ifdef MSIG_STAMPS
   a.dbg = dbg_dev;
 #endif
-  if (latency) {
+  if (part == GRU_PART_L1) {
+    if (b->gru_layers == 1) return 0;            // the one-layer model has no layer above the dropout site
+  } else if (latency) {
     a.gi = w.p<float4>(MSIG_WS_GI);
     a.gi_dir_stride = (size_t)d.NT * d.TP * 4 * 3 * 64;
     const int units = d.NT * d.TP;
@@ -2013,7 +2016,8 @@ int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
     MSIG_LAUNCH_CHECK();
     return 0;
   }
-  setup_layer1(a, b, d, w, po);
+  if (part == GRU_PART_L0) return 0;
+  setup_layer1(a, b, d, w, po, force_drop);
 #ifdef MSIG_STAMPS
   a.dbg = dbg_dev;
 #endif

@@ -959,15 +959,16 @@ int launch_normalise(const double* raw, int64_t N, int T, int C_all, const int* 
 // Host launchers
 // ------------------------------------------------------------------------------------
 int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                    const float* cw, const SoftArgs* soft) {
+                    const float* cw, const SoftArgs* soft, bool mc_tail) {
   const float* P = b->params;
-  const int thr = b->training ? b->dropout_thr : 0;
+  const int thr = (b->training || mc_tail) ? b->dropout_thr : 0;
   const int ngroups = (d.B + HEAD_ROWS - 1) / HEAD_ROWS;
   const int grid = ngroups < 1024 ? ngroups : 1024;
   { MSIG_K("head_fwd", st); head_fwd_kernel<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
                                          P + po[MSIG_P_CLS3_B], w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), d.B, d.K, thr,
                                          b->key_head, drop_scale(thr), fc); }
   MSIG_LAUNCH_CHECK();
+  if (mc_tail) return 0;
   if (b->labels) {
     MSIG_K("ce", st);
     float* dl = msig_keeps(b) ? w.p<float>(MSIG_WS_DLOGITS) : nullptr;

@@ -340,7 +340,13 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
 struct ColsumPlan;
 int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
                         bool gated = true);
-int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st);
+// Monte-Carlo dropout (include/msig_mc.h) splits an eval forward at the first dropout site.  part: which layers
+// launch_gru_fwd runs — all (every msig.h call), layer 0 alone (for gru_layers = 1 with its copy to WS_FEAT: the trunk) or layer 1
+// alone from the WS_H0 it finds (the tail; nothing to run for gru_layers = 1).  force_drop: the dropout masks of b->dropout_thr
+// although b->training = 0.  The defaults are every other call's launches, unchanged.
+enum { GRU_PART_ALL = 0, GRU_PART_L0 = 1, GRU_PART_L1 = 2 };
+int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
+                   int part = GRU_PART_ALL, bool force_drop = false);
 // adapt_bn.hip (include/msig_ab.h): part[nrows][2 * CH] of every fold of the launch -> += into the stage's slots of its accumulator;
 // the stage's slices of the BatchNorm state from the accumulator
 int launch_ab_merge(const float* part, int nrows, int stage, double count, double* acc, const FoldCtx& fc, hipStream_t st);
@@ -350,8 +356,10 @@ int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
 // taken = the plain criterion's kernels.
 struct SoftArgs { float eps; float lam[MSIG_MAX_FOLDS]; };
 // cw: class weights (include/msig_cw.h), K device floats of fold slot 0 (shifted per fold like every buffer); NULL = unweighted
+// mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of b->dropout_thr
+// although b->training = 0
 int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                    const float* cw = nullptr, const SoftArgs* soft = nullptr);
+                    const float* cw = nullptr, const SoftArgs* soft = nullptr, bool mc_tail = false);
 int launch_head_bwd(const msig_batch* b, const float* dlogits, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan,
                     const FoldCtx& fc, hipStream_t st);
 // head forward + CrossEntropy + head backward of a fused train step in one launch (few windows: see head.hip); false = not applicable

@@ -335,6 +335,36 @@ def attribute_units(kept, units, cfgs, device, rank=0):
     return done
 
 
+def uncertainty_settings(cfg):
+    """The Monte-Carlo dropout settings of a configuration (--mc-dropout ...), as uncertainty.txt / uncertainty.json name them."""
+    return {"samples": int(cfg["mc_dropout"]), "seed": int(cfg.get("mc_seed", 0)), "dropout": float(cfg["model_params"]["dropout"])}
+
+
+def uncertainty_units(kept, units, cfgs, device, rank=0):
+    """Monte-Carlo dropout of the rank's finished folds (uncertainty.fold_uncertainty): per fold, from the model the fold trained
+    (the one its test pass evaluated) and the TEST subject's windows — how sure the model is of each window and what refusing the
+    least certain ones buys.  One model at a time: a wide batch fills the chip on its own.  The models, best_model.pt,
+    fold_result.json and the LOSO summary are untouched; each fold directory gets uncertainty_result.json.  Returns the units done."""
+    from .uncertainty import fold_uncertainty
+    done = []
+    for u in sorted(kept):
+        n, _ = units[u]
+        cfg, p = cfgs[n], kept[u]
+        loader, model = p["loaders"][2], p["model"]
+        pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=device)
+        x, y = loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+        r = fold_uncertainty(model, x, y, samples=int(cfg["mc_dropout"]), seed=int(cfg.get("mc_seed", 0)))
+        r = dict(subject=p["subject"], **r)
+        (p["fold_dir"] / "uncertainty_result.json").write_text(json.dumps(r))
+        tag = f"{n}/" if n else ""
+        au = r["auroc_entropy"]
+        print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) Monte-Carlo dropout over {r['n']} windows, {r['samples']} samples: "
+              f"acc eval {r['accuracy_eval']:.4f} mc {r['accuracy_mc']:.4f} | AUROC of entropy {'n/a' if au is None else format(au, '.4f')} | "
+              f"ECE eval {r['ece_eval']:.4f} mc {r['ece_mc']:.4f}", flush=True)
+        done.append(u)
+    return done
+
+
 def _warm_imports():
     try:
         import matplotlib
@@ -402,10 +432,11 @@ def train_units(mine, groups, make, cfg0, device):
     yield from zip(mine, on_streams(lambda u: train_fold(preps[u], device), mine, device, workers=min(conc, MAX_TRAIN_STREAMS)))
 
 
-def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None, attributed=False):
+def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None, attributed=False, uncertain=False):
     """cv_summary.txt — and calibration.txt / calibration.json after --calibrate, adaptation.txt / adaptation.json after --adapt-bn,
-    attribution.txt / attribution.json after --attribute (from the folds' attribution_result.json, which every rank has written
-    before the fold metrics were gathered) — of every configuration of a job."""
+    attribution.txt / attribution.json after --attribute, uncertainty.txt / uncertainty.json after --mc-dropout (from the folds'
+    attribution_result.json / uncertainty_result.json, which every rank has written before the fold metrics were gathered) — of
+    every configuration of a job."""
     for n in cfgs:
         out_dir[n].mkdir(parents=True, exist_ok=True)
         path = write_summary(out_dir[n], results[n], cfgs[n], wall, world)
@@ -436,6 +467,13 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
             if folds:
                 path = write_attribution(out_dir[n], folds, attribution_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
                 print(f"Attribution table written to: {path}")
+        if uncertain:
+            from .uncertainty import write_uncertainty
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "uncertainty_result.json" for r in results[n]]
+            folds = [json.loads(f.read_text()) for f in files if f.exists()]
+            if folds:
+                path = write_uncertainty(out_dir[n], folds, uncertainty_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Uncertainty table written to: {path}")
 
 
 def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, world=1):
@@ -458,12 +496,13 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off
     adapt = cfg0.get("adapt_bn") is not None         # --adapt-bn: label-free BatchNorm adaptation to the test subject; absent = off
     attr = cfg0.get("attribute") is not None         # --attribute: integrated-gradients attribution on the test subject; absent = off
+    mc = cfg0.get("mc_dropout") is not None          # --mc-dropout: Monte-Carlo dropout uncertainty on the test subject; absent = off
     kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration / adaptation after the folds; -> its metrics
 
     def make(u):
         n, k = units[u]
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
-        if n_cal or adapt or attr:
+        if n_cal or adapt or attr or mc:
             kept[u] = p
         return p
 
@@ -476,6 +515,8 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     ad_local = adapt_units(kept, units, cfgs, device, rank) if adapt and kept else {}      # on its own: the LOSO model, not the calibrated one
     if attr and kept:                                # likewise the LOSO model; its records go to the fold directories
         attribute_units(kept, units, cfgs, device, rank)
+    if mc and kept:                                  # likewise
+        uncertainty_units(kept, units, cfgs, device, rank)
     # emulate_rank (bench.py --emulate-ranks): this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what
     # that rank executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
     emulate, gdev = cfg0.get("emulate_rank"), cfg0.get("gather_device", device)
@@ -499,7 +540,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         n, k = units[u]
         results[n].append({"subject": cfgs[n]["subjects"][k], "accuracy": allm[u][0], "f1_score": allm[u][1]})
     if rank == 0 or emulate:
-        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr)
+        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr, uncertain=mc)
     return results, wall
 
 
@@ -747,6 +788,17 @@ def parse_args(ap, argv=None):
             ap.error("--attribute runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
     elif args.attribute_bin is not None:
         ap.error("--attribute-bin needs --attribute")
+    if args.mc_dropout is not None:
+        from .uncertainty import check_samples, check_seed
+        try:
+            args.mc_dropout = check_samples(args.mc_dropout)
+            args.mc_seed = check_seed(0 if args.mc_seed is None else args.mc_seed)
+        except ValueError as e:
+            ap.error(f"--mc-dropout: {e}")
+        if args.hierarchical or args.ablation or args.sweep:
+            ap.error("--mc-dropout runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
+    elif args.mc_seed is not None:
+        ap.error("--mc-seed needs --mc-dropout")
     try:
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
@@ -852,6 +904,14 @@ def build_parser():
                          "and --adapt-bn, each on its own against the LOSO model)")
     ap.add_argument("--attribute-bin", type=int, default=None, metavar="SAMPLES",
                     help="samples per time bin of the attribution's time profile (default max(1, T // 60): one-second bins of 60-second windows)")
+    ap.add_argument("--mc-dropout", type=int, nargs="?", const=32, default=None, metavar="S",
+                    help="after each fold's test pass, Monte-Carlo dropout of the fold's model on the test subject's windows: S stochastic "
+                         "passes (1..256; bare flag: 32) with both dropout masks on and BatchNorm in its eval form, the deterministic trunk "
+                         "run once per window; predictive entropy, mutual information, AUROC of the entropy as an error detector, "
+                         "selective accuracy at 100 / 90 / 80 / 50 %% coverage and ECE; writes uncertainty.txt / uncertainty.json (standard "
+                         "LOSO and --model comparison runs; may be combined with --calibrate, --adapt-bn and --attribute, each on its own "
+                         "against the LOSO model)")
+    ap.add_argument("--mc-seed", type=int, default=None, metavar="SEED", help="seed of the Monte-Carlo dropout masks (default 0)")
     return ap
 
 
@@ -884,6 +944,8 @@ def build_cfg(args, kinds):
         cfg.update(attribute=args.attribute, synthetic=args.synthetic is not None)
         if args.attribute_bin is not None:
             cfg["attribute_bin"] = args.attribute_bin
+    if args.mc_dropout is not None:    # likewise
+        cfg.update(mc_dropout=args.mc_dropout, mc_seed=args.mc_seed, synthetic=args.synthetic is not None)
     return cfg
 
 

@@ -251,6 +251,18 @@ class _MsigModel(nn.Module):
         from .attribute import Attributor
         return Attributor(self, baseline=baseline).channel_occlusion(x, target)
 
+    def predict_mc(self, x, samples=32, seed=0, chunk=None, return_samples=False):
+        """Monte-Carlo dropout (uncertainty.McDropout, include/msig_mc.h) of the windows ``x`` (N, C, T): ``samples`` stochastic
+        passes with both dropout masks on at ``dropout`` and BatchNorm in its EVAL form, whatever ``self.training`` is.  Returns an
+        ``uncertainty.McPrediction``: mean and std of the softmax vectors, the prediction, predictive entropy, expected entropy,
+        mutual information and the vote split (with ``return_samples`` also the (N, S, K) logits).  The deterministic trunk — front
+        end and GRU layer 0 — runs once per window.  Windows are cut into chunks of ``chunk`` (None: the most with chunk * samples
+        <= 2048 rows); chunk j draws its masks under msig_dropout_key(seed, j, 1 / 2), so a result is a function of (weights, x,
+        seed, samples, chunk) alone.  Parameters, BatchNorm buffers, ``num_batches_tracked``, ``self.training``, the dropout step
+        counter and torch's RNG are untouched."""
+        from .uncertainty import McDropout
+        return McDropout(self, samples=samples, seed=seed, chunk=chunk).predict(x, return_samples)
+
     def forward(self, x):
         if isinstance(x, (list, tuple)):
             raise TypeError("this model takes one (B, C, T) tensor (trainer.py:135-140's list branch is for a dataset "
