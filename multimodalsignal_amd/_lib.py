@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -98,6 +98,8 @@ AT_BASE_ZERO, AT_BASE_CHANNEL, AT_BASE_SHARED, AT_BASE_OWN = range(4)      # msi
 MC_ABI_VERSION = 1    # include/msig_mc.h MSIG_MC_ABI_VERSION (Monte-Carlo dropout: trunk, expand, tail, reduce)
 MC_MAX_SAMPLES = 256  # msig_mc.h MSIG_MC_MAX_SAMPLES: stochastic passes per window
 MC_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_MC_KIND_*
+DA_ABI_VERSION = 1    # include/msig_da.h MSIG_DA_ABI_VERSION (subject-adversarial training: the discriminator's step)
+DA_MAX_BATCH = 256    # msig_da.h MSIG_DA_MAX_BATCH: rows of one discriminator step
 
 
 class Multi(C.Structure):
@@ -146,6 +148,16 @@ class St(C.Structure):
     msig_gc_clip (by address: `make_st` keeps it alive) and the mixup weight of every fold."""
     _fields_ = [("kind", C.c_int32), ("smoothing", C.c_float), ("class_weight", C.c_void_p), ("clip", C.c_void_p),
                 ("lam", C.c_float * MAX_FOLDS)]
+
+
+class Da(C.Structure):
+    """msig_da (include/msig_da.h): the subject discriminator of a launch — its size and Adam constants, the domain table and the
+    batch's store positions, its parameter / moment / statistics buffers (per fold `stride_bytes` apart) and every fold's reversal
+    weight, learning rate and step count."""
+    _fields_ = [("S", C.c_int32), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("dom", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64), ("params", C.c_void_p), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p), ("stats", C.c_void_p), ("stride_bytes", C.c_int64), ("lambda", C.c_float * MAX_FOLDS),
+                ("lr", C.c_float * MAX_FOLDS), ("step", C.c_int64 * MAX_FOLDS)]
 
 
 def make_st(kind: str, smoothing: float, class_weight=None, clip: "GcClip" = None, lams=(1.0,)) -> St:
@@ -321,6 +333,19 @@ def lib() -> C.CDLL:
         L.msig_st_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), vp, vp, f32, f32, f32, f32, i64, vp]
         L.msig_st_gather_windows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(Aug), C.POINTER(f32), vp]
         L.msig_st_gather_windows_multi.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, C.POINTER(Multi), C.POINTER(Aug), C.POINTER(f32), vp]
+        # include/msig_da.h, exported by the same library: the subject discriminator's step, alone and inside the train steps
+        L.msig_da_abi_version.restype = C.c_int
+        L.msig_da_struct_bytes.restype = C.c_int64
+        if L.msig_da_abi_version() != DA_ABI_VERSION or L.msig_da_struct_bytes() != C.sizeof(Da):
+            raise RuntimeError(f"{LIB_PATH} has msig_da.h ABI {L.msig_da_abi_version()} with msig_da of {L.msig_da_struct_bytes()} bytes; "
+                               f"this binding is {DA_ABI_VERSION} with {C.sizeof(Da)}: rebuild the library")
+        L.msig_da_param_floats.argtypes = [i32]
+        L.msig_da_param_floats.restype = C.c_int64
+        L.msig_da_step.argtypes = [C.POINTER(Da), vp, vp, i32, f32, vp]
+        L.msig_da_step_multi.argtypes = [C.POINTER(Da), C.POINTER(Multi), vp, vp, i32, C.POINTER(f32), vp]
+        L.msig_da_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Da), vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_da_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), vp, vp, f32, f32, f32, f32,
+                                               i64, vp]
         _lib = L
     return _lib
 
@@ -414,6 +439,14 @@ def gc_state_bytes(Cin: int, K: int, kind: str = "cnn_gru_attention") -> int:
     n = int(lib().msig_gc_state_bytes(Cin, K, GC_KINDS[check_kind(kind)]))
     if n < 0:
         check(n, "msig_gc_state_bytes")
+    return n
+
+
+def da_param_floats(S: int) -> int:
+    """Floats of a subject discriminator's parameter buffer for S domains (include/msig_da.h msig_da_param_floats)."""
+    n = int(lib().msig_da_param_floats(int(S)))
+    if n < 0:
+        check(n, "msig_da_param_floats")
     return n
 
 

@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h and msig_st.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h and msig_da.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -301,7 +301,7 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
 // fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch)
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
                          float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr, bool cg = false,
-                         const ClipArgs* clip = nullptr, const SoftArgs* soft = nullptr) {
+                         const ClipArgs* clip = nullptr, const SoftArgs* soft = nullptr, const DaArgs* da = nullptr) {
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
   if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
@@ -322,6 +322,8 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
   if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, cw, soft) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
+  // subject discriminator (include/msig_da.h): WS_FEAT and WS_DFEAT are complete here; its launch adds the reversed gradient to WS_DFEAT
+  if (da && (rc = launch_da_step(*da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
@@ -512,17 +514,22 @@ static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, 
   if (!b) return MSIG_E_NULL;
   return forward_fc(b, fc, st, true, s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, use ? &soft : nullptr);
 }
+static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* lam, DaArgs& da);
+// a: the subject discriminator of include/msig_da.h (NULL = msig_st_train_step[_multi] itself)
 static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
-                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st) {
+                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st,
+                         const msig_da* a = nullptr) {
   SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
   if (!b) return MSIG_E_NULL;
+  DaArgs da;
+  if (a && (rc = make_da(a, fc, b->shape.B, soft.lam, da))) return rc;
   ClipArgs cl;
   if (s->clip) {
     if (s->clip->kind != s->kind) return MSIG_E_SHAPE;
     if ((rc = make_clip(b, s->clip, fc.n, cl))) return rc;
   }
   return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st, s->class_weight,
-                       s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr);
+                       s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr);
 }
 extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
   return st_forward(b, single_fold(b), s, (hipStream_t)stream);
@@ -541,6 +548,67 @@ extern "C" int msig_st_train_step_multi(const msig_batch* b, const msig_multi* m
   if (!s) return MSIG_E_NULL;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+
+// ---- subject-adversarial training (include/msig_da.h; kernel: adversary.hip) ---------------------------------------------------------
+extern "C" int msig_da_abi_version(void) { return MSIG_DA_ABI_VERSION; }
+extern "C" int64_t msig_da_struct_bytes(void) { return (int64_t)sizeof(msig_da); }
+extern "C" int64_t msig_da_param_floats(int32_t S) {
+  if (S < 2 || S > MSIG_MAX_K) return MSIG_E_SHAPE;
+  return 64 * 128 + 64 + ((int64_t)S * 64 + 3) / 4 * 4 + (S + 3) / 4 * 4;
+}
+// every check of msig_da.h's own arguments, before any launch; fc: the folds of the launch (stride != 0: a fold batch); lam per fold
+static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* lam, DaArgs& da) {
+  if (!a || !lam) return MSIG_E_NULL;
+  if (!a->dom || !a->params || !a->exp_avg || !a->exp_avg_sq) return MSIG_E_NULL;
+  if (a->S < 2 || a->S > MSIG_MAX_K || B < 1 || B > MSIG_DA_MAX_BATCH) return MSIG_E_SHAPE;
+  const bool multi = fc.stride != 0;
+  if (multi && a->idx && a->idx_row_stride < B) return MSIG_E_SHAPE;
+  da = DaArgs{};
+  for (int i = 0; i < fc.n; ++i) {
+    if (a->step[i] < 1) return MSIG_E_SHAPE;
+    if (!(a->lambda[i] >= 0.f) || !(a->lr[i] >= 0.f) || !(lam[i] >= 0.f && lam[i] <= 1.f)) return MSIG_E_SHAPE;      // NaN included
+    const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step[i]), bc2 = 1.0 - pow((double)a->beta2, (double)a->step[i]);
+    da.lambda[i] = a->lambda[i]; da.lam[i] = lam[i];
+    da.lr_over_bc1[i] = (float)((double)a->lr[i] / bc1);
+    da.inv_sqrt_bc2[i] = (float)(1.0 / sqrt(bc2));
+  }
+  if (((uintptr_t)a->params | (uintptr_t)a->exp_avg | (uintptr_t)a->exp_avg_sq) & 15) return MSIG_E_ALIGN;
+  if (((uintptr_t)a->stats | (uintptr_t)a->idx) & 7) return MSIG_E_ALIGN;
+  if ((uintptr_t)a->dom & 3) return MSIG_E_ALIGN;
+  if (multi && (a->stride_bytes <= 0 || (a->stride_bytes & 255))) return MSIG_E_ALIGN;
+  da.S = a->S; da.B = B;
+  da.dom = a->dom; da.idx = a->idx; da.idx_row_stride = multi ? a->idx_row_stride : 0;
+  da.params = a->params; da.exp_avg = a->exp_avg; da.exp_avg_sq = a->exp_avg_sq; da.stats = a->stats;
+  da.stride = multi ? a->stride_bytes : 0;
+  da.b1 = a->beta1; da.b2 = a->beta2; da.eps = a->eps; da.wd = a->weight_decay;
+  return 0;
+}
+static int da_step(const msig_da* a, const FoldCtx& fc, const float* feat, float* dfeat, int32_t B, const float* lam, hipStream_t st) {
+  if (!feat || !dfeat) return MSIG_E_NULL;
+  DaArgs da; int rc = make_da(a, fc, B, lam, da); if (rc) return rc;
+  if (((uintptr_t)feat | (uintptr_t)dfeat) & 15) return MSIG_E_ALIGN;
+  return launch_da_step(da, feat, dfeat, fc, st);
+}
+extern "C" int msig_da_step(const msig_da* a, const float* feat, float* dfeat, int32_t B, float lam, void* stream) {
+  return da_step(a, single_fold(nullptr), feat, dfeat, B, &lam, (hipStream_t)stream);
+}
+extern "C" int msig_da_step_multi(const msig_da* a, const msig_multi* m, const float* feat, float* dfeat, int32_t B, const float* lam,
+                                  void* stream) {
+  if (!a || !m) return MSIG_E_NULL;
+  FoldCtx fc; int rc = msig_multi_fold_ctx(m, fc); if (rc) return rc;
+  return da_step(a, fc, feat, dfeat, B, lam, (hipStream_t)stream);
+}
+extern "C" int msig_da_train_step(const msig_batch* b, const msig_st* s, const msig_da* a, float* exp_avg, float* exp_avg_sq, float lr,
+                                  float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, a);
+}
+extern "C" int msig_da_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* a, float* exp_avg,
+                                        float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                        void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, a);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

@@ -52,15 +52,6 @@ __device__ __forceinline__ uint32_t ft_dropout_key(uint64_t seed, uint64_t step)
   const uint32_t b = (uint32_t)((2ull * 0x7F4A7C15ull) & 0xFFFFFFFFull);
   return fmix32(lo ^ fmix32(a + b + hi));
 }
-// torch.optim.Adam with L2-in-gradient weight decay — the arithmetic of adam_kernel (head.hip), element by element
-__device__ __forceinline__ float ft_adam(float p, float g, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
-                                         float eps, float wd) {
-  const float gr = g + wd * p;
-  m = b1 * m + (1.f - b1) * gr;
-  v = b2 * v + (1.f - b2) * gr * gr;
-  const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-  return p - lr_over_bc1 * (m / denom);
-}
 
 template <bool CW>
 __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, const FtFolds ff) {

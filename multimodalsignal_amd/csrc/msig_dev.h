@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/msig.h"
 #include "../../include/msig_gc.h"
+#include "../../include/msig_da.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -366,6 +367,18 @@ int launch_head_bwd(const msig_batch* b, const float* dlogits, const StageDims& 
 bool head_step_applies(const msig_batch* b, const StageDims& d);
 int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
                      const float* cw = nullptr, const SoftArgs* soft = nullptr);
+// Subject discriminator (include/msig_da.h, adversary.hip): msig_da after its checks, by value to the launch.  Pointers are fold
+// slot 0's adversary buffers, `stride` bytes apart per slot; B rows; lam = the folds' mixup weights; Adam's bias corrections per
+// fold, formed on the host as train_step_fc forms the model's.  One launch, between the head's and launch_gru_bwd.
+struct DaArgs {
+  int32_t S, B;
+  const int32_t* dom; const int64_t* idx; int64_t idx_row_stride;
+  float *params, *exp_avg, *exp_avg_sq; double* stats;
+  int64_t stride;
+  float b1, b2, eps, wd;
+  float lambda[MSIG_MAX_FOLDS], lam[MSIG_MAX_FOLDS], lr_over_bc1[MSIG_MAX_FOLDS], inv_sqrt_bc2[MSIG_MAX_FOLDS];
+};
+int launch_da_step(const DaArgs& a, const float* feat, float* dfeat, const FoldCtx& fc, hipStream_t st);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch

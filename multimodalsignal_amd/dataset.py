@@ -93,6 +93,8 @@ class WesadDataset(Dataset):
             raise ValueError(f"No data loaded for subjects: {subjects}. Check paths and data existence.")
         self.data = np.concatenate(self.data_list, axis=0)
         self.labels = np.concatenate(self.labels_list, axis=0)
+        # per-window ordinal of the window's subject among the subjects loaded, in order (adversary.domain_table)
+        self.subject_ordinals = np.repeat(np.arange(len(self.labels_list), dtype=np.int32), [len(y) for y in self.labels_list])
         self._dev_cache = None
 
     def __len__(self):
@@ -226,6 +228,8 @@ class StoreView:
                 continue
             a, b = store.ranges[sid]
             idx.append(np.arange(a, b, dtype=np.int64))
+        # per-window ordinal of the window's subject among the subjects of this view, in order (adversary.domain_table)
+        self.subject_ordinals = np.repeat(np.arange(len(idx), dtype=np.int32), [len(i) for i in idx])
         if not idx:
             raise ValueError(f"No data loaded for subjects: {subjects}. Check paths and data existence.")
         self.store = store
@@ -254,7 +258,10 @@ class DeviceLoader:
 
     `mixup` (a ``mixup.Mixup``; training loaders only, composes with `augment`: the batch is augmented, then mixed): every batch is
     one ``msig_st_gather_windows`` launch that blends row b with row B-1-b, lam drawn from the same (`aug_seed`, `aug_step`) on a
-    stream of its own.  `last_lam` is the lam of the batch just served — the criterion needs it (Engine.train_step(mix_lambda=))."""
+    stream of its own.  `last_lam` is the lam of the batch just served — the criterion needs it (Engine.train_step(mix_lambda=)).
+
+    `last_index` is the int64 device tensor of the store positions of the batch just served (the gather's `idx`): subject-adversarial
+    training looks the rows' domains up by it (Engine.train_step(batch_index=))."""
 
     def __init__(self, dataset: WesadDataset, batch_size: int, shuffle: bool, device, seed: Optional[int] = None, augment=None,
                  mixup=None):
@@ -270,6 +277,7 @@ class DeviceLoader:
         if self.augment is not None:
             self.augment.check_window(int(self.store.shape[2]))
         self.mixup, self.last_lam = mixup, None
+        self.last_index = None
         if mixup is not None and (int(self.store.shape[2]) < 4 or int(self.store.shape[2]) % 4):
             raise ValueError(f"mixup: the window length must be a multiple of 4, got {int(self.store.shape[2])}")
 
@@ -290,7 +298,7 @@ class DeviceLoader:
         wfl = self.store.shape[1] * self.store.shape[2]
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         for i in range(0, n, self.batch_size):
-            idx = order[i:i + self.batch_size].contiguous()
+            idx = self.last_index = order[i:i + self.batch_size].contiguous()
             b = idx.numel()
             if b not in self._bufs:   # two alternating buffers per batch size: the previous batch may still be in flight
                 self._bufs[b] = [(torch.empty((b,) + tuple(self.store.shape[1:]), device=self.device),

@@ -30,6 +30,7 @@ import torch
 from . import _lib as L
 from .augment import Augment
 from .mixup import Mixup
+from . import adversary as adversary_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
@@ -98,7 +99,17 @@ def trainer_config(cfg, fold_idx):
         tc["trainer"]["max_grad_norm"] = grad_clip_setting(cfg["max_grad_norm"])
     if cfg.get("label_smoothing") is not None:      # CrossEntropyLoss(label_smoothing=) of every loss (include/msig_st.h); absent = hard labels
         tc["trainer"]["label_smoothing"] = label_smoothing_setting(cfg["label_smoothing"])
+    if cfg.get("adversary") is not None:            # a subject discriminator inside every training step (include/msig_da.h); absent = none
+        tc["adversary"] = adversary_mod.settings(cfg["adversary"])
     return tc
+
+
+def adversary_line(cfg):
+    """The SUBJECT ADVERSARY line of a summary, or None when the configuration has none."""
+    a = adversary_mod.settings(cfg.get("adversary"))
+    if a is None:
+        return None
+    return f"SUBJECT ADVERSARY: lambda={a['lam']:g} schedule={a['schedule']} gamma={a['gamma']:g} lr_mult={a['lr_mult']:g}\n"
 
 
 def soft_targets_line(cfg):
@@ -125,6 +136,8 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
     test_pass False: whoever trains the unit leaves the test subject to the caller.  skip_empty: None for a unit whose training
     or validation set is empty (main.py:187-189)."""
     train_subjects, val_subjects = split_train_val(cfg["subjects"], subject, cfg["seed"])
+    if cfg.get("adversary") is not None:            # before any data is loaded: the discriminator's step takes at most 256 rows
+        adversary_mod.check_batch_size(cfg["batch_size"])
     train_ds, val_ds = datasets(train_subjects), datasets(val_subjects)
     if skip_empty and (len(train_ds) == 0 or len(val_ds) == 0):
         return None
@@ -190,6 +203,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
         if soft_targets_line(cfg) is not None:                      # likewise
             f.write(soft_targets_line(cfg))
+        if adversary_line(cfg) is not None:                         # likewise
+            f.write(adversary_line(cfg))
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -444,6 +459,14 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
         print(f"交叉验证汇总结果已保存至: {path}")
         print(f"{(n + ': ') if n else ''}平均准确率 (Accuracy): {np.mean(accs):.4f} ± {np.std(accs):.4f}"
               f" | LOSO wall-clock {wall:.1f}s on {world} GPU(s) ({len(units)} folds in this job; load + normalise + upload {t_data:.1f}s)")
+        if cfgs[n].get("adversary") is not None:      # from the folds' fold_result.json, which every rank has written by now
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "fold_result.json" for r in results[n]]
+            folds = [adversary_mod.fold_record(json.loads(f.read_text())) for f in files if f.exists()]
+            folds = [f for f in folds if f is not None]
+            if folds:
+                path = adversary_mod.write_adversary(out_dir[n], folds, adversary_mod.settings(cfgs[n]["adversary"]),
+                                                     synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Subject-adversary table written to: {path}")
         if cal_all is not None:
             from .calibrate import write_calibration
             folds = [{"subject": cfgs[n]["subjects"][units[u][1]], "n_cal": int(cal_all[u][2][0]), "n_eval": int(cal_all[u][2][1]),
@@ -681,6 +704,12 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
         rows[k] = dict(subject=sid, m1_accuracy=m1_acc, m1_f1=m1_f1, ternary_accuracy=acc3, ternary_f1=f13, n=int(len(pred)),
                        correct=int((pred == np.asarray(tern.labels)).sum()))
         (Path(run_output_dir) / f"fold_test_on_{sid}" / "fold_result.json").write_text(json.dumps(rows[k]))
+        if cfg.get("adversary") is not None:      # each model's adversary record beside its logs; rank 0 tabulates them after the run
+            for tag, t in trainers.items():
+                rec = adversary_mod.fold_record(dict(subject=sid, history=t.history, adversary_domains=t.adversary.S,
+                                                     accuracy=m1_acc if tag == "m1" else None))
+                if rec is not None:                 # a model that trained no epoch has no record
+                    (Path(run_output_dir) / f"fold_test_on_{sid}" / f"model_{tag}" / "adversary_result.json").write_text(json.dumps(rec))
         local[k] = (m1_acc, acc3)
         print(f"[rank {rank}] fold {k} ({sid}): M1 acc {m1_acc:.4f} | three-class acc {acc3:.4f} f1 {f13:.4f}", flush=True)
 
@@ -726,6 +755,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
             if soft_targets_line(cfg) is not None:
                 f.write(soft_targets_line(cfg))
+            if adversary_line(cfg) is not None:
+                f.write(adversary_line(cfg))
             f.write("\n")
             for r in results:
                 f.write(f"  - 测试 {r['subject']}: M1 Accuracy = {r['m1_accuracy']:.4f}, 三分类 Accuracy = {r['ternary_accuracy']:.4f}\n")
@@ -734,6 +765,14 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(f"平均三分类准确率: {np.mean([r['ternary_accuracy'] for r in results]):.4f}\n")
             f.write(f"\nwall-clock: {wall:.1f} s on {world} GPU(s)\n")
         print(f"分层分类汇总结果已保存至: {path}")
+        if cfg.get("adversary") is not None:
+            for tag in ("m1", "m2"):
+                files = [Path(run_output_dir) / f"fold_test_on_{r['subject']}" / f"model_{tag}" / "adversary_result.json" for r in results]
+                folds = [json.loads(f.read_text()) for f in files if f.exists()]
+                if folds:
+                    path = adversary_mod.write_adversary(run_output_dir, folds, adversary_mod.settings(cfg["adversary"]),
+                                                         synthetic=bool(cfg.get("synthetic")), stem=f"adversary_{tag}")
+                    print(f"Subject-adversary table written to: {path}")
     return results, wall
 
 
@@ -821,6 +860,14 @@ def parse_args(ap, argv=None):
             ap.error(f"--mixup: {e}")
         if args.synthetic is not None and (args.samples < 4 or args.samples % 4):
             ap.error(f"--mixup: the window length must be a multiple of 4, got {args.samples}")
+    if args.subject_adversarial is not None:
+        try:
+            args.subject_adversarial = adversary_mod.settings(dict(lam=args.subject_adversarial, schedule=args.adversary_schedule or "ganin",
+                                                                   lr_mult=1.0 if args.adversary_lr_mult is None else args.adversary_lr_mult))
+        except ValueError as e:
+            ap.error(f"--subject-adversarial: {e}")
+    elif args.adversary_schedule is not None or args.adversary_lr_mult is not None:
+        ap.error("--adversary-schedule / --adversary-lr-mult need --subject-adversarial")
     return args
 
 
@@ -874,6 +921,17 @@ def build_parser():
                     help="mixup of every training batch inside its gather launch: row b is blended with row B-1-b, lam ~ Beta(ALPHA, ALPHA) "
                          "per batch and fold, and the loss is taken against both labels (every mode; composes with --augment: augment, "
                          "then mix; validation, test and --calibrate never mix)")
+    ap.add_argument("--subject-adversarial", type=float, nargs="?", const=0.1, default=None, metavar="LAMBDA",
+                    help="subject-adversarial training (DANN): a subject discriminator on the 128-d feature, trained inside every training "
+                         "step, whose gradient is reversed into the extractor with weight LAMBDA (bare flag: 0.1; 0 = probe mode: the "
+                         "discriminator only measures how subject-identifiable the feature is and the model's bits are unchanged).  Every "
+                         "mode: LOSO, --ablation, --hierarchical, --model, sequential; batch sizes up to 256; writes adversary.txt / "
+                         "adversary.json")
+    ap.add_argument("--adversary-schedule", choices=list(adversary_mod.SCHEDULES), default=None,
+                    help="lambda over the training steps: ganin = LAMBDA * (2 / (1 + exp(-10 p)) - 1), p the fraction of the epoch budget "
+                         "done (default), or constant")
+    ap.add_argument("--adversary-lr-mult", type=float, default=None, metavar="X",
+                    help="the discriminator's learning rate as a multiple of the model's (default 1)")
     ap.add_argument("--model", nargs="+", choices=list(MODEL_PARAMS), default=[MODEL_TO_USE],
                     help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
                          "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
@@ -932,6 +990,9 @@ def build_cfg(args, kinds):
         cfg["label_smoothing"] = args.label_smoothing
     if args.mixup is not None:              # likewise
         cfg["mixup"] = args.mixup
+    if args.subject_adversarial is not None:      # likewise; refused here, before any data or GPU work, for a batch size it cannot take
+        adversary_mod.check_batch_size(args.batch_size)
+        cfg.update(adversary=args.subject_adversarial, synthetic=args.synthetic is not None)
     if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
         cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
         for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import adversary as A
 from .runtime import FoldArena
 from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary, label_smoothing_setting
 
@@ -46,9 +47,18 @@ def fold_result(prep, trainer, accuracy, f1_score, seconds):
     pass of its own leaves it in fold_result.json as soon as it has finished (it survives a crash of another fold)."""
     info = dict(subject=prep["subject"], accuracy=accuracy, f1_score=f1_score, seconds=seconds, epochs=len(trainer.history),
                 train_windows_per_s=trainer.train_windows / max(trainer.train_seconds, 1e-9), history=trainer.history)
+    if getattr(trainer, "adversary", None) is not None:      # config['adversary']: what main.write_adversary tabulates
+        info["adversary_domains"] = trainer.adversary.S
     if prep.get("test_pass", True):
         (prep["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
     return info
+
+
+def _domains(prep):
+    """Domains of a fold's subject adversary — the subjects of its training set — or None when config['adversary'] is not set."""
+    if A.settings(prep["config"].get("adversary")) is None:
+        return None
+    return int(np.max(prep["loaders"][0].dataset.subject_ordinals)) + 1
 
 
 def lockstep_compatible(preps) -> bool:
@@ -66,7 +76,8 @@ def lockstep_compatible(preps) -> bool:
         if (_depth(p["model"]) != d0 or _kind(p["model"]) != k0
                 or tr.batch_size != tr0.batch_size or va.batch_size != va0.batch_size or tr.store.data_ptr() != tr0.store.data_ptr()
                 or p["model"].in_channels != preps[0]["model"].in_channels or p["model"].num_classes != preps[0]["model"].num_classes
-                or p["model"].dropout_p != preps[0]["model"].dropout_p):
+                or p["model"].dropout_p != preps[0]["model"].dropout_p
+                or _domains(p) != _domains(preps[0])):       # msig_da.S is one value per launch
             return False
     return True
 
@@ -107,8 +118,18 @@ class LockstepTrainer:
         # fold asks for it; a fold of such a batch that does not is run with max_norm = inf, which is the unclipped step bit for bit
         norms = [grad_clip_setting(p["config"]["trainer"].get("max_grad_norm")) for p in preps]
         self.clip = any(v is not None for v in norms)
+        # subject-adversarial training (config['adversary'], include/msig_da.h): every fold's discriminator lives in the arena set's
+        # adversary block; S is the launch's, so the folds of a batch have equally many training subjects
+        doms = [_domains(p) for p in preps]
+        if any(d != doms[0] for d in doms):
+            raise ValueError(f"lockstep folds must share one adversary setting and domain count, got {sorted(set(map(str, doms)))}")
+        self.adv_S = doms[0]
+        if self.adv_S is not None:
+            A.check_batch_size(tr0.batch_size)
+        self.dom_stats = {}
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
-                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip)
+                               adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip,
+                               adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])))
         if self.clip:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
@@ -137,6 +158,8 @@ class LockstepTrainer:
             model.engine()
             if self.embedded:
                 model._engine.scatter()                        # into the padded layout, once: the steps train it in place
+            if self.adv_S is not None:
+                t.prepare_adversary(p["loaders"][0], self.arena.adversary_storage(slot))
             self.trainers.append(t)
         # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
         # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
@@ -237,6 +260,11 @@ class LockstepTrainer:
         mix = self.mixup
         la = [mix.lams(ld.aug_seed, range(ld.aug_step + 1, ld.aug_step + 1 + ns)) for ld, ns in zip(loaders, n_steps)] if mix is not None else None
         soft = mix is not None or self.smoothing != 0.0
+        # subject adversaries: every fold's lambda of every step of the epoch from its own schedule and step count
+        advs = [t.adversary for t in trs] if self.adv_S is not None else None
+        if advs is not None:
+            arena.adversary_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
+            dl = [[a.lam_at(a.step + 1 + k, a.total_steps) for k in range(ns)] for a, ns in zip(advs, n_steps)]
         lam_arr = (C.c_float * L.MAX_FOLDS)() if mix is not None else None
         lrs = [t.optimizer.hyper["lr"] for t in trs]
         h0 = trs[0].optimizer.hyper
@@ -259,6 +287,20 @@ class LockstepTrainer:
                     lam_arr[j] = la[r0 + j][k]
             self._gather(loaders[0], order, r0, i, b, m, aug, lam_arr)
             _, desc = self._layout(b, True)
+            if advs is not None:           # msig_da_train_step_multi: msig_st_train_step_multi plus the discriminators' launch
+                if (r0, nr, "st") not in multis:
+                    multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw,
+                                                        arena.clip(act[r0:r0 + nr], self.cw) if self.clip else None)
+                    multis[(r0, nr, "da")] = arena.da(act[r0:r0 + nr], self.adv_S, [0.0] * nr, [lrs[r0 + j] * advs[r0 + j].lr_mult for j in range(nr)],
+                                                      [1] * nr, h0["betas"], eps, wd)
+                s, a = multis[(r0, nr, "st")], multis[(r0, nr, "da")]
+                a.idx, a.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+                for j in range(nr):
+                    s.lam[j] = lam_arr[j] if mix is not None else 1.0
+                    getattr(a, "lambda")[j], a.step[j] = dl[r0 + j][k], advs[r0 + j].step + 1 + k
+                L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a), ea, eas, b1, b2, eps, wd,
+                                                     int(steps[r0][k]), st), "msig_da_train_step_multi")
+                continue
             if soft:                       # msig_st_train_step_multi: either kind, with or without class weights and clip
                 if (r0, nr, "st") not in multis:
                     multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw,
@@ -282,6 +324,12 @@ class LockstepTrainer:
         if aug is not None or mix is not None:
             for ld, ns in zip(loaders, n_steps):
                 ld.aug_step += ns
+        if advs is not None:               # the epoch's statistics: one more small read-back, only with the adversary on
+            st3 = arena.adversary_stats().cpu().numpy()
+            for f, a, ns, lams in zip(act, advs, n_steps, dl):
+                a.step += ns
+                a.last_lambda = lams[-1] if lams else a.last_lambda
+                self.dom_stats[f] = a.epoch_summary(st3[f])
         if not self.clip:
             return self.acc[:, 0].cpu().numpy()               # the epoch's only sync
         # the same sync: the loss sums and the folds' gradient-norm statistics in one read-back
@@ -375,7 +423,7 @@ class LockstepTrainer:
                         t.model._engine.gather()   # once per epoch, for the checkpoint early stopping may write (best_model.pt)
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
-                    if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f)):
+                    if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f)):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start

@@ -307,7 +307,7 @@ class Engine:
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
                    dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
-                   label_smoothing=0.0, mix_lambda=None) -> None:
+                   label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
@@ -316,10 +316,22 @@ class Engine:
         optimizer.step() (msig_gc_train_step, DESIGN.md §15): `grads` then holds the clipped gradient and grad_stats() the norms;
         float('inf') measures without clipping; None = the calls above, unchanged.
         label_smoothing / mix_lambda: the soft-target criterion (msig_st_train_step; see forward()), with or without
-        class weights and clip; 0.0 and None (or 1) = the calls above, unchanged."""
+        class weights and clip; 0.0 and None (or 1) = the calls above, unchanged.
+        adversary: an adversary.SubjectAdversary bound to this device (msig_da_train_step): one more launch trains it
+        on the step's features and adds the reversed gradient of its loss, times its scheduled lambda, to the feature gradient; it
+        advances its own step count.  batch_index: the int64 store positions of the rows (DeviceLoader.last_index) by which the
+        adversary's domain table is read; None = the table has one entry per row.  The discriminator's Adam takes THIS call's betas,
+        eps and weight_decay (L2 decay included) and lr * adversary.lr_mult.  None = the calls above, unchanged."""
         cw = self._class_weight(class_weight)
         max_norm = None if max_grad_norm is None else L.check_max_grad_norm(max_grad_norm)
         smooth, lam = L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
+        if adversary is not None:
+            if x.shape[0] > L.DA_MAX_BATCH:
+                raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
+            if batch_index is not None:
+                _require_gpu(batch_index, "batch_index")
+                if batch_index.dtype != torch.int64 or not batch_index.is_contiguous() or batch_index.numel() != x.shape[0]:
+                    raise ValueError(f"batch_index must be a contiguous int64 ({x.shape[0]},) tensor, got {batch_index.dtype} {tuple(batch_index.shape)}")
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
         g = None
@@ -328,6 +340,16 @@ class Engine:
             g = L.GcClip()
             g.kind, g.class_weight, g.state, g.state_bytes = L.GC_KINDS[self.kind], cw, state.data_ptr(), state.numel() * 8
             g.max_norm[0] = max_norm
+        if adversary is not None:
+            adversary.last_lambda = adversary.next_lambda()
+            a = adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1],
+                                     idx=None if batch_index is None else batch_index.data_ptr(), betas=betas, eps=eps, weight_decay=weight_decay)
+            s = L.make_st(self.kind, smooth, cw, g, [lam])
+            L.check(L.lib().msig_da_train_step(C.byref(b), C.byref(s), C.byref(a), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
+                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_da_train_step")
+            adversary.step += 1
+            self._keep = self._keep + (batch_index,)
+            return
         if smooth != 0.0 or lam != 1.0:
             s = L.make_st(self.kind, smooth, cw, g, [lam])
             L.check(L.lib().msig_st_train_step(C.byref(b), C.byref(s), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
@@ -463,14 +485,16 @@ class EmbeddedEngine(Engine):
         return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight, label_smoothing, mix_lambda)
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
-                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None):
+                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None):
         self._class_weight(class_weight)
         if max_grad_norm is not None:
             L.check_max_grad_norm(max_grad_norm)
         L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
+        if adversary is not None:
+            adversary.restrict_features(self.hidden)       # nothing may reach the padded feature columns (their units must stay zero)
         self.scatter()
         super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm, label_smoothing,
-                           mix_lambda)
+                           mix_lambda, adversary, batch_index)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -498,13 +522,16 @@ class FoldArena:
 
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
                  adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
-                 grad_clip: bool = False):
+                 grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
         `kind`: the model kind of every fold (Engine); it sizes the arenas from its layout.  A fold batch is uniform in kind too.
         `grad_clip`: the arenas also hold a "gc" region, each fold's clip state (include/msig_gc.h), after every other region —
-        without it the arenas and their stride are what they are without this argument."""
+        without it the arenas and their stride are what they are without this argument.
+        `adversary` = (S, store positions): every fold also gets the buffers of a subject discriminator of S domains (include/
+        msig_da.h) — parameters, both Adam moments, statistics and an int32 domain table — in a memory block of their own,
+        `da_stride` bytes apart (`adversary_storage`); the model arenas and their stride stay what they are without it."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -533,6 +560,14 @@ class FoldArena:
             at += (nbytes + 255) // 256 * 256
         self.stride = at
         self.mem = torch.zeros((n, self.stride), dtype=torch.uint8, device=self.device)
+        self.da_off, self.da_stride, self.da_mem = {}, 0, None
+        if adversary is not None:
+            S, positions = int(adversary[0]), int(adversary[1])
+            nf = L.da_param_floats(S)
+            for name, nbytes in (("params", nf * 4), ("exp_avg", nf * 4), ("exp_avg_sq", nf * 4), ("stats", 24), ("dom", positions * 4)):
+                self.da_off[name] = (self.da_stride, nbytes)
+                self.da_stride += (nbytes + 255) // 256 * 256
+            self.da_mem = torch.zeros((n, self.da_stride), dtype=torch.uint8, device=self.device)
 
     @staticmethod
     def workspace_bytes(train_batch: int, eval_batch: int, in_channels: int, T: int, num_classes: int) -> int:
@@ -571,6 +606,32 @@ class FoldArena:
 
     def ptr(self, name: str) -> int:
         return self.mem.data_ptr() + self.off[name][0]                  # arena 0's buffer
+
+    def adversary_storage(self, slot: int) -> dict:
+        """The adversary buffers of the fold in arena `slot` (adversary.SubjectAdversary.bind): typed views of its `da_mem` row."""
+        if self.da_mem is None:
+            raise RuntimeError("this FoldArena was built without adversary=(S, positions): it has no adversary buffers")
+        dt = {"stats": torch.float64, "dom": torch.int32}
+        return {name: self.da_mem[slot, o:o + nb].view(dt.get(name, torch.float32)) for name, (o, nb) in self.da_off.items()}
+
+    def da_ptr(self, name: str) -> int:
+        return self.da_mem.data_ptr() + self.da_off[name][0]            # fold slot 0's adversary buffer
+
+    def da(self, slots, S: int, lambdas, lrs, steps, betas, eps, weight_decay) -> L.Da:
+        """msig_da of a launch over `slots` (msig_da_train_step_multi): fold slot 0's adversary buffers, `da_stride` apart, and every
+        fold's reversal weight, learning rate and step count.  idx / idx_row_stride are the launch's to fill in."""
+        a = L.Da()
+        a.S, a.weight_decay, a.beta1, a.beta2, a.eps = int(S), weight_decay, betas[0], betas[1], eps
+        a.dom, a.params, a.exp_avg, a.exp_avg_sq = self.da_ptr("dom"), self.da_ptr("params"), self.da_ptr("exp_avg"), self.da_ptr("exp_avg_sq")
+        a.stats, a.stride_bytes = self.da_ptr("stats"), self.da_stride
+        for i in range(len(slots)):
+            getattr(a, "lambda")[i], a.lr[i], a.step[i] = float(lambdas[i]), float(lrs[i]), int(steps[i])
+        return a
+
+    def adversary_stats(self) -> torch.Tensor:
+        """(n, 3) float64 strided view of every fold's adversary statistics."""
+        o = self.da_off["stats"][0] // 8
+        return self.da_mem.view(torch.float64)[:, o:o + 3]
 
     def set_class_weight(self, slot: int, values) -> None:
         """Writes the class-weight vector of the fold in arena `slot` (K values, checked on the host: ValueError before anything is

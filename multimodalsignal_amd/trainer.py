@@ -22,6 +22,9 @@ own, ``config['trainer']['class_weights']`` (include/msig_cw.h).
 (include/msig_gc.h) and adds the epoch's gradient norms to ``history`` and the log.
 ``config['trainer']['label_smoothing']`` is ``CrossEntropyLoss(label_smoothing=...)`` of the training, validation and test
 losses alike (include/msig_st.h); a training loader built with ``mixup=`` has its batches' lam passed on to the step.
+``config['adversary']`` (None or a dict of lam / schedule / gamma / lr_mult / seed) trains a subject discriminator on the feature
+inside every TRAINING step and reverses its gradient into the extractor (include/msig_da.h); validation and test
+never run it; ``history`` and the log gain the epoch's domain loss, domain accuracy and lambda.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ import torch
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from . import _lib as L
+from . import adversary as A
 from .models import CnnGruAttentionModel
 
 
@@ -181,6 +185,9 @@ class Trainer:
         self.max_grad_norm = grad_clip_setting(cfg.get("max_grad_norm"))
         # CrossEntropyLoss(label_smoothing=eps) of every loss this trainer takes (include/msig_st.h); None / 0: the hard-label calls
         self.label_smoothing = label_smoothing_setting(cfg.get("label_smoothing")) or 0.0
+        # subject-adversarial training (include/msig_da.h): the settings now, the discriminator when the training set is known
+        self.adversary_cfg = A.settings(config.get("adversary"))
+        self.adversary = None
         self.verbose = cfg.get("verbose", True)
         self.optimizer = MsigAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)   # trainer.py:68
         self.scheduler = ReduceLROnPlateau(self.optimizer, mode="min", factor=0.1, patience=3)         # trainer.py:72-77
@@ -236,12 +243,36 @@ class Trainer:
             self._log(f"已启用类别加权损失，权重为: {np.asarray(w, dtype=np.float32)}")
         return self.class_weight.cpu().numpy()
 
+    def prepare_adversary(self, train_loader, storage=None):
+        """Builds the fold's subject discriminator once, when config['adversary'] is set: one domain per subject of the training
+        set, its domain table over the store the loader gathers from, its schedule over the configured epoch budget.  Its seed is
+        the setting's, else the model's dropout seed (per fold).  Its Adam shares the model's betas, eps and weight decay; its learning
+        rate is the model's (schedule included) times lr_mult.  storage: one fold's adversary buffers of a FoldArena.  ValueError
+        before any training for a batch size the discriminator's step cannot take."""
+        if self.adversary_cfg is None or self.adversary is not None:
+            return self.adversary
+        A.check_batch_size(train_loader.batch_size)
+        ds = train_loader.dataset
+        if getattr(ds, "subject_ordinals", None) is None:
+            raise ValueError("config['adversary'] needs a training dataset with per-window `subject_ordinals`")
+        c = self.adversary_cfg
+        seed = c["seed"] if c["seed"] is not None else getattr(self.model, "_seed", 0)
+        adv = A.SubjectAdversary(int(np.max(ds.subject_ordinals)) + 1, c["lam"], c["schedule"], c["gamma"], c["lr_mult"], seed)
+        adv.total_steps = self.epochs * len(train_loader)
+        adv.set_domains(A.domain_table(ds))
+        if int(getattr(self.model, "gru_num_layers", 2)) == 1:      # the embedded one-layer model: D leaves the padded feature columns alone
+            adv.restrict_features(int(self.model.gru_hidden_size))
+        self.adversary = adv.bind(self.device, storage)
+        self._log(f"subject adversary: {adv.S} domains, lambda {adv.lam:g} ({adv.schedule}), lr x {adv.lr_mult:g}")
+        return adv
+
     # ---- trainer.py:119-191 -------------------------------------------------------------------
     def train(self, train_loader, val_loader):
         eng = self.model.engine()
         self._check_labels(train_loader)
         self._check_labels(val_loader)
         self.prepare_class_weights(train_loader)
+        adv = self.prepare_adversary(train_loader)
         n_train = len(train_loader.dataset)
         for epoch in range(self.epochs):
             t0 = time.time()
@@ -249,6 +280,8 @@ class Trainer:
             eng.loss_acc.zero_()
             if self.max_grad_norm is not None:
                 eng.zero_grad_stats()
+            if adv is not None:
+                adv.stats.zero_()
             n_steps = 0
             for inputs, labels in train_loader:
                 n_steps += 1
@@ -258,24 +291,27 @@ class Trainer:
                 eng.train_step(x, y, lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
                                step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
                                class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
-                               mix_lambda=getattr(train_loader, "last_lam", None))      # the lam of the batch a mixup loader just served
+                               mix_lambda=getattr(train_loader, "last_lam", None),      # the lam of the batch a mixup loader just served
+                               adversary=adv, batch_index=getattr(train_loader, "last_index", None) if adv is not None else None)
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
             if self.max_grad_norm is None:
                 train_loss, grad = float(eng.loss_acc[0].item()) / n_train, None         # the epoch's only sync
             else:                                                                        # the same sync: one read-back for both
                 acc, stats = eng.loss_and_grad_stats()
                 train_loss, grad = acc[0] / n_train, grad_norm_summary(stats, n_steps)
+            dom = adv.epoch_summary(adv.stats.cpu().tolist()) if adv is not None else None
             dt = time.time() - t0
             self.train_windows += n_train
             self.train_seconds += dt
             val_loss, val_acc, val_f1, _, _ = self.evaluate(val_loader, is_val=True)
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad):
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom):
                 break
         self._finish_training()
 
-    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None) -> bool:
+    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None) -> bool:
         """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
-        the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were."""
+        the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were.
+        dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
@@ -284,6 +320,9 @@ class Trainer:
             self.history[-1].update(grad)
             suffix = (f" | 梯度范数: {grad['grad_norm_mean']:.4f} (max {grad['grad_norm_max']:.4f}) | "
                       f"裁剪步数: {grad['clipped_steps']} (max_grad_norm={self.max_grad_norm:g})")
+        if dom is not None:
+            self.history[-1].update(dom)
+            suffix += f" | domain loss: {dom['domain_loss']:.4f} | domain acc: {dom['domain_acc']:.4f} | lambda: {dom['adversary_lambda']:.4f}"
         self._log(f"Epoch {epoch + 1}/{self.epochs} | 耗时: {dt:.2f}s | 训练损失: {train_loss:.4f} | 验证损失: {val_loss:.4f} | "
                   f"验证Acc: {val_acc:.4f} | 验证F1: {val_f1:.4f} | {n_train / max(dt, 1e-9):.0f} windows/s" + suffix)
         if self.early_stopping:
