@@ -163,16 +163,13 @@ class BnAdapter:
 
     def _predict(self, eng, bn_state: torch.Tensor, x, y):
         """Predictions of an eval-mode forward of the model with `bn_state` (its own or the adapted copy) as running statistics."""
-        lib, out = L.lib(), []
+        out = []
         for i in range(0, x.shape[0], self.eval_batch):
             xb = x[i:i + self.eval_batch]
             b = eng._batch(xb, None, False, 0.0, 0, 0)
             b.bn_state = bn_state.data_ptr()
             b.loss_acc = None
-            if eng.kind == "cnn_gru":
-                L.check(lib.msig_cg_forward(C.byref(b), None, eng._stream()), "msig_cg_forward")
-            else:
-                L.check(lib.msig_forward(C.byref(b), eng._stream()), "msig_forward")
+            eng.forward_desc(b)
             out.append(eng.region("PRED", torch.int32, (xb.shape[0],)).clone())
         return torch.cat(out).cpu().numpy().astype(np.int64)
 

@@ -129,16 +129,13 @@ class HeadCalibrator:
     def _predict(self, eng, flat, x, y):
         """Predictions of an eval-mode forward with the parameters in `flat` (the engine's own buffer or the tuned copy) — the
         extractor's tensors are the same bits in both."""
-        lib, out = L.lib(), []
+        out = []
         for i in range(0, x.shape[0], self.eval_batch):
             xb, yb = x[i:i + self.eval_batch], y[i:i + self.eval_batch]
             b = eng._batch(xb, yb, False, 0.0, 0, 0)
             b.params = flat.data_ptr()
             b.loss_acc = None
-            if eng.kind == "cnn_gru":
-                L.check(lib.msig_cg_forward(C.byref(b), None, eng._stream()), "msig_cg_forward")
-            else:
-                L.check(lib.msig_forward(C.byref(b), eng._stream()), "msig_forward")
+            eng.forward_desc(b)
             out.append(eng.region("PRED", torch.int32, (xb.shape[0],)).clone())
         return torch.cat(out).cpu().numpy().astype(np.int64)
 

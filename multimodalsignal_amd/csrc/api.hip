@@ -236,7 +236,7 @@ extern "C" int msig_gru_fwd(const msig_batch* b, void* stream) {
 }
 extern "C" int msig_head_ce_fwd(const msig_batch* b, void* stream) {
   Ctx c; int rc = make_ctx(b, c, false); if (rc) return rc;
-  return launch_head_fwd(b, c.d, c.w, c.po, single_fold(b), (hipStream_t)stream);
+  return launch_head_fwd(b, c.d, c.w, c.po, single_fold(b), (hipStream_t)stream, StepOpts{});
 }
 extern "C" int msig_head_ce_bwd(const msig_batch* b, const float* dlogits, void* stream) {
   Ctx c; int rc = make_ctx(b, c, true); if (rc) return rc;
@@ -260,23 +260,24 @@ extern "C" int msig_frontend_bwd(const msig_batch* b, void* stream) {
   return launch_colsum_plan(plan, single_fold(b), (hipStream_t)stream);
 }
 
-// cw: class weights of include/msig_cw.h (NULL = the msig.h call); cg: CnnGruModel (include/msig_cg.h)
-// soft: soft targets of include/msig_st.h (NULL = the plain criterion's kernels)
-static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, bool with_head = true, const float* cw = nullptr,
-                      bool cg = false, const SoftArgs* soft = nullptr) {
+// Every msig_*_forward[_multi] ends here and every msig_*_train_step[_multi] in train_step_fc: an entry point checks its own
+// arguments in its header's order, fills a StepOpts (msig_dev.h; StepOpts{} = the msig.h call) and calls.  Reads o.cw, o.cg, o.soft.
+static int forward_fc(const msig_batch* b, const FoldCtx& fc, hipStream_t st, const StepOpts& o, bool with_head = true) {
+  if (!b) return MSIG_E_NULL;
   if (b->dx && fc.stride != 0) return MSIG_E_SHAPE;          // no input gradients in fold batches
-  Ctx c; int rc = make_ctx(b, c, false, cg); if (rc) return rc;
+  Ctx c; int rc = make_ctx(b, c, false, o.cg); if (rc) return rc;
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;      // nothing has been launched: no model state has changed
-  if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st, !cg))) return rc;
+  if ((rc = launch_frontend_fwd(b, c.d, c.w, c.po, fc, st, !o.cg))) return rc;
   if ((rc = launch_gru_fwd(b, c.d, c.w, c.po, fc, st))) return rc;
-  return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st, cw, soft) : 0;
+  return with_head ? launch_head_fwd(b, c.d, c.w, c.po, fc, st, o) : 0;
 }
 extern "C" int msig_forward(const msig_batch* b, void* stream) {
-  if (!b) return MSIG_E_NULL;
-  return forward_fc(b, single_fold(b), (hipStream_t)stream);
+  return forward_fc(b, single_fold(b), (hipStream_t)stream, StepOpts{});
 }
 
-static int backward_fc(const msig_batch* b, const float* dlogits, hipStream_t st, bool cg) {
+// reads o.cg
+static int backward_fc(const msig_batch* b, const float* dlogits, hipStream_t st, const StepOpts& o) {
+  const bool cg = o.cg;
   Ctx c; int rc = make_ctx(b, c, true, cg); if (rc) return rc;
   if (!msig_keeps(b)) return MSIG_E_SHAPE;
   const FoldCtx fc = single_fold(b);
@@ -287,7 +288,7 @@ static int backward_fc(const msig_batch* b, const float* dlogits, hipStream_t st
   return launch_colsum_plan(plan, fc, st);
 }
 extern "C" int msig_backward(const msig_batch* b, const float* dlogits, void* stream) {
-  return backward_fc(b, dlogits, (hipStream_t)stream, false);
+  return backward_fc(b, dlogits, (hipStream_t)stream, StepOpts{});
 }
 
 extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -298,10 +299,10 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
   return launch_adam(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
 }
 
-// fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch)
+// fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch).  Reads every field of o.
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
-                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const float* cw = nullptr, bool cg = false,
-                         const ClipArgs* clip = nullptr, const SoftArgs* soft = nullptr, const DaArgs* da = nullptr) {
+                         float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const StepOpts& o) {
+  const bool cg = o.cg;
   if (!b || !b->labels) return MSIG_E_NULL;
   if (!b->training) return MSIG_E_SHAPE;
   if (b->dx) return MSIG_E_SHAPE;                     // no input gradient in the fused step (ABI 5: msig_backward / msig_frontend_bwd only)
@@ -317,13 +318,13 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
   const bool head_step = head_step_applies(b, c.d);
-  if ((rc = forward_fc(b, fc, st, !head_step, cw, cg, soft))) return rc;
+  if ((rc = forward_fc(b, fc, st, o, !head_step))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
-  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, cw, soft) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
+  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, o) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
   // subject discriminator (include/msig_da.h): WS_FEAT and WS_DFEAT are complete here; its launch adds the reversed gradient to WS_DFEAT
-  if (da && (rc = launch_da_step(*da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
+  if (o.da && (rc = launch_da_step(*o.da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
@@ -339,13 +340,12 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   }
   const AdamArgs ad{(float*)b->params, b->grads, exp_avg, exp_avg_sq, fc.lr_over_bc1[0], fc.inv_sqrt_bc2[0], beta1, beta2, eps, weight_decay};
   // clip: the norm of the whole gradient has to be known between the reduction and the update — two launches (include/msig_gc.h)
-  return clip ? launch_colsum_clip_adam_plan(plan, ad, fc, *clip, st) : launch_colsum_adam_plan(plan, ad, fc, st);
+  return o.clip ? launch_colsum_clip_adam_plan(plan, ad, fc, *o.clip, st) : launch_colsum_adam_plan(plan, ad, fc, st);
 }
 
 extern "C" int msig_train_step(const msig_batch* b, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                                float eps, float weight_decay, int64_t step, void* stream) {
-  if (!b) return MSIG_E_NULL;
-  return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+  return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, StepOpts{});
 }
 
 // ---- fold batching -------------------------------------------------------------------------------------------------
@@ -370,12 +370,12 @@ int msig_multi_fold_ctx(const msig_multi* m, FoldCtx& fc) {
 }
 extern "C" int msig_forward_multi(const msig_batch* b, const msig_multi* m, void* stream) {
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return forward_fc(b, fc, (hipStream_t)stream);
+  return forward_fc(b, fc, (hipStream_t)stream, StepOpts{});
 }
 extern "C" int msig_train_step_multi(const msig_batch* b, const msig_multi* m, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
                                      float eps, float weight_decay, int64_t step, void* stream) {
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, StepOpts{});
 }
 
 // ---- class-weighted CrossEntropy (include/msig_cw.h): the same calls with the weight vector passed down to the loss kernels ----
@@ -384,26 +384,24 @@ static inline bool cw_misaligned(const float* cw) { return ((uintptr_t)cw & 3) !
 
 extern "C" int msig_cw_forward(const msig_batch* b, const float* class_weight, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
-  if (!b) return MSIG_E_NULL;
-  return forward_fc(b, single_fold(b), (hipStream_t)stream, true, class_weight);
+  return forward_fc(b, single_fold(b), (hipStream_t)stream, StepOpts{class_weight});
 }
 extern "C" int msig_cw_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
-  if (!b) return MSIG_E_NULL;
   return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
-                       class_weight);
+                       StepOpts{class_weight});
 }
 extern "C" int msig_cw_forward_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return forward_fc(b, fc, (hipStream_t)stream, true, class_weight);
+  return forward_fc(b, fc, (hipStream_t)stream, StepOpts{class_weight});
 }
 extern "C" int msig_cw_train_step_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight);
+  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, StepOpts{class_weight});
 }
 
 // ---- CnnGruModel, the baseline without ChannelAttention (include/msig_cg.h): the same steps on the gate-free front end ----------
@@ -412,30 +410,28 @@ extern "C" int msig_cg_param_layout(int C, int K, int64_t* off) { return param_l
 
 extern "C" int msig_cg_forward(const msig_batch* b, const float* class_weight, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
-  if (!b) return MSIG_E_NULL;
-  return forward_fc(b, single_fold(b), (hipStream_t)stream, true, class_weight, true);
+  return forward_fc(b, single_fold(b), (hipStream_t)stream, StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_backward(const msig_batch* b, const float* dlogits, void* stream) {
-  return backward_fc(b, dlogits, (hipStream_t)stream, true);
+  return backward_fc(b, dlogits, (hipStream_t)stream, StepOpts{nullptr, true});
 }
 extern "C" int msig_cg_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
-  if (!b) return MSIG_E_NULL;
   return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
-                       class_weight, true);
+                       StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_forward_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return forward_fc(b, fc, (hipStream_t)stream, true, class_weight, true);
+  return forward_fc(b, fc, (hipStream_t)stream, StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_train_step_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, class_weight,
-                       true);
+  return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
+                       StepOpts{class_weight, true});
 }
 
 // ---- gradient-norm clipping (include/msig_gc.h): the train steps with the clip between the reduction and the Adam update ---------
@@ -477,14 +473,14 @@ extern "C" int msig_gc_train_step(const msig_batch* b, const msig_gc_clip* g, fl
                                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   ClipArgs cl; int rc = make_clip(b, g, 1, cl); if (rc) return rc;
   return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
-                       g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl);
+                       StepOpts{g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl});
 }
 extern "C" int msig_gc_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_gc_clip* g, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   ClipArgs cl; if ((rc = make_clip(b, g, fc.n, cl))) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
-                       g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl);
+                       StepOpts{g->class_weight, g->kind == MSIG_GC_KIND_CNN_GRU, &cl});
 }
 
 // ---- soft targets (include/msig_st.h): label smoothing and mixup in the criterion of the same calls ------------------------------
@@ -511,14 +507,12 @@ static int make_soft(const msig_st* s, int n, SoftArgs& soft, bool& use) {
 }
 static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, hipStream_t st) {
   SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
-  if (!b) return MSIG_E_NULL;
-  return forward_fc(b, fc, st, true, s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, use ? &soft : nullptr);
+  return forward_fc(b, fc, st, StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, nullptr, use ? &soft : nullptr});
 }
 static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* lam, DaArgs& da);
 // a: the subject discriminator of include/msig_da.h (NULL = msig_st_train_step[_multi] itself)
 static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
-                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st,
-                         const msig_da* a = nullptr) {
+                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a) {
   SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
   if (!b) return MSIG_E_NULL;
   DaArgs da;
@@ -528,8 +522,8 @@ static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* 
     if (s->clip->kind != s->kind) return MSIG_E_SHAPE;
     if ((rc = make_clip(b, s->clip, fc.n, cl))) return rc;
   }
-  return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st, s->class_weight,
-                       s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr);
+  return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st,
+                       StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr});
 }
 extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
   return st_forward(b, single_fold(b), s, (hipStream_t)stream);
@@ -541,13 +535,13 @@ extern "C" int msig_st_forward_multi(const msig_batch* b, const msig_multi* m, c
 }
 extern "C" int msig_st_train_step(const msig_batch* b, const msig_st* s, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                                   float eps, float weight_decay, int64_t step, void* stream) {
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr);
 }
 extern "C" int msig_st_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   if (!s) return MSIG_E_NULL;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr);
 }
 
 // ---- subject-adversarial training (include/msig_da.h; kernel: adversary.hip) ---------------------------------------------------------
@@ -625,7 +619,7 @@ static int features_fc(const msig_batch* b, const FoldCtx& fc, int kind, float* 
   if ((uintptr_t)out & 15) return MSIG_E_ALIGN;
   if (fc.n > 1 && (out_stride_bytes < (int64_t)b->shape.B * 512 || (out_stride_bytes & 15))) return MSIG_E_SHAPE;
   const bool cg = kind == MSIG_FT_KIND_CNN_GRU;
-  int rc = forward_fc(b, fc, st, false, nullptr, cg);         // every argument check of the forward before its first launch
+  int rc = forward_fc(b, fc, st, StepOpts{nullptr, cg}, false);         // every argument check of the forward before its first launch
   if (rc) return rc;
   Ctx c;
   if ((rc = make_ctx(b, c, false, cg))) return rc;
@@ -751,7 +745,7 @@ extern "C" int msig_mc_tail(const msig_batch* b, int32_t kind, void* stream) {
   Ctx c; if ((rc = make_ctx(&t, c, false, cg))) return rc;
   if ((rc = msig_check_call_forms(&t, c.d.NT, fc))) return rc;
   if ((rc = launch_gru_fwd(&t, c.d, c.w, c.po, fc, st, GRU_PART_L1, true))) return rc;
-  return launch_head_fwd(&t, c.d, c.w, c.po, fc, st, nullptr, nullptr, true);
+  return launch_head_fwd(&t, c.d, c.w, c.po, fc, st, StepOpts{}, true);
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {

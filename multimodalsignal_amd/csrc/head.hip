@@ -959,7 +959,9 @@ int launch_normalise(const double* raw, int64_t N, int T, int C_all, const int* 
 // Host launchers
 // ------------------------------------------------------------------------------------
 int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                    const float* cw, const SoftArgs* soft, bool mc_tail) {
+                    const StepOpts& o, bool mc_tail) {
+  const float* cw = o.cw;
+  const SoftArgs* soft = o.soft;
   const float* P = b->params;
   const int thr = (b->training || mc_tail) ? b->dropout_thr : 0;
   const int ngroups = (d.B + HEAD_ROWS - 1) / HEAD_ROWS;
@@ -1016,7 +1018,9 @@ bool head_step_applies(const msig_batch* b, const StageDims& d) {
   return b->training && b->labels && (d.B + HEAD_ROWS - 1) / HEAD_ROWS <= HEAD_WG;
 }
 int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
-                     const float* cw, const SoftArgs* soft) {
+                     const StepOpts& o) {
+  const float* cw = o.cw;
+  const SoftArgs* soft = o.soft;
   const float* P = b->params;
   float* G = b->grads;
   const int thr = b->dropout_thr;

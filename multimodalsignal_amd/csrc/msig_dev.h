@@ -356,17 +356,28 @@ int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
 // Soft targets (include/msig_st.h): the launch's label smoothing and every fold's mixup weight; NULL wherever it is
 // taken = the plain criterion's kernels.
 struct SoftArgs { float eps; float lam[MSIG_MAX_FOLDS]; };
-// cw: class weights (include/msig_cw.h), K device floats of fold slot 0 (shifted per fold like every buffer); NULL = unweighted
-// mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of b->dropout_thr
-// although b->training = 0
+struct ClipArgs;
+struct DaArgs;
+// What a forward or a train step does beyond the msig.h call (host side only; api.hip's entry points fill it after their own checks).
+// Value-initialised = the plain call.  Each function that takes it reads only the fields named at its declaration.
+struct StepOpts {
+  const float* cw;          // class weights (include/msig_cw.h): K device floats of fold slot 0, shifted per fold like every buffer
+  bool cg;                  // CnnGruModel (include/msig_cg.h): no gate, and a parameter layout without the gate tensors
+  const ClipArgs* clip;     // gradient-norm clipping (include/msig_gc.h) between the reduction and the Adam update
+  const SoftArgs* soft;     // soft targets (include/msig_st.h); NULL = the plain criterion's kernels
+  const DaArgs* da;         // subject discriminator (include/msig_da.h): one more launch after the head's
+};
+// reads o.cw, o.soft.  mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of
+// b->dropout_thr although b->training = 0
 int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
-                    const float* cw = nullptr, const SoftArgs* soft = nullptr, bool mc_tail = false);
+                    const StepOpts& o, bool mc_tail = false);
 int launch_head_bwd(const msig_batch* b, const float* dlogits, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan,
                     const FoldCtx& fc, hipStream_t st);
 // head forward + CrossEntropy + head backward of a fused train step in one launch (few windows: see head.hip); false = not applicable
 bool head_step_applies(const msig_batch* b, const StageDims& d);
+// reads o.cw, o.soft
 int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, ColsumPlan& plan, const FoldCtx& fc, hipStream_t st,
-                     const float* cw = nullptr, const SoftArgs* soft = nullptr);
+                     const StepOpts& o);
 // Subject discriminator (include/msig_da.h, adversary.hip): msig_da after its checks, by value to the launch.  Pointers are fold
 // slot 0's adversary buffers, `stride` bytes apart per slot; B rows; lam = the folds' mixup weights; Adam's bias corrections per
 // fold, formed on the host as train_step_fc forms the model's.  One launch, between the head's and launch_gru_bwd.

@@ -252,7 +252,7 @@ class DeviceLoader:
     """Iterates (x, y) device batches of a WesadDataset without touching the host per step.
     Same iteration contract as ``DataLoader(ds, batch_size, shuffle)`` (no drop_last).
 
-    `augment` (an ``augment.Augment``; training loaders only): every batch is one ``msig_aug_gather_windows`` launch instead, keyed
+    `augment` (an ``augment.Augment``; training loaders only): every batch is one augmenting gather launch instead, keyed
     by (`aug_seed` = the loader's seed, `aug_step` = the batches this loader has served so far, counted from 1) — the same windows
     are augmented differently in every epoch, and two loaders with one seed serve the same batches.  None: the plain gather.
 
@@ -304,24 +304,19 @@ class DeviceLoader:
                 self._bufs[b] = [(torch.empty((b,) + tuple(self.store.shape[1:]), device=self.device),
                                   torch.empty(b, dtype=torch.int64, device=self.device)) for _ in range(2)]
             ox, oy = self._bufs[b][(i // self.batch_size) & 1]
+            if self.mixup is None and self.augment is None:      # the plain gather: it takes any window length
+                L.check(L.lib().msig_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, wfl,
+                                                    ox.data_ptr(), oy.data_ptr(), st), "msig_gather_windows")
+                yield ox, oy
+                continue
+            # augmented, mixed or both: one call (include/msig_st.h) — a NULL msig_aug is none, lam 1 the augmented gather itself
+            self.aug_step += 1
+            lam = 1.0
             if self.mixup is not None:
-                self.aug_step += 1
-                self.last_lam = self.mixup.lam(self.aug_seed, self.aug_step)
-                a = (C.byref(self.augment.struct([L.dropout_key(self.aug_seed, self.aug_step, L.AUG_STREAM_ID)]))
-                     if self.augment is not None else None)
-                L.check(L.lib().msig_st_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, self.store.shape[1],
-                                                       self.store.shape[2], ox.data_ptr(), oy.data_ptr(), a, (C.c_float * 1)(self.last_lam), st),
-                        "msig_st_gather_windows")
-                yield ox, oy
-                continue
-            if self.augment is not None:
-                self.aug_step += 1
-                a = self.augment.struct([L.dropout_key(self.aug_seed, self.aug_step, L.AUG_STREAM_ID)])
-                L.check(L.lib().msig_aug_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, self.store.shape[1],
-                                                        self.store.shape[2], ox.data_ptr(), oy.data_ptr(), C.byref(a), st),
-                        "msig_aug_gather_windows")
-                yield ox, oy
-                continue
-            L.check(L.lib().msig_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, wfl,
-                                                ox.data_ptr(), oy.data_ptr(), st), "msig_gather_windows")
+                lam = self.last_lam = self.mixup.lam(self.aug_seed, self.aug_step)
+            a = (C.byref(self.augment.struct([L.dropout_key(self.aug_seed, self.aug_step, L.AUG_STREAM_ID)]))
+                 if self.augment is not None else None)
+            L.check(L.lib().msig_st_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, self.store.shape[1],
+                                                   self.store.shape[2], ox.data_ptr(), oy.data_ptr(), a, (C.c_float * 1)(lam), st),
+                    "msig_st_gather_windows")
             yield ox, oy

@@ -14,7 +14,8 @@ stand-alone run whatever its companions, the grouping or the rank count
 (tests/test_trainer_gpu.py::test_lockstep_folds_equal_sequential, ::test_fold_results_do_not_depend_on_sharding); with
 `adaptive_forms` the backward form follows the folds still active in a launch (a fold's last bits then depend, reproducibly, on
 when its companions stop).  Folds may differ in train / val set size; folds that
-stop early leave the batch.
+stop early leave the batch.  Every train launch is msig_da_train_step_multi and every evaluation launch msig_st_forward_multi,
+whatever the folds have switched on: runtime's module docstring says why that is bit-safe.
 """
 from __future__ import annotations
 
@@ -61,12 +62,19 @@ def _domains(prep):
     return int(np.max(prep["loaders"][0].dataset.subject_ordinals)) + 1
 
 
+def _shared(values, what, show=None):
+    """The one value a launch-wide setting has in every fold of a batch, else ValueError naming the values found."""
+    if any(v != values[0] for v in values):
+        raise ValueError(f"lockstep folds must share one {what}, got {sorted(set(values) if show is None else {show(v) for v in values})}")
+    return values[0]
+
+
 def lockstep_compatible(preps) -> bool:
     """Folds can share launches when they draw from one SubjectStore with one model kind and configuration and one batch size.  Their
     train / val sets may differ in size (WESAD subjects differ by a few windows, dataset.py:17-27): full batches run as one fold
     batch, the folds' ragged last batches as launches over the folds whose batch sizes agree (`launch_plan`).  The one-layer
     32-unit model has an arena form (padded, as runtime.EmbeddedEngine); a batch is uniform in depth — msig_batch.gru_layers is
-    one value per launch, and so is the kind (msig_multi has no per-slot flag: a launch runs msig_cg_*_multi or the msig_* calls)."""
+    one value per launch, and so is the kind (msig_multi has no per-slot flag: msig_st.kind is the launch's)."""
     if not (1 <= len(preps) <= L.MAX_FOLDS):       # a batch of ONE fold is a fold batch too (a window's last fold, a rank's only one)
         return False
     tr0, va0, _ = preps[0]["loaders"]
@@ -120,10 +128,7 @@ class LockstepTrainer:
         self.clip = any(v is not None for v in norms)
         # subject-adversarial training (config['adversary'], include/msig_da.h): every fold's discriminator lives in the arena set's
         # adversary block; S is the launch's, so the folds of a batch have equally many training subjects
-        doms = [_domains(p) for p in preps]
-        if any(d != doms[0] for d in doms):
-            raise ValueError(f"lockstep folds must share one adversary setting and domain count, got {sorted(set(map(str, doms)))}")
-        self.adv_S = doms[0]
+        self.adv_S = _shared([_domains(p) for p in preps], "adversary setting and domain count", str)
         if self.adv_S is not None:
             A.check_batch_size(tr0.batch_size)
         self.dom_stats = {}
@@ -136,20 +141,11 @@ class LockstepTrainer:
         self.grad_stats = {}
         # window augmentation inside the gather (include/msig_aug.h): the training loaders carry it; a launch has ONE set of
         # parameters, so the folds of a batch must agree on them — their keys are per fold (each loader's own seed and batch count)
-        augs = [getattr(p["loaders"][0], "augment", None) for p in preps]
-        if any(a != augs[0] for a in augs):
-            raise ValueError(f"lockstep folds must share one augmentation, got {sorted({repr(a) for a in augs})}")
-        self.augment = augs[0]
+        self.augment = _shared([getattr(p["loaders"][0], "augment", None) for p in preps], "augmentation", repr)
         # soft targets (include/msig_st.h): label smoothing is the launch's and mixup's alpha decides how every fold's lam is drawn,
         # so the folds of a batch must agree on both; lam itself is per fold, from each loader's own seed and batch count
-        mixes = [getattr(p["loaders"][0], "mixup", None) for p in preps]
-        if any(m != mixes[0] for m in mixes):
-            raise ValueError(f"lockstep folds must share one mixup alpha, got {sorted({repr(m) for m in mixes})}")
-        self.mixup = mixes[0]
-        smooths = [label_smoothing_setting(p["config"]["trainer"].get("label_smoothing")) or 0.0 for p in preps]
-        if any(v != smooths[0] for v in smooths):
-            raise ValueError(f"lockstep folds must share one label_smoothing, got {sorted(set(smooths))}")
-        self.smoothing = smooths[0]
+        self.mixup = _shared([getattr(p["loaders"][0], "mixup", None) for p in preps], "mixup alpha", repr)
+        self.smoothing = _shared([label_smoothing_setting(p["config"]["trainer"].get("label_smoothing")) or 0.0 for p in preps], "label_smoothing")
         self.trainers: List[Trainer] = []
         for slot, p in enumerate(preps):
             model = p["model"]
@@ -192,27 +188,19 @@ class LockstepTrainer:
 
     def _gather(self, loader, order_mat, row0, i, b, m, aug=None, lam=None):
         """order_mat: (folds, n_max) int64 store positions of the pass; gathers columns i .. i+b of rows row0 .. row0+m.n.
-        aug: the msig_aug of a training launch whose loaders augment (its keys filled for the folds of `m`).
-        lam: the folds' mixup weights of a training launch whose loaders mix (a C float array; include/msig_st.h)."""
-        if lam is not None:
-            L.check(L.lib().msig_st_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
-                                                         order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b,
-                                                         loader.store.shape[1], loader.store.shape[2], self.arena.ptr("x"), self.arena.ptr("y"),
-                                                         C.byref(m), C.byref(aug) if aug is not None else None, lam, self._stream()),
-                    "msig_st_gather_windows_multi")
+        lam: the folds' mixup weights (a C float array; include/msig_st.h) of a training launch whose loaders augment or mix — all
+        ones without mixup, which is the augmented gather itself; aug: its msig_aug (keys filled for the folds of `m`) or None.
+        lam None: the plain gather, which takes any window length."""
+        store, idx = loader.store, order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i)
+        if lam is None:
+            L.check(L.lib().msig_gather_windows_multi(store.data_ptr(), loader.store_y.data_ptr(), idx, order_mat.shape[1], b,
+                                                      store.shape[1] * store.shape[2], self.arena.ptr("x"), self.arena.ptr("y"), C.byref(m),
+                                                      self._stream()), "msig_gather_windows_multi")
             return
-        if aug is not None:
-            L.check(L.lib().msig_aug_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
-                                                          order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b,
-                                                          loader.store.shape[1], loader.store.shape[2], self.arena.ptr("x"), self.arena.ptr("y"),
-                                                          C.byref(m), C.byref(aug), self._stream()),
-                    "msig_aug_gather_windows_multi")
-            return
-        wfl = loader.store.shape[1] * loader.store.shape[2]
-        L.check(L.lib().msig_gather_windows_multi(loader.store.data_ptr(), loader.store_y.data_ptr(),
-                                                  order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i), order_mat.shape[1], b, wfl,
-                                                  self.arena.ptr("x"), self.arena.ptr("y"), C.byref(m), self._stream()),
-                "msig_gather_windows_multi")
+        L.check(L.lib().msig_st_gather_windows_multi(store.data_ptr(), loader.store_y.data_ptr(), idx, order_mat.shape[1], b, store.shape[1],
+                                                     store.shape[2], self.arena.ptr("x"), self.arena.ptr("y"), C.byref(m),
+                                                     C.byref(aug) if aug is not None else None, lam, self._stream()),
+                "msig_st_gather_windows_multi")
 
     @staticmethod
     def _stack(rows):
@@ -236,7 +224,6 @@ class LockstepTrainer:
         launch are consecutive rows of the order matrix (`launch_plan`); which folds share a launch has no influence on any
         fold's numbers.  Returns per-arena loss sums (indexed by slot) — the epoch's only sync."""
         arena, lib = self.arena, L.lib()
-        train_multi = lib.msig_cg_train_step_multi if self.kind == "cnn_gru" else lib.msig_cw_train_step_multi
         if self.clip:
             arena.zero_grad_stats(sorted(active))
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][0].dataset))
@@ -259,66 +246,43 @@ class LockstepTrainer:
         # mixup weights: every fold's lam of every step of the epoch at once, keyed like the augmentation (the same counter)
         mix = self.mixup
         la = [mix.lams(ld.aug_seed, range(ld.aug_step + 1, ld.aug_step + 1 + ns)) for ld, ns in zip(loaders, n_steps)] if mix is not None else None
-        soft = mix is not None or self.smoothing != 0.0
         # subject adversaries: every fold's lambda of every step of the epoch from its own schedule and step count
         advs = [t.adversary for t in trs] if self.adv_S is not None else None
         if advs is not None:
             arena.adversary_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
             dl = [[a.lam_at(a.step + 1 + k, a.total_steps) for k in range(ns)] for a, ns in zip(advs, n_steps)]
-        lam_arr = (C.c_float * L.MAX_FOLDS)() if mix is not None else None
         lrs = [t.optimizer.hyper["lr"] for t in trs]
         h0 = trs[0].optimizer.hyper
         b1, b2, eps, wd = h0["betas"][0], h0["betas"][1], h0["eps"], h0["weight_decay"]
         ea, eas, st = arena.ptr("exp_avg"), arena.ptr("exp_avg_sq"), self._stream()
-        multis = {}
+        # per row run (r0, nr) and epoch: its msig_multi (slots, learning rates), its msig_st (smoothing, class weights, the clip)
+        # and its msig_da or None; the step loop only fills keys, steps, lams, lambdas and idx.  Every launch is the widest call
+        # (runtime's module docstring): with everything off it is msig_train_step_multi, bit for bit.
+        runs = {}
         self._zero_acc(act)
         for i, b, r0, nr in launch_plan(sizes, bs):
             k = i // bs
-            if (r0, nr) not in multis:                                                 # slots and learning rates: per epoch and row run
-                multis[(r0, nr)] = arena.multi(act[r0:r0 + nr], lr=lrs[r0:r0 + nr])
-            m = multis[(r0, nr)]
+            if (r0, nr) not in runs:
+                sl = act[r0:r0 + nr]
+                runs[(r0, nr)] = (arena.multi(sl, lr=lrs[r0:r0 + nr]),
+                                  arena.soft(sl, self.smoothing, None, self.cw, arena.clip(sl, self.cw) if self.clip else None),
+                                  None if advs is None else arena.da(sl, self.adv_S, [0.0] * nr, [lrs[r0 + j] * advs[r0 + j].lr_mult for j in range(nr)],
+                                                                     [1] * nr, h0["betas"], eps, wd))
+            m, s, a = runs[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
-            if aug is not None:
-                for j in range(nr):
+                if aug is not None:
                     aug.key[j] = int(ka[r0 + j][k])
-            if mix is not None:
-                for j in range(nr):
-                    lam_arr[j] = la[r0 + j][k]
-            self._gather(loaders[0], order, r0, i, b, m, aug, lam_arr)
-            _, desc = self._layout(b, True)
-            if advs is not None:           # msig_da_train_step_multi: msig_st_train_step_multi plus the discriminators' launch
-                if (r0, nr, "st") not in multis:
-                    multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw,
-                                                        arena.clip(act[r0:r0 + nr], self.cw) if self.clip else None)
-                    multis[(r0, nr, "da")] = arena.da(act[r0:r0 + nr], self.adv_S, [0.0] * nr, [lrs[r0 + j] * advs[r0 + j].lr_mult for j in range(nr)],
-                                                      [1] * nr, h0["betas"], eps, wd)
-                s, a = multis[(r0, nr, "st")], multis[(r0, nr, "da")]
-                a.idx, a.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
-                for j in range(nr):
-                    s.lam[j] = lam_arr[j] if mix is not None else 1.0
+                if mix is not None:
+                    s.lam[j] = la[r0 + j][k]
+                if a is not None:
                     getattr(a, "lambda")[j], a.step[j] = dl[r0 + j][k], advs[r0 + j].step + 1 + k
-                L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a), ea, eas, b1, b2, eps, wd,
-                                                     int(steps[r0][k]), st), "msig_da_train_step_multi")
-                continue
-            if soft:                       # msig_st_train_step_multi: either kind, with or without class weights and clip
-                if (r0, nr, "st") not in multis:
-                    multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw,
-                                                        arena.clip(act[r0:r0 + nr], self.cw) if self.clip else None)
-                s = multis[(r0, nr, "st")]
-                for j in range(nr):
-                    s.lam[j] = lam_arr[j] if mix is not None else 1.0
-                L.check(lib.msig_st_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
-                        "msig_st_train_step_multi")
-                continue
-            if self.clip:
-                if (r0, nr, "gc") not in multis:
-                    multis[(r0, nr, "gc")] = arena.clip(act[r0:r0 + nr], self.cw)
-                L.check(lib.msig_gc_train_step_multi(C.byref(desc), C.byref(m), C.byref(multis[(r0, nr, "gc")]), ea, eas, b1, b2, eps, wd,
-                                                     int(steps[r0][k]), st), "msig_gc_train_step_multi")
-                continue
-            L.check(train_multi(C.byref(desc), C.byref(m), self.cw, ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st),
-                    train_multi.__name__)           # self.cw None: exactly msig_train_step_multi (msig_cg_*: the baseline)
+            if a is not None:
+                a.idx, a.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+            self._gather(loaders[0], order, r0, i, b, m, aug, s.lam if aug is not None or mix is not None else None)
+            _, desc = self._layout(b, True)
+            L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, ea, eas,
+                                                 b1, b2, eps, wd, int(steps[r0][k]), st), "msig_da_train_step_multi")
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
         if aug is not None or mix is not None:
@@ -343,7 +307,6 @@ class LockstepTrainer:
     def _evaluate(self, active, which):
         """Validation pass of every active fold (loader index `which`): per fold (loss, acc, f1), in the order of `active`."""
         arena, lib = self.arena, L.lib()
-        fwd_multi = lib.msig_cg_forward_multi if self.kind == "cnn_gru" else lib.msig_cw_forward_multi
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][which].dataset))
         loaders = [self.preps[f]["loaders"][which] for f in act]
         for f in act:
@@ -354,21 +317,16 @@ class LockstepTrainer:
         order = self._eval_orders[key]
         sizes, bs = [len(ld.dataset) for ld in loaders], loaders[0].batch_size
         st = self._stream()
-        multis = {}
+        runs = {}
         self._zero_acc(act)
         preds = [[] for _ in act]
         for i, b, r0, nr in launch_plan(sizes, bs):
-            if (r0, nr) not in multis:
-                multis[(r0, nr)] = arena.multi(act[r0:r0 + nr])
-            m = multis[(r0, nr)]
+            if (r0, nr) not in runs:           # the criterion's label smoothing applies to validation losses too; evaluation never mixes
+                runs[(r0, nr)] = (arena.multi(act[r0:r0 + nr]), arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw))
+            m, s = runs[(r0, nr)]
             self._gather(loaders[0], order, r0, i, b, m)
             off, desc = self._layout(b, False)
-            if self.smoothing != 0.0:          # the criterion's label smoothing applies to validation losses too; evaluation never mixes
-                if (r0, nr, "st") not in multis:
-                    multis[(r0, nr, "st")] = arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw)
-                L.check(lib.msig_st_forward_multi(C.byref(desc), C.byref(m), C.byref(multis[(r0, nr, "st")]), st), "msig_st_forward_multi")
-            else:
-                L.check(fwd_multi(C.byref(desc), C.byref(m), self.cw, st), fwd_multi.__name__)
+            L.check(lib.msig_st_forward_multi(C.byref(desc), C.byref(m), C.byref(s), st), "msig_st_forward_multi")
             got = arena.across("ws", off[L.WS["PRED"]], torch.int32, b)[act[r0:r0 + nr]]      # (folds of the launch, b) copy
             for j in range(nr):
                 preds[r0 + j].append(got[j])

@@ -4,6 +4,10 @@
 buffers, the BatchNorm buffers and a cache of workspaces, builds the
 `msig_batch` descriptor for every call and launches on torch's current HIP
 stream.  It holds no arithmetic of its own.
+
+The host never chooses among entry points: every train step is msig_da_train_step[_multi], every forward msig_st_forward[_multi],
+the widest of each form.  The headers make that bit-safe — a NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL
+class_weight each give the narrower call with its launches, `kind` selects the model — and tests/test_step_dispatch_gpu.py pins it.
 """
 from __future__ import annotations
 
@@ -72,6 +76,7 @@ class Engine:
         self._last: Optional[Tuple[int, int, object]] = None
         self._keep = None
         self._cw_checked = None                 # (weakref, version) of the last class-weight tensor whose values passed the checks
+        self._st_key, self._st_desc = None, None  # the cached msig_st (`_st`)
 
     # ---- views -----------------------------------------------------------------
     def _numel(self, i):
@@ -223,6 +228,27 @@ class Engine:
             self._cw_checked = (weakref.ref(w), w._version)
         return w.data_ptr()
 
+    def _checked(self, class_weight, max_grad_norm, label_smoothing, mix_lambda):
+        """The host-side checks of what forward() and train_step() take beyond the batch, before anything is scattered or launched
+        (ValueError): (class-weight pointer or None, max_norm or None, smoothing, lam)."""
+        return (self._class_weight(class_weight), None if max_grad_norm is None else L.check_max_grad_norm(max_grad_norm),
+                L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda))
+
+    def _st(self, cw: Optional[int], max_norm: Optional[float], smoothing: float, lam: float) -> L.St:
+        """The msig_st of a call, with its msig_gc_clip when max_norm is given.  Cached under what determines it (the kind is the
+        engine's): a step writes lam[0] and builds nothing.  The library reads a descriptor during the call, never after it."""
+        state = None if max_norm is None else self.ensure_gc_state()
+        key = (smoothing, cw, max_norm, None if state is None else state.data_ptr())
+        if key != self._st_key:
+            g = None
+            if state is not None:
+                g = L.GcClip()
+                g.kind, g.class_weight, g.state, g.state_bytes = L.GC_KINDS[self.kind], cw, state.data_ptr(), state.numel() * 8
+                g.max_norm[0] = max_norm
+            self._st_key, self._st_desc = key, L.make_st(self.kind, smoothing, cw, g)
+        self._st_desc.lam[0] = lam
+        return self._st_desc
+
     # ---- calls -------------------------------------------------------------------------
     def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False,
                 class_weight: Optional[torch.Tensor] = None, label_smoothing=0.0, mix_lambda=None) -> L.Batch:
@@ -230,23 +256,16 @@ class Engine:
         that a following backward() must be given.  An eval-mode forward (training=False) takes a backward only with
         keep_for_backward=True: it then keeps the stashes in a workspace of its own, with the same logits.  class_weight: a (K,)
         float32 device tensor = CrossEntropyLoss(weight=class_weight) for the loss and, kept for a backward, WS_DLOGITS
-        (msig_cw_forward); None = the unweighted criterion.  label_smoothing / mix_lambda: the soft-target criterion of
-        include/msig_st.h (msig_st_forward) — CrossEntropyLoss(label_smoothing=eps), and with mix_lambda = lam the loss against the
+        (include/msig_cw.h); None = the unweighted criterion.  label_smoothing / mix_lambda: the soft-target criterion of
+        include/msig_st.h — CrossEntropyLoss(label_smoothing=eps), and with mix_lambda = lam the loss against the
         row's own label (weight lam) and its partner's, row B-1-b (weight 1 - lam), for an `x` that was mixed the same way
-        (mixup.Mixup.apply, DeviceLoader(mixup=)); 0.0 and None (or 1) = the calls above, unchanged."""
-        cw = self._class_weight(class_weight)
-        eps, lam = L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
-        b = self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward)
-        if eps != 0.0 or lam != 1.0:
-            s = L.make_st(self.kind, eps, cw, None, [lam])
-            L.check(L.lib().msig_st_forward(C.byref(b), C.byref(s), self._stream()), "msig_st_forward")
-            return b
-        if self.kind == "cnn_gru":
-            L.check(L.lib().msig_cg_forward(C.byref(b), cw, self._stream()), "msig_cg_forward")
-        elif cw is None:
-            L.check(L.lib().msig_forward(C.byref(b), self._stream()), "msig_forward")
-        else:
-            L.check(L.lib().msig_cw_forward(C.byref(b), cw, self._stream()), "msig_cw_forward")
+        (mixup.Mixup.apply, DeviceLoader(mixup=)); 0.0 and None (or 1) = the plain criterion."""
+        cw, _, eps, lam = self._checked(class_weight, None, label_smoothing, mix_lambda)
+        return self.forward_desc(self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward), cw, eps, lam)
+
+    def forward_desc(self, b: L.Batch, cw: Optional[int] = None, smoothing: float = 0.0, lam: float = 1.0) -> L.Batch:
+        """The forward of an already-built descriptor (`_batch`, possibly with pointers of it replaced: adapt.py, calibrate.py)."""
+        L.check(L.lib().msig_st_forward(C.byref(b), C.byref(self._st(cw, None, smoothing, lam)), self._stream()), "msig_st_forward")
         return b
 
     def backward(self, b: L.Batch, dlogits: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None):
@@ -311,20 +330,19 @@ class Engine:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
-        class_weight: (K,) float32 device tensor = criterion CrossEntropyLoss(weight=class_weight) (msig_cw_train_step).
+        class_weight: (K,) float32 device tensor = criterion CrossEntropyLoss(weight=class_weight) (include/msig_cw.h).
         max_grad_norm: torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) between loss.backward() and
-        optimizer.step() (msig_gc_train_step, DESIGN.md §15): `grads` then holds the clipped gradient and grad_stats() the norms;
-        float('inf') measures without clipping; None = the calls above, unchanged.
-        label_smoothing / mix_lambda: the soft-target criterion (msig_st_train_step; see forward()), with or without
-        class weights and clip; 0.0 and None (or 1) = the calls above, unchanged.
-        adversary: an adversary.SubjectAdversary bound to this device (msig_da_train_step): one more launch trains it
+        optimizer.step() (include/msig_gc.h, DESIGN.md §15): `grads` then holds the clipped gradient and grad_stats() the norms;
+        float('inf') measures without clipping; None = unclipped.
+        label_smoothing / mix_lambda: the soft-target criterion (include/msig_st.h; see forward()), with or without
+        class weights and clip; 0.0 and None (or 1) = the plain criterion.
+        adversary: an adversary.SubjectAdversary bound to this device (include/msig_da.h): one more launch trains it
         on the step's features and adds the reversed gradient of its loss, times its scheduled lambda, to the feature gradient; it
         advances its own step count.  batch_index: the int64 store positions of the rows (DeviceLoader.last_index) by which the
         adversary's domain table is read; None = the table has one entry per row.  The discriminator's Adam takes THIS call's betas,
-        eps and weight_decay (L2 decay included) and lr * adversary.lr_mult.  None = the calls above, unchanged."""
-        cw = self._class_weight(class_weight)
-        max_norm = None if max_grad_norm is None else L.check_max_grad_norm(max_grad_norm)
-        smooth, lam = L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
+        eps and weight_decay (L2 decay included) and lr * adversary.lr_mult.  None = no adversary.  One library call whatever is
+        on (module docstring)."""
+        cw, max_norm, smooth, lam = self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
         if adversary is not None:
             if x.shape[0] > L.DA_MAX_BATCH:
                 raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
@@ -334,40 +352,17 @@ class Engine:
                     raise ValueError(f"batch_index must be a contiguous int64 ({x.shape[0]},) tensor, got {batch_index.dtype} {tuple(batch_index.shape)}")
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
-        g = None
-        if max_norm is not None:
-            state = self.ensure_gc_state()
-            g = L.GcClip()
-            g.kind, g.class_weight, g.state, g.state_bytes = L.GC_KINDS[self.kind], cw, state.data_ptr(), state.numel() * 8
-            g.max_norm[0] = max_norm
+        a = None
         if adversary is not None:
             adversary.last_lambda = adversary.next_lambda()
-            a = adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1],
-                                     idx=None if batch_index is None else batch_index.data_ptr(), betas=betas, eps=eps, weight_decay=weight_decay)
-            s = L.make_st(self.kind, smooth, cw, g, [lam])
-            L.check(L.lib().msig_da_train_step(C.byref(b), C.byref(s), C.byref(a), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_da_train_step")
+            a = C.byref(adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1],
+                                             idx=None if batch_index is None else batch_index.data_ptr(), betas=betas, eps=eps, weight_decay=weight_decay))
+        L.check(L.lib().msig_da_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, self.exp_avg.data_ptr(),
+                                           self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
+                "msig_da_train_step")
+        if adversary is not None:
             adversary.step += 1
             self._keep = self._keep + (batch_index,)
-            return
-        if smooth != 0.0 or lam != 1.0:
-            s = L.make_st(self.kind, smooth, cw, g, [lam])
-            L.check(L.lib().msig_st_train_step(C.byref(b), C.byref(s), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_st_train_step")
-            return
-        if max_norm is not None:
-            L.check(L.lib().msig_gc_train_step(C.byref(b), C.byref(g), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_gc_train_step")
-            return
-        if self.kind == "cnn_gru":
-            L.check(L.lib().msig_cg_train_step(C.byref(b), cw, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_cg_train_step")
-        elif cw is None:
-            L.check(L.lib().msig_train_step(C.byref(b), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                            betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_train_step")
-        else:
-            L.check(L.lib().msig_cw_train_step(C.byref(b), cw, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr,
-                                               betas[0], betas[1], eps, weight_decay, step, self._stream()), "msig_cw_train_step")
 
     def features(self, x: torch.Tensor, padded: bool = False) -> torch.Tensor:
         """The (B, 128) vector the classifier sees, outputs[:, -1, :], of an EVAL-mode forward (running-statistics BatchNorm, no
@@ -479,17 +474,13 @@ class EmbeddedEngine(Engine):
     # ---- the library calls, with the embedding maintained around them ----
     def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False, class_weight=None,
                 label_smoothing=0.0, mix_lambda=None):
-        self._class_weight(class_weight)                    # the checks before the scatter: nothing runs on a bad vector
-        L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
+        self._checked(class_weight, None, label_smoothing, mix_lambda)      # before the scatter: nothing runs on a bad argument
         self.scatter()
         return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight, label_smoothing, mix_lambda)
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
                    max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None):
-        self._class_weight(class_weight)
-        if max_grad_norm is not None:
-            L.check_max_grad_norm(max_grad_norm)
-        L.check_label_smoothing(label_smoothing), L.check_mix_lambda(mix_lambda)
+        self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
         if adversary is not None:
             adversary.restrict_features(self.hidden)       # nothing may reach the padded feature columns (their units must stay zero)
         self.scatter()
@@ -618,7 +609,7 @@ class FoldArena:
         return self.da_mem.data_ptr() + self.da_off[name][0]            # fold slot 0's adversary buffer
 
     def da(self, slots, S: int, lambdas, lrs, steps, betas, eps, weight_decay) -> L.Da:
-        """msig_da of a launch over `slots` (msig_da_train_step_multi): fold slot 0's adversary buffers, `da_stride` apart, and every
+        """msig_da of a launch over `slots` (include/msig_da.h): fold slot 0's adversary buffers, `da_stride` apart, and every
         fold's reversal weight, learning rate and step count.  idx / idx_row_stride are the launch's to fill in."""
         a = L.Da()
         a.S, a.weight_decay, a.beta1, a.beta2, a.eps = int(S), weight_decay, betas[0], betas[1], eps
@@ -647,7 +638,7 @@ class FoldArena:
         self.max_norm[slot] = L.check_max_grad_norm(value)
 
     def clip(self, slots, class_weight: Optional[int] = None) -> L.GcClip:
-        """msig_gc_clip of a launch over `slots` (msig_gc_train_step_multi): arena 0's clip state, every fold's own max_norm."""
+        """msig_gc_clip of a launch over `slots` (include/msig_gc.h): arena 0's clip state, every fold's own max_norm."""
         if not self.grad_clip:
             raise RuntimeError("this FoldArena was built without grad_clip=True: it has no clip state")
         g = L.GcClip()
@@ -674,8 +665,7 @@ class FoldArena:
 
     def grad_stats(self, slot: int) -> dict:
         """Gradient-norm statistics of the fold in arena `slot` since zero_grad_stats (Engine.grad_stats; one read-back)."""
-        s = self.view(slot, "gc", torch.float64)[:L.GC_NSTAT].cpu().tolist()
-        return dict(sum=s[L.GC_SUM], max=s[L.GC_MAX], clipped=int(s[L.GC_CLIPPED]), last=s[L.GC_LAST])
+        return Engine._stats(self.view(slot, "gc", torch.float64)[:L.GC_NSTAT].cpu().tolist())
 
     def batch(self, B: int, training: bool, dropout_p: float, with_labels: bool = True) -> L.Batch:
         """msig_batch describing arena 0 (the *_multi calls shift every pointer by slot * stride)."""

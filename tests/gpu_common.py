@@ -229,3 +229,47 @@ def format_report(rep):
 
 def failures(rep):
     return [k for k, (e, tol) in rep.items() if not (e <= tol)]
+
+
+# ---- the narrow entry points, called directly ---------------------------------------------------------------------------------------
+# Engine.train_step / Engine.forward always issue the widest library call; the "is the counterpart" tests and
+# tests/test_step_dispatch_gpu.py put the entry point a header names on the other side of their comparison with these.
+def legacy_train_step(e, x, y, lr, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None, betas=(0.9, 0.999), eps=1e-8):
+    """One fused step of engine `e` through msig_cg_train_step (the cnn_gru kind), msig_cw_train_step (a class-weight tensor) or
+    msig_train_step, with EmbeddedEngine's scatter / gather around it.  Returns the name of the entry point it called."""
+    import ctypes as C
+    from multimodalsignal_amd import _lib as L
+    cw = e._class_weight(class_weight)
+    if hasattr(e, "scatter"):
+        e.scatter()
+    e.ensure_adam_state()
+    b = e._batch(x, y, True, dropout_p, seed, step)
+    tail = (e.exp_avg.data_ptr(), e.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, e._stream())
+    if e.kind == "cnn_gru":
+        name, rc = "msig_cg_train_step", L.lib().msig_cg_train_step(C.byref(b), cw, *tail)
+    elif cw is not None:
+        name, rc = "msig_cw_train_step", L.lib().msig_cw_train_step(C.byref(b), cw, *tail)
+    else:
+        name, rc = "msig_train_step", L.lib().msig_train_step(C.byref(b), *tail)
+    L.check(rc, name)
+    if hasattr(e, "gather"):
+        e.gather()
+    return name
+
+
+def legacy_forward(e, x, y=None, training=False, keep_for_backward=False, class_weight=None, dropout_p=0.0, seed=0, step=0):
+    """A forward of engine `e` through msig_cg_forward, msig_cw_forward or msig_forward, chosen as legacy_train_step chooses."""
+    import ctypes as C
+    from multimodalsignal_amd import _lib as L
+    cw = e._class_weight(class_weight)
+    if hasattr(e, "scatter"):
+        e.scatter()
+    b = e._batch(x, y, training, dropout_p, seed, step, keep_for_backward)
+    if e.kind == "cnn_gru":
+        name, rc = "msig_cg_forward", L.lib().msig_cg_forward(C.byref(b), cw, e._stream())
+    elif cw is not None:
+        name, rc = "msig_cw_forward", L.lib().msig_cw_forward(C.byref(b), cw, e._stream())
+    else:
+        name, rc = "msig_forward", L.lib().msig_forward(C.byref(b), e._stream())
+    L.check(rc, name)
+    return name

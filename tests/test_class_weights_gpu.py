@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_common import grad_tol, rel_err, stage_tol
+from gpu_common import grad_tol, legacy_forward, legacy_train_step, rel_err, stage_tol
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.runtime import EmbeddedEngine, Engine, FoldArena
 from oracle import cnn_gru_oracle as O
@@ -59,7 +59,10 @@ def test_all_ones_train_step_is_bit_identical(B, T):
     for cw in (None, torch.ones(K, device=DEV)):
         e, _ = _engine(Cc, K)
         for s in (1, 2):
-            e.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7, class_weight=cw)
+            if cw is None:       # the counterpart: msig_train_step itself (Engine.train_step issues the widest call either way)
+                assert legacy_train_step(e, x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7) == "msig_train_step"
+            else:
+                e.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7, class_weight=cw)
         out.append(e)
     torch.cuda.synchronize()
     a, b = out
@@ -79,7 +82,10 @@ def test_all_ones_eval_forward_is_bit_identical():
         out = []
         for cw in (None, torch.ones(K, device=DEV)):
             e, _ = _engine(Cc, K)
-            e.forward(x, y, training=False, keep_for_backward=keep, class_weight=cw)
+            if cw is None:       # the counterpart: msig_forward itself
+                assert legacy_forward(e, x, y, keep_for_backward=keep) == "msig_forward"
+            else:
+                e.forward(x, y, training=False, keep_for_backward=keep, class_weight=cw)
             out.append(e)
         torch.cuda.synchronize()
         a, b = out

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import legacy_train_step
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.runtime import EmbeddedEngine, Engine, FoldArena
 from oracle import cnn_gru_oracle as O
@@ -85,7 +86,10 @@ def test_max_norm_inf_is_the_unclipped_step_bit_for_bit(config, B, T, weighted):
     for mn in (None, INF):
         e, _ = _engine(Cc, K, config)
         for s in (1, 2):
-            e.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7, class_weight=cw, max_grad_norm=mn)
+            if mn is None:       # the counterpart: the existing fused step's own entry point (msig_train_step / _cw_ / _cg_)
+                legacy_train_step(e, x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7, class_weight=cw)
+            else:
+                e.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7, class_weight=cw, max_grad_norm=mn)
         out.append(e)
     torch.cuda.synchronize()
     a, b = out
@@ -203,7 +207,7 @@ def test_a_norm_below_max_norm_is_not_clipped_and_is_counted_so():
     a, _ = _engine(Cc, K)
     b, _ = _engine(Cc, K)
     for s in (1, 2, 3):
-        a.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7)
+        legacy_train_step(a, x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7)          # msig_train_step itself
         b.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7, max_grad_norm=1e6)
     torch.cuda.synchronize()
     _assert_same_state(a, b, B, K)

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 import st_reference as S
 from aug_reference import dropout_key
-from gpu_common import grad_tol, rel_err, stage_tol
+from gpu_common import grad_tol, legacy_forward, legacy_train_step, rel_err, stage_tol
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.augment import Augment
 from multimodalsignal_amd.mixup import Mixup
@@ -83,7 +83,7 @@ def _wt(w):
 
 
 def _st_train_step(e, x, y, step, smoothing, lam, seed=7, cw=None, clip=None):
-    """msig_st_train_step itself, whatever the values (Engine.train_step routes (0, 1) to the plain calls before the library does)."""
+    """msig_st_train_step itself, whatever the values."""
     e.ensure_adam_state()
     b = e._batch(x, y, True, P, seed, step)
     s = L.make_st(e.kind, smoothing, e._class_weight(cw), clip, [lam])
@@ -110,7 +110,7 @@ def test_off_train_step_is_bit_identical(B, T):
             if off:
                 _st_train_step(e, x, y, s, 0.0, 1.0)
             else:
-                e.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7)
+                assert legacy_train_step(e, x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=7) == "msig_train_step"
         out.append(e)
     torch.cuda.synchronize()
     a, b = out
@@ -128,7 +128,7 @@ def test_off_eval_forward_is_bit_identical():
     for keep in (False, True):
         a, _ = _engine(Cc, K)
         b, _ = _engine(Cc, K)
-        a.forward(x, y, training=False, keep_for_backward=keep)
+        assert legacy_forward(a, x, y, keep_for_backward=keep) == "msig_forward"
         _st_forward(b, x, y, 0.0, 1.0, keep)
         torch.cuda.synchronize()
         ra, rb = _regions(a, B, K, keep), _regions(b, B, K, keep)
@@ -474,7 +474,7 @@ def test_infinite_clip_is_the_unclipped_soft_step(B, T):
     a, _ = _engine(Cc, K)
     b, _ = _engine(Cc, K)
     for s in (1, 2):
-        a.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=5, **kw)
+        _st_train_step(a, x, y, s, 0.1, 0.3, seed=5, cw=kw["class_weight"])      # the counterpart: msig_st_train_step itself, no clip
         b.train_step(x, y, LR, weight_decay=WD, step=s, dropout_p=P, seed=5, max_grad_norm=float("inf"), **kw)
     torch.cuda.synchronize()
     for name in ("grads", "params", "exp_avg", "exp_avg_sq", "bn_state"):
