@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -100,6 +100,7 @@ MC_MAX_SAMPLES = 256  # msig_mc.h MSIG_MC_MAX_SAMPLES: stochastic passes per win
 MC_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_MC_KIND_*
 DA_ABI_VERSION = 1    # include/msig_da.h MSIG_DA_ABI_VERSION (subject-adversarial training: the discriminator's step)
 DA_MAX_BATCH = 256    # msig_da.h MSIG_DA_MAX_BATCH: rows of one discriminator step
+WA_ABI_VERSION = 1    # include/msig_wa.h MSIG_WA_ABI_VERSION (weight averaging: the shadow's update)
 
 
 class Multi(C.Structure):
@@ -158,6 +159,13 @@ class Da(C.Structure):
                 ("dom", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64), ("params", C.c_void_p), ("exp_avg", C.c_void_p),
                 ("exp_avg_sq", C.c_void_p), ("stats", C.c_void_p), ("stride_bytes", C.c_int64), ("lambda", C.c_float * MAX_FOLDS),
                 ("lr", C.c_float * MAX_FOLDS), ("step", C.c_int64 * MAX_FOLDS)]
+
+
+class Wa(C.Structure):
+    """msig_wa (include/msig_wa.h): the weight-averaging update of a launch — the model's parameters and BatchNorm state, the shadow's
+    (in a fold batch both are fold slot 0's, msig_multi.stride_bytes apart) and every fold's coefficient."""
+    _fields_ = [("n_flat", C.c_int64), ("params", C.c_void_p), ("bn_state", C.c_void_p), ("bn_count", C.c_void_p),
+                ("avg_params", C.c_void_p), ("avg_bn_state", C.c_void_p), ("avg_bn_count", C.c_void_p), ("coef", C.c_float * MAX_FOLDS)]
 
 
 def make_st(kind: str, smoothing: float, class_weight=None, clip: "GcClip" = None, lams=(1.0,)) -> St:
@@ -346,6 +354,14 @@ def lib() -> C.CDLL:
         L.msig_da_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Da), vp, vp, f32, f32, f32, f32, f32, i64, vp]
         L.msig_da_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), vp, vp, f32, f32, f32, f32,
                                                i64, vp]
+        # include/msig_wa.h, exported by the same library: the weight-averaging update of a shadow model
+        L.msig_wa_abi_version.restype = C.c_int
+        L.msig_wa_struct_bytes.restype = C.c_int64
+        if L.msig_wa_abi_version() != WA_ABI_VERSION or L.msig_wa_struct_bytes() != C.sizeof(Wa):
+            raise RuntimeError(f"{LIB_PATH} has msig_wa.h ABI {L.msig_wa_abi_version()} with msig_wa of {L.msig_wa_struct_bytes()} bytes; "
+                               f"this binding is {WA_ABI_VERSION} with {C.sizeof(Wa)}: rebuild the library")
+        L.msig_wa_update.argtypes = [C.POINTER(Wa), vp]
+        L.msig_wa_update_multi.argtypes = [C.POINTER(Wa), C.POINTER(Multi), vp]
         _lib = L
     return _lib
 
@@ -491,6 +507,20 @@ def check_mix_lambda(value) -> float:
         raise ValueError(f"mix_lambda must be a number in [0, 1], got {value!r}") from None
     if not 0.0 <= v <= 1.0:
         raise ValueError(f"mix_lambda must be a number in [0, 1], got {value!r}")
+    return C.c_float(v).value
+
+
+def check_average_coef(value) -> float:
+    """The host-side check of a weight-averaging coefficient (include/msig_wa.h): a number in [0, 1], returned as the fp32 value the
+    call will see.  ValueError otherwise."""
+    if isinstance(value, (str, bytes, bool)):
+        raise ValueError(f"an averaging coefficient must be a number in [0, 1], got {value!r}")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"an averaging coefficient must be a number in [0, 1], got {value!r}") from None
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"an averaging coefficient must be a number in [0, 1], got {value!r}")
     return C.c_float(v).value
 
 

@@ -31,10 +31,11 @@ from . import _lib as L
 from .augment import Augment
 from .mixup import Mixup
 from . import adversary as adversary_mod
+from . import averaging as averaging_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
-from .multifold import fold_result, lockstep_compatible
+from .multifold import averaged_result, fold_result, lockstep_compatible
 from .trainer import Trainer, grad_clip_setting, label_smoothing_setting
 from .waves import MAX_TRAIN_STREAMS, cap_waves, chunk_schedule, deal, on_streams, run_wave  # noqa: F401  (the first three: importable from here)
 
@@ -101,6 +102,8 @@ def trainer_config(cfg, fold_idx):
         tc["trainer"]["label_smoothing"] = label_smoothing_setting(cfg["label_smoothing"])
     if cfg.get("adversary") is not None:            # a subject discriminator inside every training step (include/msig_da.h); absent = none
         tc["adversary"] = adversary_mod.settings(cfg["adversary"])
+    if cfg.get("averaging") is not None:            # an EMA / SWA shadow of the weights (include/msig_wa.h); absent = none
+        tc["averaging"] = averaging_mod.settings(cfg["averaging"])
     return tc
 
 
@@ -175,7 +178,8 @@ def train_fold(prep, device):
     t0 = time.time()
     trainer.train(train_loader, val_loader)
     acc, f1 = trainer.evaluate(test_loader, is_test=True)[1:] if prep.get("test_pass", True) else (None, None)
-    return fold_result(prep, trainer, acc, f1, time.time() - t0)
+    seconds = time.time() - t0
+    return fold_result(prep, trainer, acc, f1, seconds, averaged_result(prep, trainer))      # config['averaging']: the averaged model's passes
 
 
 def run_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
@@ -205,6 +209,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(soft_targets_line(cfg))
         if adversary_line(cfg) is not None:                         # likewise
             f.write(adversary_line(cfg))
+        if cfg.get("averaging") is not None:                        # likewise
+            f.write(averaging_mod.settings_line(cfg["averaging"]) + "\n")
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -467,6 +473,13 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
                 path = adversary_mod.write_adversary(out_dir[n], folds, adversary_mod.settings(cfgs[n]["adversary"]),
                                                      synthetic=bool(cfgs[n].get("synthetic")))
                 print(f"Subject-adversary table written to: {path}")
+        if cfgs[n].get("averaging") is not None:      # likewise from the folds' fold_result.json
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "fold_result.json" for r in results[n]]
+            folds = [averaging_mod.fold_record(json.loads(f.read_text())) for f in files if f.exists()]
+            folds = [f for f in folds if f is not None]
+            if folds:
+                path = averaging_mod.write_averaging(out_dir[n], folds, cfgs[n]["averaging"], synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Weight-averaging table written to: {path}")
         if cal_all is not None:
             from .calibrate import write_calibration
             folds = [{"subject": cfgs[n]["subjects"][units[u][1]], "n_cal": int(cal_all[u][2][0]), "n_eval": int(cal_all[u][2][1]),
@@ -868,6 +881,20 @@ def parse_args(ap, argv=None):
             ap.error(f"--subject-adversarial: {e}")
     elif args.adversary_schedule is not None or args.adversary_lr_mult is not None:
         ap.error("--adversary-schedule / --adversary-lr-mult need --subject-adversarial")
+    if args.weight_average is not None:
+        try:
+            spec = averaging_mod.parse_flag(args.weight_average)
+            if args.average_bn is not None:
+                spec["bn"] = args.average_bn
+            if args.average_validate:
+                spec["validate"] = True
+            args.weight_average = averaging_mod.settings(spec)
+        except ValueError as e:
+            ap.error(f"--weight-average: {e}")
+        if args.hierarchical or args.ablation or args.sweep:
+            ap.error("--weight-average runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
+    elif args.average_bn is not None or args.average_validate:
+        ap.error("--average-bn / --average-validate need --weight-average")
     return args
 
 
@@ -932,6 +959,20 @@ def build_parser():
                          "done (default), or constant")
     ap.add_argument("--adversary-lr-mult", type=float, default=None, metavar="X",
                     help="the discriminator's learning rate as a multiple of the model's (default 1)")
+    ap.add_argument("--weight-average", default=None, metavar="ema[:DECAY]|swa[:START_EPOCH]",
+                    help="keep an averaged copy of every fold's weights and BatchNorm statistics beside the model: ema = an exponential "
+                         "moving average updated after every train step (DECAY in [0, 1), default 0.99, with a 10-update warm-up), swa = "
+                         "the mean of the epoch-end weights from epoch START_EPOCH on (default 10).  One more streaming launch per step "
+                         "(ema) or epoch (swa); training, early stopping, best_model.pt and every LOSO number are unchanged.  After each "
+                         "fold writes averaged_model.pt, evaluates it on the fold's validation and test windows and writes averaging.txt / "
+                         "averaging.json (standard LOSO and --model comparison runs; combines with every training-time option and with "
+                         "--calibrate, --adapt-bn, --attribute and --mc-dropout, which keep acting on the LOSO model)")
+    ap.add_argument("--average-bn", choices=list(averaging_mod.BN_MODES), default=None,
+                    help="BatchNorm statistics of the averaged model: average = averaged like the weights (ema's default), recompute = "
+                         "re-estimated on the fold's training windows under the averaged weights after training (swa's default)")
+    ap.add_argument("--average-validate", action="store_true",
+                    help="also run each epoch's validation pass under the averaged model and log it (val_loss_avg / val_acc_avg / "
+                         "val_f1_avg in the history); it steers nothing")
     ap.add_argument("--model", nargs="+", choices=list(MODEL_PARAMS), default=[MODEL_TO_USE],
                     help="model kind(s): cnn_gru_attention (the reference's model) and/or cnn_gru (the baseline without ChannelAttention). "
                          "Two kinds run the LOSO (or each sweep set) once per kind as one job, with paired folds, and write "
@@ -993,6 +1034,8 @@ def build_cfg(args, kinds):
     if args.subject_adversarial is not None:      # likewise; refused here, before any data or GPU work, for a batch size it cannot take
         adversary_mod.check_batch_size(args.batch_size)
         cfg.update(adversary=args.subject_adversarial, synthetic=args.synthetic is not None)
+    if args.weight_average is not None:           # likewise
+        cfg.update(averaging=args.weight_average, synthetic=args.synthetic is not None)
     if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was
         cfg.update(calibrate=args.calibrate, synthetic=args.synthetic is not None, calibration_batched=not args.calibration_sequential)
         for key, val in (("calibration_gap", args.calibration_gap), ("calibration_epochs", args.calibration_epochs),

@@ -15,7 +15,9 @@ stand-alone run whatever its companions, the grouping or the rank count
 `adaptive_forms` the backward form follows the folds still active in a launch (a fold's last bits then depend, reproducibly, on
 when its companions stop).  Folds may differ in train / val set size; folds that
 stop early leave the batch.  Every train launch is msig_da_train_step_multi and every evaluation launch msig_st_forward_multi,
-whatever the folds have switched on: runtime's module docstring says why that is bit-safe.
+whatever the folds have switched on: runtime's module docstring says why that is bit-safe.  With config['averaging'] every train
+launch is followed by one msig_wa_update_multi over the same folds (EMA; SWA: one per epoch), each fold at its own coefficient: the
+shadows live in the arenas, where msig_st_forward_multi can evaluate them (include/msig_wa.h).
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ import torch
 
 from . import _lib as L
 from . import adversary as A
+from . import averaging as AV
 from .runtime import FoldArena
 from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary, label_smoothing_setting
 
@@ -43,13 +46,32 @@ def _kind(model):
     return getattr(model, "kind", None) or "cnn_gru_attention"
 
 
-def fold_result(prep, trainer, accuracy, f1_score, seconds):
+def averaged_result(prep, trainer):
+    """What a fold trained with config['averaging'] adds to its result, whichever mode trained it; None without averaging.  Writes
+    averaged_model.pt beside best_model.pt and evaluates the averaged model — the shadow at the end of training — on the fold's
+    validation set and (when the fold has a test pass) its test set: the windows the LOSO model is evaluated on.  `loso_val_loss` is
+    the LOSO model's loss (the model as `_finish_training` left it) on the same validation windows."""
+    av = getattr(trainer, "averager", None)
+    if av is None:
+        return None
+    av.bind(trainer.model.engine()).save(prep["fold_dir"] / "averaged_model.pt")
+    out = av.summary()
+    out["val_loss"], out["val_acc"], out["val_f1"] = trainer.evaluate_averaged(prep["loaders"][1])
+    out["loso_val_loss"] = trainer.evaluate(prep["loaders"][1])[0]
+    out["test_loss"], out["accuracy"], out["f1_score"] = trainer.evaluate_averaged(prep["loaders"][2]) if prep.get("test_pass", True) else (None,) * 3
+    return out
+
+
+def fold_result(prep, trainer, accuracy, f1_score, seconds, averaging=None):
     """The result dict of one trained fold, whichever mode trained it (main.train_fold, LockstepTrainer.run); a fold with a test
-    pass of its own leaves it in fold_result.json as soon as it has finished (it survives a crash of another fold)."""
+    pass of its own leaves it in fold_result.json as soon as it has finished (it survives a crash of another fold).  averaging:
+    `averaged_result` of a fold trained with config['averaging'] — one more key; None adds nothing."""
     info = dict(subject=prep["subject"], accuracy=accuracy, f1_score=f1_score, seconds=seconds, epochs=len(trainer.history),
                 train_windows_per_s=trainer.train_windows / max(trainer.train_seconds, 1e-9), history=trainer.history)
     if getattr(trainer, "adversary", None) is not None:      # config['adversary']: what main.write_adversary tabulates
         info["adversary_domains"] = trainer.adversary.S
+    if averaging is not None:
+        info["averaging"] = averaging
     if prep.get("test_pass", True):
         (prep["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
     return info
@@ -132,9 +154,14 @@ class LockstepTrainer:
         if self.adv_S is not None:
             A.check_batch_size(tr0.batch_size)
         self.dom_stats = {}
+        # weight averaging (config['averaging'], include/msig_wa.h): the folds of a batch share one setting (the launches after a
+        # step and the per-epoch passes are the batch's); coefficients and counters are per fold.  The shadows are arena regions.
+        self.avg_cfg = _shared([AV.settings(p["config"].get("averaging")) for p in preps], "averaging setting", repr)
+        self._wa_started = False
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
                                adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip,
-                               adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])))
+                               adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])),
+                               averaging=self.avg_cfg is not None)
         if self.clip:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
@@ -179,12 +206,18 @@ class LockstepTrainer:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- host-side bookkeeping is kept off the per-step path: descriptors, layouts and dropout keys are prepared per epoch ----
-    def _layout(self, B, training):
-        key = (B, bool(training))
+    def _layout(self, B, training, shadow=False):
+        key = (B, bool(training)) + ((True,) if shadow else ())
         if key not in self._layouts:
             off = L.workspace_layout(B, self.C, self.T, self.K, training)
-            self._layouts[key] = (off, self.arena.batch(B, training, self.trainers[0].model.dropout_p if training else 0.0))
+            self._layouts[key] = (off, self.arena.batch(B, training, self.trainers[0].model.dropout_p if training else 0.0, shadow=shadow))
         return self._layouts[key]
+
+    def _wa_update(self, slots, coefs):
+        """One msig_wa_update_multi over arenas `slots`, each fold at its own coefficient (all zero: no launch)."""
+        if any(c != 0.0 for c in coefs):
+            L.check(L.lib().msig_wa_update_multi(C.byref(self.arena.wa(slots, coefs)), C.byref(self.arena.multi(slots)), self._stream()),
+                    "msig_wa_update_multi")
 
     def _gather(self, loader, order_mat, row0, i, b, m, aug=None, lam=None):
         """order_mat: (folds, n_max) int64 store positions of the pass; gathers columns i .. i+b of rows row0 .. row0+m.n.
@@ -251,6 +284,13 @@ class LockstepTrainer:
         if advs is not None:
             arena.adversary_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
             dl = [[a.lam_at(a.step + 1 + k, a.total_steps) for k in range(ns)] for a, ns in zip(advs, n_steps)]
+        # weight averaging: EMA's coefficient of every step of the epoch per fold, from the fold's own update count
+        avs = [t.averager for t in trs] if self.avg_cfg is not None else None
+        ema = avs is not None and self.avg_cfg["mode"] == "ema"
+        if avs is not None and not self._wa_started:          # EMA: every shadow starts as a copy of its initial model
+            self._wa_started = True
+            self._wa_update(act, [av.start_coef() for av in avs])
+        wc = [av.peek_step_coefs(ns) for av, ns in zip(avs, n_steps)] if ema else None
         lrs = [t.optimizer.hyper["lr"] for t in trs]
         h0 = trs[0].optimizer.hyper
         b1, b2, eps, wd = h0["betas"][0], h0["betas"][1], h0["eps"], h0["weight_decay"]
@@ -267,8 +307,9 @@ class LockstepTrainer:
                 runs[(r0, nr)] = (arena.multi(sl, lr=lrs[r0:r0 + nr]),
                                   arena.soft(sl, self.smoothing, None, self.cw, arena.clip(sl, self.cw) if self.clip else None),
                                   None if advs is None else arena.da(sl, self.adv_S, [0.0] * nr, [lrs[r0 + j] * advs[r0 + j].lr_mult for j in range(nr)],
-                                                                     [1] * nr, h0["betas"], eps, wd))
-            m, s, a = runs[(r0, nr)]
+                                                                     [1] * nr, h0["betas"], eps, wd),
+                                  arena.wa(sl, [0.0] * nr) if ema else None)
+            m, s, a, w = runs[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
                 if aug is not None:
@@ -283,8 +324,17 @@ class LockstepTrainer:
             _, desc = self._layout(b, True)
             L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, ea, eas,
                                                  b1, b2, eps, wd, int(steps[r0][k]), st), "msig_da_train_step_multi")
+            if w is not None:                  # EMA: one launch over the same folds, each at its own coefficient
+                for j in range(nr):
+                    w.coef[j] = wc[r0 + j][k]
+                L.check(lib.msig_wa_update_multi(C.byref(w), C.byref(m), st), "msig_wa_update_multi")
         for t, s0, ns in zip(trs, step0, n_steps):
             t.optimizer.step_count = s0 + ns
+        if ema:
+            for av, ns in zip(avs, n_steps):
+                av.advance(ns)
+        elif avs is not None:                  # SWA: the epoch-end iterate of every active fold that has reached start_epoch, one launch
+            self._wa_update(act, [av.epoch_coef(len(t.history) + 1) for av, t in zip(avs, trs)])
         if aug is not None or mix is not None:
             for ld, ns in zip(loaders, n_steps):
                 ld.aug_step += ns
@@ -304,8 +354,10 @@ class LockstepTrainer:
                            for f, ns in zip(act, n_steps) if self.trainers[f].max_grad_norm is not None}
         return sums
 
-    def _evaluate(self, active, which):
-        """Validation pass of every active fold (loader index `which`): per fold (loss, acc, f1), in the order of `active`."""
+    def _evaluate(self, active, which, shadow=False):
+        """Validation pass of every active fold (loader index `which`): per fold (loss, acc, f1), in the order of `active`.  shadow:
+        the same pass under the folds' weight-averaging shadows (the descriptor points at the "avg_*" regions), with its own
+        accumulator zeroing and read-back."""
         arena, lib = self.arena, L.lib()
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][which].dataset))
         loaders = [self.preps[f]["loaders"][which] for f in act]
@@ -325,7 +377,7 @@ class LockstepTrainer:
                 runs[(r0, nr)] = (arena.multi(act[r0:r0 + nr]), arena.soft(act[r0:r0 + nr], self.smoothing, None, self.cw))
             m, s = runs[(r0, nr)]
             self._gather(loaders[0], order, r0, i, b, m)
-            off, desc = self._layout(b, False)
+            off, desc = self._layout(b, False, shadow)
             L.check(lib.msig_st_forward_multi(C.byref(desc), C.byref(m), C.byref(s), st), "msig_st_forward_multi")
             got = arena.across("ws", off[L.WS["PRED"]], torch.int32, b)[act[r0:r0 + nr]]      # (folds of the launch, b) copy
             for j in range(nr):
@@ -374,6 +426,7 @@ class LockstepTrainer:
                 sums = self._train_epoch(active)
                 dt = time.time() - t0
                 vals = self._evaluate(active, 1)
+                avg_vals = self._validate_averaged(active)
                 still = []
                 for (vl, va, vf), f in zip(vals, active):
                     t = self.trainers[f]
@@ -381,14 +434,52 @@ class LockstepTrainer:
                         t.model._engine.gather()   # once per epoch, for the checkpoint early stopping may write (best_model.pt)
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
-                    if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f)):
+                    if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f),
+                                           avg_vals.get(f)):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start
+                        self._finish_averaging([f])
                         torch.cuda.current_stream(dev).synchronize()       # its last launches are done before the side stream reads
                         pending[f] = side.submit(finish, f)
                 active = still
             torch.cuda.current_stream(dev).synchronize()
+            self._finish_averaging(active)
+            torch.cuda.current_stream(dev).synchronize()
             for f in active:                                               # ran out of epochs without an early stop
                 pending[f] = side.submit(finish, f)
-            return [pending[f].result() for f in range(self.n)]
+            results = [pending[f].result() for f in range(self.n)]
+        return self._averaged_results(results)
+
+    # ---- weight averaging (config['averaging']) ------------------------------------------------------------------------------------
+    def _validate_averaged(self, active) -> dict:
+        """config['averaging']['validate']: {fold: the three history entries of the epoch's validation pass under the shadow};
+        None values for an SWA fold that has no iterate yet.  Empty without it."""
+        if self.avg_cfg is None or not self.avg_cfg["validate"]:
+            return {}
+        ready = [f for f in active if self.trainers[f].averager.ready]
+        out = {f: dict(val_loss_avg=None, val_acc_avg=None, val_f1_avg=None) for f in active}
+        if ready:
+            for f, (vl, va, vf) in zip(ready, self._evaluate(ready, 1, shadow=True)):
+                out[f] = dict(val_loss_avg=vl, val_acc_avg=va, val_f1_avg=vf)
+        return out
+
+    def _finish_averaging(self, folds):
+        """End of training of `folds`, before their checkpoints are restored: an SWA fold without an iterate takes the weights the
+        last step left as its single one (one launch over those folds)."""
+        if self.avg_cfg is None or not folds:
+            return
+        self._wa_update(list(folds), [self.trainers[f].averager.final_coef() for f in folds])
+
+    def _averaged_results(self, results):
+        """After every fold has finished: bn = "recompute" for all folds of the batch as ONE adapter, then each fold's averaged
+        model — averaged_model.pt, its validation and test passes — into its result (and its fold_result.json)."""
+        if self.avg_cfg is None:
+            return results
+        if self.avg_cfg["bn"] == "recompute":
+            AV.recompute_bn([t.model.engine() for t in self.trainers], [p["loaders"][0] for p in self.preps])
+        for p, t, info in zip(self.preps, self.trainers, results):
+            info["averaging"] = averaged_result(p, t)
+            if p.get("test_pass", True):
+                (p["fold_dir"] / "fold_result.json").write_text(json.dumps(info))
+        return results

@@ -32,7 +32,8 @@ class Engine:
                  kind: str = "cnn_gru_attention"):
         """`storage` (FoldArena.engine): pre-allocated flat tensors "params", "grads", "exp_avg", "exp_avg_sq", "bn_state",
         "bn_count" and a "ws" byte region to use instead of allocating — the buffers of one arena of a fold batch (plus "gc", the
-        arena's clip state, when the arena was built for gradient clipping).  `kind`:
+        arena's clip state, when the arena was built for gradient clipping, and "avg_params", "avg_bn_state", "avg_bn_count", the
+        arena's weight-averaging shadow, when it was built for averaging).  `kind`:
         "cnn_gru_attention" (include/msig.h, msig_cw.h) or "cnn_gru", the baseline without ChannelAttention (include/msig_cg.h:
         its layout and its calls)."""
         if not (1 <= in_channels <= L.MAX_C) or not (2 <= num_classes <= L.MAX_K):
@@ -57,6 +58,10 @@ class Engine:
             self.exp_avg_sq: Optional[torch.Tensor] = None
             self.loss_acc = torch.zeros(2, dtype=torch.float64, device=self.device)      # msig_batch.loss_acc: [sum of CE, #correct] of a pass
             self.gc_state: Optional[torch.Tensor] = None      # include/msig_gc.h clip state (float64), made by the first clipped step
+            # include/msig_wa.h: the weight-averaging shadow (parameters, BatchNorm state and counts), made by ensure_shadow()
+            self.avg_params: Optional[torch.Tensor] = None
+            self.avg_bn_state: Optional[torch.Tensor] = None
+            self.avg_bn_count: Optional[torch.Tensor] = None
         else:
             self.params, self.grads = storage["params"], storage["grads"]
             self.bn_state, self.bn_count = storage["bn_state"], storage["bn_count"]
@@ -66,6 +71,10 @@ class Engine:
             self.gc_state = storage.get("gc")
             if self.gc_state is not None:
                 self.gc_state.zero_()
+            self.avg_params, self.avg_bn_state, self.avg_bn_count = (storage.get(k) for k in ("avg_params", "avg_bn_state", "avg_bn_count"))
+            for t in (self.avg_params, self.avg_bn_state, self.avg_bn_count):
+                if t is not None:
+                    t.zero_()
             for t in (self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.bn_state, self.bn_count, self.loss_acc):
                 t.zero_()
         self.bn_state[16:32] = 1.0
@@ -251,7 +260,7 @@ class Engine:
 
     # ---- calls -------------------------------------------------------------------------
     def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False,
-                class_weight: Optional[torch.Tensor] = None, label_smoothing=0.0, mix_lambda=None) -> L.Batch:
+                class_weight: Optional[torch.Tensor] = None, label_smoothing=0.0, mix_lambda=None, shadow: bool = False) -> L.Batch:
         """model(inputs) [+ criterion]: logits land in region('LOGITS'); returns the descriptor
         that a following backward() must be given.  An eval-mode forward (training=False) takes a backward only with
         keep_for_backward=True: it then keeps the stashes in a workspace of its own, with the same logits.  class_weight: a (K,)
@@ -259,9 +268,18 @@ class Engine:
         (include/msig_cw.h); None = the unweighted criterion.  label_smoothing / mix_lambda: the soft-target criterion of
         include/msig_st.h — CrossEntropyLoss(label_smoothing=eps), and with mix_lambda = lam the loss against the
         row's own label (weight lam) and its partner's, row B-1-b (weight 1 - lam), for an `x` that was mixed the same way
-        (mixup.Mixup.apply, DeviceLoader(mixup=)); 0.0 and None (or 1) = the plain criterion."""
+        (mixup.Mixup.apply, DeviceLoader(mixup=)); 0.0 and None (or 1) = the plain criterion.
+        shadow: an EVAL forward of the weight-averaging shadow (include/msig_wa.h) instead of the model — the same call with
+        msig_batch.params / bn_state / bn_count pointing at it; the model's own buffers are not read."""
         cw, _, eps, lam = self._checked(class_weight, None, label_smoothing, mix_lambda)
-        return self.forward_desc(self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward), cw, eps, lam)
+        if shadow and (training or keep_for_backward):
+            raise ValueError("the weight-averaging shadow takes eval-mode forwards only (training=False, keep_for_backward=False)")
+        b = self._batch(x, labels, training, dropout_p, seed, step, keep_for_backward)
+        if shadow:
+            if self.avg_params is None:
+                raise RuntimeError("this model has no weight-averaging shadow yet: call average_update first")
+            b.params, b.bn_state, b.bn_count = self.avg_params.data_ptr(), self.avg_bn_state.data_ptr(), self.avg_bn_count.data_ptr()
+        return self.forward_desc(b, cw, eps, lam)
 
     def forward_desc(self, b: L.Batch, cw: Optional[int] = None, smoothing: float = 0.0, lam: float = 1.0) -> L.Batch:
         """The forward of an already-built descriptor (`_batch`, possibly with pointers of it replaced: adapt.py, calibrate.py)."""
@@ -323,6 +341,43 @@ class Engine:
         """(loss_acc as a list, grad_stats()) in ONE device-to-host copy: what a trainer reads at the end of a clipped epoch."""
         v = torch.cat([self.loss_acc, self.ensure_gc_state()[:L.GC_NSTAT]]).cpu().tolist()
         return v[:2], self._stats(v[2:])
+
+    # ---- weight averaging (include/msig_wa.h, DESIGN.md §22) ------------------------------------------------------------------
+    def ensure_shadow(self) -> torch.Tensor:
+        """The model's shadow — avg_params, avg_bn_state, avg_bn_count — allocated (zeroed) at first use."""
+        if self.avg_params is None:
+            self.avg_params = torch.zeros_like(self.params)
+            self.avg_bn_state = torch.zeros_like(self.bn_state)
+            self.avg_bn_count = torch.zeros_like(self.bn_count)
+        return self.avg_params
+
+    def average_update(self, a: float) -> None:
+        """One update of the shadow towards the model as it stands, shadow += a * (model - shadow) on every parameter and BatchNorm
+        statistic in three fp32 roundings (msig_wa_update): a = 1 copies the model, a = 0 does nothing (no launch).  The
+        coefficient is the caller's schedule (averaging.ema_coef / swa_coef); a number in [0, 1], else ValueError."""
+        a = L.check_average_coef(a)
+        self.ensure_shadow()
+        w = L.Wa()
+        w.n_flat, w.params, w.bn_state, w.bn_count = self.n_flat, self.params.data_ptr(), self.bn_state.data_ptr(), self.bn_count.data_ptr()
+        w.avg_params, w.avg_bn_state, w.avg_bn_count = self.avg_params.data_ptr(), self.avg_bn_state.data_ptr(), self.avg_bn_count.data_ptr()
+        w.coef[0] = a
+        L.check(L.lib().msig_wa_update(C.byref(w), self._stream()), "msig_wa_update")
+
+    def shadow_named(self) -> Dict[str, torch.Tensor]:
+        """The shadow under the reference's state_dict keys (copies): every parameter tensor of the model kind, then the BatchNorm
+        buffers in the order nn.Module.state_dict lists them."""
+        if self.avg_params is None:
+            raise RuntimeError("this model has no weight-averaging shadow yet: call average_update first")
+        out = {k: v.clone() for k, v in self._shadow_param_views().items()}
+        s, n = self.avg_bn_state, self.avg_bn_count
+        out.update({"cnn_encoder.1.running_mean": s[0:16].clone(), "cnn_encoder.1.running_var": s[16:32].clone(),
+                    "cnn_encoder.1.num_batches_tracked": n[0].clone(),
+                    "cnn_encoder.5.running_mean": s[32:64].clone(), "cnn_encoder.5.running_var": s[64:96].clone(),
+                    "cnn_encoder.5.num_batches_tracked": n[1].clone()})
+        return out
+
+    def _shadow_param_views(self) -> Dict[str, torch.Tensor]:
+        return self.named_param_views(self.avg_params)
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
                    dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
@@ -473,10 +528,21 @@ class EmbeddedEngine(Engine):
 
     # ---- the library calls, with the embedding maintained around them ----
     def forward(self, x, labels=None, training=False, dropout_p=0.0, seed=0, step=0, keep_for_backward=False, class_weight=None,
-                label_smoothing=0.0, mix_lambda=None):
+                label_smoothing=0.0, mix_lambda=None, shadow=False):
         self._checked(class_weight, None, label_smoothing, mix_lambda)      # before the scatter: nothing runs on a bad argument
         self.scatter()
-        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight, label_smoothing, mix_lambda)
+        return super().forward(x, labels, training, dropout_p, seed, step, keep_for_backward, class_weight, label_smoothing, mix_lambda, shadow)
+
+    def average_update(self, a: float) -> None:
+        """The shadow lives in the PADDED layout, like the buffers the library trains: the padding of a shadow that began as zeros
+        or as a copy stays exactly +0.0 under the update (0 + a * (0 - 0) is exact).  shadow_named() gathers it to the
+        reference-shaped tensors."""
+        L.check_average_coef(a)
+        self.scatter()
+        super().average_update(a)
+
+    def _shadow_param_views(self):
+        return self.small_views(self.avg_params.index_select(0, self.index))
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
                    max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None):
@@ -513,7 +579,7 @@ class FoldArena:
 
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
                  adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
-                 grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None):
+                 grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None, averaging: bool = False):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
@@ -522,7 +588,11 @@ class FoldArena:
         without it the arenas and their stride are what they are without this argument.
         `adversary` = (S, store positions): every fold also gets the buffers of a subject discriminator of S domains (include/
         msig_da.h) — parameters, both Adam moments, statistics and an int32 domain table — in a memory block of their own,
-        `da_stride` bytes apart (`adversary_storage`); the model arenas and their stride stay what they are without it."""
+        `da_stride` bytes apart (`adversary_storage`); the model arenas and their stride stay what they are without it.
+        `averaging`: the arenas also hold every fold's weight-averaging shadow (include/msig_wa.h) — "avg_params", "avg_bn_state",
+        "avg_bn_count" — after every other region, "gc" included: INSIDE the arenas, at the arena stride, because that is the only
+        place the *_multi forward can read an averaged model from (`batch(..., shadow=True)`).  Without it the arenas and their
+        stride are what they are without this argument."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -544,6 +614,9 @@ class FoldArena:
         self.grad_clip = bool(grad_clip)
         if self.grad_clip:
             sizes.append(("gc", L.gc_state_bytes(in_channels, num_classes, kind)))
+        self.averaging = bool(averaging)
+        if self.averaging:
+            sizes += [("avg_params", self.n_flat * 4), ("avg_bn_state", L.BN_STATE_FLOATS * 4), ("avg_bn_count", 16)]
         self.max_norm = [float("inf")] * n              # per arena: max_norm of the fold in it (set_max_norm); inf = measured, not clipped
         self.off, at = {}, 0
         for name, nbytes in sizes:
@@ -591,6 +664,9 @@ class FoldArena:
         st["ws"] = self.view(slot, "ws")
         if self.grad_clip:
             st["gc"] = self.view(slot, "gc", torch.float64)
+        if self.averaging:
+            st["avg_params"], st["avg_bn_state"] = self.view(slot, "avg_params", torch.float32), self.view(slot, "avg_bn_state", torch.float32)
+            st["avg_bn_count"] = self.view(slot, "avg_bn_count", torch.int64)
         if self.gru_layers == 1:
             return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st, kind=self.kind)
         return Engine(self.C, self.K, self.device, storage=st, kind=self.kind)
@@ -647,6 +723,20 @@ class FoldArena:
             g.max_norm[i] = self.max_norm[int(s)]
         return g
 
+    def wa(self, slots, coefs) -> L.Wa:
+        """msig_wa of a launch over `slots` (msig_wa_update_multi, include/msig_wa.h): arena 0's model and shadow buffers and the
+        coefficient of every fold of the launch (checked on the host: ValueError before anything is launched)."""
+        if not self.averaging:
+            raise RuntimeError("this FoldArena was built without averaging=True: it has no shadow regions")
+        if len(coefs) != len(slots):
+            raise ValueError(f"{len(slots)} folds need {len(slots)} coefficients, got {len(coefs)}")
+        w = L.Wa()
+        w.n_flat, w.params, w.bn_state, w.bn_count = self.n_flat, self.ptr("params"), self.ptr("bn_state"), self.ptr("bn_count")
+        w.avg_params, w.avg_bn_state, w.avg_bn_count = self.ptr("avg_params"), self.ptr("avg_bn_state"), self.ptr("avg_bn_count")
+        for i, a in enumerate(coefs):
+            w.coef[i] = L.check_average_coef(a)
+        return w
+
     def soft(self, slots, smoothing: float, lams=None, class_weight: Optional[int] = None, clip: Optional[L.GcClip] = None) -> L.St:
         """msig_st of a launch over `slots` (msig_st_*_multi, include/msig_st.h): the launch's label smoothing, lam per fold of the
         launch (None: 1 everywhere — evaluation never mixes), ptr("cw") or None, and the launch's clip (`clip(slots)`) or None.
@@ -667,8 +757,11 @@ class FoldArena:
         """Gradient-norm statistics of the fold in arena `slot` since zero_grad_stats (Engine.grad_stats; one read-back)."""
         return Engine._stats(self.view(slot, "gc", torch.float64)[:L.GC_NSTAT].cpu().tolist())
 
-    def batch(self, B: int, training: bool, dropout_p: float, with_labels: bool = True) -> L.Batch:
-        """msig_batch describing arena 0 (the *_multi calls shift every pointer by slot * stride)."""
+    def batch(self, B: int, training: bool, dropout_p: float, with_labels: bool = True, shadow: bool = False) -> L.Batch:
+        """msig_batch describing arena 0 (the *_multi calls shift every pointer by slot * stride).  shadow: the eval descriptor that
+        reads every fold's weight-averaging shadow instead of its model (params / bn_state / bn_count point at the "avg_*" regions)."""
+        if shadow and (training or not self.averaging):
+            raise ValueError("a shadow descriptor is an eval descriptor of a FoldArena built with averaging=True")
         if B > (self.max_train_batch if training else self.max_batch):
             raise ValueError(f"batch {B} exceeds the arena's {self.max_train_batch if training else self.max_batch}")
         b = L.Batch()
@@ -680,6 +773,8 @@ class FoldArena:
         b.x, b.labels = self.ptr("x"), (self.ptr("y") if with_labels else None)
         b.params, b.grads = self.ptr("params"), self.ptr("grads")
         b.bn_state, b.bn_count = self.ptr("bn_state"), self.ptr("bn_count")
+        if shadow:
+            b.params, b.bn_state, b.bn_count = self.ptr("avg_params"), self.ptr("avg_bn_state"), self.ptr("avg_bn_count")
         b.ws, b.ws_bytes = self.ptr("ws"), self.ws_bytes
         b.loss_acc = self.ptr("acc")
         b.gru_layers = self.gru_layers

@@ -25,6 +25,8 @@ losses alike (include/msig_st.h); a training loader built with `
 ``config['adversary']`` (None or a dict of lam / schedule / gamma / lr_mult / seed) trains a subject discriminator on the feature
 inside every TRAINING step and reverses its gradient into the extractor (include/msig_da.h); validation and test
 never run it; ``history`` and the log gain the epoch's domain loss, domain accuracy and lambda.
+``config['averaging']`` (None or a dict with a mode, ``averaging.settings``) keeps an EMA or SWA shadow of the weights — one more launch
+after every train step (EMA) or at the end of an epoch (SWA); it steers nothing (include/msig_wa.h).
 """
 from __future__ import annotations
 
@@ -39,6 +41,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from . import _lib as L
 from . import adversary as A
+from . import averaging as AV
 from .models import CnnGruAttentionModel
 
 
@@ -188,6 +191,9 @@ class Trainer:
         # subject-adversarial training (include/msig_da.h): the settings now, the discriminator when the training set is known
         self.adversary_cfg = A.settings(config.get("adversary"))
         self.adversary = None
+        # weight averaging (include/msig_wa.h): the fold's averager (settings and counters); the shadow itself is the engine's
+        self.averaging_cfg = AV.settings(config.get("averaging"))
+        self.averager = AV.WeightAverager(self.averaging_cfg) if self.averaging_cfg is not None else None
         self.verbose = cfg.get("verbose", True)
         self.optimizer = MsigAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)   # trainer.py:68
         self.scheduler = ReduceLROnPlateau(self.optimizer, mode="min", factor=0.1, patience=3)         # trainer.py:72-77
@@ -273,6 +279,9 @@ class Trainer:
         self._check_labels(val_loader)
         self.prepare_class_weights(train_loader)
         adv = self.prepare_adversary(train_loader)
+        av = self.averager
+        if av is not None:
+            eng.average_update(av.bind(eng).start_coef())      # EMA: the shadow starts as a copy of the initial model; SWA: no launch
         n_train = len(train_loader.dataset)
         for epoch in range(self.epochs):
             t0 = time.time()
@@ -293,6 +302,8 @@ class Trainer:
                                class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
                                mix_lambda=getattr(train_loader, "last_lam", None),      # the lam of the batch a mixup loader just served
                                adversary=adv, batch_index=getattr(train_loader, "last_index", None) if adv is not None else None)
+                if av is not None and av.mode == "ema":
+                    eng.average_update(av.step_coef())
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
             if self.max_grad_norm is None:
                 train_loss, grad = float(eng.loss_acc[0].item()) / n_train, None         # the epoch's only sync
@@ -303,15 +314,40 @@ class Trainer:
             dt = time.time() - t0
             self.train_windows += n_train
             self.train_seconds += dt
+            if av is not None and av.mode == "swa":
+                eng.average_update(av.epoch_coef(epoch + 1))     # the epoch-end iterate, from start_epoch on (before: no launch)
             val_loss, val_acc, val_f1, _, _ = self.evaluate(val_loader, is_val=True)
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom):
+            avg = self.validate_averaged(val_loader) if av is not None and av.validate else None
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg):
                 break
+        self.finish_averaging([train_loader])
         self._finish_training()
 
-    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None) -> bool:
+    def validate_averaged(self, val_loader) -> dict:
+        """config['averaging']['validate']: the epoch's validation pass once more under the shadow — its own accumulator zeroing and
+        read-back — as the three history entries; None values while an SWA shadow has no iterate yet."""
+        if not self.averager.ready:
+            return dict(val_loss_avg=None, val_acc_avg=None, val_f1_avg=None)
+        loss, acc, f1 = self.evaluate_averaged(val_loader)
+        return dict(val_loss_avg=loss, val_acc_avg=acc, val_f1_avg=f1)
+
+    def finish_averaging(self, train_loaders, recompute=True):
+        """End of training, BEFORE the early-stopping checkpoint is restored: an SWA fold without an iterate takes the weights the
+        last step left as its single one; bn = "recompute" re-estimates the shadow's BatchNorm statistics on the training windows
+        (recompute False: the caller does that for a whole fold batch with one adapter)."""
+        av = self.averager
+        if av is None or av.finished:
+            return
+        eng = self.model.engine()
+        eng.average_update(av.bind(eng).final_coef())
+        if recompute and av.bn == "recompute":
+            AV.recompute_bn([eng], train_loaders)
+
+    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None) -> bool:
         """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
         the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were.
-        dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise."""
+        dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise.  avg: the validation pass under
+        the averaging shadow when config['averaging']['validate'] is set (three more history keys; it steers nothing)."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
@@ -323,6 +359,10 @@ class Trainer:
         if dom is not None:
             self.history[-1].update(dom)
             suffix += f" | domain loss: {dom['domain_loss']:.4f} | domain acc: {dom['domain_acc']:.4f} | lambda: {dom['adversary_lambda']:.4f}"
+        if avg is not None:
+            self.history[-1].update(avg)
+            if avg["val_loss_avg"] is not None:
+                suffix += f" | averaged: val loss {avg['val_loss_avg']:.4f} acc {avg['val_acc_avg']:.4f} F1 {avg['val_f1_avg']:.4f}"
         self._log(f"Epoch {epoch + 1}/{self.epochs} | 耗时: {dt:.2f}s | 训练损失: {train_loss:.4f} | 验证损失: {val_loss:.4f} | "
                   f"验证Acc: {val_acc:.4f} | 验证F1: {val_f1:.4f} | {n_train / max(dt, 1e-9):.0f} windows/s" + suffix)
         if self.early_stopping:
@@ -339,7 +379,8 @@ class Trainer:
         self._log(f"--- 训练完成 --- 总训练时长: {time.time() - self.total_start_time:.2f}秒")
 
     # ---- trainer.py:193-247 -------------------------------------------------------------------
-    def evaluate(self, data_loader, is_test=False, is_val=False):
+    def _eval_pass(self, data_loader, shadow=False):
+        """One eval-mode pass over a loader: (loss, predictions, labels).  shadow: under the weight-averaging shadow."""
         eng = self.model.engine()
         self._check_labels(data_loader)
         self.model.eval()
@@ -347,12 +388,22 @@ class Trainer:
         preds, labs = [], []
         for inputs, labels in data_loader:
             x, y = self._to_device(inputs, labels)
-            eng.forward(x, y, training=False, class_weight=self.class_weight, label_smoothing=self.label_smoothing)   # the loss kernel adds loss * batch to eng.loss_acc (trainer.py:221)
+            eng.forward(x, y, training=False, class_weight=self.class_weight, label_smoothing=self.label_smoothing, shadow=shadow)   # the loss kernel adds loss * batch to eng.loss_acc (trainer.py:221)
             preds.append(eng.region("PRED", torch.int32, (y.shape[0],)).clone())
             labs.append(y.clone())          # DeviceLoader reuses its batch buffers
         all_preds = torch.cat(preds).cpu().numpy().astype(np.int64)
         all_labels = torch.cat(labs).cpu().numpy().astype(np.int64)
         loss = float(eng.loss_acc[0].item()) / len(data_loader.dataset)
+        return loss, all_preds, all_labels
+
+    def evaluate_averaged(self, data_loader):
+        """(loss, acc, f1) of the averaged model — the shadow — on a loader: the same eval forward with the descriptor pointing at
+        the shadow.  No plot, no log line; the model is not touched."""
+        loss, all_preds, all_labels = self._eval_pass(data_loader, shadow=True)
+        return (loss,) + accuracy_and_weighted_f1(all_labels, all_preds)
+
+    def evaluate(self, data_loader, is_test=False, is_val=False):
+        loss, all_preds, all_labels = self._eval_pass(data_loader)
         acc, f1 = accuracy_and_weighted_f1(all_labels, all_preds)
         if is_test:
             self.plot_confusion_matrix(all_labels, all_preds, filename="test_confusion_matrix.png")
