@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -101,6 +101,8 @@ MC_KINDS = {"cnn_gru_attention": 0, "cnn_gru": 1}      # MSIG_MC_KIND_*
 DA_ABI_VERSION = 1    # include/msig_da.h MSIG_DA_ABI_VERSION (subject-adversarial training: the discriminator's step)
 DA_MAX_BATCH = 256    # msig_da.h MSIG_DA_MAX_BATCH: rows of one discriminator step
 WA_ABI_VERSION = 1    # include/msig_wa.h MSIG_WA_ABI_VERSION (weight averaging: the shadow's update)
+EN_ABI_VERSION = 1    # include/msig_en.h MSIG_EN_ABI_VERSION (deep ensembles: the reduction of the members' logits)
+EN_MAX_MEMBERS = 256  # msig_en.h MSIG_EN_MAX_MEMBERS: members of one ensemble
 
 
 class Multi(C.Structure):
@@ -362,6 +364,12 @@ def lib() -> C.CDLL:
                                f"this binding is {WA_ABI_VERSION} with {C.sizeof(Wa)}: rebuild the library")
         L.msig_wa_update.argtypes = [C.POINTER(Wa), vp]
         L.msig_wa_update_multi.argtypes = [C.POINTER(Wa), C.POINTER(Multi), vp]
+        # include/msig_en.h, exported by the same library: the reduction of ensemble members' logits
+        L.msig_en_abi_version.restype = C.c_int
+        if L.msig_en_abi_version() != EN_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_en.h ABI {L.msig_en_abi_version()}; this binding is {EN_ABI_VERSION}: rebuild the library")
+        L.msig_en_reduce.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.msig_en_reduce_multi.argtypes = [vp, C.POINTER(Multi), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -33,6 +33,7 @@ from .mixup import Mixup
 from . import adversary as adversary_mod
 from . import averaging as averaging_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset
+from . import ensemble as ensemble_mod
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
 from .multifold import averaged_result, fold_result, lockstep_compatible
@@ -161,13 +162,15 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
 
 
 def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
-    """The unit of fold `fold_idx` of the simple experiment (make_unit): seed SEED + fold index, `cache` a SubjectStore (one
-    HBM-resident store for the whole run) or the host cache of WesadDataset."""
+    """The unit of fold `fold_idx` of the simple experiment (make_unit): seed SEED + fold index — seed replica cfg["replica"] of a
+    --seeds run: ensemble.replica_seed, the split stays SEED's — `cache` a SubjectStore (one HBM-resident store for the whole run) or
+    the host cache of WesadDataset."""
     datasets = cache.view if isinstance(cache, SubjectStore) else host_datasets(cfg, all_channel_names, cache, cfg["channels"], cfg["mode"])
     # cfg["shuffle"] = False: training batches in dataset order (with dropout 0 the run is deterministic up to rounding — the
     # setting tests/test_accuracy_parity_gpu.py compares fold by fold with the reference's CPU run); default as main.py:112
     return make_unit(fold_idx, subject_to_test, Path(run_output_dir) / f"fold_test_on_{subject_to_test}", datasets, len(cfg["channels"]),
-                     cfg["num_classes"], cfg["model_params"], cfg["seed"] + fold_idx, cfg, device, shuffle=bool(cfg.get("shuffle", True)))
+                     cfg["num_classes"], cfg["model_params"], ensemble_mod.replica_seed(cfg["seed"], fold_idx, cfg.get("replica", 0)), cfg, device,
+                     shuffle=bool(cfg.get("shuffle", True)))
 
 
 def train_fold(prep, device):
@@ -386,6 +389,42 @@ def uncertainty_units(kept, units, cfgs, device, rank=0):
     return done
 
 
+def ensemble_units(members, local, epochs, units, cfgs, seeds, rank=0):
+    """The deep ensembles of a --seeds run (ensemble.fold_ensemble): per (configuration, fold) of the rank, its `seeds` replicas' models
+    — the ones their test passes evaluated — on the TEST subject's windows.  Unit u * seeds + r is replica r of base unit u
+    (ensemble.deal_replicas).  The models, best_model.pt, fold_result.json and the LOSO summary are untouched; replica 0's fold
+    directory gets ensemble_result.json, which also records the members' test-pass metrics and stop epochs."""
+    for u0 in sorted(u for u in members if u % seeds == 0):
+        us = [u0 + r for r in range(seeds)]
+        n, k = units[u0]
+        p = members[u0]
+        loader = p["loaders"][2]
+        pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=loader.store.device)
+        x, y = loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+        t0 = time.time()
+        r = ensemble_mod.fold_ensemble([members[u]["model"] for u in us], x, y, eval_batch=loader.batch_size)
+        r = dict(subject=p["subject"], fold=k, seeds=[ensemble_mod.replica_seed(cfgs[n]["seed"], k, i) for i in range(seeds)],
+                 member_accuracy=[local[u][0] for u in us], member_f1=[local[u][1] for u in us], epochs=[epochs[u] for u in us],
+                 seconds=time.time() - t0, **r)
+        (p["fold_dir"] / "ensemble_result.json").write_text(json.dumps(r))
+        tag = f"{n}/" if n else ""
+        print(f"[rank {rank}] {tag}fold {k} ({p['subject']}) ensemble of {seeds} seeds over {r['n']} windows: members "
+              + " ".join(f"{a:.4f}" for a in r["member_accuracy"])
+              + f" | ensemble acc {r['ensemble']['accuracy']:.4f} f1 {r['ensemble']['f1_score']:.4f} | disagreement "
+              f"{r['ensemble']['mean_disagreement']:.4f}", flush=True)
+
+
+def write_seed_tables(run_output_dir, base, out_dir, results, seeds):
+    """seeds.txt / seeds.json of a --seeds run, from the gathered per-replica results and the folds' ensemble_result.json, which
+    every rank has written before the fold metrics were gathered."""
+    tables = {}
+    for n, cfg in base.items():
+        per = {m: [[r[m] for r in results[ensemble_mod.replica_name(n, i)]] for i in range(seeds)] for m in ("accuracy", "f1_score")}
+        files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "ensemble_result.json" for r in results[n]]
+        tables[n] = ensemble_mod.summarise_seeds([json.loads(f.read_text()) for f in files], per)
+    return ensemble_mod.write_seeds(run_output_dir, tables, seeds, synthetic=bool(next(iter(base.values())).get("synthetic")))
+
+
 def _warm_imports():
     try:
         import matplotlib
@@ -525,26 +564,41 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     # Optimizer pulled in — 0.9 s that still ended up in front of the first train step; trainer.MsigAdam no longer triggers it.)
     warm = threading.Thread(target=_warm_imports, daemon=True)
     warm.start()
+    # --seeds S (cfg["seeds"] > 1): every (configuration, fold) trains S seed replicas.  Replica r of configuration n is one more
+    # configuration, ensemble.replica_name(n, r) — r = 0 the configuration itself, r >= 1 writing to its seed_<r>/ — that shares the
+    # SubjectStore; a rank holds all replicas of the folds it holds.  base: the configurations as given (absent or 1: all of this is off)
+    S, base = int(cfg0.get("seeds") or 1), cfgs
+    if S > 1:
+        cfgs = {ensemble_mod.replica_name(n, r): dict(c, replica=r) for n, c in base.items() for r in range(S)}
     stores = subject_stores(cfgs, all_channel_names, device)
     t_data = time.time() - t0
-    units, mine, groups = rank_units(cfgs, world, rank)
+    units, mine, groups = rank_units(base, world, rank)
+    if S > 1:
+        units, mine, groups = ensemble_mod.deal_replicas(units, mine, S)
     out_dir = {n: (Path(run_output_dir) / n if n else Path(run_output_dir)) for n in cfgs}
     n_cal = int(cfg0.get("calibrate") or 0)          # --calibrate: windows per class of the test subject; 0 = off
     adapt = cfg0.get("adapt_bn") is not None         # --adapt-bn: label-free BatchNorm adaptation to the test subject; absent = off
     attr = cfg0.get("attribute") is not None         # --attribute: integrated-gradients attribution on the test subject; absent = off
     mc = cfg0.get("mc_dropout") is not None          # --mc-dropout: Monte-Carlo dropout uncertainty on the test subject; absent = off
     kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration / adaptation after the folds; -> its metrics
+    members, epochs = {}, {}                         # --seeds: every unit's prep, for the ensembles after the folds; its stop epoch
 
     def make(u):
         n, k = units[u]
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
-        if n_cal or adapt or attr or mc:
+        if (n_cal or adapt or attr or mc) and not cfgs[n].get("replica"):      # the post-LOSO passes run on replica 0 only
             kept[u] = p
+        if S > 1:
+            members[u] = p
         return p
 
-    for u, info in train_units(mine, groups, make, cfg0, device):
+    # the replicas are what fills the chip: S times the folds are resident (a sweep is one window whatever the width)
+    conc = int(cfg0.get("concurrent_folds", 1))      # 1 stays 1: sequential training, unit by unit
+    train_cfg = dict(cfg0, concurrent_folds=conc * S) if S > 1 and conc > 1 else cfg0
+    for u, info in train_units(mine, groups, make, train_cfg, device):
         n, k = units[u]
         local[u] = (info["accuracy"], info["f1_score"])
+        epochs[u] = info["epochs"]
         print(f"[rank {rank}] {n + '/' if n else ''}fold {k} ({cfgs[n]['subjects'][k]}): acc {info['accuracy']:.4f} f1 {info['f1_score']:.4f} "
               f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
     cal_local = calibrate_units(kept, units, cfgs, device, rank) if n_cal and kept else {}
@@ -556,7 +610,11 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     # emulate_rank (bench.py --emulate-ranks): this process plays rank `rank` of a `world`-GPU job ALONE on its GPU — exactly what
     # that rank executes on an 8-GPU node, less the one ~100-byte all_gather of the fold metrics
     emulate, gdev = cfg0.get("emulate_rank"), cfg0.get("gather_device", device)
-    allm = dict(local) if emulate else gather_fold_metrics(local, len(units), world, gdev)
+    if S > 1:                                        # each fold's S test-pass models as an ensemble on its test subject, before the gather
+        ensemble_units(members, local, epochs, units, cfgs, S, rank)
+    # a rank holds ceil(folds / world) folds with all their replicas: the gather's rows per rank are sized for that
+    n_rows = len(units) if S == 1 else -(-(len(units) // S) // world) * S * world
+    allm = dict(local) if emulate else gather_fold_metrics(local, n_rows, world, gdev)
     wall = time.time() - t0
     cal_all = None
     if n_cal and emulate:     # after the LOSO wall-clock is taken: the summary's timing line is the LOSO's
@@ -575,6 +633,12 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     for u in sorted(allm):
         n, k = units[u]
         results[n].append({"subject": cfgs[n]["subjects"][k], "accuracy": allm[u][0], "f1_score": allm[u][1]})
+    if S > 1:                                        # replica 0 is the run: its summaries are those of a run without --seeds
+        if rank == 0 or emulate:
+            path = write_seed_tables(run_output_dir, base, out_dir, results, S)
+            print(f"Seed-replica and ensemble table written to: {path}")
+        results = {n: results[n] for n in base}
+        cfgs = base
     if rank == 0 or emulate:
         write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr, uncertain=mc)
     return results, wall
@@ -852,6 +916,12 @@ def parse_args(ap, argv=None):
     elif args.mc_seed is not None:
         ap.error("--mc-seed needs --mc-dropout")
     try:
+        args.seeds = ensemble_mod.check_seeds(args.seeds)
+    except ValueError as e:
+        ap.error(f"--seeds: {e}")
+    if args.seeds > 1 and args.hierarchical:
+        ap.error("--seeds runs with the standard LOSO, --model, --ablation and --sweep (not --hierarchical)")
+    try:
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
         ap.error(f"--max-grad-norm: {e}")
@@ -1011,6 +1081,14 @@ def build_parser():
                          "LOSO and --model comparison runs; may be combined with --calibrate, --adapt-bn and --attribute, each on its own "
                          "against the LOSO model)")
     ap.add_argument("--mc-seed", type=int, default=None, metavar="SEED", help="seed of the Monte-Carlo dropout masks (default 0)")
+    ap.add_argument("--seeds", type=int, default=1, metavar="S",
+                    help="train S seed replicas (1..64) of every fold as fold-batch units: the same train / validation split, unit seed "
+                         "SEED + fold + r * 1000003 for replica r (initialisation, shuffle order, dropout, augmentation and mixup draws). "
+                         "Replica 0 is the run without the flag and writes its files; replica r >= 1 writes under seed_<r>/.  After "
+                         "training each fold's replicas are evaluated on its test subject as a deep ensemble (ensemble_result.json), "
+                         "and seeds.txt / seeds.json hold the LOSO means per seed with their spread, the ensemble and mean-member rows "
+                         "and, with several configurations, the paired differences over seeds.  Every training-time option applies to "
+                         "all replicas; --calibrate, --adapt-bn, --attribute and --mc-dropout act on replica 0 (not with --hierarchical)")
     return ap
 
 
@@ -1050,6 +1128,8 @@ def build_cfg(args, kinds):
             cfg["attribute_bin"] = args.attribute_bin
     if args.mc_dropout is not None:    # likewise
         cfg.update(mc_dropout=args.mc_dropout, mc_seed=args.mc_seed, synthetic=args.synthetic is not None)
+    if args.seeds > 1:                 # likewise: --seeds 1 is the run without the flag
+        cfg.update(seeds=args.seeds, synthetic=args.synthetic is not None)
     return cfg
 
 
