@@ -489,7 +489,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
       double var = red[CH + tid] / count - mean * mean;
       if (var < 0.0) var = 0.0;
       const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-      const float sc = gamma[tid] * invstd;
+      const float sc = (msig_negctl_regime == 3 ? fabsf(gamma[tid]) : gamma[tid]) * invstd;
       stat[tid] = (float)mean;
       stat[CH + tid] = invstd;
       stat[2 * CH + tid] = sc;
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
     if (tid == 0) nbt[0] += 1;
   } else if (tid < CH) {
     const float invstd = 1.0f / sqrtf(run_var[tid] + eps);
-    const float sc = gamma[tid] * invstd;
+    const float sc = (msig_negctl_regime == 3 ? fabsf(gamma[tid]) : gamma[tid]) * invstd;
     stat[tid] = run_mean[tid];
     stat[CH + tid] = invstd;
     stat[2 * CH + tid] = sc;

@@ -319,7 +319,7 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
         if constexpr (S == 0) { hpv[e] = f4e<e>(L.hp4) * L.hkeep; PINV(hpv[e]); }                         // h_{-1} = 0
         if constexpr (S == 1) { t0[e] = 1.0f - z_; PINV(t0[e]); }                                        // omz
         if constexpr (S == 2) { t1[e] = __builtin_fmaf(-z_, hpv[e], hc_); PINV(t1[e]); }                 // h_t - z h_{t-1}
-        if constexpr (S == 3) { t2[e] = __builtin_fmaxf(t0[e], 1e-30f); PINV(t2[e]); }
+        if constexpr (S == 3) { t2[e] = msig_negctl_regime == 1 ? t0[e] : __builtin_fmaxf(t0[e], 1e-30f); PINV(t2[e]); }
         if constexpr (S == 4) { t2[e] = __builtin_amdgcn_rcpf(t2[e]); PINV(t2[e]); }
         if constexpr (S == 5) { t3[e] = 1.0f - r_; PINV(t3[e]); }
         if constexpr (S == 6) { t3[e] = r_ * t3[e]; PINV(t3[e]); }

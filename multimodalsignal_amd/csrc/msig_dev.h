@@ -85,6 +85,17 @@ template <int KIND> constexpr bool msig_drop_ct() { return MSIG_DROP_CROSS_TERM 
 #else
 template <int KIND> constexpr bool msig_drop_ct() { return false; }
 #endif
+// Negative controls of the trained-like regimes (make negctl REGIME=k; never defined in the product library): one-line slips that
+// no test near initialisation can see (tests/test_trained_regimes_gpu.py must FAIL against each; tools/negative_controls.sh regime).
+//   1  gru_n_from_h and its inlined copies in gru_bwd4.hip / gru_bwd6.hip without the 1e-30 floor under 1 - z
+//   2  the sigmoid of gru_gates and sigmoidf_fast as e^x / (1 + e^x): inf / inf from x = 88.7 on
+//   3  bn_finalize_kernel's scale from |gamma|
+//   4  the head's log-sum-exp (ce_row_lse) without subtracting the row maximum
+#ifdef MSIG_NEGCTL_REGIME
+constexpr int msig_negctl_regime = MSIG_NEGCTL_REGIME;
+#else
+constexpr int msig_negctl_regime = 0;
+#endif
 // acc += A . B over one 32-wide k block, A and B given as their three pieces ([0] = leading piece)
 template <int KIND = CT_ANY>
 __device__ __forceinline__ f32x4 mfma_bf16x3(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {
@@ -156,7 +167,10 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // v_exp_f32 / v_rcp_f32 based (1 ulp each): abs error ~1e-7, far inside the parity tolerance
-__device__ __forceinline__ float sigmoidf_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float sigmoidf_fast(float x) {
+  if constexpr (msig_negctl_regime == 2) { const float ex = __expf(x); return ex * __builtin_amdgcn_rcpf(1.0f + ex); }
+  return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+}
 __device__ __forceinline__ float tanhf_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 // The GRU gate math of one lane (4 elements), written on 4-vectors so that the non-transcendental half compiles to
 // packed fp32 instructions (v_pk_mul/add/fma_f32: two elements per issue slot) — VALU time adds to MFMA time on this
@@ -165,12 +179,20 @@ __device__ __forceinline__ float tanhf_fast(float x) { return 1.0f - 2.0f * __bu
 __device__ __forceinline__ void gru_gates(const f32x4& a_r, const f32x4& a_z, const f32x4& a_in, const f32x4& a_hn, const f32x4& h,
                                           f32x4& r, f32x4& z, f32x4& n, f32x4& hnew) {
   constexpr float L2E = 1.4426950408889634f;
-  f32x4 er = a_r * (-L2E), ez = a_z * (-L2E);
+  if constexpr (msig_negctl_regime == 2) {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) { er[e] = __builtin_amdgcn_exp2f(er[e]); ez[e] = __builtin_amdgcn_exp2f(ez[e]); }
-  er = er + 1.0f; ez = ez + 1.0f;
+    for (int e = 0; e < 4; ++e) {
+      const float pr = __builtin_amdgcn_exp2f(a_r[e] * L2E), pz = __builtin_amdgcn_exp2f(a_z[e] * L2E);
+      r[e] = pr * __builtin_amdgcn_rcpf(pr + 1.0f); z[e] = pz * __builtin_amdgcn_rcpf(pz + 1.0f);
+    }
+  } else {
+    f32x4 er = a_r * (-L2E), ez = a_z * (-L2E);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = __builtin_amdgcn_rcpf(er[e]); z[e] = __builtin_amdgcn_rcpf(ez[e]); }
+    for (int e = 0; e < 4; ++e) { er[e] = __builtin_amdgcn_exp2f(er[e]); ez[e] = __builtin_amdgcn_exp2f(ez[e]); }
+    er = er + 1.0f; ez = ez + 1.0f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { r[e] = __builtin_amdgcn_rcpf(er[e]); z[e] = __builtin_amdgcn_rcpf(ez[e]); }
+  }
   f32x4 t = (a_in + r * a_hn) * (2.0f * L2E);
 #pragma unroll
   for (int e = 0; e < 4; ++e) t[e] = __builtin_amdgcn_exp2f(t[e]);
@@ -190,6 +212,7 @@ __device__ __forceinline__ void gru_gates(const f32x4& a_r, const f32x4& a_z, co
 // the clamp bounds it by (1 - z) |dh| where the quotient is noise, and z = 1 exactly (1 - z = 0) gives 0 * finite = 0, as it should.
 __device__ __forceinline__ float gru_n_from_h(float h_new, float h_prev, float z, float one_minus_z) {
   const float num = __builtin_fmaf(-z, h_prev, h_new);
+  if constexpr (msig_negctl_regime == 1) return __builtin_amdgcn_fmed3f(num * __builtin_amdgcn_rcpf(one_minus_z), -1.0f, 1.0f);
   return __builtin_amdgcn_fmed3f(num * __builtin_amdgcn_rcpf(__builtin_fmaxf(one_minus_z, 1e-30f)), -1.0f, 1.0f);
 }
 
@@ -221,6 +244,10 @@ __device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
   float mx = lg[0]; am = 0;
   for (int c = 1; c < K; ++c) if (lg[c] > mx) { mx = lg[c]; am = c; }
   float se = 0.f;
+  if constexpr (msig_negctl_regime == 4) {
+    for (int c = 0; c < K; ++c) se += expf(lg[c]);
+    return logf(se);
+  }
   for (int c = 0; c < K; ++c) se += expf(lg[c] - mx);
   return mx + logf(se);
 }

@@ -190,7 +190,7 @@ def relu_maxpool(z, choice=None):
     ``choice`` (B,C,Lout) in {0,1,2}, when given, replaces the argmax: the window's output is the chosen candidate.
     The parity tests use it for the one thing no two fp32 implementations can agree on — which of two candidates that
     are equal to within fp32 resolution is "the" maximum (tests/gpu_common.py: only such near-ties are ever overridden)."""
-    win = pool_windows(torch.clamp_min(z, 0))
+    win = pool_windows(torch.relu(z))              # nn.ReLU: no gradient at z == 0 exactly (clamp_min would pass it on)
     if choice is None:
         return win.max(dim=3).values
     return win.gather(3, choice.to(torch.int64)[..., None]).squeeze(3)

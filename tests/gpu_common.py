@@ -31,6 +31,9 @@ from oracle import cnn_gru_oracle as O
 # 20-40 x the worst observed error: a regression confined to ONE contraction passed them.
 # Negative controls (make negctl NEGCTL=1..5,9: the split-bf16 product without its a1 * b1 cross term — 2^-16 relative per
 # product — in one class of contractions; tools/negative_controls.sh, profiles/r04_negative_control.log): each of them FAILS.
+# The same table over TRAINED-LIKE parameters (saturated gates, signed / zero BatchNorm gamma, saturated logits: tests/regimes.py,
+# tests/test_trained_regimes_gpu.py, held to these constants unchanged) is in DESIGN.md section 2, "Trained-like regimes"; its
+# negative controls (make negctl REGIME=k) in profiles/regime_negative_control.log.
 K_STAGE, STAGE_FLOOR = 8.0, 2e-6
 K_GRAD = 6.0
 GRAD_FLOORS = (("gru.", 3e-6), ("classifier.3.bias", 1.2e-5), ("", 6e-6))      # first matching prefix

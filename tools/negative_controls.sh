@@ -5,6 +5,51 @@
 # (2^-16 relative per product), two-piece fp16 without a1 * b0 (2^-11).  1 backward recurrence, 2 dX, 3 dW, 4 forward recurrence,
 # 5 forward projection, 9 all of them.  Every selected case must FAIL against every control and PASS against the product library;
 # the script prints per-case verdicts and EXITS NON-ZERO when a control passes a case or the product fails one.
+# tools/negative_controls.sh regime [OUT] [LIBRARY ...]: the controls of the TRAINED-LIKE regimes instead (libraries built by
+#   for k in 1 2 3 4; do make -C multimodalsignal_amd/csrc negctl REGIME=$k; done ).  Each is one slip that is invisible near
+# initialisation (msig_dev.h MSIG_NEGCTL_REGIME): 1 the recovery of n without its floor, 2 sigmoid as e^x / (1 + e^x), 3 BatchNorm's
+# scale from |gamma|, 4 log-sum-exp without the row maximum.  Per library: one pass of tests/test_trained_regimes_gpu.py (must FAIL,
+# in the regime named below) and one of the OLD selection, tests/test_parity_gpu.py -k "golden_case or ws6" (recorded: did the suite
+# notice before?); `product` runs the new file only (the old selection against it is part of the ordinary tier).  Every pass has its
+# own time limit and the script stops at the first abnormal exit (anything but pytest's 0 / 1).  LIBRARY: product 1 2 3 4 (default
+# all); sections are kept per library beside OUT and OUT is assembled from those present, so the passes may be spread over calls.
+if [ "$1" = regime ]; then
+  OUT=${2:-regime_negctl_out/regime_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1 2 3 4}
+  OLD='golden_case or ws6'
+  want() { case $1 in 1|2) echo z_sat;; 3) echo bn_affine;; 4) echo head_sat;; esac; }
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_regime$k.so; fi
+    sec=$D/regime_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest tests/test_trained_regimes_gpu.py -q -rA -p no:cacheprovider > $D/regime_negctl_${k}_new.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# new file, tests/test_trained_regimes_gpu.py (exit $rc):   $(tail -1 $D/regime_negctl_${k}_new.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/regime_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    nfail=$(grep -c "^FAILED " $D/regime_negctl_${k}_new.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass the new file" >> $sec; bad=1; }
+      continue
+    fi
+    nwant=$(grep "^FAILED " $D/regime_negctl_${k}_new.txt | grep -c "$(want $k)")
+    if [ "$nwant" -gt 0 ]; then echo "# verdict: control $k FAILS $nfail new cases, $nwant of them under $(want $k)" >> $sec
+    else echo "!! control $k fails no new case under $(want $k) ($nfail failures in all): the new file does not catch it" >> $sec; bad=1; fi
+    MSIG_LIB=$lib timeout -k 10 600 python -m pytest tests/test_parity_gpu.py -q -rA -p no:cacheprovider -k "$OLD" > $D/regime_negctl_${k}_old.txt 2>&1; rc=$?
+    echo "# old selection, tests/test_parity_gpu.py -k \"$OLD\" (exit $rc):   $(tail -1 $D/regime_negctl_${k}_old.txt)" >> $sec
+    grep -E "^FAILED " $D/regime_negctl_${k}_old.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ $rc = 0 ]; then echo "# verdict: the old selection does NOT notice control $k" >> $sec; else echo "# verdict: the old selection notices control $k" >> $sec; fi
+  done
+  echo "# tools/negative_controls.sh regime: tests/test_trained_regimes_gpu.py and tests/test_parity_gpu.py -k \"$OLD\" against libmsig_hip_regime<k>.so (make negctl REGIME=k)" > "$OUT"
+  for k in product 1 2 3 4; do [ -f $D/regime_negctl_section_$k.log ] && cat $D/regime_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 SEL='golden_case_stages or (random_shapes and (ws6 or split) and (40-6-2-512 or 33-3-3-256 or 3100-6-2-64 or 17-6-2-320))'
 OUT=${1:-gpurun_out/r05_negative_control.log}
 mkdir -p gpurun_out
