@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
         for (int i = tid; i < 4 * KM * 16; i += 256) {
           const int k = i >> 4, o = i & 15, kc = k < K ? k : 0;
           const float v = w1[o * K + kc] * gate_s[(size_t)b * C + kc / 7];
-          ws[i] = (k < K) ? v : 0.f;
+          ws[i] = (k < K || (msig_negctl_range == 1 && CT == 0)) ? v : 0.f;
         }
       }
     }
@@ -912,7 +912,8 @@ __global__ __launch_bounds__(256, CONV1_BWD_WGS) void conv1_bwd_kernel(const flo
   FOLD_BEGIN; FS(dp1); FS(code1); FS(y1); FS(stat); FS(x); FS(g1w); FS(bpart);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int C = CT > 0 ? CT : Crt;
-  const int K = C * 7, NB = (K + 15) / 16, NB16 = NB * 16;
+  const int K = C * 7, NB16 = (K + 15) / 16 * 16;
+  const int NB = (msig_negctl_range == 2 && CT == 0) ? K / 16 : NB16 / 16;       // the MFMA and record guards; NB16 is the record stride
   constexpr int NBC = CT > 0 ? (CT * 7 + 15) / 16 : G1_MAXNB;
   float* xs = smem;                          // [C][G1_XS] natural order, sample j <-> x[2*t0 - 4 + j]
   float* dzs = xs + C * G1_XS;               // [G1_TCH / 4 quads][G1_QS] dz

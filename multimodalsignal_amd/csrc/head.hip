@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     __syncthreads();
     // weight-gradient accumulation
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < (msig_negctl_range == 3 ? 2 : 4); ++j) {
       const int idx = tid + 256 * j;
       if (idx < K * 64) {
         const int c = idx >> 6, vv = idx & 63;
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
     }
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < (msig_negctl_range == 3 ? 2 : 4); ++j) {
       const int idx = tid + 256 * j;
       if (idx < K * 64) {
         const int c = idx >> 6, vv = idx & 63;

@@ -96,6 +96,17 @@ constexpr int msig_negctl_regime = MSIG_NEGCTL_REGIME;
 #else
 constexpr int msig_negctl_regime = 0;
 #endif
+// Negative controls of the channel / class range (make negctl RANGE=k; never defined in the product library): one slip each, confined
+// to code that only C = 9..15 or K > 8 reach and IN BOUNDS by construction — an omitted term or a changed value, never an index the
+// product does not also form (tests/test_channel_class_range_gpu.py must FAIL against each; tools/negative_controls.sh range).
+//   1  conv1_fwd_kernel<0>'s gated staging without the zero fill of the padded taps (they carry w1[o * K + 0] * gate instead)
+//   2  conv1_bwd_kernel<0> with NB = K / 16 in its MFMA and record guards: the columns of the partial last block are never accumulated
+//   3  head_bwd_kernel / head_step_kernel accumulate dW3 in two of the four register slots: rows c >= 8 of the gradient stay zero
+#ifdef MSIG_NEGCTL_RANGE
+constexpr int msig_negctl_range = MSIG_NEGCTL_RANGE;
+#else
+constexpr int msig_negctl_range = 0;
+#endif
 // acc += A . B over one 32-wide k block, A and B given as their three pieces ([0] = leading piece)
 template <int KIND = CT_ANY>
 __device__ __forceinline__ f32x4 mfma_bf16x3(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {

@@ -141,9 +141,19 @@ GOLDEN = {2: "model_c6_k2_t512", 3: "model_c2_k3_t256"}
 _cache = {}
 
 
+def _seeded_features(C_, K, T, N, seed):
+    """As _golden_features for a class count no golden file has: the oracle's seeded test weights (C_ channels, K classes)."""
+    eng = Engine(C_, K, DEV)
+    eng.load_named(O.init_params(C_, K, seed=seed))
+    feat = eng.features(_x(N, C_, T, seed))
+    y = np.random.RandomState(seed + 1).randint(0, K, N)
+    y[:K] = np.arange(K)
+    return eng, feat, y.astype(np.int64)
+
+
 def _case(K, N=48):
     if K not in _cache:
-        _cache[K] = _golden_features(GOLDEN[K], N, seed=100 + K)
+        _cache[K] = _golden_features(GOLDEN[K], N, seed=100 + K) if K in GOLDEN else _seeded_features(6, K, 256, N, seed=100 + K)
     return _cache[K]
 
 
@@ -228,7 +238,7 @@ def _head0(eng):
     return {k: eng.named_param_views()[k].detach().cpu().numpy() for k in R.HEAD_KEYS}
 
 
-CW = {2: [0.6, 2.5], 3: [0.5, 2.0, 1.25]}
+CW = {2: [0.6, 2.5], 3: [0.5, 2.0, 1.25], 16: [0.5, 2.0, 1.25, 0.3, 1.0, 3.5, 0.8, 1.6, 0.25, 2.75, 1.1, 0.6, 4.0, 0.9, 1.4, 0.7]}      # 16 = MSIG_MAX_K
 SEED = 0x5EED0123456789
 
 
@@ -260,7 +270,7 @@ def _one_step(K, thr, cw, reference_wrong=None):
 
 @pytest.mark.parametrize("cw", [False, True])
 @pytest.mark.parametrize("thr", [0, 128])
-@pytest.mark.parametrize("K", [2, 3])
+@pytest.mark.parametrize("K", [2, 3, 16])
 def test_one_step_gradients_and_loss(K, thr, cw):
     rep = _one_step(K, thr, cw)
     for k, (err, tol) in rep.items():
@@ -282,7 +292,7 @@ def test_negative_control_a_wrong_head_fails_the_one_step_gate(wrong):
 @pytest.mark.parametrize("cw", [False, True])
 @pytest.mark.parametrize("thr", [0, 128])
 @pytest.mark.parametrize("batch", [16, 20])           # 20: a short last step of 8 rows
-@pytest.mark.parametrize("K", [2, 3])
+@pytest.mark.parametrize("K", [2, 3, 16])
 def test_parameters_after_five_epochs(K, batch, thr, cw):
     E, N = 5, 48
     eng, feat, y = _case(K)

@@ -182,10 +182,12 @@ def _reference(params, x, y, w, seed, step, dropout_p):
     return out
 
 
+W16 = (0.5, 2.0, 1.25, 0.3, 1.0, 3.5, 0.8, 1.6, 0.25, 2.75, 1.1, 0.6, 4.0, 0.9, 1.4, 0.7)      # K = MSIG_MAX_K
+WEIGHTED = [(w, Cc, B) for B in (64, 2049) for Cc in (1, 3, 6) for w in (W2, W3)] + [(W16, Cc, 64) for Cc in (1, 3, 6)]      # W16 at B = 64 only
+
+
 @pytest.mark.parametrize("model", [(64, 2), (32, 1)])
-@pytest.mark.parametrize("B", [64, 2049])
-@pytest.mark.parametrize("Cc", [1, 3, 6])
-@pytest.mark.parametrize("w", [W2, W3])
+@pytest.mark.parametrize("w,Cc,B", WEIGHTED, ids=[f"w{(W2, W3, W16).index(w)}-{Cc}-{B}" for w, Cc, B in WEIGHTED])
 def test_weighted_step_matches_fp64_reference(w, Cc, B, model):
     """The weighted train step's loss and parameter gradients (left in `grads` by the fused step) against torch's weighted
     CrossEntropyLoss over the fp64 oracle, within gpu_common's adaptive tolerances.  B = 64: one-launch head; B = 2049: separate

@@ -507,7 +507,7 @@ def test_fold_batch_rejects_an_unsupported_form_before_any_launch(dev, kernel_fo
     assert not torch.equal(arena.view(0, "bn_state", torch.float32), before[0].view(torch.uint8)[arena.off["bn_state"][0]:arena.off["bn_state"][0] + arena.off["bn_state"][1]].view(torch.float32))
 
 
-@pytest.mark.parametrize("Cc", [6, 3, 16])
+@pytest.mark.parametrize("Cc", [6, 3, 16, 7, 13])      # 7: an instantiation of its own (Cr = 1); 13: the generic form, Cr = 3
 def test_channel_attention_forward_standalone(Cc, dev):
     """ChannelAttention.forward on its own (models.py:24-31; msig_channel_attention) against the oracle's gate, C < 4 included
     (empty hidden layer: the gate is 0.5 everywhere)."""
@@ -720,16 +720,23 @@ def test_fused_step_equals_separate_calls_bit_for_bit(B, form, dev, kernel_forms
     2048 windows (128 groups of 16 rows; 2060 is the first size past it) the classifier's forward, CrossEntropy and backward as
     ONE launch with the loss summed in the step's last one — built from the same arithmetic: losses, the head's outputs and
     gradients are bit-identical (and so is the first update)."""
-    from multimodalsignal_amd.runtime import Engine
     kernel_forms(*FORMS[form])
-    C, K, T = 6, 2, 384
+    fused_equals_separate_calls(B, 6, 2, 384, (1, 2), dev)
+
+
+def fused_equals_separate_calls(B, C, K, T, steps, dev, resync=False):
+    """The comparison of test_fused_step_equals_separate_calls_bit_for_bit at one shape over `steps` (the kernel forms are the caller's).
+    resync: after a step's comparisons the separate engine takes over the fused one's parameters and moments, so that the NEXT step
+    starts from one state again and can be compared bit for bit too — without it the last-bit differences of the second update make
+    every later forward differ."""
+    from multimodalsignal_amd.runtime import Engine
     params, x, y = _case(B, C, K, T, 300 + B)
     xd, yd = torch.as_tensor(x).to(dev), torch.as_tensor(y).to(dev)
     fused, apart = Engine(C, K, dev), Engine(C, K, dev)
     for e in (fused, apart):
         e.load_named({k: torch.as_tensor(v) for k, v in params.items()})
         e.ensure_adam_state()
-    for step in (1, 2):
+    for step in steps:
         fused.train_step(xd, yd, lr=1e-3, weight_decay=1e-4, step=step, dropout_p=0.5, seed=21)
         b = apart.forward(xd, yd, training=True, dropout_p=0.5, seed=21, step=step)
         apart.backward(b)
@@ -749,4 +756,7 @@ def test_fused_step_equals_separate_calls_bit_for_bit(B, form, dev, kernel_forms
         if step == 1:
             assert torch.equal(fused.params, apart.params)
         assert torch.equal(fused.bn_state, apart.bn_state), step
+        if resync:
+            for name in ("params", "exp_avg", "exp_avg_sq"):
+                getattr(apart, name).copy_(getattr(fused, name))
     assert torch.equal(fused.loss_acc, apart.loss_acc) and float(fused.loss_acc[0]) > 0          # msig_batch.loss_acc: both steps' summed losses

@@ -319,6 +319,64 @@ def test_subject_store_matches_wesad_dataset(tmp_path):
         store.view(["S9"])
 
 
+WESAD14 = ["chest_ACC_x", "chest_ACC_y", "chest_ACC_z", "chest_ECG", "chest_EMG", "chest_EDA", "chest_Temp", "chest_Resp",
+           "wrist_ACC_x", "wrist_ACC_y", "wrist_ACC_z", "wrist_BVP", "wrist_EDA", "wrist_TEMP"]
+
+
+def _raw_subject(N, T, C_all, seed):
+    """(N, T, C_all) float64 raw windows and their column names.  Ordinary columns have an offset and a spread of order 1; four
+    are what a one-pass variance and a log1p find hard: chest_Temp 33 +- 0.05 and chest_ACC_x 0.9 +- 0.02 (mean >> spread),
+    chest_EDA positive and heavy-tailed (the one column under log1p), chest_EMG exactly constant at 0.75 (variance exactly 0)."""
+    names = (WESAD14 + ["aux_0", "aux_1"])[:C_all]
+    rs = np.random.RandomState(seed)
+    raw = rs.randn(N, T, C_all) * (0.5 + rs.rand(C_all)) + rs.randn(C_all)
+    raw[:, :, names.index("chest_Temp")] = 33.0 + 0.05 * rs.randn(N, T)
+    raw[:, :, names.index("chest_ACC_x")] = 0.9 + 0.02 * rs.randn(N, T)
+    raw[:, :, names.index("chest_EDA")] = np.exp(0.8 * rs.randn(N, T)) + 0.1
+    raw[:, :, names.index("chest_EMG")] = 0.75
+    return raw, names
+
+
+NORMALISE_CASES = [
+    # all 14 WESAD channels in a permuted order, chest_EDA (column 5) neither first nor last
+    (3, 128, 14, [11, 6, 0, 13, 5, 2, 9, 4, 7, 1, 12, 3, 10, 8]),
+    # 143 360 rows > norm_stats_kernel's 512 x 256 threads: its grid-stride loop runs twice for some threads; MSIG_MAX_C columns
+    (70, 2048, 16, [15, 3, 8, 0, 12, 5, 10, 1, 14, 6, 2, 9, 4, 13, 7, 11]),
+    # a subset of the columns, T not a multiple of 4
+    (5, 130, 8, [7, 5, 0, 4, 6]),
+]
+
+
+@pytest.mark.parametrize("N,T,C_all,cols", NORMALISE_CASES, ids=["n3-t128-14of14", "n70-t2048-16of16", "n5-t130-5of8"])
+def test_normalise_subject_device_matches_float64_numpy(N, T, C_all, cols):
+    """msig_normalise_subject (norm_stats / norm_finalize / norm_apply: one-pass float64 sums, log1p under the mask, z-score, cast
+    and (N,T,C) -> (N,C,T) transposition) called directly, against dataset.normalise_subject — the reference's two-pass float64
+    numpy arithmetic — cast to fp32, at the project's bound: absolute difference <= 2e-6."""
+    from multimodalsignal_amd.dataset import normalise_subject, normalise_subject_device
+    raw, names_all = _raw_subject(N, T, C_all, seed=N + T)
+    names = [names_all[c] for c in cols]
+    for need in ("chest_Temp", "chest_ACC_x", "chest_EDA", "chest_EMG"):
+        assert need in names
+    eda, const = names.index("chest_EDA"), names.index("chest_EMG")
+    assert 0 < eda < len(cols) - 1 and cols != sorted(cols)
+    want = normalise_subject(raw[:, :, cols], names).transpose(0, 2, 1).astype(np.float32)      # the fancy index is a private copy
+    got = normalise_subject_device(torch.from_numpy(raw).to(DEV), cols, names)
+    torch.cuda.synchronize()
+    assert got.shape == (N, len(cols), T) and got.dtype == torch.float32
+    got = got.cpu().numpy()
+    assert np.isfinite(got).all()
+    diff = np.abs(got.astype(np.float64) - want.astype(np.float64))
+    print(f"max |device - numpy| = {diff.max():.3e}, {100.0 * (diff > 0).mean():.3f} % of the elements differ")
+    assert diff.max() <= 2e-6
+    assert (got[:, const] == 0).all() and (want[:, const] == 0).all()                  # the constant channel: exactly 0 on both sides
+    # the comparison is not vacuous: every other channel is a z-score, and chest_EDA's is the z-score of log1p, not of the raw column
+    live = [c for c in range(len(cols)) if c != const]
+    np.testing.assert_allclose(want[:, live].transpose(1, 0, 2).reshape(len(live), -1).std(axis=1), 1.0, atol=1e-4)
+    col = raw[:, :, cols[eda]]
+    plain = ((col - col.mean()) / (col.std() + 1e-8)).astype(np.float32)
+    assert np.abs(got[:, eda] - plain).max() > 0.1
+
+
 def test_labels_outside_the_class_range_raise(tmp_path):
     """CLASSIFICATION_MODE 'ternary' (labels 0..2) with a 2-class model: torch's CrossEntropyLoss raises (trainer.py:147);
     here the loss kernel would index past the logits row, so Trainer refuses the dataset up front."""

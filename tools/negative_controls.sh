@@ -13,6 +13,49 @@
 # notice before?); `product` runs the new file only (the old selection against it is part of the ordinary tier).  Every pass has its
 # own time limit and the script stops at the first abnormal exit (anything but pytest's 0 / 1).  LIBRARY: product 1 2 3 4 (default
 # all); sections are kept per library beside OUT and OUT is assembled from those present, so the passes may be spread over calls.
+# tools/negative_controls.sh range [OUT] [LIBRARY ...]: the controls of the CHANNEL / CLASS RANGE (libraries built by
+#   for k in 1 2 3; do make -C multimodalsignal_amd/csrc negctl RANGE=$k; done ).  Each is one in-bounds slip in code that only
+# C = 9..15 or K > 8 reach (msig_dev.h MSIG_NEGCTL_RANGE): 1 conv1_fwd<0> without the zero fill of its padded taps, 2 conv1_bwd<0>
+# without its partial last column block, 3 dW3 in two of its four register slots.  Per library: one pass of
+# tests/test_channel_class_range_gpu.py (must FAIL at least one case; the product must pass every case) and one of the OLD selection,
+# tests/test_parity_gpu.py -k "golden_case or ws6" (recorded: did the suite notice before?), with the time limits, the stop at the
+# first abnormal exit and the per-library sections of the regime mode.  LIBRARY: product 1 2 3 (default all).
+if [ "$1" = range ]; then
+  OUT=${2:-range_negctl_out/range_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1 2 3}
+  OLD='golden_case or ws6'
+  NEW=tests/test_channel_class_range_gpu.py
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_range$k.so; fi
+    sec=$D/range_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/range_negctl_${k}_new.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# new file, $NEW (exit $rc):   $(tail -1 $D/range_negctl_${k}_new.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/range_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    nfail=$(grep -c "^FAILED " $D/range_negctl_${k}_new.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass the new file" >> $sec; bad=1; }
+      continue
+    fi
+    if [ "$nfail" -gt 0 ]; then echo "# verdict: control $k FAILS $nfail new cases" >> $sec
+    else echo "!! control $k fails no new case: the new file does not catch it" >> $sec; bad=1; fi
+    MSIG_LIB=$lib timeout -k 10 600 python -m pytest tests/test_parity_gpu.py -q -rA -p no:cacheprovider -k "$OLD" > $D/range_negctl_${k}_old.txt 2>&1; rc=$?
+    echo "# old selection, tests/test_parity_gpu.py -k \"$OLD\" (exit $rc):   $(tail -1 $D/range_negctl_${k}_old.txt)" >> $sec
+    grep -E "^FAILED " $D/range_negctl_${k}_old.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ $rc = 0 ]; then echo "# verdict: the old selection does NOT notice control $k" >> $sec; else echo "# verdict: the old selection notices control $k" >> $sec; fi
+  done
+  echo "# tools/negative_controls.sh range: $NEW and tests/test_parity_gpu.py -k \"$OLD\" against libmsig_hip_range<k>.so (make negctl RANGE=k)" > "$OUT"
+  for k in product 1 2 3; do [ -f $D/range_negctl_section_$k.log ] && cat $D/range_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = regime ]; then
   OUT=${2:-regime_negctl_out/regime_negative_control.log}
   D=$(dirname "$OUT")
