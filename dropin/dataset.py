@@ -3,4 +3,4 @@ put this directory first on PYTHONPATH and the reference driver runs on the MI35
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from multimodalsignal_amd.dataset import WesadDataset, DeviceLoader  # noqa: F401
+from multimodalsignal_amd.dataset import WesadDataset, DeviceLoader, reference_mask  # noqa: F401

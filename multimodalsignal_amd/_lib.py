@@ -103,6 +103,7 @@ DA_MAX_BATCH = 256    # msig_da.h MSIG_DA_MAX_BATCH: rows of one discriminator s
 WA_ABI_VERSION = 1    # include/msig_wa.h MSIG_WA_ABI_VERSION (weight averaging: the shadow's update)
 EN_ABI_VERSION = 1    # include/msig_en.h MSIG_EN_ABI_VERSION (deep ensembles: the reduction of the members' logits)
 EN_MAX_MEMBERS = 256  # msig_en.h MSIG_EN_MAX_MEMBERS: members of one ensemble
+NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
 
 
 class Multi(C.Structure):
@@ -370,6 +371,13 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} has msig_en.h ABI {L.msig_en_abi_version()}; this binding is {EN_ABI_VERSION}: rebuild the library")
         L.msig_en_reduce.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.msig_en_reduce_multi.argtypes = [vp, C.POINTER(Multi), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        # include/msig_nr.h, exported by the same library: per-subject normalisation with the statistics of reference windows
+        L.msig_nr_abi_version.restype = C.c_int
+        if L.msig_nr_abi_version() != NR_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_nr.h ABI {L.msig_nr_abi_version()}; this binding is {NR_ABI_VERSION}: rebuild the library")
+        L.msig_nr_scratch_bytes.restype = C.c_int64
+        L.msig_nr_normalise_subject.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_uint32, vp, vp, vp,
+                                                vp, vp]
         _lib = L
     return _lib
 

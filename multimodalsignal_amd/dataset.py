@@ -46,10 +46,67 @@ def map_labels(y_raw: np.ndarray, mode: str) -> np.ndarray:
     raise ValueError(f"Unknown classification_mode: {mode}")
 
 
-def normalise_subject(x: np.ndarray, names) -> np.ndarray:
+def parse_reference(reference) -> Optional[int]:
+    """The normalisation reference of a run: "subject" (every window of the subject supplies the statistics; the default),
+    "baseline" (the windows whose raw protocol label is 1) or "baseline:K" (the first K >= 1 of those in file order; window k
+    covers seconds 10 k .. 10 k + 60, so K windows are 60 + 10 (K - 1) seconds of rest).  Returns None for "subject", 0 for
+    "baseline" and K for "baseline:K"; anything else raises ValueError."""
+    if reference == "subject":
+        return None
+    if reference == "baseline":
+        return 0
+    if isinstance(reference, str) and reference.startswith("baseline:"):
+        k = reference[len("baseline:"):]
+        if k.isascii() and k.isdigit() and int(k) >= 1:
+            return int(k)
+    raise ValueError(f"normalisation reference must be 'subject', 'baseline' or 'baseline:K' with K >= 1, got {reference!r}")
+
+
+def reference_mask(y_raw: np.ndarray, reference) -> np.ndarray:
+    """Which of a subject's windows supply the normalisation statistics (bool, one per window).  `y_raw` are the RAW protocol
+    labels, before any class mapping: the mask is the same in every classification mode."""
+    k = parse_reference(reference)
+    y_raw = np.asarray(y_raw)
+    if k is None:
+        return np.ones(y_raw.shape, dtype=bool)
+    mask = y_raw == 1
+    if k:
+        mask[np.flatnonzero(mask)[k:]] = False
+    return mask
+
+
+def subject_reference(y_raw: np.ndarray, reference, sid) -> Optional[np.ndarray]:
+    """The `ref` of normalise_subject / normalise_subject_device for subject `sid`: None for the "subject" rule, else the mask.
+    A subject without a reference window gets the "subject" rule (None) and one warning line — the reference's code announces
+    that fallback and then leaves such a subject un-normalised."""
+    if parse_reference(reference) is None:
+        return None
+    mask = reference_mask(y_raw, reference)
+    if not mask.any():
+        print(f"Warning: subject {sid} has no baseline window (raw label 1); normalising with the statistics of all its windows.")
+        return None
+    return mask
+
+
+def normalise_subject(x: np.ndarray, names, ref: Optional[np.ndarray] = None) -> np.ndarray:
     """Per-subject, per-channel z-score over all of the subject's windows, std + 1e-8;
     the channel literally named 'chest_EDA' is log1p-transformed first (dataset.py:36-48).
-    `x` is (N,T,C) float64 and is modified in place."""
+    `x` is (N,T,C) float64 and is modified in place.
+
+    `ref` (a bool mask over the N windows): mean and std come from the selected windows only and are applied to all of them
+    (void/dataset.py:39-55 — the same np.mean / np.std calls on the same slices, so the result is that file's bit for bit).
+    None, or a mask that selects nothing: the rule above."""
+    if ref is not None and np.any(ref):
+        base = x[np.asarray(ref, dtype=bool)]
+        for ch, name in enumerate(names):
+            if name == "chest_EDA":
+                lg = np.log1p(base[:, :, ch])
+                m, sd = np.mean(lg), np.std(lg) + 1e-8
+                x[:, :, ch] = (np.log1p(x[:, :, ch]) - m) / sd
+            else:
+                m, sd = np.mean(base[:, :, ch]), np.std(base[:, :, ch]) + 1e-8
+                x[:, :, ch] = (x[:, :, ch] - m) / sd
+        return x
     mu = x.mean(axis=(0, 1))
     sd = x.std(axis=(0, 1)) + 1e-8
     for ch, name in enumerate(names):
@@ -63,16 +120,19 @@ def normalise_subject(x: np.ndarray, names) -> np.ndarray:
 
 class WesadDataset(Dataset):
     def __init__(self, data_path: Path, subjects: list, channels_to_use: list, all_channel_names: list,
-                 classification_mode="stress_binary", cache: Optional[dict] = None):
+                 classification_mode="stress_binary", cache: Optional[dict] = None, reference="subject"):
         """`cache` (optional, not in the reference): a dict shared between datasets of one run; a
         subject's normalised windows depend only on that subject, so the 3 x 15 datasets of a LOSO run
-        can load and normalise each subject once instead of 45 times."""
+        can load and normalise each subject once instead of 45 times.
+        `reference` (optional, not in the reference's dataset.py): which windows supply each subject's mean and std
+        (parse_reference); "subject" is the rule above."""
         data_path = Path(data_path)
+        parse_reference(reference)
         self.classification_mode = classification_mode
         self.data_list, self.labels_list = [], []
         cols = [all_channel_names.index(ch) for ch in channels_to_use]
         for sid in subjects:
-            key = (str(data_path), sid, tuple(cols), classification_mode)
+            key = (str(data_path), sid, tuple(cols), classification_mode, reference)
             if cache is not None and key in cache:
                 x, y = cache[key]
             else:
@@ -81,8 +141,10 @@ class WesadDataset(Dataset):
                     print(f"Warning: Skipping subject {sid} for data, file not found.")
                     continue
                 x = np.load(fx)[:, :, cols]                       # fancy index -> private float64 copy
-                y = map_labels(np.load(fy), classification_mode)
-                x = normalise_subject(x, [all_channel_names[i] for i in cols])
+                y_raw = np.load(fy)
+                y = map_labels(y_raw, classification_mode)
+                # the mask is taken from the raw labels, before amusement_binary drops rows
+                x = normalise_subject(x, [all_channel_names[i] for i in cols], subject_reference(y_raw, reference, sid))
                 if (y < 0).any():                                  # amusement_binary: windows of the other protocol phases are dropped
                     x, y = x[y >= 0], y[y >= 0]
                 if cache is not None:
@@ -123,8 +185,12 @@ class SubjectStore:
     and the (N,T,C)->(N,C,T) transposition on the GPU in float64 (torch ops on the raw upload)."""
 
     def __init__(self, data_path: Path, subjects: list, channels_to_use: list, all_channel_names: list,
-                 classification_mode="stress_binary", device="cuda", normalise="host"):
+                 classification_mode="stress_binary", device="cuda", normalise="host", reference="subject"):
+        """`reference`: which windows supply each subject's mean and std (parse_reference); with anything but "subject" one line
+        per subject names the windows used, and `reference_windows` holds {subject: (reference windows used, fallback applied)}."""
         self.device = torch.device(device)
+        parse_reference(reference)
+        self.reference, self.reference_windows = reference, {}
         data_path = Path(data_path)
         cols = [all_channel_names.index(ch) for ch in channels_to_use]
         names = [all_channel_names[i] for i in cols]
@@ -141,22 +207,36 @@ class SubjectStore:
                 continue
             present.append((sid, fx, fy))
 
-        def host_windows(fx):        # the reference's float64 arithmetic, then its fp32 cast (dataset.py:36-48, :63)
-            x = normalise_subject(np.load(fx)[:, :, cols], names)
+        def host_windows(job):       # the reference's float64 arithmetic, then its fp32 cast (dataset.py:36-48, :63)
+            fx, ref = job
+            x = normalise_subject(np.load(fx)[:, :, cols], names, ref)
             return np.ascontiguousarray(x.transpose(0, 2, 1), dtype=np.float32)
+
+        # the raw labels are read first: they say which windows are a subject's reference (None: the "subject" rule)
+        y_raws = [np.load(fy) for _, _, fy in present]
+        refs = [subject_reference(y_raw, reference, sid) for y_raw, (sid, _, _) in zip(y_raws, present)]
 
         # A subject's windows depend on that subject alone: the host path reads and normalises a few subjects at a time on
         # threads (numpy's reductions and copies run outside the interpreter lock; 0.9 -> 0.35 s for 15 x 270 windows) and
         # uploads them in subject order — the store is the same bit for bit.
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as pool:
-            host = pool.map(host_windows, [fx for _, fx, _ in present]) if normalise == "host" else iter(())
-            for sid, fx, fy in present:
-                y = map_labels(np.load(fy), classification_mode)
+            host = pool.map(host_windows, [(fx, ref) for (_, fx, _), ref in zip(present, refs)]) if normalise == "host" else iter(())
+            for (sid, fx, fy), y_raw, ref in zip(present, y_raws, refs):
+                y = map_labels(y_raw, classification_mode)
                 if normalise == "host":
                     xd = torch.from_numpy(next(host)).to(self.device)
-                else:
-                    xd = normalise_subject_device(torch.from_numpy(np.load(fx)).to(self.device), cols, names)
+                    n_ref = 0 if ref is None else int(ref.sum())
+                elif ref is None:
+                    xd, n_ref = normalise_subject_device(torch.from_numpy(np.load(fx)).to(self.device), cols, names), 0
+                else:       # the kernel counts the windows its mask selects: the line below reports what it used
+                    stats = torch.empty(2 * L.MAX_C + 1, dtype=torch.float64, device=self.device)
+                    xd = normalise_subject_device(torch.from_numpy(np.load(fx)).to(self.device), cols, names, ref, stats=stats)
+                    n_ref = int(stats[2 * L.MAX_C].item())
+                if parse_reference(reference) is not None:
+                    self.reference_windows[sid] = (n_ref, ref is None)
+                    print(f"[normalise {normalise}] {sid}: reference {reference}: "
+                          + (f"{n_ref} of {len(y)} windows" if ref is not None else f"no baseline window, all {len(y)} windows"))
                 xs.append(xd)
                 ys.append(torch.from_numpy(y.astype(np.int64)))
                 self.ranges[sid] = (start, start + len(y))
@@ -169,18 +249,20 @@ class SubjectStore:
 
     @classmethod
     def from_wesad(cls, data_path: Path, subjects: list, channels_to_use: list, all_channel_names: list,
-                   classification_mode="stress_binary", device="cuda", cache: Optional[dict] = None) -> "SubjectStore":
+                   classification_mode="stress_binary", device="cuda", cache: Optional[dict] = None, reference="subject") -> "SubjectStore":
         """A store of any classification mode, amusement_binary included, built from WesadDataset's per-subject arrays (its
         `cache` shared): every window is the float64 -> fp32 cast of WesadDataset.device_tensors, so a StoreView of it feeds the
         same bits as a WesadDataset of those subjects.  A subject with no window of the mode keeps an empty range."""
         self = cls.__new__(cls)
         self.device = torch.device(device)
+        self.reference, self.reference_windows = reference, {}
         xs, ys, self.ranges, start = [], [], {}, 0
         for sid in subjects:
             if not ((Path(data_path) / f"{sid}_X.npy").exists() and (Path(data_path) / f"{sid}_y.npy").exists()):
                 print(f"Warning: Skipping subject {sid} for data, file not found.")
                 continue
-            ds = WesadDataset(data_path, [sid], channels_to_use, all_channel_names, classification_mode=classification_mode, cache=cache)
+            ds = WesadDataset(data_path, [sid], channels_to_use, all_channel_names, classification_mode=classification_mode, cache=cache,
+                              reference=reference)
             xs.append(torch.from_numpy(np.ascontiguousarray(ds.data.transpose(0, 2, 1), dtype=np.float32)))
             ys.append(torch.from_numpy(ds.labels.astype(np.int64)))
             self.ranges[sid] = (start, start + len(ds))
@@ -196,9 +278,13 @@ class SubjectStore:
         return StoreView(self, subjects)
 
 
-def normalise_subject_device(raw: torch.Tensor, cols, names) -> torch.Tensor:
+def normalise_subject_device(raw: torch.Tensor, cols, names, ref=None, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(N,T,C_all) raw float64 device tensor -> normalised (N,C,T) fp32 through msig_normalise_subject
-    (float64 reduction, optional log1p, z-score, cast and transposition in HIP)."""
+    (float64 reduction, optional log1p, z-score, cast and transposition in HIP).
+
+    `ref` (a bool mask over the N windows, numpy or torch): through msig_nr_normalise_subject (include/msig_nr.h) — mean and std of
+    the selected windows, applied to all.  `stats` (with `ref`; a float64 device tensor of 2 * MAX_C + 1): receives the mean, the
+    1 / (std + 1e-8) and the number of selected windows."""
     if not raw.is_cuda or raw.dtype != torch.float64 or raw.dim() != 3:
         raise ValueError("normalise_subject_device needs a (N,T,C_all) float64 GPU tensor")
     raw = raw.contiguous()
@@ -208,9 +294,24 @@ def normalise_subject_device(raw: torch.Tensor, cols, names) -> torch.Tensor:
         if name == "chest_EDA":
             mask |= 1 << c
     out = torch.empty((N, len(cols), T), dtype=torch.float32, device=raw.device)
-    scratch = torch.empty(L.lib().msig_normalise_scratch_bytes(), dtype=torch.uint8, device=raw.device)
     carr = (C.c_int32 * len(cols))(*[int(c) for c in cols])
     st = C.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)
+    if ref is not None:
+        if not isinstance(ref, torch.Tensor):
+            ref = torch.from_numpy(np.ascontiguousarray(np.asarray(ref) != 0))
+        ref = ref.to(raw.device).contiguous()                             # a device mask stays on the device: no synchronisation
+        ref = ref.view(torch.uint8) if ref.dtype in (torch.bool, torch.uint8) else (ref != 0).view(torch.uint8)      # any non-zero byte selects
+        if ref.shape != (N,):
+            raise ValueError(f"ref must have one entry per window ({N}), got shape {tuple(ref.shape)}")
+        if stats is not None and (stats.dtype != torch.float64 or stats.device != raw.device or stats.numel() < 2 * L.MAX_C + 1
+                                  or not stats.is_contiguous()):
+            raise ValueError(f"stats must be a contiguous float64 tensor of {2 * L.MAX_C + 1} on {raw.device}")
+        scratch = torch.empty(L.lib().msig_nr_scratch_bytes(), dtype=torch.uint8, device=raw.device)
+        L.check(L.lib().msig_nr_normalise_subject(raw.data_ptr(), N, T, C_all, carr, len(cols), mask, ref.data_ptr(), out.data_ptr(),
+                                                  None if stats is None else stats.data_ptr(), scratch.data_ptr(), st),
+                "msig_nr_normalise_subject")
+        return out
+    scratch = torch.empty(L.lib().msig_normalise_scratch_bytes(), dtype=torch.uint8, device=raw.device)
     L.check(L.lib().msig_normalise_subject(raw.data_ptr(), N, T, C_all, carr, len(cols), mask, out.data_ptr(), scratch.data_ptr(), st),
             "msig_normalise_subject")
     return out

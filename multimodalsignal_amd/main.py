@@ -32,7 +32,7 @@ from .augment import Augment
 from .mixup import Mixup
 from . import adversary as adversary_mod
 from . import averaging as averaging_mod
-from .dataset import DeviceLoader, SubjectStore, WesadDataset
+from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask
 from . import ensemble as ensemble_mod
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
@@ -125,9 +125,15 @@ def soft_targets_line(cfg):
     return "SOFT TARGETS: " + " ".join(parts) + "\n"
 
 
+def norm_reference(cfg):
+    """cfg["norm_reference"]: which windows supply each subject's normalisation statistics ("subject" when absent)."""
+    return cfg.get("norm_reference", "subject")
+
+
 def host_datasets(cfg, all_channel_names, cache, channels, mode):
     """The dataset factory over host arrays: subjects -> WesadDataset (`cache`: one dict shared by the datasets of a run)."""
-    return lambda subjects: WesadDataset(cfg["data_path"], subjects, channels, all_channel_names, classification_mode=mode, cache=cache)
+    return lambda subjects: WesadDataset(cfg["data_path"], subjects, channels, all_channel_names, classification_mode=mode, cache=cache,
+                                         reference=norm_reference(cfg))
 
 
 def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, params, seed, cfg, device, shuffle=True, test_pass=True,
@@ -214,6 +220,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(adversary_line(cfg))
         if cfg.get("averaging") is not None:                        # likewise
             f.write(averaging_mod.settings_line(cfg["averaging"]) + "\n")
+        if cfg.get("norm_reference") is not None:                   # likewise
+            f.write(f"NORM_REFERENCE: {cfg['norm_reference']}\n")
         f.write("\n每个折叠的详细结果:\n")
         for r in results:
             f.write(f"  - 测试 {r['subject']}: Accuracy = {r['accuracy']:.4f}, F1-score = {r['f1_score']:.4f}\n")
@@ -438,10 +446,10 @@ def subject_stores(cfgs, all_channel_names, device):
     """{configuration name: SubjectStore}, one store per distinct data set: the model kinds of a comparison run read the same windows."""
     stores, by_data = {}, {}
     for n, c in cfgs.items():
-        dkey = (str(c["data_path"]), tuple(c["subjects"]), tuple(c["channels"]), c["mode"], c.get("normalise", "host"))
+        dkey = (str(c["data_path"]), tuple(c["subjects"]), tuple(c["channels"]), c["mode"], c.get("normalise", "host"), norm_reference(c))
         if dkey not in by_data:
             by_data[dkey] = SubjectStore(c["data_path"], c["subjects"], c["channels"], all_channel_names, classification_mode=c["mode"],
-                                         device=device, normalise=c.get("normalise", "host"))
+                                         device=device, normalise=c.get("normalise", "host"), reference=norm_reference(c))
         stores[n] = by_data[dkey]
     return stores
 
@@ -705,6 +713,90 @@ def write_comparison(run_output_dir, cmp):
     return path
 
 
+def reference_dir(reference):
+    """The directory name of a reference's configuration in a --norm-reference run of several: "baseline:30" -> "baseline_30"."""
+    return reference.replace(":", "_")
+
+
+def normalisation(results, references, data_path, subjects):
+    """The references of a --norm-reference run of several, fold by fold.  results: {set name: {reference: [per-fold dicts with
+    subject, accuracy, f1_score]}}.  Folds are paired by test subject (the references share splits, seeds and loader order); the
+    paired difference is reference - anchor, the anchor being "subject" or, where that is not among them, the first reference.
+    Per subject the number of reference windows used and whether the whole-recording fallback applied (from the raw label files:
+    what every store of the run was built from).  std is the population std (np.std, as cv_summary.txt).  Returns a JSON-ready dict."""
+    anchor = "subject" if "subject" in references else references[0]
+    windows = {}
+    for ref in references:
+        windows[ref] = {}
+        for sid in subjects:
+            fy = Path(data_path) / f"{sid}_y.npy"
+            if not fy.exists():
+                continue
+            y_raw = np.load(fy)
+            n = int(reference_mask(y_raw, ref).sum())
+            fallback = n == 0
+            windows[ref][sid] = {"n_windows": int(len(y_raw)), "reference_windows": int(len(y_raw)) if fallback else n, "fallback": fallback}
+    out = {"references": list(references), "anchor": anchor, "difference": f"reference - {anchor}", "reference_windows": windows, "sets": {}}
+    for name, per_ref in results.items():
+        base = {r["subject"]: r for r in per_ref[anchor]}
+        st = {"n_folds": len(base), "references": {}}
+        for ref in references:
+            rows = {r["subject"]: r for r in per_ref[ref]}
+            folds = [{"subject": sid, "accuracy": float(rows[sid]["accuracy"]), "f1_score": float(rows[sid]["f1_score"]),
+                      "difference": {m: float(rows[sid][m]) - float(base[sid][m]) for m in ("accuracy", "f1_score")}}
+                     for sid in base if sid in rows]
+            entry = {"folds": folds, "summary": {}, "difference": {}}
+            for m in ("accuracy", "f1_score"):
+                v = np.array([f[m] for f in folds], dtype=np.float64)
+                d = np.array([f["difference"][m] for f in folds], dtype=np.float64)
+                entry["summary"][m] = {"mean": float(v.mean()) if v.size else float("nan"), "std": float(v.std()) if v.size else float("nan")}
+                entry["difference"][m] = {"mean": float(d.mean()) if d.size else float("nan"), "std": float(d.std()) if d.size else float("nan"),
+                                          "wins": int((d > 0).sum()), "ties": int((d == 0).sum()), "losses": int((d < 0).sum())}
+            st["references"][ref] = entry
+        out["sets"][name] = st
+    return out
+
+
+def write_normalisation(run_output_dir, table, synthetic=False):
+    """normalisation.json (the dict of `normalisation`) and normalisation.txt beside the configurations' directories."""
+    run_output_dir = Path(run_output_dir)
+    table = dict(table, synthetic=bool(synthetic))
+    (run_output_dir / "normalisation.json").write_text(json.dumps(table, indent=1))
+    refs, anchor = table["references"], table["anchor"]
+    lines = [f"Normalisation references (paired LOSO folds): {', '.join(refs)}; difference = {table['difference']}"]
+    if synthetic:
+        lines.append("synthetic data: its subject effects are affine, so every reference removes them — this table shows that the "
+                     "machinery runs, not what a reference costs or gains on WESAD")
+    lines.append("")
+    for name, st in table["sets"].items():
+        if name:
+            lines.append(f"channel set {name}")
+        subjects = [f["subject"] for f in st["references"][anchor]["folds"]]
+        lines.append(f"  {'subject':<10}" + "".join(f" {r + ' acc':>18} {'F1':>8} {'d acc':>8} {'d F1':>8}" for r in refs))
+        for i, sid in enumerate(subjects):
+            row = f"  {sid:<10}"
+            for r in refs:
+                f = st["references"][r]["folds"][i]
+                row += f" {f['accuracy']:>18.4f} {f['f1_score']:>8.4f} {f['difference']['accuracy']:>+8.4f} {f['difference']['f1_score']:>+8.4f}"
+            lines.append(row)
+        for r in refs:
+            sm, df = st["references"][r]["summary"], st["references"][r]["difference"]
+            lines.append(f"  {r:<14} accuracy {sm['accuracy']['mean']:.4f} ± {sm['accuracy']['std']:.4f}   "
+                         f"weighted F1 {sm['f1_score']['mean']:.4f} ± {sm['f1_score']['std']:.4f}")
+            if r != anchor:
+                for m, label in (("accuracy", "accuracy"), ("f1_score", "weighted F1")):
+                    lines.append(f"    {label} vs {anchor}: {df[m]['mean']:+.4f} ± {df[m]['std']:.4f}; wins {df[m]['wins']} ties {df[m]['ties']} "
+                                 f"losses {df[m]['losses']} of {st['n_folds']} folds")
+        lines.append("")
+    lines.append("reference windows used per subject (fallback: no baseline window, the statistics of all windows):")
+    for r in refs:
+        lines.append(f"  {r}: " + ", ".join(f"{sid} {w['reference_windows']}/{w['n_windows']}" + (" fallback" if w["fallback"] else "")
+                                            for sid, w in table["reference_windows"][r].items()))
+    path = run_output_dir / "normalisation.txt"
+    path.write_text("\n".join(lines) + "\n", encoding="utf-8")
+    return path
+
+
 def run_simple_experiment(run_output_dir, device, all_channel_names, cfg=None, rank=0, world=1):
     """The reference's entry point (main.py:91): one configuration, 15 folds."""
     results, wall = run_experiments(run_output_dir, device, all_channel_names, {"": cfg or default_cfg()}, rank, world)
@@ -791,7 +883,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
         print(f"[rank {rank}] fold {k} ({sid}): M1 acc {m1_acc:.4f} | three-class acc {acc3:.4f} f1 {f13:.4f}", flush=True)
 
     if int(cfg.get("concurrent_folds", 1)) > 1 and cfg.get("lockstep", True) and mine:
-        stores = {tag: SubjectStore.from_wesad(cfg["data_path"], subjects, ch, all_channel_names, mode, device, cache) for tag, ch, _, mode in models}
+        stores = {tag: SubjectStore.from_wesad(cfg["data_path"], subjects, ch, all_channel_names, mode, device, cache, norm_reference(cfg))
+                  for tag, ch, _, mode in models}
         datasets = {tag: stores[tag].view for tag in stores}
         # sequential: seeding / initialisation order as in the sequential driver
         units = {(k, tag): p for k in mine for tag, p in hierarchical_units(k, cfg, models, datasets, run_output_dir, device)}
@@ -834,6 +927,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(soft_targets_line(cfg))
             if adversary_line(cfg) is not None:
                 f.write(adversary_line(cfg))
+            if cfg.get("norm_reference") is not None:
+                f.write(f"NORM_REFERENCE: {cfg['norm_reference']}\n")
             f.write("\n")
             for r in results:
                 f.write(f"  - 测试 {r['subject']}: M1 Accuracy = {r['m1_accuracy']:.4f}, 三分类 Accuracy = {r['ternary_accuracy']:.4f}\n")
@@ -965,6 +1060,24 @@ def parse_args(ap, argv=None):
             ap.error("--weight-average runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
     elif args.average_bn is not None or args.average_validate:
         ap.error("--average-bn / --average-validate need --weight-average")
+    if args.norm_reference is not None:
+        try:
+            for ref in args.norm_reference:
+                parse_reference(ref)
+        except ValueError as e:
+            ap.error(f"--norm-reference: {e}")
+        if len(set(args.norm_reference)) != len(args.norm_reference):
+            ap.error("--norm-reference: every reference once")
+        if len(args.norm_reference) > 1:
+            if len(set(args.model)) > 1:
+                ap.error("--norm-reference with several values takes one --model kind; run the kinds as separate jobs")
+            if args.hierarchical:
+                ap.error("--norm-reference with several values runs with the standard LOSO, --ablation and --sweep (not --hierarchical)")
+            post = [flag for flag, on in (("--calibrate", args.calibrate), ("--adapt-bn", args.adapt_bn is not None),
+                                          ("--attribute", args.attribute is not None), ("--mc-dropout", args.mc_dropout is not None),
+                                          ("--seeds", args.seeds > 1), ("--weight-average", args.weight_average is not None)) if on]
+            if post:
+                ap.error(f"--norm-reference with several values does not combine with {', '.join(post)}; give one reference")
     return args
 
 
@@ -1000,6 +1113,14 @@ def build_parser():
                     help="train concurrent folds on one HIP stream each instead of as one fold batch (msig_*_multi)")
     ap.add_argument("--difficulty", type=float, default=1.0, help="noise scale of the synthetic dataset")
     ap.add_argument("--normalise", choices=["host", "device"], default="host", help="where the per-subject z-score runs")
+    ap.add_argument("--norm-reference", nargs="+", default=None, metavar="REF",
+                    help="which windows supply each subject's normalisation mean and std (all of its windows are then transformed with "
+                         "them): subject = every window (the default, transductive for the test subject), baseline = the windows of the "
+                         "baseline phase (raw protocol label 1), baseline:K = the first K of those (60 + 10 (K - 1) seconds of rest).  A "
+                         "subject without a baseline window keeps the subject rule, with a warning.  One value: that reference in every "
+                         "driver and with every option.  Several: one job with one LOSO per reference on shared splits, seeds and fold "
+                         "batches, and normalisation.txt / normalisation.json with the paired differences (one --model kind, not "
+                         "--hierarchical, no post-LOSO option)")
     ap.add_argument("--class-weights", choices=["none", "balanced"], default=CLASS_WEIGHTS,
                     help="class-weighted CrossEntropyLoss for training, validation and test losses: 'balanced' = N / (K * count_c) over "
                          "each model's own training labels (M1 and M2 separately in --hierarchical)")
@@ -1130,6 +1251,9 @@ def build_cfg(args, kinds):
         cfg.update(mc_dropout=args.mc_dropout, mc_seed=args.mc_seed, synthetic=args.synthetic is not None)
     if args.seeds > 1:                 # likewise: --seeds 1 is the run without the flag
         cfg.update(seeds=args.seeds, synthetic=args.synthetic is not None)
+    if args.norm_reference is not None:      # likewise; several values: the list, which main() turns into one configuration each
+        refs = list(args.norm_reference)
+        cfg.update(norm_reference=refs[0] if len(refs) == 1 else refs, synthetic=args.synthetic is not None)
     return cfg
 
 
@@ -1195,8 +1319,23 @@ def main(argv=None):
             if not name or not chans:
                 ap.error(f"--sweep expects NAME=CH1,CH2,... (got {item!r})")
             sets[name] = chans.split(",")
+    refs = cfg.get("norm_reference")
     if args.hierarchical:
         results, wall = run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg, rank, world)
+    elif isinstance(refs, list):
+        # one job: every (reference, set) is a configuration of its own — own store and fold batches, shared splits and seeds
+        sets_ = sets or {"": list(cfg["channels"])}
+        for n, ch in sets_.items():
+            if len(ch) > 16:
+                ap.error(f"channel set {n!r} has {len(ch)} channels; the HIP path supports at most 16")
+        name = lambda ref, n: f"{reference_dir(ref)}/{n}" if n else reference_dir(ref)      # noqa: E731
+        cfgs = {name(ref, n): dict(cfg, channels=list(ch), norm_reference=ref) for n, ch in sets_.items() for ref in refs}
+        results, wall = run_experiments(run_output_dir, device, all_channel_names, cfgs, rank, world)
+        if rank == 0:
+            paired = {n: {ref: results[name(ref, n)] for ref in refs} for n in sets_}
+            path = write_normalisation(run_output_dir, normalisation(paired, refs, cfg["data_path"], cfg["subjects"]),
+                                       synthetic=bool(cfg.get("synthetic")))
+            print(f"Normalisation-reference table written to: {path}")
     elif len(kinds) > 1:
         # one job: every (kind, set) is a configuration of its own — own fold batches and streams, shared splits and seeds
         sets_ = sets or {"": list(cfg["channels"])}
