@@ -103,6 +103,9 @@ DA_MAX_BATCH = 256    # msig_da.h MSIG_DA_MAX_BATCH: rows of one discriminator s
 WA_ABI_VERSION = 1    # include/msig_wa.h MSIG_WA_ABI_VERSION (weight averaging: the shadow's update)
 EN_ABI_VERSION = 1    # include/msig_en.h MSIG_EN_ABI_VERSION (deep ensembles: the reduction of the members' logits)
 EN_MAX_MEMBERS = 256  # msig_en.h MSIG_EN_MAX_MEMBERS: members of one ensemble
+KD_ABI_VERSION = 1    # include/msig_kd.h MSIG_KD_ABI_VERSION (distillation: the teacher table and the train step's distillation term)
+KD_MAX_MEMBERS = 256  # msig_kd.h MSIG_KD_MAX_MEMBERS: members of one teacher
+KD_MIN_T, KD_MAX_T = 1.0 / 64.0, 64.0      # msig_kd.h: the temperature's range
 NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
 
 
@@ -162,6 +165,13 @@ class Da(C.Structure):
                 ("dom", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64), ("params", C.c_void_p), ("exp_avg", C.c_void_p),
                 ("exp_avg_sq", C.c_void_p), ("stats", C.c_void_p), ("stride_bytes", C.c_int64), ("lambda", C.c_float * MAX_FOLDS),
                 ("lr", C.c_float * MAX_FOLDS), ("step", C.c_int64 * MAX_FOLDS)]
+
+
+class Kd(C.Structure):
+    """msig_kd (include/msig_kd.h): the distillation term of a launch — its weight and temperature, the teacher table and the
+    batch's store positions, the optional statistics, and (fold batch) the bytes between the folds' tables and statistics."""
+    _fields_ = [("alpha", C.c_float), ("temperature", C.c_float), ("q", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64),
+                ("stats", C.c_void_p), ("stride_bytes", C.c_int64)]
 
 
 class Wa(C.Structure):
@@ -371,6 +381,19 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} has msig_en.h ABI {L.msig_en_abi_version()}; this binding is {EN_ABI_VERSION}: rebuild the library")
         L.msig_en_reduce.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.msig_en_reduce_multi.argtypes = [vp, C.POINTER(Multi), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        # include/msig_kd.h, exported by the same library: the teacher table and the train steps with the distillation term
+        L.msig_kd_abi_version.restype = C.c_int
+        L.msig_kd_struct_bytes.restype = C.c_int64
+        if L.msig_kd_abi_version() != KD_ABI_VERSION or L.msig_kd_struct_bytes() != C.sizeof(Kd):
+            raise RuntimeError(f"{LIB_PATH} has msig_kd.h ABI {L.msig_kd_abi_version()} with msig_kd of {L.msig_kd_struct_bytes()} bytes; "
+                               f"this binding is {KD_ABI_VERSION} with {C.sizeof(Kd)}: rebuild the library")
+        L.msig_kd_teacher.argtypes = [vp, i64, i32, i32, i32, f32, vp, vp]
+        L.msig_kd_teacher_multi.argtypes = [vp, C.POINTER(Multi), i32, i32, f32, vp, vp]
+        L.msig_kd_apply.argtypes = [C.POINTER(Kd), vp, vp, i32, i32, f32, vp]
+        L.msig_kd_apply_multi.argtypes = [C.POINTER(Kd), C.POINTER(Multi), vp, vp, i32, i32, C.POINTER(f32), vp]
+        L.msig_kd_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_kd_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), vp, vp, f32, f32,
+                                               f32, f32, i64, vp]
         # include/msig_nr.h, exported by the same library: per-subject normalisation with the statistics of reference windows
         L.msig_nr_abi_version.restype = C.c_int
         if L.msig_nr_abi_version() != NR_ABI_VERSION:
@@ -524,6 +547,23 @@ def check_mix_lambda(value) -> float:
     if not 0.0 <= v <= 1.0:
         raise ValueError(f"mix_lambda must be a number in [0, 1], got {value!r}")
     return C.c_float(v).value
+
+
+def check_distill(alpha, temperature):
+    """The host-side checks of a distillation setting (include/msig_kd.h): alpha a number in [0, 1] and the temperature one in
+    [1/64, 64], returned as the fp32 values the calls will see.  ValueError otherwise."""
+    out = []
+    for name, value, lo, hi in (("alpha", alpha, 0.0, 1.0), ("temperature", temperature, KD_MIN_T, KD_MAX_T)):
+        if isinstance(value, (str, bytes, bool)):
+            raise ValueError(f"a distillation {name} must be a number in [{lo:g}, {hi:g}], got {value!r}")
+        try:
+            v = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"a distillation {name} must be a number in [{lo:g}, {hi:g}], got {value!r}") from None
+        if not lo <= v <= hi:
+            raise ValueError(f"a distillation {name} must be a number in [{lo:g}, {hi:g}], got {value!r}")
+        out.append(C.c_float(v).value)
+    return tuple(out)
 
 
 def check_average_coef(value) -> float:

@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h and msig_da.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h and msig_kd.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -14,6 +14,7 @@
 #include "finetune.h"
 #include "../../include/msig_ab.h"
 #include "../../include/msig_mc.h"
+#include "../../include/msig_kd.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -317,8 +318,10 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
-  const bool head_step = head_step_applies(b, c.d);
+  // distillation (include/msig_kd.h) needs WS_LOGITS and WS_DLOGITS complete between the criterion and the head's backward: unfused
+  const bool head_step = !o.kd && head_step_applies(b, c.d);
   if ((rc = forward_fc(b, fc, st, o, !head_step))) return rc;
+  if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
@@ -510,20 +513,26 @@ static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, 
   return forward_fc(b, fc, st, StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, nullptr, use ? &soft : nullptr});
 }
 static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* lam, DaArgs& da);
-// a: the subject discriminator of include/msig_da.h (NULL = msig_st_train_step[_multi] itself)
+// a: the subject discriminator of include/msig_da.h (NULL = msig_st_train_step[_multi] itself); k: the distillation term of
+// include/msig_kd.h (NULL, or alpha == 0 after its checks = msig_da_train_step[_multi] itself)
 static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
-                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a) {
+                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a,
+                         const msig_kd* k = nullptr) {
   SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
   if (!b) return MSIG_E_NULL;
   DaArgs da;
   if (a && (rc = make_da(a, fc, b->shape.B, soft.lam, da))) return rc;
+  KdArgs kd;
+  if (k && (rc = msig_kd_make_args(k, fc, b->shape.B, b->shape.K, soft.lam, kd))) return rc;
+  const bool distil = k && k->alpha != 0.f;
   ClipArgs cl;
   if (s->clip) {
     if (s->clip->kind != s->kind) return MSIG_E_SHAPE;
     if ((rc = make_clip(b, s->clip, fc.n, cl))) return rc;
   }
   return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st,
-                       StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr});
+                       StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr,
+                                distil ? &kd : nullptr});
 }
 extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
   return st_forward(b, single_fold(b), s, (hipStream_t)stream);
@@ -603,6 +612,20 @@ extern "C" int msig_da_train_step_multi(const msig_batch* b, const msig_multi* m
   if (!s) return MSIG_E_NULL;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, a);
+}
+
+// ---- distillation (include/msig_kd.h; kernels and the stand-alone calls: distill.hip) -----------------------------------------------
+extern "C" int msig_kd_train_step(const msig_batch* b, const msig_st* s, const msig_da* da, const msig_kd* kd, float* exp_avg,
+                                  float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                  void* stream) {
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd);
+}
+extern "C" int msig_kd_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* da, const msig_kd* kd,
+                                        float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
+                                        int64_t step, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

@@ -396,6 +396,7 @@ int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
 struct SoftArgs { float eps; float lam[MSIG_MAX_FOLDS]; };
 struct ClipArgs;
 struct DaArgs;
+struct KdArgs;
 // What a forward or a train step does beyond the msig.h call (host side only; api.hip's entry points fill it after their own checks).
 // Value-initialised = the plain call.  Each function that takes it reads only the fields named at its declaration.
 struct StepOpts {
@@ -404,6 +405,7 @@ struct StepOpts {
   const ClipArgs* clip;     // gradient-norm clipping (include/msig_gc.h) between the reduction and the Adam update
   const SoftArgs* soft;     // soft targets (include/msig_st.h); NULL = the plain criterion's kernels
   const DaArgs* da;         // subject discriminator (include/msig_da.h): one more launch after the head's
+  const KdArgs* kd;         // distillation (include/msig_kd.h): the unfused head with one more launch between ce and head_bwd
 };
 // reads o.cw, o.soft.  mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of
 // b->dropout_thr although b->training = 0
@@ -428,6 +430,22 @@ struct DaArgs {
   float lambda[MSIG_MAX_FOLDS], lam[MSIG_MAX_FOLDS], lr_over_bc1[MSIG_MAX_FOLDS], inv_sqrt_bc2[MSIG_MAX_FOLDS];
 };
 int launch_da_step(const DaArgs& a, const float* feat, float* dfeat, const FoldCtx& fc, hipStream_t st);
+// Distillation (include/msig_kd.h, distill.hip): msig_kd after its checks (msig_kd_make_args), by value to the launch.  q / stats are
+// fold slot 0's, `stride` bytes apart per slot; B rows of K; om = 1.f - alpha, kappa = (float)((double)alpha * T / B), t2 = T * T in
+// fp64; lam = the folds' mixup weights.  One launch, between ce_kernel and head_bwd_kernel, on WS_LOGITS / WS_DLOGITS.
+struct msig_kd;
+struct KdArgs {
+  int32_t B, K;
+  const float* q; const int64_t* idx; int64_t idx_row_stride;
+  double* stats;
+  int64_t stride;
+  float alpha, T, om, kappa;
+  double t2;
+  float lam[MSIG_MAX_FOLDS];
+};
+// every check of msig_kd.h's own arguments, before any launch; fc: the folds of the launch (stride != 0: a fold batch); lam per fold
+int msig_kd_make_args(const msig_kd* k, const FoldCtx& fc, int32_t B, int32_t K, const float* lam, KdArgs& kd);
+int launch_kd_apply(const KdArgs& a, const float* logits, float* dlogits, const FoldCtx& fc, hipStream_t st);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch

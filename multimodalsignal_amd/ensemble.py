@@ -419,6 +419,48 @@ class Ensemble:
             L.check(lib.msig_en_reduce(stack.data_ptr(), N * K, M, N, K, *outputs(0), st), "msig_en_reduce")
         return out
 
+    @torch.no_grad()
+    def teacher(self, x, temperature: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The distillation teacher rows of the windows x (include/msig_kd.h): (N, K) float32, row n the mean over
+        the members of softmax(logits / temperature) in fp64, summed in member order and rounded once.  predict()'s chunked eval
+        forwards; with batched=True and M <= MAX_FOLDS msig_kd_teacher_multi reads the logits where the forward left them, otherwise
+        they are collected into one (M, N, K) stack for msig_kd_teacher.  All routes give the same bits, and at temperature 1 they
+        are predict()'s mean_p.  `out`: an (N, K) float32 device tensor to fill (rows of a larger table)."""
+        x = self._check_x(x)
+        _, temperature = L.check_distill(0.0, temperature)
+        N, _, T = x.shape
+        M, K, dev, lib = self.M, self.K, self.device, L.lib()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        pieces = [(i, min(self.eval_batch, N - i)) for i in range(0, N, self.eval_batch)]
+        self._arenas(T, [b for _, b in pieces])
+        if out is None:
+            out = torch.empty((N, K), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (N, K) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous float32 ({N}, {K}) tensor on {dev}, got {out.dtype} {tuple(out.shape)}")
+        in_place = self.batched and M <= L.MAX_FOLDS
+        stack = None if in_place else torch.empty((M, N, K), dtype=torch.float32, device=dev)
+        for m0 in range(0, M, self.slots):
+            n = min(self.slots, M - m0)
+            self._load(m0, n)
+            for i, b in pieces:
+                for s in range(n):
+                    self._view(s, "x", torch.float32)[:b * self.C * T].copy_(x[i:i + b].reshape(-1))
+                if self.batched:
+                    multi = self._multi(n)
+                    L.check(lib.msig_st_forward_multi(C.byref(self._desc(b)), C.byref(multi), C.byref(self._st), st), "msig_st_forward_multi")
+                    if in_place:
+                        L.check(lib.msig_kd_teacher_multi(self._logits(0, b).data_ptr(), C.byref(multi), b, K, temperature,
+                                                          out[i:].data_ptr(), st), "msig_kd_teacher_multi")
+                else:
+                    for s in range(n):
+                        L.check(lib.msig_st_forward(C.byref(self._desc(b, s)), C.byref(self._st), st), "msig_st_forward")
+                if stack is not None:
+                    for s in range(n):
+                        stack[m0 + s, i:i + b].copy_(self._logits(s, b))
+        if stack is not None:
+            L.check(lib.msig_kd_teacher(stack.data_ptr(), N * K, M, N, K, temperature, out.data_ptr(), st), "msig_kd_teacher")
+        return out
+
 
 # ---- what the driver does with a fold's replicas ------------------------------------------------------------------------------------
 def fold_ensemble(models: Sequence, x, y, eval_batch: int = 1024) -> dict:

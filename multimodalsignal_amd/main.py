@@ -33,6 +33,7 @@ from .mixup import Mixup
 from . import adversary as adversary_mod
 from . import averaging as averaging_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask
+from . import distill as distill_mod
 from . import ensemble as ensemble_mod
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
@@ -181,9 +182,12 @@ def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_
 
 def train_fold(prep, device):
     """The reference's per-fold body (main.py:116-125) on the current HIP stream.  prep["test_pass"] False: no test pass — the
-    caller evaluates the trained model itself (run_hierarchical_experiment)."""
+    caller evaluates the trained model itself (run_hierarchical_experiment).  prep["distill"]: a distill.Distillation with the
+    fold's teacher table — the fold trains as a student, as a fold batch of such preps does."""
     train_loader, val_loader, test_loader = prep["loaders"]
     trainer = prep["trainer"] = Trainer(prep["model"], prep["fold_dir"], prep["config"])
+    if prep.get("distill") is not None:
+        trainer.set_distillation(prep["distill"])
     t0 = time.time()
     trainer.train(train_loader, val_loader)
     acc, f1 = trainer.evaluate(test_loader, is_test=True)[1:] if prep.get("test_pass", True) else (None, None)
@@ -422,6 +426,108 @@ def ensemble_units(members, local, epochs, units, cfgs, seeds, rank=0):
               f"{r['ensemble']['mean_disagreement']:.4f}", flush=True)
 
 
+def _test_windows(prep):
+    """(x, y) of a prep's TEST subject on the device, in store order."""
+    loader = prep["loaders"][2]
+    pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=loader.store.device)
+    return loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+
+
+def distill_units(members, units, cfgs, out_dir, stores, seeds, kd, train_cfg, device, all_channel_names, rank=0):
+    """--distill: per (configuration, fold) of the rank, once its `seeds` replicas have finished, the fold's
+    teacher table — its test-pass models as an ensemble.Ensemble in eval mode, ensemble.Ensemble.teacher at the setting's
+    temperature, on the store positions of the fold's TRAINING subjects (every other row stays zero and is never read) — and then
+    the fold's student: one more unit of configuration replica_name(n, 0) + "/distilled" with replica 0's unit seed, split and
+    every training option, trained like any unit (train_units: fold batches per configuration, or sequentially) with the
+    distillation term on.  The students write the usual per-fold files under distilled/fold_test_on_<sid>/; replica 0's fold
+    directory gets distilled_result.json: ensemble, mean member, replica 0 and student on the test subject's windows."""
+    from .ensemble import Ensemble, ensemble_metrics
+    base_units = sorted(u for u in members if u % seeds == 0)
+    sunits, preps, teachers = {}, {}, {}
+    for u0 in base_units:
+        n, k = units[u0]
+        models = [members[u0 + r]["model"] for r in range(seeds)]
+        tr = members[u0]["loaders"][0]
+        pos = tr.index if tr.index is not None else torch.arange(len(tr.dataset), device=tr.store.device)
+        t0 = time.time()
+        table = torch.zeros((int(tr.store.shape[0]), int(cfgs[n]["num_classes"])), dtype=torch.float32, device=tr.store.device)
+        table.index_copy_(0, pos, Ensemble(models, eval_batch=members[u0]["loaders"][2].batch_size).teacher(tr.store.index_select(0, pos), kd.temperature))
+        torch.cuda.synchronize(device)
+        teachers[u0] = (table, time.time() - t0)
+        sunits[u0] = (distill_mod.student_name(n), k)
+    groups = {}
+    for u0 in base_units:
+        groups.setdefault(sunits[u0][0], []).append(u0)
+
+    def make(u0):
+        n, k = units[u0]
+        p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n] / "distilled", device, all_channel_names, dict(cfgs[n], replica=0), stores[n])
+        p["distill"] = distill_mod.Distillation(kd.alpha, kd.temperature)
+        p["distill"].set_teacher(teachers[u0][0])
+        preps[u0] = p
+        return p
+
+    infos = dict(train_units(base_units, list(groups.values()), make, train_cfg, device))
+    for u0 in base_units:
+        n, k = units[u0]
+        p0, info = members[u0], infos[u0]
+        x, y = _test_windows(p0)
+        r = ensemble_mod.fold_ensemble([members[u0 + r]["model"] for r in range(seeds)], x, y, eval_batch=p0["loaders"][2].batch_size)
+        sp = Ensemble([preps[u0]["model"]], eval_batch=p0["loaders"][2].batch_size).predict(x)
+        win, mem = r["windows"], r["member_windows"]
+        yy = np.asarray(win["y"], dtype=np.int64)
+        student = {"mean_p": sp.mean_p.double().cpu().tolist(), "entropy": sp.entropy.double().cpu().tolist(),
+                   "mutual_info": sp.mutual_info.double().cpu().tolist()}
+        en_pred = np.asarray(win["mean_p"]).argmax(axis=1)
+
+        def row(w):
+            m = ensemble_metrics(w["mean_p"], yy, w["entropy"], w["mutual_info"])
+            return dict(accuracy=m["accuracy"], f1=m["f1_score"], nll=m["nll"], brier=m["brier"], ece=m["ece"],
+                        fidelity=distill_mod.fidelity(np.asarray(w["mean_p"]).argmax(axis=1), en_pred))
+        rows = [row(w) for w in mem]
+        last = info["history"][-1] if info["history"] else {}
+        doc = dict(subject=p0["subject"], fold=k, members=seeds, alpha=kd.alpha, temperature=kd.temperature, n=int(yy.size),
+                   ensemble=row(win), mean_member={m: float(np.mean([rw[m] for rw in rows])) for m in rows[0]}, replica0=rows[0],
+                   student=row(student), kd_loss=last.get("kd_loss"), kd_agreement=last.get("kd_agreement"), student_epochs=info["epochs"],
+                   teacher_seconds=teachers[u0][1], student_seconds=info["seconds"],
+                   windows=dict(y=win["y"], ensemble=win, members=mem, student=student))
+        (p0["fold_dir"] / "distilled_result.json").write_text(json.dumps(doc))
+        tag = f"{n}/" if n else ""
+        print(f"[rank {rank}] {tag}fold {k} ({p0['subject']}) distilled from {seeds} member(s): student acc {doc['student']['accuracy']:.4f} "
+              f"fidelity {doc['student']['fidelity']:.4f} | replica 0 acc {doc['replica0']['accuracy']:.4f} | ensemble acc "
+              f"{doc['ensemble']['accuracy']:.4f}", flush=True)
+
+
+def write_distillation_tables(base, out_dir, results, kd, seeds):
+    """distillation.txt / distillation.json of every configuration of a --distill run, from the folds' distilled_result.json, which
+    every rank has written before the fold metrics were gathered: per fold and pooled over all test windows."""
+    from .ensemble import ensemble_metrics
+    paths = []
+    for n, cfg in base.items():
+        files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "distilled_result.json" for r in results[n]]
+        docs = [json.loads(f.read_text()) for f in files if f.exists()]
+        if not docs:
+            continue
+        y = np.concatenate([np.asarray(d["windows"]["y"], dtype=np.int64) for d in docs])
+        cat = lambda pick, key: np.concatenate([np.asarray(pick(d)[key], dtype=np.float64) for d in docs])
+        en_pred = cat(lambda d: d["windows"]["ensemble"], "mean_p").argmax(axis=1)
+
+        def row(pick):
+            p = cat(pick, "mean_p")
+            m = ensemble_metrics(p, y, cat(pick, "entropy"), cat(pick, "mutual_info"))
+            return dict(accuracy=m["accuracy"], f1=m["f1_score"], nll=m["nll"], brier=m["brier"], ece=m["ece"],
+                        fidelity=distill_mod.fidelity(p.argmax(axis=1), en_pred))
+        rows = [row(lambda d, i=i: d["windows"]["members"][i]) for i in range(seeds)]
+        pooled = dict(ensemble=row(lambda d: d["windows"]["ensemble"]), mean_member={m: float(np.mean([rw[m] for rw in rows])) for m in rows[0]},
+                      replica0=rows[0], student=row(lambda d: d["windows"]["student"]))
+        kdl = [d["kd_loss"] for d in docs if d.get("kd_loss") is not None]
+        if kdl:
+            pooled.update(kd_loss=float(np.mean(kdl)), kd_agreement=float(np.mean([d["kd_agreement"] for d in docs if d.get("kd_agreement") is not None])))
+        folds = [{k: v for k, v in d.items() if k not in ("windows", "teacher_seconds", "student_seconds")} for d in docs]
+        paths.append(distill_mod.write_distillation(out_dir[n], folds, kd, seeds, pooled=pooled, synthetic=bool(cfg.get("synthetic"))))
+    return paths
+
+
 def write_seed_tables(run_output_dir, base, out_dir, results, seeds):
     """seeds.txt / seeds.json of a --seeds run, from the gathered per-replica results and the folds' ensemble_result.json, which
     every rank has written before the fold metrics were gathered."""
@@ -576,6 +682,9 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     # configuration, ensemble.replica_name(n, r) — r = 0 the configuration itself, r >= 1 writing to its seed_<r>/ — that shares the
     # SubjectStore; a rank holds all replicas of the folds it holds.  base: the configurations as given (absent or 1: all of this is off)
     S, base = int(cfg0.get("seeds") or 1), cfgs
+    # --distill (cfg["distill"]): after a fold's replicas, its student — one more unit, trained against the
+    # replicas' ensemble; absent: off, and every unit, arena, launch, file and bit is what it was
+    kd = distill_mod.Distillation.parse(cfg0["distill"]) if cfg0.get("distill") is not None else None
     if S > 1:
         cfgs = {ensemble_mod.replica_name(n, r): dict(c, replica=r) for n, c in base.items() for r in range(S)}
     stores = subject_stores(cfgs, all_channel_names, device)
@@ -596,7 +705,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
         if (n_cal or adapt or attr or mc) and not cfgs[n].get("replica"):      # the post-LOSO passes run on replica 0 only
             kept[u] = p
-        if S > 1:
+        if S > 1 or kd is not None:
             members[u] = p
         return p
 
@@ -620,6 +729,8 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     emulate, gdev = cfg0.get("emulate_rank"), cfg0.get("gather_device", device)
     if S > 1:                                        # each fold's S test-pass models as an ensemble on its test subject, before the gather
         ensemble_units(members, local, epochs, units, cfgs, S, rank)
+    if kd is not None:                               # each fold's teacher table and student, likewise before the gather
+        distill_units(members, units, cfgs, out_dir, stores, S, kd, cfg0, device, all_channel_names, rank)
     # a rank holds ceil(folds / world) folds with all their replicas: the gather's rows per rank are sized for that
     n_rows = len(units) if S == 1 else -(-(len(units) // S) // world) * S * world
     allm = dict(local) if emulate else gather_fold_metrics(local, n_rows, world, gdev)
@@ -647,6 +758,9 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
             print(f"Seed-replica and ensemble table written to: {path}")
         results = {n: results[n] for n in base}
         cfgs = base
+    if kd is not None and (rank == 0 or emulate):
+        for path in write_distillation_tables(base, out_dir, results, kd, S):
+            print(f"Distillation table written to: {path}")
     if rank == 0 or emulate:
         write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr, uncertain=mc)
     return results, wall
@@ -1016,6 +1130,13 @@ def parse_args(ap, argv=None):
         ap.error(f"--seeds: {e}")
     if args.seeds > 1 and args.hierarchical:
         ap.error("--seeds runs with the standard LOSO, --model, --ablation and --sweep (not --hierarchical)")
+    if args.distill is not None:
+        try:
+            args.distill = distill_mod.Distillation.parse(args.distill).spec()
+        except ValueError as e:
+            ap.error(f"--distill: {e}")
+        if args.hierarchical:
+            ap.error("--distill runs with the standard LOSO, --model, --ablation and --sweep (not --hierarchical)")
     try:
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
@@ -1202,6 +1323,14 @@ def build_parser():
                          "LOSO and --model comparison runs; may be combined with --calibrate, --adapt-bn and --attribute, each on its own "
                          "against the LOSO model)")
     ap.add_argument("--mc-seed", type=int, default=None, metavar="SEED", help="seed of the Monte-Carlo dropout masks (default 0)")
+    ap.add_argument("--distill", nargs="?", const="0.5:2", default=None, metavar="ALPHA[:T]",
+                    help="after each fold's --seeds S replicas (S >= 1; S = 1 is born-again self-distillation) train one student of the "
+                         "fold against their ensemble's tempered probabilities as well as the labels: weight ALPHA in [0, 1] of the "
+                         "teacher's term (T^2 KL at temperature T in [1/64, 64], default 2) and 1 - ALPHA of the criterion; without a "
+                         "value 0.5:2.  The student has replica 0's seed, split and every training option (ALPHA 0 reproduces replica 0 "
+                         "bit for bit), trains as one more fold-batch unit and writes its per-fold files under distilled/; "
+                         "distilled_result.json per fold and distillation.txt / distillation.json compare ensemble, mean member, "
+                         "replica 0 and student (not with --hierarchical)")
     ap.add_argument("--seeds", type=int, default=1, metavar="S",
                     help="train S seed replicas (1..64) of every fold as fold-batch units: the same train / validation split, unit seed "
                          "SEED + fold + r * 1000003 for replica r (initialisation, shuffle order, dropout, augmentation and mixup draws). "
@@ -1251,6 +1380,8 @@ def build_cfg(args, kinds):
         cfg.update(mc_dropout=args.mc_dropout, mc_seed=args.mc_seed, synthetic=args.synthetic is not None)
     if args.seeds > 1:                 # likewise: --seeds 1 is the run without the flag
         cfg.update(seeds=args.seeds, synthetic=args.synthetic is not None)
+    if args.distill is not None:       # likewise
+        cfg.update(distill=args.distill, synthetic=args.synthetic is not None)
     if args.norm_reference is not None:      # likewise; several values: the list, which main() turns into one configuration each
         refs = list(args.norm_reference)
         cfg.update(norm_reference=refs[0] if len(refs) == 1 else refs, synthetic=args.synthetic is not None)

@@ -70,6 +70,8 @@ def fold_result(prep, trainer, accuracy, f1_score, seconds, averaging=None):
                 train_windows_per_s=trainer.train_windows / max(trainer.train_seconds, 1e-9), history=trainer.history)
     if getattr(trainer, "adversary", None) is not None:      # config['adversary']: what main.write_adversary tabulates
         info["adversary_domains"] = trainer.adversary.S
+    if getattr(trainer, "distill", None) is not None:        # a student (prep["distill"]): its setting beside the history's kd_* entries
+        info["distillation"] = dict(alpha=trainer.distill.alpha, temperature=trainer.distill.temperature)
     if averaging is not None:
         info["averaging"] = averaging
     if prep.get("test_pass", True):
@@ -154,6 +156,11 @@ class LockstepTrainer:
         if self.adv_S is not None:
             A.check_batch_size(tr0.batch_size)
         self.dom_stats = {}
+        # distillation (prep["distill"]: a distill.Distillation with the fold's teacher table, include/msig_kd.h): alpha and the
+        # temperature are the launch's, so the folds of a batch share them; every fold's table lives in the arena set's own block
+        self.kd_cfg = _shared([None if p.get("distill") is None else (p["distill"].alpha, p["distill"].temperature) for p in preps],
+                              "distillation setting", str)
+        self.kd_stats = {}
         # weight averaging (config['averaging'], include/msig_wa.h): the folds of a batch share one setting (the launches after a
         # step and the per-epoch passes are the batch's); coefficients and counters are per fold.  The shadows are arena regions.
         self.avg_cfg = _shared([AV.settings(p["config"].get("averaging")) for p in preps], "averaging setting", repr)
@@ -161,7 +168,8 @@ class LockstepTrainer:
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
                                adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip,
                                adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])),
-                               averaging=self.avg_cfg is not None)
+                               averaging=self.avg_cfg is not None,
+                               distill=None if self.kd_cfg is None else int(tr0.store.shape[0]))
         if self.clip:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
@@ -183,6 +191,8 @@ class LockstepTrainer:
                 model._engine.scatter()                        # into the padded layout, once: the steps train it in place
             if self.adv_S is not None:
                 t.prepare_adversary(p["loaders"][0], self.arena.adversary_storage(slot))
+            if self.kd_cfg is not None:
+                t.set_distillation(p["distill"], self.arena.distill_storage(slot))
             self.trainers.append(t)
         # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
         # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
@@ -284,6 +294,8 @@ class LockstepTrainer:
         if advs is not None:
             arena.adversary_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
             dl = [[a.lam_at(a.step + 1 + k, a.total_steps) for k in range(ns)] for a, ns in zip(advs, n_steps)]
+        if self.kd_cfg is not None:
+            arena.distill_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
         # weight averaging: EMA's coefficient of every step of the epoch per fold, from the fold's own update count
         avs = [t.averager for t in trs] if self.avg_cfg is not None else None
         ema = avs is not None and self.avg_cfg["mode"] == "ema"
@@ -308,8 +320,9 @@ class LockstepTrainer:
                                   arena.soft(sl, self.smoothing, None, self.cw, arena.clip(sl, self.cw) if self.clip else None),
                                   None if advs is None else arena.da(sl, self.adv_S, [0.0] * nr, [lrs[r0 + j] * advs[r0 + j].lr_mult for j in range(nr)],
                                                                      [1] * nr, h0["betas"], eps, wd),
-                                  arena.wa(sl, [0.0] * nr) if ema else None)
-            m, s, a, w = runs[(r0, nr)]
+                                  arena.wa(sl, [0.0] * nr) if ema else None,
+                                  None if self.kd_cfg is None else arena.kd(*self.kd_cfg))
+            m, s, a, w, kd = runs[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
                 if aug is not None:
@@ -322,8 +335,13 @@ class LockstepTrainer:
                 a.idx, a.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
             self._gather(loaders[0], order, r0, i, b, m, aug, s.lam if aug is not None or mix is not None else None)
             _, desc = self._layout(b, True)
-            L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, ea, eas,
-                                                 b1, b2, eps, wd, int(steps[r0][k]), st), "msig_da_train_step_multi")
+            if kd is not None:                 # a batch of students: the same call with the distillation term (alpha 0: the call below)
+                kd.idx, kd.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+                L.check(lib.msig_kd_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, C.byref(kd),
+                                                     ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_kd_train_step_multi")
+            else:
+                L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, ea, eas,
+                                                     b1, b2, eps, wd, int(steps[r0][k]), st), "msig_da_train_step_multi")
             if w is not None:                  # EMA: one launch over the same folds, each at its own coefficient
                 for j in range(nr):
                     w.coef[j] = wc[r0 + j][k]
@@ -344,6 +362,10 @@ class LockstepTrainer:
                 a.step += ns
                 a.last_lambda = lams[-1] if lams else a.last_lambda
                 self.dom_stats[f] = a.epoch_summary(st3[f])
+        if self.kd_cfg is not None:        # likewise, only for a batch of students
+            st3 = arena.distill_stats().cpu().numpy()
+            for f, t in zip(act, trs):
+                self.kd_stats[f] = t.distill.epoch_summary(st3[f])
         if not self.clip:
             return self.acc[:, 0].cpu().numpy()               # the epoch's only sync
         # the same sync: the loss sums and the folds' gradient-norm statistics in one read-back
@@ -435,7 +457,7 @@ class LockstepTrainer:
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
                     if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f),
-                                           avg_vals.get(f)):
+                                           avg_vals.get(f), self.kd_stats.get(f)):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start

@@ -6,8 +6,9 @@ buffers, the BatchNorm buffers and a cache of workspaces, builds the
 stream.  It holds no arithmetic of its own.
 
 The host never chooses among entry points: every train step is msig_da_train_step[_multi], every forward msig_st_forward[_multi],
-the widest of each form.  The headers make that bit-safe — a NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL
-class_weight each give the narrower call with its launches, `kind` selects the model — and tests/test_step_dispatch_gpu.py pins it.
+the widest of each form (a student's step, include/msig_kd.h, is msig_kd_train_step[_multi]).  The headers make that bit-safe — a
+NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL class_weight each give the narrower call with its launches, `kind`
+selects the model — and tests/test_step_dispatch_gpu.py pins it.
 """
 from __future__ import annotations
 
@@ -381,7 +382,7 @@ class Engine:
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
                    dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
-                   label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None) -> None:
+                   label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None, distill=None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
@@ -396,11 +397,15 @@ class Engine:
         advances its own step count.  batch_index: the int64 store positions of the rows (DeviceLoader.last_index) by which the
         adversary's domain table is read; None = the table has one entry per row.  The discriminator's Adam takes THIS call's betas,
         eps and weight_decay (L2 decay included) and lr * adversary.lr_mult.  None = no adversary.  One library call whatever is
-        on (module docstring)."""
+        on (module docstring).
+        distill: a distill.Distillation bound to this device (include/msig_kd.h): the head runs unfused and one more
+        launch blends the gradient of the tempered KL term against the teacher rows — read by batch_index, or one per row — into
+        the logits' gradient; the reported loss stays the criterion's, the term's own statistics go to distill.stats.  None, or
+        alpha = 0, is the call without it, bit for bit; the call is then msig_kd_train_step."""
         cw, max_norm, smooth, lam = self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
-        if adversary is not None:
-            if x.shape[0] > L.DA_MAX_BATCH:
-                raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
+        if adversary is not None and x.shape[0] > L.DA_MAX_BATCH:
+            raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
+        if adversary is not None or distill is not None:
             if batch_index is not None:
                 _require_gpu(batch_index, "batch_index")
                 if batch_index.dtype != torch.int64 or not batch_index.is_contiguous() or batch_index.numel() != x.shape[0]:
@@ -412,11 +417,22 @@ class Engine:
             adversary.last_lambda = adversary.next_lambda()
             a = C.byref(adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1],
                                              idx=None if batch_index is None else batch_index.data_ptr(), betas=betas, eps=eps, weight_decay=weight_decay))
-        L.check(L.lib().msig_da_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, self.exp_avg.data_ptr(),
-                                           self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
-                "msig_da_train_step")
+        if distill is not None:
+            if distill.q is None or distill.q.shape[1] != self.K or not distill.q.is_cuda or not distill.stats.is_cuda:
+                raise ValueError(f"distill needs a (positions, {self.K}) teacher table bound to {self.device}: set_teacher, then bind")
+            if batch_index is None and distill.q.shape[0] < x.shape[0]:
+                raise ValueError(f"a teacher table read by row needs {x.shape[0]} rows, got {distill.q.shape[0]}")
+            k = distill.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
+            L.check(L.lib().msig_kd_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, C.byref(k), self.exp_avg.data_ptr(),
+                                               self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
+                    "msig_kd_train_step")
+        else:
+            L.check(L.lib().msig_da_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, self.exp_avg.data_ptr(),
+                                               self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
+                    "msig_da_train_step")
         if adversary is not None:
             adversary.step += 1
+        if adversary is not None or distill is not None:
             self._keep = self._keep + (batch_index,)
 
     def features(self, x: torch.Tensor, padded: bool = False) -> torch.Tensor:
@@ -545,13 +561,13 @@ class EmbeddedEngine(Engine):
         return self.small_views(self.avg_params.index_select(0, self.index))
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
-                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None):
+                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None):
         self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
         if adversary is not None:
             adversary.restrict_features(self.hidden)       # nothing may reach the padded feature columns (their units must stay zero)
         self.scatter()
         super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm, label_smoothing,
-                           mix_lambda, adversary, batch_index)
+                           mix_lambda, adversary, batch_index, distill)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -579,7 +595,8 @@ class FoldArena:
 
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
                  adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
-                 grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None, averaging: bool = False):
+                 grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None, averaging: bool = False,
+                 distill: Optional[int] = None):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
@@ -592,7 +609,10 @@ class FoldArena:
         `averaging`: the arenas also hold every fold's weight-averaging shadow (include/msig_wa.h) — "avg_params", "avg_bn_state",
         "avg_bn_count" — after every other region, "gc" included: INSIDE the arenas, at the arena stride, because that is the only
         place the *_multi forward can read an averaged model from (`batch(..., shadow=True)`).  Without it the arenas and their
-        stride are what they are without this argument."""
+        stride are what they are without this argument.
+        `distill` = store positions: every fold also gets a distillation teacher table of positions x K float32 and three float64
+        statistics (include/msig_kd.h) in a memory block of their own, `kd_stride` bytes apart (`distill_storage`), as the
+        adversary's buffers are owned; the model arenas and their stride stay what they are without it."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -632,6 +652,14 @@ class FoldArena:
                 self.da_off[name] = (self.da_stride, nbytes)
                 self.da_stride += (nbytes + 255) // 256 * 256
             self.da_mem = torch.zeros((n, self.da_stride), dtype=torch.uint8, device=self.device)
+        self.kd_off, self.kd_stride, self.kd_mem = {}, 0, None
+        if distill is not None:
+            if int(distill) < 1:
+                raise ValueError(f"distill takes the number of store positions (>= 1), got {distill!r}")
+            for name, nbytes in (("stats", 24), ("q", int(distill) * num_classes * 4)):
+                self.kd_off[name] = (self.kd_stride, nbytes)
+                self.kd_stride += (nbytes + 255) // 256 * 256
+            self.kd_mem = torch.zeros((n, self.kd_stride), dtype=torch.uint8, device=self.device)
 
     @staticmethod
     def workspace_bytes(train_batch: int, eval_batch: int, in_channels: int, T: int, num_classes: int) -> int:
@@ -699,6 +727,29 @@ class FoldArena:
         """(n, 3) float64 strided view of every fold's adversary statistics."""
         o = self.da_off["stats"][0] // 8
         return self.da_mem.view(torch.float64)[:, o:o + 3]
+
+    def distill_storage(self, slot: int) -> dict:
+        """The distillation buffers of the fold in arena `slot` (distill.Distillation.bind): typed views of its `kd_mem` row."""
+        if self.kd_mem is None:
+            raise RuntimeError("this FoldArena was built without distill=positions: it has no teacher tables")
+        dt = {"stats": torch.float64, "q": torch.float32}
+        return {name: self.kd_mem[slot, o:o + nb].view(dt[name]) for name, (o, nb) in self.kd_off.items()}
+
+    def kd(self, alpha: float, temperature: float) -> L.Kd:
+        """msig_kd of a launch (include/msig_kd.h): fold slot 0's teacher table and statistics, `kd_stride` apart.  idx /
+        idx_row_stride are the launch's to fill in.  Checked on the host: ValueError before anything is launched."""
+        if self.kd_mem is None:
+            raise RuntimeError("this FoldArena was built without distill=positions: it has no teacher tables")
+        k = L.Kd()
+        k.alpha, k.temperature = L.check_distill(alpha, temperature)
+        base = self.kd_mem.data_ptr()
+        k.q, k.stats, k.stride_bytes = base + self.kd_off["q"][0], base + self.kd_off["stats"][0], self.kd_stride
+        return k
+
+    def distill_stats(self) -> torch.Tensor:
+        """(n, 3) float64 strided view of every fold's distillation statistics."""
+        o = self.kd_off["stats"][0] // 8
+        return self.kd_mem.view(torch.float64)[:, o:o + 3]
 
     def set_class_weight(self, slot: int, values) -> None:
         """Writes the class-weight vector of the fold in arena `slot` (K values, checked on the host: ValueError before anything is

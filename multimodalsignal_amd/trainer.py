@@ -191,6 +191,8 @@ class Trainer:
         # subject-adversarial training (include/msig_da.h): the settings now, the discriminator when the training set is known
         self.adversary_cfg = A.settings(config.get("adversary"))
         self.adversary = None
+        # distillation (include/msig_kd.h): a distill.Distillation with its teacher table, bound by set_distillation; None: off
+        self.distill = None
         # weight averaging (include/msig_wa.h): the fold's averager (settings and counters); the shadow itself is the engine's
         self.averaging_cfg = AV.settings(config.get("averaging"))
         self.averager = AV.WeightAverager(self.averaging_cfg) if self.averaging_cfg is not None else None
@@ -272,6 +274,20 @@ class Trainer:
         self._log(f"subject adversary: {adv.S} domains, lambda {adv.lam:g} ({adv.schedule}), lr x {adv.lr_mult:g}")
         return adv
 
+    def set_distillation(self, distillation, storage=None):
+        """Turns the fold into a student: `distillation` is a distill.Distillation whose teacher table covers the
+        store positions the training loader gathers from (the loader must serve `last_index`).  Every train step then carries the
+        distillation term; history and the epoch line gain kd_loss and kd_agreement; validation, the scheduler, early stopping and
+        best_model.pt keep following the criterion against the labels.  storage: one fold's distillation buffers of a FoldArena."""
+        if distillation.q is None:
+            raise ValueError("the distillation has no teacher table: call set_teacher first")
+        if int(distillation.q.shape[1]) != int(self.model.num_classes):
+            raise ValueError(f"the teacher table has {int(distillation.q.shape[1])} classes, the model {self.model.num_classes}")
+        self.distill = distillation.bind(self.device, storage)
+        self._log(f"distillation: alpha {distillation.alpha:g}, temperature {distillation.temperature:g}, "
+                  f"teacher table of {int(distillation.q.shape[0])} positions")
+        return self.distill
+
     # ---- trainer.py:119-191 -------------------------------------------------------------------
     def train(self, train_loader, val_loader):
         eng = self.model.engine()
@@ -279,6 +295,9 @@ class Trainer:
         self._check_labels(val_loader)
         self.prepare_class_weights(train_loader)
         adv = self.prepare_adversary(train_loader)
+        kd = self.distill
+        if kd is not None and not hasattr(train_loader, "last_index"):
+            raise ValueError("distillation needs a training loader that serves the store positions of its batches (last_index)")
         av = self.averager
         if av is not None:
             eng.average_update(av.bind(eng).start_coef())      # EMA: the shadow starts as a copy of the initial model; SWA: no launch
@@ -291,6 +310,8 @@ class Trainer:
                 eng.zero_grad_stats()
             if adv is not None:
                 adv.stats.zero_()
+            if kd is not None:
+                kd.stats.zero_()
             n_steps = 0
             for inputs, labels in train_loader:
                 n_steps += 1
@@ -301,7 +322,8 @@ class Trainer:
                                step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
                                class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
                                mix_lambda=getattr(train_loader, "last_lam", None),      # the lam of the batch a mixup loader just served
-                               adversary=adv, batch_index=getattr(train_loader, "last_index", None) if adv is not None else None)
+                               adversary=adv, distill=kd,
+                               batch_index=getattr(train_loader, "last_index", None) if adv is not None or kd is not None else None)
                 if av is not None and av.mode == "ema":
                     eng.average_update(av.step_coef())
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
@@ -311,6 +333,7 @@ class Trainer:
                 acc, stats = eng.loss_and_grad_stats()
                 train_loss, grad = acc[0] / n_train, grad_norm_summary(stats, n_steps)
             dom = adv.epoch_summary(adv.stats.cpu().tolist()) if adv is not None else None
+            kds = kd.epoch_summary(kd.stats.cpu().tolist()) if kd is not None else None
             dt = time.time() - t0
             self.train_windows += n_train
             self.train_seconds += dt
@@ -318,7 +341,7 @@ class Trainer:
                 eng.average_update(av.epoch_coef(epoch + 1))     # the epoch-end iterate, from start_epoch on (before: no launch)
             val_loss, val_acc, val_f1, _, _ = self.evaluate(val_loader, is_val=True)
             avg = self.validate_averaged(val_loader) if av is not None and av.validate else None
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg):
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds):
                 break
         self.finish_averaging([train_loader])
         self._finish_training()
@@ -343,11 +366,12 @@ class Trainer:
         if recompute and av.bn == "recompute":
             AV.recompute_bn([eng], train_loaders)
 
-    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None) -> bool:
+    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None, kd=None) -> bool:
         """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
         the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were.
         dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise.  avg: the validation pass under
-        the averaging shadow when config['averaging']['validate'] is set (three more history keys; it steers nothing)."""
+        the averaging shadow when config['averaging']['validate'] is set (three more history keys; it steers nothing).  kd:
+        Distillation.epoch_summary of the epoch for a student (set_distillation): kd_loss and kd_agreement, likewise."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
@@ -359,6 +383,10 @@ class Trainer:
         if dom is not None:
             self.history[-1].update(dom)
             suffix += f" | domain loss: {dom['domain_loss']:.4f} | domain acc: {dom['domain_acc']:.4f} | lambda: {dom['adversary_lambda']:.4f}"
+        if kd is not None:
+            self.history[-1].update(kd)
+            if kd["kd_loss"] is not None:
+                suffix += f" | kd loss: {kd['kd_loss']:.4f} | kd agreement: {kd['kd_agreement']:.4f}"
         if avg is not None:
             self.history[-1].update(avg)
             if avg["val_loss_avg"] is not None:
