@@ -25,6 +25,7 @@ import torch
 from . import _lib as L
 from .calibrate import summarise
 from .multifold import launch_plan
+from .runtime import Arenas, make_batch, workspace_need
 from .trainer import accuracy_and_weighted_f1
 
 SYNTHETIC_NOTE = ("WESAD is absent: the synthetic set has no subject shift by construction, so this table shows that the adaptation "
@@ -54,7 +55,7 @@ def batch_plan(sizes: Sequence[int], batch: int):
     return [(i, b, [order[r] for r in range(r0, r0 + nr)]) for i, b, r0, nr in launch_plan([int(sizes[j]) for j in order], int(batch))]
 
 
-class BnAdapter:
+class BnAdapter(Arenas):
     """Adapts the BatchNorm statistics of one model, or of several as a fold batch (one set of launches per batch for all of them).
 
     jobs: dicts with
@@ -81,68 +82,34 @@ class BnAdapter:
                 raise ValueError(f"expected a non-empty float32 (N, {e.C}, T) GPU tensor, got {x.dtype} {tuple(x.shape)} on {x.device}")
             if (e.kind, e.gru_layers, e.C, e.K, e.n_flat, x.shape[2]) != (e0.kind, e0.gru_layers, e0.C, e0.K, e0.n_flat, x0.shape[2]):
                 raise ValueError("the folds of an adapter share the model kind, depth, channels, classes and window length")
-        self.kind, self.C, self.K, self.T, self.device = e0.kind, e0.C, e0.K, int(x0.shape[2]), e0.device
-        self.n = len(self.jobs)
+        self.kind, self.C, self.K, self.T = e0.kind, e0.C, e0.K, int(x0.shape[2])
         self.sizes = [int(j["x"].shape[0]) for j in self.jobs]
         self.batch = max(1, min(int(eval_batch), max(self.sizes)))
         self.eval_batch = max(1, int(eval_batch))
-        # the EVALUATION workspace layout is all the calls need; it is not monotonic in B (runtime.FoldArena.workspace_bytes)
-        cand = [self.batch] + ([191 * 16] if self.batch >= 192 * 16 else [])
-        self.ws_bytes = max(L.workspace_layout(c, self.C, self.T, self.K, False)[-1] for c in cand)
-        sizes = [("params", e0.n_flat * 4), ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16), ("x", self.batch * self.C * self.T * 4),
-                 ("ws", self.ws_bytes), ("ab", L.AB_ACC_DOUBLES * 8)]
-        self.off, at = {}, 0
-        for name, nbytes in sizes:
-            self.off[name] = (at, nbytes)
-            at += (nbytes + 255) // 256 * 256
-        self.stride = at
-        self.mem = torch.zeros((self.n, self.stride), dtype=torch.uint8, device=self.device)
+        self.ws_bytes = workspace_need([self.batch], self.C, self.T, self.K, False)        # the EVALUATION layout is all the calls need
+        super().__init__(len(self.jobs), e0.device, [("params", e0.n_flat * 4), ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16),
+                                                     ("x", self.batch * self.C * self.T * 4), ("ws", self.ws_bytes), ("ab", L.AB_ACC_DOUBLES * 8)])
         self._ran = False
-
-    def view(self, slot: int, name: str, dtype=torch.uint8) -> torch.Tensor:
-        o, nb = self.off[name]
-        return self.mem[slot, o:o + nb].view(dtype)
-
-    def ptr(self, name: str, slot: int = 0) -> int:
-        return self.mem.data_ptr() + slot * self.stride + self.off[name][0]
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _desc(self, B: int, slot: int = 0) -> L.Batch:
         """The eval descriptor of a batch of B windows in arena `slot` (the *_multi calls are given arena 0's)."""
-        b = L.Batch()
-        b.shape = L.Shape(B, self.C, self.T, self.K)
-        b.training, b.bn_momentum, b.bn_eps = 0, 0.1, 1e-5
-        b.x, b.labels = self.ptr("x", slot), None
-        b.params, b.grads = self.ptr("params", slot), None
-        b.bn_state, b.bn_count = self.ptr("bn_state", slot), self.ptr("bn_count", slot)
-        b.ws, b.ws_bytes = self.ptr("ws", slot), self.ws_bytes
-        b.gru_layers = self.engines[0].gru_layers
-        L.apply_forms(b)
-        return b
-
-    def _multi(self, slots) -> L.Multi:
-        m = L.Multi()
-        m.n, m.stride_bytes, m.form_folds = len(slots), self.stride, 1
-        for i, s in enumerate(slots):
-            m.slot[i] = int(s)
-        return m
+        return make_batch(B, self.C, self.T, self.K, *(self.ptr(r, slot) for r in ("x", "params", "bn_state", "bn_count", "ws")), self.ws_bytes,
+                          self.engines[0].gru_layers)
 
     def _stage(self, stage: int):
-        lib, st, kind = L.lib(), self._stream(), L.FT_KINDS[self.kind]
+        lib, st, kind = L.lib(), self.stream(), L.FT_KINDS[self.kind]
         for i, b, slots in batch_plan(self.sizes, self.batch):
             for s in slots:
                 self.view(s, "x", torch.float32)[:b * self.C * self.T].copy_(self.jobs[s]["x"][i:i + b].reshape(-1))
             if self.batched:
-                L.check(lib.msig_ab_accumulate_multi(C.byref(self._desc(b)), C.byref(self._multi(slots)), kind, stage, self.ptr("ab"), st),
+                L.check(lib.msig_ab_accumulate_multi(C.byref(self._desc(b)), C.byref(self.multi(slots)), kind, stage, self.ptr("ab"), st),
                         "msig_ab_accumulate_multi")
             else:
                 for s in slots:
                     L.check(lib.msig_ab_accumulate(C.byref(self._desc(b, s)), kind, stage, self.ptr("ab", s), st), "msig_ab_accumulate")
         if self.batched:
             L.check(lib.msig_ab_commit_multi(self.ptr("ab"), stage, self.alpha, self.ptr("bn_state"), self.ptr("bn_state"),
-                                             C.byref(self._multi(range(self.n))), st), "msig_ab_commit_multi")
+                                             C.byref(self.multi(range(self.n))), st), "msig_ab_commit_multi")
         else:
             for s in range(self.n):
                 L.check(lib.msig_ab_commit(self.ptr("ab", s), stage, self.alpha, self.ptr("bn_state", s), self.ptr("bn_state", s), st),

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .runtime import Arenas
 from .trainer import accuracy_and_weighted_f1
 
 DEFAULT_GAP = 5          # real WESAD windows are 60 s at a 10 s stride: windows up to 5 apart share samples
@@ -66,7 +67,7 @@ def epoch_orders(n: int, epochs: int, seed: int) -> np.ndarray:
     return np.stack([rs.permutation(n) for _ in range(epochs)]).astype(np.int32) if epochs else np.zeros((0, n), np.int32)
 
 
-class HeadCalibrator:
+class HeadCalibrator(Arenas):
     """Calibrates the classifier of one model, or of several (a fold batch: one launch per epoch for all of them).
 
     jobs: dicts with
@@ -94,33 +95,17 @@ class HeadCalibrator:
         for e in self.engines:
             if (e.K, e.n_flat, e.layout[L.P_CLS0_W]) != (e0.K, e0.n_flat, e0.layout[L.P_CLS0_W]):
                 raise ValueError("the folds of a calibrator share K and the parameter layout")
-        self.K, self.n_flat, self.cls_offset, self.device = e0.K, e0.n_flat, e0.layout[L.P_CLS0_W], e0.device
+        self.K, self.n_flat, self.cls_offset = e0.K, e0.n_flat, e0.layout[L.P_CLS0_W]
         self.dropout_p = float(m0.dropout_p if dropout is None else dropout)
-        self.n = len(self.jobs)
         self.n_cal = [int(j["y_cal"].numel()) for j in self.jobs]
         if min(self.n_cal) < 1:
             raise ValueError("a calibration set is empty")
         n_max = max(self.n_cal)
-        sizes = [("params", self.n_flat * 4), ("exp_avg", self.n_flat * 4), ("exp_avg_sq", self.n_flat * 4), ("feat", n_max * 512),
-                 ("labels", n_max * 8), ("order", max(1, self.epochs) * n_max * 4), ("cw", self.K * 4), ("acc", max(1, self.epochs) * 16)]
-        self.off, at = {}, 0
-        for name, nbytes in sizes:
-            self.off[name] = (at, nbytes)
-            at += (nbytes + 255) // 256 * 256
-        self.stride = at
-        self.mem = torch.zeros((self.n, self.stride), dtype=torch.uint8, device=self.device)
+        super().__init__(len(self.jobs), e0.device,
+                         [("params", self.n_flat * 4), ("exp_avg", self.n_flat * 4), ("exp_avg_sq", self.n_flat * 4), ("feat", n_max * 512),
+                          ("labels", n_max * 8), ("order", max(1, self.epochs) * n_max * 4), ("cw", self.K * 4), ("acc", max(1, self.epochs) * 16)])
         self.weighted = any(j.get("class_weight") is not None for j in self.jobs)
         self._ran = False
-
-    def view(self, slot: int, name: str, dtype=torch.uint8) -> torch.Tensor:
-        o, nb = self.off[name]
-        return self.mem[slot, o:o + nb].view(dtype)
-
-    def ptr(self, name: str, slot: int = 0, byte_offset: int = 0) -> int:
-        return self.mem.data_ptr() + slot * self.stride + self.off[name][0] + byte_offset
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- the frozen extractor -------------------------------------------------------------------------------------------
     def _features(self, eng, x):
@@ -158,7 +143,7 @@ class HeadCalibrator:
         if self._ran:
             raise RuntimeError("a HeadCalibrator runs once (its Adam state and step counts are those of one calibration)")
         self._ran = True
-        lib, st = L.lib(), self._stream()
+        lib, st = L.lib(), self.stream()
         before = []
         for s, (j, eng) in enumerate(zip(self.jobs, self.engines)):
             if getattr(eng, "scatter", None) is not None:

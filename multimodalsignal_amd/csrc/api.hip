@@ -383,26 +383,25 @@ extern "C" int msig_train_step_multi(const msig_batch* b, const msig_multi* m, f
 
 // ---- class-weighted CrossEntropy (include/msig_cw.h): the same calls with the weight vector passed down to the loss kernels ----
 extern "C" int msig_cw_abi_version(void) { return MSIG_CW_ABI_VERSION; }
-static inline bool cw_misaligned(const float* cw) { return ((uintptr_t)cw & 3) != 0; }
 
 extern "C" int msig_cw_forward(const msig_batch* b, const float* class_weight, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   return forward_fc(b, single_fold(b), (hipStream_t)stream, StepOpts{class_weight});
 }
 extern "C" int msig_cw_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
                        StepOpts{class_weight});
 }
 extern "C" int msig_cw_forward_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return forward_fc(b, fc, (hipStream_t)stream, StepOpts{class_weight});
 }
 extern "C" int msig_cw_train_step_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, StepOpts{class_weight});
 }
@@ -412,7 +411,7 @@ extern "C" int msig_cg_abi_version(void) { return MSIG_CG_ABI_VERSION; }
 extern "C" int msig_cg_param_layout(int C, int K, int64_t* off) { return param_layout(C, K, off, false); }
 
 extern "C" int msig_cg_forward(const msig_batch* b, const float* class_weight, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   return forward_fc(b, single_fold(b), (hipStream_t)stream, StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_backward(const msig_batch* b, const float* dlogits, void* stream) {
@@ -420,18 +419,18 @@ extern "C" int msig_cg_backward(const msig_batch* b, const float* dlogits, void*
 }
 extern "C" int msig_cg_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   return train_step_fc(b, single_fold(b), &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
                        StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_forward_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return forward_fc(b, fc, (hipStream_t)stream, StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_train_step_multi(const msig_batch* b, const msig_multi* m, const float* class_weight, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (cw_misaligned(class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(class_weight, 3)) return MSIG_E_ALIGN;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return train_step_fc(b, fc, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream,
                        StepOpts{class_weight, true});
@@ -462,7 +461,7 @@ static int make_clip(const msig_batch* b, const msig_gc_clip* g, int n, ClipArgs
     if (!(g->max_norm[i] > 0.0)) return MSIG_E_SHAPE;                   // NaN included
   if (!g->state) return MSIG_E_NULL;
   if ((uintptr_t)g->state & 7) return MSIG_E_ALIGN;
-  if (cw_misaligned(g->class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(g->class_weight, 3)) return MSIG_E_ALIGN;
   const int64_t cap = gc_partials(b->shape.C, b->shape.K, g->kind);
   if (cap < 0) return (int)cap;
   if (g->state_bytes < (MSIG_GC_NSTAT + cap) * (int64_t)sizeof(double)) return MSIG_E_WORKSPACE;
@@ -505,7 +504,7 @@ static int make_soft(const msig_st* s, int n, SoftArgs& soft, bool& use) {
     use = use || s->lam[i] != 1.f;
   }
   for (int i = n; i < MSIG_MAX_FOLDS; ++i) soft.lam[i] = 1.f;
-  if (cw_misaligned(s->class_weight)) return MSIG_E_ALIGN;
+  if (msig_misaligned(s->class_weight, 3)) return MSIG_E_ALIGN;
   return 0;
 }
 static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, hipStream_t st) {

@@ -1,49 +1,16 @@
 // include/msig_kd.h: the teacher table of an ensemble's tempered probabilities and the distillation term of a train step — one
 // launch between ce_kernel and head_bwd_kernel that blends the teacher's gradient into MSIG_WS_DLOGITS.
 // Both kernels stream: a few hundred bytes per row, no MFMA, no LDS tiling.
-#include <math.h>
-#include "msig_dev.h"
-#include "../../include/msig_kd.h"
+#include "member_stats.h"
 
 #define KD_THREADS 256
 
 int msig_multi_fold_ctx(const msig_multi* m, FoldCtx& fc);                                  // api.hip: msig_multi's own checks
 
-// where member m's block starts, in floats from `logits`: (n_slots ? slot[m] : m) * stride
-struct KdWhere {
-  int64_t stride;
-  int32_t n_slots;
-  int32_t slot[MSIG_MAX_FOLDS];
-};
-
-// ------------------------------------------------------------------------------------
-// Teacher: one workgroup per window n, all of it in fp64 — en_reduce_kernel's first two phases with every logit divided by T.
-//   phase 1  thread m < M: p_m = softmax of member m's row n over T (max-subtracted) into LDS;
-//   phase 2  thread k < K: q[n][k] = (sum_m p_m[k]) / M in increasing m, rounded to fp32 on store.
-// At T = 1 the division is exact and the statements are en_reduce_kernel's for mean_p: the same bits.
-// ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(KD_THREADS) void kd_teacher_kernel(const float* __restrict__ logits, const KdWhere wh, int M, int K, double T,
-                                                                float* __restrict__ q) {
-  __shared__ double ps[MSIG_KD_MAX_MEMBERS * MSIG_MAX_K];
-  const int64_t n = blockIdx.x;
-  const int tid = threadIdx.x;
-  if (tid < M) {
-    const int64_t blk = wh.n_slots ? (int64_t)wh.slot[tid] : (int64_t)tid;
-    const float* __restrict__ row = logits + blk * wh.stride + n * K;
-    double u[MSIG_MAX_K], e[MSIG_MAX_K];
-    for (int k = 0; k < K; ++k) u[k] = (double)row[k] / T;
-    double mx = u[0];
-    for (int k = 1; k < K; ++k) if (u[k] > mx) mx = u[k];
-    double sum = 0.0;
-    for (int k = 0; k < K; ++k) { e[k] = exp(u[k] - mx); sum += e[k]; }
-    for (int k = 0; k < K; ++k) ps[tid * K + k] = e[k] / sum;
-  }
-  __syncthreads();
-  if (tid < K) {
-    double acc = 0.0;
-    for (int s = 0; s < M; ++s) acc += ps[s * K + tid];
-    q[n * K + tid] = (float)(acc / (double)M);
-  }
+// Teacher: member_stats (member_stats.h) on the logits over T, its mean alone — q[n][k] rounded to fp32 on store
+__global__ __launch_bounds__(MEMBER_THREADS) void kd_teacher_kernel(const float* __restrict__ logits, const MemberWhere wh, int M, int K,
+                                                                    double T, float* __restrict__ q) {
+  member_stats<true, MEMBER_MEAN, false>(logits, wh, M, K, T, q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------
@@ -125,7 +92,6 @@ int launch_kd_apply(const KdArgs& a, const float* logits, float* dlogits, const 
 }
 
 // ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
-static inline bool kd_mis(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
 static inline bool kd_bad_temperature(float T) { return !(T >= 1.f / 64.f && T <= 64.f); }      // NaN included
 
 extern "C" int msig_kd_abi_version(void) { return MSIG_KD_ABI_VERSION; }
@@ -144,8 +110,8 @@ int msig_kd_make_args(const msig_kd* k, const FoldCtx& fc, int32_t B, int32_t K,
     if (!(lam[i] >= 0.f && lam[i] <= 1.f)) return MSIG_E_SHAPE;
     kd.lam[i] = lam[i];
   }
-  if (kd_mis(k->q, 3)) return MSIG_E_ALIGN;
-  if (kd_mis(k->stats, 7) || kd_mis(k->idx, 7)) return MSIG_E_ALIGN;
+  if (msig_misaligned(k->q, 3)) return MSIG_E_ALIGN;
+  if (msig_misaligned(k->stats, 7) || msig_misaligned(k->idx, 7)) return MSIG_E_ALIGN;
   if (multi && (k->stride_bytes <= 0 || (k->stride_bytes & 255))) return MSIG_E_ALIGN;
   kd.B = B; kd.K = K;
   kd.q = k->q; kd.idx = k->idx; kd.idx_row_stride = multi ? k->idx_row_stride : 0;
@@ -162,7 +128,7 @@ static int kd_apply(const msig_kd* k, const FoldCtx& fc, const float* logits, fl
                     hipStream_t st) {
   if (!logits || !dlogits) return MSIG_E_NULL;
   KdArgs kd; int rc = msig_kd_make_args(k, fc, B, K, lam, kd); if (rc) return rc;
-  if (kd_mis(logits, 3) || kd_mis(dlogits, 3)) return MSIG_E_ALIGN;
+  if (msig_misaligned(logits, 3) || msig_misaligned(dlogits, 3)) return MSIG_E_ALIGN;
   return launch_kd_apply(kd, logits, dlogits, fc, st);
 }
 extern "C" int msig_kd_apply(const msig_kd* kd, const float* logits, float* dlogits, int32_t B, int32_t K, float lam, void* stream) {
@@ -175,30 +141,18 @@ extern "C" int msig_kd_apply_multi(const msig_kd* kd, const msig_multi* m, const
   return kd_apply(kd, fc, logits, dlogits, B, K, lam, (hipStream_t)stream);
 }
 
-static int kd_teacher(const float* logits, const KdWhere& wh, int32_t M, int32_t max_members, int32_t N, int32_t K, float T, float* q,
-                      hipStream_t st) {
-  if (!logits || !q) return MSIG_E_NULL;
-  if (N < 1 || M < 1 || M > max_members || K < 2 || K > MSIG_MAX_K) return MSIG_E_SHAPE;
-  if ((int64_t)M * N >= ((int64_t)1 << 31)) return MSIG_E_SHAPE;
-  if (wh.stride < (int64_t)N * K) return MSIG_E_SHAPE;
-  if (kd_bad_temperature(T)) return MSIG_E_SHAPE;
-  if (kd_mis(logits, 3) || kd_mis(q, 3)) return MSIG_E_ALIGN;
-  MSIG_K("kd_teacher", st);
-  kd_teacher_kernel<<<dim3((unsigned)N), KD_THREADS, 0, st>>>(logits, wh, M, K, (double)T, q);
-  MSIG_LAUNCH_CHECK();
-  return 0;
+static int kd_teacher(const float* logits, const MemberWhere& wh, int32_t M, int32_t max_members, int32_t N, int32_t K, float T, float* q,
+                      void* stream) {
+  return member_launch("kd_teacher", logits, M, max_members, N, K, wh.member_stride < (int64_t)N * K || kd_bad_temperature(T), {q},
+                       (hipStream_t)stream, [&](dim3 grid, dim3 block, hipStream_t st) {
+                         kd_teacher_kernel<<<grid, block, 0, st>>>(logits, wh, M, K, (double)T, q);
+                       });
 }
 extern "C" int msig_kd_teacher(const float* logits, int64_t member_stride_floats, int32_t M, int32_t N, int32_t K, float T, float* q,
                                void* stream) {
-  KdWhere wh{};
-  wh.stride = member_stride_floats;
-  return kd_teacher(logits, wh, M, MSIG_KD_MAX_MEMBERS, N, K, T, q, (hipStream_t)stream);
+  return kd_teacher(logits, member_where_stacked(member_stride_floats), M, MSIG_KD_MAX_MEMBERS, N, K, T, q, stream);
 }
 extern "C" int msig_kd_teacher_multi(const float* logits0, const msig_multi* m, int32_t N, int32_t K, float T, float* q, void* stream) {
   FoldCtx fc; const int rc = msig_multi_fold_ctx(m, fc); if (rc) return rc;
-  KdWhere wh{};
-  wh.stride = fc.stride / 4;                                 // stride_bytes is a multiple of 256
-  wh.n_slots = fc.n;
-  for (int i = 0; i < fc.n; ++i) wh.slot[i] = fc.slot[i];
-  return kd_teacher(logits0, wh, fc.n, MSIG_MAX_FOLDS, N, K, T, q, (hipStream_t)stream);
+  return kd_teacher(logits0, member_where_from_multi(fc), fc.n, MSIG_MAX_FOLDS, N, K, T, q, stream);
 }

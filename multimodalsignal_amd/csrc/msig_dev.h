@@ -351,6 +351,9 @@ __host__ __device__ inline StageDims make_dims(const msig_shape& s) {
   return d;
 }
 
+// a pointer argument that is not a multiple of mask + 1 bytes (NULL is aligned: optional pointers pass)
+inline bool msig_misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
+
 #define MSIG_LAUNCH_CHECK()                          \
   do {                                               \
     hipError_t e__ = hipGetLastError();              \

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .runtime import Arenas, make_batch, workspace_need
 from .uncertainty import COVERAGES, ECE_BINS, expected_calibration_error, window_metrics
 
 REPLICA_STRIDE = 1_000_003      # unit seed of replica r = the fold's seed + r * REPLICA_STRIDE (a prime far above any fold index)
@@ -284,7 +285,7 @@ class Ensemble:
                 self.bn_state[m].copy_(e.bn_state)
                 self.bn_count[m].copy_(e.bn_count)
         self._st = L.make_st(self.kind, 0.0)
-        self._arena_key, self.mem, self._loaded = None, None, None
+        self._arena_key, self.arenas, self._loaded = None, None, None
 
     @classmethod
     def from_run(cls, run_dir, subject: str, config_name: Optional[str] = None, device="cuda", **kw) -> "Ensemble":
@@ -316,57 +317,30 @@ class Ensemble:
         key = (T, tuple(sorted(set(sizes))))
         if key == self._arena_key:
             return
-        # the EVALUATION workspace layout is not monotonic in B (runtime.FoldArena.workspace_bytes): size for every piece that runs
-        self.ws_bytes = max(L.workspace_layout(b, self.C, T, self.K, False)[-1] for b in key[1])
-        self.off, at = {}, 0
-        for name, nbytes in (("params", self.n_flat * 4), ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16),
-                             ("x", max(key[1]) * self.C * T * 4), ("ws", self.ws_bytes)):
-            self.off[name] = (at, nbytes)
-            at += (nbytes + 255) // 256 * 256
-        self.stride, self.T = at, T
-        self.mem = torch.zeros((self.slots, self.stride), dtype=torch.uint8, device=self.device)
+        self.ws_bytes, self.T = workspace_need(key[1], self.C, T, self.K, False), T      # the evaluation layout, for every piece that runs
+        self.arenas = Arenas(self.slots, self.device, (("params", self.n_flat * 4), ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16),
+                                                       ("x", max(key[1]) * self.C * T * 4), ("ws", self.ws_bytes)))
         self._arena_key, self._loaded = key, None
 
-    def _view(self, slot: int, name: str, dtype=torch.uint8) -> torch.Tensor:
-        o, nb = self.off[name]
-        return self.mem[slot, o:o + nb].view(dtype)
-
-    def _ptr(self, name: str, slot: int = 0) -> int:
-        return self.mem.data_ptr() + slot * self.stride + self.off[name][0]
+    mem, off, stride = (property(lambda self, k=k: getattr(self.arenas, k, None)) for k in ("mem", "off", "stride"))      # the arenas' own
 
     def _load(self, m0: int, n: int):
         """Members m0 .. m0 + n - 1 into arenas 0 .. n - 1."""
         if self._loaded == (m0, n):
             return
         for s in range(n):
-            self._view(s, "params", torch.float32).copy_(self.params[m0 + s])
-            self._view(s, "bn_state", torch.float32).copy_(self.bn_state[m0 + s])
-            self._view(s, "bn_count", torch.int64)[:2].copy_(self.bn_count[m0 + s])
+            self.arenas.view(s, "params", torch.float32).copy_(self.params[m0 + s])
+            self.arenas.view(s, "bn_state", torch.float32).copy_(self.bn_state[m0 + s])
+            self.arenas.view(s, "bn_count", torch.int64)[:2].copy_(self.bn_count[m0 + s])
         self._loaded = (m0, n)
 
     def _desc(self, B: int, slot: int = 0) -> L.Batch:
-        b = L.Batch()
-        b.shape = L.Shape(B, self.C, self.T, self.K)
-        b.training, b.keep_for_backward, b.bn_momentum, b.bn_eps = 0, 0, 0.1, 1e-5
-        b.x, b.labels = self._ptr("x", slot), None
-        b.params, b.grads = self._ptr("params", slot), None
-        b.bn_state, b.bn_count = self._ptr("bn_state", slot), self._ptr("bn_count", slot)
-        b.ws, b.ws_bytes = self._ptr("ws", slot), self.ws_bytes
-        b.gru_layers = self.gru_layers
-        b.loss_acc, b.dx = None, None
-        L.apply_forms(b)
-        return b
-
-    def _multi(self, n: int) -> L.Multi:
-        m = L.Multi()
-        m.n, m.stride_bytes, m.form_folds = n, self.stride, 1
-        for i in range(n):
-            m.slot[i] = i
-        return m
+        return make_batch(B, self.C, self.T, self.K, *(self.arenas.ptr(r, slot) for r in ("x", "params", "bn_state", "bn_count", "ws")),
+                          self.ws_bytes, self.gru_layers)
 
     def _logits(self, slot: int, B: int) -> torch.Tensor:
-        o = self.off["ws"][0] + L.workspace_layout(B, self.C, self.T, self.K, False)[L.WS["LOGITS"]]
-        return self.mem[slot, o:o + B * self.K * 4].view(torch.float32).view(B, self.K)
+        o = L.workspace_layout(B, self.C, self.T, self.K, False)[L.WS["LOGITS"]]
+        return self.arenas.view(slot, "ws")[o:o + B * self.K * 4].view(torch.float32).view(B, self.K)
 
     def _check_x(self, x) -> torch.Tensor:
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != self.device:
@@ -375,14 +349,40 @@ class Ensemble:
             raise ValueError(f"expected float32 (N, {self.C}, T >= 16) input, got {x.dtype} {tuple(x.shape)}")
         return x.detach().contiguous()
 
+    def _reduce(self, x, in_slots, stacked):
+        """The members' eval forwards over x in chunks of members and pieces of windows, then the reduction: with batched=True and
+        M <= MAX_FOLDS `in_slots(logits0, multi, first window, windows, stream)` per piece, on the logits where
+        msig_st_forward_multi left them; otherwise the logits are collected into one (M, N, K) stack for `stacked(stack, stream)`."""
+        N, _, T = x.shape
+        M, K, lib, st = self.M, self.K, L.lib(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        pieces = [(i, min(self.eval_batch, N - i)) for i in range(0, N, self.eval_batch)]
+        self._arenas(T, [b for _, b in pieces])
+        in_place = self.batched and M <= L.MAX_FOLDS
+        stack = None if in_place else torch.empty((M, N, K), dtype=torch.float32, device=self.device)
+        for m0 in range(0, M, self.slots):
+            n = min(self.slots, M - m0)
+            self._load(m0, n)
+            for i, b in pieces:
+                for s in range(n):
+                    self.arenas.view(s, "x", torch.float32)[:b * self.C * T].copy_(x[i:i + b].reshape(-1))
+                if self.batched:
+                    multi = self.arenas.multi(range(n))
+                    L.check(lib.msig_st_forward_multi(C.byref(self._desc(b)), C.byref(multi), C.byref(self._st), st), "msig_st_forward_multi")
+                    if in_place:
+                        in_slots(self._logits(0, b).data_ptr(), multi, i, b, st)
+                else:
+                    for s in range(n):
+                        L.check(lib.msig_st_forward(C.byref(self._desc(b, s)), C.byref(self._st), st), "msig_st_forward")
+                if stack is not None:
+                    for s in range(n):
+                        stack[m0 + s, i:i + b].copy_(self._logits(s, b))
+        if stack is not None:
+            stacked(stack.data_ptr(), st)
+
     @torch.no_grad()
     def predict(self, x) -> EnsemblePrediction:
         x = self._check_x(x)
-        N, _, T = x.shape
-        M, K, dev, lib = self.M, self.K, self.device, L.lib()
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        pieces = [(i, min(self.eval_batch, N - i)) for i in range(0, N, self.eval_batch)]
-        self._arenas(T, [b for _, b in pieces])
+        N, M, K, dev, lib = x.shape[0], self.M, self.K, self.device, L.lib()
         out = EnsemblePrediction(
             mean_p=torch.empty((N, K), dtype=torch.float32, device=dev), std_p=torch.empty((N, K), dtype=torch.float32, device=dev),
             pred=torch.empty((N,), dtype=torch.int32, device=dev), entropy=torch.empty((N,), dtype=torch.float32, device=dev),
@@ -395,28 +395,10 @@ class Ensemble:
                     out.expected_entropy[i:].data_ptr(), out.mutual_info[i:].data_ptr(), out.votes[i:].data_ptr(),
                     out.member_pred[i:].data_ptr(), out.disagreement[i:].data_ptr())
 
-        in_place = self.batched and M <= L.MAX_FOLDS
-        stack = None if in_place else torch.empty((M, N, K), dtype=torch.float32, device=dev)
-        for m0 in range(0, M, self.slots):
-            n = min(self.slots, M - m0)
-            self._load(m0, n)
-            for i, b in pieces:
-                for s in range(n):
-                    self._view(s, "x", torch.float32)[:b * self.C * T].copy_(x[i:i + b].reshape(-1))
-                if self.batched:
-                    multi = self._multi(n)
-                    L.check(lib.msig_st_forward_multi(C.byref(self._desc(b)), C.byref(multi), C.byref(self._st), st), "msig_st_forward_multi")
-                    if in_place:
-                        L.check(lib.msig_en_reduce_multi(self._logits(0, b).data_ptr(), C.byref(multi), b, K, *outputs(i), st),
-                                "msig_en_reduce_multi")
-                else:
-                    for s in range(n):
-                        L.check(lib.msig_st_forward(C.byref(self._desc(b, s)), C.byref(self._st), st), "msig_st_forward")
-                if stack is not None:
-                    for s in range(n):
-                        stack[m0 + s, i:i + b].copy_(self._logits(s, b))
-        if stack is not None:
-            L.check(lib.msig_en_reduce(stack.data_ptr(), N * K, M, N, K, *outputs(0), st), "msig_en_reduce")
+        self._reduce(x,
+                     lambda logits0, multi, i, b, st: L.check(lib.msig_en_reduce_multi(logits0, C.byref(multi), b, K, *outputs(i), st),
+                                                              "msig_en_reduce_multi"),
+                     lambda stack, st: L.check(lib.msig_en_reduce(stack, N * K, M, N, K, *outputs(0), st), "msig_en_reduce"))
         return out
 
     @torch.no_grad()
@@ -428,37 +410,15 @@ class Ensemble:
         are predict()'s mean_p.  `out`: an (N, K) float32 device tensor to fill (rows of a larger table)."""
         x = self._check_x(x)
         _, temperature = L.check_distill(0.0, temperature)
-        N, _, T = x.shape
-        M, K, dev, lib = self.M, self.K, self.device, L.lib()
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        pieces = [(i, min(self.eval_batch, N - i)) for i in range(0, N, self.eval_batch)]
-        self._arenas(T, [b for _, b in pieces])
+        N, M, K, dev, lib = x.shape[0], self.M, self.K, self.device, L.lib()
         if out is None:
             out = torch.empty((N, K), dtype=torch.float32, device=dev)
         elif out.dtype != torch.float32 or tuple(out.shape) != (N, K) or not out.is_contiguous() or out.device != dev:
             raise ValueError(f"out must be a contiguous float32 ({N}, {K}) tensor on {dev}, got {out.dtype} {tuple(out.shape)}")
-        in_place = self.batched and M <= L.MAX_FOLDS
-        stack = None if in_place else torch.empty((M, N, K), dtype=torch.float32, device=dev)
-        for m0 in range(0, M, self.slots):
-            n = min(self.slots, M - m0)
-            self._load(m0, n)
-            for i, b in pieces:
-                for s in range(n):
-                    self._view(s, "x", torch.float32)[:b * self.C * T].copy_(x[i:i + b].reshape(-1))
-                if self.batched:
-                    multi = self._multi(n)
-                    L.check(lib.msig_st_forward_multi(C.byref(self._desc(b)), C.byref(multi), C.byref(self._st), st), "msig_st_forward_multi")
-                    if in_place:
-                        L.check(lib.msig_kd_teacher_multi(self._logits(0, b).data_ptr(), C.byref(multi), b, K, temperature,
-                                                          out[i:].data_ptr(), st), "msig_kd_teacher_multi")
-                else:
-                    for s in range(n):
-                        L.check(lib.msig_st_forward(C.byref(self._desc(b, s)), C.byref(self._st), st), "msig_st_forward")
-                if stack is not None:
-                    for s in range(n):
-                        stack[m0 + s, i:i + b].copy_(self._logits(s, b))
-        if stack is not None:
-            L.check(lib.msig_kd_teacher(stack.data_ptr(), N * K, M, N, K, temperature, out.data_ptr(), st), "msig_kd_teacher")
+        self._reduce(x,
+                     lambda logits0, multi, i, b, st: L.check(lib.msig_kd_teacher_multi(logits0, C.byref(multi), b, K, temperature,
+                                                                                        out[i:].data_ptr(), st), "msig_kd_teacher_multi"),
+                     lambda stack, st: L.check(lib.msig_kd_teacher(stack, N * K, M, N, K, temperature, out.data_ptr(), st), "msig_kd_teacher"))
         return out
 
 

@@ -236,6 +236,32 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
     return path
 
 
+def _windows(prep, loader=2, idx=None, labels=True):
+    """(x, y, pos) of one of a prep's loaders — 2, the TEST subject's, or 0, the training subjects' — on the device, in store order;
+    pos their store positions.  idx: positions within that order to take instead of all of them.  labels=False: y is None."""
+    ld = prep["loaders"][loader]
+    pos = ld.index if ld.index is not None else torch.arange(len(ld.dataset), device=ld.store.device)
+    if idx is not None:
+        pos = pos[torch.as_tensor(idx, device=pos.device)]
+    return ld.store.index_select(0, pos), ld.store_y.index_select(0, pos) if labels else None, pos
+
+
+def _tag(name):
+    """What a unit's printed lines put before "fold": the configuration's name and a slash, nothing for the unnamed one."""
+    return f"{name}/" if name else ""
+
+
+def _fold_batches(kept, units, cfgs):
+    """(configuration name, its cfg, chunk of at most MAX_FOLDS units) over the kept units in unit order, grouped by configuration in
+    order of first appearance: what calibrates or adapts as one fold batch."""
+    by_cfg = {}
+    for u in sorted(kept):
+        by_cfg.setdefault(units[u][0], []).append(u)
+    for n, us in by_cfg.items():
+        for c0 in range(0, len(us), L.MAX_FOLDS):
+            yield n, cfgs[n], us[c0:c0 + L.MAX_FOLDS]
+
+
 def calibration_settings(cfg):
     """The calibration settings of a configuration (--calibrate ...), as calibration.txt / calibration.json name them."""
     from .calibrate import DEFAULT_EPOCHS, DEFAULT_GAP
@@ -253,43 +279,34 @@ def calibrate_units(kept, units, cfgs, device, rank=0):
     best_model.pt, fold_result.json and the LOSO summary are untouched; each fold directory gets calibration_result.json.
     Returns {unit: ((acc, f1) before, (acc, f1) after, (n_cal, n_eval))}."""
     from .calibrate import HeadCalibrator, calibration_split
-    out, by_cfg = {}, {}
-    for u in sorted(kept):
-        by_cfg.setdefault(units[u][0], []).append(u)
-    for n, us in by_cfg.items():
-        cfg = cfgs[n]
-        st = calibration_settings(cfg)
-        for c0 in range(0, len(us), L.MAX_FOLDS):
-            chunk, jobs = us[c0:c0 + L.MAX_FOLDS], []
-            for u in chunk:
-                p = kept[u]
-                loader, model = p["loaders"][2], p["model"]
-                labels = np.asarray(loader.dataset.labels).astype(np.int64)
-                try:
-                    cal_idx, eval_idx = calibration_split(labels, st["windows_per_class"], st["gap"])
-                except ValueError as e:
-                    raise ValueError(f"--calibrate {st['windows_per_class']}: test subject {p['subject']}: {e}") from None
-                pos = loader.index if loader.index is not None else torch.arange(len(labels), device=device)
-                take = lambda idx: (loader.store.index_select(0, pos[torch.as_tensor(idx, device=device)]),
-                                    loader.store_y.index_select(0, pos[torch.as_tensor(idx, device=device)]))
-                (xc, yc), (xe, ye) = take(cal_idx), take(eval_idx)
-                cw = p["trainer"].class_weight if p.get("trainer") is not None else None
-                fold_seed = cfg["seed"] + p["fold"]
-                jobs.append(dict(model=model, x_cal=xc, y_cal=yc, x_eval=xe, y_eval=ye, lr=st["lr"],
-                                 seed=(model._seed ^ 0xCA11B8A7E) % (1 << 64), shuffle_seed=fold_seed + 7919,
-                                 class_weight=None if cw is None else cw.cpu().numpy()))
-            cal = HeadCalibrator(jobs, epochs=st["epochs"], batch_size=st["batch_size"], weight_decay=st["weight_decay"],
-                                 batched=bool(cfg.get("calibration_batched", True)), eval_batch=kept[chunk[0]]["loaders"][2].batch_size)
-            for u, r in zip(chunk, cal.run()):
-                p = kept[u]
-                r = dict(subject=p["subject"], settings=st, **r)
-                (p["fold_dir"] / "calibration_result.json").write_text(json.dumps(r))
-                tag = f"{n}/" if n else ""
-                print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) calibration on {r['n_cal']} windows, remainder {r['n_eval']}: "
-                      f"acc {r['before']['accuracy']:.4f} -> {r['after']['accuracy']:.4f}  f1 {r['before']['f1_score']:.4f} -> "
-                      f"{r['after']['f1_score']:.4f}", flush=True)
-                out[u] = ((r["before"]["accuracy"], r["before"]["f1_score"]), (r["after"]["accuracy"], r["after"]["f1_score"]),
-                          (float(r["n_cal"]), float(r["n_eval"])))
+    out = {}
+    for n, cfg, chunk in _fold_batches(kept, units, cfgs):
+        st, jobs = calibration_settings(cfg), []
+        for u in chunk:
+            p = kept[u]
+            loader, model = p["loaders"][2], p["model"]
+            labels = np.asarray(loader.dataset.labels).astype(np.int64)
+            try:
+                cal_idx, eval_idx = calibration_split(labels, st["windows_per_class"], st["gap"])
+            except ValueError as e:
+                raise ValueError(f"--calibrate {st['windows_per_class']}: test subject {p['subject']}: {e}") from None
+            (xc, yc, _), (xe, ye, _) = _windows(p, idx=cal_idx), _windows(p, idx=eval_idx)
+            cw = p["trainer"].class_weight if p.get("trainer") is not None else None
+            fold_seed = cfg["seed"] + p["fold"]
+            jobs.append(dict(model=model, x_cal=xc, y_cal=yc, x_eval=xe, y_eval=ye, lr=st["lr"],
+                             seed=(model._seed ^ 0xCA11B8A7E) % (1 << 64), shuffle_seed=fold_seed + 7919,
+                             class_weight=None if cw is None else cw.cpu().numpy()))
+        cal = HeadCalibrator(jobs, epochs=st["epochs"], batch_size=st["batch_size"], weight_decay=st["weight_decay"],
+                             batched=bool(cfg.get("calibration_batched", True)), eval_batch=kept[chunk[0]]["loaders"][2].batch_size)
+        for u, r in zip(chunk, cal.run()):
+            p = kept[u]
+            r = dict(subject=p["subject"], settings=st, **r)
+            (p["fold_dir"] / "calibration_result.json").write_text(json.dumps(r))
+            print(f"[rank {rank}] {_tag(n)}fold {p['fold']} ({p['subject']}) calibration on {r['n_cal']} windows, remainder {r['n_eval']}: "
+                  f"acc {r['before']['accuracy']:.4f} -> {r['after']['accuracy']:.4f}  f1 {r['before']['f1_score']:.4f} -> "
+                  f"{r['after']['f1_score']:.4f}", flush=True)
+            out[u] = ((r["before"]["accuracy"], r["before"]["f1_score"]), (r["after"]["accuracy"], r["after"]["f1_score"]),
+                      (float(r["n_cal"]), float(r["n_eval"])))
     return out
 
 
@@ -306,30 +323,23 @@ def adapt_units(kept, units, cfgs, device, rank=0):
     are untouched; each fold directory gets adaptation_result.json.
     Returns {unit: ((acc, f1) before, (acc, f1) after, (n, 0.0))}."""
     from .adapt import BnAdapter
-    out, by_cfg = {}, {}
-    for u in sorted(kept):
-        by_cfg.setdefault(units[u][0], []).append(u)
-    for n, us in by_cfg.items():
-        cfg = cfgs[n]
-        st = adaptation_settings(cfg)
-        for c0 in range(0, len(us), L.MAX_FOLDS):
-            chunk, jobs = us[c0:c0 + L.MAX_FOLDS], []
-            for u in chunk:
-                loader = kept[u]["loaders"][2]
-                pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=device)
-                jobs.append(dict(model=kept[u]["model"], x=loader.store.index_select(0, pos), y=loader.store_y.index_select(0, pos)))
-            ad = BnAdapter(jobs, alpha=st["alpha"], batched=bool(cfg.get("adapt_bn_batched", True)),
-                           eval_batch=kept[chunk[0]]["loaders"][2].batch_size)
-            for u, r in zip(chunk, ad.run()):
-                p = kept[u]
-                r = dict(subject=p["subject"], settings=st, **r)
-                (p["fold_dir"] / "adaptation_result.json").write_text(json.dumps(r))
-                tag = f"{n}/" if n else ""
-                print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) BatchNorm adaptation on {r['n']} unlabelled windows: "
-                      f"acc {r['before']['accuracy']:.4f} -> {r['after']['accuracy']:.4f}  f1 {r['before']['f1_score']:.4f} -> "
-                      f"{r['after']['f1_score']:.4f}", flush=True)
-                out[u] = ((r["before"]["accuracy"], r["before"]["f1_score"]), (r["after"]["accuracy"], r["after"]["f1_score"]),
-                          (float(r["n"]), 0.0))
+    out = {}
+    for n, cfg, chunk in _fold_batches(kept, units, cfgs):
+        st, jobs = adaptation_settings(cfg), []
+        for u in chunk:
+            x, y, _ = _windows(kept[u])
+            jobs.append(dict(model=kept[u]["model"], x=x, y=y))
+        ad = BnAdapter(jobs, alpha=st["alpha"], batched=bool(cfg.get("adapt_bn_batched", True)),
+                       eval_batch=kept[chunk[0]]["loaders"][2].batch_size)
+        for u, r in zip(chunk, ad.run()):
+            p = kept[u]
+            r = dict(subject=p["subject"], settings=st, **r)
+            (p["fold_dir"] / "adaptation_result.json").write_text(json.dumps(r))
+            print(f"[rank {rank}] {_tag(n)}fold {p['fold']} ({p['subject']}) BatchNorm adaptation on {r['n']} unlabelled windows: "
+                  f"acc {r['before']['accuracy']:.4f} -> {r['after']['accuracy']:.4f}  f1 {r['before']['f1_score']:.4f} -> "
+                  f"{r['after']['f1_score']:.4f}", flush=True)
+            out[u] = ((r["before"]["accuracy"], r["before"]["f1_score"]), (r["after"]["accuracy"], r["after"]["f1_score"]),
+                      (float(r["n"]), 0.0))
     return out
 
 
@@ -354,17 +364,15 @@ def attribute_units(kept, units, cfgs, device, rank=0):
     for u in sorted(kept):
         n, _ = units[u]
         cfg, p = cfgs[n], kept[u]
-        loader, model = p["loaders"][2], p["model"]
-        pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=device)
-        x, y = loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+        model = p["model"]
+        x, y, _ = _windows(p)
         r = fold_attribution(model, x, y, steps=int(cfg["attribute"]), bin=cfg.get("attribute_bin"), channels=cfg["channels"],
                              num_classes=cfg["num_classes"])
         model.engine().drop_workspaces(Engine.EVAL_KEEP)           # the kept-evaluation workspace of a path batch: not needed again
         r = dict(subject=p["subject"], **r)
         (p["fold_dir"] / "attribution_result.json").write_text(json.dumps(r))
         order = np.argsort(-np.asarray(r["share"]), kind="stable")
-        tag = f"{n}/" if n else ""
-        print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) attribution over {r['n']} windows, {r['steps']} path points: "
+        print(f"[rank {rank}] {_tag(n)}fold {p['fold']} ({p['subject']}) attribution over {r['n']} windows, {r['steps']} path points: "
               + ", ".join(f"{r['channels'][i]} {r['share'][i]:.3f}" for i in order)
               + f" | completeness gap mean {r['gap_rel_mean']:.2e} max {r['gap_rel_max']:.2e}", flush=True)
         done.append(u)
@@ -386,15 +394,13 @@ def uncertainty_units(kept, units, cfgs, device, rank=0):
     for u in sorted(kept):
         n, _ = units[u]
         cfg, p = cfgs[n], kept[u]
-        loader, model = p["loaders"][2], p["model"]
-        pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=device)
-        x, y = loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+        model = p["model"]
+        x, y, _ = _windows(p)
         r = fold_uncertainty(model, x, y, samples=int(cfg["mc_dropout"]), seed=int(cfg.get("mc_seed", 0)))
         r = dict(subject=p["subject"], **r)
         (p["fold_dir"] / "uncertainty_result.json").write_text(json.dumps(r))
-        tag = f"{n}/" if n else ""
         au = r["auroc_entropy"]
-        print(f"[rank {rank}] {tag}fold {p['fold']} ({p['subject']}) Monte-Carlo dropout over {r['n']} windows, {r['samples']} samples: "
+        print(f"[rank {rank}] {_tag(n)}fold {p['fold']} ({p['subject']}) Monte-Carlo dropout over {r['n']} windows, {r['samples']} samples: "
               f"acc eval {r['accuracy_eval']:.4f} mc {r['accuracy_mc']:.4f} | AUROC of entropy {'n/a' if au is None else format(au, '.4f')} | "
               f"ECE eval {r['ece_eval']:.4f} mc {r['ece_mc']:.4f}", flush=True)
         done.append(u)
@@ -410,27 +416,17 @@ def ensemble_units(members, local, epochs, units, cfgs, seeds, rank=0):
         us = [u0 + r for r in range(seeds)]
         n, k = units[u0]
         p = members[u0]
-        loader = p["loaders"][2]
-        pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=loader.store.device)
-        x, y = loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
+        x, y, _ = _windows(p)
         t0 = time.time()
-        r = ensemble_mod.fold_ensemble([members[u]["model"] for u in us], x, y, eval_batch=loader.batch_size)
+        r = ensemble_mod.fold_ensemble([members[u]["model"] for u in us], x, y, eval_batch=p["loaders"][2].batch_size)
         r = dict(subject=p["subject"], fold=k, seeds=[ensemble_mod.replica_seed(cfgs[n]["seed"], k, i) for i in range(seeds)],
                  member_accuracy=[local[u][0] for u in us], member_f1=[local[u][1] for u in us], epochs=[epochs[u] for u in us],
                  seconds=time.time() - t0, **r)
         (p["fold_dir"] / "ensemble_result.json").write_text(json.dumps(r))
-        tag = f"{n}/" if n else ""
-        print(f"[rank {rank}] {tag}fold {k} ({p['subject']}) ensemble of {seeds} seeds over {r['n']} windows: members "
+        print(f"[rank {rank}] {_tag(n)}fold {k} ({p['subject']}) ensemble of {seeds} seeds over {r['n']} windows: members "
               + " ".join(f"{a:.4f}" for a in r["member_accuracy"])
               + f" | ensemble acc {r['ensemble']['accuracy']:.4f} f1 {r['ensemble']['f1_score']:.4f} | disagreement "
               f"{r['ensemble']['mean_disagreement']:.4f}", flush=True)
-
-
-def _test_windows(prep):
-    """(x, y) of a prep's TEST subject on the device, in store order."""
-    loader = prep["loaders"][2]
-    pos = loader.index if loader.index is not None else torch.arange(len(loader.dataset), device=loader.store.device)
-    return loader.store.index_select(0, pos), loader.store_y.index_select(0, pos)
 
 
 def distill_units(members, units, cfgs, out_dir, stores, seeds, kd, train_cfg, device, all_channel_names, rank=0):
@@ -447,11 +443,11 @@ def distill_units(members, units, cfgs, out_dir, stores, seeds, kd, train_cfg, d
     for u0 in base_units:
         n, k = units[u0]
         models = [members[u0 + r]["model"] for r in range(seeds)]
-        tr = members[u0]["loaders"][0]
-        pos = tr.index if tr.index is not None else torch.arange(len(tr.dataset), device=tr.store.device)
+        store = members[u0]["loaders"][0].store
         t0 = time.time()
-        table = torch.zeros((int(tr.store.shape[0]), int(cfgs[n]["num_classes"])), dtype=torch.float32, device=tr.store.device)
-        table.index_copy_(0, pos, Ensemble(models, eval_batch=members[u0]["loaders"][2].batch_size).teacher(tr.store.index_select(0, pos), kd.temperature))
+        x, _, pos = _windows(members[u0], loader=0, labels=False)
+        table = torch.zeros((int(store.shape[0]), int(cfgs[n]["num_classes"])), dtype=torch.float32, device=store.device)
+        table.index_copy_(0, pos, Ensemble(models, eval_batch=members[u0]["loaders"][2].batch_size).teacher(x, kd.temperature))
         torch.cuda.synchronize(device)
         teachers[u0] = (table, time.time() - t0)
         sunits[u0] = (distill_mod.student_name(n), k)
@@ -471,7 +467,7 @@ def distill_units(members, units, cfgs, out_dir, stores, seeds, kd, train_cfg, d
     for u0 in base_units:
         n, k = units[u0]
         p0, info = members[u0], infos[u0]
-        x, y = _test_windows(p0)
+        x, y, _ = _windows(p0)
         r = ensemble_mod.fold_ensemble([members[u0 + r]["model"] for r in range(seeds)], x, y, eval_batch=p0["loaders"][2].batch_size)
         sp = Ensemble([preps[u0]["model"]], eval_batch=p0["loaders"][2].batch_size).predict(x)
         win, mem = r["windows"], r["member_windows"]
@@ -492,8 +488,7 @@ def distill_units(members, units, cfgs, out_dir, stores, seeds, kd, train_cfg, d
                    teacher_seconds=teachers[u0][1], student_seconds=info["seconds"],
                    windows=dict(y=win["y"], ensemble=win, members=mem, student=student))
         (p0["fold_dir"] / "distilled_result.json").write_text(json.dumps(doc))
-        tag = f"{n}/" if n else ""
-        print(f"[rank {rank}] {tag}fold {k} ({p0['subject']}) distilled from {seeds} member(s): student acc {doc['student']['accuracy']:.4f} "
+        print(f"[rank {rank}] {_tag(n)}fold {k} ({p0['subject']}) distilled from {seeds} member(s): student acc {doc['student']['accuracy']:.4f} "
               f"fidelity {doc['student']['fidelity']:.4f} | replica 0 acc {doc['replica0']['accuracy']:.4f} | ensemble acc "
               f"{doc['ensemble']['accuracy']:.4f}", flush=True)
 

@@ -588,7 +588,83 @@ class EmbeddedEngine(Engine):
         self.gather()
 
 
-class FoldArena:
+def workspace_need(batch_sizes, in_channels: int, T: int, num_classes: int, training) -> int:
+    """Bytes of a workspace that must serve every batch size in `batch_sizes` in one mode (allocates nothing).
+    msig_workspace_layout is NOT monotonic in B — the projection region WS_GI exists only below 192 batch tiles, so a ragged last
+    batch just under 3072 windows needs MORE than the full batch above it: from 192 tiles on, 191 tiles are a candidate too."""
+    cand = {int(b) for b in batch_sizes}
+    if max(cand) >= 192 * 16:
+        cand.add(191 * 16)
+    return max(L.workspace_layout(c, in_channels, T, num_classes, training)[-1] for c in cand)
+
+
+def make_batch(B: int, C_: int, T: int, K: int, x: int, params: int, bn_state: int, bn_count: int, ws: int, ws_bytes: int, gru_layers: int,
+               training: bool = False, dropout_thr: int = 0, labels: Optional[int] = None, grads: Optional[int] = None,
+               loss_acc: Optional[int] = None) -> L.Batch:
+    """msig_batch of B windows from device addresses: BatchNorm's constants, the binding's kernel forms, zero dropout keys (the
+    *_multi calls carry their own), no keep_for_backward, no dx."""
+    b = L.Batch()
+    b.shape = L.Shape(B, C_, T, K)
+    b.training = int(training)
+    b.bn_momentum, b.bn_eps = 0.1, 1e-5
+    b.dropout_thr = dropout_thr
+    b.x, b.labels = x, labels
+    b.params, b.grads = params, grads
+    b.bn_state, b.bn_count = bn_state, bn_count
+    b.ws, b.ws_bytes = ws, ws_bytes
+    b.gru_layers = gru_layers
+    b.loss_acc = loss_acc
+    L.apply_forms(b)
+    return b
+
+
+class Arenas:
+    """`n` identical arenas, `stride` bytes apart, in one zeroed allocation `mem` (n, stride): the regions of `regions`, an ordered
+    (name, nbytes) list, at the same 256-byte-aligned offsets `off[name] = (offset, nbytes)` in each — which is all a *_multi call
+    needs to run the same work on several arenas in one set of launches."""
+    form_folds = 1          # msig_multi.form_folds of multi(): the GRU backward form of ONE stand-alone fold (FoldArena.multi)
+
+    def __init__(self, n: int, device, regions):
+        self.n, self.device = int(n), torch.device(device)
+        self.off, at = {}, 0
+        for name, nbytes in regions:
+            self.off[name] = (at, nbytes)
+            at += (nbytes + 255) // 256 * 256
+        self.stride = at
+        self.mem = torch.zeros((self.n, self.stride), dtype=torch.uint8, device=self.device)
+
+    def view(self, slot: int, name: str, dtype=torch.uint8) -> torch.Tensor:
+        o, nb = self.off[name]
+        return self.mem[slot, o:o + nb].view(dtype)
+
+    def ptr(self, name: str, slot: int = 0, byte_offset: int = 0) -> int:
+        """Address of region `name` of arena `slot` (the *_multi calls are given arena 0's)."""
+        return self.mem.data_ptr() + slot * self.stride + self.off[name][0] + byte_offset
+
+    def across(self, name: str, byte_offset: int, dtype, count: int = 1) -> torch.Tensor:
+        """(n, count) strided view of `count` elements at `byte_offset` inside region `name` of every arena."""
+        o, _ = self.off[name]
+        esz = torch.empty(0, dtype=dtype).element_size()
+        flat = self.mem.view(dtype)                                    # (n, stride / esz)
+        start = (o + byte_offset) // esz
+        return flat[:, start:start + count]
+
+    def stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def multi(self, slots, key_gru=None, key_head=None, lr=None, steps=None) -> L.Multi:
+        m = L.Multi()
+        m.n, m.stride_bytes, m.form_folds = len(slots), self.stride, self.form_folds
+        for i, s in enumerate(slots):
+            m.slot[i] = int(s)
+            m.key_gru[i] = int(key_gru[i]) if key_gru is not None else 0
+            m.key_head[i] = int(key_head[i]) if key_head is not None else 0
+            m.lr[i] = float(lr[i]) if lr is not None else 0.0
+            m.step[i] = int(steps[i]) if steps is not None else 0
+        return m
+
+
+class FoldArena(Arenas):
     """Device memory of a fold batch (include/msig.h msig_multi): `n` identical arenas, `stride` bytes apart, each holding one
     model's parameters, gradients, Adam moments, BatchNorm state, one workspace region, one input batch and its labels at the
     same offsets — which is all msig_*_multi needs to run the same step for several folds in one set of launches."""
@@ -620,11 +696,17 @@ class FoldArena:
         self.gru_hidden, self.gru_layers = int(gru_hidden), int(gru_layers)
         self.kind = L.check_kind(kind)
         eval_batch = int(eval_batch) or int(train_batch)
-        self.C, self.K, self.n, self.T = in_channels, num_classes, n, T
+        self.C, self.K, self.T = in_channels, num_classes, T
         self.max_batch = max(int(train_batch), eval_batch)
         self.max_train_batch = int(train_batch)
+        # The BACKWARD GRU kernel form is chosen as for ONE stand-alone fold of this batch size, whatever the number of folds in the
+        # launch (form_folds = 1): a fold's bits must not depend on which companions share its launches, on when they stop early, on
+        # --lockstep-groups or on how many ranks the folds are dealt to, and the backward forms round differently (they group the dW
+        # partials differently).  adaptive_forms=True lets it follow the folds still active in each launch instead (msig.h: fused
+        # backward kernels from 12 tiles per launch on).  The FORWARD forms are bit-identical since round 5: the library picks per
+        # layer and per launch (gru.hip fwd_form) and this pin does not enter.
         self.adaptive_forms = bool(adaptive_forms)
-        self.device = torch.device(device)
+        self.form_folds = 0 if self.adaptive_forms else 1
         self.n_flat = L.param_layout(in_channels, num_classes, kind)[-1]
         self.ws_bytes = self.workspace_bytes(train_batch, eval_batch, in_channels, T, num_classes)
         # "cw": the fold's class-weight vector (include/msig_cw.h msig_cw_*_multi), written when a fold enters (set_class_weight)
@@ -638,52 +720,28 @@ class FoldArena:
         if self.averaging:
             sizes += [("avg_params", self.n_flat * 4), ("avg_bn_state", L.BN_STATE_FLOATS * 4), ("avg_bn_count", 16)]
         self.max_norm = [float("inf")] * n              # per arena: max_norm of the fold in it (set_max_norm); inf = measured, not clipped
-        self.off, at = {}, 0
-        for name, nbytes in sizes:
-            self.off[name] = (at, nbytes)
-            at += (nbytes + 255) // 256 * 256
-        self.stride = at
-        self.mem = torch.zeros((n, self.stride), dtype=torch.uint8, device=self.device)
+        super().__init__(n, device, sizes)
         self.da_off, self.da_stride, self.da_mem = {}, 0, None
         if adversary is not None:
             S, positions = int(adversary[0]), int(adversary[1])
             nf = L.da_param_floats(S)
-            for name, nbytes in (("params", nf * 4), ("exp_avg", nf * 4), ("exp_avg_sq", nf * 4), ("stats", 24), ("dom", positions * 4)):
-                self.da_off[name] = (self.da_stride, nbytes)
-                self.da_stride += (nbytes + 255) // 256 * 256
-            self.da_mem = torch.zeros((n, self.da_stride), dtype=torch.uint8, device=self.device)
+            da = Arenas(n, device, (("params", nf * 4), ("exp_avg", nf * 4), ("exp_avg_sq", nf * 4), ("stats", 24), ("dom", positions * 4)))
+            self.da_off, self.da_stride, self.da_mem = da.off, da.stride, da.mem
         self.kd_off, self.kd_stride, self.kd_mem = {}, 0, None
         if distill is not None:
             if int(distill) < 1:
                 raise ValueError(f"distill takes the number of store positions (>= 1), got {distill!r}")
-            for name, nbytes in (("stats", 24), ("q", int(distill) * num_classes * 4)):
-                self.kd_off[name] = (self.kd_stride, nbytes)
-                self.kd_stride += (nbytes + 255) // 256 * 256
-            self.kd_mem = torch.zeros((n, self.kd_stride), dtype=torch.uint8, device=self.device)
+            kd = Arenas(n, device, (("stats", 24), ("q", int(distill) * num_classes * 4)))
+            self.kd_off, self.kd_stride, self.kd_mem = kd.off, kd.stride, kd.mem
 
     @staticmethod
     def workspace_bytes(train_batch: int, eval_batch: int, in_channels: int, T: int, num_classes: int) -> int:
         """Bytes of an arena's workspace region (allocates nothing): it serves training steps of at most `train_batch` windows and
         evaluation passes of at most `eval_batch` (the evaluation layout has no stash and no gradient scratch: a large
-        --eval-batch-size must not be priced as a training batch).  msig_workspace_layout is NOT monotonic in B — the projection region
-        WS_GI exists only below 192 batch tiles, so a ragged last batch just under 3072 windows needs MORE than the full batch above
-        it: the maximum over every batch size that can occur."""
-        def need(bs, training):
-            cand = [int(bs)] + ([191 * 16] if bs >= 192 * 16 else [])
-            return max(L.workspace_layout(c, in_channels, T, num_classes, training)[-1] for c in cand)
-        return max(need(train_batch, True), need(int(eval_batch) or int(train_batch), False))
-
-    def view(self, slot: int, name: str, dtype=torch.uint8) -> torch.Tensor:
-        o, nb = self.off[name]
-        return self.mem[slot, o:o + nb].view(dtype)
-
-    def across(self, name: str, byte_offset: int, dtype, count: int = 1) -> torch.Tensor:
-        """(n, count) strided view of `count` elements at `byte_offset` inside region `name` of every arena."""
-        o, _ = self.off[name]
-        esz = torch.empty(0, dtype=dtype).element_size()
-        flat = self.mem.view(dtype)                                    # (n, stride / esz)
-        start = (o + byte_offset) // esz
-        return flat[:, start:start + count]
+        --eval-batch-size must not be priced as a training batch): the maximum over every batch size that can occur
+        (workspace_need)."""
+        return max(workspace_need([train_batch], in_channels, T, num_classes, True),
+                   workspace_need([int(eval_batch) or int(train_batch)], in_channels, T, num_classes, False))
 
     def engine(self, slot: int) -> Engine:
         st = {k: self.view(slot, k, torch.float32) for k in ("params", "grads", "exp_avg", "exp_avg_sq", "bn_state")}
@@ -698,9 +756,6 @@ class FoldArena:
         if self.gru_layers == 1:
             return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st, kind=self.kind)
         return Engine(self.C, self.K, self.device, storage=st, kind=self.kind)
-
-    def ptr(self, name: str) -> int:
-        return self.mem.data_ptr() + self.off[name][0]                  # arena 0's buffer
 
     def adversary_storage(self, slot: int) -> dict:
         """The adversary buffers of the fold in arena `slot` (adversary.SubjectAdversary.bind): typed views of its `da_mem` row."""
@@ -815,22 +870,10 @@ class FoldArena:
             raise ValueError("a shadow descriptor is an eval descriptor of a FoldArena built with averaging=True")
         if B > (self.max_train_batch if training else self.max_batch):
             raise ValueError(f"batch {B} exceeds the arena's {self.max_train_batch if training else self.max_batch}")
-        b = L.Batch()
-        b.shape = L.Shape(B, self.C, self.T, self.K)
-        b.training = int(training)
-        b.bn_momentum, b.bn_eps = 0.1, 1e-5
-        b.dropout_thr = L.dropout_threshold(dropout_p) if training else 0
-        b.key_gru = b.key_head = 0
-        b.x, b.labels = self.ptr("x"), (self.ptr("y") if with_labels else None)
-        b.params, b.grads = self.ptr("params"), self.ptr("grads")
-        b.bn_state, b.bn_count = self.ptr("bn_state"), self.ptr("bn_count")
-        if shadow:
-            b.params, b.bn_state, b.bn_count = self.ptr("avg_params"), self.ptr("avg_bn_state"), self.ptr("avg_bn_count")
-        b.ws, b.ws_bytes = self.ptr("ws"), self.ws_bytes
-        b.loss_acc = self.ptr("acc")
-        b.gru_layers = self.gru_layers
-        L.apply_forms(b)
-        return b
+        model = ("avg_params", "avg_bn_state", "avg_bn_count") if shadow else ("params", "bn_state", "bn_count")
+        return make_batch(B, self.C, self.T, self.K, self.ptr("x"), *(self.ptr(r) for r in model), self.ptr("ws"), self.ws_bytes, self.gru_layers,
+                          training=training, dropout_thr=L.dropout_threshold(dropout_p) if training else 0,
+                          labels=self.ptr("y") if with_labels else None, grads=self.ptr("grads"), loss_acc=self.ptr("acc"))
 
     def features(self, slots, B: int) -> torch.Tensor:
         """Eval-mode features (msig_ft_features_multi) of the B windows that sit in the "x" buffer of every arena in `slots`, in one
@@ -838,27 +881,8 @@ class FoldArena:
         the bits Engine.features gives for the same model and windows."""
         out = torch.empty((len(slots), B, 128), dtype=torch.float32, device=self.device)
         b, m = self.batch(B, False, 0.0, with_labels=False), self.multi(slots)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(L.lib().msig_ft_features_multi(C.byref(b), C.byref(m), L.FT_KINDS[self.kind], out.data_ptr(), B * 512, st),
+        L.check(L.lib().msig_ft_features_multi(C.byref(b), C.byref(m), L.FT_KINDS[self.kind], out.data_ptr(), B * 512, self.stream()),
                 "msig_ft_features_multi")
         if self.gru_layers == 1:
             return torch.cat([out[:, :, :self.gru_hidden], out[:, :, 64:64 + self.gru_hidden]], dim=2)
         return out
-
-    def multi(self, slots, key_gru=None, key_head=None, lr=None, steps=None) -> L.Multi:
-        m = L.Multi()
-        m.n, m.stride_bytes = len(slots), self.stride
-        # The BACKWARD GRU kernel form is chosen as for ONE stand-alone fold of this batch size, whatever the number of folds in the
-        # launch: a fold's bits must not depend on which companions share its launches, on when they stop early, on --lockstep-groups
-        # or on how many ranks the folds are dealt to, and the backward forms round differently (they group the dW partials
-        # differently).  adaptive_forms=True lets it follow the folds still active in each launch instead (msig.h: fused backward
-        # kernels from 12 tiles per launch on).  The FORWARD forms are bit-identical since round 5: the library picks per layer and
-        # per launch (gru.hip fwd_form) and this pin does not enter.
-        m.form_folds = 0 if self.adaptive_forms else 1
-        for i, s in enumerate(slots):
-            m.slot[i] = int(s)
-            m.key_gru[i] = int(key_gru[i]) if key_gru is not None else 0
-            m.key_head[i] = int(key_head[i]) if key_head is not None else 0
-            m.lr[i] = float(lr[i]) if lr is not None else 0.0
-            m.step[i] = int(steps[i]) if steps is not None else 0
-        return m
