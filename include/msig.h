@@ -84,7 +84,7 @@ enum msig_ws {
   MSIG_WS_GATE_PRE,      /* (B,max(C/4,1)) fc.0 output before ReLU             */
   MSIG_WS_GATE_S,        /* (B,C)      sigmoid gate               models.py:29 */
   MSIG_WS_Y1,            /* (B,L1,16)  conv1 output, time-major (NLC)          */
-  MSIG_WS_BN1_PART,      /* partial sums for BatchNorm-1 statistics            */
+  MSIG_WS_BN1_PART,      /* partial sums for BatchNorm-1 statistics (f32 + f64) */
   MSIG_WS_BN1_STAT,      /* mean,invstd,scale,shift (4 x 16)                   */
   MSIG_WS_P1,            /* (B,P1,16)  after BN+ReLU+MaxPool (NLC)             */
   MSIG_WS_Y2,            /* (B,L2,32)  conv2 output (NLC)                      */

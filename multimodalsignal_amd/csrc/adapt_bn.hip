@@ -16,10 +16,11 @@ __global__ __launch_bounds__(FIN_THREADS) void ab_merge_kernel(const float* __re
   FOLD_BEGIN; FS(part); FS(acc);
   __shared__ double red[FIN_THREADS];
   const int tid = threadIdx.x;
-  fin_colsums(part, nrows, 2 * CH, red);          // 2 * CH <= 64 columns
+  double s1, s2;
+  bn_batch_sums(part, nrows, CH, count, red, s1, s2);      // the sums bn_finalize_kernel divides (msig_dev.h)
   if (tid < CH) {
-    acc[sum0 + tid] += red[tid];
-    acc[sq0 + tid] += red[CH + tid];
+    acc[sum0 + tid] += s1;
+    acc[sq0 + tid] += s2;
   }
   if (tid == 0) acc[cnt] += count;
 }

@@ -152,7 +152,7 @@ extern "C" int msig_workspace_layout(const msig_shape* s, int training, int64_t*
   sz[MSIG_WS_GATE_PRE] = B * imax(d.Cr, 1) * F;
   sz[MSIG_WS_GATE_S] = B * d.C * F;
   sz[MSIG_WS_Y1] = B * d.L1 * 16 * F;
-  sz[MSIG_WS_BN1_PART] = (int64_t)MSIG_PERSIST_WG * 32 * F;
+  sz[MSIG_WS_BN1_PART] = (int64_t)MSIG_PERSIST_WG * 32 * (F + (int64_t)sizeof(double));      // unshifted float rows, then shifted double rows (msig_dev.h)
   sz[MSIG_WS_BN1_STAT] = 64 * F;
   sz[MSIG_WS_P1] = B * d.P1 * 16 * F;
   sz[MSIG_WS_Y2] = B * d.L2 * 32 * F;

@@ -218,6 +218,9 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
   const int nchunk = (L1 + C1_CHUNK - 1) / C1_CHUNK;
   const int nitems = B * nchunk;
   f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, ssq = {0.f, 0.f, 0.f, 0.f};
+  // the same sums of channels lq * 4 + e shifted by this thread's first value of each (msig_dev.h, "BatchNorm-1 batch statistics")
+  f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, dsq = {0.f, 0.f, 0.f, 0.f}, piv = {0.f, 0.f, 0.f, 0.f};
+  int nacc = 0;
   // Software pipeline (compile-time channel count, T % 4 == 0): the next item's x chunk and gate values are
   // loaded into registers while the current item's MFMAs run, so an item is  sync, regs -> LDS, sync, issue the
   // next loads, compute  and no workgroup ever sits on a global-load latency between two barriers.
@@ -317,6 +320,10 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
         *(float4*)(y1 + ((size_t)b * L1 + t) * 16 + lq * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { ssum[e] += acc[e]; ssq[e] += acc[e] * acc[e]; }
+        if (nacc == 0) piv = acc;
+        ++nacc;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float dv = acc[e] - piv[e]; dsum[e] += dv; dsq[e] += dv * dv; }
       }
     }
   }
@@ -333,6 +340,18 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
     }
     __syncthreads();
     if (tid < 32) part[(size_t)blockIdx.x * 32 + tid] = red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid];
+    // the shifted sums: unshifted in double, reduced in double
+    double* redd = (double*)(smem + 4 * 32);   // [4 waves][32], behind red
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      double s1, s2;
+      bn_unshift(nacc, piv[e], dsum[e], dsq[e], s1, s2);
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+      if (li == 0) { redd[w * 32 + lq * 4 + e] = s1; redd[w * 32 + 16 + lq * 4 + e] = s2; }
+    }
+    __syncthreads();
+    if (tid < 32) bn_shifted_part(part, 16)[(size_t)blockIdx.x * 32 + tid] = (redd[tid] + redd[32 + tid]) + (redd[64 + tid] + redd[96 + tid]);
   }
 }
 
@@ -472,7 +491,7 @@ __global__ __launch_bounds__(256, 2) void pool1_conv2_fwd_kernel(const float* __
 
 // ------------------------------------------------------------------------------------
 // BatchNorm statistics -> (mean, invstd, scale, shift); running-stat update
-// part: [nrows][2*CH] = per-workgroup (sum[CH], sumsq[CH]).  stat: 4*CH floats.
+// part: [nrows][2*CH] = per-workgroup (sum[CH], sumsq[CH]); stage 1's is followed by its shifted double rows (msig_dev.h).  stat: 4*CH floats.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* __restrict__ part, int nrows, int CH, double count,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -483,12 +502,13 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
   __shared__ double red[FIN_THREADS];
   const int tid = threadIdx.x;
   if (training) {
-    fin_colsums(part, nrows, 2 * CH, red);          // 2*CH <= 64 columns
+    double s1, s2;
+    bn_batch_sums(part, nrows, CH, count, red, s1, s2);      // stage 1: unshifted or shifted sums per channel (msig_dev.h)
     if (tid < CH) {
-      const double mean = red[tid] / count;
-      double var = red[CH + tid] / count - mean * mean;
+      const double mean = s1 / count;
+      double var = s2 / count - mean * mean;
       if (var < 0.0) var = 0.0;
-      const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+      const float invstd = (float)(msig_negctl_input == 2 ? 1.0 / (sqrt(var) + (double)eps) : 1.0 / sqrt(var + (double)eps));
       const float sc = (msig_negctl_regime == 3 ? fabsf(gamma[tid]) : gamma[tid]) * invstd;
       stat[tid] = (float)mean;
       stat[CH + tid] = invstd;
@@ -1348,7 +1368,7 @@ int launch_frontend_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     const int grid = clampi((int64_t)d.B * nchunk, MSIG_PERSIST_WG);
     const int KM = (d.C * 7 + 3) / 4;
     size_t smem = (size_t)(2 * d.C * C1_XP + 4 * KM * 16) * sizeof(float);
-    if (smem < 4 * 32 * sizeof(float)) smem = 4 * 32 * sizeof(float);
+    if (smem < 4 * 32 * (sizeof(float) + sizeof(double))) smem = 4 * 32 * (sizeof(float) + sizeof(double));      // the statistics' reductions
     {
       MSIG_K("conv1_fwd", st);
 #define C1F(CT, G) conv1_fwd_kernel<CT, G><<<dim3(grid, 1, fc.n), 256, smem, st>>>(b->x, P + po[MSIG_P_CONV1_W], gs, w.p<float>(MSIG_WS_Y1), \

@@ -107,6 +107,15 @@ constexpr int msig_negctl_range = MSIG_NEGCTL_RANGE;
 #else
 constexpr int msig_negctl_range = 0;
 #endif
+// Negative controls of the input regimes (make negctl INPUT=k; never defined in the product library): one slip each that no unit-scale,
+// nearly centred input can see (tests/test_input_regimes_gpu.py must FAIL against each; tools/negative_controls.sh input).
+//   1  bn_batch_sums always takes the unshifted fp32 sums: E[y^2] - mean^2 cancels in fp32 under a large channel mean
+//   2  bn_finalize_kernel's training branch adds eps outside the square root: invstd = 1 / (sqrt(var) + eps)
+#ifdef MSIG_NEGCTL_INPUT
+constexpr int msig_negctl_input = MSIG_NEGCTL_INPUT;
+#else
+constexpr int msig_negctl_input = 0;
+#endif
 // acc += A . B over one 32-wide k block, A and B given as their three pieces ([0] = leading piece)
 template <int KIND = CT_ANY>
 __device__ __forceinline__ f32x4 mfma_bf16x3(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {
@@ -263,10 +272,11 @@ __device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
   return mx + logf(se);
 }
 
-// Column sums of part[nrows][ncol] (ncol <= 64) by one 1024-thread workgroup into red[0..ncol): 1024/ncol
+// Column sums of part[nrows][ncol] (ncol <= 64; float or double rows) by one 1024-thread workgroup into red[0..ncol): 1024/ncol
 // row-lanes, 8 loads in flight per lane, fixed combination order (deterministic for a given nrows).
 #define FIN_THREADS 1024
-__device__ __forceinline__ void fin_colsums(const float* __restrict__ part, int nrows, int ncol, double* red) {
+template <typename PT>
+__device__ __forceinline__ void fin_colsums(const PT* __restrict__ part, int nrows, int ncol, double* red) {
   const int tid = threadIdx.x;
   const int col = tid % ncol, grp = tid / ncol, ngrp = FIN_THREADS / ncol;
   double a[8];
@@ -275,7 +285,7 @@ __device__ __forceinline__ void fin_colsums(const float* __restrict__ part, int 
   if (grp < ngrp) {
     int r = grp;
     for (; r + 7 * ngrp < nrows; r += 8 * ngrp) {
-      float v[8];
+      PT v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = part[(size_t)(r + j * ngrp) * ncol + col];
 #pragma unroll
@@ -492,4 +502,44 @@ PartOffsets part_offsets(const StageDims& d);
 // Number of persistent workgroups used by reduction-style kernels; partial buffers are sized for it.
 #define MSIG_PERSIST_WG 1024
 #define MSIG_DW_WG 512
+
+// ---- BatchNorm-1 batch statistics (conv1_fwd_kernel) ---------------------------------------------------------------------------
+// conv1 sees the raw input: a channel that sits many spreads from zero (a temperature column, a subject normalised against resting
+// windows) gives conv1 outputs with mean^2 >> var.  Stage 2 sees BatchNorm-1's normalised, rectified output and keeps its one set of
+// sums (BN1_STAGE_CH tells the stages apart).  A conv1 workgroup writes TWO rows of partial sums (WS_BN1_PART:
+// [MSIG_PERSIST_WG][32] floats, then [MSIG_PERSIST_WG][32] doubles):
+//   unshifted  sum y, sum y^2 per thread in fp32, reduced in fp32 — the sums this library has always formed.  Their variance
+//              E[y^2] - mean^2 loses mean^2 / var of its relative precision: exact enough while the channel mean is a few spreads,
+//              100 x worse at 10 spreads;
+//   shifted    sum (y - p), sum (y - p)^2 per thread in fp32 with p = the thread's FIRST value of the channel, so what is squared is
+//              of the size of the spread; bn_unshift turns (n, p, sums) into sum y, sum y^2 in double and the reductions stay double.
+// bn_batch_sums picks per channel: the unshifted sums where they are well conditioned, mean^2 <= BN_SHIFT_RATIO x var (judged on the
+// shifted sums) — every bit of every result on such inputs is what it was before the shifted sums existed, recorded training
+// trajectories included —, the shifted sums beyond.  At the switch the unshifted variance carries 17 x the rounding of its sums, an
+// order of magnitude inside what the parity gate allows.  bn_finalize_kernel and ab_merge_kernel both reduce through this function.
+#define BN_SHIFT_RATIO 16.0
+#define BN1_STAGE_CH 16
+__device__ __forceinline__ void bn_unshift(int n, float p, float sd, float sq, double& s1, double& s2) {
+  const double dn = (double)n, dp = (double)p, dsd = (double)sd;
+  s1 = dn * dp + dsd;
+  s2 = (double)sq + dp * (2.0 * dsd + dn * dp);
+}
+__device__ __forceinline__ const double* bn_shifted_part(const float* part, int CH) { return (const double*)(part + (size_t)MSIG_PERSIST_WG * 2 * CH); }
+__device__ __forceinline__ double* bn_shifted_part(float* part, int CH) { return (double*)(part + (size_t)MSIG_PERSIST_WG * 2 * CH); }
+// For tid < CH: the batch's sum y (s1) and sum y^2 (s2) of channel tid.  Called by all FIN_THREADS threads; red: FIN_THREADS doubles.
+__device__ __forceinline__ void bn_batch_sums(const float* __restrict__ part, int nrows, int CH, double count, double* red, double& s1, double& s2) {
+  const int tid = threadIdx.x;
+  fin_colsums(part, nrows, 2 * CH, red);          // 2 * CH <= 64 columns
+  s1 = 0.0; s2 = 0.0;
+  if (tid < CH) { s1 = red[tid]; s2 = red[CH + tid]; }
+  if (msig_negctl_input == 1 || CH != BN1_STAGE_CH) return;
+  __syncthreads();
+  fin_colsums(bn_shifted_part(part, CH), nrows, 2 * CH, red);
+  if (tid < CH) {
+    const double t1 = red[tid], t2 = red[CH + tid], m = t1 / count;
+    double v = t2 / count - m * m;
+    if (v < 0.0) v = 0.0;
+    if (m * m > BN_SHIFT_RATIO * v) { s1 = t1; s2 = t2; }
+  }
+}
 #define MSIG_CONV_DW_WG 1024      // conv weight-gradient kernels: 4 workgroups per CU hide their staging latency

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import ab_reference as R
+import input_regimes as IR
 from gpu_common import rel_err, stage_tol
 from oracle import cnn_gru_oracle as O
 from multimodalsignal_amd import _lib as L
@@ -39,11 +40,17 @@ def _same(a, b):
     return a.shape == b.shape and bool(torch.equal(_bits(a), _bits(b)))
 
 
-def _x(C_, seed, n=N):
-    """Windows with a per-channel gain in [1.5, 3] and offset in [-1, 1]."""
+def _x_host(C_, seed, n=N, regime=None):
+    """Windows with a per-channel gain in [1.5, 3] and offset in [-1, 1] (numpy), optionally moved into an input regime
+    (tests/input_regimes.py)."""
     rs = np.random.RandomState(seed)
     x = rs.randn(n, C_, T) * (1.5 + 1.5 * rs.rand(1, C_, 1)) + (2.0 * rs.rand(1, C_, 1) - 1.0)
-    return torch.as_tensor(x.astype(np.float32), device=DEV)
+    x = x.astype(np.float32)
+    return x if regime is None else IR.apply(x, regime, signs=IR.case_signs(regime, n, C_, T))
+
+
+def _x(C_, seed, n=N, regime=None):
+    return torch.as_tensor(_x_host(C_, seed, n, regime), device=DEV)
 
 
 def _named(kind, C_, seed, layers=2):
@@ -183,47 +190,53 @@ def test_stage_one_equals_the_training_forwards_running_statistics_bit_for_bit(m
 _refs, _adapted = {}, {}
 
 
-def _reference(kind, C_, layers, wrong=None):
+def _reference(kind, C_, layers, wrong=None, regime=None):
     """(float64 restatement, `own` of every tensor) of the case, computed once (batches of 16: it does not depend on the batching,
     tests/test_adapt_host.py)."""
-    key = (kind, C_, layers, wrong)
+    key = (kind, C_, layers, wrong, regime)
     if key not in _refs:
-        named, x = _named(kind, C_, 20 + C_, layers), _x(C_, seed=30 + C_).cpu()
+        named, x = _named(kind, C_, 20 + C_, layers), torch.as_tensor(_x_host(C_, seed=30 + C_, regime=regime))
         r64 = R.adapt(named, O.init_buffers(), x, batch=16, kind=kind, wrong=wrong)
         r32 = R.adapt(named, O.init_buffers(), x, batch=16, kind=kind, wrong=wrong, dtype=torch.float32)
         _refs[key] = ({k: v.numpy() for k, v in r64.items()}, {k: rel_err(r32[k].numpy(), r64[k].numpy()) for k in R.KEYS})
     return _refs[key]
 
 
-def _gpu(kind, C_, layers, batch):
-    key = (kind, C_, layers, batch)
+def _gpu(kind, C_, layers, batch, regime=None):
+    key = (kind, C_, layers, batch, regime)
     if key not in _adapted:
-        model, x = _model(kind, C_, 20 + C_, layers), _x(C_, seed=30 + C_)
+        model, x = _model(kind, C_, 20 + C_, layers), _x(C_, seed=30 + C_, regime=regime)
         ad = A.BnAdapter([dict(model=model, x=x)], alpha=1.0, eval_batch=batch)
         assert [b for _, b, _ in A.batch_plan(ad.sizes, ad.batch)] == CUTS[batch]
         _adapted[key] = {k: v.cpu().numpy() for k, v in ad.adapted_buffers(0).items()}
     return _adapted[key]
 
 
-def _gate(kind, C_, layers=2, batch=16, wrong=None):
+def _gate(kind, C_, layers=2, batch=16, wrong=None, regime=None):
     """{tensor: (error, tolerance)} of the adapted statistics against the restatement (optionally a deliberately wrong one)."""
-    ref, own = _reference(kind, C_, layers, wrong)
-    got = _gpu(kind, C_, layers, batch)
+    ref, own = _reference(kind, C_, layers, wrong, regime)
+    got = _gpu(kind, C_, layers, batch, regime)
     rep = {k: (rel_err(got[k], ref[k]), stage_tol(k, own[k])) for k in R.KEYS}
     for k, (err, tol) in rep.items():
-        print(f"{kind} C={C_} layers={layers} batch={batch} wrong={wrong} {k}: own {own[k]:.3e} gpu {err:.3e} tol {tol:.3e}")
+        print(f"{kind} C={C_} layers={layers} batch={batch} wrong={wrong} regime={regime} {k}: own {own[k]:.3e} gpu {err:.3e} tol {tol:.3e}")
     return rep
 
 
 CASES = [("cnn_gru_attention", 2, 2), ("cnn_gru_attention", 6, 2), ("cnn_gru", 2, 2), ("cnn_gru", 6, 2), ("cnn_gru_attention", 6, 1)]
 
 
-@pytest.mark.parametrize("kind,C_,layers", CASES)
-def test_both_stages_against_the_float64_restatement(kind, C_, layers):
-    rep = _gate(kind, C_, layers)
+# the same gate on windows whose channels sit 10 spreads from zero (tests/input_regimes.py "offset"): msig_ab_accumulate reduces the
+# conv kernels' BatchNorm partials.  tests/test_input_regimes_host.py asserts, on the host, that this case's `own` stays under OWN_CAP.
+REGIME_CASES = [IR.ADAPT_CASE]
+
+
+@pytest.mark.parametrize("kind,C_,layers,regime", [(*c, None) for c in CASES] + REGIME_CASES,
+                         ids=["-".join(map(str, c)) for c in CASES] + ["-".join(map(str, c)) for c in REGIME_CASES])
+def test_both_stages_against_the_float64_restatement(kind, C_, layers, regime):
+    rep = _gate(kind, C_, layers, regime=regime)
     bad = {k: v for k, v in rep.items() if not v[0] <= v[1]}
     assert not bad, bad
-    ref, _ = _reference(kind, C_, layers)
+    ref, _ = _reference(kind, C_, layers, regime=regime)
     src = O.init_buffers()
     for k in R.KEYS:                                   # the target statistics are far from the source's
         assert rel_err(src[k].numpy(), ref[k]) > 0.2, k

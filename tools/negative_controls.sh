@@ -20,6 +20,52 @@
 # tests/test_channel_class_range_gpu.py (must FAIL at least one case; the product must pass every case) and one of the OLD selection,
 # tests/test_parity_gpu.py -k "golden_case or ws6" (recorded: did the suite notice before?), with the time limits, the stop at the
 # first abnormal exit and the per-library sections of the regime mode.  LIBRARY: product 1 2 3 (default all).
+# tools/negative_controls.sh input [OUT] [LIBRARY ...]: the controls of the INPUT regimes (libraries built by
+#   for k in 1 2; do make -C multimodalsignal_amd/csrc negctl INPUT=$k; done ).  Each is one slip that no unit-scale, nearly centred
+# input can see (msig_dev.h MSIG_NEGCTL_INPUT): 1 the conv kernels' BatchNorm sums accumulated unshifted and reduced in fp32, 2 eps added
+# outside bn_finalize's square root.  Per library: one pass of tests/test_input_regimes_gpu.py with the AdaBN gate of
+# tests/test_adapt_gpu.py (must FAIL, in the regime named below) and one of the OLD selection, tests/test_parity_gpu.py -k "golden_case or
+# ws6" (recorded: did the suite notice before?  control 1 is the arithmetic those cases always ran and must pass them), with the time
+# limits, the stop at the first abnormal exit and the per-library sections of the regime mode.  LIBRARY: product 1 2 (default all).
+if [ "$1" = input ]; then
+  OUT=${2:-input_negctl_out/input_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1 2}
+  OLD='golden_case or ws6'
+  NEW='tests/test_input_regimes_gpu.py tests/test_adapt_gpu.py::test_both_stages_against_the_float64_restatement'
+  want() { case $1 in 1) echo offset;; 2) echo units_small;; esac; }
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_input$k.so; fi
+    sec=$D/input_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/input_negctl_${k}_new.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# new cases, $NEW (exit $rc):   $(tail -1 $D/input_negctl_${k}_new.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/input_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    nfail=$(grep -c "^FAILED " $D/input_negctl_${k}_new.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass the new cases" >> $sec; bad=1; }
+      continue
+    fi
+    nwant=$(grep "^FAILED " $D/input_negctl_${k}_new.txt | grep -c "$(want $k)")
+    if [ "$nwant" -gt 0 ]; then echo "# verdict: control $k FAILS $nfail new cases, $nwant of them under $(want $k)" >> $sec
+    else echo "!! control $k fails no new case under $(want $k) ($nfail failures in all): the new cases do not catch it" >> $sec; bad=1; fi
+    MSIG_LIB=$lib timeout -k 10 600 python -m pytest tests/test_parity_gpu.py -q -rA -p no:cacheprovider -k "$OLD" > $D/input_negctl_${k}_old.txt 2>&1; rc=$?
+    echo "# old selection, tests/test_parity_gpu.py -k \"$OLD\" (exit $rc):   $(tail -1 $D/input_negctl_${k}_old.txt)" >> $sec
+    grep -E "^FAILED " $D/input_negctl_${k}_old.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ $rc = 0 ]; then echo "# verdict: the old selection does NOT notice control $k" >> $sec; else echo "# verdict: the old selection notices control $k" >> $sec; fi
+    if [ "$k" = 1 ] && [ $rc != 0 ]; then echo "!! control 1 is the arithmetic the old selection always ran: it must pass it" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh input: $NEW and tests/test_parity_gpu.py -k \"$OLD\" against libmsig_hip_input<k>.so (make negctl INPUT=k)" > "$OUT"
+  for k in product 1 2; do [ -f $D/input_negctl_section_$k.log ] && cat $D/input_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = range ]; then
   OUT=${2:-range_negctl_out/range_negative_control.log}
   D=$(dirname "$OUT")
