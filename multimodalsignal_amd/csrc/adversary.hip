@@ -2,7 +2,6 @@
 // its own parameters and the REVERSED feature gradient added to MSIG_WS_DFEAT — in ONE launch between the head and the GRU backward
 // of a fused train step.
 #include "msig_dev.h"
-#include "finetune.h"
 
 // ------------------------------------------------------------------------------------
 // One workgroup of 256 threads per fold (blockIdx.z), B <= MSIG_DA_MAX_BATCH rows, the thread map of head_epoch_kernel
@@ -209,13 +208,14 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
     ls = wave_sum_d(ls); cs = wave_sum_d(cs); cn = wave_sum_d(cn);
     if ((tid & 63) == 0) { red[0][tid >> 6] = ls; red[1][tid >> 6] = cs; red[2][tid >> 6] = cn; }
   }
-  // ---- Adam, every element by its owner: parameters and moments written back ----
+  // ---- Adam, every element by its owner, in the forms these sites have always been compiled to (msig_dev.h AdamForm): parameters
+  // and moments written back ----
   const float lrb = a.lr_over_bc1[z], isb = a.inv_sqrt_bc2[z];
 #pragma unroll
   for (int j = 0; j < 32; ++j) {
     const int i = (half * 32 + j) * 128 + kcol;
     float m = ea[i], s = eas[i];
-    W0[i] = ft_adam(W0t[kcol * DA_W0S + half * 32 + j], dW0acc[j], m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
+    W0[i] = adam_update<ADAM_FUSED_V>(W0t[kcol * DA_W0S + half * 32 + j], dW0acc[j], m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
     ea[i] = m; eas[i] = s;
   }
   const int64_t o3 = W3 - W0, ob0 = b0 - W0, ob3 = b3 - W0;
@@ -224,18 +224,18 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
     const int i = tid + 256 * j;
     if (i < S * 64) {
       float m = ea[o3 + i], s = eas[o3 + i];
-      W3[i] = ft_adam(W3s[(i >> 6) * DA_W3S + (i & 63)], dW3acc[j], m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
+      W3[i] = adam_update<ADAM_FUSED_G>(W3s[(i >> 6) * DA_W3S + (i & 63)], dW3acc[j], m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
       ea[o3 + i] = m; eas[o3 + i] = s;
     }
   }
   if (tid < 64) {
     float m = ea[ob0 + tid], s = eas[ob0 + tid];
-    b0[tid] = ft_adam(b0s[tid], db0acc, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
+    b0[tid] = adam_update<ADAM_FUSED_G>(b0s[tid], db0acc, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
     ea[ob0 + tid] = m; eas[ob0 + tid] = s;
   }
   if (tid < S) {
     float m = ea[ob3 + tid], s = eas[ob3 + tid];
-    b3[tid] = ft_adam(b3s[tid], db3acc, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
+    b3[tid] = adam_update<ADAM_FUSED_G>(b3s[tid], db3acc, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
     ea[ob3 + tid] = m; eas[ob3 + tid] = s;
   }
   __syncthreads();

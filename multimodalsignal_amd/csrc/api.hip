@@ -78,8 +78,6 @@ extern "C" int64_t msig_profile_report(char* buf, int64_t cap) {
 
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                 int64_t step, hipStream_t st);
-int launch_normalise(const double* raw, int64_t N, int T, int C_all, const int* cols, int C, uint32_t mask, float* out, void* scratch,
-                     hipStream_t st);
 int launch_gather(const float* store, const int64_t* sy, const int64_t* idx, int64_t idx_row_stride, int B, int64_t wfloats, float* ox, int64_t* oy,
                   const FoldCtx& fc, hipStream_t st);
 
@@ -804,16 +802,4 @@ extern "C" int msig_channel_attention(const float* x, const float* w1, const flo
   if (B < 1 || C < 1 || C > MSIG_MAX_C || T < 1) return MSIG_E_SHAPE;
   if (C >= 4 && (!w1 || !w2)) return MSIG_E_NULL;
   return launch_channel_attention(x, w1, w2, B, C, T, out, s, scratch, (hipStream_t)stream);
-}
-
-extern "C" int64_t msig_normalise_scratch_bytes(void) { return (int64_t)(512 * 2 * MSIG_MAX_C + 2 * MSIG_MAX_C) * (int64_t)sizeof(double); }
-
-extern "C" int msig_normalise_subject(const double* raw, int64_t N, int32_t T, int32_t C_all, const int32_t* cols, int32_t C,
-                                      uint32_t log1p_mask, float* out, void* scratch, void* stream) {
-  if (!raw || !cols || !out || !scratch) return MSIG_E_NULL;
-  if (N < 1 || T < 1 || C_all < 1 || C < 1 || C > MSIG_MAX_C) return MSIG_E_SHAPE;
-  for (int c = 0; c < C; ++c)
-    if (cols[c] < 0 || cols[c] >= C_all) return MSIG_E_SHAPE;
-  if (((uintptr_t)raw | (uintptr_t)scratch) & 7) return MSIG_E_ALIGN;
-  return launch_normalise(raw, N, T, C_all, cols, C, log1p_mask, out, scratch, (hipStream_t)stream);
 }

@@ -15,14 +15,3 @@ struct FtFolds {
 int launch_head_epoch(const msig_ft_head& h, const FtFolds& ff, hipStream_t st);
 // MSIG_WS_FEAT (B,128) of every fold of the launch -> out + z * out_stride_bytes
 int launch_ft_feat_copy(const float* feat, float* out, int64_t out_stride_bytes, int B, const FoldCtx& fc, hipStream_t st);
-
-// torch.optim.Adam with L2-in-gradient weight decay — the arithmetic of adam_kernel (head.hip), element by element; shared by
-// the head epoch (finetune.hip) and the discriminator step (adversary.hip)
-__device__ __forceinline__ float ft_adam(float p, float g, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
-                                         float eps, float wd) {
-  const float gr = g + wd * p;
-  m = b1 * m + (1.f - b1) * gr;
-  v = b2 * v + (1.f - b2) * gr * gr;
-  const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-  return p - lr_over_bc1 * (m / denom);
-}

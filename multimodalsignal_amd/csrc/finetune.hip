@@ -245,19 +245,19 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
       ls = wave_sum_d(ls); cs = wave_sum_d(cs);
       if ((tid & 63) == 0) { red[0][tid >> 6] = ls; red[1][tid >> 6] = cs; }
     }
-    // ---- Adam, every element by its owner ----
+    // ---- Adam, every element by its owner, in the forms these sites have always been compiled to (msig_dev.h AdamForm) ----
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
       float* p = &W0t[kcol * FT_W0S + half * 32 + j];
-      *p = ft_adam(*p, dW0acc[j], m0[j], v0[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+      *p = adam_update<ADAM_FUSED_V>(*p, dW0acc[j], m0[j], v0[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int idx = tid + 256 * j;
-      if (idx < K * 64) W3s[idx] = ft_adam(W3s[idx], dW3acc[j], m3[j], v3[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+      if (idx < K * 64) W3s[idx] = adam_update<ADAM_PRODUCTS>(W3s[idx], dW3acc[j], m3[j], v3[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
     }
-    if (tid < 64) b0s[tid] = ft_adam(b0s[tid], db0acc, mb0, vb0, lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
-    if (tid < K) b3s[tid] = ft_adam(b3s[tid], db3acc, mb3, vb3, lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+    if (tid < 64) b0s[tid] = adam_update<ADAM_FUSED_V>(b0s[tid], db0acc, mb0, vb0, lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
+    if (tid < K) b3s[tid] = adam_update<ADAM_FUSED_V>(b3s[tid], db3acc, mb3, vb3, lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
     __syncthreads();
     if (tid == 0) {
       double ls = 0.0, cs = 0.0;

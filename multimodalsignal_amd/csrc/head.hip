@@ -579,59 +579,76 @@ static int colsum_fill(const ColsumPlan& plan, ColsumJobs& a) {
   return at;
 }
 
-__global__ __launch_bounds__(256) void colsum_plan_kernel(const ColsumJobs jobs, const FoldCtx fc) {
-  __shared__ double red[CS_LANES][CS_COLS];
+// What the three reduction kernels share: the workgroup's job and its fold's pointers, the lane sums of its 32 columns into red,
+// the barrier, and — in the lane that owns a live column c (row-lane 0: `owner`) — the folded float sum stored to out[c], or read
+// from it when the job is a gradient already in place (nrows == 0: nothing to add up, no barrier).  Every thread of the workgroup
+// must call it.
+struct ColsumCol { float* out; int c; bool owner; float gsum; };      // out: the job's, of this fold
+__device__ __forceinline__ ColsumCol colsum_column(const ColsumJobs& jobs, const FoldCtx& fc, double (*red)[CS_COLS]) {
   const int ji = colsum_find_job(jobs, blockIdx.x);
   ColsumJob jb = jobs.j[ji];
   const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
   FS(jb.part); FS(jb.out);
   const int cx = threadIdx.x & (CS_COLS - 1), ry = threadIdx.x / CS_COLS;
   const int c = ((int)blockIdx.x - jobs.blk0[ji]) * CS_COLS + cx;
-  red[ry][cx] = c < jb.ncols ? colsum_lane(jb.part + jb.col0 + c, jb.nrows, (size_t)jb.row_stride, ry) : 0.0;
-  __syncthreads();
-  if (ry == 0 && c < jb.ncols) jb.out[c] = (float)colsum_fold(red, cx);
+  if (jb.nrows > 0) {
+    red[ry][cx] = c < jb.ncols ? colsum_lane(jb.part + jb.col0 + c, jb.nrows, (size_t)jb.row_stride, ry) : 0.0;
+    __syncthreads();
+  }
+  ColsumCol r{jb.out, c, ry == 0 && c < jb.ncols, 0.f};
+  if (r.owner) {
+    if (jb.nrows > 0) { r.gsum = (float)colsum_fold(red, cx); jb.out[c] = r.gsum; }
+    else r.gsum = jb.out[c];
+  }
+  return r;
+}
+
+// The fused head's loss (launched only then): the one workgroup past the column blocks runs loss_finalize and answers true.
+template <bool CW, bool ST>
+__device__ __forceinline__ bool colsum_loss_workgroup(const ColsumJobs& jobs, const LossFin& loss_in, const FoldCtx& fc, const SoftT<ST>& sa) {
+  if ((int)blockIdx.x != jobs.blk0[MSIG_MAX_JOBS]) return false;
+  __shared__ double lred[2][CE_THREADS / 64];
+  __shared__ double wred[4];
+  LossFin lf = loss_in;
+  const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
+  FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
+  if constexpr (CW) FS(lf.cw);
+  loss_finalize<CW, ST>(lf, lred, wred, sa, (int)blockIdx.y);
+  return true;
+}
+
+// The <CW, ST> instantiation of a kernel family and its SoftT argument, picked in one place: f(CwSt<CW, ST>{}, SoftT<ST>) launches.
+template <bool CW, bool ST> struct CwSt { static constexpr bool cw = CW, st = ST; };
+template <typename F>
+static void cw_st_dispatch(const float* cw, const SoftArgs* soft, F&& f) {
+  if (soft) {
+    const SoftT<true> sa{*soft};
+    if (cw) f(CwSt<true, true>{}, sa); else f(CwSt<false, true>{}, sa);
+  }
+  else if (cw) f(CwSt<true, false>{}, SoftT<false>{});
+  else f(CwSt<false, false>{}, SoftT<false>{});
+}
+
+__global__ __launch_bounds__(256) void colsum_plan_kernel(const ColsumJobs jobs, const FoldCtx fc) {
+  __shared__ double red[CS_LANES][CS_COLS];
+  colsum_column(jobs, fc, red);
 }
 
 template <bool CW, bool ST = false>
 __global__ __launch_bounds__(256) void colsum_adam_kernel(const ColsumJobs jobs, const AdamArgs ad_in, const LossFin loss_in, const FoldCtx fc,
                                                           const SoftT<ST> sa) {
   __shared__ double red[CS_LANES][CS_COLS];
-  if ((int)blockIdx.x == jobs.blk0[MSIG_MAX_JOBS]) {          // one workgroup past the column blocks: the fused head's loss (launched only then)
-    __shared__ double lred[2][CE_THREADS / 64];
-    __shared__ double wred[4];
-    LossFin lf = loss_in;
-    const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
-    FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
-    if constexpr (CW) FS(lf.cw);
-    loss_finalize<CW, ST>(lf, lred, wred, sa, (int)blockIdx.y);
-    return;
-  }
-  const int ji = colsum_find_job(jobs, blockIdx.x);
-  ColsumJob jb = jobs.j[ji];
+  if (colsum_loss_workgroup<CW, ST>(jobs, loss_in, fc, sa)) return;
   AdamArgs ad = ad_in;
   const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
-  FS(jb.part); FS(jb.out); FS(ad.p); FS(ad.g); FS(ad.m); FS(ad.v);
-  ad.lr_over_bc1 = fc.lr_over_bc1[blockIdx.y];
-  ad.inv_sqrt_bc2 = fc.inv_sqrt_bc2[blockIdx.y];
-  const int cx = threadIdx.x & (CS_COLS - 1), ry = threadIdx.x / CS_COLS;
-  const int c = ((int)blockIdx.x - jobs.blk0[ji]) * CS_COLS + cx;
-  if (jb.nrows > 0) {
-    red[ry][cx] = c < jb.ncols ? colsum_lane(jb.part + jb.col0 + c, jb.nrows, (size_t)jb.row_stride, ry) : 0.0;
-    __syncthreads();
-  }
-  if (ry == 0 && c < jb.ncols) {
-    float gsum;
-    if (jb.nrows > 0) { gsum = (float)colsum_fold(red, cx); jb.out[c] = gsum; }
-    else gsum = jb.out[c];
-    // torch.optim.Adam with L2-in-gradient weight decay — the arithmetic of adam_kernel, element by element
-    const int64_t i = (jb.out - ad.g) + c;
-    const float gr = gsum + ad.wd * ad.p[i];
-    const float mm = ad.b1 * ad.m[i] + (1.f - ad.b1) * gr;
-    const float vv = ad.b2 * ad.v[i] + (1.f - ad.b2) * gr * gr;
-    const float denom = sqrtf(vv) * ad.inv_sqrt_bc2 + ad.eps;
-    ad.p[i] -= ad.lr_over_bc1 * (mm / denom);
-    ad.m[i] = mm;
-    ad.v[i] = vv;
+  FS(ad.p); FS(ad.g); FS(ad.m); FS(ad.v);
+  const ColsumCol col = colsum_column(jobs, fc, red);
+  if (col.owner) {
+    const int64_t i = (col.out - ad.g) + col.c;
+    float m = ad.m[i], v = ad.v[i];
+    ad.p[i] = adam_update(ad.p[i], col.gsum, m, v, fc.lr_over_bc1[blockIdx.y], fc.inv_sqrt_bc2[blockIdx.y], ad.b1, ad.b2, ad.eps, ad.wd);
+    ad.m[i] = m;
+    ad.v[i] = v;
   }
 }
 
@@ -643,13 +660,9 @@ int launch_colsum_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, const Fo
   {
     MSIG_K("colsum_adam", st);
     const dim3 grid(nblk + (plan.loss.logits ? 1 : 0), fc.n);
-    if (plan.soft && plan.loss.logits) {
-      const SoftT<true> sa{*plan.soft};
-      if (plan.loss.cw) colsum_adam_kernel<true, true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, sa);
-      else colsum_adam_kernel<false, true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, sa);
-    }
-    else if (plan.loss.cw) colsum_adam_kernel<true><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, SoftT<false>{});
-    else colsum_adam_kernel<false><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, SoftT<false>{});
+    cw_st_dispatch(plan.loss.cw, plan.loss.logits ? plan.soft : nullptr, [&](auto k, const auto& sa) {
+      colsum_adam_kernel<decltype(k)::cw, decltype(k)::st><<<grid, 256, 0, st>>>(a, ad, plan.loss, fc, sa);
+    });
   }
   MSIG_LAUNCH_CHECK();
   return 0;
@@ -673,34 +686,12 @@ template <bool CW, bool ST = false>
 __global__ __launch_bounds__(256) void colsum_sq_kernel(const ColsumJobs jobs, double* __restrict__ state, const LossFin loss_in, const FoldCtx fc,
                                                         const SoftT<ST> sa) {
   __shared__ double red[CS_LANES][CS_COLS];
-  if ((int)blockIdx.x == jobs.blk0[MSIG_MAX_JOBS]) {          // the fused head's loss, as in colsum_adam_kernel
-    __shared__ double lred[2][CE_THREADS / 64];
-    __shared__ double wred[4];
-    LossFin lf = loss_in;
-    const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
-    FS(lf.logits); FS(lf.labels); FS(lf.lossbuf); FS(lf.lacc);
-    if constexpr (CW) FS(lf.cw);
-    loss_finalize<CW, ST>(lf, lred, wred, sa, (int)blockIdx.y);
-    return;
-  }
-  const int ji = colsum_find_job(jobs, blockIdx.x);
-  ColsumJob jb = jobs.j[ji];
+  if (colsum_loss_workgroup<CW, ST>(jobs, loss_in, fc, sa)) return;
   const int64_t foff_ = (int64_t)fc.slot[blockIdx.y] * fc.stride;
-  FS(jb.part); FS(jb.out); FS(state);
-  const int cx = threadIdx.x & (CS_COLS - 1), ry = threadIdx.x / CS_COLS;
-  const int c = ((int)blockIdx.x - jobs.blk0[ji]) * CS_COLS + cx;
-  if (jb.nrows > 0) {
-    red[ry][cx] = c < jb.ncols ? colsum_lane(jb.part + jb.col0 + c, jb.nrows, (size_t)jb.row_stride, ry) : 0.0;
-    __syncthreads();
-  }
+  FS(state);
+  const ColsumCol col = colsum_column(jobs, fc, red);
   if (threadIdx.x < 64) {                                     // wave 0: lanes 0..31 own the columns, lanes 32..63 add zeros
-    double sq = 0.0;
-    if (ry == 0 && c < jb.ncols) {
-      float gsum;
-      if (jb.nrows > 0) { gsum = (float)colsum_fold(red, cx); jb.out[c] = gsum; }
-      else gsum = jb.out[c];
-      sq = (double)gsum * (double)gsum;
-    }
+    double sq = col.owner ? (double)col.gsum * (double)col.gsum : 0.0;
     sq = wave_sum_d(sq);
     if (threadIdx.x == 0) state[MSIG_GC_NSTAT + blockIdx.x] = sq;
   }
@@ -756,21 +747,14 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const ColsumJobs jobs, c
       if (idx[u] < 0) continue;
       const int64_t i = idx[u];
       {
-        // Every rounding spelled out, nothing left to contraction: the clip is a multiplication of its own, and the Adam statements
-        // are colsum_adam_kernel's AS COMPILED — there hipcc fuses wd * p, b1 * m, sqrt(vv) * inv_sqrt_bc2 and lr * (mm / denom)
-        // into FMAs and leaves (1 - b1) * gr, b2 * v and ((1 - b2) * gr) * gr as products.  Left to itself it pairs the statements
-        // of this loop into packed instructions and picks the other product of mm for the FMA: one ulp off the unclipped step.
-        // tests/test_grad_clip_gpu.py (max_norm = inf against the unclipped step, bit for bit) holds the two kernels together.
+        // The clip is a multiplication of its own, one rounding; then the train step's Adam (msig_dev.h adam_update), the function
+        // colsum_adam_kernel calls: with coef = 1 the step's bits are the unclipped step's.
 #pragma clang fp contract(off)
         const float gsum = g[u] * coef;
         ad.g[i] = gsum;
-        const float gr = __builtin_fmaf(ad.wd, p[u], gsum);
-        const float mm = __builtin_fmaf(ad.b1, m[u], (1.f - ad.b1) * gr);
-        const float vv = ad.b2 * v[u] + ((1.f - ad.b2) * gr) * gr;
-        const float denom = __builtin_fmaf(sqrtf(vv), ad.inv_sqrt_bc2, ad.eps);
-        ad.p[i] = __builtin_fmaf(-ad.lr_over_bc1, mm / denom, p[u]);
-        ad.m[i] = mm;
-        ad.v[i] = vv;
+        ad.p[i] = adam_update(p[u], gsum, m[u], v[u], ad.lr_over_bc1, ad.inv_sqrt_bc2, ad.b1, ad.b2, ad.eps, ad.wd);
+        ad.m[i] = m[u];
+        ad.v[i] = v[u];
       }
     }
   }
@@ -785,13 +769,9 @@ int launch_colsum_clip_adam_plan(const ColsumPlan& plan, const AdamArgs& ad, con
   {
     MSIG_K("colsum_sq", st);
     const dim3 grid(nblk + (plan.loss.logits ? 1 : 0), fc.n);
-    if (plan.soft && plan.loss.logits) {
-      const SoftT<true> sa{*plan.soft};
-      if (plan.loss.cw) colsum_sq_kernel<true, true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, sa);
-      else colsum_sq_kernel<false, true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, sa);
-    }
-    else if (plan.loss.cw) colsum_sq_kernel<true><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, SoftT<false>{});
-    else colsum_sq_kernel<false><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, SoftT<false>{});
+    cw_st_dispatch(plan.loss.cw, plan.loss.logits ? plan.soft : nullptr, [&](auto k, const auto& sa) {
+      colsum_sq_kernel<decltype(k)::cw, decltype(k)::st><<<grid, 256, 0, st>>>(a, cl.state, plan.loss, fc, sa);
+    });
   }
   MSIG_LAUNCH_CHECK();
   {
@@ -833,7 +813,8 @@ PartOffsets part_offsets(const StageDims& d) {
 }
 
 // ------------------------------------------------------------------------------------
-// Adam with L2 weight decay folded into the gradient (torch.optim.Adam semantics)
+// msig_adam_step: Adam on a flat buffer, four elements per thread.  Its second moment is the fused form (msig_dev.h ADAM_FUSED_V),
+// as this kernel has always been compiled: not the train step's, from the second step on.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n4, float lr_over_bc1, float inv_sqrt_bc2,
@@ -844,115 +825,11 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     float pa[4] = {pp.x, pp.y, pp.z, pp.w}, ma[4] = {mm.x, mm.y, mm.z, mm.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
     const float ga[4] = {gg.x, gg.y, gg.z, gg.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gr = ga[e] + wd * pa[e];
-      ma[e] = b1 * ma[e] + (1.f - b1) * gr;
-      va[e] = b2 * va[e] + (1.f - b2) * gr * gr;
-      const float denom = sqrtf(va[e]) * inv_sqrt_bc2 + eps;
-      pa[e] -= lr_over_bc1 * (ma[e] / denom);
-    }
+    for (int e = 0; e < 4; ++e) pa[e] = adam_update<ADAM_FUSED_V>(pa[e], ga[e], ma[e], va[e], lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, wd);
     ((float4*)p)[i] = make_float4(pa[0], pa[1], pa[2], pa[3]);
     ((float4*)m)[i] = make_float4(ma[0], ma[1], ma[2], ma[3]);
     ((float4*)v)[i] = make_float4(va[0], va[1], va[2], va[3]);
   }
-}
-
-// blockIdx.z = fold (msig_gather_windows_multi): the store is shared, idx is (n, B) contiguous, the outputs are per-arena
-__global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ store, const int64_t* __restrict__ store_y,
-                                                     const int64_t* __restrict__ idx, int64_t idx_row_stride, int64_t w4,
-                                                     float* __restrict__ ox, int64_t* __restrict__ oy, const FoldCtx fc) {
-  FOLD_BEGIN; FS(ox); FS(oy);
-  const int i = blockIdx.y;
-  const int64_t src = idx[(int64_t)blockIdx.z * idx_row_stride + i];
-  const float4* s4 = (const float4*)(store) + src * w4;
-  float4* d4 = (float4*)(ox) + (int64_t)i * w4;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < w4; j += (int64_t)gridDim.x * 256) d4[j] = s4[j];
-  if (oy && store_y && blockIdx.x == 0 && threadIdx.x == 0) oy[i] = store_y[src];
-}
-
-// ------------------------------------------------------------------------------------
-// Per-subject normalisation of raw windows (dataset.py:36-48) + the (N,T,C)->(N,C,T) fp32 layout
-// ------------------------------------------------------------------------------------
-#define NORM_WG 512
-struct NormCols { int col[MSIG_MAX_C]; };
-
-__global__ __launch_bounds__(256) void norm_stats_kernel(const double* __restrict__ raw, int64_t rows, int C_all, NormCols cols,
-                                                         int C, uint32_t log1p_mask, double* __restrict__ part) {
-  __shared__ double red[4][2 * MSIG_MAX_C];
-  double s1[MSIG_MAX_C], s2[MSIG_MAX_C];
-#pragma unroll
-  for (int c = 0; c < MSIG_MAX_C; ++c) s1[c] = s2[c] = 0.0;
-  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (int64_t)gridDim.x * 256) {
-    const double* row = raw + r * C_all;
-#pragma unroll
-    for (int c = 0; c < MSIG_MAX_C; ++c)
-      if (c < C) {
-        double v = row[cols.col[c]];
-        if ((log1p_mask >> c) & 1u) v = log1p(v);
-        s1[c] += v; s2[c] += v * v;
-      }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < MSIG_MAX_C; ++c)
-    if (c < C) {
-      const double a = wave_sum_d(s1[c]), b = wave_sum_d(s2[c]);
-      if (lane == 0) { red[w][c] = a; red[w][MSIG_MAX_C + c] = b; }
-    }
-  __syncthreads();
-  if (threadIdx.x < 2 * MSIG_MAX_C)
-    part[(size_t)blockIdx.x * 2 * MSIG_MAX_C + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-__global__ __launch_bounds__(64) void norm_finalize_kernel(const double* __restrict__ part, int nparts, int C, double count,
-                                                           double* __restrict__ stats) {
-  const int c = threadIdx.x;
-  if (c >= C) return;
-  double a = 0.0, b = 0.0;
-  for (int i = 0; i < nparts; ++i) { a += part[(size_t)i * 2 * MSIG_MAX_C + c]; b += part[(size_t)i * 2 * MSIG_MAX_C + MSIG_MAX_C + c]; }
-  const double mean = a / count;
-  double var = b / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  stats[c] = mean;
-  stats[MSIG_MAX_C + c] = 1.0 / (sqrt(var) + 1e-8);
-}
-
-__global__ __launch_bounds__(256) void norm_apply_kernel(const double* __restrict__ raw, int64_t N, int T, int C_all, NormCols cols, int C,
-                                                         uint32_t log1p_mask, const double* __restrict__ stats, float* __restrict__ out) {
-  const int64_t rows = N * T;
-  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (int64_t)gridDim.x * 256) {
-    const int64_t n = r / T;
-    const int t = (int)(r - n * T);
-    const double* row = raw + r * C_all;
-#pragma unroll
-    for (int c = 0; c < MSIG_MAX_C; ++c)
-      if (c < C) {
-        double v = row[cols.col[c]];
-        if ((log1p_mask >> c) & 1u) v = log1p(v);
-        out[((size_t)n * C + c) * T + t] = (float)((v - stats[c]) * stats[MSIG_MAX_C + c]);
-      }
-  }
-}
-
-int launch_normalise(const double* raw, int64_t N, int T, int C_all, const int* cols, int C, uint32_t mask, float* out, void* scratch,
-                     hipStream_t st) {
-  NormCols nc;
-  for (int c = 0; c < MSIG_MAX_C; ++c) nc.col[c] = c < C ? cols[c] : 0;
-  double* part = (double*)scratch;
-  double* stats = part + (size_t)NORM_WG * 2 * MSIG_MAX_C;
-  const int64_t rows = N * T;
-  int grid = (int)((rows + 255) / 256);
-  if (grid > NORM_WG) grid = NORM_WG;
-  if (grid < 1) grid = 1;
-  { MSIG_K("norm_stats", st); norm_stats_kernel<<<grid, 256, 0, st>>>(raw, rows, C_all, nc, C, mask, part); }
-  MSIG_LAUNCH_CHECK();
-  { MSIG_K("norm_finalize", st); norm_finalize_kernel<<<1, 64, 0, st>>>(part, grid, C, (double)rows, stats); }
-  MSIG_LAUNCH_CHECK();
-  int g2 = (int)((rows + 255) / 256);
-  if (g2 > 8192) g2 = 8192;
-  { MSIG_K("norm_apply", st); norm_apply_kernel<<<g2, 256, 0, st>>>(raw, N, T, C_all, nc, C, mask, stats, out); }
-  MSIG_LAUNCH_CHECK();
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -974,18 +851,11 @@ int launch_head_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, co
   if (b->labels) {
     MSIG_K("ce", st);
     float* dl = msig_keeps(b) ? w.p<float>(MSIG_WS_DLOGITS) : nullptr;
-    if (soft) {
-      const SoftT<true> sa{*soft};
-      auto* kern = cw ? ce_kernel<true, true> : ce_kernel<false, true>;
-      kern<<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                                    dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B, d.K, fc, sa);
-    }
-    else if (cw)
-      ce_kernel<true><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                                             dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B, d.K, fc, SoftT<false>{});
-    else
-      ce_kernel<false><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED),
-                                                              dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, nullptr, d.B, d.K, fc, SoftT<false>{});
+    cw_st_dispatch(cw, soft, [&](auto k, const auto& sa) {
+      ce_kernel<decltype(k)::cw, decltype(k)::st><<<dim3(1, 1, fc.n), CE_THREADS, 0, st>>>(
+          w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED), dl, w.p<float>(MSIG_WS_LOSS), b->loss_acc, cw, d.B,
+          d.K, fc, sa);
+    });
   } else {
     MSIG_K("softmax", st);
     softmax_kernel<<<dim3((d.B + 255) / 256, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED), d.B, d.K, fc);
@@ -1029,20 +899,12 @@ int launch_head_step(const msig_batch* b, const StageDims& d, const WsPtrs& w, c
   const int PS = 64 * 128 + 64 + d.K * 64 + d.K;
   {
     MSIG_K("head_step", st);
-    if (soft) {
-      const SoftT<true> sa{*soft};
-      auto* kern = cw ? head_step_kernel<true, true> : head_step_kernel<false, true>;
-      kern<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
-                                                P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS),
-                                                w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr,
-                                                b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc, sa);
-    } else {
-      auto* kern = cw ? head_step_kernel<true> : head_step_kernel<false>;
-      kern<<<dim3(grid, 1, fc.n), 256, 0, st>>>(w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W],
-                                                P + po[MSIG_P_CLS3_B], b->labels, w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS),
-                                                w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS), w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr,
-                                                b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc, SoftT<false>{});
-    }
+    cw_st_dispatch(cw, soft, [&](auto k, const auto& sa) {
+      head_step_kernel<decltype(k)::cw, decltype(k)::st><<<dim3(grid, 1, fc.n), 256, 0, st>>>(
+          w.p<float>(MSIG_WS_FEAT), P + po[MSIG_P_CLS0_W], P + po[MSIG_P_CLS0_B], P + po[MSIG_P_CLS3_W], P + po[MSIG_P_CLS3_B], b->labels,
+          w.p<float>(MSIG_WS_HID), w.p<float>(MSIG_WS_LOGITS), w.p<float>(MSIG_WS_PROBS), w.p<int>(MSIG_WS_PRED), w.p<float>(MSIG_WS_DLOGITS),
+          w.p<float>(MSIG_WS_DFEAT), part, cw, d.B, d.K, thr, b->key_head, drop_scale(thr), thr > 0 ? drop_scale(thr) : 1.0f, fc, sa);
+    });
   }
   MSIG_LAUNCH_CHECK();
   plan.loss = LossFin{w.p<float>(MSIG_WS_LOGITS), b->labels, w.p<float>(MSIG_WS_LOSS), b->loss_acc, d.B, d.K, cw};
@@ -1061,16 +923,6 @@ int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float l
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   { MSIG_K("adam", st); adam_kernel<<<(int)blocks, 256, 0, st>>>(p, g, m, v, n4, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, wd); }
-  MSIG_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_gather(const float* store, const int64_t* sy, const int64_t* idx, int64_t idx_row_stride, int B, int64_t wfloats, float* ox, int64_t* oy,
-                  const FoldCtx& fc, hipStream_t st) {
-  const int64_t w4 = wfloats / 4;
-  int gx = (int)((w4 + 255) / 256);
-  if (gx > 64) gx = 64;
-  { MSIG_K("gather", st); gather_kernel<<<dim3(gx, B, fc.n), 256, 0, st>>>(store, sy, idx, idx_row_stride, w4, ox, oy, fc); }
   MSIG_LAUNCH_CHECK();
   return 0;
 }

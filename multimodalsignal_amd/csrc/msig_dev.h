@@ -314,6 +314,39 @@ __device__ __forceinline__ void bn_running_update(float momentum, float mean, fl
   new_var = __builtin_fmaf(momentum, unbiased, (1.0f - momentum) * old_var);
 }
 
+// torch.optim.Adam with L2-in-gradient weight decay, one element, every rounding PINNED.  The library's
+// Adam is the ADAM_STEP form:
+//     gr    = fma(wd, p, g)
+//     m'    = fma(b1, m, (1 - b1) * gr)
+//     v'    = b2 * v + ((1 - b2) * gr) * gr            two rounded products and their sum
+//     denom = fma(sqrt(v'), inv_sqrt_bc2, eps)
+//     p'    = fma(-lr_over_bc1, m' / denom, p)
+// Each of m' and v' is a sum of two products, of which contraction may fuse either or neither, and before this function existed
+// the compiler chose per call site.  What it chose is kept, bit for bit, by the other three forms — they differ from ADAM_STEP in
+// those two statements (ADAM_PRODUCTS: and in denom) only, and say so in their names' comments:
+enum AdamForm {
+  ADAM_STEP,       // the train steps: colsum_adam_kernel, clip_adam_kernel
+  ADAM_FUSED_V,    // v' = fma(b2, v, ((1 - b2) * gr) * gr): adam_kernel; head_epoch_kernel's and da_step_kernel's W0 elements
+                   // (32 per thread, compiled to packed instructions); head_epoch_kernel's b0 and b3
+  ADAM_PRODUCTS,   // no sum of products fused but p': m' = b1 * m + (1 - b1) * gr as two rounded products and their sum, v' as
+                   // ADAM_STEP, denom = sqrt(v') * inv_sqrt_bc2 + eps as a rounded product and a sum: head_epoch_kernel's W3
+  ADAM_FUSED_G     // m' = fma(1 - b1, gr, b1 * m), v' as ADAM_STEP: da_step_kernel's W3, b0 and b3
+};
+template <AdamForm F = ADAM_STEP>
+__device__ __forceinline__ float adam_update(float p, float g, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
+                                             float eps, float wd) {
+#pragma clang fp contract(off)
+  const float gr = __builtin_fmaf(wd, p, g);
+  const float g1 = (1.f - b1) * gr, g2 = ((1.f - b2) * gr) * gr;
+  if constexpr (F == ADAM_PRODUCTS) m = b1 * m + g1;
+  else if constexpr (F == ADAM_FUSED_G) m = __builtin_fmaf(1.f - b1, gr, b1 * m);
+  else m = __builtin_fmaf(b1, m, g1);
+  if constexpr (F == ADAM_FUSED_V) v = __builtin_fmaf(b2, v, g2);
+  else v = b2 * v + g2;
+  const float denom = F == ADAM_PRODUCTS ? sqrtf(v) * inv_sqrt_bc2 + eps : __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+  return __builtin_fmaf(-lr_over_bc1, m / denom, p);
+}
+
 // ---- fold batching (msig_*_multi): one launch covers several independent models ("folds" of the LOSO loop) -------------
 // Every buffer of fold f (parameters, gradients, Adam moments, BN state, workspace, input batch, labels) lives at the SAME
 // offset inside a per-fold arena, arenas are `stride` bytes apart, and blockIdx.z selects the fold: every pointer a kernel
