@@ -29,6 +29,7 @@
 #include "msig_dev.h"
 
 #include "gru_args.h"
+#include "gru_frag.h"
 #include "gru_bwd4.h"
 #include "gru_dw2.h"
 
@@ -118,10 +119,10 @@ __global__ __launch_bounds__(256, (I == 32) ? 4 : 2) void gru_fwd_seq(const GruA
     }
   }
   if (tid < 64) {
-    bias_s[0][tid] = D.bih[tid] + D.bhh[tid];
-    bias_s[1][tid] = D.bih[64 + tid] + D.bhh[64 + tid];
-    bias_s[2][tid] = D.bih[128 + tid];
-    bias_s[3][tid] = D.bhh[128 + tid];
+    bias_s[0][tid] = GRU_BIAS_R(D, tid);
+    bias_s[1][tid] = GRU_BIAS_Z(D, tid);
+    bias_s[2][tid] = GRU_BIAS_IN(D, tid);
+    bias_s[3][tid] = GRU_BIAS_HN(D, tid);
   }
   for (int i = tid; i < 2 * 16 * HS; i += 256) (&hbuf[0][0][0])[i] = 0.f;
   // staged-x state (XLDS): thread -> two float4 pieces (row, c4) of the tile; running pointers like everything else
@@ -311,26 +312,16 @@ __global__ __launch_bounds__(256, 1) void gru_fwd_b3(const GruArgs a) {
   bf16x8 Ah[3][2][3], Ai[3][NKX][3];
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const float* wr = D.Whh + (size_t)(g * 64 + w * 16 + li) * 64 + kb * 32 + lq * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { __bf16 p0, p1, p2; split3(wr[j], p0, p1, p2); Ah[g][kb][0][j] = p0; Ah[g][kb][1][j] = p1; Ah[g][kb][2][j] = p2; }
-    }
-#pragma unroll
-    for (int kb = 0; kb < NKX; ++kb) {
-      const float* wi = D.Wih + (size_t)(g * 64 + w * 16 + li) * I + kb * 32 + lq * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { __bf16 p0, p1, p2; split3(wi[j], p0, p1, p2); Ai[g][kb][0][j] = p0; Ai[g][kb][1][j] = p1; Ai[g][kb][2][j] = p2; }
-    }
+    LOAD_FRAG_BF16X3(2, D.Whh + (size_t)(g * 64 + w * 16 + li) * 64, lq, Ah[g])
+    LOAD_FRAG_BF16X3(NKX, D.Wih + (size_t)(g * 64 + w * 16 + li) * I, lq, Ai[g])
   }
   f32x4 b_r, b_z, b_in, b_hn;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    b_r[e] = D.bih[u0 + e] + D.bhh[u0 + e];
-    b_z[e] = D.bih[64 + u0 + e] + D.bhh[64 + u0 + e];
-    b_in[e] = D.bih[128 + u0 + e];
-    b_hn[e] = D.bhh[128 + u0 + e];
+    b_r[e] = GRU_BIAS_R(D, u0 + e);
+    b_z[e] = GRU_BIAS_Z(D, u0 + e);
+    b_in[e] = GRU_BIAS_IN(D, u0 + e);
+    b_hn[e] = GRU_BIAS_HN(D, u0 + e);
   }
   for (int i = tid; i < 2 * 3 * 16 * HSB; i += 256) (&hb[0][0][0][0])[i] = (__bf16)0.0f;
 
@@ -528,39 +519,17 @@ __global__ __launch_bounds__(512, 2) void gru_fwd_ws(const GruArgs a, const Fold
     if constexpr (XF16) {
       for (float ds = a.drop_scale; ds > 1.0f; ds *= 0.5f) sx *= 0.5f;
 #pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        float wv[NKX][8], m = 0.f;                          // loaded ONCE: the scale needs the fragment's maximum before the split
-#pragma unroll
-        for (int kb = 0; kb < NKX; ++kb) {
-          const float4* wi = (const float4*)(D.Wih + (size_t)(g * 64 + w * 16 + li) * I + kb * 32 + lq * 8);
-          const float4 a0 = wi[0], a1 = wi[1];
-          wv[kb][0] = a0.x; wv[kb][1] = a0.y; wv[kb][2] = a0.z; wv[kb][3] = a0.w; wv[kb][4] = a1.x; wv[kb][5] = a1.y; wv[kb][6] = a1.z; wv[kb][7] = a1.w;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(wv[kb][j]));
-        }
-        const float sw = f16x2_weight_scale(m);
-        posti[g] = 1.0f / (sw * sx);
-#pragma unroll
-        for (int kb = 0; kb < NKX; ++kb)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { _Float16 p0, p1; split2(wv[kb][j], sw, p0, p1); Af[g][kb][0][j] = p0; Af[g][kb][1][j] = p1; }
-      }
+      for (int g = 0; g < 3; ++g) LOAD_FRAG_F16X2(NKX, FRAG_LOAD8_VEC4, D.Wih + (size_t)(g * 64 + w * 16 + li) * I, lq, sx, Af[g], posti[g])
     } else {
 #pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int kb = 0; kb < NKX; ++kb) {
-          const float* wi = D.Wih + (size_t)(g * 64 + w * 16 + li) * I + kb * 32 + lq * 8;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { __bf16 p0, p1, p2; split3(wi[j], p0, p1, p2); Ai[g][kb][0][j] = p0; Ai[g][kb][1][j] = p1; Ai[g][kb][2][j] = p2; }
-        }
+      for (int g = 0; g < 3; ++g) LOAD_FRAG_BF16X3(NKX, D.Wih + (size_t)(g * 64 + w * 16 + li) * I, lq, Ai[g])
     }
     f32x4 b_r, b_z, b_in;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      b_r[e] = D.bih[u0 + e] + D.bhh[u0 + e];
-      b_z[e] = D.bih[64 + u0 + e] + D.bhh[64 + u0 + e];
-      b_in[e] = D.bih[128 + u0 + e];
+      b_r[e] = GRU_BIAS_R(D, u0 + e);
+      b_z[e] = GRU_BIAS_Z(D, u0 + e);
+      b_in[e] = GRU_BIAS_IN(D, u0 + e);
     }
     // x pieces prefetched PD = 3 steps ahead into a ring of register slots (as gru_fwd_b3)
     constexpr int PD = 3;
@@ -677,22 +646,8 @@ __global__ __launch_bounds__(512, 2) void gru_fwd_ws(const GruArgs a, const Fold
   f16x8 Ah[3][2][2];
   float post[3];                                             // 1 / (S_w S_h) of each gate's fragment
 #pragma unroll
-  for (int g = 0; g < 3; ++g) {
-    float wv[2][8], m = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const float* wr = D.Whh + (size_t)(g * 64 + w * 16 + li) * 64 + kb * 32 + lq * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { wv[kb][j] = wr[j]; m = fmaxf(m, fabsf(wv[kb][j])); }
-    }
-    const float sw = f16x2_weight_scale(m);
-    post[g] = 1.0f / (sw * F16X2_H_SCALE);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { _Float16 p0, p1; split2(wv[kb][j], sw, p0, p1); Ah[g][kb][0][j] = p0; Ah[g][kb][1][j] = p1; }
-  }
-  const f32x4 b_hn = {D.bhh[128 + u0], D.bhh[128 + u0 + 1], D.bhh[128 + u0 + 2], D.bhh[128 + u0 + 3]};
+  for (int g = 0; g < 3; ++g) LOAD_FRAG_F16X2(2, FRAG_LOAD8_INDEXED, D.Whh + (size_t)(g * 64 + w * 16 + li) * 64, lq, F16X2_H_SCALE, Ah[g], post[g])
+  const f32x4 b_hn = {GRU_BIAS_HN(D, u0), GRU_BIAS_HN(D, u0 + 1), GRU_BIAS_HN(D, u0 + 2), GRU_BIAS_HN(D, u0 + 3)};
   for (int i = tid; i < 2 * 2 * 16 * HSB; i += 256) (&hb[0][0][0][0])[i] = (_Float16)0.0f;       // tid < 256 here
   const int hrow = tid >> 4, hc4 = (tid & 15) * 4;                         // store role: row hrow, columns hc4 .. hc4+3 of the tile
   float* hptr = D.h + (int64_t)min(tile * 16 + hrow, a.B - 1) * D.h_bs + (int64_t)D.t_start * D.h_ts + D.h_col + hc4;
@@ -771,39 +726,17 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_proj(const GruArgs a, int n_ti
   if constexpr (XF16) {
     for (float ds = a.drop_scale; ds > 1.0f; ds *= 0.5f) sx *= 0.5f;
 #pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      float wv[NKB][8], m = 0.f;                            // loaded ONCE (two 16-byte loads per k block): the scale needs the maximum first
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        const float4* wi = (const float4*)(D.Wih + (size_t)(g * 64 + w * 16 + li) * I + kb * 32 + lq * 8);
-        const float4 a0 = wi[0], a1 = wi[1];
-        wv[kb][0] = a0.x; wv[kb][1] = a0.y; wv[kb][2] = a0.z; wv[kb][3] = a0.w; wv[kb][4] = a1.x; wv[kb][5] = a1.y; wv[kb][6] = a1.z; wv[kb][7] = a1.w;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(wv[kb][j]));
-      }
-      const float sw = f16x2_weight_scale(m);
-      posti[g] = 1.0f / (sw * sx);
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { _Float16 p0, p1; split2(wv[kb][j], sw, p0, p1); Af[g][kb][0][j] = p0; Af[g][kb][1][j] = p1; }
-    }
+    for (int g = 0; g < 3; ++g) LOAD_FRAG_F16X2(NKB, FRAG_LOAD8_VEC4, D.Wih + (size_t)(g * 64 + w * 16 + li) * I, lq, sx, Af[g], posti[g])
   } else {
 #pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        const float* wi = D.Wih + (size_t)(g * 64 + w * 16 + li) * I + kb * 32 + lq * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { __bf16 p0, p1, p2; split3(wi[j], p0, p1, p2); Ai[g][kb][0][j] = p0; Ai[g][kb][1][j] = p1; Ai[g][kb][2][j] = p2; }
-      }
+    for (int g = 0; g < 3; ++g) LOAD_FRAG_BF16X3(NKB, D.Wih + (size_t)(g * 64 + w * 16 + li) * I, lq, Ai[g])
   }
   f32x4 b_r, b_z, b_n;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    b_r[e] = D.bih[u0 + e] + D.bhh[u0 + e];
-    b_z[e] = D.bih[64 + u0 + e] + D.bhh[64 + u0 + e];
-    b_n[e] = D.bih[128 + u0 + e];
+    b_r[e] = GRU_BIAS_R(D, u0 + e);
+    b_z[e] = GRU_BIAS_Z(D, u0 + e);
+    b_n[e] = GRU_BIAS_IN(D, u0 + e);
   }
   const int n_steps = D.n_steps, n_units = n_tiles * n_steps;
   // the x rows of the NEXT unit are loaded while this unit is split and contracted (round 5: a unit's loads used to sit in front of
@@ -905,22 +838,8 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_rec(const GruArgs a, const Fol
   f16x8 Aw[3][2][2];
   float post[3];
 #pragma unroll
-  for (int g = 0; g < 3; ++g) {
-    float wv[2][8], m = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const float* wr = D.Whh + (size_t)(g * 64 + w * 16 + li) * 64 + kb * 32 + lq * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { wv[kb][j] = wr[j]; m = fmaxf(m, fabsf(wv[kb][j])); }
-    }
-    const float sw = f16x2_weight_scale(m);
-    post[g] = 1.0f / (sw * F16X2_H_SCALE);                // a power of two: exact
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { _Float16 p0, p1; split2(wv[kb][j], sw, p0, p1); Aw[g][kb][0][j] = p0; Aw[g][kb][1][j] = p1; }
-  }
-  const f32x4 bhn = {D.bhh[128 + u0], D.bhh[128 + u0 + 1], D.bhh[128 + u0 + 2], D.bhh[128 + u0 + 3]};
+  for (int g = 0; g < 3; ++g) LOAD_FRAG_F16X2(2, FRAG_LOAD8_INDEXED, D.Whh + (size_t)(g * 64 + w * 16 + li) * 64, lq, F16X2_H_SCALE, Aw[g], post[g])
+  const f32x4 bhn = {GRU_BIAS_HN(D, u0), GRU_BIAS_HN(D, u0 + 1), GRU_BIAS_HN(D, u0 + 2), GRU_BIAS_HN(D, u0 + 3)};
   for (int i = tid; i < 2 * 2 * 16 * HSB; i += 256) (&hb[0][0][0][0])[i] = (_Float16)0.0f;
   __syncthreads();
 
@@ -1020,8 +939,8 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_rec(const GruArgs a, const Fol
   step(std::true_type{}, 0, g[0]);
   int s = 1;                                               // s = 1 (mod PD) at the top of every round: step s + i uses set (1 + i) % PD
   for (; s + PD <= n_steps; s += PD)
-    sfor_n<PD>([&](auto i) { step(std::false_type{}, s + decltype(i)::value, g[(1 + decltype(i)::value) % PD]); });
-  sfor_n<PD - 1>([&](auto i) { if (s + decltype(i)::value < n_steps) step(std::false_type{}, s + decltype(i)::value, g[(1 + decltype(i)::value) % PD]); });
+    sfor<PD>([&](auto i) { step(std::false_type{}, s + decltype(i)::value, g[(1 + decltype(i)::value) % PD]); });
+  sfor<PD - 1>([&](auto i) { if (s + decltype(i)::value < n_steps) step(std::false_type{}, s + decltype(i)::value, g[(1 + decltype(i)::value) % PD]); });
   flush();
 #ifdef MSIG_STAMPS
   if (a.dbg && tid == 0 && blockIdx.y == 0 && blockIdx.x < 256)
@@ -1032,14 +951,7 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_rec(const GruArgs a, const Fol
 }
 
 // ------------------------------------------------------------------------------------
-// Backward recurrence (BPTT) of the latency form: gru_bwd_seq4 (gru_bwd4.hip, ROLE 3) — consumes the stash written by the
-// forward kernels and replaces it with the pre-activation gradients (dr, dz, dn, dhn) that the bulk kernels below contract.
-// Round 2's fp32-MFMA gru_bwd_seq (48 v_mfma_f32_16x16x4_f32 per wave-step, 1.23 us per step) is gone: the split-bf16 recurrence
-// with the dh-independent gate math in its MFMA gaps and LDS-DMA operand prefetch takes 0.99 us (profiles/r03_bench_B64_kernels.log).
-// ------------------------------------------------------------------------------------
-// Bulk: dx[b][t][:] = W_ih^T dgi[b][t][:]   (dgi = dr,dz,dn of the stash)
-// ------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------
+// (The backward recurrence of the latency form, gru_bwd_seq4, is gru_bwd4.hip's ROLE 3; its bulk dX / dW kernels are further down.)
 // Fused backward — BPTT recurrence dh_{t-1} = dh_t z + W_hh^T dgh_t, dX = W_ih^T dgi and dW_ih / dW_hh / db in ONE kernel per
 // layer — with EVERY contraction on split-bf16 MFMA (gru_bwd_b3): the throughput form above 192 batch tiles.  One workgroup owns
 // a 16-row tile for all its steps and then moves on to its next tile with the dW accumulators still in registers (one partial
@@ -1062,8 +974,6 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_rec(const GruArgs a, const Fol
 //            dW_hh 72, dW_ih 36 bf16 MFMAs;   layer 1: recurrence 2 x 36, dX 2 x 72, dW_hh 72, dW_ih 144.
 // Plane columns: [dr | dz | dhn | dn] (cols 0..191 = the rows of W_hh) and [x (I) | h_prev (64)].
 // ------------------------------------------------------------------------------------
-#define PIN_ACC(v) asm volatile("" : "+a"(v))
-
 template <int I, bool FOLDS>
 __global__ __launch_bounds__(256, 1) void gru_bwd_b3(const GruArgs a, int n_tiles, const FoldCtx fc) {
   using G = BwdB3<I>;
@@ -1084,13 +994,11 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_b3(const GruArgs a, int n_tile
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       __bf16 p0, p1, p2;
-      split3(D.Whh[(size_t)(kb * 32 + lq * 8 + j) * 64 + w * 16 + li], p0, p1, p2);
-      AhB[kb][0][j] = p0; AhB[kb][1][j] = p1; AhB[kb][2][j] = p2;
+      FRAG_T_ELEM(AhB, D.Whh, 64, w, kb, j, true)
 #pragma unroll
       for (int kk = 0; kk < NDX; ++kk) {
         const int cb = L1K ? (2 * w + kk) : (w & 1);
-        split3(D.Wih[(size_t)(kb * 32 + lq * 8 + j) * I + cb * 16 + li], p0, p1, p2);
-        AiB[kk][kb][0][j] = p0; AiB[kk][kb][1][j] = p1; AiB[kk][kb][2][j] = p2;
+        FRAG_T_ELEM(AiB[kk], D.Wih, I, cb, kb, j, true)
       }
     }
   // The resident operands are only ever read by MFMAs, which take A / B from either half of the unified register file; left to
@@ -1618,8 +1526,7 @@ __device__ __forceinline__ void dx2_role(const GruArgs& a, const GruDir& D, cons
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           __bf16 p0, p1, p2;
-          split3(active ? Wih[(size_t)(kb * 32 + lq * 8 + j) * I + (w * KBW + kk) * 16 + li] : 0.f, p0, p1, p2);
-          At[kk][kb][0][j] = p0; At[kk][kb][1][j] = p1; At[kk][kb][2][j] = p2;
+          FRAG_T_ELEM(At[kk], Wih, I, (w * KBW + kk), kb, j, active)
         }
   };
   auto fetch = [&](const GruDir& G, int unit, float4 (&g)[3]) {     // dr, dz, dn of (row li, units w*16 + lq*4 ..): only ISSUES the loads
@@ -1847,11 +1754,10 @@ static int bulk_grid(int units, int cap_single, int n_folds, int n_dirs) {
   }
   return units < cap ? (units < 1 ? 1 : units) : cap;
 }
-#define MSIG_WS_LAYER0 1     // wave-specialised forward for layer 0 as well (0: gru_fwd_b3<32>)
 // Kernel forms: per call (msig_batch.fwd_form / bwd_form, 0 = default).  The default is by batch size unless MSIG_GRU_FWD /
 // MSIG_GRU_BWD name another one: read ONCE, at the first launch (concurrent fold threads launch while tests used to mutate the
-// environment: getenv per launch was a data race), immutable afterwards.  There is no mutable process-global form any more
-// (round 3's msig_set_kernel_form): two host threads may drive different models with different forms.
+// environment: getenv per launch was a data race), immutable afterwards.  There is no mutable process-global form: two host
+// threads may drive different models with different forms.
 #define MSIG_L1_WS_TILES_DEFAULT 32
 static int g_env_fwd_form = MSIG_FORM_AUTO, g_env_bwd_form = MSIG_FORM_AUTO, g_l1_ws_tiles = -1;
 static std::once_flag g_form_env_once;
@@ -1902,19 +1808,6 @@ static int fwd_form(const msig_batch* b, int n_tiles) {
   return f != MSIG_FORM_AUTO ? f : FWD_MIXED;
 }
 
-#ifdef MSIG_STAMPS
-static void report_fwd_stamps(const char* tag, unsigned long long* dbg_dev, int nwg, int steps, hipStream_t st) {
-  (void)hipStreamSynchronize(st);
-  unsigned long long h[8 * 256];
-  if (nwg > 256) nwg = 256;
-  (void)hipMemcpy(h, dbg_dev, sizeof(unsigned long long) * 8 * nwg, hipMemcpyDeviceToHost);
-  double acc[8] = {0};
-  for (int i = 0; i < nwg; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[i * 8 + j] / nwg;
-  fprintf(stderr, "[stamps %s fwd, cycles per step] ph0 %.0f | ph1 %.0f | ph2 %.0f | ph3 %.0f | ph4 %.0f | ph5 %.0f | ph6 %.0f  (seq: loop/init, x-MFMA, x prefetch, barrier, h-part, gates, stores; rec: acc init, barrier, reads+stores+MFMA, gates+ldsW)\n",
-          tag, acc[0] / steps, acc[1] / steps, acc[2] / steps, acc[3] / steps, acc[4] / steps, acc[5] / steps, acc[6] / steps);
-}
-#endif
-
 // > 64 KiB of dynamic LDS needs an opt-in attribute per kernel and per DEVICE (a process may drive several): set once per device.
 static int ensure_lds_optin() {
   static std::mutex mu;
@@ -1942,33 +1835,77 @@ static int ensure_lds_optin() {
 }
 
 static int bwd_form(const msig_batch* b, int n_tiles, int n_folds);
-// Every form-related rejection of a call, BEFORE its first launch (api.hip forward_fc / train_step_fc): a fold batch runs the
-// latency form and gru_fwd_ws only.  (Round 4 returned MSIG_E_FORM from launch_gru_fwd, after the front end of a training-mode
-// call had already updated the BatchNorm running statistics.)
+// A fold batch (even of one fold: its arena need not be the first) runs the latency form and gru_fwd_ws only.
+static bool fold_batch_runs(int form) { return form == MSIG_FWD_LATENCY || form == MSIG_FWD_WS || form == FWD_MIXED; }
+// Every form-related rejection of a call, BEFORE its first launch (api.hip forward_fc / train_step_fc).  (Round 4 returned
+// MSIG_E_FORM from launch_gru_fwd, after the front end of a training-mode call had already updated the BatchNorm running statistics.)
 int msig_check_call_forms(const msig_batch* b, int n_tiles, const FoldCtx& fc) {
   const int rc = msig_check_forms(b);
   if (rc) return rc;
-  const int form = fwd_form(b, n_tiles);
-  if (fc.stride != 0 && form != MSIG_FWD_LATENCY && form != MSIG_FWD_WS && form != FWD_MIXED) return MSIG_E_FORM;
+  if (fc.stride != 0 && !fold_batch_runs(fwd_form(b, n_tiles))) return MSIG_E_FORM;
   return 0;
 }
+
+// The forward launch of one layer (I = 32: layer 0, I = 128: layer 1) in one of its four forms.  keeps / folds become the kernels'
+// STASH / FOLDS template arguments (with_flag, gru_args.h).
+enum FwdRung { RUNG_LATENCY, RUNG_FP32, RUNG_WS, RUNG_B3 };
+template <int I>
+static int launch_fwd_layer(FwdRung rung, bool keeps, bool folds, GruArgs& a, const StageDims& d, const WsPtrs& w, const FoldCtx& fc, hipStream_t st) {
+  constexpr bool L0 = I == 32;
+  const dim3 grid(d.NT, 2), fgrid(d.NT, 2, fc.n);
+  if (rung == RUNG_LATENCY) {
+    // few batch tiles: bulk projection over all CUs, then the lean recurrence.  The single reverse step of the
+    // top layer is direction 1 of the same two launches (one unit per tile in the projection, a one-step
+    // recurrence), not a third launch: at this batch size a step is bound by its number of launches.
+    a.gi = w.p<float4>(MSIG_WS_GI);
+    a.gi_dir_stride = (size_t)d.NT * d.TP * 4 * 3 * 64;
+    const int units = d.NT * d.TP;
+    { MSIG_K(L0 ? "gru_fwd_proj_l0" : "gru_fwd_proj_l1", st); gru_fwd_proj<I><<<dim3(bulk_grid(units, 256, fc.n, 2), 2, fc.n), 256, 0, st>>>(a, d.NT, fc); }
+    MSIG_LAUNCH_CHECK();
+    MSIG_K(L0 ? "gru_fwd_rec_l0" : "gru_fwd_rec_l1", st);
+    with_flag(keeps, [&](auto K) { gru_fwd_rec<decltype(K)::value><<<fgrid, 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc); });
+  } else if (rung == RUNG_FP32) {
+    MSIG_K(L0 ? "gru_fwd_seq_l0" : "gru_fwd_seq_l1", st);
+    with_flag(keeps, [&](auto K) { gru_fwd_seq<I, decltype(K)::value><<<grid, 256, 0, st>>>(a); });
+  } else if (rung == RUNG_WS) {
+    MSIG_K(L0 ? "gru_fwd_ws_l0" : "gru_fwd_ws_l1", st);
+    with_flag(keeps, [&](auto K) {
+      with_flag(folds, [&](auto F) { gru_fwd_ws<I, decltype(K)::value, decltype(F)::value><<<decltype(F)::value ? fgrid : grid, 512, 0, st>>>(a, fc); });
+    });
+  } else {
+    MSIG_K(L0 ? "gru_fwd_b3_l0" : "gru_fwd_b3_l1", st);
+    with_flag(keeps, [&](auto K) { gru_fwd_b3<I, decltype(K)::value><<<grid, 256, 0, st>>>(a); });
+  }
+  MSIG_LAUNCH_CHECK();
+  return 0;
+}
+
+#ifdef MSIG_STAMPS
+static void report_fwd_stamps(int layer, const unsigned long long* dbg, const StageDims& d, hipStream_t st) {
+  stamps_report(st, dbg, d.NT < 256 ? d.NT : 256, d.TP, {{0, "ph0"}, {1, "ph1"}, {2, "ph2"}, {3, "ph3"}, {4, "ph4"}, {5, "ph5"}, {6, "ph6"}},
+                "  (seq: loop/init, x-MFMA, x prefetch, barrier, h-part, gates, stores; rec: acc init, barrier, reads+stores+MFMA, gates+ldsW)",
+                "L%d fwd, cycles per step", layer);
+}
+#endif
+
 int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, const int64_t* po, const FoldCtx& fc, hipStream_t st,
                    int part, bool force_drop) {
   GruArgs a;
-  { const int rc = msig_check_forms(b); if (rc) return rc; }
-  const int form = fwd_form(b, d.NT);
-  const bool fp32 = form == MSIG_FWD_FP32;
-  const bool folds = fc.stride != 0;                 // a fold batch (even of one fold: its arena need not be the first)
-  if (folds && form != MSIG_FWD_LATENCY && form != MSIG_FWD_WS && form != FWD_MIXED) return MSIG_E_FORM;   // fold batching: latency form and gru_fwd_ws only
-  const int launch_tiles = d.NT * (fc.n > 0 ? fc.n : 1);
-  const bool ws0 = form == MSIG_FWD_WS || form == FWD_MIXED;
-  const bool ws1 = form == MSIG_FWD_WS || (form == FWD_MIXED && launch_tiles >= g_l1_ws_tiles);
-  bool latency = form == MSIG_FWD_LATENCY;           // layer 0 here, layer 1 below
-  { const int rc = ensure_lds_optin(); if (rc) return rc; }
 #ifdef MSIG_STAMPS
   static unsigned long long* dbg_dev = nullptr;
   if (!dbg_dev) (void)hipMalloc(&dbg_dev, 256 * 8 * sizeof(unsigned long long));
 #endif
+  { const int rc = msig_check_forms(b); if (rc) return rc; }
+  const int form = fwd_form(b, d.NT);
+  const bool folds = fc.stride != 0;
+  if (folds && !fold_batch_runs(form)) return MSIG_E_FORM;
+  const bool keeps = msig_keeps(b);
+  // the automatic choice below MSIG_LATENCY_TILES: gru_fwd_ws for layer 0; for layer 1 from g_l1_ws_tiles tiles per launch on
+  const int launch_tiles = d.NT * (fc.n > 0 ? fc.n : 1);
+  const FwdRung fixed = form == MSIG_FWD_LATENCY ? RUNG_LATENCY : (form == MSIG_FWD_FP32 ? RUNG_FP32 : (form == MSIG_FWD_WS ? RUNG_WS : RUNG_B3));
+  const FwdRung rung0 = form == FWD_MIXED ? RUNG_WS : fixed;
+  const FwdRung rung1 = form == FWD_MIXED ? (launch_tiles >= g_l1_ws_tiles ? RUNG_WS : RUNG_LATENCY) : fixed;
+  { const int rc = ensure_lds_optin(); if (rc) return rc; }
   setup_layer0(a, b, d, w, po);
   // gru_bwd_b6 recomputes W_hn h + b_hn: gru_fwd_ws then stores two stash vectors per step instead of three — but only inside a
   // fused train-step call (fc.fused_step), where THIS descriptor also resolves the backward form.  As separate calls
@@ -1978,37 +1915,13 @@ int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
 #ifdef MSIG_STAMPS
   a.dbg = dbg_dev;
 #endif
-  if (part == GRU_PART_L1) {
-    if (b->gru_layers == 1) return 0;            // the one-layer model has no layer above the dropout site
-  } else if (latency) {
-    a.gi = w.p<float4>(MSIG_WS_GI);
-    a.gi_dir_stride = (size_t)d.NT * d.TP * 4 * 3 * 64;
-    const int units = d.NT * d.TP;
-    { MSIG_K("gru_fwd_proj_l0", st); gru_fwd_proj<32><<<dim3(bulk_grid(units, 256, fc.n, 2), 2, fc.n), 256, 0, st>>>(a, d.NT, fc); }
-    MSIG_LAUNCH_CHECK();
-    MSIG_K("gru_fwd_rec_l0", st);
-    if (msig_keeps(b)) gru_fwd_rec<true><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
-    else gru_fwd_rec<false><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
-  } else if (fp32) {
-    MSIG_K("gru_fwd_seq_l0", st);
-    if (msig_keeps(b)) gru_fwd_seq<32, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-    else gru_fwd_seq<32, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-  } else if (ws0 && folds) {
-    MSIG_K("gru_fwd_ws_l0", st);
-    if (msig_keeps(b)) gru_fwd_ws<32, true, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
-    else gru_fwd_ws<32, false, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
-  } else if (ws0 && MSIG_WS_LAYER0) {
-    MSIG_K("gru_fwd_ws_l0", st);
-    if (msig_keeps(b)) gru_fwd_ws<32, true, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
-    else gru_fwd_ws<32, false, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
-  } else {
-    MSIG_K("gru_fwd_b3_l0", st);
-    if (msig_keeps(b)) gru_fwd_b3<32, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-    else gru_fwd_b3<32, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
+  if (b->gru_layers == 1 && part == GRU_PART_L1) return 0;      // the one-layer model has no layer above the dropout site
+  if (part != GRU_PART_L1) {
+    const int rc = launch_fwd_layer<32>(rung0, keeps, folds, a, d, w, fc, st);
+    if (rc) return rc;
   }
-  MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
-  report_fwd_stamps("L0", dbg_dev, d.NT, d.TP, st);
+  report_fwd_stamps(0, dbg_dev, d, st);
 #endif
   if (b->gru_layers == 1) {            // one-layer model: outputs[:, -1, :] = layer 0 at the last position
     MSIG_K("feat_from_h0", st);
@@ -2021,41 +1934,9 @@ int launch_gru_fwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
 #ifdef MSIG_STAMPS
   a.dbg = dbg_dev;
 #endif
-  latency = form == MSIG_FWD_LATENCY || (form == FWD_MIXED && !ws1);
-  if (latency) {
-    // few batch tiles: bulk projection over all CUs, then the lean recurrence.  The single reverse step of the
-    // top layer is direction 1 of the same two launches (one unit per tile in the projection, a one-step
-    // recurrence), not a third launch: at this batch size a step is bound by its number of launches.
-    a.gi = w.p<float4>(MSIG_WS_GI);
-    a.gi_dir_stride = (size_t)d.NT * d.TP * 4 * 3 * 64;
-    const int units = d.NT * d.TP;
-    { MSIG_K("gru_fwd_proj_l1", st); gru_fwd_proj<128><<<dim3(bulk_grid(units, 256, fc.n, 2), 2, fc.n), 256, 0, st>>>(a, d.NT, fc); }
-    MSIG_LAUNCH_CHECK();
-    {
-      MSIG_K("gru_fwd_rec_l1", st);
-      if (msig_keeps(b)) gru_fwd_rec<true><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
-      else gru_fwd_rec<false><<<dim3(d.NT, 2, fc.n), 256, exclusive_cu_lds(d.NT * 2 * fc.n), st>>>(a, fc);
-    }
-  } else if (fp32) {
-    MSIG_K("gru_fwd_seq_l1", st);
-    if (msig_keeps(b)) gru_fwd_seq<128, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-    else gru_fwd_seq<128, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-  } else if (ws1 && folds) {
-    MSIG_K("gru_fwd_ws_l1", st);
-    if (msig_keeps(b)) gru_fwd_ws<128, true, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
-    else gru_fwd_ws<128, false, true><<<dim3(d.NT, 2, fc.n), 512, 0, st>>>(a, fc);
-  } else if (ws1) {
-    MSIG_K("gru_fwd_ws_l1", st);
-    if (msig_keeps(b)) gru_fwd_ws<128, true, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
-    else gru_fwd_ws<128, false, false><<<dim3(d.NT, 2), 512, 0, st>>>(a, fc);
-  } else {
-    MSIG_K("gru_fwd_b3_l1", st);
-    if (msig_keeps(b)) gru_fwd_b3<128, true><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-    else gru_fwd_b3<128, false><<<dim3(d.NT, 2), 256, 0, st>>>(a);
-  }
-  MSIG_LAUNCH_CHECK();
+  { const int rc = launch_fwd_layer<128>(rung1, keeps, folds, a, d, w, fc, st); if (rc) return rc; }
 #ifdef MSIG_STAMPS
-  report_fwd_stamps("L1", dbg_dev, d.NT, d.TP, st);
+  report_fwd_stamps(1, dbg_dev, d, st);
 #endif
   return 0;
 }
@@ -2074,7 +1955,7 @@ static int reduce_dw(const GruDir& g, int nwg, float* grads, const int64_t* po, 
 // Fused vs split backward.  The fused kernel (gru_bwd_b3) owns a batch tile for all steps with 108 (216) bf16 MFMAs per step on
 // its critical path: best when every CU has a tile (B >= ~3000).  With few tiles (the reference's B = 64 is 4) the recurrence
 // latency is everything, so the split form wins: a 36-MFMA-per-step recurrence (gru_bwd_seq4) and bulk dX / dW kernels that
-// spread over the otherwise idle CUs.  MSIG_GRU_BWD=b3|split / msig_set_kernel_form override.  MSIG_BWD_FUSED (round 1's
+// spread over the otherwise idle CUs.  MSIG_GRU_BWD=b3|split / msig_batch.bwd_form override.  MSIG_BWD_FUSED (round 1's
 // fp32-dW kernel, removed) is accepted as an alias of MSIG_BWD_B3.
 enum { BWD_SPLIT = MSIG_BWD_SPLIT, BWD_B3 = MSIG_BWD_B3, BWD_B4 = MSIG_BWD_B4, BWD_B5 = MSIG_BWD_B5, BWD_B6 = MSIG_BWD_B6 };
 #ifndef MSIG_BWD_DEFAULT_FUSED
@@ -2169,20 +2050,11 @@ int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
         if (rc4) return rc4;
       } else {
         MSIG_K("gru_bwd_b3_l1", st);
-        if (folds) gru_bwd_b3<128, true><<<dim3(nwg, 1, fc.n), 256, BwdB3<128>::SMEM, st>>>(one, d.NT, fc);
-        else gru_bwd_b3<128, false><<<dim3(nwg, 1), 256, BwdB3<128>::SMEM, st>>>(one, d.NT, fc);
+        with_flag(folds, [&](auto F) { gru_bwd_b3<128, decltype(F)::value><<<dim3(nwg, 1, folds ? fc.n : 1), 256, BwdB3<128>::SMEM, st>>>(one, d.NT, fc); });
       }
       MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
-      {
-        (void)hipStreamSynchronize(st);
-        unsigned long long h[8 * 256];
-        (void)hipMemcpy(h, dbg_dev, sizeof(unsigned long long) * 8 * nwg, hipMemcpyDeviceToHost);
-        double acc[8] = {0};
-        for (int i = 0; i < nwg; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[i * 8 + j] / nwg;
-        fprintf(stderr, "[stamps L1, cycles per tile (first tile of each WG), %d steps] top %.0f | dhMFMA %.0f | gates+ldsW %.0f | issue loads %.0f | dx %.0f | dW %.0f | barrier %.0f | vmcnt wait %.0f\n",
-                d.TP, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7]);
-      }
+      stamps_report(st, dbg_dev, nwg, 1, B3_STAMP_COLS, "", "L1, cycles per tile (first tile of each WG), %d steps", d.TP);
 #endif
     } else {
       {
@@ -2232,20 +2104,11 @@ int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
       if (rc) return rc;
     } else {
       MSIG_K("gru_bwd_b3_l0", st);
-      if (folds) gru_bwd_b3<32, true><<<dim3(nwg0, 2, fc.n), 256, BwdB3<32>::SMEM, st>>>(a, d.NT, fc);
-      else gru_bwd_b3<32, false><<<dim3(nwg0, 2), 256, BwdB3<32>::SMEM, st>>>(a, d.NT, fc);
+      with_flag(folds, [&](auto F) { gru_bwd_b3<32, decltype(F)::value><<<dim3(nwg0, 2, folds ? fc.n : 1), 256, BwdB3<32>::SMEM, st>>>(a, d.NT, fc); });
     }
     MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
-    {
-      (void)hipStreamSynchronize(st);
-      unsigned long long h[8 * 256];
-      (void)hipMemcpy(h, dbg_dev, sizeof(unsigned long long) * 8 * 2 * nwg0, hipMemcpyDeviceToHost);
-      double acc[8] = {0};
-      for (int i = 0; i < 2 * nwg0; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[i * 8 + j] / (2 * nwg0);
-      fprintf(stderr, "[stamps L0, cycles per tile, %d steps] top %.0f | dhMFMA %.0f | gates+ldsW %.0f | issue loads %.0f | dx %.0f | dW %.0f | barrier %.0f | vmcnt wait %.0f\n",
-              d.TP, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7]);
-    }
+    stamps_report(st, dbg_dev, 2 * nwg0, 1, B3_STAMP_COLS, "", "L0, cycles per tile, %d steps", d.TP);
 #endif
   } else {
 #ifdef MSIG_STAMPS
@@ -2258,16 +2121,8 @@ int launch_gru_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w, con
     }
     MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
-    {
-      (void)hipStreamSynchronize(st);
-      unsigned long long h[8 * 256];
-      const int nw = d.NT < 256 ? d.NT : 256;
-      (void)hipMemcpy(h, dbg_dev, sizeof(unsigned long long) * 8 * nw, hipMemcpyDeviceToHost);
-      double acc[8] = {0};
-      for (int i = 0; i < nw; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[i * 8 + j] / nw;
-      fprintf(stderr, "[stamps L0 bwd_seq, cycles per step] loop %.0f | loads+gates+stores %.0f | ldsW %.0f | barrier %.0f | MFMA+carry %.0f\n",
-              acc[0] / d.TP, acc[1] / d.TP, acc[2] / d.TP, acc[3] / d.TP, acc[4] / d.TP);
-    }
+    stamps_report(st, dbg_dev, d.NT < 256 ? d.NT : 256, d.TP,
+                  {{0, "loop"}, {1, "loads+gates+stores"}, {2, "ldsW"}, {3, "barrier"}, {4, "MFMA+carry"}}, "", "L0 bwd_seq, cycles per step");
 #endif
     a.drop_thr = 0; a.drop_scale = 1.f;   // layer-0 input (P2) has no dropout (masks are branch-free: thr 0 == keep all, scale 1)
     const int units0 = d.NT * d.TP;

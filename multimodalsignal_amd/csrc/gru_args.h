@@ -1,4 +1,5 @@
-// Declarations shared by the GRU kernel files (gru.hip, gru_bwd4.hip): argument blocks, fold-batching macros, diagnostic stamps.
+// Declarations shared by the GRU kernel files (gru.hip, gru_bwd4.hip, gru_bwd6.hip): argument blocks, fold-batching macros, the static
+// for, diagnostic stamps and their report.
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +14,9 @@
 
 // In-kernel phase stamps: compiled only into the diagnostic library (make stamps); never in the product .so.
 #ifdef MSIG_STAMPS
+#include <stdarg.h>
+#include <initializer_list>
+#include <vector>
 #define STAMP_DECL unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev_ = stamp_now()
 #define STAMP(i) do { const unsigned long long tn_ = stamp_now(); ph_[i] += tn_ - tprev_; tprev_ = tn_; } while (0)
 __device__ __forceinline__ unsigned long long stamp_now() {
@@ -22,14 +26,47 @@ __device__ __forceinline__ unsigned long long stamp_now() {
   __builtin_amdgcn_sched_barrier(0);
   return t;
 }
+// Host side: wait for the stream, read back n_rows rows of eight phase counters (one row per stamping workgroup), average every
+// phase over the rows, divide by `divisor` (the step count, or 1) and print ONE line,
+//   [stamps <tag>] <label> <cycles> | <label> <cycles> ...<tail>
+// cols picks the phases and names them; the tag is printf-formatted from the trailing arguments.
+struct StampCol { int ph; const char* label; };
+__attribute__((format(printf, 7, 8)))
+static void stamps_report(hipStream_t st, const unsigned long long* dbg, int n_rows, double divisor, std::initializer_list<StampCol> cols,
+                          const char* tail, const char* tag_fmt, ...) {
+  (void)hipStreamSynchronize(st);
+  std::vector<unsigned long long> h((size_t)8 * n_rows);
+  (void)hipMemcpy(h.data(), dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
+  double acc[8] = {0};
+  for (int i = 0; i < n_rows; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[(size_t)i * 8 + j] / n_rows;
+  char line[1024];
+  int n = snprintf(line, sizeof line, "[stamps ");
+  va_list ap;
+  va_start(ap, tag_fmt);
+  n += vsnprintf(line + n, sizeof line - n, tag_fmt, ap);
+  va_end(ap);
+  n += snprintf(line + n, sizeof line - n, "]");
+  const char* sep = " ";
+  for (const StampCol& c : cols) { n += snprintf(line + n, sizeof line - n, "%s%s %.0f", sep, c.label, acc[c.ph] / divisor); sep = " | "; }
+  fprintf(stderr, "%s%s\n", line, tail);
+}
+// what the eight counters hold: gru_bwd_b3 (per tile); a chain wave (recurrence + gate math) and a bulk wave (dX / dW) of the
+// pipelined kernels, whose second column is named by the kernel
+#define B3_STAMP_COLS {{0, "top"}, {1, "dhMFMA"}, {2, "gates+ldsW"}, {3, "issue loads"}, {4, "dx"}, {5, "dW"}, {6, "barrier"}, {7, "vmcnt wait"}}
+#define CHAIN_STAMP_COLS(reads) {{0, "loop top"}, {1, reads}, {2, "recurrence"}, {3, "dependent gate math + stores"}, {5, "barrier"}}
+#define BULK_STAMP_COLS(reads) {{0, "loop top"}, {3, reads}, {4, "dW"}, {5, "barrier"}}
 #else
 #define STAMP_DECL
 #define STAMP(i)
 #endif
 
-// compile-time unrolled loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
-template <typename F, int... Is> __device__ __forceinline__ void sfor_n_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, typename F> __device__ __forceinline__ void sfor_n(F&& f) { sfor_n_impl(f, std::make_integer_sequence<int, N>{}); }
+// compile-time unrolled loop: f(ic<0>{}) ... f(ic<N - 1>{})
+template <int N> using ic = std::integral_constant<int, N>;
+template <typename F, int... Is> __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) { (f(ic<Is>{}), ...); }
+template <int N, typename F> __device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F> static void with_flag(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
 
 struct GruDir {
   const float *Wih, *Whh, *bih, *bhh;

@@ -22,6 +22,7 @@
 // four rows a transposed 32-lane access touches fall into disjoint 16-bank windows) and 8-element chunks are XORed with
 // g(row >> 2), g = [0,3,2,1] (row reads by ds_read_b128 and the producers' ds_write_b64 are conflict-free as well).
 #include "gru_args.h"
+#include "gru_frag.h"
 #include "gru_bwd4.h"
 
 #include "gru_bwd_pipe.h"
@@ -69,15 +70,13 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
     for (int j = 0; j < 8; ++j) {
       __bf16 p0, p1, p2;
       if constexpr (!BK8) {
-        split3(D.Whh[(size_t)(kb * 32 + lq * 8 + j) * 64 + w * 16 + li], p0, p1, p2);
-        AhB[kb][0][j] = p0; AhB[kb][1][j] = p1; AhB[kb][2][j] = p2;
+        FRAG_T_ELEM(AhB, D.Whh, 64, w, kb, j, true)
       }
       if constexpr (HAS_DX) {
 #pragma unroll
         for (int kk = 0; kk < NDX; ++kk) {
           const int cb = L1K ? (2 * w + kk) : w;
-          split3(D.Wih[(size_t)(kb * 32 + lq * 8 + j) * I + cb * 16 + li], p0, p1, p2);
-          AiB[kk][kb][0][j] = p0; AiB[kk][kb][1][j] = p1; AiB[kk][kb][2][j] = p2;
+          FRAG_T_ELEM(AiB[kk], D.Wih, I, cb, kb, j, true)
         }
       }
     }
@@ -95,14 +94,10 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
   //   A block = 32 consecutive columns of the gate-gradient planes [dr|dz|dhn|dn], B block = 32 columns of [x | h_prev]
   int aoff[NTA], boff[NTA];
   aoff[0] = boff[0] = 0;
-  if constexpr (ROLE == 0 || ROLE == 5) {    // 32 n-gate units: dW_ih <- dn . x, dW_hh <- dhn . h_prev
-    aoff[0] = 192 + 32 * w; boff[0] = 0;
-    aoff[1] = 128 + 32 * w; boff[1] = 32;
-    aoff[2] = 128 + 32 * w; boff[2] = 64;
-  } else if constexpr (ROLE == 1 || ROLE == 6) {   // wave 2: the r gate, wave 3: the z gate; units lo / hi x columns x, h lo, h hi
-    const int gc = (w - 2) * 64;
-#pragma unroll
-    for (int t = 0; t < 6; ++t) { aoff[t] = gc + 32 * (t / 3); boff[t] = 32 * (t % 3); }
+  if constexpr (ROLE == 0 || ROLE == 5) {
+    DW_TILES_N(w, aoff, boff)
+  } else if constexpr (ROLE == 1 || ROLE == 6) {
+    DW_TILES_RZ(w, aoff, boff)
   } else if constexpr (ROLE == 2) {          // layer 1: one full 32-column block (6 unit blocks) + half of another (3 unit blocks)
     const int cF = w == 0 ? 0 : (w == 1 ? 64 : (w == 2 ? 96 : 160));
     const int cH = w < 2 ? 32 : 128;
@@ -471,10 +466,10 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
         constexpr int n = decltype(nc)::value;
         if constexpr (n < 18) {
           constexpr int blk = n / 6, pp = (n % 6) / 2, h = n % 2;
-          put_half<h>(Bf[blk][pp], lds_tr_read4(ring + cur + tr_xh[h] + 32 * blk + pp * XHP));
+          put_half<h>(Bf[blk][pp], lds_tr_read(ring + cur + tr_xh[h] + 32 * blk + pp * XHP));
         } else if constexpr (n < 30) {
           constexpr int m = n - 18, blk = m / 6, pp = (m % 6) / 2, h = m % 2;
-          put_half<h>(Af[blk][pp], lds_tr_read4(ring + cur + tr_dg[h] + aoff[R4 == 1 ? 3 * blk : blk] + pp * DGP));
+          put_half<h>(Af[blk][pp], lds_tr_read(ring + cur + tr_dg[h] + aoff[R4 == 1 ? 3 * blk : blk] + pp * DGP));
         }
       };
       constexpr int PRE = 16, NR1 = (FULL && !BK8) ? PRE + 72 : 0;        // Q1 operations consumed by the recurrence phase
@@ -614,10 +609,10 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
             constexpr int n = s - 40;
             if constexpr (n < 12) {
               constexpr int blk = n / 6, pp = (n % 6) / 2, h = n % 2;
-              put_half<h>(Bf[blk][pp], lds_tr_read4(ring + cur + tr_xh[h] + boff[blk == 0 ? 0 : 6] + pp * XHP));
+              put_half<h>(Bf[blk][pp], lds_tr_read(ring + cur + tr_xh[h] + boff[blk == 0 ? 0 : 6] + pp * XHP));
             } else {
               constexpr int m = n - 12, pp = m / 2, h = m % 2;
-              put_half<h>(Af[0][pp], lds_tr_read4(ring + cur + tr_dg[h] + aoff[0] + pp * DGP));
+              put_half<h>(Af[0][pp], lds_tr_read(ring + cur + tr_dg[h] + aoff[0] + pp * DGP));
             }
           }
           if constexpr (!USE_DMA && FULL && s < 4) reg_piece(L, s, s_ld);     // r, z, hn, h_prev of step j+2: the coefficients of step j+1 are done
@@ -638,7 +633,7 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
         FENCE();
         if constexpr (ROLE == 2 && tI + 1 < NT) {        // the A block of the next tile, one transposed read per slot, other register set
           constexpr int pp = t / 2, h = t % 2;
-          put_half<h>(Af[(tI + 1) & 1][pp], lds_tr_read4(ring + cur + tr_dg[h] + aoff[tI + 1] + pp * DGP));
+          put_half<h>(Af[(tI + 1) & 1][pp], lds_tr_read(ring + cur + tr_dg[h] + aoff[tI + 1] + pp * DGP));
         }
         if constexpr (HAS_DX && s == 1) {
           if (valid) {
@@ -802,14 +797,8 @@ int launch_gru_bwd_seq4(int dh_mode, const GruArgs& a, int n_tiles, int ndir, co
   else gru_bwd_seq4<128><<<grid, 256, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc);
   MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
-  if (a.dbg && a.dir[0].n_steps > 1) {
-    (void)hipStreamSynchronize(st);
-    static unsigned long long h[8];
-    (void)hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost);          // workgroup 0, direction 0, waves 0,1
-    const double steps = a.dir[0].n_steps;
-    fprintf(stderr, "[stamps seq4 dh_mode %d, cycles per step] loop top %.0f | wait + staged reads + 16 ops %.0f | recurrence %.0f | dependent gate math + stores %.0f | barrier %.0f\n",
-            dh_mode, h[0] / steps, h[1] / steps, h[2] / steps, h[3] / steps, h[5] / steps);
-  }
+  if (a.dbg && a.dir[0].n_steps > 1)                                    // workgroup 0, direction 0, waves 0,1
+    stamps_report(st, a.dbg, 1, a.dir[0].n_steps, CHAIN_STAMP_COLS("wait + staged reads + 16 ops"), "", "seq4 dh_mode %d, cycles per step", dh_mode);
 #endif
   return 0;
 }
@@ -824,41 +813,26 @@ int launch_gru_bwd_seq4_dw1(const GruArgs& a, const GruArgs& a1, int n_tiles, in
 int launch_gru_bwd_b4(int I, bool folds, const GruArgs& a, int n_tiles, int nwg, int ndir, const FoldCtx& fc, hipStream_t st, bool waves8) {
   const dim3 grid(nwg, ndir, folds ? fc.n : 1);
   if (I == 32 && waves8) {
-    if (folds) gru_bwd_b5<true><<<grid, 512, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc);
-    else gru_bwd_b5<false><<<grid, 512, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc);
+    with_flag(folds, [&](auto F) { gru_bwd_b5<decltype(F)::value><<<grid, 512, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc); });
     MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
     if (a.dbg) {
-      (void)hipStreamSynchronize(st);
-      static unsigned long long h[3 * 2 * 256 * 8];
-      const int per = ndir * nwg;
-      (void)hipMemcpy(h, a.dbg, sizeof(unsigned long long) * 8 * 3 * per, hipMemcpyDeviceToHost);
-      const char* names[3] = {"chain wave 0", "bulk wave 4 (dX + 3 dW tiles)", "bulk wave 6 (6 dW tiles, x staging)"};
-      for (int role = 0; role < 3; ++role) {
-        double acc[8] = {0};
-        for (int i = 0; i < per; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[((size_t)role * per + i) * 8 + j] / per;
-        const double steps = a.dir[0].n_steps;
-        if (role == 0)
-          fprintf(stderr, "[stamps b5 %s, cycles per step (first tile)] loop top %.0f | wait + staged reads + 16 ops %.0f | recurrence %.0f | dependent gate math + stores %.0f | barrier %.0f\n",
-                  names[role], acc[0] / steps, acc[1] / steps, acc[2] / steps, acc[3] / steps, acc[5] / steps);
-        else
-          fprintf(stderr, "[stamps b5 %s, cycles per step (first tile)] loop top %.0f | x fetch / fragment reads + dX %.0f | dW %.0f | barrier %.0f\n",
-                  names[role], acc[0] / steps, acc[3] / steps, acc[4] / steps, acc[5] / steps);
-      }
+      const int per = ndir * nwg, steps = a.dir[0].n_steps;
+      stamps_report(st, a.dbg, per, steps, CHAIN_STAMP_COLS("wait + staged reads + 16 ops"), "", "b5 chain wave 0, cycles per step (first tile)");
+      stamps_report(st, a.dbg + (size_t)8 * per, per, steps, BULK_STAMP_COLS("x fetch / fragment reads + dX"), "", "b5 bulk wave 4 (dX + 3 dW tiles), cycles per step (first tile)");
+      stamps_report(st, a.dbg + (size_t)16 * per, per, steps, BULK_STAMP_COLS("x fetch / fragment reads + dX"), "", "b5 bulk wave 6 (6 dW tiles, x staging), cycles per step (first tile)");
     }
 #endif
     return 0;
   } else if (I == 32) {
-    if (folds) gru_bwd_b4<32, true><<<grid, 256, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc);
-    else gru_bwd_b4<32, false><<<grid, 256, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc);
+    with_flag(folds, [&](auto F) { gru_bwd_b4<32, decltype(F)::value><<<grid, 256, BwdB4<32>::SMEM, st>>>(a, n_tiles, fc); });
   } else {
     // Layer 1 (ROLE 2) is NOT shipped: its 216 resident weight registers + 144 accumulator registers leave ~150 for a pipelined
     // gate math that needs ~240.  With the DMA ring every scratch reload's compiler-made vmcnt(0) drains the ring: 2.36 ms; with
     // register loads instead (USE_DMA = false, what the code does now) 67 dwords of scratch per lane: 2.59 ms — against 1.72 ms
     // for gru_bwd_b3<128> (profiles/r03_bwd4_stamps.log).  Parity-green both ways; make EXTRA=-DMSIG_B4_L1 builds it.
 #ifdef MSIG_B4_L1
-    if (folds) gru_bwd_b4<128, true><<<grid, 256, BwdB4<128>::SMEM, st>>>(a, n_tiles, fc);
-    else gru_bwd_b4<128, false><<<grid, 256, BwdB4<128>::SMEM, st>>>(a, n_tiles, fc);
+    with_flag(folds, [&](auto F) { gru_bwd_b4<128, decltype(F)::value><<<grid, 256, BwdB4<128>::SMEM, st>>>(a, n_tiles, fc); });
 #else
     return MSIG_E_SHAPE;
 #endif
@@ -866,17 +840,11 @@ int launch_gru_bwd_b4(int I, bool folds, const GruArgs& a, int n_tiles, int nwg,
   MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
   if (a.dbg) {
-    (void)hipStreamSynchronize(st);
-    static unsigned long long h[2 * 2 * 256 * 8];
     const int per = ndir * nwg;
-    (void)hipMemcpy(h, a.dbg, sizeof(unsigned long long) * 8 * 2 * per, hipMemcpyDeviceToHost);
-    for (int role = 0; role < (I == 32 ? 2 : 1); ++role) {
-      double acc[8] = {0};
-      for (int i = 0; i < per; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[((size_t)role * per + i) * 8 + j] / per;
-      const double steps = a.dir[0].n_steps;
-      fprintf(stderr, "[stamps b4 I=%d waves %s, cycles per step (first tile)] loop top %.0f | reads + vmcnt wait + 16 ops %.0f | recurrence %.0f | dX %.0f | dW %.0f | barrier %.0f\n",
-              I, role ? "2,3" : "0,1", acc[0] / steps, acc[1] / steps, acc[2] / steps, acc[3] / steps, acc[4] / steps, acc[5] / steps);
-    }
+    for (int role = 0; role < (I == 32 ? 2 : 1); ++role)
+      stamps_report(st, a.dbg + (size_t)8 * role * per, per, a.dir[0].n_steps,
+                    {{0, "loop top"}, {1, "reads + vmcnt wait + 16 ops"}, {2, "recurrence"}, {3, "dX"}, {4, "dW"}, {5, "barrier"}}, "",
+                    "b4 I=%d waves %s, cycles per step (first tile)", I, role ? "2,3" : "0,1");
   }
 #endif
   return 0;

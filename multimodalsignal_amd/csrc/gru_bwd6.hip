@@ -18,6 +18,7 @@
 // LDS: gate-gradient planes 2 x 27 648 B | [x | h_prev] planes 4 x 9 216 B | hn ring 2 x 4 096 B | staging 2 x 16 384 B | bulk A's hn
 // weight pieces 2 x 12 288 B = 157 696 B.
 #include "gru_args.h"
+#include "gru_frag.h"
 #include "gru_bwd4.h"
 #include "gru_bwd_pipe.h"
 
@@ -47,11 +48,9 @@ __device__ __forceinline__ void bwd6_run(const GruArgs& a, const GruDir& D, cons
       for (int j = 0; j < 8; ++j) {
         __bf16 p0, p1, p2;
         if constexpr (CH) {
-          split3(D.Whh[(size_t)(kb * 32 + lq * 8 + j) * 64 + w * 16 + li], p0, p1, p2);
-          AhB[kb][0][j] = p0; AhB[kb][1][j] = p1; AhB[kb][2][j] = p2;
+          FRAG_T_ELEM(AhB, D.Whh, 64, w, kb, j, true)
         } else {
-          split3(D.Wih[(size_t)(kb * 32 + lq * 8 + j) * I + w * 16 + li], p0, p1, p2);
-          AiB[kb][0][j] = p0; AiB[kb][1][j] = p1; AiB[kb][2][j] = p2;
+          FRAG_T_ELEM(AiB, D.Wih, I, w, kb, j, true)
         }
       }
 #pragma unroll
@@ -72,28 +71,22 @@ __device__ __forceinline__ void bwd6_run(const GruArgs& a, const GruDir& D, cons
     for (int ub = 0; ub < 2; ++ub) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        const float* wr = D.Whh + (size_t)(128 + (w + 2 * ub) * 16 + li) * 64 + kb * 32 + lq * 8;
         bf16x8 P[3];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { __bf16 p0, p1, p2; split3(wr[j], p0, p1, p2); P[0][j] = p0; P[1][j] = p1; P[2][j] = p2; }
+        LOAD_FRAG_BF16X3_BLOCK(D.Whh + (size_t)(128 + (w + 2 * ub) * 16 + li) * 64 + kb * 32 + lq * 8, P)
 #pragma unroll
         for (int pp = 0; pp < 3; ++pp) *(bf16x8*)(whn + ((ub * 2 + kb) * 3 + pp) * 1024) = P[pp];
       }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) b_hn[ub][e] = D.bhh[128 + (w + 2 * ub) * 16 + lq * 4 + e];
+      for (int e = 0; e < 4; ++e) b_hn[ub][e] = GRU_BIAS_HN(D, (w + 2 * ub) * 16 + lq * 4 + e);
     }
   }
   // ---- persistent dW accumulators: tile t = (A block of the gate-gradient planes [dr|dz|dhn|dn], B block of [x | h_prev]) ----
   int aoff[NTA], boff[NTA];
   aoff[0] = boff[0] = 0;
-  if constexpr (BA) {                      // 32 n-gate units: dW_ih <- dn . x, dW_hh <- dhn . h_prev
-    aoff[0] = 192 + 32 * w; boff[0] = 0;
-    aoff[1] = 128 + 32 * w; boff[1] = 32;
-    aoff[2] = 128 + 32 * w; boff[2] = 64;
-  } else if constexpr (BB) {               // wave 2: the r gate, wave 3: the z gate; units lo / hi x columns x, h lo, h hi
-    const int gc = (w - 2) * 64;
-#pragma unroll
-    for (int t = 0; t < 6; ++t) { aoff[t] = gc + 32 * (t / 3); boff[t] = 32 * (t % 3); }
+  if constexpr (BA) {
+    DW_TILES_N(w, aoff, boff)
+  } else if constexpr (BB) {
+    DW_TILES_RZ(w, aoff, boff)
   }
   f32x16 accW[NTA];
 #pragma unroll
@@ -456,10 +449,10 @@ __device__ __forceinline__ void bwd6_run(const GruArgs& a, const GruDir& D, cons
         constexpr int n = decltype(nc)::value;
         if constexpr (n < 6 * NBR) {
           constexpr int blk = n / 6, pp = (n % 6) / 2, h = n % 2;
-          put_half<h>(Bf[blk][pp], lds_tr_read4(ring + xcur + tr_xh[h] + 32 * blk + pp * XHP));
+          put_half<h>(Bf[blk][pp], lds_tr_read(ring + xcur + tr_xh[h] + 32 * blk + pp * XHP));
         } else if constexpr (n < NFR) {
           constexpr int m = n - 6 * NBR, blk = m / 6, pp = (m % 6) / 2, h = m % 2;
-          put_half<h>(Af[blk][pp], lds_tr_read4(ring + cur + tr_dg[h] + aoff[BB ? 3 * blk : blk] + pp * DGP));
+          put_half<h>(Af[blk][pp], lds_tr_read(ring + cur + tr_dg[h] + aoff[BB ? 3 * blk : blk] + pp * DGP));
         }
       };
       [[maybe_unused]] const int xnew = xh_buf(j + 3);
@@ -536,7 +529,7 @@ __device__ __forceinline__ void bwd6_run(const GruArgs& a, const GruDir& D, cons
         accW[tI] = mf32<t, CT_DW>(Af[ai], Bf[bi], accW[tI]);
         PINA(accW[tI]);
         FENCE();
-        if constexpr (BA && tI == 1) put_half<t % 2>(Bf[0][t / 2], lds_tr_read4(ring + xcur + tr_xh[t % 2] + 64 + (t / 2) * XHP));   // h hi for tile 2
+        if constexpr (BA && tI == 1) put_half<t % 2>(Bf[0][t / 2], lds_tr_read(ring + xcur + tr_xh[t % 2] + 64 + (t / 2) * XHP));   // h hi for tile 2
         if constexpr (BA && s == 1) {
           if (valid) *(float4*)(dxq + w * 16) = make_float4(ax[0], ax[1], ax[2], ax[3]);
           dxq -= dxstep;
@@ -619,27 +612,14 @@ int gru_bwd_b6_lds_optin() {
 
 int launch_gru_bwd_b6(bool folds, const GruArgs& a, int n_tiles, int nwg, int ndir, const FoldCtx& fc, hipStream_t st) {
   const dim3 grid(nwg, ndir, folds ? fc.n : 1);
-  if (folds) gru_bwd_b6<true><<<grid, 512, BwdB6::SMEM, st>>>(a, n_tiles, fc);
-  else gru_bwd_b6<false><<<grid, 512, BwdB6::SMEM, st>>>(a, n_tiles, fc);
+  with_flag(folds, [&](auto F) { gru_bwd_b6<decltype(F)::value><<<grid, 512, BwdB6::SMEM, st>>>(a, n_tiles, fc); });
   MSIG_LAUNCH_CHECK();
 #ifdef MSIG_STAMPS
   if (a.dbg) {
-    (void)hipStreamSynchronize(st);
-    static unsigned long long h[3 * 2 * 256 * 8];
-    const int per = ndir * nwg;
-    (void)hipMemcpy(h, a.dbg, sizeof(unsigned long long) * 8 * 3 * per, hipMemcpyDeviceToHost);
-    const char* names[3] = {"chain wave 0", "bulk wave 4 (hn, dX, 3 dW tiles)", "bulk wave 6 (6 dW tiles, x / h staging)"};
-    for (int role = 0; role < 3; ++role) {
-      double acc[8] = {0};
-      for (int i = 0; i < per; ++i) for (int j = 0; j < 8; ++j) acc[j] += (double)h[((size_t)role * per + i) * 8 + j] / per;
-      const double steps = a.dir[0].n_steps;
-      if (role == 0)
-        fprintf(stderr, "[stamps b6 %s, cycles per step (first tile)] loop top %.0f | wait + staged reads %.0f | recurrence %.0f | dependent gate math + stores %.0f | barrier %.0f\n",
-                names[role], acc[0] / steps, acc[1] / steps, acc[2] / steps, acc[3] / steps, acc[5] / steps);
-      else
-        fprintf(stderr, "[stamps b6 %s, cycles per step (first tile)] loop top %.0f | hn + fragment reads + dX %.0f | dW %.0f | barrier %.0f\n",
-                names[role], acc[0] / steps, acc[3] / steps, acc[4] / steps, acc[5] / steps);
-    }
+    const int per = ndir * nwg, steps = a.dir[0].n_steps;
+    stamps_report(st, a.dbg, per, steps, CHAIN_STAMP_COLS("wait + staged reads"), "", "b6 chain wave 0, cycles per step (first tile)");
+    stamps_report(st, a.dbg + (size_t)8 * per, per, steps, BULK_STAMP_COLS("hn + fragment reads + dX"), "", "b6 bulk wave 4 (hn, dX, 3 dW tiles), cycles per step (first tile)");
+    stamps_report(st, a.dbg + (size_t)16 * per, per, steps, BULK_STAMP_COLS("hn + fragment reads + dX"), "", "b6 bulk wave 6 (6 dW tiles, x / h staging), cycles per step (first tile)");
   }
 #endif
   return 0;

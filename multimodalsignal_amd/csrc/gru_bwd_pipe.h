@@ -1,10 +1,10 @@
 // Building blocks of the software-pipelined GRU backward kernels (gru_bwd4.hip: gru_bwd_b4 / b5 / seq4; gru_bwd6.hip: gru_bwd_b6):
-// slot fences, register-class pins, the staged three-piece split, split-bf16 MFMA terms, transposed LDS reads.
+// slot fences, register-class pins, the staged three-piece split, split-bf16 MFMA terms.
 #pragma once
 #include "gru_args.h"
+#include "gru_frag.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define LDS_AS __attribute__((address_space(3)))
 // A slot boundary.  sched_barrier(0) fences the machine scheduler only: instruction selection linearises a basic block's DAG by
 // register pressure and moves every node without a chain (MFMAs, VALU) to its use, across any number of fences (first version of
 // this kernel: 18 MFMAs back to back, then 26 VALU in a row).  What does hold an operation in its slot is a dependence on an
@@ -12,20 +12,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // but volatile asms keep their program order), and the boundary is a volatile asm with a memory clobber, which orders the LDS
 // and global memory operations of the slots as well.
 #define FENCE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define PIN_ACC(v) asm volatile("" : "+a"(v))
-#define PINA(v) asm volatile("" : "+a"(v))
+#define PINA(v) PIN_ACC(v)
 #define PINV(v) asm volatile("" : "+v"(v))
 #define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n) : "memory")
 
-template <int N> using ic = std::integral_constant<int, N>;
-template <typename F, int... Is> __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) { (f(ic<Is>{}), ...); }
-template <int N, typename F> __device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-
-__device__ __forceinline__ bf16x4 lds_tr_read4(const __bf16* p) {      // ds_read_b64_tr_b16; EXEC must be all ones
-  typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 v4;
-  const v4 r = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS v4*)p);
-  return __builtin_bit_cast(bf16x4, r);
-}
 // term T of the six-term split-bf16 product (smallest cross terms first, as mfma_bf16x3)
 template <int T, int KIND> __device__ __forceinline__ f32x4 mf16(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {
   constexpr int ai[6] = {2, 0, 1, 1, 0, 0}, bi[6] = {0, 2, 1, 0, 1, 0};

@@ -3,15 +3,7 @@
 // the latency form".
 #pragma once
 #include "gru_args.h"
-
-#ifndef LDS_AS
-#define LDS_AS __attribute__((address_space(3)))
-#endif
-__device__ __forceinline__ bf16x4 lds_tr_read(const __bf16* p) {      // ds_read_b64_tr_b16; EXEC must be all ones
-  typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 v4;
-  const v4 r = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS v4*)p);
-  return __builtin_bit_cast(bf16x4, r);
-}
+#include "gru_frag.h"
 
 template <int I> struct BwdB3 {
   static constexpr bool L1K = (I == 128);
