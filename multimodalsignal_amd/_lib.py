@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -106,6 +106,9 @@ EN_MAX_MEMBERS = 256  # msig_en.h MSIG_EN_MAX_MEMBERS: members of one ensemble
 KD_ABI_VERSION = 1    # include/msig_kd.h MSIG_KD_ABI_VERSION (distillation: the teacher table and the train step's distillation term)
 KD_MAX_MEMBERS = 256  # msig_kd.h MSIG_KD_MAX_MEMBERS: members of one teacher
 KD_MIN_T, KD_MAX_T = 1.0 / 64.0, 64.0      # msig_kd.h: the temperature's range
+SAM_ABI_VERSION = 1   # include/msig_sam.h MSIG_SAM_ABI_VERSION (sharpness-aware minimisation: perturbation, restore, the two-pass train step)
+SAM_NORM_SUM, SAM_NORM_MAX, SAM_NORM_LAST, SAM_SHARP_SUM, SAM_SHARP_LAST, SAM_STEPS = range(6)      # msig_sam.h: the state's statistics
+SAM_NSTAT = 8         # msig_sam.h MSIG_SAM_NSTAT: float64 statistics at the head of a model's SAM state
 NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
 
 
@@ -172,6 +175,13 @@ class Kd(C.Structure):
     batch's store positions, the optional statistics, and (fold batch) the bytes between the folds' tables and statistics."""
     _fields_ = [("alpha", C.c_float), ("temperature", C.c_float), ("q", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64),
                 ("stats", C.c_void_p), ("stride_bytes", C.c_int64)]
+
+
+class Sam(C.Structure):
+    """msig_sam (include/msig_sam.h): the sharpness-aware step of a launch — model kind, SAM or ASAM, rho and eta, and the caller-owned
+    state (fold slot 0's in a fold batch)."""
+    _fields_ = [("kind", C.c_int32), ("adaptive", C.c_int32), ("rho", C.c_float), ("eta", C.c_float), ("state", C.c_void_p),
+                ("state_bytes", C.c_int64)]
 
 
 class Wa(C.Structure):
@@ -394,6 +404,19 @@ def lib() -> C.CDLL:
         L.msig_kd_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), vp, vp, f32, f32, f32, f32, f32, i64, vp]
         L.msig_kd_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), vp, vp, f32, f32,
                                                f32, f32, i64, vp]
+        # include/msig_sam.h, exported by the same library: the perturbation, the restore and the two-pass train steps
+        L.msig_sam_abi_version.restype = C.c_int
+        L.msig_sam_struct_bytes.restype = C.c_int64
+        if L.msig_sam_abi_version() != SAM_ABI_VERSION or L.msig_sam_struct_bytes() != C.sizeof(Sam):
+            raise RuntimeError(f"{LIB_PATH} has msig_sam.h ABI {L.msig_sam_abi_version()} with msig_sam of {L.msig_sam_struct_bytes()} bytes; "
+                               f"this binding is {SAM_ABI_VERSION} with {C.sizeof(Sam)}: rebuild the library")
+        L.msig_sam_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.msig_sam_state_bytes.restype = C.c_int64
+        L.msig_sam_perturb.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Sam), vp]
+        L.msig_sam_restore.argtypes = [vp, vp, vp, vp, i32, C.c_int, C.c_int, C.POINTER(Sam), vp]
+        L.msig_sam_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Kd), C.POINTER(Sam), vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_sam_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Kd), C.POINTER(Sam), vp, vp, f32, f32,
+                                                f32, f32, i64, vp]
         # include/msig_nr.h, exported by the same library: per-subject normalisation with the statistics of reference windows
         L.msig_nr_abi_version.restype = C.c_int
         if L.msig_nr_abi_version() != NR_ABI_VERSION:
@@ -494,6 +517,14 @@ def gc_state_bytes(Cin: int, K: int, kind: str = "cnn_gru_attention") -> int:
     n = int(lib().msig_gc_state_bytes(Cin, K, GC_KINDS[check_kind(kind)]))
     if n < 0:
         check(n, "msig_gc_state_bytes")
+    return n
+
+
+def sam_state_bytes(Cin: int, K: int, kind: str = "cnn_gru_attention") -> int:
+    """Bytes of one model's SAM state (include/msig_sam.h msig_sam_state_bytes)."""
+    n = int(lib().msig_sam_state_bytes(Cin, K, GC_KINDS[check_kind(kind)]))
+    if n < 0:
+        check(n, "msig_sam_state_bytes")
     return n
 
 

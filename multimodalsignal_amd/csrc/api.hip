@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h and msig_kd.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h, msig_kd.h and msig_sam.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -15,6 +15,7 @@
 #include "../../include/msig_ab.h"
 #include "../../include/msig_mc.h"
 #include "../../include/msig_kd.h"
+#include "../../include/msig_sam.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -107,8 +108,9 @@ extern "C" int msig_stage_lengths(int T, int32_t* out) {
   return 0;
 }
 
-// gated = false: CnnGruModel's layout (include/msig_cg.h), the gate's two tensors with zero size
-static int param_layout(int C, int K, int64_t* off, bool gated) {
+// gated = false: CnnGruModel's layout (include/msig_cg.h), the gate's two tensors with zero size.  len (optional): the tensors' true
+// lengths — what lies between a tensor's end and the next offset is padding
+static int param_layout(int C, int K, int64_t* off, bool gated, int64_t* len = nullptr) {
   if (!off) return MSIG_E_NULL;
   if (C < 1 || C > MSIG_MAX_C || K < 2 || K > MSIG_MAX_K) return MSIG_E_SHAPE;
   int64_t n[MSIG_NPARAM];
@@ -129,10 +131,12 @@ static int param_layout(int C, int K, int64_t* off, bool gated) {
   n[MSIG_P_CLS0_W] = 64 * 128; n[MSIG_P_CLS0_B] = 64;
   n[MSIG_P_CLS3_W] = (int64_t)K * 64; n[MSIG_P_CLS3_B] = K;
   int64_t o = 0;
-  for (int i = 0; i < MSIG_NPARAM; ++i) { off[i] = o; o += (n[i] + 3) / 4 * 4; }
+  for (int i = 0; i < MSIG_NPARAM; ++i) { off[i] = o; o += (n[i] + 3) / 4 * 4; if (len) len[i] = n[i]; }
   off[MSIG_NPARAM] = o;
   return 0;
 }
+// the layout of a MSIG_GC_KIND_* with the lengths (sam.hip walks the tensors, never the padding)
+int msig_param_table(int C, int K, int kind, int64_t* off, int64_t* len) { return param_layout(C, K, off, kind == MSIG_GC_KIND_ATTENTION, len); }
 extern "C" int msig_param_layout(int C, int K, int64_t* off) { return param_layout(C, K, off, true); }
 
 static inline int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -315,9 +319,32 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   if ((rc = make_ctx(b, c, true, cg))) return rc;          // every argument check of the step before its first launch
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
+  // sharpness-aware step (include/msig_sam.h): pass 1 here — forward with the head unfused, backward, the reduction WITHOUT Adam, the
+  // perturbation — then this function once more on copies of the descriptors that report nowhere (pass2), with the same keys
+  if (o.sam && !o.sam->pass2) {
+    if ((rc = forward_fc(b, fc, st, o, true))) return rc;
+    if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
+    ColsumPlan plan1;
+    if ((rc = launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan1, fc, st))) return rc;
+    if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan1, fc, st))) return rc;
+    if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan1, fc, st, !cg))) return rc;
+    if ((rc = launch_colsum_plan(plan1, fc, st))) return rc;
+    if ((rc = launch_sam_perturb(*o.sam, (float*)b->params, b->grads, b->bn_state, b->bn_count, c.w.p<float>(MSIG_WS_LOSS), fc, st))) return rc;
+    msig_batch b2 = *b;
+    b2.loss_acc = nullptr;                  // epoch sums count a batch once, at w
+    SamArgs sam2 = *o.sam;
+    sam2.pass2 = true;
+    KdArgs kd2;
+    StepOpts o2 = o;
+    o2.sam = &sam2;
+    if (o.kd) { kd2 = *o.kd; kd2.stats = nullptr; o2.kd = &kd2; }
+    fc.fused_step = 0;                      // as this call received it: the second one sets it after its own checks
+    return train_step_fc(&b2, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st, o2);
+  }
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
   // distillation (include/msig_kd.h) needs WS_LOGITS and WS_DLOGITS complete between the criterion and the head's backward: unfused
-  const bool head_step = !o.kd && head_step_applies(b, c.d);
+  // a sharpness-aware step's second pass restores MSIG_WS_LOSS before the last launch, where head_step would finalise its sums: unfused
+  const bool head_step = !o.kd && !o.sam && head_step_applies(b, c.d);
   if ((rc = forward_fc(b, fc, st, o, !head_step))) return rc;
   if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
@@ -328,6 +355,8 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   if (o.da && (rc = launch_da_step(*o.da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
+  // second pass of a sharpness-aware step: back to w (and to pass 1's BatchNorm state and losses) before Adam reads the parameters
+  if (o.sam && (rc = launch_sam_restore(*o.sam, (float*)b->params, b->bn_state, b->bn_count, c.w.p<float>(MSIG_WS_LOSS), c.d.B, fc, st))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
   for (int i = 0; i < 6; ++i) {
     const int t = in_place[i];
@@ -514,8 +543,16 @@ static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* 
 // include/msig_kd.h (NULL, or alpha == 0 after its checks = msig_da_train_step[_multi] itself)
 static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
                          float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a,
-                         const msig_kd* k = nullptr) {
-  SoftArgs soft; bool use; int rc = make_soft(s, fc.n, soft, use); if (rc) return rc;
+                         const msig_kd* k = nullptr, const msig_sam* sm = nullptr) {
+  if (sm && (!s || !b)) return MSIG_E_NULL;
+  SamArgs sam;                             // include/msig_sam.h: its own checks first; rho == 0 after them = the call without it
+  int rc;
+  if (sm) {
+    if ((rc = msig_sam_make_args(sm, b->shape.C, b->shape.K, sam))) return rc;
+    if (sm->kind != s->kind) return MSIG_E_SHAPE;
+    if (sm->rho == 0.f) sm = nullptr;
+  }
+  SoftArgs soft; bool use; if ((rc = make_soft(s, fc.n, soft, use))) return rc;
   if (!b) return MSIG_E_NULL;
   DaArgs da;
   if (a && (rc = make_da(a, fc, b->shape.B, soft.lam, da))) return rc;
@@ -529,7 +566,7 @@ static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* 
   }
   return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st,
                        StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr,
-                                distil ? &kd : nullptr});
+                                distil ? &kd : nullptr, sm ? &sam : nullptr});
 }
 extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
   return st_forward(b, single_fold(b), s, (hipStream_t)stream);
@@ -623,6 +660,21 @@ extern "C" int msig_kd_train_step_multi(const msig_batch* b, const msig_multi* m
   if (!s) return MSIG_E_NULL;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd);
+}
+
+// ---- sharpness-aware minimisation (include/msig_sam.h; kernels and the stand-alone calls: sam.hip) --------------------------------
+extern "C" int msig_sam_train_step(const msig_batch* b, const msig_st* s, const msig_kd* kd, const msig_sam* sam, float* exp_avg,
+                                   float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                   void* stream) {
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr,
+                       kd, sam);
+}
+extern "C" int msig_sam_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_kd* kd, const msig_sam* sam,
+                                         float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
+                                         int64_t step, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr, kd, sam);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

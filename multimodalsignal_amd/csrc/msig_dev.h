@@ -443,6 +443,7 @@ struct SoftArgs { float eps; float lam[MSIG_MAX_FOLDS]; };
 struct ClipArgs;
 struct DaArgs;
 struct KdArgs;
+struct SamArgs;
 // What a forward or a train step does beyond the msig.h call (host side only; api.hip's entry points fill it after their own checks).
 // Value-initialised = the plain call.  Each function that takes it reads only the fields named at its declaration.
 struct StepOpts {
@@ -452,6 +453,7 @@ struct StepOpts {
   const SoftArgs* soft;     // soft targets (include/msig_st.h); NULL = the plain criterion's kernels
   const DaArgs* da;         // subject discriminator (include/msig_da.h): one more launch after the head's
   const KdArgs* kd;         // distillation (include/msig_kd.h): the unfused head with one more launch between ce and head_bwd
+  const SamArgs* sam;       // sharpness-aware step (include/msig_sam.h): two passes with the unfused head, perturbation and restore between
 };
 // reads o.cw, o.soft.  mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of
 // b->dropout_thr although b->training = 0
@@ -492,6 +494,26 @@ struct KdArgs {
 // every check of msig_kd.h's own arguments, before any launch; fc: the folds of the launch (stride != 0: a fold batch); lam per fold
 int msig_kd_make_args(const msig_kd* k, const FoldCtx& fc, int32_t B, int32_t K, const float* lam, KdArgs& kd);
 int launch_kd_apply(const KdArgs& a, const float* logits, float* dlogits, const FoldCtx& fc, hipStream_t st);
+// Sharpness-aware minimisation (include/msig_sam.h, sam.hip): msig_sam after its checks (msig_sam_make_args), by value to the launches.
+// state: fold slot 0's, shifted per fold like every buffer; off / len: the parameter tensors' offsets and TRUE lengths in floats (the
+// padding between tensors is len short of the next offset); n_flat: the padded total; a16: the state is 16-byte aligned.  pass2 is
+// host side only: train_step_fc's second pass, which restores before its last launch.
+#define SAM_WG 32                      // workgroups per fold of every sam.hip launch: the norm's partial sums are SAM_WG doubles
+struct msig_sam;
+struct SamArgs {
+  int32_t adaptive, a16;
+  float rho, eta;
+  char* state;
+  int64_t n_flat;
+  int32_t off[MSIG_NPARAM], len[MSIG_NPARAM];
+  bool pass2;
+};
+int msig_sam_make_args(const msig_sam* s, int C, int K, SamArgs& a);
+// two launches: the per-workgroup sums of squares, then backup / perturbation / the copies of bn_state, bn_count, ws_loss[0..2]
+int launch_sam_perturb(const SamArgs& a, float* params, const float* grads, const float* bn_state, const int64_t* bn_count,
+                       const float* ws_loss, const FoldCtx& fc, hipStream_t st);
+int launch_sam_restore(const SamArgs& a, float* params, float* bn_state, int64_t* bn_count, float* ws_loss, int B, const FoldCtx& fc,
+                       hipStream_t st);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch

@@ -34,6 +34,7 @@ from . import adversary as adversary_mod
 from . import averaging as averaging_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask
 from . import distill as distill_mod
+from . import sam as sam_mod
 from . import ensemble as ensemble_mod
 from .loso import folds_for_rank, gather_fold_metrics, split_train_val
 from .models import CnnGruAttentionModel, CnnGruModel
@@ -102,6 +103,8 @@ def trainer_config(cfg, fold_idx):
         tc["trainer"]["max_grad_norm"] = grad_clip_setting(cfg["max_grad_norm"])
     if cfg.get("label_smoothing") is not None:      # CrossEntropyLoss(label_smoothing=) of every loss (include/msig_st.h); absent = hard labels
         tc["trainer"]["label_smoothing"] = label_smoothing_setting(cfg["label_smoothing"])
+    if cfg.get("sam") is not None:                  # sharpness-aware train steps (include/msig_sam.h); absent = the plain step
+        tc["trainer"]["sam"] = sam_mod.setting(cfg["sam"]).spec()
     if cfg.get("adversary") is not None:            # a subject discriminator inside every training step (include/msig_da.h); absent = none
         tc["adversary"] = adversary_mod.settings(cfg["adversary"])
     if cfg.get("averaging") is not None:            # an EMA / SWA shadow of the weights (include/msig_wa.h); absent = none
@@ -216,6 +219,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
         if cfg.get("max_grad_norm") is not None:                    # likewise
             f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
+        if cfg.get("sam") is not None:                              # likewise
+            f.write(f"SAM: {cfg['sam']}\n")
         if cfg.get("augment") is not None:                          # likewise
             f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
         if soft_targets_line(cfg) is not None:                      # likewise
@@ -1030,6 +1035,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(f"CLASS_WEIGHTS: {trainer_class_weights(cfg)}\n")
             if cfg.get("max_grad_norm") is not None:
                 f.write(f"MAX_GRAD_NORM: {cfg['max_grad_norm']:g}\n")
+            if cfg.get("sam") is not None:
+                f.write(f"SAM: {cfg['sam']}\n")
             if cfg.get("augment") is not None:
                 f.write(f"AUGMENT: {Augment.coerce(cfg['augment']).spec()}\n")
             if soft_targets_line(cfg) is not None:
@@ -1136,6 +1143,14 @@ def parse_args(ap, argv=None):
         args.max_grad_norm = grad_clip_setting(args.max_grad_norm)
     except ValueError as e:
         ap.error(f"--max-grad-norm: {e}")
+    if args.sam is not None:
+        try:
+            args.sam = sam_mod.Sam.parse(args.sam)
+        except ValueError as e:
+            ap.error(f"--sam: {e}")
+        if args.subject_adversarial is not None:
+            ap.error("--sam cannot be combined with --subject-adversarial: the discriminator's own Adam would advance in both passes of a step")
+        args.sam = args.sam.spec() if args.sam.on else None         # --sam 0 is the run without the flag
     if args.augment is not None:
         try:
             args.augment = Augment.parse(args.augment)
@@ -1243,6 +1258,12 @@ def build_parser():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="torch.nn.utils.clip_grad_norm_(model.parameters(), X) between backward and Adam inside the fused train step "
                          "(every mode: LOSO, --ablation, --hierarchical, --model, sequential); logs each epoch's gradient norms")
+    ap.add_argument("--sam", default=None, metavar="RHO[:adaptive[:ETA]]",
+                    help="sharpness-aware minimisation inside the fused train step: per batch the gradient at w, a step of length RHO "
+                         "along it, the gradient there (same dropout masks), and Adam at w with that second gradient; ':adaptive' = ASAM "
+                         "with T_w = |w| + ETA (default 0.01).  A step costs about two (every mode: LOSO, --ablation, --sweep, "
+                         "--hierarchical, --model, --seeds, --distill, sequential; not with --subject-adversarial); logs each epoch's "
+                         "sam_grad_norm and sam_sharpness; 0 = off")
     ap.add_argument("--augment", default=None, metavar="SPEC",
                     help="augment every training batch inside its gather launch, e.g. scale=0.1,jitter=0.05,mask=0.5:320,chandrop=0.1: "
                          "per-channel gain 1 + scale * g, additive noise jitter * g per sample, with probability mask=P one zeroed span of "
@@ -1348,6 +1369,8 @@ def build_cfg(args, kinds):
                class_weights=args.class_weights, model=kinds[0], model_params=dict(MODEL_PARAMS[kinds[0]]))
     if args.max_grad_norm is not None:      # without the flag the configuration has no such key
         cfg["max_grad_norm"] = args.max_grad_norm
+    if args.sam is not None:                # likewise
+        cfg["sam"] = args.sam
     if args.augment is not None:            # likewise
         cfg["augment"] = args.augment
     if args.label_smoothing is not None:    # likewise

@@ -17,7 +17,9 @@ when its companions stop).  Folds may differ in train / val set size; folds that
 stop early leave the batch.  Every train launch is msig_da_train_step_multi and every evaluation launch msig_st_forward_multi,
 whatever the folds have switched on: runtime's module docstring says why that is bit-safe.  With config['averaging'] every train
 launch is followed by one msig_wa_update_multi over the same folds (EMA; SWA: one per epoch), each fold at its own coefficient: the
-shadows live in the arenas, where msig_st_forward_multi can evaluate them (include/msig_wa.h).
+shadows live in the arenas, where msig_st_forward_multi can evaluate them (include/msig_wa.h).  With
+config['trainer']['sam'] every train launch is msig_sam_train_step_multi instead — two passes of all folds of the launch, each fold's
+SAM state one more region of its arena (include/msig_sam.h); without the key the launches are the ones above.
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ import torch
 from . import _lib as L
 from . import adversary as A
 from . import averaging as AV
+from . import sam as SAM
 from .runtime import FoldArena
 from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary, label_smoothing_setting
 
@@ -165,11 +168,19 @@ class LockstepTrainer:
         # step and the per-epoch passes are the batch's); coefficients and counters are per fold.  The shadows are arena regions.
         self.avg_cfg = _shared([AV.settings(p["config"].get("averaging")) for p in preps], "averaging setting", repr)
         self._wa_started = False
+        # sharpness-aware minimisation (config['trainer']['sam'], include/msig_sam.h): rho, the form and eta are the launch's, so the
+        # folds of a batch share them; every fold's state is one more region of its arena
+        self.sam_cfg = _shared([SAM.setting(p["config"]["trainer"].get("sam")) for p in preps], "sam setting", repr)
+        if self.sam_cfg is not None and not self.sam_cfg.on:
+            self.sam_cfg = None
+        if self.sam_cfg is not None and self.adv_S is not None:
+            raise ValueError("config['trainer']['sam'] cannot be combined with config['adversary']")
+        self.sam_stats = {}
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
                                adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip,
                                adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])),
                                averaging=self.avg_cfg is not None,
-                               distill=None if self.kd_cfg is None else int(tr0.store.shape[0]))
+                               distill=None if self.kd_cfg is None else int(tr0.store.shape[0]), sam=self.sam_cfg is not None)
         if self.clip:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
@@ -269,6 +280,8 @@ class LockstepTrainer:
         arena, lib = self.arena, L.lib()
         if self.clip:
             arena.zero_grad_stats(sorted(active))
+        if self.sam_cfg is not None:
+            arena.zero_sam_stats(sorted(active))
         act = sorted(active, key=lambda f: -len(self.preps[f]["loaders"][0].dataset))
         trs = [self.trainers[f] for f in act]
         loaders = [self.preps[f]["loaders"][0] for f in act]
@@ -321,8 +334,9 @@ class LockstepTrainer:
                                   None if advs is None else arena.da(sl, self.adv_S, [0.0] * nr, [lrs[r0 + j] * advs[r0 + j].lr_mult for j in range(nr)],
                                                                      [1] * nr, h0["betas"], eps, wd),
                                   arena.wa(sl, [0.0] * nr) if ema else None,
-                                  None if self.kd_cfg is None else arena.kd(*self.kd_cfg))
-            m, s, a, w, kd = runs[(r0, nr)]
+                                  None if self.kd_cfg is None else arena.kd(*self.kd_cfg),
+                                  None if self.sam_cfg is None else arena.sam(self.sam_cfg))
+            m, s, a, w, kd, sm = runs[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
                 if aug is not None:
@@ -335,8 +349,12 @@ class LockstepTrainer:
                 a.idx, a.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
             self._gather(loaders[0], order, r0, i, b, m, aug, s.lam if aug is not None or mix is not None else None)
             _, desc = self._layout(b, True)
-            if kd is not None:                 # a batch of students: the same call with the distillation term (alpha 0: the call below)
+            if kd is not None:
                 kd.idx, kd.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+            if sm is not None:                 # sharpness-aware steps: two passes of every fold of the launch, whatever else is on
+                L.check(lib.msig_sam_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(kd) if kd is not None else None, C.byref(sm),
+                                                      ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_sam_train_step_multi")
+            elif kd is not None:               # a batch of students: the same call with the distillation term (alpha 0: the call below)
                 L.check(lib.msig_kd_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, C.byref(kd),
                                                      ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_kd_train_step_multi")
             else:
@@ -366,6 +384,18 @@ class LockstepTrainer:
             st3 = arena.distill_stats().cpu().numpy()
             for f, t in zip(act, trs):
                 self.kd_stats[f] = t.distill.epoch_summary(st3[f])
+        if self.sam_cfg is not None:       # the same sync: the loss sums, the SAM statistics and (with the clip) the gradient norms
+            parts = [self.acc[:, :1], arena.across("sam", 0, torch.float64, L.SAM_NSTAT)]
+            if self.clip:
+                parts.append(arena.across("gc", 0, torch.float64, L.GC_NSTAT))
+            both = torch.cat(parts, dim=1).cpu().numpy()
+            self.sam_stats = {f: SAM.summary(both[f, 1:1 + L.SAM_NSTAT].tolist(), ns) for f, ns in zip(act, n_steps)}
+            if self.clip:
+                st4 = both[:, 1 + L.SAM_NSTAT:]
+                self.grad_stats = {f: grad_norm_summary(dict(sum=float(st4[f, L.GC_SUM]), max=float(st4[f, L.GC_MAX]),
+                                                             clipped=int(st4[f, L.GC_CLIPPED])), ns)
+                                   for f, ns in zip(act, n_steps) if self.trainers[f].max_grad_norm is not None}
+            return both[:, 0]
         if not self.clip:
             return self.acc[:, 0].cpu().numpy()               # the epoch's only sync
         # the same sync: the loss sums and the folds' gradient-norm statistics in one read-back
@@ -457,7 +487,7 @@ class LockstepTrainer:
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
                     if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f),
-                                           avg_vals.get(f), self.kd_stats.get(f)):
+                                           avg_vals.get(f), self.kd_stats.get(f), self.sam_stats.get(f)):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start

@@ -8,7 +8,8 @@ stream.  It holds no arithmetic of its own.
 The host never chooses among entry points: every train step is msig_da_train_step[_multi], every forward msig_st_forward[_multi],
 the widest of each form (a student's step, include/msig_kd.h, is msig_kd_train_step[_multi]).  The headers make that bit-safe — a
 NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL class_weight each give the narrower call with its launches, `kind`
-selects the model — and tests/test_step_dispatch_gpu.py pins it.
+selects the model — and tests/test_step_dispatch_gpu.py pins it.  A sharpness-aware step (include/msig_sam.h) is
+msig_sam_train_step[_multi], whatever else is on; without `sam` the calls are exactly the ones above.
 """
 from __future__ import annotations
 
@@ -59,6 +60,7 @@ class Engine:
             self.exp_avg_sq: Optional[torch.Tensor] = None
             self.loss_acc = torch.zeros(2, dtype=torch.float64, device=self.device)      # msig_batch.loss_acc: [sum of CE, #correct] of a pass
             self.gc_state: Optional[torch.Tensor] = None      # include/msig_gc.h clip state (float64), made by the first clipped step
+            self.sam_state: Optional[torch.Tensor] = None     # include/msig_sam.h state (float64 view), made by the first SAM step
             # include/msig_wa.h: the weight-averaging shadow (parameters, BatchNorm state and counts), made by ensure_shadow()
             self.avg_params: Optional[torch.Tensor] = None
             self.avg_bn_state: Optional[torch.Tensor] = None
@@ -72,6 +74,9 @@ class Engine:
             self.gc_state = storage.get("gc")
             if self.gc_state is not None:
                 self.gc_state.zero_()
+            self.sam_state = storage.get("sam")
+            if self.sam_state is not None:
+                self.sam_state.zero_()
             self.avg_params, self.avg_bn_state, self.avg_bn_count = (storage.get(k) for k in ("avg_params", "avg_bn_state", "avg_bn_count"))
             for t in (self.avg_params, self.avg_bn_state, self.avg_bn_count):
                 if t is not None:
@@ -338,6 +343,33 @@ class Engine:
     def _stats(s) -> dict:
         return dict(sum=s[L.GC_SUM], max=s[L.GC_MAX], clipped=int(s[L.GC_CLIPPED]), last=s[L.GC_LAST])
 
+    # ---- sharpness-aware minimisation (include/msig_sam.h) -------------------------------------------------------
+    def ensure_sam_state(self) -> torch.Tensor:
+        """The model's SAM state: L.SAM_NSTAT float64 statistics, then the step's scratch and backups."""
+        if self.sam_state is None:
+            self.sam_state = torch.zeros(L.sam_state_bytes(self.C, self.K, self.kind) // 8, dtype=torch.float64, device=self.device)
+        return self.sam_state
+
+    def zero_sam_stats(self):
+        if self.sam_state is not None:
+            self.sam_state[:L.SAM_NSTAT].zero_()
+
+    def sam_stats(self) -> Optional[list]:
+        """The SAM statistics since zero_sam_stats() as a list indexed by L.SAM_* (one read-back: a sync); None before the first SAM step."""
+        return None if self.sam_state is None else self.sam_state[:L.SAM_NSTAT].cpu().tolist()
+
+    def epoch_stats(self, grad: bool = False, sam: bool = False):
+        """(loss_acc as a list, grad_stats() or None, sam_stats() or None) in ONE device-to-host copy: what a trainer reads at the end
+        of an epoch."""
+        parts = [self.loss_acc]
+        if grad:
+            parts.append(self.ensure_gc_state()[:L.GC_NSTAT])
+        if sam:
+            parts.append(self.ensure_sam_state()[:L.SAM_NSTAT])
+        v = (torch.cat(parts) if len(parts) > 1 else parts[0]).cpu().tolist()
+        g = self._stats(v[2:2 + L.GC_NSTAT]) if grad else None
+        return v[:2], g, (v[-L.SAM_NSTAT:] if sam else None)
+
     def loss_and_grad_stats(self):
         """(loss_acc as a list, grad_stats()) in ONE device-to-host copy: what a trainer reads at the end of a clipped epoch."""
         v = torch.cat([self.loss_acc, self.ensure_gc_state()[:L.GC_NSTAT]]).cpu().tolist()
@@ -382,7 +414,8 @@ class Engine:
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
                    dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
-                   label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None, distill=None) -> None:
+                   label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None, distill=None,
+                   sam=None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
@@ -401,8 +434,15 @@ class Engine:
         distill: a distill.Distillation bound to this device (include/msig_kd.h): the head runs unfused and one more
         launch blends the gradient of the tempered KL term against the teacher rows — read by batch_index, or one per row — into
         the logits' gradient; the reported loss stays the criterion's, the term's own statistics go to distill.stats.  None, or
-        alpha = 0, is the call without it, bit for bit; the call is then msig_kd_train_step."""
+        alpha = 0, is the call without it, bit for bit; the call is then msig_kd_train_step.
+        sam: a sam.Sam (include/msig_sam.h): the step runs twice over the batch — gradient at w, perturbation to
+        w + e, gradient there with the same dropout masks, restore, Adam at w with the second gradient; `grads` holds that second
+        gradient, region('LOSS') / loss_acc / the BatchNorm state are the first pass's, sam_stats() the norms and the sharpness.
+        The call is msig_sam_train_step whatever else is on; rho = 0 is the step without it, bit for bit.  Not with `adversary`
+        (ValueError): two passes would advance the discriminator twice.  None = the calls above, exactly."""
         cw, max_norm, smooth, lam = self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
+        if sam is not None and adversary is not None:
+            raise ValueError("sam cannot be combined with adversary: the discriminator's own Adam would advance in both passes")
         if adversary is not None and x.shape[0] > L.DA_MAX_BATCH:
             raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
         if adversary is not None or distill is not None:
@@ -423,6 +463,15 @@ class Engine:
             if batch_index is None and distill.q.shape[0] < x.shape[0]:
                 raise ValueError(f"a teacher table read by row needs {x.shape[0]} rows, got {distill.q.shape[0]}")
             k = distill.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
+        else:
+            k = None
+        if sam is not None:
+            state = self.ensure_sam_state()
+            sd = sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8)
+            L.check(L.lib().msig_sam_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), None if k is None else C.byref(k),
+                                                C.byref(sd), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps,
+                                                weight_decay, step, self._stream()), "msig_sam_train_step")
+        elif k is not None:
             L.check(L.lib().msig_kd_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, C.byref(k), self.exp_avg.data_ptr(),
                                                self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
                     "msig_kd_train_step")
@@ -561,13 +610,15 @@ class EmbeddedEngine(Engine):
         return self.small_views(self.avg_params.index_select(0, self.index))
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
-                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None):
+                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None, sam=None):
         self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
+        if sam is not None and adversary is not None:
+            raise ValueError("sam cannot be combined with adversary: the discriminator's own Adam would advance in both passes")
         if adversary is not None:
             adversary.restrict_features(self.hidden)       # nothing may reach the padded feature columns (their units must stay zero)
         self.scatter()
         super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm, label_smoothing,
-                           mix_lambda, adversary, batch_index, distill)
+                           mix_lambda, adversary, batch_index, distill, sam)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -672,7 +723,7 @@ class FoldArena(Arenas):
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
                  adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
                  grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None, averaging: bool = False,
-                 distill: Optional[int] = None):
+                 distill: Optional[int] = None, sam: bool = False):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
@@ -688,7 +739,9 @@ class FoldArena(Arenas):
         stride are what they are without this argument.
         `distill` = store positions: every fold also gets a distillation teacher table of positions x K float32 and three float64
         statistics (include/msig_kd.h) in a memory block of their own, `kd_stride` bytes apart (`distill_storage`), as the
-        adversary's buffers are owned; the model arenas and their stride stay what they are without it."""
+        adversary's buffers are owned; the model arenas and their stride stay what they are without it.
+        `sam`: the arenas also hold a "sam" region, each fold's SAM state (include/msig_sam.h), after every other region, the shadow
+        included — without it the arenas and their stride are what they are without this argument."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -719,6 +772,9 @@ class FoldArena(Arenas):
         self.averaging = bool(averaging)
         if self.averaging:
             sizes += [("avg_params", self.n_flat * 4), ("avg_bn_state", L.BN_STATE_FLOATS * 4), ("avg_bn_count", 16)]
+        self.sam_on = bool(sam)
+        if self.sam_on:
+            sizes.append(("sam", L.sam_state_bytes(in_channels, num_classes, kind)))
         self.max_norm = [float("inf")] * n              # per arena: max_norm of the fold in it (set_max_norm); inf = measured, not clipped
         super().__init__(n, device, sizes)
         self.da_off, self.da_stride, self.da_mem = {}, 0, None
@@ -753,6 +809,8 @@ class FoldArena(Arenas):
         if self.averaging:
             st["avg_params"], st["avg_bn_state"] = self.view(slot, "avg_params", torch.float32), self.view(slot, "avg_bn_state", torch.float32)
             st["avg_bn_count"] = self.view(slot, "avg_bn_count", torch.int64)
+        if self.sam_on:
+            st["sam"] = self.view(slot, "sam", torch.float64)
         if self.gru_layers == 1:
             return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st, kind=self.kind)
         return Engine(self.C, self.K, self.device, storage=st, kind=self.kind)
@@ -851,6 +909,19 @@ class FoldArena(Arenas):
         if len(lams) != len(slots):
             raise ValueError(f"{len(slots)} folds need {len(slots)} mixup weights, got {len(lams)}")
         return L.make_st(self.kind, L.check_label_smoothing(smoothing), class_weight, clip, lams)
+
+    def sam(self, setting) -> L.Sam:
+        """msig_sam of a launch (include/msig_sam.h) from a sam.Sam: arena 0's SAM state, the arena stride apart."""
+        if not self.sam_on:
+            raise RuntimeError("this FoldArena was built without sam=True: it has no SAM state")
+        return setting.descriptor(self.kind, self.ptr("sam"), self.off["sam"][1])
+
+    def zero_sam_stats(self, slots=None) -> None:
+        st = self.across("sam", 0, torch.float64, L.SAM_NSTAT)
+        if slots is None:
+            st.zero_()
+        else:
+            st.index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
 
     def zero_grad_stats(self, slots=None) -> None:
         st = self.across("gc", 0, torch.float64, L.GC_NSTAT)

@@ -27,6 +27,9 @@ inside every TRAINING step and reverses its gradient into the extractor (include
 never run it; ``history`` and the log gain the epoch's domain loss, domain accuracy and lambda.
 ``config['averaging']`` (None or a dict with a mode, ``averaging.settings``) keeps an EMA or SWA shadow of the weights — one more launch
 after every train step (EMA) or at the end of an epoch (SWA); it steers nothing (include/msig_wa.h).
+``config['trainer']['sam']`` (None, or ``RHO[:adaptive[:ETA]]``) makes every TRAINING step a sharpness-aware one (include/msig_sam.h,
+DESIGN.md §28): ``history`` and the log gain the epoch's ``sam_grad_norm`` (mean and max) and ``sam_sharpness``; a rho of 0 is the
+run without the key; not with ``config['adversary']``.
 """
 from __future__ import annotations
 
@@ -42,6 +45,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 from . import _lib as L
 from . import adversary as A
 from . import averaging as AV
+from . import sam as SAM
 from .models import CnnGruAttentionModel
 
 
@@ -194,6 +198,13 @@ class Trainer:
         # distillation (include/msig_kd.h): a distill.Distillation with its teacher table, bound by set_distillation; None: off
         self.distill = None
         # weight averaging (include/msig_wa.h): the fold's averager (settings and counters); the shadow itself is the engine's
+        # sharpness-aware minimisation (include/msig_sam.h): a sam.Sam, or None (also for rho = 0: the run without it)
+        self.sam = SAM.setting(cfg.get("sam"))
+        if self.sam is not None and not self.sam.on:
+            self.sam = None
+        if self.sam is not None and self.adversary_cfg is not None:
+            raise ValueError("config['trainer']['sam'] cannot be combined with config['adversary']: the discriminator's own Adam would "
+                             "advance in both passes of a step")
         self.averaging_cfg = AV.settings(config.get("averaging"))
         self.averager = AV.WeightAverager(self.averaging_cfg) if self.averaging_cfg is not None else None
         self.verbose = cfg.get("verbose", True)
@@ -312,6 +323,9 @@ class Trainer:
                 adv.stats.zero_()
             if kd is not None:
                 kd.stats.zero_()
+            if self.sam is not None:
+                eng.ensure_sam_state()
+                eng.zero_sam_stats()
             n_steps = 0
             for inputs, labels in train_loader:
                 n_steps += 1
@@ -322,12 +336,17 @@ class Trainer:
                                step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
                                class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
                                mix_lambda=getattr(train_loader, "last_lam", None),      # the lam of the batch a mixup loader just served
-                               adversary=adv, distill=kd,
+                               adversary=adv, distill=kd, sam=self.sam,
                                batch_index=getattr(train_loader, "last_index", None) if adv is not None or kd is not None else None)
                 if av is not None and av.mode == "ema":
                     eng.average_update(av.step_coef())
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
-            if self.max_grad_norm is None:
+            sam = None
+            if self.sam is not None:                                                     # the same sync: one read-back for all three
+                acc, stats, ss = eng.epoch_stats(self.max_grad_norm is not None, True)
+                train_loss, sam = acc[0] / n_train, SAM.summary(ss, n_steps)
+                grad = grad_norm_summary(stats, n_steps) if stats is not None else None
+            elif self.max_grad_norm is None:
                 train_loss, grad = float(eng.loss_acc[0].item()) / n_train, None         # the epoch's only sync
             else:                                                                        # the same sync: one read-back for both
                 acc, stats = eng.loss_and_grad_stats()
@@ -341,7 +360,7 @@ class Trainer:
                 eng.average_update(av.epoch_coef(epoch + 1))     # the epoch-end iterate, from start_epoch on (before: no launch)
             val_loss, val_acc, val_f1, _, _ = self.evaluate(val_loader, is_val=True)
             avg = self.validate_averaged(val_loader) if av is not None and av.validate else None
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds):
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds, sam):
                 break
         self.finish_averaging([train_loader])
         self._finish_training()
@@ -366,12 +385,13 @@ class Trainer:
         if recompute and av.bn == "recompute":
             AV.recompute_bn([eng], train_loaders)
 
-    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None, kd=None) -> bool:
+    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None, kd=None, sam=None) -> bool:
         """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
         the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were.
         dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise.  avg: the validation pass under
         the averaging shadow when config['averaging']['validate'] is set (three more history keys; it steers nothing).  kd:
-        Distillation.epoch_summary of the epoch for a student (set_distillation): kd_loss and kd_agreement, likewise."""
+        Distillation.epoch_summary of the epoch for a student (set_distillation): kd_loss and kd_agreement, likewise.  sam:
+        sam.summary of the epoch when config['trainer']['sam'] is set: sam_grad_norm, sam_grad_norm_max and sam_sharpness, likewise."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
@@ -387,6 +407,10 @@ class Trainer:
             self.history[-1].update(kd)
             if kd["kd_loss"] is not None:
                 suffix += f" | kd loss: {kd['kd_loss']:.4f} | kd agreement: {kd['kd_agreement']:.4f}"
+        if sam is not None:
+            self.history[-1].update(sam)
+            suffix += (f" | sam grad norm: {sam['sam_grad_norm']:.4f} (max {sam['sam_grad_norm_max']:.4f}) | "
+                       f"sam sharpness: {sam['sam_sharpness']:.6f} (sam={self.sam.spec()})")
         if avg is not None:
             self.history[-1].update(avg)
             if avg["val_loss_avg"] is not None:
