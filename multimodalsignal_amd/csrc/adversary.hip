@@ -2,11 +2,12 @@
 // its own parameters and the REVERSED feature gradient added to MSIG_WS_DFEAT — in ONE launch between the head and the GRU backward
 // of a fused train step.
 #include "msig_dev.h"
+#include "head_mlp.h"
 
 // ------------------------------------------------------------------------------------
 // One workgroup of 256 threads per fold (blockIdx.z), B <= MSIG_DA_MAX_BATCH rows, the thread map of head_epoch_kernel
-// (finetune.hip): D's 9.3 k floats sit in LDS for the call, every element of W0 / b0 / W3 / b3 has ONE owner thread that accumulates
-// its gradient over the rows in batch order and applies Adam,
+// (finetune.hip) and the classifier's pieces (head_mlp.h): D's 9.3 k floats sit in LDS for the call, every element of W0 / b0 /
+// W3 / b3 has ONE owner thread that accumulates its gradient over the rows in batch order and applies Adam,
 //   W0 (64,128): thread (kcol = tid & 127, half = tid >> 7) owns rows half * 32 + j, j < 32, of column kcol; TRANSPOSED in LDS,
 //                W0t[k * 65 + v]: the forward (lane = v), the owners and the feature gradient (lane = k, stride 65) all reach it
 //                without a bank conflict;
@@ -18,8 +19,6 @@
 // waves; the launch is bound by its seven barriers per chunk, the serial FMA chains between them and the global round trip of D and
 // its moments — 81 us at B = 64, 58 us without the feature gradient — which the matrix pipes would not shorten.
 // ------------------------------------------------------------------------------------
-#define DA_ROWS 16
-#define DA_W0S 65
 #define DA_W3S 65      // the logits' lanes are (row, class): classes of a row 65 floats apart sit in different banks
 
 __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const float* __restrict__ feat, float* __restrict__ dfeat,
@@ -39,15 +38,15 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
   float* W3 = b0 + 64;
   float* b3 = W3 + S * 64;
 
-  __shared__ float W0t[128 * DA_W0S];
+  __shared__ float W0t[128 * W0T_S];
   __shared__ float W3s[MSIG_MAX_K * DA_W3S];
   __shared__ float b0s[64];
   __shared__ float b3s[MSIG_MAX_K];
-  __shared__ __attribute__((aligned(16))) float fs[DA_ROWS * 128];
-  __shared__ float hs[DA_ROWS * 64];
-  __shared__ float dps[DA_ROWS * 64];
-  __shared__ float dls[DA_ROWS * MSIG_MAX_K];
-  __shared__ float lgs[DA_ROWS * MSIG_MAX_K];
+  __shared__ __attribute__((aligned(16))) float fs[HEAD_ROWS * 128];
+  __shared__ float hs[HEAD_ROWS * 64];
+  __shared__ float dps[HEAD_ROWS * 64];
+  __shared__ float dls[HEAD_ROWS * MSIG_MAX_K];
+  __shared__ float lgs[HEAD_ROWS * MSIG_MAX_K];
   __shared__ int ds[MSIG_DA_MAX_BATCH];
   __shared__ double rowloss[MSIG_DA_MAX_BATCH];
   __shared__ float rowok[MSIG_DA_MAX_BATCH];
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
 
   // ---- D: global -> LDS ----
 #pragma unroll
-  for (int j = 0; j < 32; ++j) W0t[kcol * DA_W0S + half * 32 + j] = W0[(half * 32 + j) * 128 + kcol];
+  for (int j = 0; j < 32; ++j) W0t[kcol * W0T_S + half * 32 + j] = W0[(half * 32 + j) * 128 + kcol];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int i = tid + 256 * j;
@@ -85,34 +84,18 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
   if (tid < 64) b0s[tid] = b0[tid];
   if (tid < S) b3s[tid] = b3[tid];
 
-  float dW0acc[32];
-#pragma unroll
-  for (int j = 0; j < 32; ++j) dW0acc[j] = 0.f;
-  float dW3acc[4] = {0.f, 0.f, 0.f, 0.f};
-  float db0acc = 0.f, db3acc = 0.f;
+  HEAD_GRADS_ZERO
   const float lambda = a.lambda[z], nlambda = -lambda;
   __syncthreads();
 
 #pragma unroll 1
-  for (int r0 = 0; r0 < B; r0 += DA_ROWS) {
-    // ---- 16 rows of features ----
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int i4 = tid + 256 * q, rl = i4 >> 5, c4 = i4 & 31, row = r0 + rl;
-      float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < B) val = ((const float4*)(feat + (size_t)row * 128))[c4];
-      ((float4*)fs)[i4] = val;
-    }
+  for (int r0 = 0; r0 < B; r0 += HEAD_ROWS) {
+    HEAD_STAGE_ROWS4(feat + (size_t)row * 128, r0, B)
     __syncthreads();
     // ---- h = relu(f W0^T + b0) ----
     {
       const float bv = b0s[v];
-      float acc[4] = {bv, bv, bv, bv};
-      for (int k = 0; k < 128; ++k) {
-        const float wv = W0t[k * DA_W0S + v];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] += wv * fs[(rg * 4 + r) * 128 + k];
-      }
+      HEAD_HIDDEN_CHAIN(acc, W0t, bv)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = r0 + rg * 4 + r;
@@ -121,15 +104,14 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
     }
     __syncthreads();
     // ---- z = h W3^T + b3 ----
-    for (int i = tid; i < DA_ROWS * S; i += 256) {
+    for (int i = tid; i < HEAD_ROWS * S; i += 256) {
       const int rl = i / S, c = i - rl * S;
-      float acc = b3s[c];
-      for (int vv = 0; vv < 64; ++vv) acc += W3s[c * DA_W3S + vv] * hs[rl * 64 + vv];
+      HEAD_LOGIT(acc, W3s, DA_W3S, b3s, c, rl)
       lgs[rl * MSIG_MAX_K + c] = acc;
     }
     __syncthreads();
     // ---- CrossEntropy against the row's own and its partner's domain label ----
-    if (tid < DA_ROWS) {
+    if (tid < HEAD_ROWS) {
       const int row = r0 + tid;
       if (row < B) {
         const float* lg = &lgs[tid * MSIG_MAX_K];
@@ -151,40 +133,14 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
       }
     }
     __syncthreads();
-    // ---- dpre = relu'(h) * (dz W3) ----
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rl = rg * 4 + r;
-      float acc = 0.f;
-      for (int c = 0; c < S; ++c) acc += W3s[c * DA_W3S + v] * dls[rl * MSIG_MAX_K + c];
-      dps[rl * 64 + v] = hs[rl * 64 + v] > 0.f ? acc : 0.f;
-    }
+    HEAD_DPRE(W3s, DA_W3S, S, a)                 // dpre = relu'(h) * (dz W3)
     __syncthreads();
-    // ---- the owners' gradient chains over the chunk's rows ----
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = tid + 256 * j;
-      if (i < S * 64) {
-        const int c = i >> 6, vv = i & 63;
-        float acc = 0.f;
-#pragma unroll 4
-        for (int rl = 0; rl < DA_ROWS; ++rl) acc += dls[rl * MSIG_MAX_K + c] * hs[rl * 64 + vv];
-        dW3acc[j] += acc;
-      }
-    }
-    if (tid < S) { float acc = 0.f; for (int rl = 0; rl < DA_ROWS; ++rl) acc += dls[rl * MSIG_MAX_K + tid]; db3acc += acc; }
-    if (tid < 64) { float acc = 0.f; for (int rl = 0; rl < DA_ROWS; ++rl) acc += dps[rl * 64 + tid]; db0acc += acc; }
-#pragma unroll 1
-    for (int rl = 0; rl < DA_ROWS; ++rl) {
-      const float fv = fs[rl * 128 + kcol];
-#pragma unroll
-      for (int j = 0; j < 32; ++j) dW0acc[j] += dps[rl * 64 + half * 32 + j] * fv;
-    }
+    HEAD_GRADS_ADD(S)                            // the owners' gradient chains over the chunk's rows
     // ---- g = dpre W0 through the parameters as found; dfeat += -lambda g, two roundings ----
     if (lambda != 0.f) {
       float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       for (int vv = 0; vv < 64; ++vv) {
-        const float wv = W0t[kcol * DA_W0S + vv];
+        const float wv = W0t[kcol * W0T_S + vv];
 #pragma unroll
         for (int r = 0; r < 8; ++r) g[r] += wv * dps[(half * 8 + r) * 64 + vv];
       }
@@ -211,33 +167,27 @@ __global__ __launch_bounds__(256) void da_step_kernel(const DaArgs a, const floa
   // ---- Adam, every element by its owner, in the forms these sites have always been compiled to (msig_dev.h AdamForm): parameters
   // and moments written back ----
   const float lrb = a.lr_over_bc1[z], isb = a.inv_sqrt_bc2[z];
+  // parameter DST, with its moments at element `at` of theirs, from its LDS value P and its gradient G, by its owner
+#define DA_OWNER_ADAM(FORM, DST, at, P, G)                                                                                 \
+  {                                                                                                                    \
+    float m = ea[at], s = eas[at];                                                                                     \
+    DST = adam_update<FORM>(P, G, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);                                            \
+    ea[at] = m; eas[at] = s;                                                                                           \
+  }
 #pragma unroll
   for (int j = 0; j < 32; ++j) {
     const int i = (half * 32 + j) * 128 + kcol;
-    float m = ea[i], s = eas[i];
-    W0[i] = adam_update<ADAM_FUSED_V>(W0t[kcol * DA_W0S + half * 32 + j], dW0acc[j], m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
-    ea[i] = m; eas[i] = s;
+    DA_OWNER_ADAM(ADAM_FUSED_V, W0[i], i, W0t[kcol * W0T_S + half * 32 + j], dW0acc[j])
   }
   const int64_t o3 = W3 - W0, ob0 = b0 - W0, ob3 = b3 - W0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int i = tid + 256 * j;
-    if (i < S * 64) {
-      float m = ea[o3 + i], s = eas[o3 + i];
-      W3[i] = adam_update<ADAM_FUSED_G>(W3s[(i >> 6) * DA_W3S + (i & 63)], dW3acc[j], m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
-      ea[o3 + i] = m; eas[o3 + i] = s;
-    }
+    if (i < S * 64) DA_OWNER_ADAM(ADAM_FUSED_G, W3[i], o3 + i, W3s[(i >> 6) * DA_W3S + (i & 63)], dW3acc[j])
   }
-  if (tid < 64) {
-    float m = ea[ob0 + tid], s = eas[ob0 + tid];
-    b0[tid] = adam_update<ADAM_FUSED_G>(b0s[tid], db0acc, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
-    ea[ob0 + tid] = m; eas[ob0 + tid] = s;
-  }
-  if (tid < S) {
-    float m = ea[ob3 + tid], s = eas[ob3 + tid];
-    b3[tid] = adam_update<ADAM_FUSED_G>(b3s[tid], db3acc, m, s, lrb, isb, a.b1, a.b2, a.eps, a.wd);
-    ea[ob3 + tid] = m; eas[ob3 + tid] = s;
-  }
+  if (tid < 64) DA_OWNER_ADAM(ADAM_FUSED_G, b0[tid], ob0 + tid, b0s[tid], db0acc)
+  if (tid < S) DA_OWNER_ADAM(ADAM_FUSED_G, b3[tid], ob3 + tid, b3s[tid], db3acc)
+#undef DA_OWNER_ADAM
   __syncthreads();
   if (tid == 0 && stats) {
     double ls = 0.0, cs = 0.0, cn = 0.0;

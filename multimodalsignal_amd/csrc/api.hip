@@ -821,11 +821,7 @@ extern "C" int msig_mc_tail(const msig_batch* b, int32_t kind, void* stream) {
 }
 
 extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {
-  const uint32_t lo = (uint32_t)(seed & 0xFFFFFFFFu), hi = (uint32_t)(seed >> 32);
-  const uint32_t a = (uint32_t)((step * 0x9E3779B9ull) & 0xFFFFFFFFull);
-  const uint32_t b = (uint32_t)(((uint64_t)stream_id * 0x7F4A7C15ull) & 0xFFFFFFFFull);
-  const uint32_t inner = fmix32(a + b + hi);
-  return fmix32(lo ^ inner);
+  return dropout_key(seed, step, stream_id);
 }
 
 extern "C" int msig_gather_windows(const float* store, const int64_t* store_labels, const int64_t* idx, int32_t B,

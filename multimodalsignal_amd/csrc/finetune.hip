@@ -2,6 +2,7 @@
 // consecutive classifier-only train steps on cached features in ONE launch (few-shot subject calibration).
 #include "msig_dev.h"
 #include "finetune.h"
+#include "head_mlp.h"
 
 // ------------------------------------------------------------------------------------
 // MSIG_WS_FEAT (B,128) of fold z -> out + z * out_stride
@@ -30,27 +31,18 @@ int launch_ft_feat_copy(const float* feat, float* out, int64_t out_stride_bytes,
 //                accumulator map); kept TRANSPOSED in LDS, W0t[k * 65 + v], which the forward (lane = v) and the owners
 //                (lane = k, stride 65) both reach without a bank conflict;
 //   W3 (K,64)  : thread tid owns elements tid + 256 * j, j < 4;   b0: tid < 64;   b3: tid < K.
-// A step's rows run through the statements of head_fwd_kernel / ce_kernel / head_bwd_kernel in chunks of 16 rows, in batch order:
-// a weight-gradient element is the chain  acc += dps[row] * feat[row]  over the step's rows 0, 1, 2, ... — one fixed order.  The
-// loss and the class-weight total are fp64 sums in ce_kernel's / cw_total's order for a batch of <= 256 rows (lane = row, wave
-// reduction, the four wave sums in wave order).  Nothing depends on the number of steps, on the position of a step inside the
-// call or on the folds beside it.  Plain fp32 FMA, no MFMA: a step's contractions are 2 x 131 k multiply-adds per 16 rows — about
+// A step's rows run through head_mlp.h's pieces — the text head_fwd_kernel / ce_kernel / head_bwd_kernel expand — in chunks of 16
+// rows, in batch order: a weight-gradient element is the chain  acc += dps[row] * feat[row]  over the step's rows 0, 1, 2, ... —
+// one fixed order.  The loss and the class-weight total are fp64 sums in ce_kernel's / cw_total's order for a batch of <= 256 rows
+// (lane = row, wave reduction, the four wave sums in wave order).  Nothing depends on the number of steps, on the position of a
+// step inside the call or on the folds beside it.  Plain fp32 FMA, no MFMA: a step's contractions are 2 x 131 k multiply-adds per 16 rows — about
 // a microsecond on four waves — beside six barriers; the matrix pipes would shorten only that microsecond, at the price of
 // fragment shuffles through LDS for operands that are already there in the layout the VALU wants.
 // ------------------------------------------------------------------------------------
-#define FT_ROWS 16
-#define FT_W0S 65
-
 __device__ __forceinline__ double ft_powi(double b, int64_t e) {      // b^e by squaring: a function of (b, e) alone
   double r = 1.0;
   while (e > 0) { if (e & 1) r *= b; b *= b; e >>= 1; }
   return r;
-}
-__device__ __forceinline__ uint32_t ft_dropout_key(uint64_t seed, uint64_t step) {      // msig_dropout_key(seed, step, 2) (api.hip)
-  const uint32_t lo = (uint32_t)(seed & 0xFFFFFFFFu), hi = (uint32_t)(seed >> 32);
-  const uint32_t a = (uint32_t)((step * 0x9E3779B9ull) & 0xFFFFFFFFull);
-  const uint32_t b = (uint32_t)((2ull * 0x7F4A7C15ull) & 0xFFFFFFFFull);
-  return fmix32(lo ^ fmix32(a + b + hi));
 }
 
 template <bool CW>
@@ -68,16 +60,16 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
   float* b3 = W3 + (K * 64 + 3) / 4 * 4;
   const int64_t om = W0 - params;      // the moments' tensors sit at the same offsets
 
-  __shared__ float W0t[128 * FT_W0S];
+  __shared__ float W0t[128 * W0T_S];
   __shared__ float W3s[MSIG_MAX_K * 64];
   __shared__ float b0s[64];
   __shared__ float b3s[MSIG_MAX_K];
   __shared__ float cws[MSIG_MAX_K];
-  __shared__ __attribute__((aligned(16))) float fs[FT_ROWS * 128];
-  __shared__ float hs[FT_ROWS * 64];
-  __shared__ float dps[FT_ROWS * 64];
-  __shared__ float dls[FT_ROWS * MSIG_MAX_K];
-  __shared__ float lgs[FT_ROWS * MSIG_MAX_K];
+  __shared__ __attribute__((aligned(16))) float fs[HEAD_ROWS * 128];
+  __shared__ float hs[HEAD_ROWS * 64];
+  __shared__ float dps[HEAD_ROWS * 64];
+  __shared__ float dls[HEAD_ROWS * MSIG_MAX_K];
+  __shared__ float lgs[HEAD_ROWS * MSIG_MAX_K];
   __shared__ int idxs[MSIG_FT_MAX_BATCH];
   __shared__ int ys[MSIG_FT_MAX_BATCH];
   __shared__ double rowloss[MSIG_FT_MAX_BATCH];
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
 #pragma unroll
   for (int j = 0; j < 32; ++j) {
     const int i = (half * 32 + j) * 128 + kcol;
-    W0t[kcol * FT_W0S + half * 32 + j] = W0[i];
+    W0t[kcol * W0T_S + half * 32 + j] = W0[i];
     m0[j] = ea[om + i]; v0[j] = eas[om + i];
   }
 #pragma unroll
@@ -116,7 +108,7 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
     const int pos0 = (h.first_step + s) * h.batch;
     const int nb = min(h.batch, h.n_order - pos0);
     const int64_t t = ff.step0[fold] + s;
-    const uint32_t key = ft_dropout_key(ff.seed[fold], (uint64_t)t);
+    const uint32_t key = dropout_key(ff.seed[fold], (uint64_t)t, 2);
     // ---- the step's rows and labels; W = sum_b w[y_b] in cw_total's order ----
     if (tid < nb) {
       const int r = min(max(order[pos0 + tid], 0), h.N - 1);
@@ -138,54 +130,33 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
     const double bc1 = 1.0 - ft_powi((double)h.beta1, t), bc2 = 1.0 - ft_powi((double)h.beta2, t);
     const float lr_over_bc1 = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
 
-    float dW0acc[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) dW0acc[j] = 0.f;
-    float dW3acc[4] = {0.f, 0.f, 0.f, 0.f};
-    float db0acc = 0.f, db3acc = 0.f;
+    HEAD_GRADS_ZERO
     __syncthreads();                     // idxs / ys are written; the previous step's parameter update is visible
 
 #pragma unroll 1
-    for (int r0 = 0; r0 < nb; r0 += FT_ROWS) {
-      // ---- gather 16 rows of features ----
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int i4 = tid + 256 * q, rl = i4 >> 5, c4 = i4 & 31, row = r0 + rl;
-        float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < nb) val = ((const float4*)(feat + (size_t)idxs[row] * 128))[c4];
-        ((float4*)fs)[i4] = val;
-      }
+    for (int r0 = 0; r0 < nb; r0 += HEAD_ROWS) {
+      HEAD_STAGE_ROWS4(feat + (size_t)idxs[row] * 128, r0, nb)
       __syncthreads();
       // ---- head_fwd_kernel ----
       {
         const float bv = b0s[v];
-        float acc[4] = {bv, bv, bv, bv};
-        for (int k = 0; k < 128; ++k) {
-          const float wv = W0t[k * FT_W0S + v];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[r] += wv * fs[(rg * 4 + r) * 128 + k];
-        }
+        HEAD_HIDDEN_CHAIN(acc, W0t, bv)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = r0 + rg * 4 + r;
-          float hv = acc[r] > 0.f ? acc[r] : 0.f;
-          if (thr > 0) {
-            const uint32_t e = (uint32_t)row * 64u + (uint32_t)v;
-            hv *= drop_mul(drop_word(e, key), e & 3, thr, dscale);
-          }
-          hs[(rg * 4 + r) * 64 + v] = row < nb ? hv : 0.f;       // head_bwd_kernel reads hid as 0 for the rows past the batch
+          HEAD_RELU_DROPOUT(hv, acc[r], row, thr, key, dscale)
+          hs[(rg * 4 + r) * 64 + v] = row < nb ? hv : 0.f;       // the backward pieces read hid as 0 for the rows past the batch
         }
       }
       __syncthreads();
-      for (int i = tid; i < FT_ROWS * K; i += 256) {
+      for (int i = tid; i < HEAD_ROWS * K; i += 256) {
         const int rl = i / K, c = i - rl * K;
-        float a = b3s[c];
-        for (int vv = 0; vv < 64; ++vv) a += W3s[c * 64 + vv] * hs[rl * 64 + vv];
+        HEAD_LOGIT(a, W3s, 64, b3s, c, rl)
         lgs[rl * MSIG_MAX_K + c] = a;
       }
       __syncthreads();
       // ---- ce_kernel, the rows of this chunk ----
-      if (tid < FT_ROWS) {
+      if (tid < HEAD_ROWS) {
         const int row = r0 + tid;
         if (row < nb) {
           const float* lg = &lgs[tid * MSIG_MAX_K];
@@ -193,15 +164,11 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
           const float lse = ce_row_lse(lg, K, am);
           const int y = ys[row];
           const float wy = cws[y];
-          if constexpr (CW) rowloss[row] = (double)wy * (double)(lse - lg[y]);
-          else rowloss[row] = (double)(lse - lg[y]);
+          rowloss[row] = HEAD_CE_ROW_LOSS(lg, lse, y, wy);
           rowok[row] = (am == y) ? 1.f : 0.f;
           for (int c = 0; c < K; ++c) {
             const float p = expf(lg[c] - lse);
-            float dl;
-            if constexpr (CW) dl = (wy * (p - (c == y ? 1.f : 0.f))) * inv;
-            else dl = (p - (c == y ? 1.f : 0.f)) * inv;
-            dls[tid * MSIG_MAX_K + c] = dl;
+            dls[tid * MSIG_MAX_K + c] = HEAD_CE_DL(p, c, y, wy, inv);
           }
         } else {
           for (int c = 0; c < K; ++c) dls[tid * MSIG_MAX_K + c] = 0.f;
@@ -209,33 +176,9 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
       }
       __syncthreads();
       // ---- head_bwd_kernel, without dfeat (the extractor is frozen) ----
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rl = rg * 4 + r;
-        float a = 0.f;
-        for (int c = 0; c < K; ++c) a += W3s[c * 64 + v] * dls[rl * MSIG_MAX_K + c];
-        dps[rl * 64 + v] = hs[rl * 64 + v] > 0.f ? a * dscale_bwd : 0.f;
-      }
+      HEAD_DPRE(W3s, 64, K, a * dscale_bwd)
       __syncthreads();
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int idx = tid + 256 * j;
-        if (idx < K * 64) {
-          const int c = idx >> 6, vv = idx & 63;
-          float a = 0.f;
-#pragma unroll 4
-          for (int rl = 0; rl < FT_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + c] * hs[rl * 64 + vv];
-          dW3acc[j] += a;
-        }
-      }
-      if (tid < K) { float a = 0.f; for (int rl = 0; rl < FT_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + tid]; db3acc += a; }
-      if (tid < 64) { float a = 0.f; for (int rl = 0; rl < FT_ROWS; ++rl) a += dps[rl * 64 + tid]; db0acc += a; }
-#pragma unroll 1
-      for (int rl = 0; rl < FT_ROWS; ++rl) {
-        const float fv = fs[rl * 128 + kcol];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) dW0acc[j] += dps[rl * 64 + half * 32 + j] * fv;
-      }
+      HEAD_GRADS_ADD(K)
       __syncthreads();                   // the next chunk overwrites fs / hs / dps / dls
     }
 
@@ -248,7 +191,7 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
     // ---- Adam, every element by its owner, in the forms these sites have always been compiled to (msig_dev.h AdamForm) ----
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
-      float* p = &W0t[kcol * FT_W0S + half * 32 + j];
+      float* p = &W0t[kcol * W0T_S + half * 32 + j];
       *p = adam_update<ADAM_FUSED_V>(*p, dW0acc[j], m0[j], v0[j], lr_over_bc1, inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.weight_decay);
     }
 #pragma unroll
@@ -272,7 +215,7 @@ __global__ __launch_bounds__(256) void head_epoch_kernel(const msig_ft_head h, c
 #pragma unroll
   for (int j = 0; j < 32; ++j) {
     const int i = (half * 32 + j) * 128 + kcol;
-    W0[i] = W0t[kcol * FT_W0S + half * 32 + j];
+    W0[i] = W0t[kcol * W0T_S + half * 32 + j];
     ea[om + i] = m0[j]; eas[om + i] = v0[j];
   }
 #pragma unroll

@@ -2,11 +2,10 @@
 // eval-time softmax/argmax (trainer.py:224-225), Adam (trainer.py:68,149) and the small
 // utility kernels (partial-sum reduction, window gather).  These stages are <0.1 % of the
 // FLOPs, so they are plain VALU kernels; what matters is that they stay on the stream and
-// never force a host sync.
+// never force a host sync.  The classifier's statements themselves are head_mlp.h's.
 #include "msig_dev.h"
+#include "head_mlp.h"
 
-#define HEAD_ROWS 16
-#define W0T_S 65     // padded row stride of the transposed Linear(128,64) weight in LDS
 #define HEAD_WG 128
 
 // ------------------------------------------------------------------------------------
@@ -23,46 +22,26 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   __shared__ float fs[HEAD_ROWS * 128];
   __shared__ float hs[HEAD_ROWS * 64];
   const int tid = threadIdx.x;
-  for (int j0 = 0; j0 < 32; j0 += 8) {            // 32 KB of W0, transposed into LDS: eight loads in flight per thread (a plain loop is 32 round trips)
-    float q[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) q[u] = W0[tid + 256 * (j0 + u)];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const int i = tid + 256 * (j0 + u), v = i >> 7, k = i & 127; W0t[k * W0T_S + v] = q[u]; }
-  }
-  for (int i = tid; i < K * 64; i += 256) W3s[i] = W3[i];
+  HEAD_STAGE_WEIGHTS(W0, W3, K, W0t, W3s)
   const int ngroups = (B + HEAD_ROWS - 1) / HEAD_ROWS;
   const int v = tid & 63, rg = tid >> 6;
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int r0 = grp * HEAD_ROWS;
     __syncthreads();
-    for (int i = tid; i < HEAD_ROWS * 128; i += 256) {
-      const int row = r0 + (i >> 7);
-      fs[i] = row < B ? feat[(size_t)row * 128 + (i & 127)] : 0.f;
-    }
+    HEAD_STAGE_ROWS(feat, r0, B)
     __syncthreads();
-    float acc[4] = {b0[v], b0[v], b0[v], b0[v]};
-    for (int k = 0; k < 128; ++k) {
-      const float wv = W0t[k * W0T_S + v];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] += wv * fs[(rg * 4 + r) * 128 + k];
-    }
+    HEAD_HIDDEN_CHAIN(acc, W0t, b0[v])
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = r0 + rg * 4 + r;
-      float hv = acc[r] > 0.f ? acc[r] : 0.f;
-      if (drop_thr > 0) {
-        const uint32_t e = (uint32_t)row * 64u + (uint32_t)v;
-        hv *= drop_mul(drop_word(e, drop_key), e & 3, drop_thr, dscale);
-      }
+      HEAD_RELU_DROPOUT(hv, acc[r], row, drop_thr, drop_key, dscale)
       hs[(rg * 4 + r) * 64 + v] = hv;
       if (row < B) hid[(size_t)row * 64 + v] = hv;
     }
     __syncthreads();
     for (int i = tid; i < HEAD_ROWS * K; i += 256) {
       const int rl = i / K, c = i - rl * K, row = r0 + rl;
-      float a = b3[c];
-      for (int vv = 0; vv < 64; ++vv) a += W3s[c * 64 + vv] * hs[rl * 64 + vv];
+      HEAD_LOGIT(a, W3s, 64, b3, c, rl)
       if (row < B) logits[(size_t)row * K + c] = a;
     }
   }
@@ -85,59 +64,49 @@ __device__ __forceinline__ double cw_total(const float* __restrict__ cw, const i
   return (red4[0] + red4[1]) + (red4[2] + red4[3]);
 }
 
-// Soft targets (include/msig_st.h): label smoothing eps of the launch and the mixup weight lam of each fold, the
-// partner of row b being row B-1-b.  ST is one more flag beside CW on ce_kernel / head_step_kernel / loss_finalize (and on the two
-// kernels the finalizer rides in); the ST = false instantiations take an empty SoftT and are what they were.  A fold with eps = 0
-// and lam = 1 (`plain`, uniform per fold) runs the plain statements, so its bits are the plain kernel's whatever its companions
-// use.  Every operation of the soft statements is one rounding (contraction off): ce_kernel and head_step_kernel + loss_finalize
-// agree in every bit because they share these functions, not because the compiler happens to fuse alike.
+// Soft targets (head_mlp.h): ST is one more flag beside CW on ce_kernel / head_step_kernel / loss_finalize (and on the two kernels
+// the finalizer rides in); the ST = false instantiations take an empty SoftT and are what they were.  ce_kernel and
+// head_step_kernel + loss_finalize agree in every bit because they share head_mlp.h's statements, not because the compiler happens to fuse alike.
 template <bool ST> struct SoftT {};
 template <> struct SoftT<true> { SoftArgs a; };
-struct SoftCoef { bool plain; float a1, a2, ek, wsum; double d1, d2, dk; };
-template <bool CW>
-__device__ __forceinline__ SoftCoef soft_coef(float eps, float lam, const float* __restrict__ cw, int K) {
-#pragma clang fp contract(off)
-  SoftCoef s;
-  s.plain = eps == 0.f && lam == 1.f;
-  const float om = 1.f - eps;
-  s.a1 = om * lam; s.a2 = om * (1.f - lam); s.ek = eps / (float)K;
-  const double de = (double)eps, dl = (double)lam, dom = 1.0 - de;
-  s.d1 = dom * dl; s.d2 = dom * (1.0 - dl); s.dk = de / (double)K;
-  s.wsum = (float)K;
-  if constexpr (CW) { float t = 0.f; for (int c = 0; c < K; ++c) t = t + cw[c]; s.wsum = t; }
-  return s;
+// what a launch's CrossEntropy rows share: W (class weights: cw_total's; else B, read when ST) and the fold's soft-target terms
+template <bool CW, bool ST>
+struct CeCtx { double W = 0.0; SoftCoef sc{}; bool soft = false; };
+template <bool CW, bool ST>
+__device__ __forceinline__ CeCtx<CW, ST> ce_ctx(const float* cw, const int64_t* labels, int B, int K, double* wred, const SoftT<ST>& sa, int fold) {
+  CeCtx<CW, ST> x;
+  if constexpr (CW) x.W = cw_total(cw, labels, B, wred);
+  if constexpr (ST) {
+    x.sc = soft_coef<CW>(sa.a.eps, sa.a.lam[fold], cw, K);
+    x.soft = !x.sc.plain;
+    if constexpr (!CW) x.W = (double)B;
+  }
+  return x;
 }
-// one row's term of the loss sum, fp64: (1-eps)(lam w[y] l(y) + (1-lam) w[y'] l(y')) + (eps/K) sum_c w_c l(c), l(c) = lse - lg[c]
-template <bool CW>
-__device__ __forceinline__ double soft_row_loss(const SoftCoef& s, const float* lg, float lse, int y, int y2, const float* __restrict__ cw, int K) {
-#pragma clang fp contract(off)
-  const double wy = CW ? (double)cw[y] : 1.0, wy2 = CW ? (double)cw[y2] : 1.0;
-  double all = 0.0;
-  for (int c = 0; c < K; ++c) all = all + (CW ? (double)cw[c] : 1.0) * (double)(lse - lg[c]);
-  const double own = (s.d1 * wy) * (double)(lse - lg[y]);
-  const double par = (s.d2 * wy2) * (double)(lse - lg[y2]);
-  return (own + par) + s.dk * all;
-}
-// dL/dz[b][c] of the same, fp32
-__device__ __forceinline__ float soft_dlogit(const SoftCoef& s, float p, int c, int y, int y2, float wy, float wy2, float wc, float invW) {
-#pragma clang fp contract(off)
-  const float own = (s.a1 * wy) * (p - (c == y ? 1.f : 0.f));
-  const float par = (s.a2 * wy2) * (p - (c == y2 ? 1.f : 0.f));
-  const float sm = s.ek * (p * s.wsum - wc);
-  return ((own + par) + sm) * invW;
+// thread 0's tail of the loss: the sixteen wave sums in order, then lossbuf[0] = mean loss of this batch; lossbuf[1] = summed loss
+// of this batch (loss.item() * B, trainer.py:152,221); lossbuf[2] = #correct of this batch — plain stores, no running sums: layouts
+// of different batch sizes alias one pooled workspace, and the epoch sums live with the caller (lacc: msig_batch.loss_acc, the
+// caller's running sums of a pass; one thread, stream order).
+#define CE_THREADS 1024
+template <bool WEIGHTED>
+__device__ __forceinline__ void loss_tail(const double (*red)[CE_THREADS / 64], int B, double W, float* __restrict__ lossbuf, double* __restrict__ lacc) {
+  double ls = 0.0, cs = 0.0;
+  for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
+  const double sum = WEIGHTED ? ls * ((double)B / W) : ls;
+  lossbuf[0] = (float)(ls / (WEIGHTED ? W : (double)B));
+  lossbuf[1] = (float)sum;
+  lossbuf[2] = (float)cs;
+  if (lacc) { lacc[0] += sum; lacc[1] += cs; }
 }
 
 // ------------------------------------------------------------------------------------
 // CrossEntropy (mean), dlogits, softmax probabilities, argmax, accuracy counter.
 // Single workgroup (one deterministic sum) of CE_THREADS threads — with 256 the 32 rows per thread of a B = 8192 batch took 62 us,
-// all of it exp / log latency.  lossbuf[0] = mean loss of this batch;
-// lossbuf[1] = summed loss of this batch (loss.item() * B, trainer.py:152,221); lossbuf[2] = #correct of this batch — plain
-// stores, no running sums: layouts of different batch sizes alias one pooled workspace, and the epoch sums live with the caller.
+// all of it exp / log latency.
 // CW = class weights w (K floats, include/msig_cw.h; torch's CrossEntropyLoss(weight=w)): row b's terms carry w[y_b], the mean
 // divides by W = sum_b w[y_b] (cw_total) instead of B, and lossbuf[1] / loss_acc[0] get B times that mean.  Arranged so that w = 1
 // reproduces the unweighted instantiation's bits: W = B exactly, w_y * v = v, ls * (B / W) = ls.
 // ------------------------------------------------------------------------------------
-#define CE_THREADS 1024
 template <bool CW, bool ST = false>
 __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                  float* __restrict__ probs, int* __restrict__ pred,
@@ -145,92 +114,36 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict_
                                                  const float* __restrict__ cw, int B, int K, const FoldCtx fc, const SoftT<ST> sa) {
   FOLD_BEGIN; FS(logits); FS(labels); FS(probs); FS(pred); FS(dlogits); FS(lossbuf); FS(lacc);
   __shared__ double red[2][CE_THREADS / 64];
+  __shared__ double wred[4];
   const int tid = threadIdx.x;
   double lsum = 0.0, correct = 0.0;
-  float invB = 1.0f / (float)B;
-  double W = 0.0;
-  if constexpr (CW) {
-    __shared__ double wred[4];
-    FS(cw);
-    W = cw_total(cw, labels, B, wred);
-    invB = 1.0f / (float)W;
-  }
-  SoftCoef sc{};
-  bool soft = false;
-  if constexpr (ST) {
-    sc = soft_coef<CW>(sa.a.eps, sa.a.lam[blockIdx.z], cw, K);
-    soft = !sc.plain;
-    if constexpr (!CW) W = (double)B;
-  }
+  if constexpr (CW) FS(cw);
+  const CeCtx<CW, ST> x = ce_ctx<CW, ST>(cw, labels, B, K, wred, sa, blockIdx.z);
+  const float inv = 1.0f / (CW ? (float)x.W : (float)B);
   for (int row = tid; row < B; row += CE_THREADS) {
-    const float* lg = logits + (size_t)row * K;
+    const int y = (int)labels[row], y2 = x.soft ? (int)labels[B - 1 - row] : y;
     int am;
-    const float lse = ce_row_lse(lg, K, am);
-    const int y = (int)labels[row];
-    const float wy = CW ? cw[y] : 1.f;
-    if constexpr (ST) {
-      if (soft) {                                 // uniform per fold: the soft-target statements of this row, then the next row
-        const int y2 = (int)labels[B - 1 - row];
-        const float wy2 = CW ? cw[y2] : 1.f;
-        lsum += soft_row_loss<CW>(sc, lg, lse, y, y2, cw, K);
-        correct += (am == y) ? 1.0 : 0.0;
-        pred[row] = am;
-        for (int c = 0; c < K; ++c) {
-          const float p = expf(lg[c] - lse);
-          probs[(size_t)row * K + c] = p;
-          if (dlogits) dlogits[(size_t)row * K + c] = soft_dlogit(sc, p, c, y, y2, wy, wy2, CW ? cw[c] : 1.f, invB);
-        }
-        continue;
-      }
-    }
-    if constexpr (CW) lsum += (double)wy * (double)(lse - lg[y]);
-    else lsum += (double)(lse - lg[y]);
-    correct += (am == y) ? 1.0 : 0.0;
-    pred[row] = am;
-    for (int c = 0; c < K; ++c) {
-      const float p = expf(lg[c] - lse);
+    lsum += ce_row_terms<CW, ST>(logits + (size_t)row * K, K, y, y2, cw, inv, x.soft, x.sc, am, [&](int c, float p, float dl) {
       probs[(size_t)row * K + c] = p;
-      if constexpr (CW) { if (dlogits) dlogits[(size_t)row * K + c] = (wy * (p - (c == y ? 1.f : 0.f))) * invB; }
-      else { if (dlogits) dlogits[(size_t)row * K + c] = (p - (c == y ? 1.f : 0.f)) * invB; }
-    }
+      if (dlogits) dlogits[(size_t)row * K + c] = dl;
+    });
+    pred[row] = am;
+    correct += (am == y) ? 1.0 : 0.0;
   }
   lsum = wave_sum_d(lsum); correct = wave_sum_d(correct);
   if ((tid & 63) == 0) { red[0][tid >> 6] = lsum; red[1][tid >> 6] = correct; }
   __syncthreads();
-  if (tid == 0) {
-    double ls = 0.0, cs = 0.0;
-    for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
-    if constexpr (CW || ST) {
-      const double sum = ls * ((double)B / W);
-      lossbuf[0] = (float)(ls / W);
-      lossbuf[1] = (float)sum;
-      lossbuf[2] = (float)cs;
-      if (lacc) { lacc[0] += sum; lacc[1] += cs; }
-    } else {
-      lossbuf[0] = (float)(ls / (double)B);
-      lossbuf[1] = (float)ls;
-      lossbuf[2] = (float)cs;
-      if (lacc) { lacc[0] += ls; lacc[1] += cs; }      // msig_batch.loss_acc: the caller's running sums of a pass (one thread, stream order)
-    }
-  }
+  if (tid == 0) loss_tail<CW || ST>(red, B, x.W, lossbuf, lacc);
 }
 
 // The reduction half of ce_kernel for the fused head (head_step_kernel wrote pred / probs / dlogits; the loss and the accuracy
 // counter are sums over the whole batch): one workgroup of 256 threads plays ce_kernel's 1024 — virtual thread q * 256 + tid sums
 // the rows ce_kernel's thread of that index sums, each real wave reduces four virtual waves, thread 0 adds the sixteen wave sums in
-// ce_kernel's order.  Same values, same order: the loss is ce_kernel's, bit for bit (CW: with cw_total's W, as ce_kernel<true>).
+// ce_kernel's order.  Same values (ce_row_terms' return), same order, same tail: the loss is ce_kernel's, bit for bit.
 template <bool CW, bool ST = false>
 __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[CE_THREADS / 64], double* wred, const SoftT<ST>& sa, int fold) {
   const int tid = threadIdx.x;
-  double W = 0.0;
-  if constexpr (CW) W = cw_total(lf.cw, lf.labels, lf.B, wred);
-  SoftCoef sc{};
-  bool soft = false;
-  if constexpr (ST) {
-    sc = soft_coef<CW>(sa.a.eps, sa.a.lam[fold], lf.cw, lf.K);
-    soft = !sc.plain;
-    if constexpr (!CW) W = (double)lf.B;
-  }
+  const CeCtx<CW, ST> x = ce_ctx<CW, ST>(lf.cw, lf.labels, lf.B, lf.K, wred, sa, fold);
 #pragma unroll 1
   for (int q = 0; q < CE_THREADS / 256; ++q) {
     double lsum = 0.0, correct = 0.0;
@@ -239,31 +152,15 @@ __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[C
       int am;
       const float lse = ce_row_lse(lg, lf.K, am);
       const int y = (int)lf.labels[row];
-      if (ST && soft) lsum += soft_row_loss<CW>(sc, lg, lse, y, (int)lf.labels[lf.B - 1 - row], lf.cw, lf.K);
-      else if constexpr (CW) lsum += (double)lf.cw[y] * (double)(lse - lg[y]);
-      else lsum += (double)(lse - lg[y]);
+      if (ST && x.soft) lsum += soft_row_loss<CW>(x.sc, lg, lse, y, (int)lf.labels[lf.B - 1 - row], lf.cw, lf.K);
+      else lsum += HEAD_CE_ROW_LOSS(lg, lse, y, lf.cw[y]);
       correct += (am == y) ? 1.0 : 0.0;
     }
     lsum = wave_sum_d(lsum); correct = wave_sum_d(correct);
     if ((tid & 63) == 0) { red[0][q * 4 + (tid >> 6)] = lsum; red[1][q * 4 + (tid >> 6)] = correct; }
   }
   __syncthreads();
-  if (tid == 0) {
-    double ls = 0.0, cs = 0.0;
-    for (int i = 0; i < CE_THREADS / 64; ++i) { ls += red[0][i]; cs += red[1][i]; }
-    if constexpr (CW || ST) {
-      const double sum = ls * ((double)lf.B / W);
-      lf.lossbuf[0] = (float)(ls / W);
-      lf.lossbuf[1] = (float)sum;
-      lf.lossbuf[2] = (float)cs;
-      if (lf.lacc) { lf.lacc[0] += sum; lf.lacc[1] += cs; }
-    } else {
-      lf.lossbuf[0] = (float)(ls / (double)lf.B);
-      lf.lossbuf[1] = (float)ls;
-      lf.lossbuf[2] = (float)cs;
-      if (lf.lacc) { lf.lacc[0] += ls; lf.lacc[1] += cs; }
-    }
-  }
+  if (tid == 0) loss_tail<CW || ST>(red, lf.B, x.W, lf.lossbuf, lf.lacc);
 }
 
 // softmax + argmax only (no labels)
@@ -282,8 +179,7 @@ __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------
-// head backward: dlogits -> dW3, db3, dW0, db0 (per-workgroup partials) and dfeat
-// partial row layout: [dW0 64*128][db0 64][dW3 K*64][db3 K]
+// head backward: dlogits -> dW3, db3, dW0, db0 (per-workgroup partials, HEAD_PART_STORE's layout) and dfeat
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ feat,
                                                        const float* __restrict__ hid, const float* __restrict__ W0,
@@ -297,82 +193,32 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   __shared__ float dps[HEAD_ROWS * 64];
   __shared__ float dls[HEAD_ROWS * MSIG_MAX_K];
   const int tid = threadIdx.x;
-  for (int j0 = 0; j0 < 32; j0 += 8) {            // 32 KB of W0, transposed into LDS: eight loads in flight per thread (a plain loop is 32 round trips)
-    float q[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) q[u] = W0[tid + 256 * (j0 + u)];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const int i = tid + 256 * (j0 + u), v = i >> 7, k = i & 127; W0t[k * W0T_S + v] = q[u]; }
-  }
-  for (int i = tid; i < K * 64; i += 256) W3s[i] = W3[i];
-  float dW0acc[32];
-#pragma unroll
-  for (int j = 0; j < 32; ++j) dW0acc[j] = 0.f;
-  float dW3acc[4] = {0.f, 0.f, 0.f, 0.f};
-  float db0acc = 0.f, db3acc = 0.f;
+  HEAD_STAGE_WEIGHTS(W0, W3, K, W0t, W3s)
+  HEAD_GRADS_ZERO
   const int ngroups = (B + HEAD_ROWS - 1) / HEAD_ROWS;
   const int v = tid & 63, rg = tid >> 6, kcol = tid & 127, half = tid >> 7;
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int r0 = grp * HEAD_ROWS;
     __syncthreads();
-    for (int i = tid; i < HEAD_ROWS * 128; i += 256) { const int row = r0 + (i >> 7); fs[i] = row < B ? feat[(size_t)row * 128 + (i & 127)] : 0.f; }
+    HEAD_STAGE_ROWS(feat, r0, B)
     for (int i = tid; i < HEAD_ROWS * 64; i += 256) { const int row = r0 + (i >> 6); hs[i] = row < B ? hid[(size_t)row * 64 + (i & 63)] : 0.f; }
     for (int i = tid; i < HEAD_ROWS * K; i += 256) { const int row = r0 + i / K; dls[(i / K) * MSIG_MAX_K + (i % K)] = row < B ? dlogits[(size_t)row * K + (i % K)] : 0.f; }
     __syncthreads();
-    // d(pre-activation of Linear(128,64))
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rl = rg * 4 + r;
-      float a = 0.f;
-      for (int c = 0; c < K; ++c) a += W3s[c * 64 + v] * dls[rl * MSIG_MAX_K + c];
-      dps[rl * 64 + v] = hs[rl * 64 + v] > 0.f ? a * dscale : 0.f;
-    }
+    HEAD_DPRE(W3s, 64, K, a * dscale)
     __syncthreads();
-    // weight-gradient accumulation
-#pragma unroll
-    for (int j = 0; j < (msig_negctl_range == 3 ? 2 : 4); ++j) {
-      const int idx = tid + 256 * j;
-      if (idx < K * 64) {
-        const int c = idx >> 6, vv = idx & 63;
-        float a = 0.f;
-#pragma unroll 4
-        for (int rl = 0; rl < HEAD_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + c] * hs[rl * 64 + vv];
-        dW3acc[j] += a;
-      }
-    }
-    if (tid < K) { float a = 0.f; for (int rl = 0; rl < HEAD_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + tid]; db3acc += a; }
-    if (tid < 64) { float a = 0.f; for (int rl = 0; rl < HEAD_ROWS; ++rl) a += dps[rl * 64 + tid]; db0acc += a; }
-#pragma unroll 1
-    for (int rl = 0; rl < HEAD_ROWS; ++rl) {
-      const float fv = fs[rl * 128 + kcol];
-#pragma unroll
-      for (int j = 0; j < 32; ++j) dW0acc[j] += dps[rl * 64 + half * 32 + j] * fv;
-    }
-    // dfeat[row][k] = sum_v W0[v][k] dpre[row][v]; thread: column kcol, rows half*8..+8
-#pragma unroll 1
-    for (int r = 0; r < 8; ++r) {
-      const int rl = half * 8 + r, row = r0 + rl;
-      float a = 0.f;
-#pragma unroll 8
-      for (int vv = 0; vv < 64; ++vv) a += W0t[kcol * W0T_S + vv] * dps[rl * 64 + vv];
-      if (row < B) dfeat[(size_t)row * 128 + kcol] = a;
-    }
+    HEAD_GRADS_ADD(K)
+    HEAD_DFEAT(W0t, dfeat, r0, B)
   }
   float* P = part + (size_t)blockIdx.x * (64 * 128 + 64 + K * 64 + K);
-#pragma unroll
-  for (int j = 0; j < 32; ++j) P[(half * 32 + j) * 128 + kcol] = dW0acc[j];
-  if (tid < 64) P[64 * 128 + tid] = db0acc;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { const int idx = tid + 256 * j; if (idx < K * 64) P[64 * 128 + 64 + idx] = dW3acc[j]; }
-  if (tid < K) P[64 * 128 + 64 + K * 64 + tid] = db3acc;
+  HEAD_PART_STORE(P, K)
 }
 
 // ------------------------------------------------------------------------------------
 // The head of a fused train step at few windows, one launch instead of three (head_fwd, ce, head_bwd): a workgroup takes ONE
 // group of 16 rows through the classifier, its rows' CrossEntropy terms (dlogits need nothing but their own row) and the
 // backward pass, with the weights, the features, the hidden layer and dlogits staying in LDS.  What needs the whole batch — the
-// loss and the accuracy counter — is summed by loss_finalize in the step's last launch.  Every statement is the corresponding one
-// of head_fwd_kernel / ce_kernel / head_bwd_kernel: the step's bits are those of the three launches
+// loss and the accuracy counter — is summed by loss_finalize in the step's last launch.  The pieces are the ones head_fwd_kernel /
+// ce_kernel / head_bwd_kernel are made of (head_mlp.h, one text each): the step's bits are those of the three launches
 // (tests/test_parity_gpu.py::test_fused_step_equals_separate_calls_bit_for_bit).  grid = (B + 15) / 16 <= HEAD_WG workgroups, each
 // writing one partial row, as head_bwd_kernel does at that size.  CW: class-weighted CrossEntropy (ce_kernel<true>) — a row's dlogits
 // need the whole batch's W, which every workgroup sums itself over all B <= 2048 labels in cw_total's one order (no extra launch).
@@ -395,20 +241,10 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
   __shared__ float dls[HEAD_ROWS * MSIG_MAX_K];
   __shared__ float lgs[HEAD_ROWS * MSIG_MAX_K];
   const int tid = threadIdx.x;
-  for (int j0 = 0; j0 < 32; j0 += 8) {
-    float q[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) q[u] = W0[tid + 256 * (j0 + u)];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const int i = tid + 256 * (j0 + u), v = i >> 7, k = i & 127; W0t[k * W0T_S + v] = q[u]; }
-  }
-  for (int i = tid; i < K * 64; i += 256) W3s[i] = W3[i];
+  HEAD_STAGE_WEIGHTS(W0, W3, K, W0t, W3s)
   const int v = tid & 63, rg = tid >> 6, kcol = tid & 127, half = tid >> 7;
   const int r0 = blockIdx.x * HEAD_ROWS;
-  for (int i = tid; i < HEAD_ROWS * 128; i += 256) {
-    const int row = r0 + (i >> 7);
-    fs[i] = row < B ? feat[(size_t)row * 128 + (i & 127)] : 0.f;
-  }
+  HEAD_STAGE_ROWS(feat, r0, B)
   float invW = 0.f;
   if constexpr (CW) {
     __shared__ double wred[4];
@@ -418,20 +254,11 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
   __syncthreads();
   // ---- head_fwd_kernel ----
   {
-    float acc[4] = {b0[v], b0[v], b0[v], b0[v]};
-    for (int k = 0; k < 128; ++k) {
-      const float wv = W0t[k * W0T_S + v];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] += wv * fs[(rg * 4 + r) * 128 + k];
-    }
+    HEAD_HIDDEN_CHAIN(acc, W0t, b0[v])
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = r0 + rg * 4 + r;
-      float hv = acc[r] > 0.f ? acc[r] : 0.f;
-      if (drop_thr > 0) {
-        const uint32_t e = (uint32_t)row * 64u + (uint32_t)v;
-        hv *= drop_mul(drop_word(e, drop_key), e & 3, drop_thr, dscale);
-      }
+      HEAD_RELU_DROPOUT(hv, acc[r], row, drop_thr, drop_key, dscale)
       hs[(rg * 4 + r) * 64 + v] = hv;
       if (row < B) hid[(size_t)row * 64 + v] = hv;
     }
@@ -439,8 +266,7 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
   __syncthreads();
   for (int i = tid; i < HEAD_ROWS * K; i += 256) {
     const int rl = i / K, c = i - rl * K, row = r0 + rl;
-    float a = b3[c];
-    for (int vv = 0; vv < 64; ++vv) a += W3s[c * 64 + vv] * hs[rl * 64 + vv];
+    HEAD_LOGIT(a, W3s, 64, b3, c, rl)
     lgs[rl * MSIG_MAX_K + c] = a;
     if (row < B) logits[(size_t)row * K + c] = a;
   }
@@ -470,8 +296,7 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
         probs[(size_t)row * K + c] = p;
         float dl;
         if (ST && soft) dl = soft_dlogit(sc, p, c, y, y2, wy, wy2, CW ? cw[c] : 1.f, CW ? invW : invB);
-        else if constexpr (CW) dl = (wy * (p - (c == y ? 1.f : 0.f))) * invW;
-        else dl = (p - (c == y ? 1.f : 0.f)) * invB;
+        else dl = HEAD_CE_DL(p, c, y, wy, (CW ? invW : invB));
         dlogits[(size_t)row * K + c] = dl;
         dls[tid * MSIG_MAX_K + c] = dl;
       }
@@ -479,59 +304,19 @@ __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict_
       for (int c = 0; c < K; ++c) dls[tid * MSIG_MAX_K + c] = 0.f;
     }
   }
-  // head_bwd_kernel reads hid as 0 for the rows past the batch
+  // the backward pieces read hid as 0 for the rows past the batch
   for (int i = tid; i < HEAD_ROWS * 64; i += 256) if (r0 + (i >> 6) >= B) hs[i] = 0.f;
   __syncthreads();
   // ---- head_bwd_kernel ----
-  float dW0acc[32];
-#pragma unroll
-  for (int j = 0; j < 32; ++j) dW0acc[j] = 0.f;
-  float dW3acc[4] = {0.f, 0.f, 0.f, 0.f};
-  float db0acc = 0.f, db3acc = 0.f;
+  HEAD_GRADS_ZERO
   {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rl = rg * 4 + r;
-      float a = 0.f;
-      for (int c = 0; c < K; ++c) a += W3s[c * 64 + v] * dls[rl * MSIG_MAX_K + c];
-      dps[rl * 64 + v] = hs[rl * 64 + v] > 0.f ? a * dscale_bwd : 0.f;
-    }
+    HEAD_DPRE(W3s, 64, K, a * dscale_bwd)
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < (msig_negctl_range == 3 ? 2 : 4); ++j) {
-      const int idx = tid + 256 * j;
-      if (idx < K * 64) {
-        const int c = idx >> 6, vv = idx & 63;
-        float a = 0.f;
-#pragma unroll 4
-        for (int rl = 0; rl < HEAD_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + c] * hs[rl * 64 + vv];
-        dW3acc[j] += a;
-      }
-    }
-    if (tid < K) { float a = 0.f; for (int rl = 0; rl < HEAD_ROWS; ++rl) a += dls[rl * MSIG_MAX_K + tid]; db3acc += a; }
-    if (tid < 64) { float a = 0.f; for (int rl = 0; rl < HEAD_ROWS; ++rl) a += dps[rl * 64 + tid]; db0acc += a; }
-#pragma unroll 1
-    for (int rl = 0; rl < HEAD_ROWS; ++rl) {
-      const float fv = fs[rl * 128 + kcol];
-#pragma unroll
-      for (int j = 0; j < 32; ++j) dW0acc[j] += dps[rl * 64 + half * 32 + j] * fv;
-    }
-#pragma unroll 1
-    for (int r = 0; r < 8; ++r) {
-      const int rl = half * 8 + r, row = r0 + rl;
-      float a = 0.f;
-#pragma unroll 8
-      for (int vv = 0; vv < 64; ++vv) a += W0t[kcol * W0T_S + vv] * dps[rl * 64 + vv];
-      if (row < B) dfeat[(size_t)row * 128 + kcol] = a;
-    }
+    HEAD_GRADS_ADD(K)
+    HEAD_DFEAT(W0t, dfeat, r0, B)
   }
   float* P = part + (size_t)blockIdx.x * (64 * 128 + 64 + K * 64 + K);
-#pragma unroll
-  for (int j = 0; j < 32; ++j) P[(half * 32 + j) * 128 + kcol] = dW0acc[j];
-  if (tid < 64) P[64 * 128 + tid] = db0acc;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { const int idx = tid + 256 * j; if (idx < K * 64) P[64 * 128 + 64 + idx] = dW3acc[j]; }
-  if (tid < K) P[64 * 128 + 64 + K * 64 + tid] = db3acc;
+  HEAD_PART_STORE(P, K)
 }
 
 // ------------------------------------------------------------------------------------

@@ -101,7 +101,8 @@ constexpr int msig_negctl_regime = 0;
 // product does not also form (tests/test_channel_class_range_gpu.py must FAIL against each; tools/negative_controls.sh range).
 //   1  conv1_fwd_kernel<0>'s gated staging without the zero fill of the padded taps (they carry w1[o * K + 0] * gate instead)
 //   2  conv1_bwd_kernel<0> with NB = K / 16 in its MFMA and record guards: the columns of the partial last block are never accumulated
-//   3  head_bwd_kernel / head_step_kernel accumulate dW3 in two of the four register slots: rows c >= 8 of the gradient stay zero
+//   3  HEAD_GRADS_ADD (head_mlp.h: head_bwd_kernel, head_step_kernel, head_epoch_kernel, da_step_kernel) accumulates dW3 in two of
+//      the four register slots: rows c >= 8 of the gradient stay zero
 #ifdef MSIG_NEGCTL_RANGE
 constexpr int msig_negctl_range = MSIG_NEGCTL_RANGE;
 #else
@@ -240,6 +241,13 @@ __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
   return h;
 }
+// The dropout key of (seed, optimiser step, stream: 1 GRU, 2 head): msig_dropout_key (api.hip), and the head epoch's per step
+__host__ __device__ __forceinline__ uint32_t dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id) {
+  const uint32_t lo = (uint32_t)(seed & 0xFFFFFFFFu), hi = (uint32_t)(seed >> 32);
+  const uint32_t a = (uint32_t)((step * 0x9E3779B9ull) & 0xFFFFFFFFull);
+  const uint32_t b = (uint32_t)(((uint64_t)stream_id * 0x7F4A7C15ull) & 0xFFFFFFFFull);
+  return fmix32(lo ^ fmix32(a + b + hi));
+}
 // Dropout: element e is kept iff byte (e&3) of fmix32((e>>2) ^ key) >= thr.
 __device__ __forceinline__ uint32_t drop_word(uint32_t elem_idx, uint32_t key) { return fmix32((elem_idx >> 2) ^ key); }
 __device__ __forceinline__ float drop_mul(uint32_t word, int byte, int thr, float scale) {
@@ -258,8 +266,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// One row of CrossEntropy: argmax and log-sum-exp of its K logits — shared by ce_kernel, head_step_kernel, the loss finalizer of
-// the fused step (colsum_adam_kernel) — which must agree in every bit — and the head epoch (finetune.hip).
+// One row of CrossEntropy: argmax and log-sum-exp of its K logits (head_mlp.h ce_row_terms, and the discriminator's two-label form).
 __device__ __forceinline__ float ce_row_lse(const float* lg, int K, int& am) {
   float mx = lg[0]; am = 0;
   for (int c = 1; c < K; ++c) if (lg[c] > mx) { mx = lg[c]; am = c; }
