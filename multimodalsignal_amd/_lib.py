@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -109,6 +109,10 @@ KD_MIN_T, KD_MAX_T = 1.0 / 64.0, 64.0      # msig_kd.h: the temperature's range
 SAM_ABI_VERSION = 1   # include/msig_sam.h MSIG_SAM_ABI_VERSION (sharpness-aware minimisation: perturbation, restore, the two-pass train step)
 SAM_NORM_SUM, SAM_NORM_MAX, SAM_NORM_LAST, SAM_SHARP_SUM, SAM_SHARP_LAST, SAM_STEPS = range(6)      # msig_sam.h: the state's statistics
 SAM_NSTAT = 8         # msig_sam.h MSIG_SAM_NSTAT: float64 statistics at the head of a model's SAM state
+DRO_ABI_VERSION = 1   # include/msig_dro.h MSIG_DRO_ABI_VERSION (group-DRO: the group weights and the per-row rescale of the train step's gradient)
+DRO_MAX_GROUPS = 64   # msig_dro.h MSIG_DRO_MAX_GROUPS: groups of one fold
+DRO_MAX_BATCH = 2048  # msig_dro.h MSIG_DRO_MAX_BATCH: rows of one step with the term
+DRO_STATS = 3 * DRO_MAX_GROUPS + 2      # msig_dro.h MSIG_DRO_STATS: T_g, W_g, n_g per group, the robust loss's sum, the steps
 NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
 
 
@@ -175,6 +179,13 @@ class Kd(C.Structure):
     batch's store positions, the optional statistics, and (fold batch) the bytes between the folds' tables and statistics."""
     _fields_ = [("alpha", C.c_float), ("temperature", C.c_float), ("q", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64),
                 ("stats", C.c_void_p), ("stride_bytes", C.c_int64)]
+
+
+class Dro(C.Structure):
+    """msig_dro (include/msig_dro.h): the group-DRO term of a launch — group count, step size, the frozen flag, the group table and the
+    batch's store positions, the weights q, the optional statistics, and (fold batch) the bytes between the folds' q, grp and stats."""
+    _fields_ = [("G", C.c_int32), ("eta", C.c_float), ("frozen", C.c_int32), ("grp", C.c_void_p), ("idx", C.c_void_p),
+                ("idx_row_stride", C.c_int64), ("q", C.c_void_p), ("stats", C.c_void_p), ("stride_bytes", C.c_int64)]
 
 
 class Sam(C.Structure):
@@ -417,6 +428,18 @@ def lib() -> C.CDLL:
         L.msig_sam_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Kd), C.POINTER(Sam), vp, vp, f32, f32, f32, f32, f32, i64, vp]
         L.msig_sam_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Kd), C.POINTER(Sam), vp, vp, f32, f32,
                                                 f32, f32, i64, vp]
+        # include/msig_dro.h, exported by the same library: the group-DRO term and the train steps with it
+        L.msig_dro_abi_version.restype = C.c_int
+        L.msig_dro_struct_bytes.restype = C.c_int64
+        if L.msig_dro_abi_version() != DRO_ABI_VERSION or L.msig_dro_struct_bytes() != C.sizeof(Dro):
+            raise RuntimeError(f"{LIB_PATH} has msig_dro.h ABI {L.msig_dro_abi_version()} with msig_dro of {L.msig_dro_struct_bytes()} bytes; "
+                               f"this binding is {DRO_ABI_VERSION} with {C.sizeof(Dro)}: rebuild the library")
+        L.msig_dro_apply.argtypes = [C.POINTER(Dro), vp, vp, vp, f32, vp, i32, i32, vp]
+        L.msig_dro_apply_multi.argtypes = [C.POINTER(Dro), C.POINTER(Multi), vp, vp, vp, f32, vp, i32, i32, vp]
+        L.msig_dro_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), C.POINTER(Sam), C.POINTER(Dro), vp, vp,
+                                          f32, f32, f32, f32, f32, i64, vp]
+        L.msig_dro_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), C.POINTER(Sam),
+                                                C.POINTER(Dro), vp, vp, f32, f32, f32, f32, i64, vp]
         # include/msig_nr.h, exported by the same library: per-subject normalisation with the statistics of reference windows
         L.msig_nr_abi_version.restype = C.c_int
         if L.msig_nr_abi_version() != NR_ABI_VERSION:

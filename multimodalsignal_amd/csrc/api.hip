@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h, msig_kd.h and msig_sam.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h, msig_kd.h, msig_sam.h and msig_dro.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -16,6 +16,7 @@
 #include "../../include/msig_mc.h"
 #include "../../include/msig_kd.h"
 #include "../../include/msig_sam.h"
+#include "../../include/msig_dro.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -323,6 +324,7 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   // perturbation — then this function once more on copies of the descriptors that report nowhere (pass2), with the same keys
   if (o.sam && !o.sam->pass2) {
     if ((rc = forward_fc(b, fc, st, o, true))) return rc;
+    if (o.dro && (rc = launch_dro_apply(*o.dro, c.w.p<float>(MSIG_WS_LOGITS), b->labels, o.cw, c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
     if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
     ColsumPlan plan1;
     if ((rc = launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan1, fc, st))) return rc;
@@ -335,17 +337,21 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
     SamArgs sam2 = *o.sam;
     sam2.pass2 = true;
     KdArgs kd2;
+    DroArgs dro2;
     StepOpts o2 = o;
     o2.sam = &sam2;
     if (o.kd) { kd2 = *o.kd; kd2.stats = nullptr; o2.kd = &kd2; }
+    if (o.dro) { dro2 = *o.dro; dro2.frozen = 1; dro2.stats = nullptr; o2.dro = &dro2; }      // q moved once, in pass 1
     fc.fused_step = 0;                      // as this call received it: the second one sets it after its own checks
     return train_step_fc(&b2, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st, o2);
   }
   // few windows: the head's forward, CrossEntropy and backward are one launch (head.hip head_step_kernel), its loss sums ride in the last one
   // distillation (include/msig_kd.h) needs WS_LOGITS and WS_DLOGITS complete between the criterion and the head's backward: unfused
   // a sharpness-aware step's second pass restores MSIG_WS_LOSS before the last launch, where head_step would finalise its sums: unfused
-  const bool head_step = !o.kd && !o.sam && head_step_applies(b, c.d);
+  // group-DRO (include/msig_dro.h) rescales WS_DLOGITS between the criterion and the distillation term: unfused
+  const bool head_step = !o.kd && !o.sam && !o.dro && head_step_applies(b, c.d);
   if ((rc = forward_fc(b, fc, st, o, !head_step))) return rc;
+  if (o.dro && (rc = launch_dro_apply(*o.dro, c.w.p<float>(MSIG_WS_LOGITS), b->labels, o.cw, c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
   if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
   // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
@@ -543,8 +549,8 @@ static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* 
 // include/msig_kd.h (NULL, or alpha == 0 after its checks = msig_da_train_step[_multi] itself)
 static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
                          float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a,
-                         const msig_kd* k = nullptr, const msig_sam* sm = nullptr) {
-  if (sm && (!s || !b)) return MSIG_E_NULL;
+                         const msig_kd* k = nullptr, const msig_sam* sm = nullptr, const msig_dro* dr = nullptr) {
+  if ((sm || dr) && (!s || !b)) return MSIG_E_NULL;
   SamArgs sam;                             // include/msig_sam.h: its own checks first; rho == 0 after them = the call without it
   int rc;
   if (sm) {
@@ -559,6 +565,11 @@ static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* 
   KdArgs kd;
   if (k && (rc = msig_kd_make_args(k, fc, b->shape.B, b->shape.K, soft.lam, kd))) return rc;
   const bool distil = k && k->alpha != 0.f;
+  DroArgs dro;                             // include/msig_dro.h: a blended row has no group
+  if (dr) {
+    if ((rc = msig_dro_make_args(dr, fc, b->shape.B, b->shape.K, soft.eps, dro))) return rc;
+    for (int i = 0; i < fc.n; ++i) if (soft.lam[i] != 1.f) return MSIG_E_SHAPE;
+  }
   ClipArgs cl;
   if (s->clip) {
     if (s->clip->kind != s->kind) return MSIG_E_SHAPE;
@@ -566,7 +577,7 @@ static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* 
   }
   return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st,
                        StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr,
-                                distil ? &kd : nullptr, sm ? &sam : nullptr});
+                                distil ? &kd : nullptr, sm ? &sam : nullptr, dr ? &dro : nullptr});
 }
 extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
   return st_forward(b, single_fold(b), s, (hipStream_t)stream);
@@ -675,6 +686,24 @@ extern "C" int msig_sam_train_step_multi(const msig_batch* b, const msig_multi* 
   if (!s) return MSIG_E_NULL;
   FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
   return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr, kd, sam);
+}
+
+// ---- group-DRO (include/msig_dro.h; kernel and the stand-alone calls: dro.hip) -------------------------------------------------------
+extern "C" int msig_dro_train_step(const msig_batch* b, const msig_st* s, const msig_da* da, const msig_kd* kd, const msig_sam* sam,
+                                   const msig_dro* dro, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, int64_t step, void* stream) {
+  if (da && sam) return MSIG_E_SHAPE;
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da,
+                       kd, sam, dro);
+}
+extern "C" int msig_dro_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* da, const msig_kd* kd,
+                                         const msig_sam* sam, const msig_dro* dro, float* exp_avg, float* exp_avg_sq, float beta1,
+                                         float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  if (da && sam) return MSIG_E_SHAPE;
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd, sam,
+                       dro);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

@@ -451,6 +451,7 @@ struct ClipArgs;
 struct DaArgs;
 struct KdArgs;
 struct SamArgs;
+struct DroArgs;
 // What a forward or a train step does beyond the msig.h call (host side only; api.hip's entry points fill it after their own checks).
 // Value-initialised = the plain call.  Each function that takes it reads only the fields named at its declaration.
 struct StepOpts {
@@ -461,6 +462,7 @@ struct StepOpts {
   const DaArgs* da;         // subject discriminator (include/msig_da.h): one more launch after the head's
   const KdArgs* kd;         // distillation (include/msig_kd.h): the unfused head with one more launch between ce and head_bwd
   const SamArgs* sam;       // sharpness-aware step (include/msig_sam.h): two passes with the unfused head, perturbation and restore between
+  const DroArgs* dro;       // group-DRO (include/msig_dro.h): the unfused head with one more launch between ce and kd_apply / head_bwd
 };
 // reads o.cw, o.soft.  mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of
 // b->dropout_thr although b->training = 0
@@ -521,6 +523,21 @@ int launch_sam_perturb(const SamArgs& a, float* params, const float* grads, cons
                        const float* ws_loss, const FoldCtx& fc, hipStream_t st);
 int launch_sam_restore(const SamArgs& a, float* params, float* bn_state, int64_t* bn_count, float* ws_loss, int B, const FoldCtx& fc,
                        hipStream_t st);
+// Group-DRO (include/msig_dro.h, dro.hip): msig_dro after its checks (msig_dro_make_args), by value to the launch.  grp / q / stats are
+// fold slot 0's, `stride` bytes apart per slot; B rows of K; eps: the launch's label smoothing.  One launch, between ce_kernel and
+// kd_apply_kernel / head_bwd_kernel, on WS_LOGITS / WS_DLOGITS; labels and cw are the step's (fold slot 0's, shifted like every buffer).
+struct msig_dro;
+struct DroArgs {
+  int32_t G, B, K, frozen;
+  float eta, eps;
+  const int32_t* grp; const int64_t* idx; int64_t idx_row_stride;
+  float* q; double* stats;
+  int64_t stride;
+};
+// every check of msig_dro.h's own arguments, before any launch; fc: the folds of the launch (stride != 0: a fold batch)
+int msig_dro_make_args(const msig_dro* k, const FoldCtx& fc, int32_t B, int32_t K, float smoothing, DroArgs& a);
+int launch_dro_apply(const DroArgs& a, const float* logits, const int64_t* labels, const float* cw, float* dlogits, const FoldCtx& fc,
+                     hipStream_t st);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch

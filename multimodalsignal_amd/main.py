@@ -31,6 +31,7 @@ from . import _lib as L
 from .augment import Augment
 from .mixup import Mixup
 from . import adversary as adversary_mod
+from . import dro as dro_mod
 from . import averaging as averaging_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask
 from . import distill as distill_mod
@@ -105,6 +106,8 @@ def trainer_config(cfg, fold_idx):
         tc["trainer"]["label_smoothing"] = label_smoothing_setting(cfg["label_smoothing"])
     if cfg.get("sam") is not None:                  # sharpness-aware train steps (include/msig_sam.h); absent = the plain step
         tc["trainer"]["sam"] = sam_mod.setting(cfg["sam"]).spec()
+    if cfg.get("group_dro") is not None:            # group-DRO over the training subjects (include/msig_dro.h); absent = the pooled mean
+        tc["trainer"]["group_dro"] = dro_mod.settings(cfg["group_dro"])
     if cfg.get("adversary") is not None:            # a subject discriminator inside every training step (include/msig_da.h); absent = none
         tc["adversary"] = adversary_mod.settings(cfg["adversary"])
     if cfg.get("averaging") is not None:            # an EMA / SWA shadow of the weights (include/msig_wa.h); absent = none
@@ -152,6 +155,10 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
     train_subjects, val_subjects = split_train_val(cfg["subjects"], subject, cfg["seed"])
     if cfg.get("adversary") is not None:            # before any data is loaded: the discriminator's step takes at most 256 rows
         adversary_mod.check_batch_size(cfg["batch_size"])
+    if cfg.get("group_dro") is not None:            # likewise: the term's launch takes at most 2048 rows, and a blended row has no group
+        dro_mod.check_batch_size(cfg["batch_size"])
+        if Mixup.coerce(cfg.get("mixup")) is not None:
+            raise ValueError("group_dro cannot be combined with mixup: a row blended from two subjects has no group")
     train_ds, val_ds = datasets(train_subjects), datasets(val_subjects)
     if skip_empty and (len(train_ds) == 0 or len(val_ds) == 0):
         return None
@@ -168,7 +175,7 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
     model = make_model(cfg, in_channels, num_classes, params)
     model.set_dropout_seed(seed * 0x9E3779B97F4A7C15 + 12345)
     return dict(fold=fold_idx, subject=subject, fold_dir=fold_dir, loaders=loaders, model=model, config=trainer_config(cfg, fold_idx),
-                test_pass=test_pass)
+                test_pass=test_pass, train_subjects=list(train_subjects), val_subjects=list(val_subjects))
 
 
 def prepare_fold(fold_idx, subject_to_test, run_output_dir, device, all_channel_names, cfg, cache=None):
@@ -191,6 +198,7 @@ def train_fold(prep, device):
     trainer = prep["trainer"] = Trainer(prep["model"], prep["fold_dir"], prep["config"])
     if prep.get("distill") is not None:
         trainer.set_distillation(prep["distill"])
+    trainer.subject_names = (prep.get("train_subjects"), prep.get("val_subjects"))      # named in the group-DRO log entries
     t0 = time.time()
     trainer.train(train_loader, val_loader)
     acc, f1 = trainer.evaluate(test_loader, is_test=True)[1:] if prep.get("test_pass", True) else (None, None)
@@ -227,6 +235,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(soft_targets_line(cfg))
         if adversary_line(cfg) is not None:                         # likewise
             f.write(adversary_line(cfg))
+        if cfg.get("group_dro") is not None:                        # likewise
+            f.write(dro_mod.settings_line(cfg["group_dro"]) + "\n")
         if cfg.get("averaging") is not None:                        # likewise
             f.write(averaging_mod.settings_line(cfg["averaging"]) + "\n")
         if cfg.get("norm_reference") is not None:                   # likewise
@@ -626,6 +636,13 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
                 path = adversary_mod.write_adversary(out_dir[n], folds, adversary_mod.settings(cfgs[n]["adversary"]),
                                                      synthetic=bool(cfgs[n].get("synthetic")))
                 print(f"Subject-adversary table written to: {path}")
+        if cfgs[n].get("group_dro") is not None:      # likewise from the folds' fold_result.json
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "fold_result.json" for r in results[n]]
+            folds = [dro_mod.fold_record(json.loads(f.read_text())) for f in files if f.exists()]
+            folds = [f for f in folds if f is not None]
+            if folds:
+                path = dro_mod.write_dro(out_dir[n], folds, cfgs[n]["group_dro"], synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Group-DRO table written to: {path}")
         if cfgs[n].get("averaging") is not None:      # likewise from the folds' fold_result.json
             files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "fold_result.json" for r in results[n]]
             folds = [averaging_mod.fold_record(json.loads(f.read_text())) for f in files if f.exists()]
@@ -993,6 +1010,15 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                                                      accuracy=m1_acc if tag == "m1" else None))
                 if rec is not None:                 # a model that trained no epoch has no record
                     (Path(run_output_dir) / f"fold_test_on_{sid}" / f"model_{tag}" / "adversary_result.json").write_text(json.dumps(rec))
+        if cfg.get("group_dro") is not None:      # likewise each model's group-DRO record
+            for tag, t in trainers.items():
+                if t.dro is None:
+                    continue
+                info = dict(subject=sid, history=t.history, accuracy=m1_acc if tag == "m1" else None,
+                            group_dro=dro_mod.fold_info(t.dro, t.subject_names[0]))
+                rec = dro_mod.fold_record(info)
+                if rec is not None:
+                    (Path(run_output_dir) / f"fold_test_on_{sid}" / f"model_{tag}" / "dro_result.json").write_text(json.dumps(rec))
         local[k] = (m1_acc, acc3)
         print(f"[rank {rank}] fold {k} ({sid}): M1 acc {m1_acc:.4f} | three-class acc {acc3:.4f} f1 {f13:.4f}", flush=True)
 
@@ -1043,6 +1069,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(soft_targets_line(cfg))
             if adversary_line(cfg) is not None:
                 f.write(adversary_line(cfg))
+            if cfg.get("group_dro") is not None:
+                f.write(dro_mod.settings_line(cfg["group_dro"]) + "\n")
             if cfg.get("norm_reference") is not None:
                 f.write(f"NORM_REFERENCE: {cfg['norm_reference']}\n")
             f.write("\n")
@@ -1061,6 +1089,13 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                     path = adversary_mod.write_adversary(run_output_dir, folds, adversary_mod.settings(cfg["adversary"]),
                                                          synthetic=bool(cfg.get("synthetic")), stem=f"adversary_{tag}")
                     print(f"Subject-adversary table written to: {path}")
+        if cfg.get("group_dro") is not None:
+            for tag in ("m1", "m2"):
+                files = [Path(run_output_dir) / f"fold_test_on_{r['subject']}" / f"model_{tag}" / "dro_result.json" for r in results]
+                folds = [json.loads(f.read_text()) for f in files if f.exists()]
+                if folds:
+                    path = dro_mod.write_dro(run_output_dir, folds, cfg["group_dro"], synthetic=bool(cfg.get("synthetic")), stem=f"dro_{tag}")
+                    print(f"Group-DRO table written to: {path}")
     return results, wall
 
 
@@ -1177,6 +1212,16 @@ def parse_args(ap, argv=None):
             ap.error(f"--subject-adversarial: {e}")
     elif args.adversary_schedule is not None or args.adversary_lr_mult is not None:
         ap.error("--adversary-schedule / --adversary-lr-mult need --subject-adversarial")
+    if args.group_dro is not None:
+        try:
+            args.group_dro = dro_mod.parse(args.group_dro, args.dro_groups)
+            dro_mod.check_batch_size(args.batch_size)
+        except ValueError as e:
+            ap.error(f"--group-dro: {e}")
+        if args.mixup is not None:
+            ap.error("--group-dro cannot be combined with --mixup: a row blended from two subjects has no group")
+    elif args.dro_groups is not None:
+        ap.error("--dro-groups needs --group-dro")
     if args.weight_average is not None:
         try:
             spec = averaging_mod.parse_flag(args.weight_average)
@@ -1282,6 +1327,15 @@ def build_parser():
                          "discriminator only measures how subject-identifiable the feature is and the model's bits are unchanged).  Every "
                          "mode: LOSO, --ablation, --hierarchical, --model, sequential; batch sizes up to 256; writes adversary.txt / "
                          "adversary.json")
+    ap.add_argument("--group-dro", type=float, nargs="?", const=dro_mod.DEFAULT_ETA, default=None, metavar="ETA",
+                    help="group-DRO over the training subjects (Sagawa et al., 2020, the online algorithm): every fold keeps one adversarial "
+                         "weight per group, raised with that group's loss at step size ETA (default 0.01) inside every training step, "
+                         "and the step descends the weighted sum of the groups' losses instead of the pooled mean (include/msig_dro.h); "
+                         "ETA 0 is the probe mode: uniform weights, the per-subject losses are measured; every training mode: LOSO, "
+                         "--ablation / --sweep, --hierarchical, --model, --seeds, --distill, sequential; batch sizes up to 2048; not "
+                         "with --mixup; writes dro.txt / dro.json")
+    ap.add_argument("--dro-groups", choices=list(dro_mod.GROUPS), default=None,
+                    help="the groups of --group-dro: a fold's training subjects (default) or its (subject, class) pairs")
     ap.add_argument("--adversary-schedule", choices=list(adversary_mod.SCHEDULES), default=None,
                     help="lambda over the training steps: ganin = LAMBDA * (2 / (1 + exp(-10 p)) - 1), p the fraction of the epoch budget "
                          "done (default), or constant")
@@ -1380,6 +1434,8 @@ def build_cfg(args, kinds):
     if args.subject_adversarial is not None:      # likewise; refused here, before any data or GPU work, for a batch size it cannot take
         adversary_mod.check_batch_size(args.batch_size)
         cfg.update(adversary=args.subject_adversarial, synthetic=args.synthetic is not None)
+    if args.group_dro is not None:                # likewise
+        cfg.update(group_dro=args.group_dro, synthetic=args.synthetic is not None)
     if args.weight_average is not None:           # likewise
         cfg.update(averaging=args.weight_average, synthetic=args.synthetic is not None)
     if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was

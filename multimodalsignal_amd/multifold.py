@@ -33,6 +33,7 @@ import torch
 
 from . import _lib as L
 from . import adversary as A
+from . import dro as DRO
 from . import averaging as AV
 from . import sam as SAM
 from .runtime import FoldArena
@@ -75,6 +76,10 @@ def fold_result(prep, trainer, accuracy, f1_score, seconds, averaging=None):
         info["adversary_domains"] = trainer.adversary.S
     if getattr(trainer, "distill", None) is not None:        # a student (prep["distill"]): its setting beside the history's kd_* entries
         info["distillation"] = dict(alpha=trainer.distill.alpha, temperature=trainer.distill.temperature)
+    if getattr(trainer, "dro", None) is not None:            # config['trainer']['group_dro']: what main's dro tables tabulate
+        info["group_dro"] = DRO.fold_info(trainer.dro, prep.get("train_subjects"))
+        hist = [h for h in trainer.history if h.get("dro_subject_loss") is not None]
+        info["group_dro"]["subject_loss"] = hist[-1]["dro_subject_loss"] if hist else None      # per-subject mean training loss, last epoch
     if averaging is not None:
         info["averaging"] = averaging
     if prep.get("test_pass", True):
@@ -87,6 +92,14 @@ def _domains(prep):
     if A.settings(prep["config"].get("adversary")) is None:
         return None
     return int(np.max(prep["loaders"][0].dataset.subject_ordinals)) + 1
+
+
+def _dro_groups(prep):
+    """(setting, G) of a fold's group-DRO term, or None when config['trainer']['group_dro'] is not set."""
+    c = DRO.settings(prep["config"]["trainer"].get("group_dro"))
+    if c is None:
+        return None
+    return (c["eta"], c["groups"], DRO.group_count(prep["loaders"][0].dataset, c["groups"], prep["model"].num_classes))
 
 
 def _shared(values, what, show=None):
@@ -112,7 +125,8 @@ def lockstep_compatible(preps) -> bool:
                 or tr.batch_size != tr0.batch_size or va.batch_size != va0.batch_size or tr.store.data_ptr() != tr0.store.data_ptr()
                 or p["model"].in_channels != preps[0]["model"].in_channels or p["model"].num_classes != preps[0]["model"].num_classes
                 or p["model"].dropout_p != preps[0]["model"].dropout_p
-                or _domains(p) != _domains(preps[0])):       # msig_da.S is one value per launch
+                or _domains(p) != _domains(preps[0])         # msig_da.S is one value per launch
+                or _dro_groups(p) != _dro_groups(preps[0])):  # and so are msig_dro.G and eta
             return False
     return True
 
@@ -176,11 +190,18 @@ class LockstepTrainer:
         if self.sam_cfg is not None and self.adv_S is not None:
             raise ValueError("config['trainer']['sam'] cannot be combined with config['adversary']")
         self.sam_stats = {}
+        # group-DRO (config['trainer']['group_dro'], include/msig_dro.h): eta and G are the launch's, so the folds of a batch share
+        # them; every fold's q, group table and statistics live in the arena set's own block
+        self.dro_cfg = _shared([_dro_groups(p) for p in preps], "group_dro setting and group count", str)
+        if self.dro_cfg is not None:
+            DRO.check_batch_size(tr0.batch_size)
+        self.dro_stats, self.val_worst = {}, {}
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
                                adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip,
                                adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])),
                                averaging=self.avg_cfg is not None,
-                               distill=None if self.kd_cfg is None else int(tr0.store.shape[0]), sam=self.sam_cfg is not None)
+                               distill=None if self.kd_cfg is None else int(tr0.store.shape[0]), sam=self.sam_cfg is not None,
+                               dro=None if self.dro_cfg is None else (self.dro_cfg[2], int(tr0.store.shape[0])))
         if self.clip:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
@@ -204,6 +225,9 @@ class LockstepTrainer:
                 t.prepare_adversary(p["loaders"][0], self.arena.adversary_storage(slot))
             if self.kd_cfg is not None:
                 t.set_distillation(p["distill"], self.arena.distill_storage(slot))
+            t.subject_names = (p.get("train_subjects"), p.get("val_subjects"))
+            if self.dro_cfg is not None:
+                t.prepare_dro(p["loaders"][0], self.arena.dro_storage(slot))
             self.trainers.append(t)
         # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
         # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
@@ -309,6 +333,8 @@ class LockstepTrainer:
             dl = [[a.lam_at(a.step + 1 + k, a.total_steps) for k in range(ns)] for a, ns in zip(advs, n_steps)]
         if self.kd_cfg is not None:
             arena.distill_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
+        if self.dro_cfg is not None:
+            arena.zero_dro_stats(act)
         # weight averaging: EMA's coefficient of every step of the epoch per fold, from the fold's own update count
         avs = [t.averager for t in trs] if self.avg_cfg is not None else None
         ema = avs is not None and self.avg_cfg["mode"] == "ema"
@@ -335,8 +361,9 @@ class LockstepTrainer:
                                                                      [1] * nr, h0["betas"], eps, wd),
                                   arena.wa(sl, [0.0] * nr) if ema else None,
                                   None if self.kd_cfg is None else arena.kd(*self.kd_cfg),
-                                  None if self.sam_cfg is None else arena.sam(self.sam_cfg))
-            m, s, a, w, kd, sm = runs[(r0, nr)]
+                                  None if self.sam_cfg is None else arena.sam(self.sam_cfg),
+                                  None if self.dro_cfg is None else arena.dro(self.dro_cfg[0]))
+            m, s, a, w, kd, sm, dr = runs[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
                 if aug is not None:
@@ -351,7 +378,12 @@ class LockstepTrainer:
             _, desc = self._layout(b, True)
             if kd is not None:
                 kd.idx, kd.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
-            if sm is not None:                 # sharpness-aware steps: two passes of every fold of the launch, whatever else is on
+            if dr is not None:                 # group-DRO: the widest call, with whatever else is on
+                dr.idx, dr.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+                L.check(lib.msig_dro_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None,
+                                                      C.byref(kd) if kd is not None else None, C.byref(sm) if sm is not None else None,
+                                                      C.byref(dr), ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_dro_train_step_multi")
+            elif sm is not None:               # sharpness-aware steps: two passes of every fold of the launch, whatever else is on
                 L.check(lib.msig_sam_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(kd) if kd is not None else None, C.byref(sm),
                                                       ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_sam_train_step_multi")
             elif kd is not None:               # a batch of students: the same call with the distillation term (alpha 0: the call below)
@@ -384,6 +416,9 @@ class LockstepTrainer:
             st3 = arena.distill_stats().cpu().numpy()
             for f, t in zip(act, trs):
                 self.kd_stats[f] = t.distill.epoch_summary(st3[f])
+        if self.dro_cfg is not None:       # likewise, only with group-DRO on: every fold's statistics and weights in one read-back
+            sq = arena.dro_stats().cpu().numpy()
+            self.dro_stats = {f: (sq[f, :L.DRO_STATS], sq[f, L.DRO_STATS:]) for f in act}
         if self.sam_cfg is not None:       # the same sync: the loss sums, the SAM statistics and (with the clip) the gradient norms
             parts = [self.acc[:, :1], arena.across("sam", 0, torch.float64, L.SAM_NSTAT)]
             if self.clip:
@@ -441,6 +476,8 @@ class LockstepTrainer:
             pred = torch.cat(preds[j]).cpu().numpy().astype(np.int64)
             acc, f1 = accuracy_and_weighted_f1(np.asarray(ds.labels).astype(np.int64), pred)
             out[f] = (float(sums[f]) / len(ds), acc, f1)
+            if which == 1 and not shadow and self.dro_cfg is not None:
+                self.val_worst[f] = self.trainers[f].val_worst_subject(loaders[j], pred, np.asarray(ds.labels).astype(np.int64))
         return [out[f] for f in active]
 
     def run(self, t_start: float = None):
@@ -487,7 +524,8 @@ class LockstepTrainer:
                     t.train_windows += n_train[f]
                     t.train_seconds += dt
                     if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f),
-                                           avg_vals.get(f), self.kd_stats.get(f), self.sam_stats.get(f)):
+                                           avg_vals.get(f), self.kd_stats.get(f), self.sam_stats.get(f),
+                                           None if self.dro_cfg is None else t.dro_epoch(*self.dro_stats[f], self.val_worst.get(f))):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start

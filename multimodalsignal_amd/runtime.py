@@ -9,7 +9,8 @@ The host never chooses among entry points: every train step is msig_da_train_ste
 the widest of each form (a student's step, include/msig_kd.h, is msig_kd_train_step[_multi]).  The headers make that bit-safe — a
 NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL class_weight each give the narrower call with its launches, `kind`
 selects the model — and tests/test_step_dispatch_gpu.py pins it.  A sharpness-aware step (include/msig_sam.h) is
-msig_sam_train_step[_multi], whatever else is on; without `sam` the calls are exactly the ones above.
+msig_sam_train_step[_multi], whatever else is on; without `sam` the calls are exactly the ones above.  A group-DRO step
+(include/msig_dro.h) is msig_dro_train_step[_multi], whatever else is on — `sam` included; without `dro` the calls are exactly those.
 """
 from __future__ import annotations
 
@@ -415,7 +416,7 @@ class Engine:
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
                    dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
                    label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None, distill=None,
-                   sam=None) -> None:
+                   sam=None, dro=None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
@@ -439,13 +440,25 @@ class Engine:
         w + e, gradient there with the same dropout masks, restore, Adam at w with the second gradient; `grads` holds that second
         gradient, region('LOSS') / loss_acc / the BatchNorm state are the first pass's, sam_stats() the norms and the sharpness.
         The call is msig_sam_train_step whatever else is on; rho = 0 is the step without it, bit for bit.  Not with `adversary`
-        (ValueError): two passes would advance the discriminator twice.  None = the calls above, exactly."""
+        (ValueError): two passes would advance the discriminator twice.  None = the calls above, exactly.
+        dro: a dro.GroupDro bound to this device (include/msig_dro.h): the head runs unfused and one more launch
+        moves the group weights dro.q with the groups' losses — groups read by batch_index, or one table entry per row — and
+        rescales the logits' gradient so that the step descends sum_g q_g L_g; the reported loss stays the criterion's, the term's
+        statistics go to dro.stats.  Under `sam` the weights move once, in the first pass.  Not with mixup (ValueError): a blended
+        row has no group.  The call is msig_dro_train_step whatever else is on; None = the calls above, exactly."""
         cw, max_norm, smooth, lam = self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
+        if dro is not None:
+            if lam != 1.0:
+                raise ValueError("group-DRO cannot be combined with mixup: a row blended from two subjects has no group")
+            if x.shape[0] > L.DRO_MAX_BATCH:
+                raise ValueError(f"group-DRO takes batches of at most {L.DRO_MAX_BATCH} windows, got {x.shape[0]}")
+            if batch_index is None and (dro.grp is None or dro.grp.numel() < x.shape[0]):
+                raise ValueError(f"a group table read by row needs {x.shape[0]} entries")
         if sam is not None and adversary is not None:
             raise ValueError("sam cannot be combined with adversary: the discriminator's own Adam would advance in both passes")
         if adversary is not None and x.shape[0] > L.DA_MAX_BATCH:
             raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
-        if adversary is not None or distill is not None:
+        if adversary is not None or distill is not None or dro is not None:
             if batch_index is not None:
                 _require_gpu(batch_index, "batch_index")
                 if batch_index.dtype != torch.int64 or not batch_index.is_contiguous() or batch_index.numel() != x.shape[0]:
@@ -465,7 +478,16 @@ class Engine:
             k = distill.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
         else:
             k = None
-        if sam is not None:
+        if dro is not None:
+            sd = None
+            if sam is not None:
+                state = self.ensure_sam_state()
+                sd = C.byref(sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8))
+            dd = dro.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
+            L.check(L.lib().msig_dro_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, None if k is None else C.byref(k), sd,
+                                                C.byref(dd), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps,
+                                                weight_decay, step, self._stream()), "msig_dro_train_step")
+        elif sam is not None:
             state = self.ensure_sam_state()
             sd = sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8)
             L.check(L.lib().msig_sam_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), None if k is None else C.byref(k),
@@ -481,7 +503,7 @@ class Engine:
                     "msig_da_train_step")
         if adversary is not None:
             adversary.step += 1
-        if adversary is not None or distill is not None:
+        if adversary is not None or distill is not None or dro is not None:
             self._keep = self._keep + (batch_index,)
 
     def features(self, x: torch.Tensor, padded: bool = False) -> torch.Tensor:
@@ -610,7 +632,8 @@ class EmbeddedEngine(Engine):
         return self.small_views(self.avg_params.index_select(0, self.index))
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
-                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None, sam=None):
+                   max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None, sam=None,
+                   dro=None):
         self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
         if sam is not None and adversary is not None:
             raise ValueError("sam cannot be combined with adversary: the discriminator's own Adam would advance in both passes")
@@ -618,7 +641,7 @@ class EmbeddedEngine(Engine):
             adversary.restrict_features(self.hidden)       # nothing may reach the padded feature columns (their units must stay zero)
         self.scatter()
         super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm, label_smoothing,
-                           mix_lambda, adversary, batch_index, distill, sam)
+                           mix_lambda, adversary, batch_index, distill, sam, dro)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -723,7 +746,7 @@ class FoldArena(Arenas):
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
                  adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
                  grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None, averaging: bool = False,
-                 distill: Optional[int] = None, sam: bool = False):
+                 distill: Optional[int] = None, sam: bool = False, dro: Optional[Tuple[int, int]] = None):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
@@ -741,7 +764,10 @@ class FoldArena(Arenas):
         statistics (include/msig_kd.h) in a memory block of their own, `kd_stride` bytes apart (`distill_storage`), as the
         adversary's buffers are owned; the model arenas and their stride stay what they are without it.
         `sam`: the arenas also hold a "sam" region, each fold's SAM state (include/msig_sam.h), after every other region, the shadow
-        included — without it the arenas and their stride are what they are without this argument."""
+        included — without it the arenas and their stride are what they are without this argument.
+        `dro` = (G, store positions): every fold also gets the buffers of a group-DRO term of G groups (include/msig_dro.h) — the
+        weights q, the statistics and an int32 group table — in a memory block of their own, `dro_stride` bytes apart
+        (`dro_storage`), as the adversary's buffers are owned; the model arenas and their stride stay what they are without it."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -789,6 +815,13 @@ class FoldArena(Arenas):
                 raise ValueError(f"distill takes the number of store positions (>= 1), got {distill!r}")
             kd = Arenas(n, device, (("stats", 24), ("q", int(distill) * num_classes * 4)))
             self.kd_off, self.kd_stride, self.kd_mem = kd.off, kd.stride, kd.mem
+        self.dro_off, self.dro_stride, self.dro_mem, self.dro_G = {}, 0, None, None
+        if dro is not None:
+            G, positions = int(dro[0]), int(dro[1])
+            if not 1 <= G <= L.DRO_MAX_GROUPS or positions < 1:
+                raise ValueError(f"dro takes (groups in 1..{L.DRO_MAX_GROUPS}, store positions >= 1), got {dro!r}")
+            dr = Arenas(n, device, (("q", L.DRO_MAX_GROUPS * 4), ("stats", L.DRO_STATS * 8), ("grp", positions * 4)))
+            self.dro_off, self.dro_stride, self.dro_mem, self.dro_G = dr.off, dr.stride, dr.mem, G
 
     @staticmethod
     def workspace_bytes(train_batch: int, eval_batch: int, in_channels: int, T: int, num_classes: int) -> int:
@@ -863,6 +896,34 @@ class FoldArena(Arenas):
         """(n, 3) float64 strided view of every fold's distillation statistics."""
         o = self.kd_off["stats"][0] // 8
         return self.kd_mem.view(torch.float64)[:, o:o + 3]
+
+    def dro_storage(self, slot: int) -> dict:
+        """The group-DRO buffers of the fold in arena `slot` (dro.GroupDro.bind): typed views of its `dro_mem` row."""
+        if self.dro_mem is None:
+            raise RuntimeError("this FoldArena was built without dro=(G, positions): it has no group-DRO buffers")
+        dt = {"q": torch.float32, "stats": torch.float64, "grp": torch.int32}
+        return {name: self.dro_mem[slot, o:o + nb].view(dt[name]) for name, (o, nb) in self.dro_off.items()}
+
+    def dro(self, eta: float, frozen: bool = False) -> L.Dro:
+        """msig_dro of a launch (include/msig_dro.h): fold slot 0's q, group table and statistics, `dro_stride` apart.  idx /
+        idx_row_stride are the launch's to fill in."""
+        if self.dro_mem is None:
+            raise RuntimeError("this FoldArena was built without dro=(G, positions): it has no group-DRO buffers")
+        d = L.Dro()
+        d.G, d.eta, d.frozen = self.dro_G, float(eta), int(bool(frozen))
+        base = self.dro_mem.data_ptr()
+        d.q, d.grp, d.stats, d.stride_bytes = base + self.dro_off["q"][0], base + self.dro_off["grp"][0], base + self.dro_off["stats"][0], self.dro_stride
+        return d
+
+    def dro_stats(self) -> torch.Tensor:
+        """(n, DRO_STATS + DRO_MAX_GROUPS) float64 copy of every fold's group-DRO statistics followed by its q (widened)."""
+        o, oq = self.dro_off["stats"][0] // 8, self.dro_off["q"][0] // 4
+        return torch.cat([self.dro_mem.view(torch.float64)[:, o:o + L.DRO_STATS],
+                          self.dro_mem.view(torch.float32)[:, oq:oq + L.DRO_MAX_GROUPS].to(torch.float64)], dim=1)
+
+    def zero_dro_stats(self, slots) -> None:
+        o = self.dro_off["stats"][0] // 8
+        self.dro_mem.view(torch.float64)[:, o:o + L.DRO_STATS].index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
 
     def set_class_weight(self, slot: int, values) -> None:
         """Writes the class-weight vector of the fold in arena `slot` (K values, checked on the host: ValueError before anything is

@@ -30,6 +30,10 @@ after every train step (EMA) or at the end of an epoch (SWA); it steers nothing 
 ``config['trainer']['sam']`` (None, or ``RHO[:adaptive[:ETA]]``) makes every TRAINING step a sharpness-aware one (include/msig_sam.h,
 DESIGN.md §28): ``history`` and the log gain the epoch's ``sam_grad_norm`` (mean and max) and ``sam_sharpness``; a rho of 0 is the
 run without the key; not with ``config['adversary']``.
+``config['trainer']['group_dro']`` (None, a number — eta — or a dict with eta / groups, ``dro.settings``) makes every TRAINING step
+descend the group-DRO objective over the training subjects (include/msig_dro.h): ``history`` and the log gain
+``dro_robust_loss``, ``dro_worst_group_loss`` (and its subject), ``dro_q_max``, ``dro_q_entropy`` and the worst validation subject's
+accuracy; the reported losses, the scheduler, early stopping and ``best_model.pt`` keep following the criterion; not with mixup.
 """
 from __future__ import annotations
 
@@ -44,6 +48,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from . import _lib as L
 from . import adversary as A
+from . import dro as DRO
 from . import averaging as AV
 from . import sam as SAM
 from .models import CnnGruAttentionModel
@@ -205,6 +210,10 @@ class Trainer:
         if self.sam is not None and self.adversary_cfg is not None:
             raise ValueError("config['trainer']['sam'] cannot be combined with config['adversary']: the discriminator's own Adam would "
                              "advance in both passes of a step")
+        # group-DRO (include/msig_dro.h): the settings now, the group weights when the training set is known
+        self.dro_cfg = DRO.settings(cfg.get("group_dro"))
+        self.dro = None
+        self.subject_names = (None, None)        # (training, validation) subjects in ordinal order, when the driver knows them
         self.averaging_cfg = AV.settings(config.get("averaging"))
         self.averager = AV.WeightAverager(self.averaging_cfg) if self.averaging_cfg is not None else None
         self.verbose = cfg.get("verbose", True)
@@ -285,6 +294,46 @@ class Trainer:
         self._log(f"subject adversary: {adv.S} domains, lambda {adv.lam:g} ({adv.schedule}), lr x {adv.lr_mult:g}")
         return adv
 
+    def prepare_dro(self, train_loader, storage=None):
+        """Builds the fold's group-DRO state once, when config['trainer']['group_dro'] is set: one group per subject of the training
+        set (or per (subject, class) pair), its group table over the store the loader gathers from, q uniform at 1 / G.  storage: one
+        fold's group-DRO buffers of a FoldArena.  ValueError before any training for a batch size the term's launch cannot take, for
+        a loader that mixes, and for more than 64 groups."""
+        if self.dro_cfg is None or self.dro is not None:
+            return self.dro
+        DRO.check_batch_size(train_loader.batch_size)
+        if getattr(train_loader, "mixup", None) is not None:
+            raise ValueError("group_dro cannot be combined with mixup: a row blended from two subjects has no group")
+        ds = train_loader.dataset
+        if getattr(ds, "subject_ordinals", None) is None:
+            raise ValueError("config['trainer']['group_dro'] needs a training dataset with per-window `subject_ordinals`")
+        c, K = self.dro_cfg, int(self.model.num_classes)
+        d = DRO.GroupDro(c["eta"], c["groups"])
+        d.set_groups(DRO.group_table(ds, c["groups"], K), DRO.group_count(ds, c["groups"], K), K)
+        self.dro = d.bind(self.device, storage)
+        self._log(f"group-DRO: {d.G} groups ({d.groups}), eta {d.eta:g}")
+        return d
+
+    def val_worst_subject(self, val_loader, preds, labels) -> "dict | None":
+        """With group-DRO on: the validation subject with the lowest accuracy, from the predictions of the epoch's validation pass
+        (host side; the validation loader serves its windows in dataset order)."""
+        ords = getattr(getattr(val_loader, "dataset", None), "subject_ordinals", None)
+        if self.dro_cfg is None or ords is None or len(ords) != len(preds):
+            return None
+        s, acc = DRO.worst_subject_accuracy(preds, labels, ords)
+        names = self.subject_names[1]
+        return dict(val_worst_subject=None if s is None else (str(names[s]) if names is not None and s < len(names) else f"#{s}"),
+                    val_worst_subject_acc=acc)
+
+    def dro_epoch(self, stats, q, worst=None) -> dict:
+        """The epoch's group-DRO entries of history and the log line: GroupDro.epoch_summary, the worst group's subject by name, and
+        the worst validation subject."""
+        out = self.dro.epoch_summary(stats, q)
+        names, s = self.subject_names[0], out["dro_worst_subject"]
+        out["dro_worst_subject"] = None if s is None else (str(names[s]) if names is not None and s < len(names) else f"#{s}")
+        out.update(worst or dict(val_worst_subject=None, val_worst_subject_acc=None))
+        return out
+
     def set_distillation(self, distillation, storage=None):
         """Turns the fold into a student: `distillation` is a distill.Distillation whose teacher table covers the
         store positions the training loader gathers from (the loader must serve `last_index`).  Every train step then carries the
@@ -306,6 +355,7 @@ class Trainer:
         self._check_labels(val_loader)
         self.prepare_class_weights(train_loader)
         adv = self.prepare_adversary(train_loader)
+        dro = self.prepare_dro(train_loader)
         kd = self.distill
         if kd is not None and not hasattr(train_loader, "last_index"):
             raise ValueError("distillation needs a training loader that serves the store positions of its batches (last_index)")
@@ -323,6 +373,8 @@ class Trainer:
                 adv.stats.zero_()
             if kd is not None:
                 kd.stats.zero_()
+            if dro is not None:
+                dro.stats.zero_()
             if self.sam is not None:
                 eng.ensure_sam_state()
                 eng.zero_sam_stats()
@@ -336,8 +388,8 @@ class Trainer:
                                step=self.optimizer.step_count, dropout_p=self.model.dropout_p, seed=self.model._seed,
                                class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
                                mix_lambda=getattr(train_loader, "last_lam", None),      # the lam of the batch a mixup loader just served
-                               adversary=adv, distill=kd, sam=self.sam,
-                               batch_index=getattr(train_loader, "last_index", None) if adv is not None or kd is not None else None)
+                               adversary=adv, distill=kd, sam=self.sam, dro=dro,
+                               batch_index=getattr(train_loader, "last_index", None) if adv is not None or kd is not None or dro is not None else None)
                 if av is not None and av.mode == "ema":
                     eng.average_update(av.step_coef())
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
@@ -358,9 +410,12 @@ class Trainer:
             self.train_seconds += dt
             if av is not None and av.mode == "swa":
                 eng.average_update(av.epoch_coef(epoch + 1))     # the epoch-end iterate, from start_epoch on (before: no launch)
-            val_loss, val_acc, val_f1, _, _ = self.evaluate(val_loader, is_val=True)
+            val_loss, val_acc, val_f1, vp, vl = self.evaluate(val_loader, is_val=True)
             avg = self.validate_averaged(val_loader) if av is not None and av.validate else None
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds, sam):
+            drs = None
+            if dro is not None:
+                drs = self.dro_epoch(dro.stats.cpu().tolist(), dro.q.cpu().tolist(), self.val_worst_subject(val_loader, vp, vl))
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds, sam, drs):
                 break
         self.finish_averaging([train_loader])
         self._finish_training()
@@ -385,13 +440,16 @@ class Trainer:
         if recompute and av.bn == "recompute":
             AV.recompute_bn([eng], train_loaders)
 
-    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None, kd=None, sam=None) -> bool:
+    def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None, kd=None, sam=None,
+                      dro=None) -> bool:
         """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
         the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were.
         dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise.  avg: the validation pass under
         the averaging shadow when config['averaging']['validate'] is set (three more history keys; it steers nothing).  kd:
         Distillation.epoch_summary of the epoch for a student (set_distillation): kd_loss and kd_agreement, likewise.  sam:
-        sam.summary of the epoch when config['trainer']['sam'] is set: sam_grad_norm, sam_grad_norm_max and sam_sharpness, likewise."""
+        sam.summary of the epoch when config['trainer']['sam'] is set: sam_grad_norm, sam_grad_norm_max and sam_sharpness, likewise.
+        dro: dro_epoch of the epoch when config['trainer']['group_dro'] is set: the robust loss, the worst group's loss and subject,
+        max and entropy of q, the per-subject losses and weights and the worst validation subject, likewise (it steers nothing)."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
@@ -411,6 +469,13 @@ class Trainer:
             self.history[-1].update(sam)
             suffix += (f" | sam grad norm: {sam['sam_grad_norm']:.4f} (max {sam['sam_grad_norm_max']:.4f}) | "
                        f"sam sharpness: {sam['sam_sharpness']:.6f} (sam={self.sam.spec()})")
+        if dro is not None:
+            self.history[-1].update(dro)
+            if dro["dro_robust_loss"] is not None:
+                suffix += (f" | dro robust loss: {dro['dro_robust_loss']:.4f} | worst group loss: {dro['dro_worst_group_loss']:.4f} "
+                           f"({dro['dro_worst_subject']}) | q max: {dro['dro_q_max']:.4f} | q entropy: {dro['dro_q_entropy']:.4f}")
+            if dro["val_worst_subject_acc"] is not None:
+                suffix += f" | worst val subject: {dro['val_worst_subject']} acc {dro['val_worst_subject_acc']:.4f}"
         if avg is not None:
             self.history[-1].update(avg)
             if avg["val_loss_avg"] is not None:
