@@ -1,5 +1,6 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h).
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h, include/msig_nr.h,
+include/msig_rec.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -114,6 +115,7 @@ DRO_MAX_GROUPS = 64   # msig_dro.h MSIG_DRO_MAX_GROUPS: groups of one fold
 DRO_MAX_BATCH = 2048  # msig_dro.h MSIG_DRO_MAX_BATCH: rows of one step with the term
 DRO_STATS = 3 * DRO_MAX_GROUPS + 2      # msig_dro.h MSIG_DRO_STATS: T_g, W_g, n_g per group, the robust loss's sum, the steps
 NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
+REC_ABI_VERSION = 1   # include/msig_rec.h MSIG_REC_ABI_VERSION (statistics and normalised window batches straight from a continuous recording)
 
 
 class Multi(C.Structure):
@@ -447,6 +449,17 @@ def lib() -> C.CDLL:
         L.msig_nr_scratch_bytes.restype = C.c_int64
         L.msig_nr_normalise_subject.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_uint32, vp, vp, vp,
                                                 vp, vp]
+        # include/msig_rec.h, exported by the same library: statistics and window batches of a continuous recording
+        L.msig_rec_abi_version.restype = C.c_int
+        if L.msig_rec_abi_version() != REC_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_rec.h ABI {L.msig_rec_abi_version()}; this binding is {REC_ABI_VERSION}: rebuild the library")
+        L.msig_rec_scratch_bytes.restype = C.c_int64
+        L.msig_rec_count.argtypes = [i64, i64, i64]
+        L.msig_rec_count.restype = C.c_int64
+        rec = [vp, i64, i32, C.POINTER(i32), i32, C.c_uint32, i64, i64]      # sig, L, C_all, cols, C, log1p_mask, T, S
+        L.msig_rec_stats.argtypes = rec + [i64, i64, vp, vp, vp]
+        L.msig_rec_windows.argtypes = rec + [i64, i32, vp, vp, vp]
+        L.msig_rec_windows_multi.argtypes = rec + [i64, i32, vp, vp, C.POINTER(Multi), vp]
         _lib = L
     return _lib
 

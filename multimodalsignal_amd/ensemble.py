@@ -228,6 +228,34 @@ def write_seeds(run_output_dir, configurations: Dict[str, dict], seeds: int, syn
 
 
 # ---- the ensemble on the GPU ------------------------------------------------------------------------------------------------------
+def member_files(run_dir, subject: str, config_name: Optional[str] = None) -> List[Path]:
+    """The checkpoints of the fold that tested `subject` in the run at `run_dir` (configuration `config_name`): replica 0's
+    fold_test_on_<subject>/best_model.pt, then every seed_<r>/fold_test_on_<subject>/best_model.pt, r = 1, 2, ... while they exist."""
+    base = Path(run_dir) / config_name if config_name else Path(run_dir)
+    files, r = [base / f"fold_test_on_{subject}" / "best_model.pt"], 1
+    while (base / f"seed_{r}" / f"fold_test_on_{subject}" / "best_model.pt").exists():
+        files.append(base / f"seed_{r}" / f"fold_test_on_{subject}" / "best_model.pt")
+        r += 1
+    if not files[0].exists():
+        raise FileNotFoundError(files[0])
+    return files
+
+
+def load_members(files: Sequence, device="cuda") -> list:
+    """The models of the checkpoints `files`, in eval mode on `device`; the model kind, depth, C and K are read off each checkpoint."""
+    from .models import CnnGruAttentionModel, CnnGruModel
+    models = []
+    for f in files:
+        sd = torch.load(f, weights_only=True, map_location="cpu")
+        klass = CnnGruAttentionModel if "channel_attention.fc.0.weight" in sd else CnnGruModel
+        with torch.random.fork_rng(devices=[]):         # the constructor draws an initialisation: torch's RNG stays where it was
+            model = klass(in_channels=int(sd["cnn_encoder.0.weight"].shape[1]), num_classes=int(sd["classifier.3.weight"].shape[0]),
+                          gru_hidden_size=int(sd["gru.weight_hh_l0"].shape[1]), gru_num_layers=2 if "gru.weight_ih_l1" in sd else 1)
+        model.load_state_dict(sd)
+        models.append(model.to(device).eval())
+    return models
+
+
 @dataclass
 class EnsemblePrediction:
     """What Ensemble.predict returns, on the input's device — msig_en_reduce's outputs (include/msig_en.h): mean_p and std_p (N, K)
@@ -292,24 +320,7 @@ class Ensemble:
         """The ensemble of the fold that tested `subject` in the run at `run_dir` (configuration `config_name` of a --model / sweep
         run): replica 0's fold_test_on_<subject>/best_model.pt and every seed_<r>/fold_test_on_<subject>/best_model.pt, r = 1, 2, ...
         The model kind, depth, C and K are read off the checkpoints."""
-        from .models import CnnGruAttentionModel, CnnGruModel
-        base = Path(run_dir) / config_name if config_name else Path(run_dir)
-        files, r = [base / f"fold_test_on_{subject}" / "best_model.pt"], 1
-        while (base / f"seed_{r}" / f"fold_test_on_{subject}" / "best_model.pt").exists():
-            files.append(base / f"seed_{r}" / f"fold_test_on_{subject}" / "best_model.pt")
-            r += 1
-        if not files[0].exists():
-            raise FileNotFoundError(files[0])
-        models = []
-        for f in files:
-            sd = torch.load(f, weights_only=True, map_location="cpu")
-            klass = CnnGruAttentionModel if "channel_attention.fc.0.weight" in sd else CnnGruModel
-            with torch.random.fork_rng(devices=[]):         # the constructor draws an initialisation: torch's RNG stays where it was
-                model = klass(in_channels=int(sd["cnn_encoder.0.weight"].shape[1]), num_classes=int(sd["classifier.3.weight"].shape[0]),
-                              gru_hidden_size=int(sd["gru.weight_hh_l0"].shape[1]), gru_num_layers=2 if "gru.weight_ih_l1" in sd else 1)
-            model.load_state_dict(sd)
-            models.append(model.to(device).eval())
-        return cls(models, **kw)
+        return cls(load_members(member_files(run_dir, subject, config_name), device), **kw)
 
     # ---- the arenas -------------------------------------------------------------------------------------------------------------
     def _arenas(self, T: int, sizes: Sequence[int]):
@@ -349,6 +360,11 @@ class Ensemble:
             raise ValueError(f"expected float32 (N, {self.C}, T >= 16) input, got {x.dtype} {tuple(x.shape)}")
         return x.detach().contiguous()
 
+    def _fill(self, x, i: int, b: int, n: int):
+        """Windows i .. i + b - 1 of x into the x buffer of arenas 0 .. n - 1 (monitor.RecordingEnsemble fills them from a recording)."""
+        for s in range(n):
+            self.arenas.view(s, "x", torch.float32)[:b * self.C * self.T].copy_(x[i:i + b].reshape(-1))
+
     def _reduce(self, x, in_slots, stacked):
         """The members' eval forwards over x in chunks of members and pieces of windows, then the reduction: with batched=True and
         M <= MAX_FOLDS `in_slots(logits0, multi, first window, windows, stream)` per piece, on the logits where
@@ -363,8 +379,7 @@ class Ensemble:
             n = min(self.slots, M - m0)
             self._load(m0, n)
             for i, b in pieces:
-                for s in range(n):
-                    self.arenas.view(s, "x", torch.float32)[:b * self.C * T].copy_(x[i:i + b].reshape(-1))
+                self._fill(x, i, b, n)
                 if self.batched:
                     multi = self.arenas.multi(range(n))
                     L.check(lib.msig_st_forward_multi(C.byref(self._desc(b)), C.byref(multi), C.byref(self._st), st), "msig_st_forward_multi")

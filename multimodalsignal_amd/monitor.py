@@ -1,0 +1,413 @@
+"""A finished run applied to a continuous recording: the stress timeline (include/msig_rec.h).
+
+A wearable's output is one multichannel signal, not windows.  `RecordingWindows` holds the (L, C_all) float64 recording on the GPU
+and hands out its 60 s / 10 s-stride windows normalised and transposed — msig_rec_stats and msig_rec_windows[_multi] read the
+recording itself, the windows are never materialised.  `Monitor` runs an ensemble's eval forwards over them on `Ensemble`'s arenas
+(msig_st_forward[_multi], msig_en_reduce[_multi]; each piece of windows is filled into every member's arena by one
+msig_rec_windows_multi) and turns the positive class's probability into a smoothed score, a hysteresis state and a list of events.
+
+The host helpers (`parse_recording_reference`, `ema`, `hysteresis`, `find_events`, `Timeline`, the CLI's argument checks) need no
+GPU (`count_windows` asks the library, which loads without one).  `RecordingWindows` and `Monitor.run` have no CPU fallback.
+
+Out of scope: a live push(samples) interface, sharing the front end between overlapping windows (not exact: the channel gate is a
+mean over ONE window and the convolutions pad at ITS edges) and the hand-crafted feature branch.
+
+CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
+      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K] [--stride-s 10] --out DIR
+"""
+from __future__ import annotations
+
+import argparse
+import ast
+import ctypes as C
+import json
+import re
+from dataclasses import dataclass, field
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .ensemble import Ensemble, load_members, member_files
+
+SYNTHETIC_NOTE = ("synthetic recording: the stress phases are planted and easy, so the timeline shows that the recording-to-events "
+                  "machinery works, not what detection is worth on WESAD")
+SYNTHETIC_PHASES = [(1, 600.0), (2, 300.0), (4, 300.0), (3, 240.0), (2, 360.0), (1, 600.0)]      # 40 minutes
+
+
+# ---- the parts that need no GPU ---------------------------------------------------------------------------------------------------
+def count_windows(L_: int, T: int, S: int) -> int:
+    """msig_rec_count: the windows [n * S, n * S + T) inside L samples; 0 if L < T."""
+    n = int(L.lib().msig_rec_count(int(L_), int(T), int(S)))
+    if n < 0:
+        raise ValueError(f"window length and stride must be >= 1, got {T} and {S}")
+    return n
+
+
+def parse_recording_reference(reference, n: int):
+    """Which windows supply a recording's mean and std: "recording" (all of them: the counterpart of training's --norm-reference
+    subject), "head:K" (the first K >= 1: the counterpart of baseline:K, 60 + 10 (K - 1) seconds at the default window and
+    stride) or a pair (w0, w1) of window indices, 0 <= w0 < w1 <= n.  Returns (w0, w1, warm-up windows) — the warm-up count is K
+    for "head:K" and 0 otherwise.  A tensor of statistics is not parsed here (RecordingWindows takes it as it is)."""
+    if reference == "recording":
+        return 0, int(n), 0
+    if isinstance(reference, str) and reference.startswith("head:"):
+        k = reference[len("head:"):]
+        if k.isascii() and k.isdigit() and int(k) >= 1:
+            if int(k) > n:
+                raise ValueError(f"reference {reference!r} needs {int(k)} windows; the recording has {n}")
+            return 0, int(k), int(k)
+        raise ValueError(f"reference must be 'recording', 'head:K' with K >= 1, a (w0, w1) pair or a statistics tensor, got {reference!r}")
+    if isinstance(reference, (tuple, list)) and len(reference) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+                                                                             for v in reference):
+        w0, w1 = int(reference[0]), int(reference[1])
+        if not 0 <= w0 < w1 <= n:
+            raise ValueError(f"reference windows must satisfy 0 <= w0 < w1 <= {n}, got {reference!r}")
+        return w0, w1, 0
+    raise ValueError(f"reference must be 'recording', 'head:K' with K >= 1, a (w0, w1) pair or a statistics tensor, got {reference!r}")
+
+
+def ema(score, halflife: float) -> np.ndarray:
+    """The causal exponential moving average in float64: s_0 = score_0, s_n = s_{n-1} + a (score_n - s_{n-1}) with
+    a = 1 - 2^(-1 / halflife) — after `halflife` windows a step has covered half its height.  halflife 0: the score itself."""
+    x = np.asarray(score, dtype=np.float64).reshape(-1)
+    if not halflife >= 0:
+        raise ValueError(f"halflife must be >= 0 windows, got {halflife!r}")
+    a = 1.0 if halflife == 0 else 1.0 - 2.0 ** (-1.0 / float(halflife))
+    out = np.empty_like(x)
+    s = 0.0
+    for n, v in enumerate(x):
+        s = float(v) if n == 0 else s + a * (float(v) - s)
+        out[n] = s
+    return out
+
+
+def hysteresis(smoothed, on: float, off: float, min_on: int = 1) -> np.ndarray:
+    """The state machine over a smoothed score: off at the start, on from the window where smoothed >= `on`, off again from the
+    window where smoothed <= `off` (off < on: between the two the state holds).  An episode — a maximal run of on windows — shorter
+    than `min_on` windows is dropped.  Returns (N,) bool."""
+    if not off < on:
+        raise ValueError(f"hysteresis needs off < on, got off = {off!r}, on = {on!r}")
+    if isinstance(min_on, bool) or int(min_on) < 1:
+        raise ValueError(f"min_on must be an integer >= 1, got {min_on!r}")
+    x = np.asarray(smoothed, dtype=np.float64).reshape(-1)
+    state = np.zeros(x.size, dtype=bool)
+    cur = False
+    for n, v in enumerate(x):
+        if not cur and v >= on:
+            cur = True
+        elif cur and v <= off:
+            cur = False
+        state[n] = cur
+    for a, b in _runs(state):
+        if b - a < int(min_on):
+            state[a:b] = False
+    return state
+
+
+def _runs(state) -> List[Tuple[int, int]]:
+    """The maximal runs of True in a bool vector as (first, one past last)."""
+    s = np.concatenate(([False], np.asarray(state, dtype=bool), [False]))
+    edges = np.flatnonzero(s[1:] != s[:-1])
+    return [(int(a), int(b)) for a, b in zip(edges[0::2], edges[1::2])]
+
+
+def find_events(state, smoothed, t_end) -> List[Tuple[float, float, float, float]]:
+    """(start_s, end_s, peak, mean) of every episode of `state`: the end time of its first and of its last window (an episode is
+    known from the moment its first window is complete), and the maximum and the mean of the smoothed score over it."""
+    x, t = np.asarray(smoothed, dtype=np.float64), np.asarray(t_end, dtype=np.float64)
+    return [(float(t[a]), float(t[b - 1]), float(x[a:b].max()), float(x[a:b].mean())) for a, b in _runs(state)]
+
+
+@dataclass
+class Timeline:
+    """What Monitor.run returns, on the host: per window its end time t_end = (n S + T) / fs in seconds, the ensemble's mean_p and
+    std_p (N, K), pred, entropy, mutual_info (N,), votes (N, K), score = mean_p[:, positive], smoothed (float64), state (bool),
+    warmup (bool: the window supplied the statistics of a "head:K" reference); `events` as find_events lists them; `meta` the
+    settings."""
+    t_end: np.ndarray
+    mean_p: np.ndarray
+    std_p: np.ndarray
+    pred: np.ndarray
+    entropy: np.ndarray
+    mutual_info: np.ndarray
+    votes: np.ndarray
+    score: np.ndarray
+    smoothed: np.ndarray
+    state: np.ndarray
+    warmup: np.ndarray
+    events: List[Tuple[float, float, float, float]]
+    meta: dict = field(default_factory=dict)
+
+    def to_csv(self, path) -> Path:
+        path = Path(path)
+        lines = ["window,t_end_s,score,std,smoothed,state,pred,entropy,mutual_info,warmup"]
+        pos = int(self.meta.get("positive", 1))
+        for n in range(len(self.t_end)):
+            lines.append(f"{n},{self.t_end[n]:.6f},{self.score[n]:.9g},{self.std_p[n, pos]:.9g},{self.smoothed[n]:.9g},{int(self.state[n])},"
+                         f"{int(self.pred[n])},{self.entropy[n]:.9g},{self.mutual_info[n]:.9g},{int(self.warmup[n])}")
+        path.write_text("\n".join(lines) + "\n")
+        return path
+
+    def to_json(self, path) -> Path:
+        path = Path(path)
+        doc = dict(self.meta, windows=int(len(self.t_end)), flagged_windows=int(self.state.sum()),
+                   events=[dict(start_s=a, end_s=b, peak=p, mean=m) for a, b, p, m in self.events])
+        path.write_text(json.dumps(doc, indent=1))
+        return path
+
+
+def phase_shares(timeline: Timeline, table, T: int, S: int) -> dict:
+    """Of the windows that lie wholly inside a phase of a synthetic recording's phase table, the share flagged per raw label."""
+    out = {}
+    for row in table:
+        n = np.arange(len(timeline.t_end))
+        inside = (n * S >= row["start"]) & (n * S + T <= row["end"])
+        tot, hit = out.get(row["label"], (0, 0))
+        out[row["label"]] = (tot + int(inside.sum()), hit + int(timeline.state[inside].sum()))
+    return {str(k): {"windows": t, "flagged": h, "share": (h / t if t else None)} for k, (t, h) in sorted(out.items())}
+
+
+# ---- the recording on the GPU ------------------------------------------------------------------------------------------------------
+class RecordingWindows:
+    """The windows [n * stride, n * stride + T) of a (L, C_all) float64 recording (a numpy array, uploaded, or a GPU tensor), columns
+    `names`, of which `channels` are selected in that order; the channel literally named 'chest_EDA' is log1p-transformed first, as
+    in dataset.normalise_subject_device.  `reference`: parse_recording_reference, or a float64 tensor of 2 * MAX_C + 1 statistics
+    (msig_nr.h's layout) taken as it is.  `.n` windows, `.shape` = (n, C, T), `.stats` the statistics on the device, `.warmup` the
+    number of leading windows that supplied them ("head:K")."""
+
+    def __init__(self, sig, names: Sequence[str], channels: Sequence[str], T: int, stride: int,
+                 reference: Union[str, tuple, torch.Tensor] = "recording", device="cuda"):
+        if isinstance(sig, np.ndarray):
+            sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float64)).to(device)
+        if not isinstance(sig, torch.Tensor) or not sig.is_cuda or sig.dtype != torch.float64 or sig.dim() != 2:
+            raise ValueError("a recording is a (L, C_all) float64 array: numpy, or a tensor on the GPU (there is no CPU fallback)")
+        names, channels = list(names), list(channels)
+        if len(names) != sig.shape[1]:
+            raise ValueError(f"{len(names)} channel names for a recording of {sig.shape[1]} columns")
+        if not 1 <= len(channels) <= L.MAX_C:
+            raise ValueError(f"1..{L.MAX_C} channels can be selected, got {len(channels)}")
+        missing = [c for c in channels if c not in names]
+        if missing:
+            raise ValueError(f"the recording has no channel {missing}; it has {names}")
+        self.sig, self.device = sig.contiguous(), sig.device
+        self.L, self.C_all = int(sig.shape[0]), int(sig.shape[1])
+        self.T, self.S, self.C = int(T), int(stride), len(channels)
+        self.n = count_windows(self.L, self.T, self.S)
+        if self.n < 1:
+            raise ValueError(f"the recording has {self.L} samples: shorter than one window of {self.T}")
+        self.shape = (self.n, self.C, self.T)
+        self.cols = (C.c_int32 * self.C)(*[names.index(c) for c in channels])
+        self.mask = sum(1 << c for c, name in enumerate(channels) if name == "chest_EDA")
+        if isinstance(reference, torch.Tensor):
+            if reference.dtype != torch.float64 or reference.numel() < 2 * L.MAX_C + 1:
+                raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
+            self.stats, self.reference_windows, self.warmup = reference.to(self.device).contiguous().clone(), None, 0
+        else:
+            w0, w1, self.warmup = parse_recording_reference(reference, self.n)
+            self.reference_windows = (w0, w1)
+            self.stats = torch.empty(2 * L.MAX_C + 1, dtype=torch.float64, device=self.device)
+            scratch = torch.empty(L.lib().msig_rec_scratch_bytes(), dtype=torch.uint8, device=self.device)
+            L.check(L.lib().msig_rec_stats(*self._head(), w0, w1, self.stats.data_ptr(), scratch.data_ptr(), self._stream()), "msig_rec_stats")
+
+    def _head(self):
+        return self.sig.data_ptr(), self.L, self.C_all, self.cols, self.C, self.mask, self.T, self.S
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def batch(self, n0: int, B: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Windows n0 .. n0 + B - 1 as a (B, C, T) float32 tensor (msig_rec_windows)."""
+        if out is None:
+            out = torch.empty((int(B), self.C, self.T), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (int(B), self.C, self.T) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 ({B}, {self.C}, {self.T}) tensor on {self.device}")
+        L.check(L.lib().msig_rec_windows(*self._head(), int(n0), int(B), self.stats.data_ptr(), out.data_ptr(), self._stream()),
+                "msig_rec_windows")
+        return out
+
+    def fill(self, x0: int, multi: L.Multi, n0: int, B: int):
+        """Windows n0 .. n0 + B - 1 into the x buffer of every arena slot of `multi`; x0 is arena 0's (msig_rec_windows_multi)."""
+        L.check(L.lib().msig_rec_windows_multi(*self._head(), int(n0), int(B), self.stats.data_ptr(), x0, C.byref(multi), self._stream()),
+                "msig_rec_windows_multi")
+
+    def materialise(self) -> torch.Tensor:
+        """Every window, (n, C, T) float32, in one msig_rec_windows call.  For tests: it is the copy a monitor avoids."""
+        return self.batch(0, self.n)
+
+
+class RecordingEnsemble(Ensemble):
+    """An Ensemble whose input is a RecordingWindows: predict(rw) runs Ensemble's own pieces, forwards and reduction; only the
+    filling of the arenas differs — one msig_rec_windows_multi per piece instead of a copy per member."""
+
+    def _check_x(self, x):
+        if not isinstance(x, RecordingWindows):
+            return super()._check_x(x)
+        if x.device != self.device or x.C != self.C or x.T < 16:
+            raise ValueError(f"expected windows of {self.C} channels and T >= 16 on {self.device}, got {x.C} channels, T = {x.T} on {x.device}")
+        return x
+
+    def _fill(self, x, i: int, b: int, n: int):
+        if not isinstance(x, RecordingWindows):
+            return super()._fill(x, i, b, n)
+        x.fill(self.arenas.ptr("x"), self.arenas.multi(range(n)), i, b)
+
+
+class Monitor:
+    """An ensemble of 1..256 trained models (M = 1: one model) over continuous recordings sampled at `fs` Hz: windows of `window_s`
+    seconds every `stride_s`, normalised by `reference` (parse_recording_reference), `eval_batch` windows per piece.  `channels`: the
+    names of the models' input channels in their order (None: the recording's columns as they come).  score = the probability of
+    class `positive`; smoothed = ema(score, halflife) (in windows); state = hysteresis(smoothed, on, off, min_on)."""
+
+    def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="recording", eval_batch: int = 256,
+                 positive: int = 1, halflife: float = 3, on: float = 0.6, off: float = 0.4, min_on: int = 2,
+                 channels: Optional[Sequence[str]] = None):
+        if not float(fs) > 0:
+            raise ValueError(f"fs must be > 0, got {fs!r}")
+        self.fs = float(fs)
+        self.T, self.S = int(round(float(window_s) * self.fs)), int(round(float(stride_s) * self.fs))
+        if self.T < 16 or self.S < 1:
+            raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
+        hysteresis([], on, off, min_on)
+        ema([], halflife)
+        self.ensemble = RecordingEnsemble(models, eval_batch=eval_batch)
+        if not 0 <= int(positive) < self.ensemble.K:
+            raise ValueError(f"positive must be a class in 0..{self.ensemble.K - 1}, got {positive!r}")
+        self.reference, self.positive, self.halflife, self.on, self.off, self.min_on = reference, int(positive), float(halflife), float(on), float(off), int(min_on)
+        self.channels = None if channels is None else list(channels)
+        if self.channels is not None and len(self.channels) != self.ensemble.C:
+            raise ValueError(f"the models take {self.ensemble.C} channels, got {len(self.channels)} names")
+        self.files: List[Path] = []
+
+    @staticmethod
+    def run_files(run_dir, subject: Optional[str] = None, config_name: Optional[str] = None) -> List[Path]:
+        """The checkpoints from_run loads.  `subject` given: that fold's members by Ensemble.from_run's rule (ensemble.member_files).
+        None — the recording is of a person no fold held out: replica 0 of every fold, fold_test_on_*/best_model.pt in natural order
+        of the subject names (S2 before S10)."""
+        if subject is not None:
+            return member_files(run_dir, subject, config_name)
+        base = Path(run_dir) / config_name if config_name else Path(run_dir)
+        files = [d / "best_model.pt" for d in base.glob("fold_test_on_*") if (d / "best_model.pt").exists()]
+        if not files:
+            raise FileNotFoundError(f"no fold_test_on_*/best_model.pt below {base}")
+        return sorted(files, key=lambda f: [int(p) if p.isdigit() else p for p in re.split(r"(\d+)", f.parent.name)])
+
+    @staticmethod
+    def run_channels(run_dir, config_name: Optional[str] = None) -> Optional[List[str]]:
+        """CHANNELS_TO_USE of the run's cv_summary.txt, or None where there is none."""
+        base = Path(run_dir) / config_name if config_name else Path(run_dir)
+        for path in (base / "cv_summary.txt", Path(run_dir) / "cv_summary.txt"):
+            if path.exists():
+                for line in path.read_text(encoding="utf-8").splitlines():
+                    if line.startswith("CHANNELS_TO_USE:"):
+                        return [str(c) for c in ast.literal_eval(line.split(":", 1)[1].strip())]
+        return None
+
+    @classmethod
+    def from_run(cls, run_dir, subject: Optional[str] = None, config_name: Optional[str] = None, fs: float = 64.0, device="cuda", **kw) -> "Monitor":
+        files = cls.run_files(run_dir, subject, config_name)
+        kw.setdefault("channels", cls.run_channels(run_dir, config_name))
+        self = cls(load_members(files, device), fs, **kw)
+        self.files = files
+        return self
+
+    def windows(self, sig, names: Sequence[str]) -> RecordingWindows:
+        names = list(names)
+        return RecordingWindows(sig, names, self.channels if self.channels is not None else names, self.T, self.S, self.reference,
+                                device=self.ensemble.device)
+
+    @torch.no_grad()
+    def run(self, sig, names: Sequence[str]) -> Timeline:
+        rw = self.windows(sig, names)
+        p = self.ensemble.predict(rw)
+        host = lambda t: t.cpu().numpy()      # noqa: E731
+        mean_p = host(p.mean_p)
+        score = mean_p[:, self.positive].astype(np.float64)
+        t_end = (np.arange(rw.n, dtype=np.float64) * self.S + self.T) / self.fs
+        smoothed = ema(score, self.halflife)
+        state = hysteresis(smoothed, self.on, self.off, self.min_on)
+        warmup = np.arange(rw.n) < rw.warmup
+        meta = dict(fs=self.fs, window_samples=self.T, stride_samples=self.S, members=self.ensemble.M, positive=self.positive,
+                    halflife=self.halflife, on=self.on, off=self.off, min_on=self.min_on, samples=rw.L,
+                    reference=self.reference if isinstance(self.reference, str) else ("statistics" if rw.reference_windows is None
+                                                                                      else list(rw.reference_windows)),
+                    warmup_windows=int(rw.warmup), files=[str(f) for f in self.files])
+        return Timeline(t_end=t_end, mean_p=mean_p, std_p=host(p.std_p), pred=host(p.pred), entropy=host(p.entropy),
+                        mutual_info=host(p.mutual_info), votes=host(p.votes), score=score, smoothed=smoothed, state=state, warmup=warmup,
+                        events=find_events(state, smoothed, t_end), meta=meta)
+
+
+# ---- the command line ----------------------------------------------------------------------------------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m multimodalsignal_amd.monitor",
+                                 description="The stress timeline of a continuous recording from a trained run: timeline.csv and timeline.json.")
+    ap.add_argument("--run", type=Path, required=True, help="the run directory (the one that holds fold_test_on_*/)")
+    ap.add_argument("--subject", default=None, help="use the members of the fold that tested this subject (default: replica 0 of every fold)")
+    ap.add_argument("--config", default=None, help="configuration name of a --model / sweep run")
+    ap.add_argument("--recording", type=Path, default=None, help="(L, C_all) float64 .npy")
+    ap.add_argument("--names", type=Path, default=None, help="the recording's channel names, one per line")
+    ap.add_argument("--synthetic-recording", action="store_true", help="a seeded 40-minute recording with planted stress phases")
+    ap.add_argument("--fs", type=float, default=64.0, help="sampling rate the models were trained at")
+    ap.add_argument("--resample-from", type=float, default=None, help="the recording's own sampling rate: it is resampled to --fs first")
+    ap.add_argument("--reference", default="recording", help="recording | head:K")
+    ap.add_argument("--window-s", type=float, default=60.0)
+    ap.add_argument("--stride-s", type=float, default=10.0)
+    ap.add_argument("--seed", type=int, default=42, help="seed of --synthetic-recording")
+    ap.add_argument("--difficulty", type=float, default=1.0, help="difficulty of --synthetic-recording")
+    ap.add_argument("--out", type=Path, required=True)
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """The arguments, checked before anything touches the GPU."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.synthetic_recording == (a.recording is not None):
+        ap.error("give exactly one of --recording X.npy and --synthetic-recording")
+    if a.recording is not None and a.names is None:
+        ap.error("--recording needs --names FILE (one channel name per line)")
+    if a.synthetic_recording and (a.names is not None or a.resample_from is not None):
+        ap.error("--synthetic-recording takes neither --names nor --resample-from")
+    if not a.fs > 0 or (a.resample_from is not None and not a.resample_from > 0):
+        ap.error("--fs and --resample-from must be > 0")
+    if not a.window_s > 0 or not a.stride_s > 0:
+        ap.error("--window-s and --stride-s must be > 0")
+    try:
+        parse_recording_reference(a.reference, 1 << 62)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def main(argv=None) -> Timeline:
+    a = parse_args(argv)
+    mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference)
+    table = None
+    if a.synthetic_recording:
+        from .synth import CHANNELS6, make_synthetic_recording
+        names = list(CHANNELS6)
+        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty)
+    else:
+        sig = np.load(a.recording)
+        names = [ln.strip() for ln in a.names.read_text().splitlines() if ln.strip()]
+    sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float64)).to(mon.ensemble.device)
+    if a.resample_from is not None:
+        from .preprocess import resample_device
+        sig = resample_device(sig, int(sig.shape[0] * (a.fs / a.resample_from)))
+    tl = mon.run(sig, names)
+    if table is not None:
+        tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, mon.T, mon.S))
+    a.out.mkdir(parents=True, exist_ok=True)
+    tl.to_csv(a.out / "timeline.csv")
+    path = tl.to_json(a.out / "timeline.json")
+    print(f"{len(tl.t_end)} windows, {int(tl.state.sum())} flagged, {len(tl.events)} events; timeline written to: {path}")
+    if table is not None:
+        print("NOTE: " + SYNTHETIC_NOTE + ".")
+        print("flagged windows by raw label: " + json.dumps(tl.meta["flagged_by_label"]))
+    return tl
+
+
+if __name__ == "__main__":
+    main()

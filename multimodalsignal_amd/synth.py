@@ -59,3 +59,53 @@ def make_synthetic_wesad(out_dir, subjects=ALL_SUBJECTS, windows_per_subject=270
         np.save(out / f"{sid}_y.npy", y.astype(np.int64))
     (out / "_channel_names.txt").write_text("\n".join(channels) + "\n")
     return out
+
+
+def make_synthetic_recording(phases, fs=64.0, channels=CHANNELS6, seed=42, difficulty=1.0, block_s=60.0):
+    """ONE continuous recording with make_synthetic_wesad's planted effects, piecewise per protocol phase: `phases` is a list of
+    (raw label 1..4, seconds).  Returns (sig (L, C) float64, phase table) — the table one dict per phase with its raw label, its
+    first and one-past-last sample and the same in seconds.
+
+    What make_synthetic_wesad draws per window (heart and breathing rate, tonic EDA level) is drawn here per `block_s` seconds of a
+    phase and held; the two rhythms' frequencies are integrated over the whole recording, so their phase is continuous across
+    blocks and protocol phases; the EDA ramp of the stress class rises over the first `block_s` seconds of a stress phase and
+    stays.  Subject gain and offset are one draw for the recording.  The draws are this function's own (RandomState(seed)):
+    make_synthetic_wesad's stream and files do not depend on it."""
+    phases = [(int(lab), float(sec)) for lab, sec in phases]
+    if not phases or any(lab not in (1, 2, 3, 4) or not sec > 0 for lab, sec in phases):
+        raise ValueError(f"phases must be a non-empty list of (raw label 1..4, seconds > 0), got {phases!r}")
+    rs = np.random.RandomState(seed)
+    C = len(channels)
+    a = 1.0 / float(difficulty)
+    lens = [int(round(sec * fs)) for _, sec in phases]
+    L = int(sum(lens))
+    table, at = [], 0
+    for (lab, _), n in zip(phases, lens):
+        table.append({"label": lab, "start": at, "end": at + n, "start_s": at / fs, "end_s": (at + n) / fs})
+        at += n
+    gain = 0.7 + 0.6 * rs.rand(C)
+    offs = rs.randn(C)
+    x = rs.randn(L, C)
+    t = np.arange(L) / fs
+    stress, hr, level, br, ramp = (np.zeros(L) for _ in range(5))
+    blk = max(1, int(round(block_s * fs)))
+    for row in table:
+        s = 1.0 if row["label"] == 2 else 0.0
+        for b0 in range(row["start"], row["end"], blk):
+            b1 = min(b0 + blk, row["end"])
+            hr[b0:b1] = 1.1 + 0.30 * a * s + 0.12 * rs.randn()
+            level[b0:b1] = 1.0 + 0.5 * a * s + 0.35 * rs.randn()
+            br[b0:b1] = 0.25 + 0.06 * a * s + 0.04 * rs.randn()
+        stress[row["start"]:row["end"]] = s
+        ramp[row["start"]:row["end"]] = np.minimum(t[row["start"]:row["end"]] - row["start_s"], block_s)
+    x[:, 0] += 1.5 * np.sin(2 * np.pi * np.cumsum(hr) / fs + rs.rand() * 6.28)
+    if C > 1:
+        x[:, 1] = np.abs(x[:, 1]) * 0.2 + np.abs(level) + 0.0015 * a * ramp * stress
+    if C > 2:
+        x[:, 2] += np.sin(2 * np.pi * np.cumsum(br) / fs)
+    for c in range(3, C):
+        x[:, c] += 0.3 * a * stress * np.sin(2 * np.pi * (0.5 + 0.1 * c) * t)
+    x = x * gain[None, :] + offs[None, :]
+    if C > 1:
+        x[:, 1] = np.abs(x[:, 1]) + 0.05
+    return np.ascontiguousarray(x, dtype=np.float64), table
