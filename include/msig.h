@@ -248,12 +248,15 @@ int msig_train_step_multi(const msig_batch* b, const msig_multi* m, float* exp_a
 uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stream_id);
 
 /* dataset.py:62-65 batched: gathers windows idx[0..B) from a device-resident
- * (N,C,T) fp32 store into a contiguous (B,C,T) batch plus labels. */
+ * (N,C,T) fp32 store into a contiguous (B,C,T) batch plus labels.  window_floats = C * T is any count >= 1
+ * (0 or negative: MSIG_E_SHAPE).  A multiple of 4 is copied by 16-byte vectors, and store and out_x must then be
+ * 16-byte aligned (MSIG_E_ALIGN); any other count is copied element by element with no alignment demand. */
 int msig_gather_windows(const float* store, const int64_t* store_labels, const int64_t* idx, int32_t B,
                         int64_t window_floats, float* out_x, int64_t* out_y, void* stream);
 
 /* The same for a fold batch: row z of idx (rows idx_row_stride elements apart, >= B) holds fold z's window indices into
- * the SHARED store, and the outputs of fold z land in arena m->slot[z] (out_x / out_y are arena 0's buffers). */
+ * the SHARED store, and the outputs of fold z land in arena m->slot[z] (out_x / out_y are arena 0's buffers).
+ * window_floats: the rule of msig_gather_windows. */
 int msig_gather_windows_multi(const float* store, const int64_t* store_labels, const int64_t* idx, int64_t idx_row_stride, int32_t B,
                               int64_t window_floats, float* out_x, int64_t* out_y, const msig_multi* m, void* stream);
 

@@ -856,16 +856,16 @@ extern "C" uint32_t msig_dropout_key(uint64_t seed, uint64_t step, uint32_t stre
 extern "C" int msig_gather_windows(const float* store, const int64_t* store_labels, const int64_t* idx, int32_t B,
                                    int64_t window_floats, float* out_x, int64_t* out_y, void* stream) {
   if (!store || !idx || !out_x) return MSIG_E_NULL;
-  if (B < 1 || window_floats < 4 || (window_floats & 3)) return MSIG_E_SHAPE;
-  if (((uintptr_t)store | (uintptr_t)out_x) & 15) return MSIG_E_ALIGN;
+  if (B < 1 || window_floats < 1) return MSIG_E_SHAPE;
+  if (!(window_floats & 3) && (((uintptr_t)store | (uintptr_t)out_x) & 15)) return MSIG_E_ALIGN;      // the float4 copy; any other length goes element by element
   return launch_gather(store, store_labels, idx, B, B, window_floats, out_x, out_y, single_fold(nullptr), (hipStream_t)stream);
 }
 
 extern "C" int msig_gather_windows_multi(const float* store, const int64_t* store_labels, const int64_t* idx, int64_t idx_row_stride, int32_t B,
                                          int64_t window_floats, float* out_x, int64_t* out_y, const msig_multi* m, void* stream) {
   if (!store || !idx || !out_x || !m) return MSIG_E_NULL;
-  if (B < 1 || idx_row_stride < B || window_floats < 4 || (window_floats & 3)) return MSIG_E_SHAPE;
-  if (((uintptr_t)store | (uintptr_t)out_x) & 15) return MSIG_E_ALIGN;
+  if (B < 1 || idx_row_stride < B || window_floats < 1) return MSIG_E_SHAPE;
+  if (!(window_floats & 3) && (((uintptr_t)store | (uintptr_t)out_x) & 15)) return MSIG_E_ALIGN;
   msig_batch dummy{};
   FoldCtx fc; int rc = make_fold_ctx(&dummy, m, fc); if (rc) return rc;
   return launch_gather(store, store_labels, idx, idx_row_stride, B, window_floats, out_x, out_y, fc, (hipStream_t)stream);

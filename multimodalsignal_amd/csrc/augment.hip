@@ -1,4 +1,5 @@
-// The window gathers.  gather_kernel is the plain float4 copy (msig_gather_windows*, api.hip).  On-device window augmentation inside
+// The window gathers.  gather_kernel is the plain copy (msig_gather_windows*, api.hip): by float4 when the window's float count is a
+// multiple of 4, element by element otherwise (any window length: C * T need not be a multiple of 4).  On-device window augmentation inside
 // the training gather (include/msig_aug.h) is that copy with per-channel magnitude scaling, additive jitter, a
 // time mask and channel dropout applied in registers.  A streaming kernel: every input byte is read once and every output byte
 // written once, as in the plain gather; the draws are counter-based hashes of (key, row, channel, sample), so there is no state and
@@ -10,25 +11,32 @@
 
 int msig_multi_fold_ctx(const msig_multi* m, FoldCtx& fc);                                  // api.hip: msig_multi's own checks
 
-// blockIdx.z = fold (msig_gather_windows_multi): the store is shared, idx is (n, B) contiguous, the outputs are per-arena
+// blockIdx.z = fold (msig_gather_windows_multi): the store is shared, idx is (n, B) contiguous, the outputs are per-arena.
+// V = float4: wv = window_floats / 4, rows 16-byte aligned (the caller checks); V = float: wv = window_floats, no alignment demand.
+template <typename V>
 __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ store, const int64_t* __restrict__ store_y,
-                                                     const int64_t* __restrict__ idx, int64_t idx_row_stride, int64_t w4,
+                                                     const int64_t* __restrict__ idx, int64_t idx_row_stride, int64_t wv,
                                                      float* __restrict__ ox, int64_t* __restrict__ oy, const FoldCtx fc) {
   FOLD_BEGIN; FS(ox); FS(oy);
   const int i = blockIdx.y;
   const int64_t src = idx[(int64_t)blockIdx.z * idx_row_stride + i];
-  const float4* s4 = (const float4*)(store) + src * w4;
-  float4* d4 = (float4*)(ox) + (int64_t)i * w4;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < w4; j += (int64_t)gridDim.x * 256) d4[j] = s4[j];
+  const V* sv = (const V*)(store) + src * wv;
+  V* dv = (V*)(ox) + (int64_t)i * wv;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < wv; j += (int64_t)gridDim.x * 256) dv[j] = sv[j];
   if (oy && store_y && blockIdx.x == 0 && threadIdx.x == 0) oy[i] = store_y[src];
 }
 
 int launch_gather(const float* store, const int64_t* sy, const int64_t* idx, int64_t idx_row_stride, int B, int64_t wfloats, float* ox, int64_t* oy,
                   const FoldCtx& fc, hipStream_t st) {
-  const int64_t w4 = wfloats / 4;
-  int gx = (int)((w4 + 255) / 256);
+  const bool vec = (wfloats & 3) == 0;
+  const int64_t wv = vec ? wfloats / 4 : wfloats;
+  int gx = (int)((wv + 255) / 256);
   if (gx > 64) gx = 64;
-  { MSIG_K("gather", st); gather_kernel<<<dim3(gx, B, fc.n), 256, 0, st>>>(store, sy, idx, idx_row_stride, w4, ox, oy, fc); }
+  {
+    MSIG_K("gather", st);
+    if (vec) gather_kernel<float4><<<dim3(gx, B, fc.n), 256, 0, st>>>(store, sy, idx, idx_row_stride, wv, ox, oy, fc);
+    else gather_kernel<float><<<dim3(gx, B, fc.n), 256, 0, st>>>(store, sy, idx, idx_row_stride, wv, ox, oy, fc);
+  }
   MSIG_LAUNCH_CHECK();
   return 0;
 }

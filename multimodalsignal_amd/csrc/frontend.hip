@@ -184,7 +184,7 @@ __device__ __forceinline__ void stage_x_chunk(float* xs, const float* __restrict
       const int c = i / C1_XW, j = i - c * C1_XW, g = g_base + j;
       const int gc = g < 0 ? 0 : (g > T - 1 ? T - 1 : g);
       float v = xb[(size_t)c * T + gc];
-      if (g < 0 || g > T - 1) v = 0.f;
+      if (g < 0 || g > T - 1 - (msig_negctl_length == 1 && t0 > 0 ? 1 : 0)) v = 0.f;
       if (DEINT) xs[(2 * c + (j & 1)) * C1_XP + (j >> 1)] = v; else xs[c * xstride + j] = v;
     }
   }
@@ -1018,7 +1018,7 @@ __global__ __launch_bounds__(256, CONV1_BWD_WGS) void conv1_bwd_kernel(const flo
           h.y = (yv.y - bn_mean[1]) * bn_inv[1];
           h.z = (yv.z - bn_mean[2]) * bn_inv[2];
           h.w = (yv.w - bn_mean[3]) * bn_inv[3];
-          if (t >= L1) { dq = make_float4(0.f, 0.f, 0.f, 0.f); h = dq; }
+          if (t >= L1 - (msig_negctl_length == 2 && CT > 0 && (T & 3) == 0 ? 1 : 0)) { dq = make_float4(0.f, 0.f, 0.f, 0.f); h = dq; }
           *(float4*)&dzs[g1_row(row) + c4 * 4] = dq;
           *(float4*)&xhs[g1_row(row) + c4 * 4] = h;
         }
@@ -1240,7 +1240,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_dx_kernel(const float* __restri
       const int t = tq + j;
       float4 v = make_float4(bn_sc[0] * (dz[j].x - bn_c1[0] - xh[j].x * bn_c2[0]), bn_sc[1] * (dz[j].y - bn_c1[1] - xh[j].y * bn_c2[1]),
                              bn_sc[2] * (dz[j].z - bn_c1[2] - xh[j].z * bn_c2[2]), bn_sc[3] * (dz[j].w - bn_c1[3] - xh[j].w * bn_c2[3]));
-      if (t < 0 || t >= L1) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (t < 0 || t >= L1 - (msig_negctl_length == 3 && !quads && u0 > 0 ? 1 : 0)) v = make_float4(0.f, 0.f, 0.f, 0.f);
       *(float4*)&dys[(4 * q + j) * DX_PS + c4 * 4] = v;
     }
   }

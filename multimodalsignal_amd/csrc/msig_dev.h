@@ -117,6 +117,17 @@ constexpr int msig_negctl_input = MSIG_NEGCTL_INPUT;
 #else
 constexpr int msig_negctl_input = 0;
 #endif
+// Negative controls of the window lengths (make negctl LENGTH=k; never defined in the product library): one slip each in a guard that
+// only an unaligned window with more than one chunk reaches — a changed comparison, never an address the product does not also form
+// (tests/test_window_lengths_gpu.py must FAIL against each; tools/negative_controls.sh length).
+//   1  stage_x_chunk's scalar branch, item with t0 > 0: the padding test is g >= T - 1, so the window's last sample is read as padding
+//   2  conv1_bwd_kernel<CT > 0>'s non-prefetch staging at T % 4 == 0 (i.e. T % 8 == 4): the zeroing guard is t >= L1 - 1
+//   3  conv1_bwd_dx_kernel's position-wise staging, item with u0 > 0: the zeroing guard is t >= L1 - 1
+#ifdef MSIG_NEGCTL_LENGTH
+constexpr int msig_negctl_length = MSIG_NEGCTL_LENGTH;
+#else
+constexpr int msig_negctl_length = 0;
+#endif
 // acc += A . B over one 32-wide k block, A and B given as their three pieces ([0] = leading piece)
 template <int KIND = CT_ANY>
 __device__ __forceinline__ f32x4 mfma_bf16x3(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {

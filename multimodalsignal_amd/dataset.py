@@ -405,7 +405,7 @@ class DeviceLoader:
                 self._bufs[b] = [(torch.empty((b,) + tuple(self.store.shape[1:]), device=self.device),
                                   torch.empty(b, dtype=torch.int64, device=self.device)) for _ in range(2)]
             ox, oy = self._bufs[b][(i // self.batch_size) & 1]
-            if self.mixup is None and self.augment is None:      # the plain gather: it takes any window length
+            if self.mixup is None and self.augment is None:      # the plain gather: any window length (C * T % 4 != 0: element by element)
                 L.check(L.lib().msig_gather_windows(self.store.data_ptr(), self.store_y.data_ptr(), idx.data_ptr(), b, wfl,
                                                     ox.data_ptr(), oy.data_ptr(), st), "msig_gather_windows")
                 yield ox, oy

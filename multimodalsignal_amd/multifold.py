@@ -268,7 +268,8 @@ class LockstepTrainer:
         """order_mat: (folds, n_max) int64 store positions of the pass; gathers columns i .. i+b of rows row0 .. row0+m.n.
         lam: the folds' mixup weights (a C float array; include/msig_st.h) of a training launch whose loaders augment or mix — all
         ones without mixup, which is the augmented gather itself; aug: its msig_aug (keys filled for the folds of `m`) or None.
-        lam None: the plain gather, which takes any window length."""
+        lam None: the plain gather, which takes any window length (C * T a multiple of 4: the float4 copy; otherwise element by
+        element).  The augmenting / mixing gather needs T % 4 == 0 and refuses any other before a launch."""
         store, idx = loader.store, order_mat.data_ptr() + 8 * (row0 * order_mat.shape[1] + i)
         if lam is None:
             L.check(L.lib().msig_gather_windows_multi(store.data_ptr(), loader.store_y.data_ptr(), idx, order_mat.shape[1], b,

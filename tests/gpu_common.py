@@ -37,6 +37,9 @@ from oracle import cnn_gru_oracle as O
 # The same table over INPUT regimes (offsets of 10 spreads, units, spikes, zero spans, flat windows: tests/input_regimes.py,
 # tests/test_input_regimes_gpu.py, held to these constants unchanged) is in DESIGN.md section 2, "Input regimes"; its negative
 # controls (make negctl INPUT=k) in profiles/input_negative_control.log.
+# The same table over WINDOW LENGTHS (every residue T % 16, unaligned lengths and T % 8 == 4 across the conv chunk borders, T' = 2 .. 8:
+# tests/window_lengths.py, tests/test_window_lengths_gpu.py, held to these constants unchanged) is in DESIGN.md section 2, "Window
+# lengths"; its negative controls (make negctl LENGTH=k) in profiles/length_negative_control.log.
 K_STAGE, STAGE_FLOOR = 8.0, 2e-6
 K_GRAD = 6.0
 GRAD_FLOORS = (("gru.", 3e-6), ("classifier.3.bias", 1.2e-5), ("", 6e-6))      # first matching prefix

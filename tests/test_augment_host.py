@@ -130,6 +130,32 @@ def test_msig_multis_own_checks_come_first():
     assert _calls(_aug(), addr + 4, m=bad)[1] == E_SHAPE
 
 
+def test_plain_gather_takes_any_window_length():
+    """msig_gather_windows[_multi] (include/msig.h): window_floats is any count >= 1; only a multiple of 4 — the 16-byte copy —
+    asks for 16-byte aligned rows.  The augmenting gathers keep their multiple-of-4 rule (test_bad_shapes_are_shape_errors)."""
+    _k, addr = _addr()
+    lib = L.lib()
+    mm = C.byref(_multi())
+
+    def plain(wf, store=addr, idx=addr, out=addr, B_=B, stride=B, m=mm):
+        return [lib.msig_gather_windows(store, addr, idx, B_, wf, out, addr, None),
+                lib.msig_gather_windows_multi(store, addr, idx, stride, B_, wf, out, addr, m, None)]
+
+    for wf in (0, -1, -4, -CH * 251):
+        assert plain(wf, store=addr + 4) == [E_SHAPE] * 2, wf
+    for wf in (CH * 251, CH * T):
+        for which in ("store", "idx", "out"):
+            assert plain(wf, **{which: None}) == [E_NULL] * 2, (wf, which)
+        assert plain(wf, m=None)[1] == E_NULL
+        assert plain(wf, B_=0) == [E_SHAPE] * 2 and plain(wf, stride=B - 1)[1] == E_SHAPE
+    assert plain(CH * T, store=addr + 8) == [E_ALIGN] * 2 and plain(CH * T, out=addr + 4) == [E_ALIGN] * 2
+    # 6 x 251 floats: rows are 4-byte aligned at best, and no alignment is asked for — the call gets as far as msig_multi's own checks
+    bad = _multi(2)
+    bad.slot[1] = 0
+    assert plain(CH * 251, store=addr + 4, out=addr + 4, m=C.byref(bad))[1] == E_SHAPE
+    assert plain(CH * T, store=addr + 4, out=addr + 4, m=C.byref(bad))[1] == E_ALIGN
+
+
 # ---- Augment / parse / command line -----------------------------------------------------------------------------------------
 def test_augment_round_trips():
     a = Augment(scale=0.1, jitter=0.05, mask_prob=0.5, mask_max=320, chan_drop=0.1)

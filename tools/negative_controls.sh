@@ -27,6 +27,55 @@
 # tests/test_adapt_gpu.py (must FAIL, in the regime named below) and one of the OLD selection, tests/test_parity_gpu.py -k "golden_case or
 # ws6" (recorded: did the suite notice before?  control 1 is the arithmetic those cases always ran and must pass them), with the time
 # limits, the stop at the first abnormal exit and the per-library sections of the regime mode.  LIBRARY: product 1 2 (default all).
+# tools/negative_controls.sh length [OUT] [LIBRARY ...]: the controls of the WINDOW LENGTHS (libraries built by
+#   for k in 1 2 3; do make -C multimodalsignal_amd/csrc negctl LENGTH=$k; done ).  Each is one in-bounds slip in a guard that only an
+# unaligned window with more than one chunk reaches (msig_dev.h MSIG_NEGCTL_LENGTH): 1 stage_x_chunk's scalar branch reads the window's
+# last sample as padding in an item with t0 > 0, 2 conv1_bwd<CT > 0>'s non-prefetch staging at T % 8 == 4 zeroes position L1 - 1,
+# 3 conv1_bwd_dx's position-wise staging zeroes position L1 - 1 in an item with u0 > 0.  Per library: one pass of
+# tests/test_window_lengths_gpu.py (must FAIL at least one case; the product must pass every case) and one of the cases that ran
+# unaligned lengths BEFORE — T = 137 and 250 of tests/test_parity_gpu.py, tests/test_input_grad_gpu.py, the T = 137, 250 and 511 cases
+# of tests/test_channel_class_range_gpu.py and the input-gradient cases (T = 511) of tests/test_input_regimes_gpu.py — which must PASS:
+# that pass is the evidence that the suite had the gap.  Time limits, the stop at the first abnormal exit and the per-library
+# sections as in the regime mode.  LIBRARY: product 1 2 3 (default all).
+if [ "$1" = length ]; then
+  OUT=${2:-length_negctl_out/length_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1 2 3}
+  OLDF='tests/test_parity_gpu.py tests/test_input_grad_gpu.py tests/test_channel_class_range_gpu.py tests/test_input_regimes_gpu.py'
+  OLD='(test_parity_gpu and random_shapes and (137 or 250)) or test_input_grad_gpu or (test_channel_class_range_gpu and (137 or 250 or 511)) or (test_input_regimes_gpu and input_gradient)'
+  NEW=tests/test_window_lengths_gpu.py
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_length$k.so; fi
+    sec=$D/length_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/length_negctl_${k}_new.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# new file, $NEW (exit $rc):   $(tail -1 $D/length_negctl_${k}_new.txt)" >> $sec
+    if [ "$k" = product ]; then grep -E "^(PASSED|FAILED) " $D/length_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec
+    else grep -E "^FAILED " $D/length_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec; fi
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    nfail=$(grep -c "^FAILED " $D/length_negctl_${k}_new.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass the new file" >> $sec; bad=1; }
+      continue
+    fi
+    if [ "$nfail" -gt 0 ]; then echo "# verdict: control $k FAILS $nfail new cases" >> $sec
+    else echo "!! control $k fails no new case: the new file does not catch it" >> $sec; bad=1; fi
+    MSIG_LIB=$lib timeout -k 10 900 python -m pytest $OLDF -q -rA -p no:cacheprovider -k "$OLD" > $D/length_negctl_${k}_old.txt 2>&1; rc=$?
+    echo "# cases that ran unaligned lengths before, $OLDF -k \"$OLD\" (exit $rc):   $(tail -1 $D/length_negctl_${k}_old.txt)" >> $sec
+    grep -E "^FAILED " $D/length_negctl_${k}_old.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ $rc = 0 ]; then echo "# verdict: the cases the suite had do NOT notice control $k" >> $sec
+    else echo "!! the cases the suite had notice control $k: the slip is not confined to the new lengths" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh length: $NEW and the unaligned cases the suite had against libmsig_hip_length<k>.so (make negctl LENGTH=k)" > "$OUT"
+  for k in product 1 2 3; do [ -f $D/length_negctl_section_$k.log ] && cat $D/length_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = input ]; then
   OUT=${2:-input_negctl_out/input_negative_control.log}
   D=$(dirname "$OUT")
