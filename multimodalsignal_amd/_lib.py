@@ -1,5 +1,5 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
-include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h, include/msig_nr.h,
+include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h, include/msig_sc.h, include/msig_nr.h,
 include/msig_rec.h).
 
 There is deliberately no fallback: if the shared library is missing the import
@@ -114,8 +114,20 @@ DRO_ABI_VERSION = 1   # include/msig_dro.h MSIG_DRO_ABI_VERSION (group-DRO: the 
 DRO_MAX_GROUPS = 64   # msig_dro.h MSIG_DRO_MAX_GROUPS: groups of one fold
 DRO_MAX_BATCH = 2048  # msig_dro.h MSIG_DRO_MAX_BATCH: rows of one step with the term
 DRO_STATS = 3 * DRO_MAX_GROUPS + 2      # msig_dro.h MSIG_DRO_STATS: T_g, W_g, n_g per group, the robust loss's sum, the steps
+SC_ABI_VERSION = 1    # include/msig_sc.h MSIG_SC_ABI_VERSION (supervised contrastive loss on the feature inside the train steps)
+SC_MAX_BATCH = 2048   # msig_sc.h MSIG_SC_MAX_BATCH: rows of one step with the term
+SC_STATS = 4          # msig_sc.h MSIG_SC_STATS: sum of the anchors' losses, anchors, anchors whose nearest row is a positive, steps
+SC_POSITIVES = {"class": 0, "cross-subject": 1}      # MSIG_SC_POS_*
 NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
 REC_ABI_VERSION = 1   # include/msig_rec.h MSIG_REC_ABI_VERSION (statistics and normalised window batches straight from a continuous recording)
+
+
+class Sc(C.Structure):
+    """msig_sc (include/msig_sc.h): the supervised contrastive term of a launch — which rows are positives, the temperature, the
+    subject table and the batch's store positions (cross-subject mode), the scratch, the optional statistics, (fold batch) the bytes
+    between the folds' grp, scratch and stats, and a weight per fold."""
+    _fields_ = [("positives", C.c_int32), ("tau", C.c_float), ("grp", C.c_void_p), ("idx", C.c_void_p), ("idx_row_stride", C.c_int64),
+                ("scratch", C.c_void_p), ("stats", C.c_void_p), ("stride_bytes", C.c_int64), ("weight", C.c_float * MAX_FOLDS)]
 
 
 class Multi(C.Structure):
@@ -442,6 +454,20 @@ def lib() -> C.CDLL:
                                           f32, f32, f32, f32, f32, i64, vp]
         L.msig_dro_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), C.POINTER(Sam),
                                                 C.POINTER(Dro), vp, vp, f32, f32, f32, f32, i64, vp]
+        # include/msig_sc.h, exported by the same library: the supervised contrastive term and the train steps with it
+        L.msig_sc_abi_version.restype = C.c_int
+        L.msig_sc_struct_bytes.restype = C.c_int64
+        if L.msig_sc_abi_version() != SC_ABI_VERSION or L.msig_sc_struct_bytes() != C.sizeof(Sc):
+            raise RuntimeError(f"{LIB_PATH} has msig_sc.h ABI {L.msig_sc_abi_version()} with msig_sc of {L.msig_sc_struct_bytes()} bytes; "
+                               f"this binding is {SC_ABI_VERSION} with {C.sizeof(Sc)}: rebuild the library")
+        L.msig_sc_scratch_bytes.argtypes = [i32]
+        L.msig_sc_scratch_bytes.restype = C.c_int64
+        L.msig_sc_apply.argtypes = [C.POINTER(Sc), vp, vp, vp, i32, i32, vp]
+        L.msig_sc_apply_multi.argtypes = [C.POINTER(Sc), C.POINTER(Multi), vp, vp, vp, i32, i32, vp]
+        L.msig_sc_train_step.argtypes = [C.POINTER(Batch), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), C.POINTER(Sam), C.POINTER(Dro),
+                                         C.POINTER(Sc), vp, vp, f32, f32, f32, f32, f32, i64, vp]
+        L.msig_sc_train_step_multi.argtypes = [C.POINTER(Batch), C.POINTER(Multi), C.POINTER(St), C.POINTER(Da), C.POINTER(Kd), C.POINTER(Sam),
+                                               C.POINTER(Dro), C.POINTER(Sc), vp, vp, f32, f32, f32, f32, i64, vp]
         # include/msig_nr.h, exported by the same library: per-subject normalisation with the statistics of reference windows
         L.msig_nr_abi_version.restype = C.c_int
         if L.msig_nr_abi_version() != NR_ABI_VERSION:

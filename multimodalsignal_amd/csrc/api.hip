@@ -1,4 +1,4 @@
-// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h, msig_kd.h, msig_sam.h and msig_dro.h): argument checks,
+// extern "C" surface of libmsig_hip.so (declared in include/msig.h, msig_cw.h, msig_cg.h, msig_ft.h, msig_gc.h, msig_st.h, msig_da.h, msig_kd.h, msig_sam.h, msig_dro.h and msig_sc.h): argument checks,
 // parameter / workspace layout, and the stage launch order.
 #include <math.h>
 #include <stdio.h>
@@ -17,6 +17,7 @@
 #include "../../include/msig_kd.h"
 #include "../../include/msig_sam.h"
 #include "../../include/msig_dro.h"
+#include "../../include/msig_sc.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -328,6 +329,7 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
     if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
     ColsumPlan plan1;
     if ((rc = launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan1, fc, st))) return rc;
+    if (o.sc && (rc = launch_sc_apply(*o.sc, c.w.p<float>(MSIG_WS_FEAT), b->labels, c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
     if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan1, fc, st))) return rc;
     if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan1, fc, st, !cg))) return rc;
     if ((rc = launch_colsum_plan(plan1, fc, st))) return rc;
@@ -338,10 +340,12 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
     sam2.pass2 = true;
     KdArgs kd2;
     DroArgs dro2;
+    ScArgs sc2;
     StepOpts o2 = o;
     o2.sam = &sam2;
     if (o.kd) { kd2 = *o.kd; kd2.stats = nullptr; o2.kd = &kd2; }
     if (o.dro) { dro2 = *o.dro; dro2.frozen = 1; dro2.stats = nullptr; o2.dro = &dro2; }      // q moved once, in pass 1
+    if (o.sc) { sc2 = *o.sc; sc2.stats = nullptr; o2.sc = &sc2; }                              // the term is stateless: measured once, at w
     fc.fused_step = 0;                      // as this call received it: the second one sets it after its own checks
     return train_step_fc(&b2, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st, o2);
   }
@@ -359,6 +363,8 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, o) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
   // subject discriminator (include/msig_da.h): WS_FEAT and WS_DFEAT are complete here; its launch adds the reversed gradient to WS_DFEAT
   if (o.da && (rc = launch_da_step(*o.da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
+  // supervised contrastive term (include/msig_sc.h): two launches that add its gradient to WS_DFEAT; the head stays fused where it was
+  if (o.sc && (rc = launch_sc_apply(*o.sc, c.w.p<float>(MSIG_WS_FEAT), b->labels, c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
   // second pass of a sharpness-aware step: back to w (and to pass 1's BatchNorm state and losses) before Adam reads the parameters
@@ -545,12 +551,13 @@ static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, 
   return forward_fc(b, fc, st, StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, nullptr, use ? &soft : nullptr});
 }
 static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* lam, DaArgs& da);
+int msig_sc_check_align(const msig_sc* k, const FoldCtx& fc, int32_t B);      // supcon.hip: what follows msig_sc_make_args and the lam check
 // a: the subject discriminator of include/msig_da.h (NULL = msig_st_train_step[_multi] itself); k: the distillation term of
 // include/msig_kd.h (NULL, or alpha == 0 after its checks = msig_da_train_step[_multi] itself)
 static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
                          float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a,
-                         const msig_kd* k = nullptr, const msig_sam* sm = nullptr, const msig_dro* dr = nullptr) {
-  if ((sm || dr) && (!s || !b)) return MSIG_E_NULL;
+                         const msig_kd* k = nullptr, const msig_sam* sm = nullptr, const msig_dro* dr = nullptr, const msig_sc* sk = nullptr) {
+  if ((sm || dr || sk) && (!s || !b)) return MSIG_E_NULL;
   SamArgs sam;                             // include/msig_sam.h: its own checks first; rho == 0 after them = the call without it
   int rc;
   if (sm) {
@@ -570,6 +577,12 @@ static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* 
     if ((rc = msig_dro_make_args(dr, fc, b->shape.B, b->shape.K, soft.eps, dro))) return rc;
     for (int i = 0; i < fc.n; ++i) if (soft.lam[i] != 1.f) return MSIG_E_SHAPE;
   }
+  ScArgs sc;                               // include/msig_sc.h: a blended row has no label to contrast
+  if (sk) {
+    if ((rc = msig_sc_make_args(sk, fc, b->shape.B, b->shape.K, sc))) return rc;
+    for (int i = 0; i < fc.n; ++i) if (soft.lam[i] != 1.f) return MSIG_E_SHAPE;
+    if ((rc = msig_sc_check_align(sk, fc, b->shape.B))) return rc;
+  }
   ClipArgs cl;
   if (s->clip) {
     if (s->clip->kind != s->kind) return MSIG_E_SHAPE;
@@ -577,7 +590,7 @@ static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* 
   }
   return train_step_fc(b, fc, lrs, steps, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, st,
                        StepOpts{s->class_weight, s->kind == MSIG_GC_KIND_CNN_GRU, s->clip ? &cl : nullptr, use ? &soft : nullptr, a ? &da : nullptr,
-                                distil ? &kd : nullptr, sm ? &sam : nullptr, dr ? &dro : nullptr});
+                                distil ? &kd : nullptr, sm ? &sam : nullptr, dr ? &dro : nullptr, sk ? &sc : nullptr});
 }
 extern "C" int msig_st_forward(const msig_batch* b, const msig_st* s, void* stream) {
   return st_forward(b, single_fold(b), s, (hipStream_t)stream);
@@ -704,6 +717,24 @@ extern "C" int msig_dro_train_step_multi(const msig_batch* b, const msig_multi* 
   if (da && sam) return MSIG_E_SHAPE;
   return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd, sam,
                        dro);
+}
+
+// ---- supervised contrastive term (include/msig_sc.h; kernels and the stand-alone calls: supcon.hip) ---------------------------------
+extern "C" int msig_sc_train_step(const msig_batch* b, const msig_st* s, const msig_da* da, const msig_kd* kd, const msig_sam* sam,
+                                  const msig_dro* dro, const msig_sc* sc, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int64_t step, void* stream) {
+  if (da && sam) return MSIG_E_SHAPE;
+  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da,
+                       kd, sam, dro, sc);
+}
+extern "C" int msig_sc_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* da, const msig_kd* kd,
+                                        const msig_sam* sam, const msig_dro* dro, const msig_sc* sc, float* exp_avg, float* exp_avg_sq,
+                                        float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  if (da && sam) return MSIG_E_SHAPE;
+  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd, sam,
+                       dro, sc);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

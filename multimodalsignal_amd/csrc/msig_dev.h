@@ -128,6 +128,14 @@ constexpr int msig_negctl_length = MSIG_NEGCTL_LENGTH;
 #else
 constexpr int msig_negctl_length = 0;
 #endif
+// Negative control of the supervised contrastive term (make negctl SUPCON=1; never defined in the product library): sc_grad_kernel
+// without the transposed term C_ji of G_ij = C_ij + C_ji — a gradient that stays finite and plausible, and wrong (the `apply` parity
+// cases of tests/test_supcon_gpu.py must FAIL against it; tools/negative_controls.sh supcon).
+#ifdef MSIG_NEGCTL_SUPCON
+constexpr int msig_negctl_supcon = MSIG_NEGCTL_SUPCON;
+#else
+constexpr int msig_negctl_supcon = 0;
+#endif
 // acc += A . B over one 32-wide k block, A and B given as their three pieces ([0] = leading piece)
 template <int KIND = CT_ANY>
 __device__ __forceinline__ f32x4 mfma_bf16x3(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {
@@ -463,6 +471,7 @@ struct DaArgs;
 struct KdArgs;
 struct SamArgs;
 struct DroArgs;
+struct ScArgs;
 // What a forward or a train step does beyond the msig.h call (host side only; api.hip's entry points fill it after their own checks).
 // Value-initialised = the plain call.  Each function that takes it reads only the fields named at its declaration.
 struct StepOpts {
@@ -474,6 +483,7 @@ struct StepOpts {
   const KdArgs* kd;         // distillation (include/msig_kd.h): the unfused head with one more launch between ce and head_bwd
   const SamArgs* sam;       // sharpness-aware step (include/msig_sam.h): two passes with the unfused head, perturbation and restore between
   const DroArgs* dro;       // group-DRO (include/msig_dro.h): the unfused head with one more launch between ce and kd_apply / head_bwd
+  const ScArgs* sc;         // supervised contrastive term (include/msig_sc.h): two more launches after the head's (and the adversary's)
 };
 // reads o.cw, o.soft.  mc_tail (include/msig_mc.h): the classifier's launch alone — no loss, no softmax — with the dropout mask of
 // b->dropout_thr although b->training = 0
@@ -549,6 +559,21 @@ struct DroArgs {
 int msig_dro_make_args(const msig_dro* k, const FoldCtx& fc, int32_t B, int32_t K, float smoothing, DroArgs& a);
 int launch_dro_apply(const DroArgs& a, const float* logits, const int64_t* labels, const float* cw, float* dlogits, const FoldCtx& fc,
                      hipStream_t st);
+// Supervised contrastive term (include/msig_sc.h, supcon.hip): msig_sc after its checks (msig_sc_make_args), by value to the launches.
+// grp / scratch / stats are fold slot 0's, `stride` bytes apart per slot; B rows of 128; weight per fold.  Two launches, between the
+// head's launch (the adversary's when there is one) and launch_gru_bwd, on WS_FEAT / WS_DFEAT; labels are the step's.
+struct msig_sc;
+struct ScArgs {
+  int32_t positives, B, K;
+  float tau;
+  const int32_t* grp; const int64_t* idx; int64_t idx_row_stride;
+  char* scratch; double* stats;
+  int64_t stride;
+  float weight[MSIG_MAX_FOLDS];
+};
+// every check of msig_sc.h's own arguments, before any launch; fc: the folds of the launch (stride != 0: a fold batch)
+int msig_sc_make_args(const msig_sc* k, const FoldCtx& fc, int32_t B, int32_t K, ScArgs& a);
+int launch_sc_apply(const ScArgs& a, const float* feat, const int64_t* labels, float* dfeat, const FoldCtx& fc, hipStream_t st);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch

@@ -32,6 +32,7 @@ from .augment import Augment
 from .mixup import Mixup
 from . import adversary as adversary_mod
 from . import dro as dro_mod
+from . import supcon as supcon_mod
 from . import averaging as averaging_mod
 from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask
 from . import distill as distill_mod
@@ -108,6 +109,8 @@ def trainer_config(cfg, fold_idx):
         tc["trainer"]["sam"] = sam_mod.setting(cfg["sam"]).spec()
     if cfg.get("group_dro") is not None:            # group-DRO over the training subjects (include/msig_dro.h); absent = the pooled mean
         tc["trainer"]["group_dro"] = dro_mod.settings(cfg["group_dro"])
+    if cfg.get("supcon") is not None:               # supervised contrastive loss on the feature (include/msig_sc.h); absent = none
+        tc["trainer"]["supcon"] = supcon_mod.settings(cfg["supcon"])
     if cfg.get("adversary") is not None:            # a subject discriminator inside every training step (include/msig_da.h); absent = none
         tc["adversary"] = adversary_mod.settings(cfg["adversary"])
     if cfg.get("averaging") is not None:            # an EMA / SWA shadow of the weights (include/msig_wa.h); absent = none
@@ -159,6 +162,10 @@ def make_unit(fold_idx, subject, fold_dir, datasets, in_channels, num_classes, p
         dro_mod.check_batch_size(cfg["batch_size"])
         if Mixup.coerce(cfg.get("mixup")) is not None:
             raise ValueError("group_dro cannot be combined with mixup: a row blended from two subjects has no group")
+    if cfg.get("supcon") is not None:               # likewise: at most 2048 rows, and a blended row has no label to contrast
+        supcon_mod.check_batch_size(cfg["batch_size"])
+        if Mixup.coerce(cfg.get("mixup")) is not None:
+            raise ValueError("supcon cannot be combined with mixup: a row blended from two windows has no label to contrast")
     train_ds, val_ds = datasets(train_subjects), datasets(val_subjects)
     if skip_empty and (len(train_ds) == 0 or len(val_ds) == 0):
         return None
@@ -237,6 +244,8 @@ def write_summary(run_output_dir, results, cfg, wall_s, world):
             f.write(adversary_line(cfg))
         if cfg.get("group_dro") is not None:                        # likewise
             f.write(dro_mod.settings_line(cfg["group_dro"]) + "\n")
+        if cfg.get("supcon") is not None:                           # likewise
+            f.write(supcon_mod.settings_line(cfg["supcon"]) + "\n")
         if cfg.get("averaging") is not None:                        # likewise
             f.write(averaging_mod.settings_line(cfg["averaging"]) + "\n")
         if cfg.get("norm_reference") is not None:                   # likewise
@@ -643,6 +652,13 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
             if folds:
                 path = dro_mod.write_dro(out_dir[n], folds, cfgs[n]["group_dro"], synthetic=bool(cfgs[n].get("synthetic")))
                 print(f"Group-DRO table written to: {path}")
+        if cfgs[n].get("supcon") is not None:         # likewise from the folds' fold_result.json
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "fold_result.json" for r in results[n]]
+            folds = [supcon_mod.fold_record(json.loads(f.read_text())) for f in files if f.exists()]
+            folds = [f for f in folds if f is not None]
+            if folds:
+                path = supcon_mod.write_supcon(out_dir[n], folds, cfgs[n]["supcon"], synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Supcon table written to: {path}")
         if cfgs[n].get("averaging") is not None:      # likewise from the folds' fold_result.json
             files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "fold_result.json" for r in results[n]]
             folds = [averaging_mod.fold_record(json.loads(f.read_text())) for f in files if f.exists()]
@@ -1019,6 +1035,14 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 rec = dro_mod.fold_record(info)
                 if rec is not None:
                     (Path(run_output_dir) / f"fold_test_on_{sid}" / f"model_{tag}" / "dro_result.json").write_text(json.dumps(rec))
+        if cfg.get("supcon") is not None:         # likewise each model's supcon record
+            for tag, t in trainers.items():
+                if t.supcon is None:
+                    continue
+                rec = supcon_mod.fold_record(dict(subject=sid, history=t.history, accuracy=m1_acc if tag == "m1" else None,
+                                                  supcon=supcon_mod.fold_info(t.supcon)))
+                if rec is not None:
+                    (Path(run_output_dir) / f"fold_test_on_{sid}" / f"model_{tag}" / "supcon_result.json").write_text(json.dumps(rec))
         local[k] = (m1_acc, acc3)
         print(f"[rank {rank}] fold {k} ({sid}): M1 acc {m1_acc:.4f} | three-class acc {acc3:.4f} f1 {f13:.4f}", flush=True)
 
@@ -1071,6 +1095,8 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 f.write(adversary_line(cfg))
             if cfg.get("group_dro") is not None:
                 f.write(dro_mod.settings_line(cfg["group_dro"]) + "\n")
+            if cfg.get("supcon") is not None:
+                f.write(supcon_mod.settings_line(cfg["supcon"]) + "\n")
             if cfg.get("norm_reference") is not None:
                 f.write(f"NORM_REFERENCE: {cfg['norm_reference']}\n")
             f.write("\n")
@@ -1096,6 +1122,13 @@ def run_hierarchical_experiment(run_output_dir, device, all_channel_names, cfg=N
                 if folds:
                     path = dro_mod.write_dro(run_output_dir, folds, cfg["group_dro"], synthetic=bool(cfg.get("synthetic")), stem=f"dro_{tag}")
                     print(f"Group-DRO table written to: {path}")
+        if cfg.get("supcon") is not None:
+            for tag in ("m1", "m2"):
+                files = [Path(run_output_dir) / f"fold_test_on_{r['subject']}" / f"model_{tag}" / "supcon_result.json" for r in results]
+                folds = [json.loads(f.read_text()) for f in files if f.exists()]
+                if folds:
+                    path = supcon_mod.write_supcon(run_output_dir, folds, cfg["supcon"], synthetic=bool(cfg.get("synthetic")), stem=f"supcon_{tag}")
+                    print(f"Supcon table written to: {path}")
     return results, wall
 
 
@@ -1222,6 +1255,16 @@ def parse_args(ap, argv=None):
             ap.error("--group-dro cannot be combined with --mixup: a row blended from two subjects has no group")
     elif args.dro_groups is not None:
         ap.error("--dro-groups needs --group-dro")
+    if args.supcon is not None:
+        try:
+            args.supcon = supcon_mod.parse(args.supcon, args.supcon_positives)
+        except ValueError as e:
+            ap.error(f"--supcon: {e}")
+        supcon_mod.check_batch_size(args.batch_size)          # ValueError, before any data or GPU work
+        if args.mixup is not None:
+            raise ValueError("--supcon cannot be combined with --mixup: a row blended from two windows has no label to contrast")
+    elif args.supcon_positives is not None:
+        ap.error("--supcon-positives needs --supcon")
     if args.weight_average is not None:
         try:
             spec = averaging_mod.parse_flag(args.weight_average)
@@ -1336,6 +1379,15 @@ def build_parser():
                          "with --mixup; writes dro.txt / dro.json")
     ap.add_argument("--dro-groups", choices=list(dro_mod.GROUPS), default=None,
                     help="the groups of --group-dro: a fold's training subjects (default) or its (subject, class) pairs")
+    ap.add_argument("--supcon", nargs="?", const="", default=None, metavar="WEIGHT[:TAU]",
+                    help="supervised contrastive loss (Khosla et al., 2020) on the 128-d feature the classifier sees, added to the "
+                         f"criterion with WEIGHT (default {supcon_mod.DEFAULT_WEIGHT:g}) at temperature TAU (default {supcon_mod.DEFAULT_TAU:g}) "
+                         "inside every training step (include/msig_sc.h); WEIGHT 0 measures the loss and trains as without it; not with "
+                         "--mixup, batches of at most 2048; history and the epoch line gain supcon_loss / supcon_top1 / supcon_anchors; "
+                         "writes supcon.txt / supcon.json")
+    ap.add_argument("--supcon-positives", choices=list(supcon_mod.POSITIVES), default=None,
+                    help="the positives of --supcon: every window of the anchor's class (default), or only those of its class from a "
+                         "different subject (windows of the same class and subject are then neither positives nor negatives)")
     ap.add_argument("--adversary-schedule", choices=list(adversary_mod.SCHEDULES), default=None,
                     help="lambda over the training steps: ganin = LAMBDA * (2 / (1 + exp(-10 p)) - 1), p the fraction of the epoch budget "
                          "done (default), or constant")
@@ -1436,6 +1488,8 @@ def build_cfg(args, kinds):
         cfg.update(adversary=args.subject_adversarial, synthetic=args.synthetic is not None)
     if args.group_dro is not None:                # likewise
         cfg.update(group_dro=args.group_dro, synthetic=args.synthetic is not None)
+    if args.supcon is not None:                   # likewise
+        cfg.update(supcon=args.supcon, synthetic=args.synthetic is not None)
     if args.weight_average is not None:           # likewise
         cfg.update(averaging=args.weight_average, synthetic=args.synthetic is not None)
     if args.calibrate:        # without the flag the configuration — and with it every log, summary and result — is what it was

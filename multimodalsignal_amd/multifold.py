@@ -34,6 +34,7 @@ import torch
 from . import _lib as L
 from . import adversary as A
 from . import dro as DRO
+from . import supcon as SC
 from . import averaging as AV
 from . import sam as SAM
 from .runtime import FoldArena
@@ -80,6 +81,8 @@ def fold_result(prep, trainer, accuracy, f1_score, seconds, averaging=None):
         info["group_dro"] = DRO.fold_info(trainer.dro, prep.get("train_subjects"))
         hist = [h for h in trainer.history if h.get("dro_subject_loss") is not None]
         info["group_dro"]["subject_loss"] = hist[-1]["dro_subject_loss"] if hist else None      # per-subject mean training loss, last epoch
+    if getattr(trainer, "supcon", None) is not None:         # config['trainer']['supcon']: what main's supcon tables tabulate
+        info["supcon"] = SC.fold_info(trainer.supcon)
     if averaging is not None:
         info["averaging"] = averaging
     if prep.get("test_pass", True):
@@ -100,6 +103,12 @@ def _dro_groups(prep):
     if c is None:
         return None
     return (c["eta"], c["groups"], DRO.group_count(prep["loaders"][0].dataset, c["groups"], prep["model"].num_classes))
+
+
+def _supcon(prep):
+    """(weight, tau, positives) of a fold's supervised contrastive term, or None when config['trainer']['supcon'] is not set."""
+    c = SC.settings(prep["config"]["trainer"].get("supcon"))
+    return None if c is None else (c["weight"], c["tau"], c["positives"])
 
 
 def _shared(values, what, show=None):
@@ -126,7 +135,8 @@ def lockstep_compatible(preps) -> bool:
                 or p["model"].in_channels != preps[0]["model"].in_channels or p["model"].num_classes != preps[0]["model"].num_classes
                 or p["model"].dropout_p != preps[0]["model"].dropout_p
                 or _domains(p) != _domains(preps[0])         # msig_da.S is one value per launch
-                or _dro_groups(p) != _dro_groups(preps[0])):  # and so are msig_dro.G and eta
+                or _dro_groups(p) != _dro_groups(preps[0])   # and so are msig_dro.G and eta
+                or _supcon(p) != _supcon(preps[0])):          # and msig_sc.tau and positives
             return False
     return True
 
@@ -196,12 +206,20 @@ class LockstepTrainer:
         if self.dro_cfg is not None:
             DRO.check_batch_size(tr0.batch_size)
         self.dro_stats, self.val_worst = {}, {}
+        # supervised contrastive term (config['trainer']['supcon'], include/msig_sc.h): tau and the positives are the launch's, so the
+        # folds of a batch share them (and, with one configuration, the weight); every fold's subject table, scratch and statistics
+        # live in the arena set's own block
+        self.sc_cfg = _shared([_supcon(p) for p in preps], "supcon setting", str)
+        if self.sc_cfg is not None:
+            SC.check_batch_size(tr0.batch_size)
+        self.sc_stats = {}
         self.arena = FoldArena(self.C, self.K, self.device, self.n, tr0.batch_size, self.T, eval_batch=max(va0.batch_size, te0.batch_size),
                                adaptive_forms=adaptive_forms, gru_hidden=hidden, gru_layers=layers, kind=self.kind, grad_clip=self.clip,
                                adversary=None if self.adv_S is None else (self.adv_S, int(tr0.store.shape[0])),
                                averaging=self.avg_cfg is not None,
                                distill=None if self.kd_cfg is None else int(tr0.store.shape[0]), sam=self.sam_cfg is not None,
-                               dro=None if self.dro_cfg is None else (self.dro_cfg[2], int(tr0.store.shape[0])))
+                               dro=None if self.dro_cfg is None else (self.dro_cfg[2], int(tr0.store.shape[0])),
+                               supcon=None if self.sc_cfg is None else int(tr0.store.shape[0]))
         if self.clip:
             for slot, v in enumerate(norms):
                 self.arena.set_max_norm(slot, float("inf") if v is None else v)
@@ -228,6 +246,8 @@ class LockstepTrainer:
             t.subject_names = (p.get("train_subjects"), p.get("val_subjects"))
             if self.dro_cfg is not None:
                 t.prepare_dro(p["loaders"][0], self.arena.dro_storage(slot))
+            if self.sc_cfg is not None:
+                t.prepare_supcon(p["loaders"][0], self.arena.sc_storage(slot))
             self.trainers.append(t)
         # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
         # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
@@ -336,6 +356,8 @@ class LockstepTrainer:
             arena.distill_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
         if self.dro_cfg is not None:
             arena.zero_dro_stats(act)
+        if self.sc_cfg is not None:
+            arena.zero_sc_stats(act)
         # weight averaging: EMA's coefficient of every step of the epoch per fold, from the fold's own update count
         avs = [t.averager for t in trs] if self.avg_cfg is not None else None
         ema = avs is not None and self.avg_cfg["mode"] == "ema"
@@ -363,8 +385,9 @@ class LockstepTrainer:
                                   arena.wa(sl, [0.0] * nr) if ema else None,
                                   None if self.kd_cfg is None else arena.kd(*self.kd_cfg),
                                   None if self.sam_cfg is None else arena.sam(self.sam_cfg),
-                                  None if self.dro_cfg is None else arena.dro(self.dro_cfg[0]))
-            m, s, a, w, kd, sm, dr = runs[(r0, nr)]
+                                  None if self.dro_cfg is None else arena.dro(self.dro_cfg[0]),
+                                  None if self.sc_cfg is None else arena.sc(self.sc_cfg[2], self.sc_cfg[1], [self.sc_cfg[0]] * nr))
+            m, s, a, w, kd, sm, dr, sc = runs[(r0, nr)]
             for j in range(nr):
                 m.key_gru[j] = int(kg[r0 + j][k]); m.key_head[j] = int(kh[r0 + j][k]); m.step[j] = int(steps[r0 + j][k])
                 if aug is not None:
@@ -379,8 +402,16 @@ class LockstepTrainer:
             _, desc = self._layout(b, True)
             if kd is not None:
                 kd.idx, kd.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
-            if dr is not None:                 # group-DRO: the widest call, with whatever else is on
+            if dr is not None:
                 dr.idx, dr.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+            if sc is not None:                 # the supervised contrastive term: the widest call, with whatever else is on
+                if sc.positives:
+                    sc.idx, sc.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+                L.check(lib.msig_sc_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None,
+                                                     C.byref(kd) if kd is not None else None, C.byref(sm) if sm is not None else None,
+                                                     C.byref(dr) if dr is not None else None, C.byref(sc), ea, eas, b1, b2, eps, wd,
+                                                     int(steps[r0][k]), st), "msig_sc_train_step_multi")
+            elif dr is not None:               # group-DRO: the widest call without the term above, with whatever else is on
                 L.check(lib.msig_dro_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None,
                                                       C.byref(kd) if kd is not None else None, C.byref(sm) if sm is not None else None,
                                                       C.byref(dr), ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_dro_train_step_multi")
@@ -420,6 +451,9 @@ class LockstepTrainer:
         if self.dro_cfg is not None:       # likewise, only with group-DRO on: every fold's statistics and weights in one read-back
             sq = arena.dro_stats().cpu().numpy()
             self.dro_stats = {f: (sq[f, :L.DRO_STATS], sq[f, L.DRO_STATS:]) for f in act}
+        if self.sc_cfg is not None:        # likewise, only with the supervised contrastive term on
+            st5 = arena.sc_stats().cpu().numpy()
+            self.sc_stats = {f: SC.SupCon.epoch_summary(st5[f]) for f in act}
         if self.sam_cfg is not None:       # the same sync: the loss sums, the SAM statistics and (with the clip) the gradient norms
             parts = [self.acc[:, :1], arena.across("sam", 0, torch.float64, L.SAM_NSTAT)]
             if self.clip:
@@ -526,7 +560,8 @@ class LockstepTrainer:
                     t.train_seconds += dt
                     if not t._end_of_epoch(epoch, float(sums[f]) / n_train[f], dt, n_train[f], vl, va, vf, self.grad_stats.get(f), self.dom_stats.get(f),
                                            avg_vals.get(f), self.kd_stats.get(f), self.sam_stats.get(f),
-                                           None if self.dro_cfg is None else t.dro_epoch(*self.dro_stats[f], self.val_worst.get(f))):
+                                           None if self.dro_cfg is None else t.dro_epoch(*self.dro_stats[f], self.val_worst.get(f)),
+                                           self.sc_stats.get(f)):
                         still.append(f)
                     else:
                         t.finished_at = time.time() - t_start

@@ -11,6 +11,8 @@ NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL class_weight eac
 selects the model — and tests/test_step_dispatch_gpu.py pins it.  A sharpness-aware step (include/msig_sam.h) is
 msig_sam_train_step[_multi], whatever else is on; without `sam` the calls are exactly the ones above.  A group-DRO step
 (include/msig_dro.h) is msig_dro_train_step[_multi], whatever else is on — `sam` included; without `dro` the calls are exactly those.
+A step with the supervised contrastive term (include/msig_sc.h) is msig_sc_train_step[_multi], whatever else is on — `sam` and `dro`
+included; without `supcon` the calls are exactly those.
 """
 from __future__ import annotations
 
@@ -416,7 +418,7 @@ class Engine:
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
                    dropout_p=0.0, seed=0, class_weight: Optional[torch.Tensor] = None, max_grad_norm: Optional[float] = None,
                    label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index: Optional[torch.Tensor] = None, distill=None,
-                   sam=None, dro=None) -> None:
+                   sam=None, dro=None, supcon=None) -> None:
         """optimizer.zero_grad(); loss = criterion(model(x), y); loss.backward(); optimizer.step()
         (trainer.py:144-149) as one asynchronous call; the batch loss is left in region('LOSS')[0] and added, times the batch size,
         to loss_acc[0] (loss_acc[1] += correctly classified windows): the caller zeroes loss_acc when an epoch starts.
@@ -445,8 +447,21 @@ class Engine:
         moves the group weights dro.q with the groups' losses — groups read by batch_index, or one table entry per row — and
         rescales the logits' gradient so that the step descends sum_g q_g L_g; the reported loss stays the criterion's, the term's
         statistics go to dro.stats.  Under `sam` the weights move once, in the first pass.  Not with mixup (ValueError): a blended
-        row has no group.  The call is msig_dro_train_step whatever else is on; None = the calls above, exactly."""
+        row has no group.  The call is msig_dro_train_step whatever else is on; None = the calls above, exactly.
+        supcon: a supcon.SupCon bound to this device (include/msig_sc.h): two more launches between the head's (the
+        adversary's) and the GRU backward add weight x the gradient of the supervised contrastive loss on the step's features to
+        the feature gradient — subjects read by batch_index, or one table entry per row, in cross-subject mode; the head stays fused
+        where it was, the reported loss stays the criterion's, the term's statistics go to supcon.stats.  Under `sam` it runs in both
+        passes.  weight = 0 measures and leaves the step its bits.  Not with mixup, not above 2048 windows (ValueError before any
+        launch).  The call is msig_sc_train_step whatever else is on; None = the calls above, exactly."""
         cw, max_norm, smooth, lam = self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
+        if supcon is not None:
+            if lam != 1.0:
+                raise ValueError("supcon cannot be combined with mixup: a row blended from two windows has no label to contrast")
+            if x.shape[0] > min(L.SC_MAX_BATCH, supcon.max_batch or L.SC_MAX_BATCH):
+                raise ValueError(f"supcon takes batches of at most {min(L.SC_MAX_BATCH, supcon.max_batch or L.SC_MAX_BATCH)} windows, got {x.shape[0]}")
+            if supcon.cross_subject and batch_index is None and (supcon.grp is None or supcon.grp.numel() < x.shape[0]):
+                raise ValueError(f"a subject table read by row needs {x.shape[0]} entries")
         if dro is not None:
             if lam != 1.0:
                 raise ValueError("group-DRO cannot be combined with mixup: a row blended from two subjects has no group")
@@ -458,7 +473,7 @@ class Engine:
             raise ValueError("sam cannot be combined with adversary: the discriminator's own Adam would advance in both passes")
         if adversary is not None and x.shape[0] > L.DA_MAX_BATCH:
             raise ValueError(f"subject-adversarial training takes batches of at most {L.DA_MAX_BATCH} windows, got {x.shape[0]}")
-        if adversary is not None or distill is not None or dro is not None:
+        if adversary is not None or distill is not None or dro is not None or supcon is not None:
             if batch_index is not None:
                 _require_gpu(batch_index, "batch_index")
                 if batch_index.dtype != torch.int64 or not batch_index.is_contiguous() or batch_index.numel() != x.shape[0]:
@@ -478,7 +493,17 @@ class Engine:
             k = distill.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
         else:
             k = None
-        if dro is not None:
+        if supcon is not None:
+            sd = None
+            if sam is not None:
+                state = self.ensure_sam_state()
+                sd = C.byref(sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8))
+            dd = None if dro is None else C.byref(dro.descriptor(idx=None if batch_index is None else batch_index.data_ptr()))
+            cd = supcon.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
+            L.check(L.lib().msig_sc_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, None if k is None else C.byref(k), sd,
+                                               dd, C.byref(cd), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps,
+                                               weight_decay, step, self._stream()), "msig_sc_train_step")
+        elif dro is not None:
             sd = None
             if sam is not None:
                 state = self.ensure_sam_state()
@@ -503,7 +528,7 @@ class Engine:
                     "msig_da_train_step")
         if adversary is not None:
             adversary.step += 1
-        if adversary is not None or distill is not None or dro is not None:
+        if adversary is not None or distill is not None or dro is not None or supcon is not None:
             self._keep = self._keep + (batch_index,)
 
     def features(self, x: torch.Tensor, padded: bool = False) -> torch.Tensor:
@@ -633,7 +658,7 @@ class EmbeddedEngine(Engine):
 
     def train_step(self, x, labels, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
                    max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None, sam=None,
-                   dro=None):
+                   dro=None, supcon=None):
         self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
         if sam is not None and adversary is not None:
             raise ValueError("sam cannot be combined with adversary: the discriminator's own Adam would advance in both passes")
@@ -641,7 +666,7 @@ class EmbeddedEngine(Engine):
             adversary.restrict_features(self.hidden)       # nothing may reach the padded feature columns (their units must stay zero)
         self.scatter()
         super().train_step(x, labels, lr, betas, eps, weight_decay, step, dropout_p, seed, class_weight, max_grad_norm, label_smoothing,
-                           mix_lambda, adversary, batch_index, distill, sam, dro)
+                           mix_lambda, adversary, batch_index, distill, sam, dro, supcon)
         self.gather()
 
     def features(self, x, padded: bool = False):
@@ -746,7 +771,7 @@ class FoldArena(Arenas):
     def __init__(self, in_channels: int, num_classes: int, device, n: int, train_batch: int, T: int, eval_batch: int = 0,
                  adaptive_forms: bool = False, gru_hidden: int = 64, gru_layers: int = 2, kind: str = "cnn_gru_attention",
                  grad_clip: bool = False, adversary: Optional[Tuple[int, int]] = None, averaging: bool = False,
-                 distill: Optional[int] = None, sam: bool = False, dro: Optional[Tuple[int, int]] = None):
+                 distill: Optional[int] = None, sam: bool = False, dro: Optional[Tuple[int, int]] = None, supcon: Optional[int] = None):
         """(gru_hidden, gru_layers) = (32, 1): the arenas hold the one-layer model in EmbeddedEngine's padded 64-unit layout (params,
         grads and both Adam moments; the padding is written once, when a model enters its arena, and stays exactly zero), and every
         launch of the batch runs msig_batch.gru_layers = 1.  A fold batch is uniform in depth (msig_multi has no per-slot depth).
@@ -767,7 +792,10 @@ class FoldArena(Arenas):
         included — without it the arenas and their stride are what they are without this argument.
         `dro` = (G, store positions): every fold also gets the buffers of a group-DRO term of G groups (include/msig_dro.h) — the
         weights q, the statistics and an int32 group table — in a memory block of their own, `dro_stride` bytes apart
-        (`dro_storage`), as the adversary's buffers are owned; the model arenas and their stride stay what they are without it."""
+        (`dro_storage`), as the adversary's buffers are owned; the model arenas and their stride stay what they are without it.
+        `supcon` = store positions: every fold also gets the buffers of a supervised contrastive term (include/msig_sc.h) — the
+        statistics, an int32 subject table and the scratch of a training batch — in a memory block of their own, `sc_stride` bytes
+        apart (`sc_storage`), likewise; the model arenas and their stride stay what they are without it."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -822,6 +850,14 @@ class FoldArena(Arenas):
                 raise ValueError(f"dro takes (groups in 1..{L.DRO_MAX_GROUPS}, store positions >= 1), got {dro!r}")
             dr = Arenas(n, device, (("q", L.DRO_MAX_GROUPS * 4), ("stats", L.DRO_STATS * 8), ("grp", positions * 4)))
             self.dro_off, self.dro_stride, self.dro_mem, self.dro_G = dr.off, dr.stride, dr.mem, G
+        self.sc_off, self.sc_stride, self.sc_mem = {}, 0, None
+        if supcon is not None:
+            if int(supcon) < 1 or int(train_batch) > L.SC_MAX_BATCH:
+                raise ValueError(f"supcon takes the number of store positions (>= 1) and training batches of at most {L.SC_MAX_BATCH} "
+                                 f"windows, got {supcon!r} and {train_batch}")
+            sc = Arenas(n, device, (("stats", L.SC_STATS * 8), ("grp", int(supcon) * 4),
+                                    ("scratch", int(L.lib().msig_sc_scratch_bytes(int(train_batch))))))
+            self.sc_off, self.sc_stride, self.sc_mem = sc.off, sc.stride, sc.mem
 
     @staticmethod
     def workspace_bytes(train_batch: int, eval_batch: int, in_channels: int, T: int, num_classes: int) -> int:
@@ -924,6 +960,35 @@ class FoldArena(Arenas):
     def zero_dro_stats(self, slots) -> None:
         o = self.dro_off["stats"][0] // 8
         self.dro_mem.view(torch.float64)[:, o:o + L.DRO_STATS].index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
+
+    def sc_storage(self, slot: int) -> dict:
+        """The supervised contrastive term's buffers of the fold in arena `slot` (supcon.SupCon.bind): typed views of its `sc_mem` row."""
+        if self.sc_mem is None:
+            raise RuntimeError("this FoldArena was built without supcon=positions: it has no supcon buffers")
+        dt = {"stats": torch.float64, "grp": torch.int32, "scratch": torch.uint8}
+        return {name: self.sc_mem[slot, o:o + nb].view(dt[name]) for name, (o, nb) in self.sc_off.items()}
+
+    def sc(self, positives: str, tau: float, weights) -> L.Sc:
+        """msig_sc of a launch (include/msig_sc.h): fold slot 0's subject table, scratch and statistics, `sc_stride` apart, and the
+        weight of every fold of the launch.  idx / idx_row_stride are the launch's to fill in (cross-subject mode)."""
+        if self.sc_mem is None:
+            raise RuntimeError("this FoldArena was built without supcon=positions: it has no supcon buffers")
+        d = L.Sc()
+        d.positives, d.tau = L.SC_POSITIVES[positives], float(tau)
+        base = self.sc_mem.data_ptr()
+        d.grp = base + self.sc_off["grp"][0] if d.positives else None
+        d.scratch, d.stats, d.stride_bytes = base + self.sc_off["scratch"][0], base + self.sc_off["stats"][0], self.sc_stride
+        for i, w in enumerate(weights):
+            d.weight[i] = float(w)
+        return d
+
+    def sc_stats(self) -> torch.Tensor:
+        """(n, SC_STATS) float64 strided view of every fold's supcon statistics."""
+        o = self.sc_off["stats"][0] // 8
+        return self.sc_mem.view(torch.float64)[:, o:o + L.SC_STATS]
+
+    def zero_sc_stats(self, slots) -> None:
+        self.sc_stats().index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
 
     def set_class_weight(self, slot: int, values) -> None:
         """Writes the class-weight vector of the fold in arena `slot` (K values, checked on the host: ValueError before anything is

@@ -49,6 +49,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 from . import _lib as L
 from . import adversary as A
 from . import dro as DRO
+from . import supcon as SC
 from . import averaging as AV
 from . import sam as SAM
 from .models import CnnGruAttentionModel
@@ -213,6 +214,9 @@ class Trainer:
         # group-DRO (include/msig_dro.h): the settings now, the group weights when the training set is known
         self.dro_cfg = DRO.settings(cfg.get("group_dro"))
         self.dro = None
+        # supervised contrastive term on the feature (include/msig_sc.h): the settings now, the buffers when the training set is known
+        self.supcon_cfg = SC.settings(cfg.get("supcon"))
+        self.supcon = None
         self.subject_names = (None, None)        # (training, validation) subjects in ordinal order, when the driver knows them
         self.averaging_cfg = AV.settings(config.get("averaging"))
         self.averager = AV.WeightAverager(self.averaging_cfg) if self.averaging_cfg is not None else None
@@ -314,6 +318,26 @@ class Trainer:
         self._log(f"group-DRO: {d.G} groups ({d.groups}), eta {d.eta:g}")
         return d
 
+    def prepare_supcon(self, train_loader, storage=None):
+        """Builds the fold's supervised contrastive term once, when config['trainer']['supcon'] is set: in cross-subject mode its
+        subject table over the store the loader gathers from.  storage: one fold's supcon buffers of a FoldArena.  ValueError before
+        any training for a batch size the term's launches cannot take and for a loader that mixes."""
+        if self.supcon_cfg is None or self.supcon is not None:
+            return self.supcon
+        SC.check_batch_size(train_loader.batch_size)
+        if getattr(train_loader, "mixup", None) is not None:
+            raise ValueError("supcon cannot be combined with mixup: a row blended from two windows has no label to contrast")
+        c = self.supcon_cfg
+        sc = SC.SupCon(c["weight"], c["tau"], c["positives"])
+        if sc.cross_subject:
+            ds = train_loader.dataset
+            if getattr(ds, "subject_ordinals", None) is None:
+                raise ValueError("supcon positives 'cross-subject' need a training dataset with per-window `subject_ordinals`")
+            sc.set_subjects(SC.subject_table(ds))
+        self.supcon = sc.bind(self.device, storage, max_batch=int(train_loader.batch_size))
+        self._log(f"supcon: weight {sc.weight:g}, tau {sc.tau:g}, positives {sc.positives}")
+        return sc
+
     def val_worst_subject(self, val_loader, preds, labels) -> "dict | None":
         """With group-DRO on: the validation subject with the lowest accuracy, from the predictions of the epoch's validation pass
         (host side; the validation loader serves its windows in dataset order)."""
@@ -356,6 +380,7 @@ class Trainer:
         self.prepare_class_weights(train_loader)
         adv = self.prepare_adversary(train_loader)
         dro = self.prepare_dro(train_loader)
+        sc = self.prepare_supcon(train_loader)
         kd = self.distill
         if kd is not None and not hasattr(train_loader, "last_index"):
             raise ValueError("distillation needs a training loader that serves the store positions of its batches (last_index)")
@@ -375,6 +400,8 @@ class Trainer:
                 kd.stats.zero_()
             if dro is not None:
                 dro.stats.zero_()
+            if sc is not None:
+                sc.stats.zero_()
             if self.sam is not None:
                 eng.ensure_sam_state()
                 eng.zero_sam_stats()
@@ -389,7 +416,8 @@ class Trainer:
                                class_weight=self.class_weight, max_grad_norm=self.max_grad_norm, label_smoothing=self.label_smoothing,
                                mix_lambda=getattr(train_loader, "last_lam", None),      # the lam of the batch a mixup loader just served
                                adversary=adv, distill=kd, sam=self.sam, dro=dro,
-                               batch_index=getattr(train_loader, "last_index", None) if adv is not None or kd is not None or dro is not None else None)
+                               batch_index=getattr(train_loader, "last_index", None) if adv is not None or kd is not None or dro is not None
+                               or sc is not None else None, supcon=sc)
                 if av is not None and av.mode == "ema":
                     eng.average_update(av.step_coef())
                 # running_loss += loss.item() * batch (trainer.py:152) happens inside the step: the loss kernel adds to eng.loss_acc
@@ -415,7 +443,8 @@ class Trainer:
             drs = None
             if dro is not None:
                 drs = self.dro_epoch(dro.stats.cpu().tolist(), dro.q.cpu().tolist(), self.val_worst_subject(val_loader, vp, vl))
-            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds, sam, drs):
+            scs = sc.epoch_summary(sc.stats.cpu().tolist()) if sc is not None else None
+            if self._end_of_epoch(epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad, dom, avg, kds, sam, drs, scs):
                 break
         self.finish_averaging([train_loader])
         self._finish_training()
@@ -441,7 +470,7 @@ class Trainer:
             AV.recompute_bn([eng], train_loaders)
 
     def _end_of_epoch(self, epoch, train_loss, dt, n_train, val_loss, val_acc, val_f1, grad=None, dom=None, avg=None, kd=None, sam=None,
-                      dro=None) -> bool:
+                      dro=None, supcon=None) -> bool:
         """Scheduler step, history, log line, early stopping (trainer.py:160-185); True = stop training.  grad: grad_norm_summary of
         the epoch when max_grad_norm is set — three more history keys and a suffix of the log line; None leaves both as they were.
         dom: SubjectAdversary.epoch_summary of the epoch when config['adversary'] is set, likewise.  avg: the validation pass under
@@ -449,7 +478,9 @@ class Trainer:
         Distillation.epoch_summary of the epoch for a student (set_distillation): kd_loss and kd_agreement, likewise.  sam:
         sam.summary of the epoch when config['trainer']['sam'] is set: sam_grad_norm, sam_grad_norm_max and sam_sharpness, likewise.
         dro: dro_epoch of the epoch when config['trainer']['group_dro'] is set: the robust loss, the worst group's loss and subject,
-        max and entropy of q, the per-subject losses and weights and the worst validation subject, likewise (it steers nothing)."""
+        max and entropy of q, the per-subject losses and weights and the worst validation subject, likewise (it steers nothing).
+        supcon: SupCon.epoch_summary of the epoch when config['trainer']['supcon'] is set: supcon_loss, supcon_top1 and
+        supcon_anchors, likewise."""
         self.scheduler.step(val_loss)
         self.history.append(dict(epoch=epoch + 1, train_loss=train_loss, val_loss=val_loss, val_acc=val_acc, val_f1=val_f1,
                                  lr=self.optimizer.hyper["lr"], seconds=dt))
@@ -476,6 +507,11 @@ class Trainer:
                            f"({dro['dro_worst_subject']}) | q max: {dro['dro_q_max']:.4f} | q entropy: {dro['dro_q_entropy']:.4f}")
             if dro["val_worst_subject_acc"] is not None:
                 suffix += f" | worst val subject: {dro['val_worst_subject']} acc {dro['val_worst_subject_acc']:.4f}"
+        if supcon is not None:
+            self.history[-1].update(supcon)
+            if supcon["supcon_loss"] is not None:
+                suffix += (f" | supcon loss: {supcon['supcon_loss']:.4f} | top-1: {supcon['supcon_top1']:.4f} | "
+                           f"anchors: {supcon['supcon_anchors']:.1f}")
         if avg is not None:
             self.history[-1].update(avg)
             if avg["val_loss_avg"] is not None:

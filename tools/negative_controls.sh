@@ -37,6 +37,43 @@
 # of tests/test_channel_class_range_gpu.py and the input-gradient cases (T = 511) of tests/test_input_regimes_gpu.py — which must PASS:
 # that pass is the evidence that the suite had the gap.  Time limits, the stop at the first abnormal exit and the per-library
 # sections as in the regime mode.  LIBRARY: product 1 2 3 (default all).
+# tools/negative_controls.sh supcon [OUT] [LIBRARY ...]: the control of the SUPERVISED CONTRASTIVE term (library
+# built by  make -C multimodalsignal_amd/csrc negctl SUPCON=1 ): sc_grad_kernel without the transposed term C_ji (msig_dev.h
+# MSIG_NEGCTL_SUPCON).  Per library: one pass of the `apply` parity cases of tests/test_supcon_gpu.py — the product must pass every
+# case, the control must FAIL every case whose gradient is not identically zero (B = 1 has no anchor and writes nothing; at B = 2 an
+# anchor has one positive and nothing else in A(i), so C_ij = 1 - 1 = 0 whatever the features are).  Time limit, the stop at the
+# first abnormal exit and the per-library sections as in the regime mode.  LIBRARY: product 1 (default both).
+if [ "$1" = supcon ]; then
+  OUT=${2:-supcon_negctl_out/supcon_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1}
+  NEW=tests/test_supcon_gpu.py::test_apply_matches_the_fp64_restatement
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_supcon$k.so; fi
+    sec=$D/supcon_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/supcon_negctl_${k}.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# $NEW (exit $rc):   $(tail -1 $D/supcon_negctl_${k}.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/supcon_negctl_${k}.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass every case" >> $sec; bad=1; }
+      continue
+    fi
+    npass=$(grep -E "^PASSED " $D/supcon_negctl_${k}.txt | grep -vc "\[[12]-")
+    nfail=$(grep -c "^FAILED " $D/supcon_negctl_${k}.txt)
+    if [ "$npass" = 0 ] && [ "$nfail" -gt 0 ]; then echo "# verdict: control $k FAILS all $nfail cases with B >= 3 (B = 1, 2: the gradient is identically zero)" >> $sec
+    else echo "!! control $k passes $npass cases with B >= 3: the gate does not catch it there" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh supcon: $NEW against libmsig_hip_supcon1.so (make negctl SUPCON=1)" > "$OUT"
+  for k in product 1; do [ -f $D/supcon_negctl_section_$k.log ] && cat $D/supcon_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = length ]; then
   OUT=${2:-length_negctl_out/length_negative_control.log}
   D=$(dirname "$OUT")
