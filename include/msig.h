@@ -85,11 +85,11 @@ enum msig_ws {
   MSIG_WS_GATE_S,        /* (B,C)      sigmoid gate               models.py:29 */
   MSIG_WS_Y1,            /* (B,L1,16)  conv1 output, time-major (NLC)          */
   MSIG_WS_BN1_PART,      /* partial sums for BatchNorm-1 statistics (f32 + f64) */
-  MSIG_WS_BN1_STAT,      /* mean,invstd,scale,shift (4 x 16)                   */
+  MSIG_WS_BN1_STAT,      /* mean,invstd,scale,shift,mean rounding/spread (5 x 16) */
   MSIG_WS_P1,            /* (B,P1,16)  after BN+ReLU+MaxPool (NLC)             */
   MSIG_WS_Y2,            /* (B,L2,32)  conv2 output (NLC)                      */
-  MSIG_WS_BN2_PART,
-  MSIG_WS_BN2_STAT,      /* 4 x 32                                             */
+  MSIG_WS_BN2_PART,      /* the same for BatchNorm-2 (f32 + f64)               */
+  MSIG_WS_BN2_STAT,      /* 5 x 32                                             */
   MSIG_WS_P2,            /* (B,TP,32)  == x.permute(0,2,1)        models.py:77 */
   MSIG_WS_H0,            /* (B,TP,128) GRU layer-0 outputs [fwd|rev]           */
   MSIG_WS_H1,            /* (B,TP,64)  GRU layer-1 forward-direction outputs   */

@@ -157,11 +157,11 @@ extern "C" int msig_workspace_layout(const msig_shape* s, int training, int64_t*
   sz[MSIG_WS_GATE_S] = B * d.C * F;
   sz[MSIG_WS_Y1] = B * d.L1 * 16 * F;
   sz[MSIG_WS_BN1_PART] = (int64_t)MSIG_PERSIST_WG * 32 * (F + (int64_t)sizeof(double));      // unshifted float rows, then shifted double rows (msig_dev.h)
-  sz[MSIG_WS_BN1_STAT] = 64 * F;
+  sz[MSIG_WS_BN1_STAT] = 80 * F;      // five rows: bn_finalize_kernel (frontend.hip)
   sz[MSIG_WS_P1] = B * d.P1 * 16 * F;
   sz[MSIG_WS_Y2] = B * d.L2 * 32 * F;
-  sz[MSIG_WS_BN2_PART] = (int64_t)MSIG_PERSIST_WG * 64 * F;
-  sz[MSIG_WS_BN2_STAT] = 128 * F;
+  sz[MSIG_WS_BN2_PART] = (int64_t)MSIG_PERSIST_WG * 64 * (F + (int64_t)sizeof(double));      // the same two sets of rows
+  sz[MSIG_WS_BN2_STAT] = 160 * F;
   sz[MSIG_WS_P2] = B * d.TP * 32 * F;
   sz[MSIG_WS_H0] = B * d.TP * 128 * F;
   sz[MSIG_WS_H1] = B * d.TP * 64 * F;

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
   const int nchunk = (L1 + C1_CHUNK - 1) / C1_CHUNK;
   const int nitems = B * nchunk;
   f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, ssq = {0.f, 0.f, 0.f, 0.f};
-  // the same sums of channels lq * 4 + e shifted by this thread's first value of each (msig_dev.h, "BatchNorm-1 batch statistics")
+  // the same sums of channels lq * 4 + e shifted by this thread's first value of each (msig_dev.h, "BatchNorm batch statistics")
   f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, dsq = {0.f, 0.f, 0.f, 0.f}, piv = {0.f, 0.f, 0.f, 0.f};
   int nacc = 0;
   // Software pipeline (compile-time channel count, T % 4 == 0): the next item's x chunk and gate values are
@@ -356,8 +356,8 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------
-// conv2 forward: Conv1d(16,32,k5,s2,p2), NLC in / NLC out + BN partials — with stage 1's BatchNorm + ReLU + MaxPool fused into
-// its staging (round 2).  As two kernels, p1 was written by bn_relu_pool<16> and read back by conv2_fwd (0.31 + 0.23 ms,
+// conv2 forward: Conv1d(16,32,k5,s2,p2), NLC in / NLC out + BN partials (unshifted float rows, then shifted double rows, msig_dev.h)
+// — with stage 1's BatchNorm + ReLU + MaxPool fused into its staging (round 2).  As two kernels, p1 was written by bn_relu_pool<16> and read back by conv2_fwd (0.31 + 0.23 ms,
 // 2.56 GB); here an item stages the y1 rows of its chunk
 // (4 t0 - 5 .. 4 t0 + 513) normalised into LDS, pools them into the p1 rows the convolution needs (2 t0 - 2 .. 2 t0 + 256), writes the
 // rows it OWNS (2 t0 .. 2 t0 + 255: every p1 row has exactly one owner) with their pooling codes for the backward pass, and runs
@@ -386,6 +386,10 @@ __global__ __launch_bounds__(256, 2) void pool1_conv2_fwd_kernel(const float* __
   const int nchunk = (L2 + C2_CHUNK - 1) / C2_CHUNK;
   const int nitems = B * nchunk;
   f32x4 ssum[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, ssq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  // the same sums of channels ob * 16 + lq * 4 + e shifted by this thread's first value of each (msig_dev.h, "BatchNorm batch statistics")
+  f32x4 dsum[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dsq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  f32x4 piv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  int nacc = 0;
   const float NINF = -__builtin_huge_valf();
   // every piece a thread stages has channel quad c4 = tid & 3
   const int c4s = tid & 3;
@@ -469,6 +473,14 @@ __global__ __launch_bounds__(256, 2) void pool1_conv2_fwd_kernel(const float* __
           ssum[0][e] += acc0[e]; ssq[0][e] += acc0[e] * acc0[e];
           ssum[1][e] += acc1[e]; ssq[1][e] += acc1[e] * acc1[e];
         }
+        if (nacc == 0) { piv[0] = acc0; piv[1] = acc1; }
+        ++nacc;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d0 = acc0[e] - piv[0][e], d1 = acc1[e] - piv[1][e];
+          dsum[0][e] += d0; dsq[0][e] += d0 * d0;
+          dsum[1][e] += d1; dsq[1][e] += d1 * d1;
+        }
       }
     }
   }
@@ -484,6 +496,20 @@ __global__ __launch_bounds__(256, 2) void pool1_conv2_fwd_kernel(const float* __
       }
     __syncthreads();
     if (tid < 64) part[(size_t)blockIdx.x * 64 + tid] = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
+    // the shifted sums: unshifted in double, reduced in double (as conv1_fwd_kernel has them)
+    double* redd = (double*)zs;   // [4 waves][64]: every thread is past its last read of zs (the barrier before its last convolution)
+#pragma unroll
+    for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        double s1, s2;
+        bn_unshift(nacc, piv[ob][e], dsum[ob][e], dsq[ob][e], s1, s2);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+        if (li == 0) { redd[w * 64 + ob * 16 + lq * 4 + e] = s1; redd[w * 64 + 32 + ob * 16 + lq * 4 + e] = s2; }
+      }
+    __syncthreads();
+    if (tid < 64) bn_shifted_part(part, 32)[(size_t)blockIdx.x * 64 + tid] = (redd[tid] + redd[64 + tid]) + (redd[128 + tid] + redd[192 + tid]);
   }
 }
 
@@ -491,7 +517,8 @@ __global__ __launch_bounds__(256, 2) void pool1_conv2_fwd_kernel(const float* __
 
 // ------------------------------------------------------------------------------------
 // BatchNorm statistics -> (mean, invstd, scale, shift); running-stat update
-// part: [nrows][2*CH] = per-workgroup (sum[CH], sumsq[CH]); stage 1's is followed by its shifted double rows (msig_dev.h).  stat: 4*CH floats.
+// part: [nrows][2*CH] = per-workgroup (sum[CH], sumsq[CH]), followed by the stage's shifted double rows (msig_dev.h).  stat: 5*CH floats
+// (mean, invstd, scale, shift, and the rounding of the mean in units of the spread).
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* __restrict__ part, int nrows, int CH, double count,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -503,7 +530,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
   const int tid = threadIdx.x;
   if (training) {
     double s1, s2;
-    bn_batch_sums(part, nrows, CH, count, red, s1, s2);      // stage 1: unshifted or shifted sums per channel (msig_dev.h)
+    const bool shifted = bn_batch_sums(part, nrows, CH, count, red, s1, s2);      // unshifted or shifted sums per channel (msig_dev.h)
     if (tid < CH) {
       const double mean = s1 / count;
       double var = s2 / count - mean * mean;
@@ -514,6 +541,9 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
       stat[CH + tid] = invstd;
       stat[2 * CH + tid] = sc;
       stat[3 * CH + tid] = beta[tid] - (float)mean * sc;
+      // what every consumer's xhat = (y - (float)mean) * invstd is off by, for bn_bwd_finalize_kernel; 0 on the unshifted side of the
+      // switch, where |mean| is a few spreads and nothing that ran before may move
+      stat[4 * CH + tid] = shifted ? (float)((mean - (double)(float)mean) * (double)invstd) : 0.f;
       const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
       float new_mean, new_var;
       bn_running_update(momentum, (float)mean, (float)unbiased, run_mean[tid], run_var[tid], new_mean, new_var);
@@ -528,6 +558,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
     stat[CH + tid] = invstd;
     stat[2 * CH + tid] = sc;
     stat[3 * CH + tid] = beta[tid] - run_mean[tid] * sc;
+    stat[4 * CH + tid] = 0.f;
   }
 }
 
@@ -665,16 +696,25 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_pass1(const float* __restrict
 // sums -> c1 = mean(dz), c2 = mean(dz*xhat); also d(gamma), d(beta).  After an eval-mode forward (batch_stats = 0) the normalisation
 // used constants (the running statistics), not functions of the batch: BatchNorm's backward is then dy = scale * dz, i.e. c1 = c2 = 0
 // in the consumers' scale * (dz - c1 - xhat * c2); d(gamma) = sum dz * xhat and d(beta) = sum dz as in training.
+// The consumers form xhat = (y - (float)mean) * invstd: the exact xhat plus m = (mean - (float)mean) * invstd, a constant per channel
+// that a channel hundreds of spreads off centre makes 1e-6 (tests/regimes.py conv2_offcentre), and scale * (dz - c1 - xhat * c2) then
+// no longer sums to zero over the batch — at one window that put dL/d(beta of BatchNorm-1) 1.2e-5 of its largest element off.  With
+// g = sum dz * xhat - m * sum dz, c2 = g / n and c1 = (sum dz - m * g) / n the consumers' expression is the exact one again, and
+// d(gamma) = g; m is stat's fifth row (bn_finalize_kernel), 0 wherever the unshifted sums were taken: every bit as before there.
 __global__ __launch_bounds__(FIN_THREADS) void bn_bwd_finalize_kernel(const float* __restrict__ part, int nrows, int CH, double count,
-                                                              float* __restrict__ cstat, float* __restrict__ dgamma,
-                                                              float* __restrict__ dbeta, int batch_stats, const FoldCtx fc) {
-  FOLD_BEGIN; FS(part); FS(cstat); FS(dgamma); FS(dbeta);
+                                                              const float* __restrict__ stat, float* __restrict__ cstat,
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, int batch_stats,
+                                                              const FoldCtx fc) {
+  FOLD_BEGIN; FS(part); FS(stat); FS(cstat); FS(dgamma); FS(dbeta);
   __shared__ double red[FIN_THREADS];
   const int tid = threadIdx.x, ncol = 2 * CH;
   fin_colsums(part, nrows, ncol, red);
   if (tid < ncol) {
-    const double s = red[tid];
-    if (tid < CH) dbeta[tid] = (float)s; else dgamma[tid - CH] = (float)s;
+    const int ch = tid < CH ? tid : tid - CH;
+    const double sdz = red[ch], m = batch_stats ? (double)stat[4 * CH + ch] : 0.0;
+    const double g = red[CH + ch] - m * sdz;
+    const double s = tid < CH ? sdz - m * g : g;
+    if (tid < CH) dbeta[tid] = (float)sdz; else dgamma[ch] = (float)g;
     cstat[tid] = batch_stats ? (float)(s / count) : 0.f;
   }
 }
@@ -1426,7 +1466,7 @@ int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
     { MSIG_K("pool_bn_bwd_pass1_32", st); pool_bn_bwd_pass1<32><<<dim3(grid, 1, fc.n), 256, 0, st>>>(dxa, dxb, w.p<uint8_t>(MSIG_WS_POOLC2), w.p<float>(MSIG_WS_Y2),
                                                 w.p<float>(MSIG_WS_BN2_STAT), w.p<float>(MSIG_WS_DY2), bpart, d.B, d.L2, d.TP, fc); }
     MSIG_LAUNCH_CHECK();
-    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 32, (double)d.B * d.L2, cstat, G + po[MSIG_P_BN2_G], G + po[MSIG_P_BN2_B], b->training, fc); }
+    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 32, (double)d.B * d.L2, w.p<float>(MSIG_WS_BN2_STAT), cstat, G + po[MSIG_P_BN2_G], G + po[MSIG_P_BN2_B], b->training, fc); }
     MSIG_LAUNCH_CHECK();
     // (pass 2 of this stage is fused into the staging of conv2_bwd: WS_DY2 keeps dL/d(bn2 output))
   }
@@ -1460,7 +1500,7 @@ int launch_frontend_bwd(const msig_batch* b, const StageDims& d, const WsPtrs& w
 #undef C1B
     }
     MSIG_LAUNCH_CHECK();
-    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 16, (double)d.B * d.L1, cstat, G + po[MSIG_P_BN1_G], G + po[MSIG_P_BN1_B], b->training, fc); }
+    { MSIG_K("bn_bwd_finalize", st); bn_bwd_finalize_kernel<<<dim3(1, 1, fc.n), FIN_THREADS, 0, st>>>(bpart, grid, 16, (double)d.B * d.L1, w.p<float>(MSIG_WS_BN1_STAT), cstat, G + po[MSIG_P_BN1_G], G + po[MSIG_P_BN1_B], b->training, fc); }
     MSIG_LAUNCH_CHECK();
     {
       MSIG_K("conv1_bwd_fin", st);

@@ -117,6 +117,15 @@ constexpr int msig_negctl_input = MSIG_NEGCTL_INPUT;
 #else
 constexpr int msig_negctl_input = 0;
 #endif
+// Negative control of the stage-2 regimes (make negctl STAGE2=1; never defined in the product library): bn_batch_sums takes the unshifted
+// fp32 sums for every channel of stage 2 (CH = 32) — the arithmetic stage 2 had before pool1_conv2_fwd_kernel carried shifted sums: exact
+// enough on every channel near its centre, wrong where conv2's mean sits hundreds of spreads out (the conv2_offcentre cases of
+// tests/test_stage2_regimes_gpu.py must FAIL against it; tools/negative_controls.sh stage2).
+#ifdef MSIG_NEGCTL_STAGE2
+constexpr int msig_negctl_stage2 = MSIG_NEGCTL_STAGE2;
+#else
+constexpr int msig_negctl_stage2 = 0;
+#endif
 // Negative controls of the window lengths (make negctl LENGTH=k; never defined in the product library): one slip each in a guard that
 // only an unaligned window with more than one chunk reaches — a changed comparison, never an address the product does not also form
 // (tests/test_window_lengths_gpu.py must FAIL against each; tools/negative_controls.sh length).
@@ -618,11 +627,14 @@ PartOffsets part_offsets(const StageDims& d);
 #define MSIG_PERSIST_WG 1024
 #define MSIG_DW_WG 512
 
-// ---- BatchNorm-1 batch statistics (conv1_fwd_kernel) ---------------------------------------------------------------------------
+// ---- BatchNorm batch statistics (conv1_fwd_kernel, pool1_conv2_fwd_kernel) --------------------------------------------------------
 // conv1 sees the raw input: a channel that sits many spreads from zero (a temperature column, a subject normalised against resting
-// windows) gives conv1 outputs with mean^2 >> var.  Stage 2 sees BatchNorm-1's normalised, rectified output and keeps its one set of
-// sums (BN1_STAGE_CH tells the stages apart).  A conv1 workgroup writes TWO rows of partial sums (WS_BN1_PART:
-// [MSIG_PERSIST_WG][32] floats, then [MSIG_PERSIST_WG][32] doubles):
+// windows) gives conv1 outputs with mean^2 >> var.  conv2 sees BatchNorm-1's normalised, rectified output — centred enough near
+// initialisation (mean^2 / var <= 7), but a trained BatchNorm-1 channel with a small gamma under a positive beta is "always on", and
+// one-signed conv2 taps over such channels put conv2's mean a thousand spreads out (tests/regimes.py conv2_offcentre: mean^2 / var up
+// to 1300; the one set of sums stage 2 used to keep failed the parity gate there at 1 .. 37 work items).  A workgroup of either kernel
+// writes TWO rows of partial sums (WS_BN1_PART: [MSIG_PERSIST_WG][32] floats, then [MSIG_PERSIST_WG][32] doubles; WS_BN2_PART the
+// same with 64 columns):
 //   unshifted  sum y, sum y^2 per thread in fp32, reduced in fp32 — the sums this library has always formed.  Their variance
 //              E[y^2] - mean^2 loses mean^2 / var of its relative precision: exact enough while the channel mean is a few spreads,
 //              100 x worse at 10 spreads;
@@ -641,20 +653,24 @@ __device__ __forceinline__ void bn_unshift(int n, float p, float sd, float sq, d
 }
 __device__ __forceinline__ const double* bn_shifted_part(const float* part, int CH) { return (const double*)(part + (size_t)MSIG_PERSIST_WG * 2 * CH); }
 __device__ __forceinline__ double* bn_shifted_part(float* part, int CH) { return (double*)(part + (size_t)MSIG_PERSIST_WG * 2 * CH); }
-// For tid < CH: the batch's sum y (s1) and sum y^2 (s2) of channel tid.  Called by all FIN_THREADS threads; red: FIN_THREADS doubles.
-__device__ __forceinline__ void bn_batch_sums(const float* __restrict__ part, int nrows, int CH, double count, double* red, double& s1, double& s2) {
+// For tid < CH: the batch's sum y (s1) and sum y^2 (s2) of channel tid; returns whether they are the shifted ones.  Called by all
+// FIN_THREADS threads; red: FIN_THREADS doubles.
+__device__ __forceinline__ bool bn_batch_sums(const float* __restrict__ part, int nrows, int CH, double count, double* red, double& s1, double& s2) {
   const int tid = threadIdx.x;
   fin_colsums(part, nrows, 2 * CH, red);          // 2 * CH <= 64 columns
   s1 = 0.0; s2 = 0.0;
   if (tid < CH) { s1 = red[tid]; s2 = red[CH + tid]; }
-  if (msig_negctl_input == 1 || CH != BN1_STAGE_CH) return;
+  if (msig_negctl_input == 1 || (msig_negctl_stage2 == 1 && CH != BN1_STAGE_CH)) return false;
   __syncthreads();
   fin_colsums(bn_shifted_part(part, CH), nrows, 2 * CH, red);
+  bool shifted = false;
   if (tid < CH) {
     const double t1 = red[tid], t2 = red[CH + tid], m = t1 / count;
     double v = t2 / count - m * m;
     if (v < 0.0) v = 0.0;
-    if (m * m > BN_SHIFT_RATIO * v) { s1 = t1; s2 = t2; }
+    shifted = m * m > BN_SHIFT_RATIO * v;
+    if (shifted) { s1 = t1; s2 = t2; }
   }
+  return shifted;
 }
 #define MSIG_CONV_DW_WG 1024      // conv weight-gradient kernels: 4 workgroups per CU hide their staging latency

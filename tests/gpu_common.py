@@ -40,6 +40,10 @@ from oracle import cnn_gru_oracle as O
 # The same table over WINDOW LENGTHS (every residue T % 16, unaligned lengths and T % 8 == 4 across the conv chunk borders, T' = 2 .. 8:
 # tests/window_lengths.py, tests/test_window_lengths_gpu.py, held to these constants unchanged) is in DESIGN.md section 2, "Window
 # lengths"; its negative controls (make negctl LENGTH=k) in profiles/length_negative_control.log.
+# The same table over STAGE-2 regimes (conv2 channels at mean^2 / var of 16 .. 200 and 500 .. 1300 at 1, 2, 4, 24, 37 and 300 work items,
+# zeroed and 1e-3 / 1e3 convolution rows: tests/regimes.py, tests/test_stage2_regimes_host.py, tests/test_stage2_regimes_gpu.py, held to
+# these constants unchanged) is in DESIGN.md section 2, "Stage-2 regimes"; its negative control (make negctl STAGE2=1) in
+# profiles/stage2_negative_control.log.
 K_STAGE, STAGE_FLOOR = 8.0, 2e-6
 K_GRAD = 6.0
 GRAD_FLOORS = (("gru.", 3e-6), ("classifier.3.bias", 1.2e-5), ("", 6e-6))      # first matching prefix

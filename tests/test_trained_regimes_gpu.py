@@ -28,7 +28,8 @@ OWN_CAP = 1e-5
 MAIN = (24, 6, 2, 256, 0.5)            # two batch tiles (the second ragged), T' = 16, C = 6: one live hidden unit in the gate MLP
 RAGGED = (37, 3, 3, 72, 0.25)          # three tiles (the last ragged), odd T' = 5, K = 3, no gate
 LONG = (4, 6, 2, 3840, 0.5)            # the default window, T' = 240: a unit with z == 1 carries its state through all of it
-CASES = ([(r, *MAIN, f) for r in regimes.REGIMES for f in SHIPPED]
+TRAINED = tuple(r for r in regimes.REGIMES if r not in regimes.STAGE2_REGIMES)      # those run in tests/test_stage2_regimes_gpu.py, MAIN included
+CASES = ([(r, *MAIN, f) for r in TRAINED for f in SHIPPED]
          + [(r, *RAGGED, f) for r in ("z_sat", "r_sat") for f in SHIPPED]
          + [(r, *LONG, "ws6") for r in ("z_sat", "r_sat")]
          + [("z_sat", *MAIN, f) for f in OTHER])      # each has its own copy of the recovery of n
@@ -107,6 +108,8 @@ def assert_regime_active(regime, named, st64):
             assert any((p[:, c] == p[0, c, 0]).all() and p[0, c, 0] > 0 for c in dead_pos), f"{stage}: no constant positive channel"
     elif regime == "head_sat":
         assert np.abs(st64["logits"]).max() > 88.0, np.abs(st64["logits"]).max()
+    elif regime in regimes.STAGE2_REGIMES:      # conv2's mean^2 / var in the regime's band beside an ordinary channel; the zeroed / scaled rows
+        regimes.assert_stage2_regime_active(regime, named, st64)
 
 
 def assert_own_capped(own):

@@ -43,6 +43,52 @@
 # case, the control must FAIL every case whose gradient is not identically zero (B = 1 has no anchor and writes nothing; at B = 2 an
 # anchor has one positive and nothing else in A(i), so C_ij = 1 - 1 = 0 whatever the features are).  Time limit, the stop at the
 # first abnormal exit and the per-library sections as in the regime mode.  LIBRARY: product 1 (default both).
+# tools/negative_controls.sh stage2 [OUT] [LIBRARY ...]: the control of the STAGE-2 regimes (DESIGN.md "Stage-2 regimes"; library built by
+#   make -C multimodalsignal_amd/csrc negctl STAGE2=1 ): bn_batch_sums takes the unshifted fp32 sums for every conv2 channel (msig_dev.h
+# MSIG_NEGCTL_STAGE2) — the arithmetic stage 2 had before pool1_conv2_fwd_kernel carried shifted sums.  Per library: one pass of
+# tests/test_stage2_regimes_gpu.py (the product must pass every case; the control must FAIL the conv2_offcentre cases at one, two and
+# four work items) and one of the files that held the regimes BEFORE, tests/test_trained_regimes_gpu.py and
+# tests/test_input_regimes_gpu.py, which must PASS against the control: it is the arithmetic they always ran, and that pass is the
+# evidence that the suite had the gap.  Time limits, the stop at the first abnormal exit and the per-library sections as in the regime
+# mode.  LIBRARY: product 1 (default both).
+if [ "$1" = stage2 ]; then
+  OUT=${2:-stage2_negctl_out/stage2_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1}
+  NEW=tests/test_stage2_regimes_gpu.py
+  OLDF='tests/test_trained_regimes_gpu.py tests/test_input_regimes_gpu.py'
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_stage2$k.so; fi
+    sec=$D/stage2_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/stage2_negctl_${k}_new.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# new file, $NEW (exit $rc):   $(tail -1 $D/stage2_negctl_${k}_new.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/stage2_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    nfail=$(grep -c "^FAILED " $D/stage2_negctl_${k}_new.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass the new file" >> $sec; bad=1; }
+      continue
+    fi
+    nwant=$(grep "^FAILED " $D/stage2_negctl_${k}_new.txt | grep -cE "conv2_offcentre-(1-6|2-6|4-3)-2-256")
+    if [ "$nwant" = 6 ]; then echo "# verdict: control $k FAILS $nfail new cases, all 6 conv2_offcentre cases at 1, 2 and 4 work items among them" >> $sec
+    else echo "!! control $k fails $nwant of the 6 conv2_offcentre cases at 1, 2 and 4 work items ($nfail failures in all)" >> $sec; bad=1; fi
+    MSIG_LIB=$lib timeout -k 10 600 python -m pytest $OLDF -q -rA -p no:cacheprovider > $D/stage2_negctl_${k}_old.txt 2>&1; rc=$?
+    echo "# the regime files the suite had, $OLDF (exit $rc):   $(tail -1 $D/stage2_negctl_${k}_old.txt)" >> $sec
+    grep -E "^FAILED " $D/stage2_negctl_${k}_old.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ $rc = 0 ]; then echo "# verdict: the regime files the suite had do NOT notice control $k" >> $sec
+    else echo "!! the regime files the suite had notice control $k: it is the arithmetic they always ran and must pass them" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh stage2: $NEW and $OLDF against libmsig_hip_stage21.so (make negctl STAGE2=1)" > "$OUT"
+  for k in product 1; do [ -f $D/stage2_negctl_section_$k.log ] && cat $D/stage2_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = supcon ]; then
   OUT=${2:-supcon_negctl_out/supcon_negative_control.log}
   D=$(dirname "$OUT")
