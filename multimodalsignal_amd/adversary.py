@@ -3,7 +3,7 @@
 A ``SubjectAdversary`` is the discriminator D = Linear(128, 64) -> ReLU -> Linear(64, S) of ONE model: its flat parameter and Adam
 moment buffers, its own optimiser step count, the schedule of the reversal weight lambda and the int32 table that maps a store
 position to the domain (training subject) of the window there.  The arithmetic is the library's: ``runtime.Engine.train_step(...,
-adversary=)`` and ``multifold.LockstepTrainer`` hand these buffers to ``msig_da_train_step[_multi]``.  The buffers are no part of
+adversary=)`` and ``multifold.LockstepTrainer`` hand these buffers to the one train-step call (``msig_sc_train_step[_multi]``) as its ``msig_da``.  The buffers are no part of
 the model's ``state_dict``: ``best_model.pt`` is what it is without the adversary.
 """
 from __future__ import annotations
@@ -127,7 +127,7 @@ class SubjectAdversary:
                 "2.weight": flat[lay[2]:lay[2] + S * 64].view(S, 64), "2.bias": flat[lay[3]:lay[3] + S]}
 
     def bind(self, device, storage: Optional[dict] = None) -> "SubjectAdversary":
-        """Moves the buffers to `device`, or with `storage` (runtime.FoldArena.adversary_storage) into one fold's regions of an arena:
+        """Moves the buffers to `device`, or with `storage` (runtime.FoldArena.side_storage("adversary", slot)) into one fold's regions of an arena:
         float32 "params" / "exp_avg" / "exp_avg_sq", float64 "stats", int32 "dom"."""
         if storage is None:
             for name in ("params", "exp_avg", "exp_avg_sq", "stats", "dom"):

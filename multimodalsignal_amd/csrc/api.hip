@@ -304,6 +304,24 @@ extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg,
   return launch_adam(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
 }
 
+// One pass of a train step, forward through front-end backward, with every optional term at its place; the weight-gradient partials go to
+// `plan`, which the caller reduces.  Both passes of a sharpness-aware step and every other step run THIS sequence: a term has one place.
+// head_step: the head's forward, CrossEntropy and backward as one launch (train_step_fc decides).  Reads every field of o but clip and sam.
+static int step_pass(const msig_batch* b, const Ctx& c, const FoldCtx& fc, hipStream_t st, const StepOpts& o, bool head_step, ColsumPlan& plan) {
+  int rc;
+  if ((rc = forward_fc(b, fc, st, o, !head_step))) return rc;
+  if (o.dro && (rc = launch_dro_apply(*o.dro, c.w.p<float>(MSIG_WS_LOGITS), b->labels, o.cw, c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
+  if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
+  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, o) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
+  // subject discriminator (include/msig_da.h): WS_FEAT and WS_DFEAT are complete here; its launch adds the reversed gradient to WS_DFEAT
+  // (never under a sharpness-aware step: st_train_step refuses the pair)
+  if (o.da && (rc = launch_da_step(*o.da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
+  // supervised contrastive term (include/msig_sc.h): two launches that add its gradient to WS_DFEAT; the head stays fused where it was
+  if (o.sc && (rc = launch_sc_apply(*o.sc, c.w.p<float>(MSIG_WS_FEAT), b->labels, c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
+  if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
+  return launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !o.cg);
+}
+
 // fc.lr_over_bc1 is filled in here from `lr` (single fold) or from m->lr (fold batch).  Reads every field of o.
 static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, const int64_t* steps, float* exp_avg, float* exp_avg_sq, float beta1,
                          float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const StepOpts& o) {
@@ -321,17 +339,11 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   if ((rc = make_ctx(b, c, true, cg))) return rc;          // every argument check of the step before its first launch
   if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;
   fc.fused_step = 1;        // forward and backward forms resolve from this one descriptor: gru_fwd_ws may store the two-vector stash
-  // sharpness-aware step (include/msig_sam.h): pass 1 here — forward with the head unfused, backward, the reduction WITHOUT Adam, the
-  // perturbation — then this function once more on copies of the descriptors that report nowhere (pass2), with the same keys
+  // sharpness-aware step (include/msig_sam.h): pass 1 here — the pass with the head unfused and a plan of its own, the reduction WITHOUT
+  // Adam, the perturbation — then this function once more on copies of the descriptors that report nowhere (pass2), with the same keys
   if (o.sam && !o.sam->pass2) {
-    if ((rc = forward_fc(b, fc, st, o, true))) return rc;
-    if (o.dro && (rc = launch_dro_apply(*o.dro, c.w.p<float>(MSIG_WS_LOGITS), b->labels, o.cw, c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
-    if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
     ColsumPlan plan1;
-    if ((rc = launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan1, fc, st))) return rc;
-    if (o.sc && (rc = launch_sc_apply(*o.sc, c.w.p<float>(MSIG_WS_FEAT), b->labels, c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
-    if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan1, fc, st))) return rc;
-    if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan1, fc, st, !cg))) return rc;
+    if ((rc = step_pass(b, c, fc, st, o, false, plan1))) return rc;
     if ((rc = launch_colsum_plan(plan1, fc, st))) return rc;
     if ((rc = launch_sam_perturb(*o.sam, (float*)b->params, b->grads, b->bn_state, b->bn_count, c.w.p<float>(MSIG_WS_LOSS), fc, st))) return rc;
     msig_batch b2 = *b;
@@ -354,19 +366,10 @@ static int train_step_fc(const msig_batch* b, FoldCtx fc, const float* lrs, cons
   // a sharpness-aware step's second pass restores MSIG_WS_LOSS before the last launch, where head_step would finalise its sums: unfused
   // group-DRO (include/msig_dro.h) rescales WS_DLOGITS between the criterion and the distillation term: unfused
   const bool head_step = !o.kd && !o.sam && !o.dro && head_step_applies(b, c.d);
-  if ((rc = forward_fc(b, fc, st, o, !head_step))) return rc;
-  if (o.dro && (rc = launch_dro_apply(*o.dro, c.w.p<float>(MSIG_WS_LOGITS), b->labels, o.cw, c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
-  if (o.kd && (rc = launch_kd_apply(*o.kd, c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), fc, st))) return rc;
-  // backward, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
+  // the pass, then ONE launch that reduces every weight-gradient partial and applies Adam to each reduced element
   // (plus the few gradients their kernels write in place): the arithmetic of msig_backward + msig_adam_step
   ColsumPlan plan;
-  if ((rc = head_step ? launch_head_step(b, c.d, c.w, c.po, plan, fc, st, o) : launch_head_bwd(b, nullptr, c.d, c.w, c.po, plan, fc, st))) return rc;
-  // subject discriminator (include/msig_da.h): WS_FEAT and WS_DFEAT are complete here; its launch adds the reversed gradient to WS_DFEAT
-  if (o.da && (rc = launch_da_step(*o.da, c.w.p<float>(MSIG_WS_FEAT), c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
-  // supervised contrastive term (include/msig_sc.h): two launches that add its gradient to WS_DFEAT; the head stays fused where it was
-  if (o.sc && (rc = launch_sc_apply(*o.sc, c.w.p<float>(MSIG_WS_FEAT), b->labels, c.w.p<float>(MSIG_WS_DFEAT), fc, st))) return rc;
-  if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
-  if ((rc = launch_frontend_bwd(b, c.d, c.w, c.po, plan, fc, st, !cg))) return rc;
+  if ((rc = step_pass(b, c, fc, st, o, head_step, plan))) return rc;
   // second pass of a sharpness-aware step: back to w (and to pass 1's BatchNorm state and losses) before Adam reads the parameters
   if (o.sam && (rc = launch_sam_restore(*o.sam, (float*)b->params, b->bn_state, b->bn_count, c.w.p<float>(MSIG_WS_LOSS), c.d.B, fc, st))) return rc;
   const int in_place[6] = {MSIG_P_GATE_W1, MSIG_P_GATE_W2, MSIG_P_BN1_G, MSIG_P_BN1_B, MSIG_P_BN2_G, MSIG_P_BN2_B};
@@ -552,11 +555,20 @@ static int st_forward(const msig_batch* b, const FoldCtx& fc, const msig_st* s, 
 }
 static int make_da(const msig_da* a, const FoldCtx& fc, int32_t B, const float* lam, DaArgs& da);
 int msig_sc_check_align(const msig_sc* k, const FoldCtx& fc, int32_t B);      // supcon.hip: what follows msig_sc_make_args and the lam check
-// a: the subject discriminator of include/msig_da.h (NULL = msig_st_train_step[_multi] itself); k: the distillation term of
-// include/msig_kd.h (NULL, or alpha == 0 after its checks = msig_da_train_step[_multi] itself)
-static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const float* lrs, const int64_t* steps, float* exp_avg,
-                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st, const msig_da* a,
-                         const msig_kd* k = nullptr, const msig_sam* sm = nullptr, const msig_dro* dr = nullptr, const msig_sc* sk = nullptr) {
+// The optional terms of a train step as an entry point received them; a NULL member is the step without that term, StepTerms{} is
+// msig_st_train_step[_multi] itself.  A narrower entry point leaves the members it has no parameter for NULL.
+struct StepTerms {
+  const msig_da* da;        // subject discriminator (include/msig_da.h)
+  const msig_kd* kd;        // distillation (include/msig_kd.h); alpha == 0 after its checks = the step without it
+  const msig_sam* sam;      // sharpness-aware step (include/msig_sam.h); rho == 0 after its checks = the step without it
+  const msig_dro* dro;      // group-DRO (include/msig_dro.h)
+  const msig_sc* sc;        // supervised contrastive term (include/msig_sc.h)
+};
+// Every msig_{st,da,kd,sam,dro,sc}_train_step[_multi] after its own first checks: the terms' checks in the headers' order, then train_step_fc.
+static int st_train_step(const msig_batch* b, const FoldCtx& fc, const msig_st* s, const StepTerms& t, const float* lrs, const int64_t* steps,
+                         float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step, hipStream_t st) {
+  if (t.da && t.sam) return MSIG_E_SHAPE;      // two passes would advance the discriminator's own Adam twice
+  const msig_da* a = t.da; const msig_kd* k = t.kd; const msig_sam* sm = t.sam; const msig_dro* dr = t.dro; const msig_sc* sk = t.sc;
   if ((sm || dr || sk) && (!s || !b)) return MSIG_E_NULL;
   SamArgs sam;                             // include/msig_sam.h: its own checks first; rho == 0 after them = the call without it
   int rc;
@@ -602,13 +614,18 @@ extern "C" int msig_st_forward_multi(const msig_batch* b, const msig_multi* m, c
 }
 extern "C" int msig_st_train_step(const msig_batch* b, const msig_st* s, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                                   float eps, float weight_decay, int64_t step, void* stream) {
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr);
+  return st_train_step(b, single_fold(b), s, StepTerms{}, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+// the *_multi forms share their first checks: msig_st, then msig_multi's own
+static int st_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const StepTerms& t, float* exp_avg, float* exp_avg_sq,
+                               float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (!s) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return st_train_step(b, fc, s, t, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
 }
 extern "C" int msig_st_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (!s) return MSIG_E_NULL;
-  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr);
+  return st_train_step_multi(b, m, s, StepTerms{}, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 // ---- subject-adversarial training (include/msig_da.h; kernel: adversary.hip) ---------------------------------------------------------
@@ -662,79 +679,64 @@ extern "C" int msig_da_step_multi(const msig_da* a, const msig_multi* m, const f
 }
 extern "C" int msig_da_train_step(const msig_batch* b, const msig_st* s, const msig_da* a, float* exp_avg, float* exp_avg_sq, float lr,
                                   float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, a);
+  return st_train_step(b, single_fold(b), s, StepTerms{a}, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
 }
 extern "C" int msig_da_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* a, float* exp_avg,
                                         float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                                         void* stream) {
-  if (!s) return MSIG_E_NULL;
-  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, a);
+  return st_train_step_multi(b, m, s, StepTerms{a}, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 // ---- distillation (include/msig_kd.h; kernels and the stand-alone calls: distill.hip) -----------------------------------------------
 extern "C" int msig_kd_train_step(const msig_batch* b, const msig_st* s, const msig_da* da, const msig_kd* kd, float* exp_avg,
                                   float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                                   void* stream) {
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd);
+  return st_train_step(b, single_fold(b), s, StepTerms{da, kd}, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step,
+                       (hipStream_t)stream);
 }
 extern "C" int msig_kd_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* da, const msig_kd* kd,
                                         float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
                                         int64_t step, void* stream) {
-  if (!s) return MSIG_E_NULL;
-  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd);
+  return st_train_step_multi(b, m, s, StepTerms{da, kd}, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 // ---- sharpness-aware minimisation (include/msig_sam.h; kernels and the stand-alone calls: sam.hip) --------------------------------
 extern "C" int msig_sam_train_step(const msig_batch* b, const msig_st* s, const msig_kd* kd, const msig_sam* sam, float* exp_avg,
                                    float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                                    void* stream) {
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr,
-                       kd, sam);
+  return st_train_step(b, single_fold(b), s, StepTerms{nullptr, kd, sam}, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step,
+                       (hipStream_t)stream);
 }
 extern "C" int msig_sam_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_kd* kd, const msig_sam* sam,
                                          float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
                                          int64_t step, void* stream) {
-  if (!s) return MSIG_E_NULL;
-  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, nullptr, kd, sam);
+  return st_train_step_multi(b, m, s, StepTerms{nullptr, kd, sam}, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 // ---- group-DRO (include/msig_dro.h; kernel and the stand-alone calls: dro.hip) -------------------------------------------------------
 extern "C" int msig_dro_train_step(const msig_batch* b, const msig_st* s, const msig_da* da, const msig_kd* kd, const msig_sam* sam,
                                    const msig_dro* dro, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, int64_t step, void* stream) {
-  if (da && sam) return MSIG_E_SHAPE;
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da,
-                       kd, sam, dro);
+  return st_train_step(b, single_fold(b), s, StepTerms{da, kd, sam, dro}, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step,
+                       (hipStream_t)stream);
 }
 extern "C" int msig_dro_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* da, const msig_kd* kd,
                                          const msig_sam* sam, const msig_dro* dro, float* exp_avg, float* exp_avg_sq, float beta1,
                                          float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (!s) return MSIG_E_NULL;
-  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  if (da && sam) return MSIG_E_SHAPE;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd, sam,
-                       dro);
+  return st_train_step_multi(b, m, s, StepTerms{da, kd, sam, dro}, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 // ---- supervised contrastive term (include/msig_sc.h; kernels and the stand-alone calls: supcon.hip) ---------------------------------
 extern "C" int msig_sc_train_step(const msig_batch* b, const msig_st* s, const msig_da* da, const msig_kd* kd, const msig_sam* sam,
                                   const msig_dro* dro, const msig_sc* sc, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                                   float eps, float weight_decay, int64_t step, void* stream) {
-  if (da && sam) return MSIG_E_SHAPE;
-  return st_train_step(b, single_fold(b), s, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da,
-                       kd, sam, dro, sc);
+  return st_train_step(b, single_fold(b), s, StepTerms{da, kd, sam, dro, sc}, &lr, nullptr, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step,
+                       (hipStream_t)stream);
 }
 extern "C" int msig_sc_train_step_multi(const msig_batch* b, const msig_multi* m, const msig_st* s, const msig_da* da, const msig_kd* kd,
                                         const msig_sam* sam, const msig_dro* dro, const msig_sc* sc, float* exp_avg, float* exp_avg_sq,
                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
-  if (!s) return MSIG_E_NULL;
-  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
-  if (da && sam) return MSIG_E_SHAPE;
-  return st_train_step(b, fc, s, m->lr, m->step, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, da, kd, sam,
-                       dro, sc);
+  return st_train_step_multi(b, m, s, StepTerms{da, kd, sam, dro, sc}, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 // ---- window embeddings and classifier-only training (include/msig_ft.h) ---------------------------------------------------------

@@ -3,8 +3,8 @@
 A ``Distillation`` is the setting of ONE student — the weight alpha of the teacher's term and the temperature T — together with
 what the term reads and writes on the device: the fp32 teacher table (K tempered probabilities per store position, built by
 ``ensemble.Ensemble.teacher`` or ``teacher_table``) and three float64 statistics.  The arithmetic is the library's:
-``runtime.Engine.train_step(..., distill=)`` hands these buffers to ``msig_kd_train_step``, a fold batch to
-``msig_kd_train_step_multi`` (``runtime.FoldArena(..., distill=positions)`` owns the tables at arena stride).  Nothing here is part
+``runtime.Engine.train_step(..., distill=)`` hands these buffers to the one train-step call (``msig_sc_train_step``) as its
+``msig_kd``, a fold batch to its ``_multi`` form (``runtime.FoldArena(..., distill=positions)`` owns the tables in a side block).  Nothing here is part
 of a model's ``state_dict``.
 """
 from __future__ import annotations
@@ -62,7 +62,7 @@ class Distillation:
         self.q = t.contiguous()
 
     def bind(self, device, storage: Optional[dict] = None) -> "Distillation":
-        """Moves the buffers to `device`, or with `storage` (runtime.FoldArena.distill_storage) into one fold's regions of an arena:
+        """Moves the buffers to `device`, or with `storage` (runtime.FoldArena.side_storage("distill", slot)) into one fold's regions of an arena:
         float32 "q" (positions * K), float64 "stats"."""
         if storage is None:
             self.stats = self.stats.to(device)

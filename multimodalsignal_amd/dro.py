@@ -3,7 +3,7 @@
 A ``GroupDro`` is the state of ONE model's robust objective: the G adversarial weights ``q`` (uniform at 1 / G when training starts,
 never reset — not by a learning-rate reduction either), the int32 table that maps a store position to the group of the window
 there, and the epoch's statistics.  The arithmetic is the library's: ``runtime.Engine.train_step(..., dro=)`` and
-``multifold.LockstepTrainer`` hand these buffers to ``msig_dro_train_step[_multi]``, whose one extra launch moves ``q`` with the
+``multifold.LockstepTrainer`` hand these buffers to the one train-step call (``msig_sc_train_step[_multi]``) as its ``msig_dro``, whose one extra launch moves ``q`` with the
 groups' losses and rescales the logits' gradient so that the step descends sum_g q_g L_g instead of the pooled mean.  What a step
 reports stays the criterion's; the buffers are no part of the model's ``state_dict``.
 """
@@ -129,7 +129,7 @@ class GroupDro:
         return self
 
     def bind(self, device, storage: Optional[dict] = None) -> "GroupDro":
-        """Moves the buffers to `device`, or with `storage` (runtime.FoldArena.dro_storage) into one fold's regions of an arena:
+        """Moves the buffers to `device`, or with `storage` (runtime.FoldArena.side_storage("dro", slot)) into one fold's regions of an arena:
         float32 "q", float64 "stats", int32 "grp"."""
         if self.q is None:
             raise RuntimeError("the group-DRO state has no groups: call set_groups first")

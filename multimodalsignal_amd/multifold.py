@@ -14,12 +14,13 @@ stand-alone run whatever its companions, the grouping or the rank count
 (tests/test_trainer_gpu.py::test_lockstep_folds_equal_sequential, ::test_fold_results_do_not_depend_on_sharding); with
 `adaptive_forms` the backward form follows the folds still active in a launch (a fold's last bits then depend, reproducibly, on
 when its companions stop).  Folds may differ in train / val set size; folds that
-stop early leave the batch.  Every train launch is msig_da_train_step_multi and every evaluation launch msig_st_forward_multi,
-whatever the folds have switched on: runtime's module docstring says why that is bit-safe.  With config['averaging'] every train
-launch is followed by one msig_wa_update_multi over the same folds (EMA; SWA: one per epoch), each fold at its own coefficient: the
-shadows live in the arenas, where msig_st_forward_multi can evaluate them (include/msig_wa.h).  With
-config['trainer']['sam'] every train launch is msig_sam_train_step_multi instead — two passes of all folds of the launch, each fold's
-SAM state one more region of its arena (include/msig_sam.h); without the key the launches are the ones above.
+stop early leave the batch.  Every train launch is msig_sc_train_step_multi, with NULL for each optional term that is off, and every
+evaluation launch msig_st_forward_multi, whatever the folds have switched on: runtime's module docstring says why that is bit-safe.
+With config['averaging'] every train launch is followed by one msig_wa_update_multi over the same folds (EMA; SWA: one per epoch),
+each fold at its own coefficient: the shadows live in the arenas, where msig_st_forward_multi can evaluate them (include/msig_wa.h,
+DESIGN.md §22).  With config['trainer']['sam'] the same launch runs two passes of all its folds, each fold's SAM state one more
+region of its arena (include/msig_sam.h).  The buffers of the adversary, distillation, group-DRO and supervised
+contrastive terms are side blocks of the arena set, one table (runtime.FoldArena.side).
 """
 from __future__ import annotations
 
@@ -37,7 +38,7 @@ from . import dro as DRO
 from . import supcon as SC
 from . import averaging as AV
 from . import sam as SAM
-from .runtime import FoldArena
+from .runtime import FoldArena, _ref
 from .trainer import Trainer, accuracy_and_weighted_f1, grad_clip_setting, grad_norm_summary, label_smoothing_setting
 
 
@@ -240,14 +241,14 @@ class LockstepTrainer:
             if self.embedded:
                 model._engine.scatter()                        # into the padded layout, once: the steps train it in place
             if self.adv_S is not None:
-                t.prepare_adversary(p["loaders"][0], self.arena.adversary_storage(slot))
+                t.prepare_adversary(p["loaders"][0], self.arena.side_storage("adversary", slot))
             if self.kd_cfg is not None:
-                t.set_distillation(p["distill"], self.arena.distill_storage(slot))
+                t.set_distillation(p["distill"], self.arena.side_storage("distill", slot))
             t.subject_names = (p.get("train_subjects"), p.get("val_subjects"))
             if self.dro_cfg is not None:
-                t.prepare_dro(p["loaders"][0], self.arena.dro_storage(slot))
+                t.prepare_dro(p["loaders"][0], self.arena.side_storage("dro", slot))
             if self.sc_cfg is not None:
-                t.prepare_supcon(p["loaders"][0], self.arena.sc_storage(slot))
+                t.prepare_supcon(p["loaders"][0], self.arena.side_storage("supcon", slot))
             self.trainers.append(t)
         # class-weighted CrossEntropy (config['trainer']['class_weights'], include/msig_cw.h): each fold's own vector — 'balanced'
         # from its own training set — in its arena; a fold without one gets all ones, which is the unweighted criterion bit for bit
@@ -350,14 +351,11 @@ class LockstepTrainer:
         # subject adversaries: every fold's lambda of every step of the epoch from its own schedule and step count
         advs = [t.adversary for t in trs] if self.adv_S is not None else None
         if advs is not None:
-            arena.adversary_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
             dl = [[a.lam_at(a.step + 1 + k, a.total_steps) for k in range(ns)] for a, ns in zip(advs, n_steps)]
-        if self.kd_cfg is not None:
-            arena.distill_stats().index_fill_(0, torch.as_tensor(act, dtype=torch.int64, device=self.device), 0.0)
-        if self.dro_cfg is not None:
-            arena.zero_dro_stats(act)
-        if self.sc_cfg is not None:
-            arena.zero_sc_stats(act)
+        # the optional terms that are on, by their name in the arena's table of side blocks: statistics zeroed here, read back below
+        terms = [t for t, on in (("adversary", advs), ("distill", self.kd_cfg), ("dro", self.dro_cfg), ("supcon", self.sc_cfg)) if on is not None]
+        for t in terms:
+            arena.zero_side_stats(t, act)
         # weight averaging: EMA's coefficient of every step of the epoch per fold, from the fold's own update count
         avs = [t.averager for t in trs] if self.avg_cfg is not None else None
         ema = avs is not None and self.avg_cfg["mode"] == "ema"
@@ -396,34 +394,13 @@ class LockstepTrainer:
                     s.lam[j] = la[r0 + j][k]
                 if a is not None:
                     getattr(a, "lambda")[j], a.step[j] = dl[r0 + j][k], advs[r0 + j].step + 1 + k
-            if a is not None:
-                a.idx, a.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
             self._gather(loaders[0], order, r0, i, b, m, aug, s.lam if aug is not None or mix is not None else None)
             _, desc = self._layout(b, True)
-            if kd is not None:
-                kd.idx, kd.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
-            if dr is not None:
-                dr.idx, dr.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
-            if sc is not None:                 # the supervised contrastive term: the widest call, with whatever else is on
-                if sc.positives:
-                    sc.idx, sc.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
-                L.check(lib.msig_sc_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None,
-                                                     C.byref(kd) if kd is not None else None, C.byref(sm) if sm is not None else None,
-                                                     C.byref(dr) if dr is not None else None, C.byref(sc), ea, eas, b1, b2, eps, wd,
-                                                     int(steps[r0][k]), st), "msig_sc_train_step_multi")
-            elif dr is not None:               # group-DRO: the widest call without the term above, with whatever else is on
-                L.check(lib.msig_dro_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None,
-                                                      C.byref(kd) if kd is not None else None, C.byref(sm) if sm is not None else None,
-                                                      C.byref(dr), ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_dro_train_step_multi")
-            elif sm is not None:               # sharpness-aware steps: two passes of every fold of the launch, whatever else is on
-                L.check(lib.msig_sam_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(kd) if kd is not None else None, C.byref(sm),
-                                                      ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_sam_train_step_multi")
-            elif kd is not None:               # a batch of students: the same call with the distillation term (alpha 0: the call below)
-                L.check(lib.msig_kd_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, C.byref(kd),
-                                                     ea, eas, b1, b2, eps, wd, int(steps[r0][k]), st), "msig_kd_train_step_multi")
-            else:
-                L.check(lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), C.byref(a) if a is not None else None, ea, eas,
-                                                     b1, b2, eps, wd, int(steps[r0][k]), st), "msig_da_train_step_multi")
+            for d in (a, kd, dr, sc if sc is not None and sc.positives else None):      # the descriptors that read by store position
+                if d is not None:
+                    d.idx, d.idx_row_stride = order.data_ptr() + 8 * (r0 * order.shape[1] + i), order.shape[1]
+            L.check(lib.msig_sc_train_step_multi(C.byref(desc), C.byref(m), C.byref(s), _ref(a), _ref(kd), _ref(sm), _ref(dr), _ref(sc), ea, eas,
+                                                 b1, b2, eps, wd, int(steps[r0][k]), st), "msig_sc_train_step_multi")
             if w is not None:                  # EMA: one launch over the same folds, each at its own coefficient
                 for j in range(nr):
                     w.coef[j] = wc[r0 + j][k]
@@ -438,43 +415,35 @@ class LockstepTrainer:
         if aug is not None or mix is not None:
             for ld, ns in zip(loaders, n_steps):
                 ld.aug_step += ns
-        if advs is not None:               # the epoch's statistics: one more small read-back, only with the adversary on
-            st3 = arena.adversary_stats().cpu().numpy()
+        # the epoch's statistics of each term that is on: one more small read-back per term
+        stats = {t: (arena.dro_stats() if t == "dro" else arena.side_stats(t)).cpu().numpy() for t in terms}
+        if advs is not None:
             for f, a, ns, lams in zip(act, advs, n_steps, dl):
                 a.step += ns
                 a.last_lambda = lams[-1] if lams else a.last_lambda
-                self.dom_stats[f] = a.epoch_summary(st3[f])
-        if self.kd_cfg is not None:        # likewise, only for a batch of students
-            st3 = arena.distill_stats().cpu().numpy()
+                self.dom_stats[f] = a.epoch_summary(stats["adversary"][f])
+        if self.kd_cfg is not None:
             for f, t in zip(act, trs):
-                self.kd_stats[f] = t.distill.epoch_summary(st3[f])
-        if self.dro_cfg is not None:       # likewise, only with group-DRO on: every fold's statistics and weights in one read-back
-            sq = arena.dro_stats().cpu().numpy()
-            self.dro_stats = {f: (sq[f, :L.DRO_STATS], sq[f, L.DRO_STATS:]) for f in act}
-        if self.sc_cfg is not None:        # likewise, only with the supervised contrastive term on
-            st5 = arena.sc_stats().cpu().numpy()
-            self.sc_stats = {f: SC.SupCon.epoch_summary(st5[f]) for f in act}
-        if self.sam_cfg is not None:       # the same sync: the loss sums, the SAM statistics and (with the clip) the gradient norms
-            parts = [self.acc[:, :1], arena.across("sam", 0, torch.float64, L.SAM_NSTAT)]
-            if self.clip:
-                parts.append(arena.across("gc", 0, torch.float64, L.GC_NSTAT))
-            both = torch.cat(parts, dim=1).cpu().numpy()
+                self.kd_stats[f] = t.distill.epoch_summary(stats["distill"][f])
+        if self.dro_cfg is not None:       # every fold's statistics and weights
+            self.dro_stats = {f: (stats["dro"][f, :L.DRO_STATS], stats["dro"][f, L.DRO_STATS:]) for f in act}
+        if self.sc_cfg is not None:
+            self.sc_stats = {f: SC.SupCon.epoch_summary(stats["supcon"][f]) for f in act}
+        # the epoch's only other sync: the loss sums, with the SAM statistics and the folds' gradient-norm statistics when they are on
+        parts = [self.acc[:, :1]]
+        if self.sam_cfg is not None:
+            parts.append(arena.across("sam", 0, torch.float64, L.SAM_NSTAT))
+        if self.clip:
+            parts.append(arena.across("gc", 0, torch.float64, L.GC_NSTAT))
+        both = (torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]).cpu().numpy()
+        if self.sam_cfg is not None:
             self.sam_stats = {f: SAM.summary(both[f, 1:1 + L.SAM_NSTAT].tolist(), ns) for f, ns in zip(act, n_steps)}
-            if self.clip:
-                st4 = both[:, 1 + L.SAM_NSTAT:]
-                self.grad_stats = {f: grad_norm_summary(dict(sum=float(st4[f, L.GC_SUM]), max=float(st4[f, L.GC_MAX]),
-                                                             clipped=int(st4[f, L.GC_CLIPPED])), ns)
-                                   for f, ns in zip(act, n_steps) if self.trainers[f].max_grad_norm is not None}
-            return both[:, 0]
-        if not self.clip:
-            return self.acc[:, 0].cpu().numpy()               # the epoch's only sync
-        # the same sync: the loss sums and the folds' gradient-norm statistics in one read-back
-        both = torch.cat([self.acc[:, :1], arena.across("gc", 0, torch.float64, L.GC_NSTAT)], dim=1).cpu().numpy()
-        sums, st4 = both[:, 0], both[:, 1:]
-        self.grad_stats = {f: grad_norm_summary(dict(sum=float(st4[f, L.GC_SUM]), max=float(st4[f, L.GC_MAX]),
-                                                     clipped=int(st4[f, L.GC_CLIPPED])), ns)
-                           for f, ns in zip(act, n_steps) if self.trainers[f].max_grad_norm is not None}
-        return sums
+        if self.clip:
+            st4 = both[:, -L.GC_NSTAT:]
+            self.grad_stats = {f: grad_norm_summary(dict(sum=float(st4[f, L.GC_SUM]), max=float(st4[f, L.GC_MAX]),
+                                                         clipped=int(st4[f, L.GC_CLIPPED])), ns)
+                               for f, ns in zip(act, n_steps) if self.trainers[f].max_grad_norm is not None}
+        return both[:, 0]
 
     def _evaluate(self, active, which, shadow=False):
         """Validation pass of every active fold (loader index `which`): per fold (loss, acc, f1), in the order of `active`.  shadow:

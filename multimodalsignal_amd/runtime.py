@@ -5,14 +5,11 @@ buffers, the BatchNorm buffers and a cache of workspaces, builds the
 `msig_batch` descriptor for every call and launches on torch's current HIP
 stream.  It holds no arithmetic of its own.
 
-The host never chooses among entry points: every train step is msig_da_train_step[_multi], every forward msig_st_forward[_multi],
-the widest of each form (a student's step, include/msig_kd.h, is msig_kd_train_step[_multi]).  The headers make that bit-safe — a
-NULL msig_da, smoothing 0 with every lam 1, a NULL clip, a NULL class_weight each give the narrower call with its launches, `kind`
-selects the model — and tests/test_step_dispatch_gpu.py pins it.  A sharpness-aware step (include/msig_sam.h) is
-msig_sam_train_step[_multi], whatever else is on; without `sam` the calls are exactly the ones above.  A group-DRO step
-(include/msig_dro.h) is msig_dro_train_step[_multi], whatever else is on — `sam` included; without `dro` the calls are exactly those.
-A step with the supervised contrastive term (include/msig_sc.h) is msig_sc_train_step[_multi], whatever else is on — `sam` and `dro`
-included; without `supcon` the calls are exactly those.
+The host never chooses among entry points: every train step is msig_sc_train_step[_multi], every forward msig_st_forward[_multi],
+the widest of each form, with NULL for every optional term that is off.  The headers make that bit-safe — a NULL
+msig_da, msig_kd, msig_sam, msig_dro or msig_sc, smoothing 0 with every lam 1, a NULL clip, a NULL class_weight each give the
+narrower call with its launches, `kind` selects the model — and tests/test_step_dispatch_gpu.py pins it, term by term, against the
+narrower entry points called directly.  A new term widens the widest call; it adds no branch here.
 """
 from __future__ import annotations
 
@@ -23,6 +20,11 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib as L
+
+
+def _ref(desc):
+    """byref of a descriptor, or None (a NULL pointer) for a term that is off."""
+    return None if desc is None else C.byref(desc)
 
 
 def _require_gpu(t: torch.Tensor, what: str):
@@ -375,8 +377,7 @@ class Engine:
 
     def loss_and_grad_stats(self):
         """(loss_acc as a list, grad_stats()) in ONE device-to-host copy: what a trainer reads at the end of a clipped epoch."""
-        v = torch.cat([self.loss_acc, self.ensure_gc_state()[:L.GC_NSTAT]]).cpu().tolist()
-        return v[:2], self._stats(v[2:])
+        return self.epoch_stats(grad=True)[:2]
 
     # ---- weight averaging (include/msig_wa.h, DESIGN.md §22) ------------------------------------------------------------------
     def ensure_shadow(self) -> torch.Tensor:
@@ -437,23 +438,24 @@ class Engine:
         distill: a distill.Distillation bound to this device (include/msig_kd.h): the head runs unfused and one more
         launch blends the gradient of the tempered KL term against the teacher rows — read by batch_index, or one per row — into
         the logits' gradient; the reported loss stays the criterion's, the term's own statistics go to distill.stats.  None, or
-        alpha = 0, is the call without it, bit for bit; the call is then msig_kd_train_step.
+        alpha = 0, is the step without it, bit for bit.
         sam: a sam.Sam (include/msig_sam.h): the step runs twice over the batch — gradient at w, perturbation to
         w + e, gradient there with the same dropout masks, restore, Adam at w with the second gradient; `grads` holds that second
         gradient, region('LOSS') / loss_acc / the BatchNorm state are the first pass's, sam_stats() the norms and the sharpness.
-        The call is msig_sam_train_step whatever else is on; rho = 0 is the step without it, bit for bit.  Not with `adversary`
-        (ValueError): two passes would advance the discriminator twice.  None = the calls above, exactly.
+        rho = 0 is the step without it, bit for bit.  Not with `adversary` (ValueError): two passes would advance the discriminator
+        twice.  None = the step without it, exactly.
         dro: a dro.GroupDro bound to this device (include/msig_dro.h): the head runs unfused and one more launch
         moves the group weights dro.q with the groups' losses — groups read by batch_index, or one table entry per row — and
         rescales the logits' gradient so that the step descends sum_g q_g L_g; the reported loss stays the criterion's, the term's
         statistics go to dro.stats.  Under `sam` the weights move once, in the first pass.  Not with mixup (ValueError): a blended
-        row has no group.  The call is msig_dro_train_step whatever else is on; None = the calls above, exactly.
+        row has no group.  None = the step without it, exactly.
         supcon: a supcon.SupCon bound to this device (include/msig_sc.h): two more launches between the head's (the
         adversary's) and the GRU backward add weight x the gradient of the supervised contrastive loss on the step's features to
         the feature gradient — subjects read by batch_index, or one table entry per row, in cross-subject mode; the head stays fused
         where it was, the reported loss stays the criterion's, the term's statistics go to supcon.stats.  Under `sam` it runs in both
         passes.  weight = 0 measures and leaves the step its bits.  Not with mixup, not above 2048 windows (ValueError before any
-        launch).  The call is msig_sc_train_step whatever else is on; None = the calls above, exactly."""
+        launch).  None = the step without it, exactly.
+        Whatever is on, the step is ONE library call, msig_sc_train_step, with NULL for each term that is off (module docstring)."""
         cw, max_norm, smooth, lam = self._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
         if supcon is not None:
             if lam != 1.0:
@@ -480,52 +482,29 @@ class Engine:
                     raise ValueError(f"batch_index must be a contiguous int64 ({x.shape[0]},) tensor, got {batch_index.dtype} {tuple(batch_index.shape)}")
         self.ensure_adam_state()
         b = self._batch(x, labels, True, dropout_p, seed, step)
-        a = None
+        # the descriptors of the terms that are on, each built once; the library reads them during the call, never after it
+        idx = None if batch_index is None else batch_index.data_ptr()
+        a = k = sd = dd = cd = None
         if adversary is not None:
             adversary.last_lambda = adversary.next_lambda()
-            a = C.byref(adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1],
-                                             idx=None if batch_index is None else batch_index.data_ptr(), betas=betas, eps=eps, weight_decay=weight_decay))
+            a = adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1], idx=idx, betas=betas, eps=eps,
+                                     weight_decay=weight_decay)
         if distill is not None:
             if distill.q is None or distill.q.shape[1] != self.K or not distill.q.is_cuda or not distill.stats.is_cuda:
                 raise ValueError(f"distill needs a (positions, {self.K}) teacher table bound to {self.device}: set_teacher, then bind")
             if batch_index is None and distill.q.shape[0] < x.shape[0]:
                 raise ValueError(f"a teacher table read by row needs {x.shape[0]} rows, got {distill.q.shape[0]}")
-            k = distill.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
-        else:
-            k = None
-        if supcon is not None:
-            sd = None
-            if sam is not None:
-                state = self.ensure_sam_state()
-                sd = C.byref(sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8))
-            dd = None if dro is None else C.byref(dro.descriptor(idx=None if batch_index is None else batch_index.data_ptr()))
-            cd = supcon.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
-            L.check(L.lib().msig_sc_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, None if k is None else C.byref(k), sd,
-                                               dd, C.byref(cd), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps,
-                                               weight_decay, step, self._stream()), "msig_sc_train_step")
-        elif dro is not None:
-            sd = None
-            if sam is not None:
-                state = self.ensure_sam_state()
-                sd = C.byref(sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8))
-            dd = dro.descriptor(idx=None if batch_index is None else batch_index.data_ptr())
-            L.check(L.lib().msig_dro_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, None if k is None else C.byref(k), sd,
-                                                C.byref(dd), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps,
-                                                weight_decay, step, self._stream()), "msig_dro_train_step")
-        elif sam is not None:
+            k = distill.descriptor(idx=idx)
+        if sam is not None:
             state = self.ensure_sam_state()
             sd = sam.descriptor(self.kind, state.data_ptr(), state.numel() * 8)
-            L.check(L.lib().msig_sam_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), None if k is None else C.byref(k),
-                                                C.byref(sd), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps,
-                                                weight_decay, step, self._stream()), "msig_sam_train_step")
-        elif k is not None:
-            L.check(L.lib().msig_kd_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, C.byref(k), self.exp_avg.data_ptr(),
-                                               self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
-                    "msig_kd_train_step")
-        else:
-            L.check(L.lib().msig_da_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), a, self.exp_avg.data_ptr(),
-                                               self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, self._stream()),
-                    "msig_da_train_step")
+        if dro is not None:
+            dd = dro.descriptor(idx=idx)
+        if supcon is not None:
+            cd = supcon.descriptor(idx=idx)
+        L.check(L.lib().msig_sc_train_step(C.byref(b), C.byref(self._st(cw, max_norm, smooth, lam)), _ref(a), _ref(k), _ref(sd), _ref(dd), _ref(cd),
+                                           self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step,
+                                           self._stream()), "msig_sc_train_step")
         if adversary is not None:
             adversary.step += 1
         if adversary is not None or distill is not None or dro is not None or supcon is not None:
@@ -717,19 +696,25 @@ def make_batch(B: int, C_: int, T: int, K: int, x: int, params: int, bn_state: i
     return b
 
 
+def arena_layout(regions):
+    """({name: (offset, nbytes)}, stride) of an arena that holds `regions`, an ordered (name, nbytes[, ...]) list, each at a
+    256-byte-aligned offset.  Allocates nothing: tests/test_arena_layout_host.py pins the numbers."""
+    off, at = {}, 0
+    for name, nbytes, *_ in regions:
+        off[name] = (at, nbytes)
+        at += (nbytes + 255) // 256 * 256
+    return off, at
+
+
 class Arenas:
     """`n` identical arenas, `stride` bytes apart, in one zeroed allocation `mem` (n, stride): the regions of `regions`, an ordered
-    (name, nbytes) list, at the same 256-byte-aligned offsets `off[name] = (offset, nbytes)` in each — which is all a *_multi call
-    needs to run the same work on several arenas in one set of launches."""
+    (name, nbytes) list, at the same 256-byte-aligned offsets `off[name] = (offset, nbytes)` in each (`arena_layout`) — which is all a
+    *_multi call needs to run the same work on several arenas in one set of launches."""
     form_folds = 1          # msig_multi.form_folds of multi(): the GRU backward form of ONE stand-alone fold (FoldArena.multi)
 
     def __init__(self, n: int, device, regions):
         self.n, self.device = int(n), torch.device(device)
-        self.off, at = {}, 0
-        for name, nbytes in regions:
-            self.off[name] = (at, nbytes)
-            at += (nbytes + 255) // 256 * 256
-        self.stride = at
+        self.off, self.stride = arena_layout(regions)
         self.mem = torch.zeros((self.n, self.stride), dtype=torch.uint8, device=self.device)
 
     def view(self, slot: int, name: str, dtype=torch.uint8) -> torch.Tensor:
@@ -778,24 +763,16 @@ class FoldArena(Arenas):
         `kind`: the model kind of every fold (Engine); it sizes the arenas from its layout.  A fold batch is uniform in kind too.
         `grad_clip`: the arenas also hold a "gc" region, each fold's clip state (include/msig_gc.h), after every other region —
         without it the arenas and their stride are what they are without this argument.
-        `adversary` = (S, store positions): every fold also gets the buffers of a subject discriminator of S domains (include/
-        msig_da.h) — parameters, both Adam moments, statistics and an int32 domain table — in a memory block of their own,
-        `da_stride` bytes apart (`adversary_storage`); the model arenas and their stride stay what they are without it.
+        `adversary` = (S, store positions), `distill` = store positions, `dro` = (G, store positions), `supcon` = store positions:
+        every fold also gets the buffers of that optional step term — `side_regions` lists them — in a memory block of the term's
+        own, an `Arenas` in `side[term]` with its own stride (`side_storage`, `side_stats`); the model arenas and their stride stay
+        what they are without it.
         `averaging`: the arenas also hold every fold's weight-averaging shadow (include/msig_wa.h) — "avg_params", "avg_bn_state",
         "avg_bn_count" — after every other region, "gc" included: INSIDE the arenas, at the arena stride, because that is the only
         place the *_multi forward can read an averaged model from (`batch(..., shadow=True)`).  Without it the arenas and their
         stride are what they are without this argument.
-        `distill` = store positions: every fold also gets a distillation teacher table of positions x K float32 and three float64
-        statistics (include/msig_kd.h) in a memory block of their own, `kd_stride` bytes apart (`distill_storage`), as the
-        adversary's buffers are owned; the model arenas and their stride stay what they are without it.
         `sam`: the arenas also hold a "sam" region, each fold's SAM state (include/msig_sam.h), after every other region, the shadow
-        included — without it the arenas and their stride are what they are without this argument.
-        `dro` = (G, store positions): every fold also gets the buffers of a group-DRO term of G groups (include/msig_dro.h) — the
-        weights q, the statistics and an int32 group table — in a memory block of their own, `dro_stride` bytes apart
-        (`dro_storage`), as the adversary's buffers are owned; the model arenas and their stride stay what they are without it.
-        `supcon` = store positions: every fold also gets the buffers of a supervised contrastive term (include/msig_sc.h) — the
-        statistics, an int32 subject table and the scratch of a training batch — in a memory block of their own, `sc_stride` bytes
-        apart (`sc_storage`), likewise; the model arenas and their stride stay what they are without it."""
+        included — without it the arenas and their stride are what they are without this argument."""
         if not (1 <= n <= L.MAX_FOLDS):
             raise ValueError(f"1..{L.MAX_FOLDS} folds per arena set")
         if (gru_hidden, gru_layers) not in ((64, 2), (32, 1)):
@@ -815,49 +792,67 @@ class FoldArena(Arenas):
         self.adaptive_forms = bool(adaptive_forms)
         self.form_folds = 0 if self.adaptive_forms else 1
         self.n_flat = L.param_layout(in_channels, num_classes, kind)[-1]
-        self.ws_bytes = self.workspace_bytes(train_batch, eval_batch, in_channels, T, num_classes)
-        # "cw": the fold's class-weight vector (include/msig_cw.h msig_cw_*_multi), written when a fold enters (set_class_weight)
-        sizes = [("params", self.n_flat * 4), ("grads", self.n_flat * 4), ("exp_avg", self.n_flat * 4), ("exp_avg_sq", self.n_flat * 4),
-                 ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16), ("acc", 16), ("x", self.max_batch * in_channels * T * 4), ("y", self.max_batch * 8),
-                 ("ws", self.ws_bytes), ("cw", num_classes * 4)]
-        self.grad_clip = bool(grad_clip)
-        if self.grad_clip:
-            sizes.append(("gc", L.gc_state_bytes(in_channels, num_classes, kind)))
-        self.averaging = bool(averaging)
-        if self.averaging:
-            sizes += [("avg_params", self.n_flat * 4), ("avg_bn_state", L.BN_STATE_FLOATS * 4), ("avg_bn_count", 16)]
-        self.sam_on = bool(sam)
-        if self.sam_on:
-            sizes.append(("sam", L.sam_state_bytes(in_channels, num_classes, kind)))
+        self.grad_clip, self.averaging, self.sam_on = bool(grad_clip), bool(averaging), bool(sam)
         self.max_norm = [float("inf")] * n              # per arena: max_norm of the fold in it (set_max_norm); inf = measured, not clipped
-        super().__init__(n, device, sizes)
-        self.da_off, self.da_stride, self.da_mem = {}, 0, None
+        side = self.side_regions(num_classes, train_batch, adversary, distill, dro, supcon)
+        super().__init__(n, device, self.model_regions(in_channels, num_classes, T, train_batch, eval_batch, kind, self.grad_clip, self.averaging,
+                                                       self.sam_on))
+        self.ws_bytes = self.off["ws"][1]
+        # the optional step terms: {term: (its memory block, `n` rows of its own stride; {region: dtype})} for the terms that are on
+        self.side = {term: (Arenas(n, device, regs), {name: dt for name, _, dt in regs}) for term, regs in side.items()}
+        self.dro_G = None if dro is None else int(dro[0])
+
+    @classmethod
+    def model_regions(cls, in_channels: int, num_classes: int, T: int, train_batch: int, eval_batch: int = 0, kind: str = "cnn_gru_attention",
+                      grad_clip: bool = False, averaging: bool = False, sam: bool = False) -> list:
+        """The ordered (name, nbytes) regions of one model arena (allocates nothing; `arena_layout` places them)."""
+        n_flat = L.param_layout(in_channels, num_classes, kind)[-1]
+        max_batch = max(int(train_batch), int(eval_batch) or int(train_batch))
+        # "cw": the fold's class-weight vector (include/msig_cw.h msig_cw_*_multi), written when a fold enters (set_class_weight)
+        sizes = [("params", n_flat * 4), ("grads", n_flat * 4), ("exp_avg", n_flat * 4), ("exp_avg_sq", n_flat * 4),
+                 ("bn_state", L.BN_STATE_FLOATS * 4), ("bn_count", 16), ("acc", 16), ("x", max_batch * in_channels * T * 4), ("y", max_batch * 8),
+                 ("ws", cls.workspace_bytes(train_batch, eval_batch, in_channels, T, num_classes)), ("cw", num_classes * 4)]
+        if grad_clip:
+            sizes.append(("gc", L.gc_state_bytes(in_channels, num_classes, kind)))
+        if averaging:
+            sizes += [("avg_params", n_flat * 4), ("avg_bn_state", L.BN_STATE_FLOATS * 4), ("avg_bn_count", 16)]
+        if sam:
+            sizes.append(("sam", L.sam_state_bytes(in_channels, num_classes, kind)))
+        return sizes
+
+    # constructor argument of each optional step term, as the "built without" error names it
+    SIDE_ARGS = {"adversary": "adversary=(S, positions)", "distill": "distill=positions", "dro": "dro=(G, positions)", "supcon": "supcon=positions"}
+
+    @staticmethod
+    def side_regions(num_classes: int, train_batch: int, adversary=None, distill=None, dro=None, supcon=None) -> dict:
+        """{term: ordered (name, nbytes, dtype) regions of one fold's row of the term's block} for the terms that are on, from the
+        constructor's arguments (allocates nothing; `arena_layout` places them).  "stats" is every term's float64 statistics.
+        adversary (include/msig_da.h): the discriminator's parameters, both Adam moments and an int32 domain table; distill
+        (include/msig_kd.h): a teacher table of positions x K; dro (include/msig_dro.h): the weights q and an int32 group table;
+        supcon (include/msig_sc.h): an int32 subject table and the scratch of a training batch."""
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        side = {}
         if adversary is not None:
             S, positions = int(adversary[0]), int(adversary[1])
             nf = L.da_param_floats(S)
-            da = Arenas(n, device, (("params", nf * 4), ("exp_avg", nf * 4), ("exp_avg_sq", nf * 4), ("stats", 24), ("dom", positions * 4)))
-            self.da_off, self.da_stride, self.da_mem = da.off, da.stride, da.mem
-        self.kd_off, self.kd_stride, self.kd_mem = {}, 0, None
+            side["adversary"] = (("params", nf * 4, f32), ("exp_avg", nf * 4, f32), ("exp_avg_sq", nf * 4, f32), ("stats", 24, f64),
+                                 ("dom", positions * 4, i32))
         if distill is not None:
             if int(distill) < 1:
                 raise ValueError(f"distill takes the number of store positions (>= 1), got {distill!r}")
-            kd = Arenas(n, device, (("stats", 24), ("q", int(distill) * num_classes * 4)))
-            self.kd_off, self.kd_stride, self.kd_mem = kd.off, kd.stride, kd.mem
-        self.dro_off, self.dro_stride, self.dro_mem, self.dro_G = {}, 0, None, None
+            side["distill"] = (("stats", 24, f64), ("q", int(distill) * num_classes * 4, f32))
         if dro is not None:
             G, positions = int(dro[0]), int(dro[1])
             if not 1 <= G <= L.DRO_MAX_GROUPS or positions < 1:
                 raise ValueError(f"dro takes (groups in 1..{L.DRO_MAX_GROUPS}, store positions >= 1), got {dro!r}")
-            dr = Arenas(n, device, (("q", L.DRO_MAX_GROUPS * 4), ("stats", L.DRO_STATS * 8), ("grp", positions * 4)))
-            self.dro_off, self.dro_stride, self.dro_mem, self.dro_G = dr.off, dr.stride, dr.mem, G
-        self.sc_off, self.sc_stride, self.sc_mem = {}, 0, None
+            side["dro"] = (("q", L.DRO_MAX_GROUPS * 4, f32), ("stats", L.DRO_STATS * 8, f64), ("grp", positions * 4, i32))
         if supcon is not None:
             if int(supcon) < 1 or int(train_batch) > L.SC_MAX_BATCH:
                 raise ValueError(f"supcon takes the number of store positions (>= 1) and training batches of at most {L.SC_MAX_BATCH} "
                                  f"windows, got {supcon!r} and {train_batch}")
-            sc = Arenas(n, device, (("stats", L.SC_STATS * 8), ("grp", int(supcon) * 4),
-                                    ("scratch", int(L.lib().msig_sc_scratch_bytes(int(train_batch))))))
-            self.sc_off, self.sc_stride, self.sc_mem = sc.off, sc.stride, sc.mem
+            side["supcon"] = (("stats", L.SC_STATS * 8, f64), ("grp", int(supcon) * 4, i32),
+                              ("scratch", int(L.lib().msig_sc_scratch_bytes(int(train_batch))), torch.uint8))
+        return side
 
     @staticmethod
     def workspace_bytes(train_batch: int, eval_batch: int, in_channels: int, T: int, num_classes: int) -> int:
@@ -884,111 +879,71 @@ class FoldArena(Arenas):
             return EmbeddedEngine(self.C, self.K, self.device, self.gru_hidden, storage=st, kind=self.kind)
         return Engine(self.C, self.K, self.device, storage=st, kind=self.kind)
 
-    def adversary_storage(self, slot: int) -> dict:
-        """The adversary buffers of the fold in arena `slot` (adversary.SubjectAdversary.bind): typed views of its `da_mem` row."""
-        if self.da_mem is None:
-            raise RuntimeError("this FoldArena was built without adversary=(S, positions): it has no adversary buffers")
-        dt = {"stats": torch.float64, "dom": torch.int32}
-        return {name: self.da_mem[slot, o:o + nb].view(dt.get(name, torch.float32)) for name, (o, nb) in self.da_off.items()}
+    # ---- the optional step terms' side blocks: one table (`side`), one set of accessors -----------------------------------------------
+    def _side(self, term: str) -> Arenas:
+        if term not in self.side:
+            raise RuntimeError(f"this FoldArena was built without {self.SIDE_ARGS[term]}: it has no {term} buffers")
+        return self.side[term][0]
 
-    def da_ptr(self, name: str) -> int:
-        return self.da_mem.data_ptr() + self.da_off[name][0]            # fold slot 0's adversary buffer
+    def side_storage(self, term: str, slot: int) -> dict:
+        """The buffers of `term` ("adversary", "distill", "dro", "supcon") of the fold in arena `slot`, what the term's object binds to
+        (adversary.SubjectAdversary.bind, distill.Distillation.bind, dro.GroupDro.bind, supcon.SupCon.bind): typed views of its row."""
+        blk = self._side(term)
+        return {name: blk.view(slot, name, dt) for name, dt in self.side[term][1].items()}
+
+    def side_stats(self, term: str) -> torch.Tensor:
+        """(n, statistics) float64 strided view of every fold's statistics of `term`."""
+        blk = self._side(term)
+        return blk.across("stats", 0, torch.float64, blk.off["stats"][1] // 8)
+
+    def zero_side_stats(self, term: str, slots) -> None:
+        self.side_stats(term).index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
 
     def da(self, slots, S: int, lambdas, lrs, steps, betas, eps, weight_decay) -> L.Da:
-        """msig_da of a launch over `slots` (include/msig_da.h): fold slot 0's adversary buffers, `da_stride` apart, and every
+        """msig_da of a launch over `slots` (include/msig_da.h): fold slot 0's adversary buffers, the block's stride apart, and every
         fold's reversal weight, learning rate and step count.  idx / idx_row_stride are the launch's to fill in."""
+        blk = self._side("adversary")
         a = L.Da()
         a.S, a.weight_decay, a.beta1, a.beta2, a.eps = int(S), weight_decay, betas[0], betas[1], eps
-        a.dom, a.params, a.exp_avg, a.exp_avg_sq = self.da_ptr("dom"), self.da_ptr("params"), self.da_ptr("exp_avg"), self.da_ptr("exp_avg_sq")
-        a.stats, a.stride_bytes = self.da_ptr("stats"), self.da_stride
+        a.dom, a.params, a.exp_avg, a.exp_avg_sq = blk.ptr("dom"), blk.ptr("params"), blk.ptr("exp_avg"), blk.ptr("exp_avg_sq")
+        a.stats, a.stride_bytes = blk.ptr("stats"), blk.stride
         for i in range(len(slots)):
             getattr(a, "lambda")[i], a.lr[i], a.step[i] = float(lambdas[i]), float(lrs[i]), int(steps[i])
         return a
 
-    def adversary_stats(self) -> torch.Tensor:
-        """(n, 3) float64 strided view of every fold's adversary statistics."""
-        o = self.da_off["stats"][0] // 8
-        return self.da_mem.view(torch.float64)[:, o:o + 3]
-
-    def distill_storage(self, slot: int) -> dict:
-        """The distillation buffers of the fold in arena `slot` (distill.Distillation.bind): typed views of its `kd_mem` row."""
-        if self.kd_mem is None:
-            raise RuntimeError("this FoldArena was built without distill=positions: it has no teacher tables")
-        dt = {"stats": torch.float64, "q": torch.float32}
-        return {name: self.kd_mem[slot, o:o + nb].view(dt[name]) for name, (o, nb) in self.kd_off.items()}
-
     def kd(self, alpha: float, temperature: float) -> L.Kd:
-        """msig_kd of a launch (include/msig_kd.h): fold slot 0's teacher table and statistics, `kd_stride` apart.  idx /
+        """msig_kd of a launch (include/msig_kd.h): fold slot 0's teacher table and statistics, the block's stride apart.  idx /
         idx_row_stride are the launch's to fill in.  Checked on the host: ValueError before anything is launched."""
-        if self.kd_mem is None:
-            raise RuntimeError("this FoldArena was built without distill=positions: it has no teacher tables")
+        blk = self._side("distill")
         k = L.Kd()
         k.alpha, k.temperature = L.check_distill(alpha, temperature)
-        base = self.kd_mem.data_ptr()
-        k.q, k.stats, k.stride_bytes = base + self.kd_off["q"][0], base + self.kd_off["stats"][0], self.kd_stride
+        k.q, k.stats, k.stride_bytes = blk.ptr("q"), blk.ptr("stats"), blk.stride
         return k
 
-    def distill_stats(self) -> torch.Tensor:
-        """(n, 3) float64 strided view of every fold's distillation statistics."""
-        o = self.kd_off["stats"][0] // 8
-        return self.kd_mem.view(torch.float64)[:, o:o + 3]
-
-    def dro_storage(self, slot: int) -> dict:
-        """The group-DRO buffers of the fold in arena `slot` (dro.GroupDro.bind): typed views of its `dro_mem` row."""
-        if self.dro_mem is None:
-            raise RuntimeError("this FoldArena was built without dro=(G, positions): it has no group-DRO buffers")
-        dt = {"q": torch.float32, "stats": torch.float64, "grp": torch.int32}
-        return {name: self.dro_mem[slot, o:o + nb].view(dt[name]) for name, (o, nb) in self.dro_off.items()}
-
     def dro(self, eta: float, frozen: bool = False) -> L.Dro:
-        """msig_dro of a launch (include/msig_dro.h): fold slot 0's q, group table and statistics, `dro_stride` apart.  idx /
+        """msig_dro of a launch (include/msig_dro.h): fold slot 0's q, group table and statistics, the block's stride apart.  idx /
         idx_row_stride are the launch's to fill in."""
-        if self.dro_mem is None:
-            raise RuntimeError("this FoldArena was built without dro=(G, positions): it has no group-DRO buffers")
+        blk = self._side("dro")
         d = L.Dro()
         d.G, d.eta, d.frozen = self.dro_G, float(eta), int(bool(frozen))
-        base = self.dro_mem.data_ptr()
-        d.q, d.grp, d.stats, d.stride_bytes = base + self.dro_off["q"][0], base + self.dro_off["grp"][0], base + self.dro_off["stats"][0], self.dro_stride
+        d.q, d.grp, d.stats, d.stride_bytes = blk.ptr("q"), blk.ptr("grp"), blk.ptr("stats"), blk.stride
         return d
 
     def dro_stats(self) -> torch.Tensor:
         """(n, DRO_STATS + DRO_MAX_GROUPS) float64 copy of every fold's group-DRO statistics followed by its q (widened)."""
-        o, oq = self.dro_off["stats"][0] // 8, self.dro_off["q"][0] // 4
-        return torch.cat([self.dro_mem.view(torch.float64)[:, o:o + L.DRO_STATS],
-                          self.dro_mem.view(torch.float32)[:, oq:oq + L.DRO_MAX_GROUPS].to(torch.float64)], dim=1)
-
-    def zero_dro_stats(self, slots) -> None:
-        o = self.dro_off["stats"][0] // 8
-        self.dro_mem.view(torch.float64)[:, o:o + L.DRO_STATS].index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
-
-    def sc_storage(self, slot: int) -> dict:
-        """The supervised contrastive term's buffers of the fold in arena `slot` (supcon.SupCon.bind): typed views of its `sc_mem` row."""
-        if self.sc_mem is None:
-            raise RuntimeError("this FoldArena was built without supcon=positions: it has no supcon buffers")
-        dt = {"stats": torch.float64, "grp": torch.int32, "scratch": torch.uint8}
-        return {name: self.sc_mem[slot, o:o + nb].view(dt[name]) for name, (o, nb) in self.sc_off.items()}
+        return torch.cat([self.side_stats("dro"), self._side("dro").across("q", 0, torch.float32, L.DRO_MAX_GROUPS).to(torch.float64)], dim=1)
 
     def sc(self, positives: str, tau: float, weights) -> L.Sc:
-        """msig_sc of a launch (include/msig_sc.h): fold slot 0's subject table, scratch and statistics, `sc_stride` apart, and the
-        weight of every fold of the launch.  idx / idx_row_stride are the launch's to fill in (cross-subject mode)."""
-        if self.sc_mem is None:
-            raise RuntimeError("this FoldArena was built without supcon=positions: it has no supcon buffers")
+        """msig_sc of a launch (include/msig_sc.h): fold slot 0's subject table, scratch and statistics, the block's stride apart, and
+        the weight of every fold of the launch.  idx / idx_row_stride are the launch's to fill in (cross-subject mode)."""
+        blk = self._side("supcon")
         d = L.Sc()
         d.positives, d.tau = L.SC_POSITIVES[positives], float(tau)
-        base = self.sc_mem.data_ptr()
-        d.grp = base + self.sc_off["grp"][0] if d.positives else None
-        d.scratch, d.stats, d.stride_bytes = base + self.sc_off["scratch"][0], base + self.sc_off["stats"][0], self.sc_stride
+        d.grp = blk.ptr("grp") if d.positives else None
+        d.scratch, d.stats, d.stride_bytes = blk.ptr("scratch"), blk.ptr("stats"), blk.stride
         for i, w in enumerate(weights):
             d.weight[i] = float(w)
         return d
-
-    def sc_stats(self) -> torch.Tensor:
-        """(n, SC_STATS) float64 strided view of every fold's supcon statistics."""
-        o = self.sc_off["stats"][0] // 8
-        return self.sc_mem.view(torch.float64)[:, o:o + L.SC_STATS]
-
-    def zero_sc_stats(self, slots) -> None:
-        self.sc_stats().index_fill_(0, torch.as_tensor(list(slots), dtype=torch.int64, device=self.device), 0.0)
 
     def set_class_weight(self, slot: int, values) -> None:
         """Writes the class-weight vector of the fold in arena `slot` (K values, checked on the host: ValueError before anything is

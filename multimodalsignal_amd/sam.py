@@ -1,8 +1,8 @@
 """Sharpness-aware minimisation (include/msig_sam.h): the host side of a SAM / ASAM train step.
 
 A ``Sam`` is the setting of one run — rho, SAM or ASAM, and ASAM's eta.  The arithmetic is the library's:
-``runtime.Engine.train_step(..., sam=)`` hands it to ``msig_sam_train_step`` with the engine's SAM state, a fold batch to
-``msig_sam_train_step_multi`` (``runtime.FoldArena(..., sam=True)`` owns every fold's state as one more arena region).  Nothing here
+``runtime.Engine.train_step(..., sam=)`` hands it to the one train-step call (``msig_sc_train_step``) as its ``msig_sam`` with the engine's SAM
+state, a fold batch to its ``_multi`` form (``runtime.FoldArena(..., sam=True)`` owns every fold's state as one more arena region).  Nothing here
 is part of a model's ``state_dict``.
 """
 from __future__ import annotations

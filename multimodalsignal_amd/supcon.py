@@ -110,7 +110,7 @@ class SupCon:
 
     def bind(self, device, storage: Optional[dict] = None, max_batch: int = L.SC_MAX_BATCH) -> "SupCon":
         """Moves the buffers to `device` with a scratch for batches of up to `max_batch` rows, or with `storage`
-        (runtime.FoldArena.sc_storage) into one fold's regions of an arena: int32 "grp", uint8 "scratch", float64 "stats"."""
+        (runtime.FoldArena.side_storage("supcon", slot)) into one fold's regions of an arena: int32 "grp", uint8 "scratch", float64 "stats"."""
         if self.cross_subject and self.grp is None:
             raise RuntimeError("cross-subject positives need a subject table: call set_subjects first")
         if storage is None:

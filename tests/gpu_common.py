@@ -270,6 +270,56 @@ def legacy_train_step(e, x, y, lr, weight_decay=0.0, step=1, dropout_p=0.0, seed
     return name
 
 
+def narrow_train_step(e, x, y, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dropout_p=0.0, seed=0, class_weight=None,
+                      max_grad_norm=None, label_smoothing=0.0, mix_lambda=None, adversary=None, batch_index=None, distill=None, sam=None,
+                      dro=None, supcon=None, entry=None):
+    """One fused step of engine `e` through the NARROWEST entry point whose signature has every term given — msig_sc_train_step with
+    `supcon`, else msig_dro_train_step with `dro`, else msig_sam_train_step with `sam`, else msig_kd_train_step with `distill`, else
+    msig_da_train_step — or through `entry`, called directly on the library with the descriptors Engine.train_step builds and with its
+    bookkeeping (the adversary's lambda and step count, EmbeddedEngine's scatter / gather).  Engine.train_step always issues the
+    widest call; this is the other side of the comparisons that hold it to the narrower ones.  Returns the entry point's name."""
+    import ctypes as C
+    from multimodalsignal_amd import _lib as L
+    ref = lambda d: None if d is None else C.byref(d)      # noqa: E731
+    name = entry or ("msig_sc_train_step" if supcon is not None else "msig_dro_train_step" if dro is not None else
+                     "msig_sam_train_step" if sam is not None else "msig_kd_train_step" if distill is not None else "msig_da_train_step")
+    cw, max_norm, smooth, lam = e._checked(class_weight, max_grad_norm, label_smoothing, mix_lambda)
+    if adversary is not None and hasattr(e, "hidden"):
+        adversary.restrict_features(e.hidden)
+    if hasattr(e, "scatter"):
+        e.scatter()
+    e.ensure_adam_state()
+    b = e._batch(x, y, True, dropout_p, seed, step)
+    idx = None if batch_index is None else batch_index.data_ptr()
+    a = k = sd = dd = cd = None
+    if adversary is not None:
+        adversary.last_lambda = adversary.next_lambda()
+        a = adversary.descriptor([adversary.last_lambda], [lr * adversary.lr_mult], [adversary.step + 1], idx=idx, betas=betas, eps=eps,
+                                 weight_decay=weight_decay)
+    if distill is not None:
+        k = distill.descriptor(idx=idx)
+    if sam is not None:
+        state = e.ensure_sam_state()
+        sd = sam.descriptor(e.kind, state.data_ptr(), state.numel() * 8)
+    if dro is not None:
+        dd = dro.descriptor(idx=idx)
+    if supcon is not None:
+        cd = supcon.descriptor(idx=idx)
+    terms = {"msig_da_train_step": (a,), "msig_kd_train_step": (a, k), "msig_sam_train_step": (k, sd), "msig_dro_train_step": (a, k, sd, dd),
+             "msig_sc_train_step": (a, k, sd, dd, cd)}[name]
+    given = [d for d in (a, k, sd, dd, cd) if d is not None]
+    assert all(any(d is t for t in terms) for d in given), f"{name} has no parameter for a term that was given"
+    rc = getattr(L.lib(), name)(C.byref(b), C.byref(e._st(cw, max_norm, smooth, lam)), *[ref(t) for t in terms], e.exp_avg.data_ptr(),
+                                e.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, step, e._stream())
+    L.check(rc, name)
+    if adversary is not None:
+        adversary.step += 1
+    e._keep = e._keep + (batch_index,)
+    if hasattr(e, "gather"):
+        e.gather()
+    return name
+
+
 def legacy_forward(e, x, y=None, training=False, keep_for_backward=False, class_weight=None, dropout_p=0.0, seed=0, step=0):
     """A forward of engine `e` through msig_cg_forward, msig_cw_forward or msig_forward, chosen as legacy_train_step chooses."""
     import ctypes as C

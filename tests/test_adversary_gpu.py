@@ -406,7 +406,7 @@ def test_train_step_multi_equals_the_single_calls_and_fold_zero_the_plain_step()
     for f in range(n):
         adv = SubjectAdversary(S, lam=lam_rev[f], schedule="constant", seed=40 + f)
         adv.set_domains(doms[f])
-        advs.append(adv.bind(DEV, arena.adversary_storage(f)))
+        advs.append(adv.bind(DEV, arena.side_storage("adversary", f)))
         x, y = data[f]
         arena.view(f, "x", torch.float32)[:x.numel()].copy_(x.reshape(-1))
         arena.view(f, "y", torch.int64)[:B].copy_(y)
@@ -457,7 +457,7 @@ def test_embedded_fold_batch_keeps_its_padding_zero_and_equals_the_single_calls(
         adv = SubjectAdversary(S, lam=lam_rev[f], schedule="constant", seed=40 + f)
         adv.set_domains(doms[f])
         adv.restrict_features(32)
-        advs.append(adv.bind(DEV, arena.adversary_storage(f)))
+        advs.append(adv.bind(DEV, arena.side_storage("adversary", f)))
     slots = list(range(n))
     sd = arena.soft(slots, 0.0)
     desc = arena.batch(B, True, 0.5)

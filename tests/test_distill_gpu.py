@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 import kd_reference as R
 from conftest import load_golden_model
-from gpu_common import FIXED_TOL, grad_tol, rel_err, split_named, to_t
+from gpu_common import FIXED_TOL, grad_tol, narrow_train_step, rel_err, split_named, to_t
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.adversary import SubjectAdversary
 from multimodalsignal_amd.distill import Distillation, teacher_table
@@ -394,8 +394,8 @@ def _distill(alpha, table, T=2.0):
 
 @pytest.mark.parametrize("model", [(ATT, 64, 2), (CG, 64, 2), (ATT, 32, 1)], ids=["attention", "cnn_gru", "embedded"])
 def test_null_and_alpha_zero_are_the_plain_step_bit_for_bit(model):
-    """Three steps with eps = 0.1, lam = 0.4, clip and dropout: distill=None (msig_da_train_step), a NULL msig_kd and alpha = 0
-    (msig_kd_train_step) leave the same parameters, gradients, moments, BatchNorm state and loss; alpha = 0.5 does not."""
+    """Three steps with eps = 0.1, lam = 0.4, clip and dropout: msig_da_train_step itself, msig_kd_train_step with a NULL msig_kd
+    and Engine.train_step at alpha = 0 leave the same parameters, gradients, moments, BatchNorm state and loss; alpha = 0.5 does not."""
     kind, hidden, layers = model
     Cc, K, B, T = 3, 2, 21, 512
     _, _, table, idx = _case(B, K, 4)
@@ -417,8 +417,10 @@ def test_null_and_alpha_zero_are_the_plain_step_bit_for_bit(model):
                                                    e.exp_avg_sq.data_ptr(), LR, 0.9, 0.999, 1e-8, 1e-4, s, _stream()), "msig_kd_train_step")
                 if layers == 1:
                     e.gather()
+            elif mode == "plain":                            # msig_da_train_step, called directly (Engine.train_step is msig_sc_train_step)
+                assert narrow_train_step(e, x, y, LR, **kw) == "msig_da_train_step"
             else:
-                e.train_step(x, y, LR, distill=d, batch_index=idx_d if d is not None else None, **kw)
+                e.train_step(x, y, LR, distill=d, batch_index=idx_d, **kw)
         torch.cuda.synchronize()
         engines.append((e, d))
     plain = engines[0][0]
@@ -490,11 +492,11 @@ def test_train_step_multi_equals_the_single_calls(with_adversary):
     for f in range(n):
         d = Distillation(alpha, Tk)
         d.set_teacher(tables[f])
-        kds.append(d.bind(DEV, arena.distill_storage(f)))
+        kds.append(d.bind(DEV, arena.side_storage("distill", f)))
         if with_adversary:
             adv = SubjectAdversary(S, lam=lam_rev[f], schedule="constant", seed=40 + f)
             adv.set_domains(doms[f])
-            advs.append(adv.bind(DEV, arena.adversary_storage(f)))
+            advs.append(adv.bind(DEV, arena.side_storage("adversary", f)))
         x, y = data[f]
         arena.view(f, "x", torch.float32)[:x.numel()].copy_(x.reshape(-1))
         arena.view(f, "y", torch.int64)[:B].copy_(y)
@@ -534,7 +536,7 @@ def test_train_step_multi_equals_the_single_calls(with_adversary):
             for name in ("params", "exp_avg", "exp_avg_sq"):
                 assert torch.equal(_bits(getattr(adv, name)), _bits(getattr(advs[f], name))), (f, name)
             assert torch.equal(adv.stats, advs[f].stats)
-    assert torch.equal(arena.distill_stats().cpu(), torch.stack([d.stats.cpu() for d in kds]))
+    assert torch.equal(arena.side_stats("distill").cpu(), torch.stack([d.stats.cpu() for d in kds]))
 
 
 # ---- 6. a student learns its teacher --------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 import dro_reference as R
 from conftest import load_golden_model
-from gpu_common import FIXED_TOL, grad_tol, rel_err, split_named, to_t
+from gpu_common import FIXED_TOL, grad_tol, narrow_train_step, rel_err, split_named, to_t
 from mc_reference import ulp32, within_store_rounding
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.adversary import SubjectAdversary
@@ -439,8 +439,8 @@ def _same_state(a, b):
 @pytest.mark.parametrize("with_sam", [False, True], ids=["kd", "sam"])
 @pytest.mark.parametrize("model", [(ATT, 64, 2), (CG, 64, 2), (ATT, 32, 1)], ids=["attention", "cnn_gru", "embedded"])
 def test_null_and_one_unit_group_are_the_plain_step_bit_for_bit(model, with_sam):
-    """Three steps with eps = 0.1, clip and dropout: the engine's own call without the option (msig_da_train_step, or
-    msig_sam_train_step with sam), msig_dro_train_step with a NULL msig_dro, and one group with q = [1] leave the same parameters,
+    """Three steps with eps = 0.1, clip and dropout: the narrower entry point without the option called directly (msig_da_train_step,
+    or msig_sam_train_step with sam), msig_dro_train_step with a NULL msig_dro, and one group with q = [1] leave the same parameters,
     gradients, moments, BatchNorm state and losses, and the NULL call makes the same launches; three groups do not."""
     kind, hidden, layers = model
     Cc, K, B, T = 3, 2, 21, 512
@@ -469,6 +469,10 @@ def test_null_and_one_unit_group_are_the_plain_step_bit_for_bit(model, with_sam)
                                                         e.exp_avg_sq.data_ptr(), LR, 0.9, 0.999, 1e-8, 1e-4, s, _stream()), "msig_dro_train_step")
                     if layers == 1:
                         e.gather()
+                elif mode == "plain":                            # the narrower entry point, called directly (Engine.train_step is msig_sc_train_step)
+                    name = narrow_train_step(e, x, y, LR, weight_decay=1e-4, step=s, dropout_p=0.5, seed=7, label_smoothing=0.1, max_grad_norm=1.0,
+                                             sam=sam)
+                    assert name == ("msig_sam_train_step" if with_sam else "msig_da_train_step")
                 else:
                     e.train_step(x, y, LR, weight_decay=1e-4, step=s, dropout_p=0.5, seed=7, label_smoothing=0.1, max_grad_norm=1.0, sam=sam, dro=d)
                 torch.cuda.synchronize()
@@ -547,11 +551,11 @@ def test_train_step_multi_equals_the_single_calls(extra):
     engs = [_engine(Cc, K, seed=10 + f, storage_engine=arena.engine(f)) for f in range(n)]
     dros, advs = [], []
     for f in range(n):
-        dros.append(GroupDro(0.5).set_groups(tables[f], G).bind(DEV, arena.dro_storage(f)))
+        dros.append(GroupDro(0.5).set_groups(tables[f], G).bind(DEV, arena.side_storage("dro", f)))
         if extra == "adversary":
             adv = SubjectAdversary(S, lam=lam_rev[f], schedule="constant", seed=40 + f)
             adv.set_domains(doms[f])
-            advs.append(adv.bind(DEV, arena.adversary_storage(f)))
+            advs.append(adv.bind(DEV, arena.side_storage("adversary", f)))
         arena.set_max_norm(f, 1.0)
     slots = list(range(n))
     desc = arena.batch(B, True, 0.5)
@@ -619,7 +623,7 @@ def test_embedded_fold_batch_keeps_its_padding_zero_and_equals_the_single_calls(
     idx = _dev(rs.randint(0, npos, size=(n, B)).astype(np.int64))
     arena = FoldArena(Cc, K, DEV, n, B, T, gru_hidden=32, gru_layers=1, dro=(G, npos))
     engs = [_engine(Cc, K, 32, 1, seed=10 + f, storage_engine=arena.engine(f)) for f in range(n)]
-    dros = [GroupDro(1.0).set_groups(tables[f], G).bind(DEV, arena.dro_storage(f)) for f in range(n)]
+    dros = [GroupDro(1.0).set_groups(tables[f], G).bind(DEV, arena.side_storage("dro", f)) for f in range(n)]
     slots = list(range(n))
     sd = arena.soft(slots, 0.0)
     desc = arena.batch(B, True, 0.5)

@@ -10,7 +10,7 @@ import torch
 
 import sam_reference as R
 from conftest import load_golden_model
-from gpu_common import FIXED_TOL, GRAD_FLOOR, K_GRAD, grad_tol, rel_err, split_named, to_t
+from gpu_common import FIXED_TOL, GRAD_FLOOR, K_GRAD, grad_tol, narrow_train_step, rel_err, split_named, to_t
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.distill import Distillation
 from multimodalsignal_amd.runtime import EmbeddedEngine, Engine, FoldArena
@@ -323,8 +323,8 @@ def test_sam_steps_match_the_oracle_differentiated_twice(name, kind, layers, ada
 # ---- 4. off = the plain step ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", [(ATT, 64, 2), (CG, 64, 2), (ATT, 32, 1)], ids=["attention", "cnn_gru", "embedded"])
 def test_none_null_and_rho_zero_are_the_plain_step_bit_for_bit(model):
-    """Three steps with eps = 0.1, lam = 0.4, clip and dropout: sam=None (msig_da_train_step), msig_kd_train_step itself, a NULL
-    msig_sam and rho = 0 (msig_sam_train_step) leave the same parameters, gradients, moments, BatchNorm state and losses; rho > 0
+    """Three steps with eps = 0.1, lam = 0.4, clip and dropout: msig_da_train_step and msig_kd_train_step themselves, msig_sam_train_step
+    with a NULL msig_sam and Engine.train_step at rho = 0 leave the same parameters, gradients, moments, BatchNorm state and losses; rho > 0
     does not."""
     kind, hidden, layers = model
     Cc, K, B, T = 3, 2, 16, 256
@@ -347,8 +347,10 @@ def test_none_null_and_rho_zero_are_the_plain_step_bit_for_bit(model):
                     L.check(L.lib().msig_sam_train_step(C.byref(b), sd, None, None, *tail), "msig_sam_train_step")
                 if layers == 1:
                     e.gather()
+            elif mode == "plain":                                # msig_da_train_step, called directly (Engine.train_step is msig_sc_train_step)
+                assert narrow_train_step(e, x, y, LR, **kw) == "msig_da_train_step"
             else:
-                e.train_step(x, y, LR, sam={"plain": None, "zero": Sam(0.0), "on": Sam(0.05)}[mode], **kw)
+                e.train_step(x, y, LR, sam={"zero": Sam(0.0), "on": Sam(0.05)}[mode], **kw)
         torch.cuda.synchronize()
     plain = engines["plain"]
     for mode in ("kd", "null", "zero", "on"):
@@ -441,7 +443,7 @@ def test_train_step_multi_equals_the_single_calls(extras, adaptive):
         if extras:
             d = Distillation(alpha, Tk)
             d.set_teacher(tables[j])
-            kds[f] = d.bind(DEV, arena.distill_storage(f))
+            kds[f] = d.bind(DEV, arena.side_storage("distill", f))
             arena.set_max_norm(f, norms[j])
     m = arena.multi(slots, key_gru=[L.dropout_key(100 + f, msteps[j], 1) for j, f in enumerate(slots)],
                     key_head=[L.dropout_key(100 + f, msteps[j], 2) for j, f in enumerate(slots)], lr=lrs, steps=msteps)

@@ -1,19 +1,26 @@
-"""GPU tier: the property the host's single dispatch rests on.  Engine.train_step always issues msig_da_train_step, Engine.forward
-msig_st_forward, the lockstep trainer msig_da_train_step_multi / msig_st_forward_multi, the loaders msig_st_gather_windows whenever
+"""GPU tier: the property the host's single dispatch rests on.  Engine.train_step always issues msig_sc_train_step, Engine.forward
+msig_st_forward, the lockstep trainer msig_sc_train_step_multi / msig_st_forward_multi, the loaders msig_st_gather_windows whenever
 they augment or mix.  Here the bits of each of those widest calls, with a feature off, are held to the bits of the entry point that
-the feature's header names as its counterpart, called directly on the library.  Every comparison is torch.equal: no tolerance."""
+the feature's header names as its counterpart, called directly on the library; and with ONE optional term on (adversary,
+distillation, SAM, group-DRO) to the bits of the narrowest entry point whose signature has that term — msig_da_, msig_kd_, msig_sam_,
+msig_dro_train_step[_multi] — given the same descriptors.  Every comparison is torch.equal: no tolerance."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-from gpu_common import legacy_forward, legacy_train_step
+from gpu_common import legacy_forward, legacy_train_step, narrow_train_step
 from multimodalsignal_amd import _lib as L
+from multimodalsignal_amd.adversary import SubjectAdversary
 from multimodalsignal_amd.augment import Augment
 from multimodalsignal_amd.dataset import DeviceLoader
+from multimodalsignal_amd.distill import Distillation
+from multimodalsignal_amd.dro import GroupDro
 from multimodalsignal_amd.mixup import Mixup
 from multimodalsignal_amd.runtime import EmbeddedEngine, Engine, FoldArena
+from multimodalsignal_amd.sam import Sam
+from multimodalsignal_amd.supcon import SupCon
 from oracle import cnn_gru_oracle as O
 from test_soft_targets_gpu import AUG_ON, _gather
 
@@ -103,6 +110,68 @@ def test_train_step_has_the_bits_of_the_entry_point_its_header_names(config, B, 
         assert a.gc_state is None
 
 
+S_DOM, G_DRO = 4, 3
+TERM_STATE = {"adversary": ("params", "exp_avg", "exp_avg_sq", "stats"), "distill": ("stats",), "dro": ("q", "stats"), "supcon": ("stats",)}
+NARROWEST = {"adversary": "msig_da_train_step", "distill": "msig_kd_train_step", "sam": "msig_sam_train_step", "dro": "msig_dro_train_step"}
+
+
+def _term(name, rows, seed, storage=None):
+    """A fresh optional step term over `rows` table entries (read by row, or by the store positions 0 .. rows-1), bound to the device or
+    to a fold's side block; the same (name, rows, seed) gives the same initial state."""
+    rs = np.random.RandomState(seed)
+    if name == "adversary":
+        t = SubjectAdversary(S_DOM, lam=0.5, schedule="constant", seed=40 + seed)
+        t.set_domains(rs.randint(-1, S_DOM, size=rows).astype(np.int32))
+    elif name == "distill":
+        q = np.exp(1.5 * rs.randn(rows, K))
+        t = Distillation(0.5, 2.0)
+        t.set_teacher((q / q.sum(axis=1, keepdims=True)).astype(np.float32))
+    elif name == "dro":
+        t = GroupDro(0.5).set_groups((np.arange(rows) % G_DRO).astype(np.int32), G_DRO)
+    elif name == "supcon":
+        t = SupCon(0.5, 0.2, "cross-subject").set_subjects((np.arange(rows) % 3).astype(np.int32))
+        return t.bind(DEV, max_batch=rows) if storage is None else t.bind(DEV, storage)
+    else:
+        return Sam(0.05)
+    return t.bind(DEV) if storage is None else t.bind(DEV, storage)
+
+
+@pytest.mark.parametrize("names", [("adversary",), ("distill",), ("sam",), ("dro",), ("adversary", "distill", "dro", "supcon"),
+                                   ("sam", "distill", "dro", "supcon")], ids="+".join)
+def test_train_step_with_terms_on_has_the_bits_of_the_narrowest_entry_point(names):
+    """Three consecutive steps of Engine.train_step (msig_sc_train_step with NULL for what is off) against a twin engine driven, with
+    the same descriptors, through the narrowest entry point whose signature has the term: msig_da_, msig_kd_ (alpha 0.5), msig_sam_
+    (rho 0.05), msig_dro_train_step; the widest combinations (adversary or SAM + distillation + group-DRO + supcon) against
+    msig_sc_train_step called directly, which guards the argument plumbing.  Dropout 0.5, smoothing 0.1, the clip on.  B = 8: the head
+    fuses wherever the terms allow it.  The adversary, the one term of the four that leaves the head fused, would also run at B = 2064
+    (129 head groups: the separate head and ce_kernel), but MSIG_DA_MAX_BATCH (256, asserted) admits no batch above 2048 windows, so
+    B = 8 is its only row."""
+    assert L.DA_MAX_BATCH <= 2048
+    B = 8
+    x, y = _data(B)
+    a, b = _engine("full"), _engine("full")
+    ta, tb = ({n: _term(n, B, 5) for n in names} for _ in range(2))
+    kw = dict(weight_decay=WD, dropout_p=P, seed=SEED, label_smoothing=0.1, max_grad_norm=0.5)
+    for s in (1, 2, 3):
+        a.train_step(x, y, LR, step=s, **kw, **ta)
+        assert narrow_train_step(b, x, y, LR, step=s, **kw, **tb) == (NARROWEST[names[0]] if len(names) == 1 else "msig_sc_train_step")
+    torch.cuda.synchronize()
+    _assert_same_model(a, b, names)
+    assert torch.equal(_bits(a.grads), _bits(b.grads))
+    assert torch.equal(a.gc_state[:L.GC_NSTAT], b.gc_state[:L.GC_NSTAT]) and a.grad_stats()["last"] > 0
+    if "sam" in names:
+        assert torch.equal(a.sam_state[:L.SAM_NSTAT], b.sam_state[:L.SAM_NSTAT]) and float(a.sam_state[L.SAM_STEPS]) == 3.0
+    else:
+        assert a.sam_state is None and b.sam_state is None
+    for n in names:
+        for field in TERM_STATE.get(n, ()):
+            assert torch.equal(_bits(getattr(ta[n], field)), _bits(getattr(tb[n], field))), (names, n, field)
+        if n != "sam":
+            assert ta[n].stats.any(), (names, n)                           # the term ran: its statistics were written
+    if "adversary" in names:
+        assert ta["adversary"].step == tb["adversary"].step == 3
+
+
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("config,B", CONFIGS)
 def test_eval_forward_has_the_bits_of_the_entry_point_its_header_names(config, B, weighted):
@@ -120,14 +189,19 @@ def test_eval_forward_has_the_bits_of_the_entry_point_its_header_names(config, B
 
 
 # ---- a fold batch --------------------------------------------------------------------------------------------------------------------
-def _arena_run(widest):
+def _arena_run(widest, term=None):
     """Three folds (own weights, own dropout keys) in one FoldArena of batch 8; two steps, each a launch over folds {0, 1, 2} at B = 8
-    and a ragged launch over folds {0, 1} at B = 5.  widest: msig_da_train_step_multi with everything off, built as
-    LockstepTrainer._train_epoch builds it (FoldArena.soft, a NULL msig_da); else msig_train_step_multi."""
+    and a ragged launch over folds {0, 1} at B = 5.  widest: msig_sc_train_step_multi built as LockstepTrainer._train_epoch builds it
+    (FoldArena.soft, NULL for every term that is off, idx rows of an order matrix); else, with everything off, msig_train_step_multi,
+    and with `term` on ("adversary", "distill", "sam", "dro") the narrowest *_multi entry point whose signature has it."""
     n, B = 3, 8
-    arena = FoldArena(CC, K, DEV, n, B, T)
+    arena = FoldArena(CC, K, DEV, n, B, T, adversary=(S_DOM, B) if term == "adversary" else None, distill=B if term == "distill" else None,
+                      sam=term == "sam", dro=(G_DRO, B) if term == "dro" else None)
     for f in range(n):
         _engine("full", seed=10 + f, storage_engine=arena.engine(f))
+        if term in TERM_STATE:
+            _term(term, B, 20 + f, arena.side_storage(term, f))
+    order = torch.arange(B, dtype=torch.int64, device=DEV).repeat(n, 1).contiguous()      # store positions: row r of fold f reads entry r
     lib, st = L.lib(), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
     ea, eas, count = arena.ptr("exp_avg"), arena.ptr("exp_avg_sq"), 0
     for s in (1, 2):
@@ -140,11 +214,25 @@ def _arena_run(widest):
             m = arena.multi(slots, key_gru=[L.dropout_key(100 + f, count, 1) for f in slots],
                             key_head=[L.dropout_key(100 + f, count, 2) for f in slots], lr=[LR] * len(slots), steps=[count] * len(slots))
             desc = arena.batch(b, True, P)
+            sd = arena.soft(slots, 0.0, None, None, None)
+            d = {"adversary": lambda: arena.da(slots, S_DOM, [0.5] * len(slots), [LR] * len(slots), [count] * len(slots), (0.9, 0.999), 1e-8, WD),
+                 "distill": lambda: arena.kd(0.5, 2.0), "sam": lambda: arena.sam(Sam(0.05)), "dro": lambda: arena.dro(0.5), None: lambda: None}[term]()
+            if term in TERM_STATE:
+                d.idx, d.idx_row_stride = order.data_ptr(), B
+            ref, tail = (None if d is None else C.byref(d)), (ea, eas, 0.9, 0.999, 1e-8, WD, count, st)
             if widest:
-                sd = arena.soft(slots, 0.0, None, None, None)
-                rc = lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(sd), None, ea, eas, 0.9, 0.999, 1e-8, WD, count, st)
+                terms = [ref if term == t else None for t in ("adversary", "distill", "sam", "dro", "supcon")]
+                rc = lib.msig_sc_train_step_multi(C.byref(desc), C.byref(m), C.byref(sd), *terms, *tail)
+            elif term is None:
+                rc = lib.msig_train_step_multi(C.byref(desc), C.byref(m), *tail)
+            elif term == "adversary":
+                rc = lib.msig_da_train_step_multi(C.byref(desc), C.byref(m), C.byref(sd), ref, *tail)
+            elif term == "distill":
+                rc = lib.msig_kd_train_step_multi(C.byref(desc), C.byref(m), C.byref(sd), None, ref, *tail)
+            elif term == "sam":
+                rc = lib.msig_sam_train_step_multi(C.byref(desc), C.byref(m), C.byref(sd), None, ref, *tail)
             else:
-                rc = lib.msig_train_step_multi(C.byref(desc), C.byref(m), ea, eas, 0.9, 0.999, 1e-8, WD, count, st)
+                rc = lib.msig_dro_train_step_multi(C.byref(desc), C.byref(m), C.byref(sd), None, None, None, ref, *tail)
             L.check(rc, "train_step_multi")
     torch.cuda.synchronize()
     return arena
@@ -157,6 +245,24 @@ def test_fold_batch_has_the_bits_of_msig_train_step_multi():
         o, nb = a.off[name]
         assert torch.equal(a.mem[:, o:o + nb], b.mem[:, o:o + nb]), name
     assert float(a.across("acc", 0, torch.float64, 2)[2, 0]) > 0 and not torch.equal(a.view(0, "params"), a.view(2, "params"))
+
+
+@pytest.mark.parametrize("term", ["adversary", "distill", "sam", "dro"])
+def test_fold_batch_with_a_term_on_has_the_bits_of_the_narrowest_multi_entry_point(term):
+    """The launch as LockstepTrainer._train_epoch builds it, msig_sc_train_step_multi, against msig_da_, msig_kd_, msig_sam_ and
+    msig_dro_train_step_multi with the same descriptor: every arena region compared above, the gradients, and the term's own state —
+    its whole side block, or for SAM the arenas' "sam" region."""
+    a, b = _arena_run(True, term), _arena_run(False, term)
+    assert a.stride == b.stride
+    for name in ("params", "grads", "exp_avg", "exp_avg_sq", "bn_state", "acc") + (("sam",) if term == "sam" else ()):
+        o, nb = a.off[name]
+        assert torch.equal(a.mem[:, o:o + nb], b.mem[:, o:o + nb]), (term, name)
+    if term == "sam":
+        assert float(a.across("sam", 0, torch.float64, L.SAM_NSTAT)[0, L.SAM_STEPS]) == 4.0 and float(a.across("sam", 0, torch.float64, L.SAM_NSTAT)[2, L.SAM_STEPS]) == 2.0
+    else:
+        assert torch.equal(a.side[term][0].mem, b.side[term][0].mem) and a.side[term][0].stride == b.side[term][0].stride
+        assert a.side_stats(term)[2].any()                                  # the term ran in every fold: its statistics were written
+    assert float(a.across("acc", 0, torch.float64, 2)[2, 0]) > 0
 
 
 # ---- the loaders ---------------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 import sc_reference as R
 from conftest import load_golden_model
-from gpu_common import FIXED_TOL, GRAD_FLOOR, K_GRAD, grad_tol, rel_err, split_named, to_t
+from gpu_common import FIXED_TOL, GRAD_FLOOR, K_GRAD, grad_tol, narrow_train_step, rel_err, split_named, to_t
 from multimodalsignal_amd import _lib as L
 from multimodalsignal_amd.adversary import SubjectAdversary
 from multimodalsignal_amd.runtime import EmbeddedEngine, Engine, FoldArena
@@ -238,7 +238,8 @@ def _same_state(a, b):
 @pytest.mark.parametrize("with_sam", [False, True], ids=["plain", "sam"])
 @pytest.mark.parametrize("model", [(ATT, 64, 2), (CG, 64, 2), (ATT, 32, 1)], ids=["attention", "cnn_gru", "embedded"])
 def test_null_and_zero_weight_are_the_plain_step_bit_for_bit(model, with_sam):
-    """Three steps with eps = 0.1, clip and dropout: the engine's own call without the option, msig_sc_train_step with a NULL msig_sc
+    """Three steps with eps = 0.1, clip and dropout: the narrower entry point without the option called directly (msig_da_train_step, or msig_sam_train_step
+    with sam), msig_sc_train_step with a NULL msig_sc
     and the term at weight 0 leave the same parameters, gradients, moments, BatchNorm state and losses; the NULL call makes the same
     launches, the probe two more per pass and fills its statistics; weight 0.5 does change the model."""
     kind, hidden, layers = model
@@ -269,6 +270,10 @@ def test_null_and_zero_weight_are_the_plain_step_bit_for_bit(model, with_sam):
                             "msig_sc_train_step")
                     if layers == 1:
                         e.gather()
+                elif mode == "plain":                            # the narrower entry point, called directly (Engine.train_step is msig_sc_train_step)
+                    name = narrow_train_step(e, x, y, LR, weight_decay=1e-4, step=s, dropout_p=0.5, seed=7, label_smoothing=0.1, max_grad_norm=1.0,
+                                             sam=sam)
+                    assert name == ("msig_sam_train_step" if with_sam else "msig_da_train_step")
                 else:
                     e.train_step(x, y, LR, weight_decay=1e-4, step=s, dropout_p=0.5, seed=7, label_smoothing=0.1, max_grad_norm=1.0, sam=sam,
                                  supcon=sc)
@@ -434,11 +439,11 @@ def test_train_step_multi_equals_the_single_calls(extra):
     engs = [_engine(Cc, K, seed=10 + f, storage_engine=arena.engine(f)) for f in range(n)]
     scs, advs = [], []
     for f in range(n):
-        scs.append(SupCon(weights[f], 0.2, "cross-subject").set_subjects(tables[f]).bind(DEV, arena.sc_storage(f)))
+        scs.append(SupCon(weights[f], 0.2, "cross-subject").set_subjects(tables[f]).bind(DEV, arena.side_storage("supcon", f)))
         if extra == "adversary":
             adv = SubjectAdversary(S, lam=lam_rev[f], schedule="constant", seed=40 + f)
             adv.set_domains(doms[f])
-            advs.append(adv.bind(DEV, arena.adversary_storage(f)))
+            advs.append(adv.bind(DEV, arena.side_storage("adversary", f)))
         arena.set_max_norm(f, 1.0)
     slots = list(range(n))
     desc = arena.batch(B, True, 0.5)
@@ -481,7 +486,7 @@ def test_train_step_multi_equals_the_single_calls(extra):
         if extra == "adversary":
             for name in ("params", "exp_avg", "exp_avg_sq"):
                 assert torch.equal(_bits(getattr(adv, name)), _bits(getattr(advs[f], name))), (f, name)
-    assert torch.equal(arena.sc_stats().cpu(), torch.stack([s.stats.cpu() for s in scs]))
+    assert torch.equal(arena.side_stats("supcon").cpu(), torch.stack([s.stats.cpu() for s in scs]))
 
 
 def test_embedded_fold_batch_keeps_its_padding_zero_and_equals_the_single_calls():
@@ -492,7 +497,7 @@ def test_embedded_fold_batch_keeps_its_padding_zero_and_equals_the_single_calls(
     idx = _dev(rs.randint(0, npos, size=(n, B)).astype(np.int64))
     arena = FoldArena(Cc, K, DEV, n, B, T, gru_hidden=32, gru_layers=1, supcon=npos)
     engs = [_engine(Cc, K, 32, 1, seed=10 + f, storage_engine=arena.engine(f)) for f in range(n)]
-    scs = [SupCon(0.5, 0.1, "cross-subject").set_subjects(tables[f]).bind(DEV, arena.sc_storage(f)) for f in range(n)]
+    scs = [SupCon(0.5, 0.1, "cross-subject").set_subjects(tables[f]).bind(DEV, arena.side_storage("supcon", f)) for f in range(n)]
     slots = list(range(n))
     sd = arena.soft(slots, 0.0)
     desc = arena.batch(B, True, 0.5)

@@ -137,7 +137,7 @@ def folds(dev, n, reps, blocks, warmup, g, without_only):
         for f in range(n):
             adv = SubjectAdversary(S_DOMAINS, seed=f)
             adv.set_domains(dom)
-            adv.bind(dev, arena.adversary_storage(f))
+            adv.bind(dev, arena.side_storage("adversary", f))
         sd = arena.soft(slots, 0.0)
 
         def make(lam):

@@ -148,8 +148,8 @@ def folds(dev, n, reps, blocks, warmup, g, without_only):
         for f in range(n):
             kd = Distillation(0.5, 2.0)
             kd.set_teacher(teacher(B, K))
-            kd.bind(dev, arena.distill_storage(f))
-            GroupDro(0.01).set_groups(table, GROUPS).bind(dev, arena.dro_storage(f))
+            kd.bind(dev, arena.side_storage("distill", f))
+            GroupDro(0.01).set_groups(table, GROUPS).bind(dev, arena.side_storage("dro", f))
         sd = arena.soft(slots, 0.0)
         k = arena.kd(0.5, 2.0)
 

@@ -133,7 +133,7 @@ def folds(dev, n, reps, blocks, warmup, g, without_only):
         from multimodalsignal_amd.supcon import SupCon
         table = np.arange(B, dtype=np.int32) % SUBJECTS
         for f in range(n):
-            SupCon(0.1, 0.1, "cross-subject").set_subjects(table).bind(dev, arena.sc_storage(f))
+            SupCon(0.1, 0.1, "cross-subject").set_subjects(table).bind(dev, arena.side_storage("supcon", f))
         sd = arena.soft(slots, 0.0)
 
         def make(w):
