@@ -18,6 +18,7 @@
 #include "../../include/msig_sam.h"
 #include "../../include/msig_dro.h"
 #include "../../include/msig_sc.h"
+#include "../../include/msig_tt.h"
 
 // ---- profiling aid --------------------------------------------------------------
 struct ProfRec { const char* name; hipEvent_t a, b; };
@@ -281,11 +282,10 @@ extern "C" int msig_forward(const msig_batch* b, void* stream) {
 }
 
 // reads o.cg
-static int backward_fc(const msig_batch* b, const float* dlogits, hipStream_t st, const StepOpts& o) {
+static int backward_fc(const msig_batch* b, const float* dlogits, const FoldCtx& fc, hipStream_t st, const StepOpts& o) {
   const bool cg = o.cg;
   Ctx c; int rc = make_ctx(b, c, true, cg); if (rc) return rc;
   if (!msig_keeps(b)) return MSIG_E_SHAPE;
-  const FoldCtx fc = single_fold(b);
   ColsumPlan plan;      // every weight-gradient reduction of the pass, done by one launch at the end
   if ((rc = launch_head_bwd(b, dlogits, c.d, c.w, c.po, plan, fc, st))) return rc;
   if ((rc = launch_gru_bwd(b, c.d, c.w, c.po, plan, fc, st))) return rc;
@@ -293,7 +293,7 @@ static int backward_fc(const msig_batch* b, const float* dlogits, hipStream_t st
   return launch_colsum_plan(plan, fc, st);
 }
 extern "C" int msig_backward(const msig_batch* b, const float* dlogits, void* stream) {
-  return backward_fc(b, dlogits, (hipStream_t)stream, StepOpts{});
+  return backward_fc(b, dlogits, single_fold(b), (hipStream_t)stream, StepOpts{});
 }
 
 extern "C" int msig_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -457,7 +457,7 @@ extern "C" int msig_cg_forward(const msig_batch* b, const float* class_weight, v
   return forward_fc(b, single_fold(b), (hipStream_t)stream, StepOpts{class_weight, true});
 }
 extern "C" int msig_cg_backward(const msig_batch* b, const float* dlogits, void* stream) {
-  return backward_fc(b, dlogits, (hipStream_t)stream, StepOpts{nullptr, true});
+  return backward_fc(b, dlogits, single_fold(b), (hipStream_t)stream, StepOpts{nullptr, true});
 }
 extern "C" int msig_cg_train_step(const msig_batch* b, const float* class_weight, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
@@ -845,6 +845,40 @@ extern "C" int msig_ab_commit(const double* acc, int stage, float alpha, const f
 extern "C" int msig_ab_commit_multi(const double* acc, int stage, float alpha, const float* bn_src, float* bn_dst, const msig_multi* m, void* stream) {
   FoldCtx fc; int rc = msig_multi_fold_ctx(m, fc); if (rc) return rc;
   return ab_commit_fc(acc, stage, alpha, bn_src, bn_dst, fc, (hipStream_t)stream);
+}
+
+// ---- entropy-minimisation adaptation (include/msig_tt.h; kernels and the stand-alone calls: tta.hip) ------------------------------
+// One step: the eval forward kept for a backward, the objective's launch on WS_LOGITS -> WS_DLOGITS, msig_backward's arithmetic over
+// the folds of the launch, the selective Adam.  Every argument check, in the header's order, before the first launch.
+static int tt_step_fc(const msig_batch* b, FoldCtx fc, const msig_tt* t, const float* lrs, const int64_t* steps, int64_t step, hipStream_t st) {
+  if (!b || !t) return MSIG_E_NULL;
+  if (b->training || !b->keep_for_backward || b->dx) return MSIG_E_SHAPE;
+  TtSel sel;
+  int rc = msig_tt_make_sel(b->shape.C, b->shape.K, t->kind, t->select, sel); if (rc) return rc;
+  if (msig_tt_bad_diversity(t->diversity) || b->shape.B > MSIG_TT_MAX_BATCH) return MSIG_E_SHAPE;
+  if (!t->exp_avg || !t->exp_avg_sq) return MSIG_E_NULL;
+  if (step < 1) return MSIG_E_SHAPE;
+  if (steps)
+    for (int i = 0; i < fc.n; ++i) if (steps[i] < 0) return MSIG_E_SHAPE;
+  if (((uintptr_t)t->exp_avg | (uintptr_t)t->exp_avg_sq) & 15) return MSIG_E_ALIGN;
+  if ((uintptr_t)t->stats & 7) return MSIG_E_ALIGN;
+  const StepOpts o{nullptr, t->kind == MSIG_FT_KIND_CNN_GRU};
+  Ctx c;
+  if ((rc = make_ctx(b, c, true, o.cg))) return rc;
+  if ((rc = msig_check_call_forms(b, c.d.NT, fc))) return rc;
+  if ((rc = forward_fc(b, fc, st, o))) return rc;
+  if ((rc = launch_tt_objective(c.w.p<float>(MSIG_WS_LOGITS), c.w.p<float>(MSIG_WS_DLOGITS), t->stats, c.d.B, c.d.K, t->diversity, fc, st))) return rc;
+  if ((rc = backward_fc(b, nullptr, fc, st, o))) return rc;
+  msig_tt_fill_adam(fc, lrs, steps, step, t->beta1, t->beta2);
+  return launch_tt_adam((float*)b->params, b->grads, t->exp_avg, t->exp_avg_sq, sel, t->beta1, t->beta2, t->eps, t->weight_decay, fc, st);
+}
+extern "C" int msig_tt_step(const msig_batch* b, const msig_tt* t, float lr, int64_t step, void* stream) {
+  return tt_step_fc(b, single_fold(b), t, &lr, nullptr, step, (hipStream_t)stream);
+}
+extern "C" int msig_tt_step_multi(const msig_batch* b, const msig_multi* m, const msig_tt* t, int64_t step, void* stream) {
+  if (!b || !m || !t) return MSIG_E_NULL;
+  FoldCtx fc; int rc = make_fold_ctx(b, m, fc); if (rc) return rc;
+  return tt_step_fc(b, fc, t, m->lr, m->step, step, (hipStream_t)stream);
 }
 
 // ---- Monte-Carlo dropout (include/msig_mc.h; kernels of its own: mc.hip) ------------------------------------------------------------

@@ -583,6 +583,17 @@ struct ScArgs {
 // every check of msig_sc.h's own arguments, before any launch; fc: the folds of the launch (stride != 0: a fold batch)
 int msig_sc_make_args(const msig_sc* k, const FoldCtx& fc, int32_t B, int32_t K, ScArgs& a);
 int launch_sc_apply(const ScArgs& a, const float* feat, const int64_t* labels, float* dfeat, const FoldCtx& fc, hipStream_t st);
+// Entropy-minimisation adaptation (include/msig_tt.h, tta.hip).  The objective: one launch on WS_LOGITS that writes WS_DLOGITS, between
+// the forward's last launch and launch_head_bwd; logits / dlogits / stats are fold slot 0's, shifted per fold like every buffer.  The
+// selective Adam: the selected tensors' slots of the flat layout as (first float4, running float4 count) pairs, by value to the launch;
+// fc.lr_over_bc1 / inv_sqrt_bc2 per fold from msig_tt_fill_adam.
+struct TtSel { int32_t n, total4; int32_t first4[MSIG_NPARAM], cum4[MSIG_NPARAM]; };
+bool msig_tt_bad_diversity(float div);
+int msig_tt_make_sel(int C, int K, int kind, uint32_t select, TtSel& sel);
+void msig_tt_fill_adam(FoldCtx& fc, const float* lrs, const int64_t* steps, int64_t step, float beta1, float beta2);
+int launch_tt_objective(const float* logits, float* dlogits, double* stats, int B, int K, float div, const FoldCtx& fc, hipStream_t st);
+int launch_tt_adam(float* p, const float* g, float* m, float* v, const TtSel& sel, float b1, float b2, float eps, float wd, const FoldCtx& fc,
+                   hipStream_t st);
 // Weight-gradient reductions.  Every backward kernel leaves per-workgroup partials in its OWN sub-region of
 // MSIG_WS_GRAD_PART (nothing aliases), and only records what has to be summed: out[c] = sum_r part[r*stride +
 // col0 + c], fp64 accumulation in a fixed order.  The whole backward pass is then reduced by ONE launch

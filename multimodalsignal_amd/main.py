@@ -367,6 +367,42 @@ def adapt_units(kept, units, cfgs, device, rank=0):
     return out
 
 
+def entropy_units(kept, units, cfgs, device, rank=0):
+    """Label-free entropy-minimisation adaptation of the rank's finished folds (tta.EntropyAdapter): per fold the selected tensors of
+    a COPY of the fold's model (the one its test pass evaluated) descend the entropy of its own predictions on the TEST subject's
+    windows, labels unread by the objective, and the LOSO model and the adapted one are evaluated on those same windows.  With
+    --adapt-bn also given the adaptation starts from the AdaBN statistics (an adapt.BnAdapter of its own, the flag's alpha) and the
+    record has the AdaBN column too.  All folds of a configuration adapt as one fold batch (cfg["adapt_entropy_batched"] False:
+    single calls, the same bits).  The models, best_model.pt, fold_result.json and the LOSO summary are untouched; each fold
+    directory gets entropy_adaptation_result.json.  Returns the units adapted."""
+    from . import tta
+    from .adapt import BnAdapter
+    done = []
+    for n, cfg, chunk in _fold_batches(kept, units, cfgs):
+        st, jobs = tta.settings_of(cfg), []
+        for u in chunk:
+            x, y, _ = _windows(kept[u])
+            jobs.append(dict(model=kept[u]["model"], x=x, y=y))
+        eval_batch = kept[chunk[0]]["loaders"][2].batch_size
+        bn = None
+        if cfg.get("adapt_bn") is not None:
+            bn = BnAdapter([dict(model=j["model"], x=j["x"]) for j in jobs], alpha=float(cfg["adapt_bn"]), eval_batch=eval_batch)
+            for i, j in enumerate(jobs):
+                j["bn_state"] = bn.adapted_state(i).clone()
+        ad = tta.EntropyAdapter(jobs, lr=st["lr"], epochs=st["epochs"], diversity=st["diversity"], batch=st["batch"], params=st["params"],
+                                seed=st["seed"], order=st["order"], batched=bool(cfg.get("adapt_entropy_batched", True)), eval_batch=eval_batch)
+        for u, r in zip(chunk, ad.run()):
+            p = kept[u]
+            r = dict(subject=p["subject"], settings=st, **r)
+            (p["fold_dir"] / "entropy_adaptation_result.json").write_text(json.dumps(r))
+            mid = f" -> {r['start']['accuracy']:.4f} (AdaBN)" if "start" in r else ""
+            print(f"[rank {rank}] {_tag(n)}fold {p['fold']} ({p['subject']}) entropy adaptation on {r['n']} unlabelled windows: "
+                  f"acc {r['before']['accuracy']:.4f}{mid} -> {r['after']['accuracy']:.4f}  entropy {r['entropy']['before']:.4f} -> "
+                  f"{r['entropy']['after']:.4f}  {r['flipped']} predictions flipped", flush=True)
+            done.append(u)
+    return done
+
+
 def attribution_settings(cfg):
     """The attribution settings of a configuration (--attribute ...), as attribution.txt / attribution.json name them; the bin is
     the flag's, else one second of a 60-second window of T samples (None while T is not known)."""
@@ -625,7 +661,8 @@ def train_units(mine, groups, make, cfg0, device):
     yield from zip(mine, on_streams(lambda u: train_fold(preps[u], device), mine, device, workers=min(conc, MAX_TRAIN_STREAMS)))
 
 
-def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None, attributed=False, uncertain=False):
+def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all=None, attributed=False, uncertain=False,
+                    entropy=False):
     """cv_summary.txt — and calibration.txt / calibration.json after --calibrate, adaptation.txt / adaptation.json after --adapt-bn,
     attribution.txt / attribution.json after --attribute, uncertainty.txt / uncertainty.json after --mc-dropout (from the folds'
     attribution_result.json / uncertainty_result.json, which every rank has written before the fold metrics were gathered) — of
@@ -682,6 +719,13 @@ def write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data,
                      for u in sorted(ad_all) if units[u][0] == n]
             path = write_adaptation(out_dir[n], folds, adaptation_settings(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
             print(f"BatchNorm adaptation table written to: {path}")
+        if entropy:      # entropy_adaptation.txt / .json after --adapt-entropy, from the folds' entropy_adaptation_result.json
+            from .tta import settings_of, write_entropy_adaptation
+            files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "entropy_adaptation_result.json" for r in results[n]]
+            folds = [json.loads(f.read_text()) for f in files if f.exists()]
+            if folds:
+                path = write_entropy_adaptation(out_dir[n], folds, settings_of(cfgs[n]), synthetic=bool(cfgs[n].get("synthetic")))
+                print(f"Entropy adaptation table written to: {path}")
         if attributed:
             from .attribute import write_attribution
             files = [out_dir[n] / f"fold_test_on_{r['subject']}" / "attribution_result.json" for r in results[n]]
@@ -730,13 +774,14 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
     adapt = cfg0.get("adapt_bn") is not None         # --adapt-bn: label-free BatchNorm adaptation to the test subject; absent = off
     attr = cfg0.get("attribute") is not None         # --attribute: integrated-gradients attribution on the test subject; absent = off
     mc = cfg0.get("mc_dropout") is not None          # --mc-dropout: Monte-Carlo dropout uncertainty on the test subject; absent = off
+    tent = cfg0.get("adapt_entropy") is not None     # --adapt-entropy: entropy-minimisation adaptation to the test subject; absent = off
     kept, local = {}, {}                             # unit -> its prep (model, loaders), kept for the calibration / adaptation after the folds; -> its metrics
     members, epochs = {}, {}                         # --seeds: every unit's prep, for the ensembles after the folds; its stop epoch
 
     def make(u):
         n, k = units[u]
         p = prepare_fold(k, cfgs[n]["subjects"][k], out_dir[n], device, all_channel_names, cfgs[n], stores[n])
-        if (n_cal or adapt or attr or mc) and not cfgs[n].get("replica"):      # the post-LOSO passes run on replica 0 only
+        if (n_cal or adapt or attr or mc or tent) and not cfgs[n].get("replica"):      # the post-LOSO passes run on replica 0 only
             kept[u] = p
         if S > 1 or kd is not None:
             members[u] = p
@@ -753,6 +798,8 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
               f"{info['epochs']} epochs {info['seconds']:.1f}s {info['train_windows_per_s']:.0f} windows/s", flush=True)
     cal_local = calibrate_units(kept, units, cfgs, device, rank) if n_cal and kept else {}
     ad_local = adapt_units(kept, units, cfgs, device, rank) if adapt and kept else {}      # on its own: the LOSO model, not the calibrated one
+    if tent and kept:                                # on copies of the LOSO model; its records go to the fold directories
+        entropy_units(kept, units, cfgs, device, rank)
     if attr and kept:                                # likewise the LOSO model; its records go to the fold directories
         attribute_units(kept, units, cfgs, device, rank)
     if mc and kept:                                  # likewise
@@ -795,7 +842,7 @@ def run_experiments(run_output_dir, device, all_channel_names, cfgs, rank=0, wor
         for path in write_distillation_tables(base, out_dir, results, kd, S):
             print(f"Distillation table written to: {path}")
     if rank == 0 or emulate:
-        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr, uncertain=mc)
+        write_summaries(cfgs, units, out_dir, results, cal_all, wall, world, t_data, ad_all, attributed=attr, uncertain=mc, entropy=tent)
     return results, wall
 
 
@@ -1172,6 +1219,18 @@ def parse_args(ap, argv=None):
             ap.error("--adapt-bn runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
     elif args.adapt_bn_sequential:
         ap.error("--adapt-bn-sequential needs --adapt-bn")
+    if args.adapt_entropy is not None:
+        from . import tta
+        try:
+            args.adapt_entropy = tta.parse_flag(args.adapt_entropy)
+            tta.check_settings(**args.adapt_entropy, params=args.adapt_entropy_params or "bn",
+                               batch=64 if args.adapt_entropy_batch is None else args.adapt_entropy_batch)
+        except ValueError as e:
+            ap.error(f"--adapt-entropy: {e}")
+        if args.hierarchical or args.ablation or args.sweep:
+            ap.error("--adapt-entropy runs with the standard LOSO and the --model comparison run (not --hierarchical, --ablation or --sweep)")
+    elif args.adapt_entropy_sequential or args.adapt_entropy_params is not None or args.adapt_entropy_batch is not None:
+        ap.error("--adapt-entropy-params / --adapt-entropy-batch / --adapt-entropy-sequential need --adapt-entropy")
     if args.attribute is not None:
         from .attribute import check_bin, check_steps
         try:
@@ -1293,7 +1352,7 @@ def parse_args(ap, argv=None):
             if args.hierarchical:
                 ap.error("--norm-reference with several values runs with the standard LOSO, --ablation and --sweep (not --hierarchical)")
             post = [flag for flag, on in (("--calibrate", args.calibrate), ("--adapt-bn", args.adapt_bn is not None),
-                                          ("--attribute", args.attribute is not None), ("--mc-dropout", args.mc_dropout is not None),
+                                          ("--adapt-entropy", args.adapt_entropy is not None), ("--attribute", args.attribute is not None), ("--mc-dropout", args.mc_dropout is not None),
                                           ("--seeds", args.seeds > 1), ("--weight-average", args.weight_average is not None)) if on]
             if post:
                 ap.error(f"--norm-reference with several values does not combine with {', '.join(post)}; give one reference")
@@ -1429,6 +1488,21 @@ def build_parser():
                          "each on its own against the LOSO model)")
     ap.add_argument("--adapt-bn-sequential", action="store_true",
                     help="adapt with single calls per fold instead of one fold batch for all folds of a rank (the same bits)")
+    ap.add_argument("--adapt-entropy", nargs="?", const="", default=None, metavar="LR[:EPOCHS[:DIVERSITY]]",
+                    help="after each fold's test pass, label-free entropy-minimisation adaptation (TENT) of a COPY of the fold's model on "
+                         "the test subject's unlabelled windows: every weight frozen but the BatchNorm scale and shift (see "
+                         "--adapt-entropy-params), which take EPOCHS passes (default 1) of Adam at LR (default 1e-3) down the entropy of the "
+                         "model's own eval-mode predictions, less DIVERSITY (default 0) times the entropy of a batch's mean prediction; "
+                         "evaluates the LOSO model and the adapted one on the same windows and writes entropy_adaptation.txt / "
+                         "entropy_adaptation.json with the prediction entropy, flipped predictions and predicted-class shares; with "
+                         "--adapt-bn it starts from the AdaBN statistics and the table has the AdaBN column too (standard LOSO and --model "
+                         "comparison runs; replica 0 under --seeds)")
+    ap.add_argument("--adapt-entropy-params", choices=("bn", "bn+gate", "all"), default=None,
+                    help="the tensors --adapt-entropy lets move: the BatchNorm scale and shift (default), those and ChannelAttention's two "
+                         "matrices, or every parameter")
+    ap.add_argument("--adapt-entropy-batch", type=int, default=None, metavar="B", help="windows per adaptation step (default 64, at most 2048)")
+    ap.add_argument("--adapt-entropy-sequential", action="store_true",
+                    help="adapt with single calls per fold instead of one fold batch for all folds of a rank (the same bits)")
     ap.add_argument("--attribute", type=int, nargs="?", const=32, default=None, metavar="STEPS",
                     help="after each fold's test pass, integrated-gradients attribution of the fold's model on the test subject's windows "
                          "(zero baseline, each window's predicted class, STEPS midpoints of the path, 1..256; bare flag: 32): which channels "
@@ -1500,6 +1574,13 @@ def build_cfg(args, kinds):
                 cfg[key] = val
     if args.adapt_bn is not None:      # likewise: without the flag there is no such key
         cfg.update(adapt_bn=args.adapt_bn, synthetic=args.synthetic is not None, adapt_bn_batched=not args.adapt_bn_sequential)
+    if args.adapt_entropy is not None:      # likewise
+        cfg.update(adapt_entropy=dict(args.adapt_entropy), synthetic=args.synthetic is not None,
+                   adapt_entropy_batched=not args.adapt_entropy_sequential)
+        if args.adapt_entropy_params is not None:
+            cfg["adapt_entropy_params"] = args.adapt_entropy_params
+        if args.adapt_entropy_batch is not None:
+            cfg["adapt_entropy_batch"] = args.adapt_entropy_batch
     if args.attribute is not None:     # likewise
         cfg.update(attribute=args.attribute, synthetic=args.synthetic is not None)
         if args.attribute_bin is not None:

@@ -236,6 +236,25 @@ class _MsigModel(nn.Module):
             self.engine().load_named(bufs)
         return bufs
 
+    @torch.no_grad()
+    def adapt_entropy(self, x, lr=1e-3, epochs=1, diversity=0.0, params="bn", batch=64, seed=0, order="shuffled", inplace=False):
+        """Label-free entropy-minimisation adaptation (TENT, tta.EntropyAdapter, include/msig_tt.h): the tensors ``params`` names
+        ("bn": the BatchNorm scale and shift; "bn+gate"; "all") after ``epochs`` passes of Adam at ``lr`` down the entropy of this
+        model's own eval-mode predictions on the unlabelled windows ``x`` (N, C, T), less ``diversity`` times the entropy of a
+        batch's mean prediction.  Returned under the reference's ``state_dict`` names.  The BatchNorm buffers,
+        ``num_batches_tracked``, ``self.training``, every ``.grad`` and the dropout step counter are untouched; with
+        ``inplace=False`` so is every parameter, and ``inplace=True`` loads the returned tensors into the model."""
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.adapt_entropy needs a GPU tensor: the MI355X path has no CPU fallback")
+        from .tta import EntropyAdapter
+        out = EntropyAdapter([dict(model=self, x=x)], lr=lr, epochs=epochs, diversity=diversity, batch=batch, params=params, seed=seed,
+                             order=order).adapted_tensors(0)
+        if inplace:
+            named = dict(self.named_parameters())
+            for k, v in out.items():
+                named[k].data.copy_(v)                  # the parameters are views of the engine's buffers: this is the load
+        return out
+
     def attribute(self, x, target="predicted", steps=32, baseline=None, bin=None, return_map=True):
         """Integrated-gradients attribution (attribute.Attributor, include/msig_at.h) of the windows ``x`` (N, C, T) in EVAL mode
         whatever ``self.training`` is: ``(x - baseline) * mean_p df/dx`` at ``steps`` midpoints of the straight path from the

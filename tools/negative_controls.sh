@@ -51,6 +51,43 @@
 # tests/test_input_regimes_gpu.py, which must PASS against the control: it is the arithmetic they always ran, and that pass is the
 # evidence that the suite had the gap.  Time limits, the stop at the first abnormal exit and the per-library sections as in the regime
 # mode.  LIBRARY: product 1 (default both).
+# tools/negative_controls.sh tent [OUT] [LIBRARY ...]: the control of the ENTROPY-MINIMISATION objective (library
+# built by  make -C multimodalsignal_amd/csrc negctl TENT=1 ): tt_objective_kernel's gradient without H_b, -p lp alone (tta.hip
+# MSIG_NEGCTL_TENT).  Per library: one pass of the objective's parity cases of tests/test_entropy_adapt_gpu.py — the product must pass
+# every case, the control must FAIL every case (every case holds a row whose entropy is of order 1: uniform rows, and saturated rows
+# with their peak twice).  Time limit, the stop at the first abnormal exit and the per-library sections as in the regime mode.
+# LIBRARY: product 1 (default both).
+if [ "$1" = tent ]; then
+  OUT=${2:-tent_negctl_out/entropy_adapt_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1}
+  NEW=tests/test_entropy_adapt_gpu.py::test_objective_against_the_reference
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_tent$k.so; fi
+    sec=$D/tent_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 420 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/tent_negctl_${k}.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# $NEW (exit $rc):   $(tail -1 $D/tent_negctl_${k}.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/tent_negctl_${k}.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    npass=$(grep -c "^PASSED " $D/tent_negctl_${k}.txt)
+    nfail=$(grep -c "^FAILED " $D/tent_negctl_${k}.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] && [ "$nfail" = 0 ] && [ "$npass" -gt 0 ] || { echo "!! the product library must pass every case" >> $sec; bad=1; }
+      continue
+    fi
+    if [ "$npass" = 0 ] && [ "$nfail" -gt 0 ]; then echo "# verdict: control $k FAILS all $nfail cases" >> $sec
+    else echo "!! control $k passes $npass cases: the gate does not catch it there" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh tent: $NEW against libmsig_hip_tent1.so (make negctl TENT=1)" > "$OUT"
+  for k in product 1; do [ -f $D/tent_negctl_section_$k.log ] && cat $D/tent_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = stage2 ]; then
   OUT=${2:-stage2_negctl_out/stage2_negative_control.log}
   D=$(dirname "$OUT")
