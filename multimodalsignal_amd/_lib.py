@@ -1,6 +1,6 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
 include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h, include/msig_sc.h, include/msig_nr.h,
-include/msig_rec.h).
+include/msig_rec.h, include/msig_lv.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -120,6 +120,8 @@ SC_STATS = 4          # msig_sc.h MSIG_SC_STATS: sum of the anchors' losses, anc
 SC_POSITIVES = {"class": 0, "cross-subject": 1}      # MSIG_SC_POS_*
 NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject normalisation with the statistics of reference windows)
 REC_ABI_VERSION = 1   # include/msig_rec.h MSIG_REC_ABI_VERSION (statistics and normalised window batches straight from a continuous recording)
+LV_ABI_VERSION = 1    # include/msig_lv.h MSIG_LV_ABI_VERSION (a pool of sample rings and window batches whose rows come from different sessions)
+LV_MAX_SESSIONS = 4096        # MSIG_LV_MAX_SESSIONS
 
 
 class Sc(C.Structure):
@@ -486,6 +488,14 @@ def lib() -> C.CDLL:
         L.msig_rec_stats.argtypes = rec + [i64, i64, vp, vp, vp]
         L.msig_rec_windows.argtypes = rec + [i64, i32, vp, vp, vp]
         L.msig_rec_windows_multi.argtypes = rec + [i64, i32, vp, vp, C.POINTER(Multi), vp]
+        # include/msig_lv.h, exported by the same library: sample rings of many sessions and mixed window batches
+        L.msig_lv_abi_version.restype = C.c_int
+        if L.msig_lv_abi_version() != LV_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_lv.h ABI {L.msig_lv_abi_version()}; this binding is {LV_ABI_VERSION}: rebuild the library")
+        pool = [vp, i32, i64, i64, i32]                                       # pool, sessions, R, ring_bytes, C_all
+        L.msig_lv_push.argtypes = pool + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
+        L.msig_lv_windows_multi.argtypes = pool + [C.POINTER(i32), i32, C.c_uint32, i64, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32,
+                                                   vp, vp, C.POINTER(Multi), vp]
         _lib = L
     return _lib
 

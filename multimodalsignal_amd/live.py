@@ -1,0 +1,530 @@
+"""Live monitoring: push(samples) for many wearers, bit-equal to the offline timeline (include/msig_lv.h).
+
+A wearable delivers a few seconds of samples at a time, and one GPU serves many wearers.  `LiveMonitor` keeps one ring of the last
+`ring_s` seconds per open session in a device pool.  One `push` appends every session's chunk (msig_lv_push), collects every window
+that became complete across all sessions, and runs them through the ensemble as mixed batches of at most `eval_batch` rows: one
+msig_lv_windows_multi, one msig_st_forward_multi and one msig_en_reduce_multi per piece and member chunk, on `Ensemble`'s own
+forward and reduction code (`LiveEnsemble` overrides the filling of the arenas, as monitor.RecordingEnsemble does, and their size).  What a
+session reports equals, bit for bit, what `Monitor.run` reports for the same samples as one recording: a "head:K" reference is
+causal, a row's eval bits do not depend on its batch, and the smoothing is `monitor.ema`'s recurrence continued.
+
+The offline state drops episodes shorter than `min_on` after the fact; a live system cannot take back an alarm.  So an `onset` alarm
+is raised at the window where a run of the raw hysteresis state reaches `min_on` windows (it carries the run's first window), and an
+`offset` alarm at the window where such a run ends: every offline event (a, b) yields one onset at window a + min_on - 1 and one
+offset at window b; runs the offline timeline drops yield nothing.  `timeline(sid)` is the offline `Timeline` of everything pushed
+so far.
+
+The host parts (`Smoother`, `AlarmMachine`, `RingBook`, the CLI's argument checks) need no GPU.  `LiveMonitor` has no CPU fallback.
+
+Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py), drifting or re-estimated statistics
+(a session's statistics are fixed once its head is complete), and any network or serial front end — push() is the interface.
+
+CLI:  python -m multimodalsignal_amd.live --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
+      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6] --out DIR
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+from dataclasses import asdict, dataclass
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .ensemble import Ensemble, load_members
+from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, ema, find_events, hysteresis,
+                      parse_recording_reference, phase_shares)
+
+FIELDS = ("mean_p", "std_p", "pred", "entropy", "mutual_info", "votes")      # what a session stores per window, as Ensemble.predict gives it
+
+
+# ---- the parts that need no GPU ---------------------------------------------------------------------------------------------------
+class Smoother:
+    """monitor.ema one score at a time: the same float64 operations in the same order, so after n scores `value` holds
+    ema(scores, halflife)[n - 1] bit for bit."""
+
+    def __init__(self, halflife: float):
+        ema([], halflife)
+        self.a = 1.0 if halflife == 0 else 1.0 - 2.0 ** (-1.0 / float(halflife))
+        self.n, self.value = 0, 0.0
+
+    def push(self, score) -> float:
+        v = float(score)
+        self.value = v if self.n == 0 else self.value + self.a * (v - self.value)
+        self.n += 1
+        return self.value
+
+
+@dataclass(frozen=True)
+class Alarm:
+    """kind "onset": at `window` a run of the raw hysteresis state that began at `start_window` reached min_on windows; "offset":
+    `window` is the first window after such a run.  t_s and start_s are the end times of `window` and `start_window` in seconds
+    (None where the machine was given no clock)."""
+    kind: str
+    window: int
+    start_window: int
+    t_s: Optional[float] = None
+    start_s: Optional[float] = None
+
+
+class AlarmMachine:
+    """monitor.hysteresis one smoothed score at a time, with the live min_on rule (module docstring).  step(v) returns (on, alarm):
+    `on` — a run of at least min_on windows is in progress at this window; `alarm` — the Alarm raised at this window or None."""
+
+    def __init__(self, on: float, off: float, min_on: int = 1):
+        hysteresis([], on, off, min_on)
+        self.on, self.off, self.min_on = float(on), float(off), int(min_on)
+        self.n, self.raw, self.start = 0, False, 0
+
+    def step(self, v) -> Tuple[bool, Optional[Alarm]]:
+        v, n, alarm = float(v), self.n, None
+        if not self.raw and v >= self.on:
+            self.raw, self.start = True, n
+        elif self.raw and v <= self.off:
+            self.raw = False
+            if n - self.start >= self.min_on:
+                alarm = Alarm("offset", n, self.start)
+        if self.raw and n - self.start + 1 == self.min_on:
+            alarm = Alarm("onset", n, self.start)
+        self.n += 1
+        return self.raw and n - self.start + 1 >= self.min_on, alarm
+
+
+def alarms_of_events(state, min_on: int) -> List[Tuple[str, int, int]]:
+    """(kind, window, start_window) of the alarms the offline state vector implies: per episode (a, b) an onset at a + min_on - 1
+    and, where the episode ends inside the vector, an offset at b — in window order."""
+    s = np.concatenate(([False], np.asarray(state, dtype=bool), [False]))
+    edges = np.flatnonzero(s[1:] != s[:-1])
+    out = []
+    for a, b in zip(edges[0::2], edges[1::2]):
+        out.append(("onset", int(a) + int(min_on) - 1, int(a)))
+        if b < len(s) - 2:
+            out.append(("offset", int(b), int(a)))
+    return sorted(out, key=lambda e: e[1])
+
+
+class RingBook:
+    """The bookkeeping of one session's ring of R rows, windows of T samples every S, `warm` leading windows that supply the
+    statistics (0: the statistics are given).  `written` samples so far, windows below `next_window` are handed out.
+
+    A push of n samples is appended in segments.  A segment never overwrites a sample that a window not yet handed out still needs:
+    its length is at most next_window * S + R - written (>= 1 while R >= T), and at most R (S > T: the samples between two windows
+    are needed by none).  While the statistics are pending no window is handed
+    out, so next_window = 0 and no segment wraps: the head span (warm - 1) * S + T <= R lies unwrapped at the ring's start when the
+    segment that completes it has been appended — that is where the statistics are taken, before the next segment is.  After each
+    segment `advance` says whether the statistics are due and which windows became complete."""
+
+    def __init__(self, R: int, T: int, S: int, warm: int = 0):
+        R, T, S, warm = int(R), int(T), int(S), int(warm)
+        if T < 1 or S < 1 or warm < 0:
+            raise ValueError(f"a ring needs T >= 1, S >= 1 and warm >= 0, got {T}, {S}, {warm}")
+        self.head = (warm - 1) * S + T if warm else 0
+        if R < max(T, self.head):
+            raise ValueError(f"a ring of {R} rows cannot hold {'the head span of ' + str(self.head) if warm else 'one window of ' + str(T)} samples")
+        self.R, self.T, self.S, self.warm = R, T, S, warm
+        self.written, self.next_window, self.pending = 0, 0, warm > 0
+
+    def complete(self) -> int:
+        """The number of complete windows (msig_rec_count of the samples written)."""
+        return 0 if self.written < self.T else (self.written - self.T) // self.S + 1
+
+    def segment(self, n: int) -> int:
+        """How many of n waiting samples the next append may take."""
+        return min(int(n), self.R, self.next_window * self.S + self.R - self.written)
+
+    def advance(self, a: int) -> Tuple[bool, range]:
+        """`a` samples were appended: (the statistics are due now, the windows to hand out now)."""
+        if not 0 <= a <= min(self.R, self.next_window * self.S + self.R - self.written):
+            raise ValueError(f"a segment of {a} samples would overwrite window {self.next_window}")
+        self.written += int(a)
+        due = self.pending and self.written >= self.head
+        if due:
+            self.pending = False
+        if self.pending:
+            return False, range(0)
+        w = range(self.next_window, self.complete())
+        self.next_window = w.stop if len(w) else self.next_window
+        return due, w
+
+    def plan(self, n: int) -> List[Tuple[int, bool, range]]:
+        """The segments of a push of n samples as (length, statistics due after it, windows handed out after it); advances the book."""
+        out, n = [], int(n)
+        while n > 0:
+            a = self.segment(n)
+            out.append((a, *self.advance(a)))
+            n -= a
+        return out
+
+
+@dataclass
+class LiveUpdate:
+    """One new window of one session: its index, t_end = (window S + T) / fs, the timeline's row (score = mean_p[positive], std =
+    std_p[positive], entropy, mutual_info, pred, smoothed, warmup), `on` (AlarmMachine: an alarm is active) and the Alarm raised at
+    this window, if any."""
+    sid: object
+    window: int
+    t_end: float
+    score: float
+    std: float
+    entropy: float
+    mutual_info: float
+    pred: int
+    smoothed: float
+    warmup: bool
+    on: bool
+    alarm: Optional[Alarm] = None
+
+
+# ---- the sessions on the GPU -------------------------------------------------------------------------------------------------------
+class LiveBatch:
+    """Rows of a mixed batch: window win[b] of the session in pool slot sess[b], which holds written[b] samples."""
+
+    def __init__(self, monitor: "LiveMonitor", rows: Sequence[Tuple[int, int, int]]):
+        self.monitor, self.device = monitor, monitor.device
+        self.sess = np.ascontiguousarray([r[0] for r in rows], dtype=np.int32)
+        self.win = np.ascontiguousarray([r[1] for r in rows], dtype=np.int64)
+        self.written = np.ascontiguousarray([r[2] for r in rows], dtype=np.int64)
+        self.C, self.T = monitor.ensemble.C, monitor.T
+        self.shape = (len(rows), self.C, self.T)
+
+    def fill(self, x0: int, multi: L.Multi, i: int, b: int):
+        """Rows i .. i + b - 1 into the x buffer of every arena slot of `multi`; x0 is arena 0's (msig_lv_windows_multi)."""
+        mon = self.monitor
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        L.check(L.lib().msig_lv_windows_multi(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, self.sess[i:].ctypes.data_as(p32),
+                                              self.win[i:].ctypes.data_as(p64), self.written[i:].ctypes.data_as(p64), int(b),
+                                              mon.stats.data_ptr(), x0, C.byref(multi), mon._stream()), "msig_lv_windows_multi")
+
+
+class LiveEnsemble(Ensemble):
+    """An Ensemble whose input is a LiveBatch: predict(batch) runs Ensemble's own pieces, forwards and reduction; only the filling
+    of the arenas differs — one msig_lv_windows_multi per piece.  Its arenas are sized for eval_batch rows once: a tick's pieces
+    have any size up to that, and none of them allocates."""
+
+    def _arenas(self, T: int, sizes):
+        super()._arenas(T, [self.eval_batch])
+
+    def _check_x(self, x):
+        if not isinstance(x, LiveBatch):
+            return super()._check_x(x)
+        if x.device != self.device or x.C != self.C or x.T < 16 or x.shape[0] < 1:
+            raise ValueError(f"expected windows of {self.C} channels and T >= 16 on {self.device}, got {x.C} channels, T = {x.T} on {x.device}")
+        return x
+
+    def _fill(self, x, i: int, b: int, n: int):
+        if not isinstance(x, LiveBatch):
+            return super()._fill(x, i, b, n)
+        x.fill(self.arenas.ptr("x"), self.arenas.multi(range(n)), i, b)
+
+
+class _Session:
+    def __init__(self, sid, slot: int, book: RingBook, mon: "LiveMonitor"):
+        self.sid, self.slot, self.book = sid, slot, book
+        self.smoother, self.machine = Smoother(mon.halflife), AlarmMachine(mon.on, mon.off, mon.min_on)
+        self.given = book.warm == 0
+        self.rows: Dict[str, list] = {k: [] for k in FIELDS}
+        self.score: List[float] = []
+        self.smoothed: List[float] = []
+        self.alarms: List[Alarm] = []
+
+
+class LiveMonitor:
+    """An ensemble of 1..256 trained models over up to `max_sessions` live sessions sampled at `fs` Hz: windows of `window_s` seconds
+    every `stride_s`, a ring of `ring_s` seconds per session (None: the head span or one window, plus 8 strides), `eval_batch` rows
+    per piece.  `reference`: "head:K" — a session's first K windows supply its statistics and are emitted together, flagged warmup,
+    when window K - 1 completes — or a float64 statistics tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.
+    "recording" is refused: it is not causal.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.
+
+    open(sid, names, stats=None) / close(sid); push({sid: samples}) or push(sid, samples); timeline(sid); alarms(sid)."""
+
+    def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="head:6", max_sessions: int = 64,
+                 ring_s: Optional[float] = None, eval_batch: int = 256, positive: int = 1, halflife: float = 3, on: float = 0.6,
+                 off: float = 0.4, min_on: int = 2, channels: Optional[Sequence[str]] = None):
+        if not float(fs) > 0:
+            raise ValueError(f"fs must be > 0, got {fs!r}")
+        self.fs = float(fs)
+        self.T, self.S = int(round(float(window_s) * self.fs)), int(round(float(stride_s) * self.fs))
+        if self.T < 16 or self.S < 1:
+            raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
+        if isinstance(reference, torch.Tensor):
+            if reference.dtype != torch.float64 or reference.numel() < 2 * L.MAX_C + 1:
+                raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
+            self.warm = 0
+        elif isinstance(reference, str) and reference.startswith("head:"):
+            self.warm = parse_recording_reference(reference, 1 << 62)[2]
+        else:
+            raise ValueError(f"a live reference is 'head:K' or a statistics tensor (anything else is not causal), got {reference!r}")
+        if isinstance(max_sessions, bool) or not 1 <= int(max_sessions) <= L.LV_MAX_SESSIONS:
+            raise ValueError(f"max_sessions must be an integer in 1..{L.LV_MAX_SESSIONS}, got {max_sessions!r}")
+        head = (self.warm - 1) * self.S + self.T if self.warm else self.T
+        self.R = head + 8 * self.S if ring_s is None else int(round(float(ring_s) * self.fs))
+        RingBook(self.R, self.T, self.S, self.warm)                  # refuses a ring shorter than the head span
+        if self.R >= 1 << 31:
+            raise ValueError(f"a ring holds fewer than 2^31 samples, got {self.R}")
+        hysteresis([], on, off, min_on)
+        ema([], halflife)
+        self.models = list(models)
+        self.ensemble = LiveEnsemble(self.models, eval_batch=eval_batch)
+        self.device = self.ensemble.device
+        if not 0 <= int(positive) < self.ensemble.K:
+            raise ValueError(f"positive must be a class in 0..{self.ensemble.K - 1}, got {positive!r}")
+        self.reference, self.positive, self.halflife, self.on, self.off, self.min_on = reference, int(positive), float(halflife), float(on), float(off), int(min_on)
+        self.channels = None if channels is None else list(channels)
+        if self.channels is not None and len(self.channels) != self.ensemble.C:
+            raise ValueError(f"the models take {self.ensemble.C} channels, got {len(self.channels)} names")
+        self.max_sessions = int(max_sessions)
+        self.files: List[Path] = []
+        self.names: Optional[List[str]] = None       # the columns of every session's samples: fixed by the first open()
+        self.sessions: Dict[object, _Session] = {}
+        self.free = list(range(self.max_sessions))
+        self.stats = torch.zeros((self.max_sessions, 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
+        self.scratch = torch.empty(L.lib().msig_rec_scratch_bytes(), dtype=torch.uint8, device=self.device)
+        self.pool = None
+
+    @classmethod
+    def from_run(cls, run_dir, subject: Optional[str] = None, config_name: Optional[str] = None, fs: float = 64.0, device="cuda", **kw) -> "LiveMonitor":
+        """The checkpoints Monitor.from_run loads (Monitor.run_files) and the run's channels (Monitor.run_channels)."""
+        files = Monitor.run_files(run_dir, subject, config_name)
+        kw.setdefault("channels", Monitor.run_channels(run_dir, config_name))
+        self = cls(load_members(files, device), fs, **kw)
+        self.files = files
+        return self
+
+    # ---- sessions ---------------------------------------------------------------------------------------------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _pool_args(self):
+        return self.pool.data_ptr(), self.max_sessions, self.R, self.pool.shape[1] * 8, self.C_all
+
+    def _bind(self, names: Sequence[str]):
+        names = list(names)
+        channels = self.channels if self.channels is not None else names
+        if not 1 <= len(channels) <= L.MAX_C or len(channels) != self.ensemble.C:
+            raise ValueError(f"the models take {self.ensemble.C} channels, the sessions supply {len(channels)}")
+        missing = [c for c in channels if c not in names]
+        if missing:
+            raise ValueError(f"the sessions have no channel {missing}; they have {names}")
+        self.names, self.C_all = names, len(names)
+        self.cols = (C.c_int32 * len(channels))(*[names.index(c) for c in channels])
+        self.mask = sum(1 << c for c, name in enumerate(channels) if name == "chest_EDA")
+        self.pool = torch.empty((self.max_sessions, self.R * self.C_all), dtype=torch.float64, device=self.device)
+
+    def open(self, sid, names: Optional[Sequence[str]] = None, stats: Optional[torch.Tensor] = None):
+        """A new session `sid` (any hashable) whose samples have the columns `names` — every session of a monitor has the same
+        columns, so after the first open `names` may be None.  `stats`: this wearer's statistics, enrolled earlier: no warm-up."""
+        if sid in self.sessions:
+            raise ValueError(f"session {sid!r} is open")
+        if self.names is None:
+            if names is None:
+                raise ValueError("the first open() names the columns of the samples")
+            self._bind(names)
+        elif names is not None and list(names) != self.names:
+            raise ValueError(f"every session of a monitor has the columns {self.names}, got {list(names)}")
+        given = stats if stats is not None else (self.reference if isinstance(self.reference, torch.Tensor) else None)
+        if given is not None and (not isinstance(given, torch.Tensor) or given.dtype != torch.float64 or given.numel() < 2 * L.MAX_C + 1):
+            raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
+        if not self.free:
+            raise ValueError(f"all {self.max_sessions} sessions of the pool are open")
+        slot = self.free.pop(0)
+        if given is not None:
+            self.stats[slot].copy_(given.reshape(-1)[:2 * L.MAX_C + 1].to(self.device))
+        self.sessions[sid] = _Session(sid, slot, RingBook(self.R, self.T, self.S, 0 if given is not None else self.warm), self)
+
+    def close(self, sid):
+        """Ends session `sid`; its slot of the pool is free for the next open()."""
+        self.free.append(self._session(sid).slot)
+        self.free.sort()
+        del self.sessions[sid]
+
+    def _session(self, sid) -> _Session:
+        if sid not in self.sessions:
+            raise ValueError(f"no open session {sid!r}")
+        return self.sessions[sid]
+
+    # ---- push -------------------------------------------------------------------------------------------------------------------
+    def _samples(self, x):
+        if isinstance(x, np.ndarray):
+            x = np.ascontiguousarray(x, dtype=np.float64)
+        elif not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != self.device or x.dtype != torch.float64:
+            raise ValueError("samples are a (n, C_all) float64 array: numpy, or a tensor on the monitor's GPU (there is no CPU fallback)")
+        if x.ndim != 2 or x.shape[1] != self.C_all:
+            raise ValueError(f"samples are (n, {self.C_all}) — the columns {self.names} — got {tuple(x.shape)}")
+        return x
+
+    @torch.no_grad()
+    def push(self, samples, chunk=None) -> Union[Dict[object, List[LiveUpdate]], List[LiveUpdate]]:
+        """push({sid: samples, ...}) -> {sid: [LiveUpdate, ...]}; push(sid, samples) -> [LiveUpdate, ...].  Everything is checked
+        before anything is appended."""
+        single = chunk is not None or not isinstance(samples, dict)
+        if single:
+            if chunk is None:
+                raise ValueError("push takes {sid: samples} or (sid, samples)")
+            samples = {samples: chunk}
+        todo = [(self._session(sid), self._samples(x)) for sid, x in samples.items()]
+        out: Dict[object, List[LiveUpdate]] = {sid: [] for sid in samples}
+        at = [0] * len(todo)
+        lib = L.lib()
+        while True:
+            seg = [(j, s, s.book.segment(x.shape[0] - at[j])) for j, (s, x) in enumerate(todo) if x.shape[0] > at[j]]
+            if not seg:
+                break
+            parts = [todo[j][1][at[j]:at[j] + a] for j, _s, a in seg]
+            if all(isinstance(p, np.ndarray) for p in parts):                  # one upload of the round's chunks, back to back
+                staging = torch.from_numpy(np.concatenate(parts) if len(parts) > 1 else parts[0]).to(self.device)
+            else:
+                staging = torch.cat([torch.from_numpy(p).to(self.device) if isinstance(p, np.ndarray) else p for p in parts]).contiguous()
+            n = len(seg)
+            L.check(lib.msig_lv_push(*self._pool_args(), (C.c_int32 * n)(*[s.slot for _j, s, _a in seg]),
+                                     (C.c_int64 * n)(*[s.book.written for _j, s, _a in seg]), (C.c_int64 * n)(*[a for _j, _s, a in seg]), n,
+                                     staging.data_ptr(), self._stream()), "msig_lv_push")
+            rows, owners = [], []
+            for j, s, a in seg:
+                at[j] += a
+                due, windows = s.book.advance(a)
+                if due:          # the head span lies unwrapped at the ring's start: the offline call's statistics (RingBook)
+                    L.check(lib.msig_rec_stats(self.pool[s.slot].data_ptr(), s.book.head, self.C_all, self.cols, self.ensemble.C, self.mask,
+                                               self.T, self.S, 0, s.book.warm, self.stats[s.slot].data_ptr(), self.scratch.data_ptr(),
+                                               self._stream()), "msig_rec_stats")
+                rows += [(s.slot, w, s.book.written) for w in windows]
+                owners += [s] * len(windows)
+            if rows:
+                self._evaluate(rows, owners, out)
+        return out[next(iter(samples))] if single else out
+
+    def _evaluate(self, rows, owners: List[_Session], out):
+        p = self.ensemble.predict(LiveBatch(self, rows))
+        host = {k: getattr(p, k).cpu().numpy() for k in FIELDS}
+        for b, s in enumerate(owners):
+            n = rows[b][1]
+            for k in FIELDS:
+                s.rows[k].append(host[k][b].copy())
+            score = float(host["mean_p"][b, self.positive].astype(np.float64))
+            smoothed = s.smoother.push(score)
+            on, alarm = s.machine.step(smoothed)
+            t_end = lambda w: (float(w) * self.S + self.T) / self.fs      # noqa: E731
+            if alarm is not None:
+                alarm = Alarm(alarm.kind, alarm.window, alarm.start_window, t_end(alarm.window), t_end(alarm.start_window))
+                s.alarms.append(alarm)
+            s.score.append(score)
+            s.smoothed.append(smoothed)
+            out[s.sid].append(LiveUpdate(sid=s.sid, window=int(n), t_end=t_end(n), score=score, std=float(host["std_p"][b, self.positive]),
+                                         entropy=float(host["entropy"][b]), mutual_info=float(host["mutual_info"][b]), pred=int(host["pred"][b]),
+                                         smoothed=smoothed, warmup=n < s.book.warm, on=on, alarm=alarm))
+
+    # ---- what a session has reported so far -------------------------------------------------------------------------------------
+    def alarms(self, sid) -> List[Alarm]:
+        return list(self._session(sid).alarms)
+
+    def session_stats(self, sid) -> torch.Tensor:
+        """The statistics of session `sid` on the device (undefined while its warm-up is pending)."""
+        return self.stats[self._session(sid).slot]
+
+    def timeline(self, sid) -> Timeline:
+        """The Timeline of everything pushed to `sid` so far, Monitor.run's fields: state and events by the offline rule."""
+        s = self._session(sid)
+        n, K, M = len(s.score), self.ensemble.K, self.ensemble.M
+        empty = dict(mean_p=((0, K), np.float32), std_p=((0, K), np.float32), pred=((0,), np.int32), entropy=((0,), np.float32),
+                     mutual_info=((0,), np.float32), votes=((0, K), np.int32))
+        f = {k: np.stack(s.rows[k]) if n else np.zeros(*empty[k]) for k in FIELDS}
+        score, smoothed = np.array(s.score, dtype=np.float64), np.array(s.smoothed, dtype=np.float64)
+        t_end = (np.arange(n, dtype=np.float64) * self.S + self.T) / self.fs
+        state = hysteresis(smoothed, self.on, self.off, self.min_on)
+        meta = dict(fs=self.fs, window_samples=self.T, stride_samples=self.S, members=M, positive=self.positive, halflife=self.halflife,
+                    on=self.on, off=self.off, min_on=self.min_on, samples=s.book.written,
+                    reference="statistics" if s.given else self.reference, warmup_windows=int(s.book.warm),
+                    files=[str(p) for p in self.files])
+        return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.book.warm,
+                        events=find_events(state, smoothed, t_end), meta=meta, **f)
+
+
+def timelines_equal(a: Timeline, b: Timeline) -> bool:
+    """Every per-window field of two timelines bit for bit, and their events."""
+    for k in ("t_end", "mean_p", "std_p", "pred", "entropy", "mutual_info", "votes", "score", "smoothed", "state", "warmup"):
+        x, y = getattr(a, k), getattr(b, k)
+        if x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes():
+            return False
+    return a.events == b.events
+
+
+# ---- the command line ----------------------------------------------------------------------------------------------------------------
+def build_parser():
+    ap = _monitor_parser()
+    ap.prog = "python -m multimodalsignal_amd.live"
+    ap.description = ("Replays a recording into N live sessions in chunks, out of phase: timeline.csv / timeline.json of session 0 (the files "
+                      "monitor writes for the recording), alarms.json, and whether session 0's timeline equals Monitor.run's bit for bit.")
+    ap.add_argument("--sessions", type=int, default=1, help="live sessions fed with the recording; session k starts k chunks late")
+    ap.add_argument("--chunk-s", type=float, default=2.5, help="seconds of samples per push and session")
+    ap.set_defaults(reference="head:6")
+    return ap
+
+
+def parse_args(argv=None):
+    """The arguments, checked before anything touches the GPU."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.synthetic_recording == (a.recording is not None):
+        ap.error("give exactly one of --recording X.npy and --synthetic-recording")
+    if a.recording is not None and a.names is None:
+        ap.error("--recording needs --names FILE (one channel name per line)")
+    if a.synthetic_recording and (a.names is not None or a.resample_from is not None):
+        ap.error("--synthetic-recording takes neither --names nor --resample-from")
+    if not a.fs > 0 or (a.resample_from is not None and not a.resample_from > 0):
+        ap.error("--fs and --resample-from must be > 0")
+    if not a.window_s > 0 or not a.stride_s > 0 or not a.chunk_s > 0:
+        ap.error("--window-s, --stride-s and --chunk-s must be > 0")
+    if not 1 <= a.sessions <= L.LV_MAX_SESSIONS:
+        ap.error(f"--sessions must be in 1..{L.LV_MAX_SESSIONS}")
+    if not (isinstance(a.reference, str) and a.reference.startswith("head:")):
+        ap.error("a live --reference is head:K ('recording' is not causal)")
+    try:
+        parse_recording_reference(a.reference, 1 << 62)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def main(argv=None) -> Timeline:
+    a = parse_args(argv)
+    live = LiveMonitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference,
+                                max_sessions=a.sessions)
+    table = None
+    if a.synthetic_recording:
+        from .synth import CHANNELS6, make_synthetic_recording
+        names = list(CHANNELS6)
+        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty)
+    else:
+        sig = np.load(a.recording)
+        names = [ln.strip() for ln in a.names.read_text().splitlines() if ln.strip()]
+    sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float64)).to(live.device)
+    if a.resample_from is not None:
+        from .preprocess import resample_device
+        sig = resample_device(sig, int(sig.shape[0] * (a.fs / a.resample_from)))
+    chunk = max(1, int(round(a.chunk_s * a.fs)))
+    ticks = -(-int(sig.shape[0]) // chunk)
+    for k in range(a.sessions):
+        live.open(k, names)
+    for t in range(ticks + a.sessions - 1):          # session k is k chunks behind session 0
+        live.push({k: sig[(t - k) * chunk:(t - k + 1) * chunk] for k in range(a.sessions) if 0 <= t - k < ticks})
+    tl = live.timeline(0)
+    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, channels=live.channels)
+    equal = timelines_equal(tl, offline.run(sig, names))
+    if table is not None:
+        tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, live.T, live.S))
+    a.out.mkdir(parents=True, exist_ok=True)
+    tl.to_csv(a.out / "timeline.csv")
+    path = tl.to_json(a.out / "timeline.json")
+    (a.out / "alarms.json").write_text(json.dumps({str(k): [asdict(al) for al in live.alarms(k)] for k in range(a.sessions)}, indent=1))
+    print(f"{a.sessions} sessions, {ticks} pushes of {chunk} samples each; session 0: {len(tl.t_end)} windows, {int(tl.state.sum())} flagged, "
+          f"{len(tl.events)} events, {len(live.alarms(0))} alarms; timeline written to: {path}")
+    print(f"session 0's timeline and Monitor.run's for the same recording: {'equal' if equal else 'NOT EQUAL'} bit for bit")
+    if table is not None:
+        print("NOTE: " + SYNTHETIC_NOTE + ".")
+    return tl
+
+
+if __name__ == "__main__":
+    main()

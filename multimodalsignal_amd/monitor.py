@@ -9,8 +9,8 @@ msig_rec_windows_multi) and turns the positive class's probability into a smooth
 The host helpers (`parse_recording_reference`, `ema`, `hysteresis`, `find_events`, `Timeline`, the CLI's argument checks) need no
 GPU (`count_windows` asks the library, which loads without one).  `RecordingWindows` and `Monitor.run` have no CPU fallback.
 
-Out of scope: a live push(samples) interface, sharing the front end between overlapping windows (not exact: the channel gate is a
-mean over ONE window and the convolutions pad at ITS edges) and the hand-crafted feature branch.
+Out of scope: sharing the front end between overlapping windows (not exact: the channel gate is a mean over ONE window and the
+convolutions pad at ITS edges) and the hand-crafted feature branch.  The live push(samples) interface is live.py.
 
 CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
       --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K] [--stride-s 10] --out DIR
