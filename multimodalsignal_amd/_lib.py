@@ -1,6 +1,6 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
 include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h, include/msig_sc.h, include/msig_nr.h,
-include/msig_rec.h, include/msig_lv.h).
+include/msig_rec.h, include/msig_lv.h, include/msig_rn.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -122,6 +122,8 @@ NR_ABI_VERSION = 1    # include/msig_nr.h MSIG_NR_ABI_VERSION (per-subject norma
 REC_ABI_VERSION = 1   # include/msig_rec.h MSIG_REC_ABI_VERSION (statistics and normalised window batches straight from a continuous recording)
 LV_ABI_VERSION = 1    # include/msig_lv.h MSIG_LV_ABI_VERSION (a pool of sample rings and window batches whose rows come from different sessions)
 LV_MAX_SESSIONS = 4096        # MSIG_LV_MAX_SESSIONS
+RN_ABI_VERSION = 1    # include/msig_rn.h MSIG_RN_ABI_VERSION (causal running references: a statistics record per window, offline and live)
+RN_MAX_K = 4096               # MSIG_RN_MAX_K
 
 
 class Sc(C.Structure):
@@ -496,6 +498,19 @@ def lib() -> C.CDLL:
         L.msig_lv_push.argtypes = pool + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
         L.msig_lv_windows_multi.argtypes = pool + [C.POINTER(i32), i32, C.c_uint32, i64, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32,
                                                    vp, vp, C.POINTER(Multi), vp]
+        # include/msig_rn.h, exported by the same library: window sums, a statistics record per window, batches with a record per row
+        L.msig_rn_abi_version.restype = C.c_int
+        if L.msig_rn_abi_version() != RN_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_rn.h ABI {L.msig_rn_abi_version()}; this binding is {RN_ABI_VERSION}: rebuild the library")
+        L.msig_rn_state_bytes.argtypes = [i32]
+        L.msig_rn_state_bytes.restype = C.c_int64
+        L.msig_rn_sums.argtypes = rec + [i64, i64, vp, vp]
+        L.msig_rn_stats.argtypes = rec + [vp, i64, i32, vp, vp]
+        L.msig_rn_windows.argtypes = rec + [i64, i32, vp, vp, vp]
+        L.msig_rn_windows_multi.argtypes = rec + [i64, i32, vp, vp, C.POINTER(Multi), vp]
+        rows = [C.POINTER(i32), i32, C.c_uint32, i64, i64]                    # cols, C, log1p_mask, T, S
+        L.msig_rn_lv_step.argtypes = pool + rows + [i32, vp, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
+        L.msig_rn_lv_windows_multi.argtypes = pool + rows + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp, C.POINTER(Multi), vp]
         _lib = L
     return _lib
 

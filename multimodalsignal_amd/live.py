@@ -5,8 +5,11 @@ A wearable delivers a few seconds of samples at a time, and one GPU serves many 
 that became complete across all sessions, and runs them through the ensemble as mixed batches of at most `eval_batch` rows: one
 msig_lv_windows_multi, one msig_st_forward_multi and one msig_en_reduce_multi per piece and member chunk, on `Ensemble`'s own
 forward and reduction code (`LiveEnsemble` overrides the filling of the arenas, as monitor.RecordingEnsemble does, and their size).  What a
-session reports equals, bit for bit, what `Monitor.run` reports for the same samples as one recording: a "head:K" reference is
-causal, a row's eval bits do not depend on its batch, and the smoothing is `monitor.ema`'s recurrence continued.
+session reports equals, bit for bit, what `Monitor.run` reports for the same samples as one recording, under every causal reference:
+"head:K", and the running references "expanding" and "trailing:K" (include/msig_rn.h), whose statistics follow
+the wearer: a per-session state block on the device, one msig_rn_lv_step per piece that forms each new window's sums from the ring
+and its statistics record, and msig_rn_lv_windows_multi, which normalises every row with its own record.  A row's eval bits do not
+depend on its batch, and the smoothing is `monitor.ema`'s recurrence continued.
 
 The offline state drops episodes shorter than `min_on` after the fact; a live system cannot take back an alarm.  So an `onset` alarm
 is raised at the window where a run of the raw hysteresis state reaches `min_on` windows (it carries the run's first window), and an
@@ -16,11 +19,12 @@ so far.
 
 The host parts (`Smoother`, `AlarmMachine`, `RingBook`, the CLI's argument checks) need no GPU.  `LiveMonitor` has no CPU fallback.
 
-Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py), drifting or re-estimated statistics
-(a session's statistics are fixed once its head is complete), and any network or serial front end — push() is the interface.
+Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py), decayed (EMA) statistics, training
+under a matching causal normalisation (--norm-reference has no expanding or trailing form), and any network or serial front end —
+push() is the interface.
 
 CLI:  python -m multimodalsignal_amd.live --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6] --out DIR
+      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]] --out DIR
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ import torch
 from . import _lib as L
 from .ensemble import Ensemble, load_members
 from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, ema, find_events, hysteresis,
-                      parse_recording_reference, phase_shares)
+                      parse_recording_reference, phase_shares, running_reference)
 
 FIELDS = ("mean_p", "std_p", "pred", "entropy", "mutual_info", "votes")      # what a session stores per window, as Ensemble.predict gives it
 
@@ -189,11 +193,38 @@ class LiveBatch:
         self.written = np.ascontiguousarray([r[2] for r in rows], dtype=np.int64)
         self.C, self.T = monitor.ensemble.C, monitor.T
         self.shape = (len(rows), self.C, self.T)
+        self.table, self.stepped = None, set()
+        if monitor.running is not None:          # a statistics record per row, written by msig_rn_lv_step piece by piece
+            self.table = torch.zeros((len(rows), 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
 
-    def fill(self, x0: int, multi: L.Multi, i: int, b: int):
-        """Rows i .. i + b - 1 into the x buffer of every arena slot of `multi`; x0 is arena 0's (msig_lv_windows_multi)."""
+    def _step(self, i: int, b: int):
+        """msig_rn_lv_step for rows i .. i + b - 1, once: the sessions' states advance in row order (a piece is filled once per
+        member chunk, and the pieces of the first chunk come in row order)."""
+        if i in self.stepped:
+            return
         mon = self.monitor
         p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        nxt = np.ascontiguousarray([mon.rn_next[int(s)] for s in self.sess[i:i + b]], dtype=np.int64)
+        L.check(L.lib().msig_rn_lv_step(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, mon.running[0], mon.rn_state.data_ptr(),
+                                        mon.rn_state.shape[1] * 8, self.sess[i:].ctypes.data_as(p32), self.win[i:].ctypes.data_as(p64),
+                                        self.written[i:].ctypes.data_as(p64), nxt.ctypes.data_as(p64), int(b), self.table[i].data_ptr(),
+                                        mon._stream()), "msig_rn_lv_step")
+        self.stepped.add(i)
+        for r in range(i, i + b):
+            mon.rn_next[int(self.sess[r])] += 1
+            mon.rn_latest[int(self.sess[r])] = self.table[r]
+
+    def fill(self, x0: int, multi: L.Multi, i: int, b: int):
+        """Rows i .. i + b - 1 into the x buffer of every arena slot of `multi`; x0 is arena 0's (msig_lv_windows_multi, or under a
+        running reference msig_rn_lv_step and msig_rn_lv_windows_multi)."""
+        mon = self.monitor
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        if self.table is not None:
+            self._step(i, b)
+            L.check(L.lib().msig_rn_lv_windows_multi(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, self.sess[i:].ctypes.data_as(p32),
+                                                     self.win[i:].ctypes.data_as(p64), self.written[i:].ctypes.data_as(p64), int(b),
+                                                     self.table[i].data_ptr(), x0, C.byref(multi), mon._stream()), "msig_rn_lv_windows_multi")
+            return
         L.check(L.lib().msig_lv_windows_multi(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, self.sess[i:].ctypes.data_as(p32),
                                               self.win[i:].ctypes.data_as(p64), self.written[i:].ctypes.data_as(p64), int(b),
                                               mon.stats.data_ptr(), x0, C.byref(multi), mon._stream()), "msig_lv_windows_multi")
@@ -224,7 +255,8 @@ class _Session:
     def __init__(self, sid, slot: int, book: RingBook, mon: "LiveMonitor"):
         self.sid, self.slot, self.book = sid, slot, book
         self.smoother, self.machine = Smoother(mon.halflife), AlarmMachine(mon.on, mon.off, mon.min_on)
-        self.given = book.warm == 0
+        self.given = book.warm == 0 and mon.running is None
+        self.flagged = mon.running[1] if mon.running is not None else book.warm      # leading windows flagged warmup
         self.rows: Dict[str, list] = {k: [] for k in FIELDS}
         self.score: List[float] = []
         self.smoothed: List[float] = []
@@ -235,8 +267,10 @@ class LiveMonitor:
     """An ensemble of 1..256 trained models over up to `max_sessions` live sessions sampled at `fs` Hz: windows of `window_s` seconds
     every `stride_s`, a ring of `ring_s` seconds per session (None: the head span or one window, plus 8 strides), `eval_batch` rows
     per piece.  `reference`: "head:K" — a session's first K windows supply its statistics and are emitted together, flagged warmup,
-    when window K - 1 completes — or a float64 statistics tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.
-    "recording" is refused: it is not causal.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.
+    when window K - 1 completes — "expanding[:W]" or "trailing:K[:W]" (monitor.running_reference) — window n is normalised with
+    windows 0..n or with the last K, emitted in the push that completes it, the first W flagged warmup — or a float64 statistics
+    tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.  "recording" is refused: it is not causal; "expanding" is
+    its causal counterpart.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.
 
     open(sid, names, stats=None) / close(sid); push({sid: samples}) or push(sid, samples); timeline(sid); alarms(sid)."""
 
@@ -255,8 +289,12 @@ class LiveMonitor:
             self.warm = 0
         elif isinstance(reference, str) and reference.startswith("head:"):
             self.warm = parse_recording_reference(reference, 1 << 62)[2]
+        elif running_reference(reference) is not None:
+            self.warm = 0                        # no delay: a window's statistics are complete with the window
         else:
-            raise ValueError(f"a live reference is 'head:K' or a statistics tensor (anything else is not causal), got {reference!r}")
+            raise ValueError("a live reference is 'head:K', 'expanding[:W]', 'trailing:K[:W]' or a statistics tensor (anything else is not "
+                             f"causal; 'expanding' is the causal counterpart of 'recording'), got {reference!r}")
+        self.running = running_reference(reference)
         if isinstance(max_sessions, bool) or not 1 <= int(max_sessions) <= L.LV_MAX_SESSIONS:
             raise ValueError(f"max_sessions must be an integer in 1..{L.LV_MAX_SESSIONS}, got {max_sessions!r}")
         head = (self.warm - 1) * self.S + self.T if self.warm else self.T
@@ -283,6 +321,10 @@ class LiveMonitor:
         self.stats = torch.zeros((self.max_sessions, 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
         self.scratch = torch.empty(L.lib().msig_rec_scratch_bytes(), dtype=torch.uint8, device=self.device)
         self.pool = None
+        if self.running is not None:             # per session: the pivot, the expanding carry and the ring of the last K window sums
+            self.rn_state = torch.zeros((self.max_sessions, L.lib().msig_rn_state_bytes(self.running[0]) // 8), dtype=torch.float64, device=self.device)
+            self.rn_next = [0] * self.max_sessions               # the host's mirror of every state's next expected window
+            self.rn_latest: Dict[int, torch.Tensor] = {}         # slot -> the session's latest statistics record
 
     @classmethod
     def from_run(cls, run_dir, subject: Optional[str] = None, config_name: Optional[str] = None, fs: float = 64.0, device="cuda", **kw) -> "LiveMonitor":
@@ -327,9 +369,13 @@ class LiveMonitor:
         given = stats if stats is not None else (self.reference if isinstance(self.reference, torch.Tensor) else None)
         if given is not None and (not isinstance(given, torch.Tensor) or given.dtype != torch.float64 or given.numel() < 2 * L.MAX_C + 1):
             raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
+        if given is not None and self.running is not None:
+            raise ValueError(f"a monitor with the running reference {self.reference!r} takes no given statistics")
         if not self.free:
             raise ValueError(f"all {self.max_sessions} sessions of the pool are open")
         slot = self.free.pop(0)
+        if self.running is not None:
+            self._reset_state(slot)
         if given is not None:
             self.stats[slot].copy_(given.reshape(-1)[:2 * L.MAX_C + 1].to(self.device))
         self.sessions[sid] = _Session(sid, slot, RingBook(self.R, self.T, self.S, 0 if given is not None else self.warm), self)
@@ -338,7 +384,14 @@ class LiveMonitor:
         """Ends session `sid`; its slot of the pool is free for the next open()."""
         self.free.append(self._session(sid).slot)
         self.free.sort()
+        if self.running is not None:
+            self._reset_state(self._session(sid).slot)
         del self.sessions[sid]
+
+    def _reset_state(self, slot: int):
+        self.rn_state[slot].zero_()
+        self.rn_next[slot] = 0
+        self.rn_latest.pop(slot, None)
 
     def _session(self, sid) -> _Session:
         if sid not in self.sessions:
@@ -413,14 +466,17 @@ class LiveMonitor:
             s.smoothed.append(smoothed)
             out[s.sid].append(LiveUpdate(sid=s.sid, window=int(n), t_end=t_end(n), score=score, std=float(host["std_p"][b, self.positive]),
                                          entropy=float(host["entropy"][b]), mutual_info=float(host["mutual_info"][b]), pred=int(host["pred"][b]),
-                                         smoothed=smoothed, warmup=n < s.book.warm, on=on, alarm=alarm))
+                                         smoothed=smoothed, warmup=n < s.flagged, on=on, alarm=alarm))
 
     # ---- what a session has reported so far -------------------------------------------------------------------------------------
     def alarms(self, sid) -> List[Alarm]:
         return list(self._session(sid).alarms)
 
     def session_stats(self, sid) -> torch.Tensor:
-        """The statistics of session `sid` on the device (undefined while its warm-up is pending)."""
+        """The statistics of session `sid` on the device (undefined while its warm-up is pending); under a running reference the
+        latest window's record (None before the first window)."""
+        if self.running is not None:
+            return self.rn_latest.get(self._session(sid).slot)
         return self.stats[self._session(sid).slot]
 
     def timeline(self, sid) -> Timeline:
@@ -435,9 +491,11 @@ class LiveMonitor:
         state = hysteresis(smoothed, self.on, self.off, self.min_on)
         meta = dict(fs=self.fs, window_samples=self.T, stride_samples=self.S, members=M, positive=self.positive, halflife=self.halflife,
                     on=self.on, off=self.off, min_on=self.min_on, samples=s.book.written,
-                    reference="statistics" if s.given else self.reference, warmup_windows=int(s.book.warm),
+                    reference="statistics" if s.given else self.reference, warmup_windows=int(s.flagged),
                     files=[str(p) for p in self.files])
-        return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.book.warm,
+        if self.running is not None:
+            meta["reference_window_counts"] = [k + 1 if self.running[0] == 0 else min(k + 1, self.running[0]) for k in range(n)]
+        return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.flagged,
                         events=find_events(state, smoothed, t_end), meta=meta, **f)
 
 
@@ -478,9 +536,10 @@ def parse_args(argv=None):
         ap.error("--window-s, --stride-s and --chunk-s must be > 0")
     if not 1 <= a.sessions <= L.LV_MAX_SESSIONS:
         ap.error(f"--sessions must be in 1..{L.LV_MAX_SESSIONS}")
-    if not (isinstance(a.reference, str) and a.reference.startswith("head:")):
-        ap.error("a live --reference is head:K ('recording' is not causal)")
     try:
+        if not (isinstance(a.reference, str) and a.reference.startswith("head:")) and running_reference(a.reference) is None:
+            ap.error("a live --reference is head:K, expanding[:W] or trailing:K[:W] ('recording' is not causal; 'expanding' is its causal "
+                     "counterpart)")
         parse_recording_reference(a.reference, 1 << 62)
     except ValueError as e:
         ap.error(str(e))

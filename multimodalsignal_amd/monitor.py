@@ -12,8 +12,12 @@ GPU (`count_windows` asks the library, which loads without one).  `RecordingWind
 Out of scope: sharing the front end between overlapping windows (not exact: the channel gate is a mean over ONE window and the
 convolutions pad at ITS edges) and the hand-crafted feature branch.  The live push(samples) interface is live.py.
 
+Causal running references (include/msig_rn.h): "expanding" normalises window n with windows 0..n, "trailing:K"
+with the last K — a statistics record per window (one msig_rn_sums, one msig_rn_stats) and batches whose every row has its own
+record (msig_rn_windows[_multi]).
+
 CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K] [--stride-s 10] --out DIR
+      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K|expanding[:W]|trailing:K[:W]] [--stride-s 10] --out DIR
 """
 from __future__ import annotations
 
@@ -46,27 +50,54 @@ def count_windows(L_: int, T: int, S: int) -> int:
     return n
 
 
+REFERENCE_FORMS = ("'recording', 'head:K' with K >= 1, 'expanding[:W]', 'trailing:K[:W]' with K in 1..%d and W >= 0, a (w0, w1) pair or a "
+                   "statistics tensor" % L.RN_MAX_K)
+RUNNING_WARMUP = 6          # windows a running reference flags `warmup` by default: head:6's count
+
+
+def running_reference(reference) -> Optional[Tuple[int, int]]:
+    """(K, W) of a causal running reference — "expanding" / "expanding:W" (K = 0: window n is normalised with windows 0..n) or
+    "trailing:K" / "trailing:K:W" (with the last K, 1 <= K <= RN_MAX_K); W >= 0 leading windows are flagged `warmup` (default 6).
+    None for anything that is not spelled as one; ValueError for one that is spelled wrongly."""
+    if not isinstance(reference, str) or reference.split(":")[0] not in ("expanding", "trailing"):
+        return None
+    kind, *rest = reference.split(":")
+    want = 0 if kind == "expanding" else 1
+    ok = want <= len(rest) <= want + 1 and all(v.isascii() and v.isdigit() for v in rest)
+    if ok:
+        K = int(rest[0]) if want else 0
+        W = int(rest[want]) if len(rest) > want else RUNNING_WARMUP
+        if not want or 1 <= K <= L.RN_MAX_K:
+            return K, W
+    raise ValueError(f"reference must be {REFERENCE_FORMS}, got {reference!r}")
+
+
 def parse_recording_reference(reference, n: int):
     """Which windows supply a recording's mean and std: "recording" (all of them: the counterpart of training's --norm-reference
     subject), "head:K" (the first K >= 1: the counterpart of baseline:K, 60 + 10 (K - 1) seconds at the default window and
     stride) or a pair (w0, w1) of window indices, 0 <= w0 < w1 <= n.  Returns (w0, w1, warm-up windows) — the warm-up count is K
-    for "head:K" and 0 otherwise.  A tensor of statistics is not parsed here (RecordingWindows takes it as it is)."""
+    for "head:K" and 0 otherwise.  A running reference (running_reference: "expanding[:W]", "trailing:K[:W]") has statistics per
+    window: it returns (0, n, W), the windows any row may draw on and the number flagged.  A tensor of statistics is not parsed here
+    (RecordingWindows takes it as it is)."""
     if reference == "recording":
         return 0, int(n), 0
+    run = running_reference(reference)
+    if run is not None:
+        return 0, int(n), run[1]
     if isinstance(reference, str) and reference.startswith("head:"):
         k = reference[len("head:"):]
         if k.isascii() and k.isdigit() and int(k) >= 1:
             if int(k) > n:
                 raise ValueError(f"reference {reference!r} needs {int(k)} windows; the recording has {n}")
             return 0, int(k), int(k)
-        raise ValueError(f"reference must be 'recording', 'head:K' with K >= 1, a (w0, w1) pair or a statistics tensor, got {reference!r}")
+        raise ValueError(f"reference must be {REFERENCE_FORMS}, got {reference!r}")
     if isinstance(reference, (tuple, list)) and len(reference) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool)
                                                                              for v in reference):
         w0, w1 = int(reference[0]), int(reference[1])
         if not 0 <= w0 < w1 <= n:
             raise ValueError(f"reference windows must satisfy 0 <= w0 < w1 <= {n}, got {reference!r}")
         return w0, w1, 0
-    raise ValueError(f"reference must be 'recording', 'head:K' with K >= 1, a (w0, w1) pair or a statistics tensor, got {reference!r}")
+    raise ValueError(f"reference must be {REFERENCE_FORMS}, got {reference!r}")
 
 
 def ema(score, halflife: float) -> np.ndarray:
@@ -125,8 +156,9 @@ def find_events(state, smoothed, t_end) -> List[Tuple[float, float, float, float
 class Timeline:
     """What Monitor.run returns, on the host: per window its end time t_end = (n S + T) / fs in seconds, the ensemble's mean_p and
     std_p (N, K), pred, entropy, mutual_info (N,), votes (N, K), score = mean_p[:, positive], smoothed (float64), state (bool),
-    warmup (bool: the window supplied the statistics of a "head:K" reference); `events` as find_events lists them; `meta` the
-    settings."""
+    warmup (bool: the window supplied the statistics of a "head:K" reference, or is one of a running reference's first W); `events`
+    as find_events lists them; `meta` the settings (under a running reference also reference_window_counts: per window the number
+    of windows its statistics were taken over)."""
     t_end: np.ndarray
     mean_p: np.ndarray
     std_p: np.ndarray
@@ -176,7 +208,8 @@ class RecordingWindows:
     `names`, of which `channels` are selected in that order; the channel literally named 'chest_EDA' is log1p-transformed first, as
     in dataset.normalise_subject_device.  `reference`: parse_recording_reference, or a float64 tensor of 2 * MAX_C + 1 statistics
     (msig_nr.h's layout) taken as it is.  `.n` windows, `.shape` = (n, C, T), `.stats` the statistics on the device, `.warmup` the
-    number of leading windows that supplied them ("head:K")."""
+    number of leading windows that supplied them ("head:K").  Under a running reference (running_reference) `.stats` is the
+    (n, 2 * MAX_C + 1) table of one record per window, `.running` = (K, W) and `.warmup` = W, the windows flagged."""
 
     def __init__(self, sig, names: Sequence[str], channels: Sequence[str], T: int, stride: int,
                  reference: Union[str, tuple, torch.Tensor] = "recording", device="cuda"):
@@ -201,7 +234,15 @@ class RecordingWindows:
         self.shape = (self.n, self.C, self.T)
         self.cols = (C.c_int32 * self.C)(*[names.index(c) for c in channels])
         self.mask = sum(1 << c for c, name in enumerate(channels) if name == "chest_EDA")
-        if isinstance(reference, torch.Tensor):
+        self.running = running_reference(reference)
+        if self.running is not None:            # a record per window: the windows' own sums, then their ordered sums (msig_rn.h)
+            self.reference_windows, self.warmup = None, self.running[1]
+            sums = torch.empty((self.n, 2 * L.MAX_C), dtype=torch.float64, device=self.device)
+            self.stats = torch.zeros((self.n, 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
+            L.check(L.lib().msig_rn_sums(*self._head(), 0, self.n, sums.data_ptr(), self._stream()), "msig_rn_sums")
+            L.check(L.lib().msig_rn_stats(*self._head(), sums.data_ptr(), self.n, self.running[0], self.stats.data_ptr(), self._stream()),
+                    "msig_rn_stats")
+        elif isinstance(reference, torch.Tensor):
             if reference.dtype != torch.float64 or reference.numel() < 2 * L.MAX_C + 1:
                 raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
             self.stats, self.reference_windows, self.warmup = reference.to(self.device).contiguous().clone(), None, 0
@@ -218,18 +259,32 @@ class RecordingWindows:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _rows(self, n0: int, B: int):
+        if not (0 <= int(n0) and int(B) >= 1 and int(n0) + int(B) <= self.n):          # the table's row is addressed before the library checks
+            raise ValueError(f"windows {n0} .. {int(n0) + int(B) - 1} are not all among the recording's {self.n}")
+
     def batch(self, n0: int, B: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Windows n0 .. n0 + B - 1 as a (B, C, T) float32 tensor (msig_rec_windows)."""
         if out is None:
             out = torch.empty((int(B), self.C, self.T), dtype=torch.float32, device=self.device)
         elif out.dtype != torch.float32 or tuple(out.shape) != (int(B), self.C, self.T) or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"out must be a contiguous float32 ({B}, {self.C}, {self.T}) tensor on {self.device}")
+        if self.running is not None:
+            self._rows(n0, B)
+            L.check(L.lib().msig_rn_windows(*self._head(), int(n0), int(B), self.stats[int(n0)].data_ptr(), out.data_ptr(), self._stream()),
+                    "msig_rn_windows")
+            return out
         L.check(L.lib().msig_rec_windows(*self._head(), int(n0), int(B), self.stats.data_ptr(), out.data_ptr(), self._stream()),
                 "msig_rec_windows")
         return out
 
     def fill(self, x0: int, multi: L.Multi, n0: int, B: int):
         """Windows n0 .. n0 + B - 1 into the x buffer of every arena slot of `multi`; x0 is arena 0's (msig_rec_windows_multi)."""
+        if self.running is not None:
+            self._rows(n0, B)
+            L.check(L.lib().msig_rn_windows_multi(*self._head(), int(n0), int(B), self.stats[int(n0)].data_ptr(), x0, C.byref(multi),
+                                                  self._stream()), "msig_rn_windows_multi")
+            return
         L.check(L.lib().msig_rec_windows_multi(*self._head(), int(n0), int(B), self.stats.data_ptr(), x0, C.byref(multi), self._stream()),
                 "msig_rec_windows_multi")
 
@@ -334,6 +389,8 @@ class Monitor:
                     reference=self.reference if isinstance(self.reference, str) else ("statistics" if rw.reference_windows is None
                                                                                       else list(rw.reference_windows)),
                     warmup_windows=int(rw.warmup), files=[str(f) for f in self.files])
+        if rw.running is not None:
+            meta["reference_window_counts"] = [int(v) for v in rw.stats[:, 2 * L.MAX_C].cpu().numpy()]
         return Timeline(t_end=t_end, mean_p=mean_p, std_p=host(p.std_p), pred=host(p.pred), entropy=host(p.entropy),
                         mutual_info=host(p.mutual_info), votes=host(p.votes), score=score, smoothed=smoothed, state=state, warmup=warmup,
                         events=find_events(state, smoothed, t_end), meta=meta)
@@ -351,7 +408,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--synthetic-recording", action="store_true", help="a seeded 40-minute recording with planted stress phases")
     ap.add_argument("--fs", type=float, default=64.0, help="sampling rate the models were trained at")
     ap.add_argument("--resample-from", type=float, default=None, help="the recording's own sampling rate: it is resampled to --fs first")
-    ap.add_argument("--reference", default="recording", help="recording | head:K")
+    ap.add_argument("--reference", default="recording", help="recording | head:K | expanding[:W] | trailing:K[:W]")
     ap.add_argument("--window-s", type=float, default=60.0)
     ap.add_argument("--stride-s", type=float, default=10.0)
     ap.add_argument("--seed", type=int, default=42, help="seed of --synthetic-recording")
