@@ -1,6 +1,6 @@
 """ctypes binding of libmsig_hip.so (include/msig.h, include/msig_cw.h, include/msig_cg.h, include/msig_ft.h, include/msig_gc.h,
 include/msig_aug.h, include/msig_st.h, include/msig_ab.h, include/msig_at.h, include/msig_mc.h, include/msig_da.h, include/msig_wa.h, include/msig_en.h, include/msig_kd.h, include/msig_sam.h, include/msig_dro.h, include/msig_sc.h, include/msig_nr.h,
-include/msig_rec.h, include/msig_lv.h, include/msig_rn.h).
+include/msig_rec.h, include/msig_lv.h, include/msig_rn.h, include/msig_rd.h).
 
 There is deliberately no fallback: if the shared library is missing the import
 of anything that computes raises, and every launcher raises RuntimeError on a
@@ -124,6 +124,8 @@ LV_ABI_VERSION = 1    # include/msig_lv.h MSIG_LV_ABI_VERSION (a pool of sample 
 LV_MAX_SESSIONS = 4096        # MSIG_LV_MAX_SESSIONS
 RN_ABI_VERSION = 1    # include/msig_rn.h MSIG_RN_ABI_VERSION (causal running references: a statistics record per window, offline and live)
 RN_MAX_K = 4096               # MSIG_RN_MAX_K
+RD_ABI_VERSION = 1    # include/msig_rd.h MSIG_RD_ABI_VERSION (the exponentially decayed running reference, offline and live)
+RD_MAX_H = 1 << 20            # half-life of a decayed reference in windows at most (the host's limit: the library takes any decay in [0, 1])
 
 
 class Sc(C.Structure):
@@ -511,6 +513,12 @@ def lib() -> C.CDLL:
         rows = [C.POINTER(i32), i32, C.c_uint32, i64, i64]                    # cols, C, log1p_mask, T, S
         L.msig_rn_lv_step.argtypes = pool + rows + [i32, vp, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
         L.msig_rn_lv_windows_multi.argtypes = pool + rows + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp, C.POINTER(Multi), vp]
+        # include/msig_rd.h, exported by the same library: the decayed reference's statistics table and its live step
+        L.msig_rd_abi_version.restype = C.c_int
+        if L.msig_rd_abi_version() != RD_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_rd.h ABI {L.msig_rd_abi_version()}; this binding is {RD_ABI_VERSION}: rebuild the library")
+        L.msig_rd_stats.argtypes = rec + [vp, i64, C.c_double, vp, vp]
+        L.msig_rd_lv_step.argtypes = pool + rows + [C.c_double, vp, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
         _lib = L
     return _lib
 

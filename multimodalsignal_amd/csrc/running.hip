@@ -11,6 +11,7 @@
 // sample's row once and stores the C values into every arena slot; consecutive lanes are consecutive t on the store side.
 #include "msig_dev.h"
 #include "../../include/msig_rn.h"
+#include "../../include/msig_rd.h"
 
 int msig_multi_fold_ctx(const msig_multi* m, FoldCtx& fc);                                  // api.hip: msig_multi's own checks
 
@@ -235,6 +236,71 @@ __global__ __launch_bounds__(256) void rn_lv_step_kernel(const double* __restric
   if (j == 0) { st[RN_NEXT] = (double)(r.n0 + r.count); st[RN_NEXT + 1] = (double)K; }
 }
 
+// ---- the decayed reference (include/msig_rd.h) -------------------------------------------------
+// A_n = fma(decay, A_{n-1}, W_n) per column, c_n = fma(decay, c_{n-1}, 1), A_0 = W_0, c_0 = 1; rn_finalize with n_ref = c_n.
+#define RD_C MSIG_RD_STATE_C            // a session's state: the effective window count c, then the decay of the last step
+static_assert(RD_C > RN_NEXT + 1 && RD_C + 2 <= MSIG_RN_STATE_HEAD, "c and the decay live in the head's reserved doubles");
+
+// one wave scans the N windows: rn_stats_kernel's expanding branch with the decayed recurrence in place of the sum
+__global__ __launch_bounds__(64) void rd_stats_kernel(const double* __restrict__ sig, RnCols cols, int C, uint32_t log1p_mask, double T,
+                                                      const double* __restrict__ sums, int64_t N, double decay, double* __restrict__ table) {
+  const int j = threadIdx.x;
+  const bool on = j < RN_PART && (j & (MSIG_MAX_C - 1)) < C;
+  double p = 0.0;
+  if (j < C) p = rn_value(sig, cols.col[j], (log1p_mask >> j) & 1u);
+  double acc = 0.0, cn = 0.0;
+  for (int64_t n = 0; n < N; n += RN_BLOCK) {
+    double t[RN_BLOCK];
+#pragma unroll
+    for (int q = 0; q < RN_BLOCK; ++q) t[q] = on && n + q < N ? sums[(n + q) * RN_PART + j] : 0.0;
+#pragma unroll
+    for (int q = 0; q < RN_BLOCK; ++q)
+      if (n + q < N) {
+        acc = n + q == 0 ? t[q] : fma(decay, acc, t[q]);
+        cn = n + q == 0 ? 1.0 : fma(decay, cn, 1.0);
+        rn_finalize(acc, p, C, cn, T, table + (n + q) * RN_REC);
+      }
+  }
+}
+
+// run blockIdx.x: rn_lv_step_kernel's expanding branch with the decayed recurrence; every lane of wave 0 carries c, lane 0 stores it
+__global__ __launch_bounds__(256) void rd_lv_step_kernel(const double* __restrict__ pool, int64_t ring_doubles, int64_t R, int C_all, RnCols cols,
+                                                         int C, uint32_t log1p_mask, int64_t T, int64_t S, double decay, double* state_all,
+                                                         int64_t state_doubles, double* __restrict__ table, RnRuns runs) {
+  __shared__ double red[4][RN_PART];
+  __shared__ double w[RN_PART];
+  const RnRun r = runs.e[blockIdx.x];
+  const RnRing ad{pool + (int64_t)r.session * ring_doubles, C_all, R};
+  double* st = state_all + (int64_t)r.session * state_doubles;
+  const bool first = r.n0 == 0;                       // the session starts here: sample 0 is in ring row 0 (window 0 is whole)
+  double pv[MSIG_MAX_C];
+#pragma unroll
+  for (int c = 0; c < MSIG_MAX_C; ++c) {
+    pv[c] = 0.0;
+    if (c < C) pv[c] = first ? rn_value(ad.row(0), cols.col[c], (log1p_mask >> c) & 1u) : st[c];
+  }
+  const int j = threadIdx.x;
+  const bool on = j < RN_PART && (j & (MSIG_MAX_C - 1)) < C;
+  double p = 0.0, acc = 0.0, cn = 0.0;
+  if (j < C) {
+    p = first ? rn_value(ad.row(0), cols.col[j], (log1p_mask >> j) & 1u) : st[j];
+    if (first) st[j] = p;                             // nobody reads st[0 .. C) in a launch that writes it
+  }
+  if (on && !first) acc = st[MSIG_MAX_C + j];
+  if (j < 64 && !first) cn = st[RD_C];                // wave 0 alone reads c, and its lane 0 alone stores it, at the end
+  for (int q = 0; q < r.count; ++q) {
+    const int64_t n = r.n0 + q;
+    rn_window_sums(ad, n * S, T, cols, C, log1p_mask, pv, red, w);
+    if (j < 64) {
+      if (on) acc = n == 0 ? w[j] : fma(decay, acc, w[j]);
+      cn = n == 0 ? 1.0 : fma(decay, cn, 1.0);
+      rn_finalize(acc, p, C, cn, (double)T, table + (int64_t)(r.b0 + q) * RN_REC);
+    }
+  }
+  if (on) st[MSIG_MAX_C + j] = acc;
+  if (j == 0) { st[RN_NEXT] = (double)(r.n0 + r.count); st[RN_NEXT + 1] = 0.0; st[RD_C] = cn; st[RD_C + 1] = decay; }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------
 static int64_t rn_count(int64_t L, int64_t T, int64_t S) { return L < T ? 0 : (L - T) / S + 1; }
 
@@ -268,17 +334,36 @@ extern "C" int msig_rn_sums(const double* sig, int64_t L, int32_t C_all, const i
   return 0;
 }
 
-extern "C" int msig_rn_stats(const double* sig, int64_t L, int32_t C_all, const int32_t* cols, int32_t C, uint32_t log1p_mask, int64_t T,
-                             int64_t S, const double* sums, int64_t N, int32_t K, double* table, void* stream) {
+// the reference's mode: K windows (0: expanding), or — decayed — a decay in [0, 1] (a NaN fails both comparisons)
+struct RnMode { int32_t K; double decay; bool decayed; };
+static bool rn_mode_ok(const RnMode& md) { return md.decayed ? md.decay >= 0.0 && md.decay <= 1.0 : md.K >= 0 && md.K <= MSIG_RN_MAX_K; }
+
+static int rn_stats(const double* sig, int64_t L, int32_t C_all, const int32_t* cols, int32_t C, uint32_t log1p_mask, int64_t T, int64_t S,
+                    const double* sums, int64_t N, const RnMode& md, double* table, void* stream) {
   RnCols nc;
   int rc = rn_rec_check(sig, L, C_all, cols, C, T, S, sums, !table, nc); if (rc) return rc;
-  if (N < 1 || N > rn_count(L, T, S) || K < 0 || K > MSIG_RN_MAX_K) return MSIG_E_SHAPE;
+  if (N < 1 || N > rn_count(L, T, S) || !rn_mode_ok(md)) return MSIG_E_SHAPE;
   if (((uintptr_t)sig | (uintptr_t)sums | (uintptr_t)table) & 7) return MSIG_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = K == 0 ? 1u : (unsigned)(N > 65536 ? 65536 : N);
-  { MSIG_K("rn_stats", st); rn_stats_kernel<<<grid, 64, 0, st>>>(sig, nc, C, log1p_mask, (double)T, sums, N, K, table); }
+  if (md.decayed) {
+    MSIG_K("rd_stats", st); rd_stats_kernel<<<1, 64, 0, st>>>(sig, nc, C, log1p_mask, (double)T, sums, N, md.decay, table);
+  } else {
+    const unsigned grid = md.K == 0 ? 1u : (unsigned)(N > 65536 ? 65536 : N);
+    MSIG_K("rn_stats", st); rn_stats_kernel<<<grid, 64, 0, st>>>(sig, nc, C, log1p_mask, (double)T, sums, N, md.K, table);
+  }
   MSIG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int msig_rn_stats(const double* sig, int64_t L, int32_t C_all, const int32_t* cols, int32_t C, uint32_t log1p_mask, int64_t T,
+                             int64_t S, const double* sums, int64_t N, int32_t K, double* table, void* stream) {
+  return rn_stats(sig, L, C_all, cols, C, log1p_mask, T, S, sums, N, RnMode{K, 0.0, false}, table, stream);
+}
+
+extern "C" int msig_rd_abi_version(void) { return MSIG_RD_ABI_VERSION; }
+extern "C" int msig_rd_stats(const double* sig, int64_t L, int32_t C_all, const int32_t* cols, int32_t C, uint32_t log1p_mask, int64_t T,
+                             int64_t S, const double* sums, int64_t N, double decay, double* table, void* stream) {
+  return rn_stats(sig, L, C_all, cols, C, log1p_mask, T, S, sums, N, RnMode{0, decay, true}, table, stream);
 }
 
 static int rn_slots(const msig_multi* m, bool multi, int32_t B, int32_t C, int64_t T, RnSlots& sl) {
@@ -344,14 +429,14 @@ static int rn_lv_rows_check(int32_t sessions, int64_t R, int32_t C_all, const in
   return 0;
 }
 
-extern "C" int msig_rn_lv_step(const double* pool, int32_t sessions, int64_t R, int64_t ring_bytes, int32_t C_all, const int32_t* cols, int32_t C,
-                               uint32_t log1p_mask, int64_t T, int64_t S, int32_t K, double* state, int64_t state_bytes, const int32_t* sess,
-                               const int64_t* win, const int64_t* written, const int64_t* next, int32_t B, double* table, void* stream) {
+static int rn_lv_step(const double* pool, int32_t sessions, int64_t R, int64_t ring_bytes, int32_t C_all, const int32_t* cols, int32_t C,
+                      uint32_t log1p_mask, int64_t T, int64_t S, const RnMode& md, double* state, int64_t state_bytes, const int32_t* sess,
+                      const int64_t* win, const int64_t* written, const int64_t* next, int32_t B, double* table, void* stream) {
   if (!pool || !cols || !state || !sess || !win || !written || !next || !table) return MSIG_E_NULL;
   int rc = rn_pool_shape(sessions, R, ring_bytes, C_all); if (rc) return rc;
   RnCols nc;
   rc = rn_lv_rows_check(sessions, R, C_all, cols, C, T, S, sess, win, written, B, nc); if (rc) return rc;
-  if (K < 0 || K > MSIG_RN_MAX_K || state_bytes < msig_rn_state_bytes(K)) return MSIG_E_SHAPE;
+  if (!rn_mode_ok(md) || state_bytes < msig_rn_state_bytes(md.K)) return MSIG_E_SHAPE;
   uint64_t seen[MSIG_LV_MAX_SESSIONS / 64] = {};
   for (int b = 0; b < B; ++b) {
     if (b > 0 && sess[b] == sess[b - 1]) {
@@ -374,13 +459,30 @@ extern "C" int msig_rn_lv_step(const double* pool, int32_t sessions, int64_t R, 
       runs.e[k] = RnRun{win[b], sess[b], e - b, b, 0};
       b = e;
     }
-    {
+    if (md.decayed) {
+      MSIG_K("rd_lv_step", st);
+      rd_lv_step_kernel<<<(unsigned)k, 256, 0, st>>>(pool, ring_bytes / 8, R, C_all, nc, C, log1p_mask, T, S, md.decay, state, state_bytes / 8, table, runs);
+    } else {
       MSIG_K("rn_lv_step", st);
-      rn_lv_step_kernel<<<(unsigned)k, 256, 0, st>>>(pool, ring_bytes / 8, R, C_all, nc, C, log1p_mask, T, S, K, state, state_bytes / 8, table, runs);
+      rn_lv_step_kernel<<<(unsigned)k, 256, 0, st>>>(pool, ring_bytes / 8, R, C_all, nc, C, log1p_mask, T, S, md.K, state, state_bytes / 8, table, runs);
     }
     MSIG_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int msig_rn_lv_step(const double* pool, int32_t sessions, int64_t R, int64_t ring_bytes, int32_t C_all, const int32_t* cols, int32_t C,
+                               uint32_t log1p_mask, int64_t T, int64_t S, int32_t K, double* state, int64_t state_bytes, const int32_t* sess,
+                               const int64_t* win, const int64_t* written, const int64_t* next, int32_t B, double* table, void* stream) {
+  return rn_lv_step(pool, sessions, R, ring_bytes, C_all, cols, C, log1p_mask, T, S, RnMode{K, 0.0, false}, state, state_bytes, sess, win, written, next,
+                    B, table, stream);
+}
+
+extern "C" int msig_rd_lv_step(const double* pool, int32_t sessions, int64_t R, int64_t ring_bytes, int32_t C_all, const int32_t* cols, int32_t C,
+                               uint32_t log1p_mask, int64_t T, int64_t S, double decay, double* state, int64_t state_bytes, const int32_t* sess,
+                               const int64_t* win, const int64_t* written, const int64_t* next, int32_t B, double* table, void* stream) {
+  return rn_lv_step(pool, sessions, R, ring_bytes, C_all, cols, C, log1p_mask, T, S, RnMode{0, decay, true}, state, state_bytes, sess, win, written, next,
+                    B, table, stream);
 }
 
 extern "C" int msig_rn_lv_windows_multi(const double* pool, int32_t sessions, int64_t R, int64_t ring_bytes, int32_t C_all, const int32_t* cols,

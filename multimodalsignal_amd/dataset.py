@@ -13,13 +13,14 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Union
 
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
 from . import _lib as L
+from .reference import Running, parse_running
 
 LABEL_MODES = ("stress_binary", "ternary", "amusement_binary")
 
@@ -46,11 +47,15 @@ def map_labels(y_raw: np.ndarray, mode: str) -> np.ndarray:
     raise ValueError(f"Unknown classification_mode: {mode}")
 
 
-def parse_reference(reference) -> Optional[int]:
+def parse_reference(reference) -> Union[None, int, Running]:
     """The normalisation reference of a run: "subject" (every window of the subject supplies the statistics; the default),
     "baseline" (the windows whose raw protocol label is 1) or "baseline:K" (the first K >= 1 of those in file order; window k
     covers seconds 10 k .. 10 k + 60, so K windows are 60 + 10 (K - 1) seconds of rest).  Returns None for "subject", 0 for
-    "baseline" and K for "baseline:K"; anything else raises ValueError."""
+    "baseline" and K for "baseline:K"; anything else raises ValueError.
+
+    The causal running references "expanding", "trailing:K" and "decayed:H" (reference.parse_running: the monitors' grammar, here
+    without a warm-up count ':W', which is a flag of the monitors) return a reference.Running: window n of a subject's file is
+    normalised with the windows up to n, the file taken as consecutive windows of one recording."""
     if reference == "subject":
         return None
     if reference == "baseline":
@@ -59,15 +64,29 @@ def parse_reference(reference) -> Optional[int]:
         k = reference[len("baseline:"):]
         if k.isascii() and k.isdigit() and int(k) >= 1:
             return int(k)
-    raise ValueError(f"normalisation reference must be 'subject', 'baseline' or 'baseline:K' with K >= 1, got {reference!r}")
+    try:
+        run = parse_running(reference, warmup=False)
+    except ValueError as e:
+        raise ValueError(f"normalisation reference: {e}") from None
+    if run is not None:
+        return run
+    raise ValueError("normalisation reference must be 'subject', 'baseline', 'baseline:K' with K >= 1, 'expanding', 'trailing:K' with K in "
+                     f"1..{L.RN_MAX_K} or 'decayed:H' with H in 1..{L.RD_MAX_H}, got {reference!r}")
+
+
+def running_norm_reference(reference) -> Optional[Running]:
+    """The reference.Running of a running normalisation reference, None for "subject", "baseline" and "baseline:K"."""
+    run = parse_reference(reference)
+    return run if isinstance(run, Running) else None
 
 
 def reference_mask(y_raw: np.ndarray, reference) -> np.ndarray:
     """Which of a subject's windows supply the normalisation statistics (bool, one per window).  `y_raw` are the RAW protocol
-    labels, before any class mapping: the mask is the same in every classification mode."""
+    labels, before any class mapping: the mask is the same in every classification mode.  Under a running reference every window
+    supplies statistics — to itself and to the windows after it."""
     k = parse_reference(reference)
     y_raw = np.asarray(y_raw)
-    if k is None:
+    if k is None or isinstance(k, Running):
         return np.ones(y_raw.shape, dtype=bool)
     mask = y_raw == 1
     if k:
@@ -79,7 +98,8 @@ def subject_reference(y_raw: np.ndarray, reference, sid) -> Optional[np.ndarray]
     """The `ref` of normalise_subject / normalise_subject_device for subject `sid`: None for the "subject" rule, else the mask.
     A subject without a reference window gets the "subject" rule (None) and one warning line — the reference's code announces
     that fallback and then leaves such a subject un-normalised."""
-    if parse_reference(reference) is None:
+    k = parse_reference(reference)
+    if k is None or isinstance(k, Running):          # a running reference has no mask: normalise_subject_running / running=
         return None
     mask = reference_mask(y_raw, reference)
     if not mask.any():
@@ -118,6 +138,50 @@ def normalise_subject(x: np.ndarray, names, ref: Optional[np.ndarray] = None) ->
     return x
 
 
+def running_statistics(v: np.ndarray, run: Running):
+    """include/msig_rn.h's and msig_rd.h's definition in float64 numpy for a subject's (N, T, C) window file `v` (after log1p),
+    taken as the consecutive windows of one recording: the pivot p = v[0, 0], window sums W1[n] = sum_t (v - p), W2[n] = sum_t
+    (v - p)^2, the reference's sums A[n] — expanding: the carry A[n - 1] + W[n]; trailing:K: W[a] + ... + W[n] left to right,
+    a = max(0, n - K + 1); decayed:H: lambda A[n - 1] + W[n], c[n] = lambda c[n - 1] + 1, lambda = exp2(-1 / H) — and
+    dm = A1 / (c T), var = max(0, A2 / (c T) - dm^2), mean = p + dm, inv = 1 / (sqrt(var) + 1e-8).
+    Returns (mean (N, C), inv (N, C), c (N,) float64)."""
+    v = np.ascontiguousarray(v)          # numpy's summation order depends on the strides: one layout, one result
+    N, T, _C = v.shape
+    p = v[0, 0].copy()
+    d = v - p
+    W = np.stack([d.sum(axis=1), (d * d).sum(axis=1)], axis=1)                  # (N, 2, C)
+    A, c = np.empty_like(W), np.empty(N, dtype=np.float64)
+    for n in range(N):
+        if n == 0:
+            A[0], c[0] = W[0], 1.0
+        elif run.kind == "expanding":
+            A[n], c[n] = A[n - 1] + W[n], n + 1.0
+        elif run.kind == "decayed":
+            A[n], c[n] = run.decay * A[n - 1] + W[n], run.decay * c[n - 1] + 1.0
+        else:
+            a = max(0, n - run.K + 1)
+            acc = W[a].copy()
+            for k in range(a + 1, n + 1):
+                acc = acc + W[k]
+            A[n], c[n] = acc, n - a + 1.0
+    cnt = (c * float(T))[:, None]
+    dm = A[:, 0] / cnt
+    var = np.maximum(A[:, 1] / cnt - dm * dm, 0.0)
+    return p + dm, 1.0 / (np.sqrt(var) + 1e-8), c
+
+
+def normalise_subject_running(x: np.ndarray, names, run: Running) -> np.ndarray:
+    """A subject's (N, T, C) float64 windows under a running reference, in place: window n becomes (v - mean[n]) * inv[n] with
+    running_statistics' record of window n; the channel literally named 'chest_EDA' is log1p-transformed first."""
+    for ch, name in enumerate(names):
+        if name == "chest_EDA":
+            x[:, :, ch] = np.log1p(x[:, :, ch])
+    mean, inv, _c = running_statistics(x, run)
+    x -= mean[:, None, :]
+    x *= inv[:, None, :]
+    return x
+
+
 class WesadDataset(Dataset):
     def __init__(self, data_path: Path, subjects: list, channels_to_use: list, all_channel_names: list,
                  classification_mode="stress_binary", cache: Optional[dict] = None, reference="subject"):
@@ -125,9 +189,10 @@ class WesadDataset(Dataset):
         subject's normalised windows depend only on that subject, so the 3 x 15 datasets of a LOSO run
         can load and normalise each subject once instead of 45 times.
         `reference` (optional, not in the reference's dataset.py): which windows supply each subject's mean and std
-        (parse_reference); "subject" is the rule above."""
+        (parse_reference); "subject" is the rule above.  A running reference (expanding, trailing:K, decayed:H) normalises window n
+        with the windows up to n in file order (normalise_subject_running) — like the mask, before amusement_binary drops rows."""
         data_path = Path(data_path)
-        parse_reference(reference)
+        run = running_norm_reference(reference)
         self.classification_mode = classification_mode
         self.data_list, self.labels_list = [], []
         cols = [all_channel_names.index(ch) for ch in channels_to_use]
@@ -144,7 +209,10 @@ class WesadDataset(Dataset):
                 y_raw = np.load(fy)
                 y = map_labels(y_raw, classification_mode)
                 # the mask is taken from the raw labels, before amusement_binary drops rows
-                x = normalise_subject(x, [all_channel_names[i] for i in cols], subject_reference(y_raw, reference, sid))
+                if run is not None:
+                    x = normalise_subject_running(x, [all_channel_names[i] for i in cols], run)
+                else:
+                    x = normalise_subject(x, [all_channel_names[i] for i in cols], subject_reference(y_raw, reference, sid))
                 if (y < 0).any():                                  # amusement_binary: windows of the other protocol phases are dropped
                     x, y = x[y >= 0], y[y >= 0]
                 if cache is not None:
@@ -187,10 +255,14 @@ class SubjectStore:
     def __init__(self, data_path: Path, subjects: list, channels_to_use: list, all_channel_names: list,
                  classification_mode="stress_binary", device="cuda", normalise="host", reference="subject"):
         """`reference`: which windows supply each subject's mean and std (parse_reference); with anything but "subject" one line
-        per subject names the windows used, and `reference_windows` holds {subject: (reference windows used, fallback applied)}."""
+        per subject names the windows used, and `reference_windows` holds {subject: (reference windows used, fallback applied)}.
+        Under a running reference (expanding, trailing:K, decayed:H) window n is normalised with the windows up to n in file order
+        — the entry is ("per window", False) — and with normalise="device" `reference_tables` holds {subject: the (N, 2 * MAX_C + 1)
+        table of one statistics record per window on the device}: msig_rn_sums on the raw upload as a recording of N * T samples
+        at stride T, msig_rn_stats or msig_rd_stats, msig_rn_windows — the rows a Monitor feeds the model for that recording."""
         self.device = torch.device(device)
-        parse_reference(reference)
-        self.reference, self.reference_windows = reference, {}
+        run = running_norm_reference(reference)
+        self.reference, self.reference_windows, self.reference_tables = reference, {}, {}
         data_path = Path(data_path)
         cols = [all_channel_names.index(ch) for ch in channels_to_use]
         names = [all_channel_names[i] for i in cols]
@@ -209,7 +281,8 @@ class SubjectStore:
 
         def host_windows(job):       # the reference's float64 arithmetic, then its fp32 cast (dataset.py:36-48, :63)
             fx, ref = job
-            x = normalise_subject(np.load(fx)[:, :, cols], names, ref)
+            x = np.load(fx)[:, :, cols]
+            x = normalise_subject_running(x, names, run) if run is not None else normalise_subject(x, names, ref)
             return np.ascontiguousarray(x.transpose(0, 2, 1), dtype=np.float32)
 
         # the raw labels are read first: they say which windows are a subject's reference (None: the "subject" rule)
@@ -227,13 +300,20 @@ class SubjectStore:
                 if normalise == "host":
                     xd = torch.from_numpy(next(host)).to(self.device)
                     n_ref = 0 if ref is None else int(ref.sum())
+                elif run is not None:
+                    table = torch.zeros((len(y), 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
+                    xd = normalise_subject_device(torch.from_numpy(np.load(fx)).to(self.device), cols, names, stats=table, running=run)
+                    self.reference_tables[sid], n_ref = table, 0
                 elif ref is None:
                     xd, n_ref = normalise_subject_device(torch.from_numpy(np.load(fx)).to(self.device), cols, names), 0
                 else:       # the kernel counts the windows its mask selects: the line below reports what it used
                     stats = torch.empty(2 * L.MAX_C + 1, dtype=torch.float64, device=self.device)
                     xd = normalise_subject_device(torch.from_numpy(np.load(fx)).to(self.device), cols, names, ref, stats=stats)
                     n_ref = int(stats[2 * L.MAX_C].item())
-                if parse_reference(reference) is not None:
+                if run is not None:
+                    self.reference_windows[sid] = ("per window", False)
+                    print(f"[normalise {normalise}] {sid}: reference {reference}: per window, {len(y)} windows in file order")
+                elif parse_reference(reference) is not None:
                     self.reference_windows[sid] = (n_ref, ref is None)
                     print(f"[normalise {normalise}] {sid}: reference {reference}: "
                           + (f"{n_ref} of {len(y)} windows" if ref is not None else f"no baseline window, all {len(y)} windows"))
@@ -255,7 +335,7 @@ class SubjectStore:
         same bits as a WesadDataset of those subjects.  A subject with no window of the mode keeps an empty range."""
         self = cls.__new__(cls)
         self.device = torch.device(device)
-        self.reference, self.reference_windows = reference, {}
+        self.reference, self.reference_windows, self.reference_tables = reference, {}, {}
         xs, ys, self.ranges, start = [], [], {}, 0
         for sid in subjects:
             if not ((Path(data_path) / f"{sid}_X.npy").exists() and (Path(data_path) / f"{sid}_y.npy").exists()):
@@ -278,13 +358,22 @@ class SubjectStore:
         return StoreView(self, subjects)
 
 
-def normalise_subject_device(raw: torch.Tensor, cols, names, ref=None, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+RUNNING_PIECE = 1 << 20          # windows per msig_rn_windows call of the running store build (the call's B is an int32)
+
+
+def normalise_subject_device(raw: torch.Tensor, cols, names, ref=None, stats: Optional[torch.Tensor] = None,
+                             running: Optional[Running] = None) -> torch.Tensor:
     """(N,T,C_all) raw float64 device tensor -> normalised (N,C,T) fp32 through msig_normalise_subject
     (float64 reduction, optional log1p, z-score, cast and transposition in HIP).
 
     `ref` (a bool mask over the N windows, numpy or torch): through msig_nr_normalise_subject (include/msig_nr.h) — mean and std of
     the selected windows, applied to all.  `stats` (with `ref`; a float64 device tensor of 2 * MAX_C + 1): receives the mean, the
-    1 / (std + 1e-8) and the number of selected windows."""
+    1 / (std + 1e-8) and the number of selected windows.
+
+    `running` (a reference.Running, without `ref`): the file is a recording of L = N * T samples whose windows lie at stride T —
+    msig_rn_sums, then msig_rn_stats (expanding, trailing:K) or msig_rd_stats (decayed:H), then msig_rn_windows in pieces of
+    RUNNING_PIECE windows: row n is normalised with its own record.  `stats` (optional; a contiguous float64 device tensor of
+    (N, 2 * MAX_C + 1)): receives the table of one record per window."""
     if not raw.is_cuda or raw.dtype != torch.float64 or raw.dim() != 3:
         raise ValueError("normalise_subject_device needs a (N,T,C_all) float64 GPU tensor")
     raw = raw.contiguous()
@@ -296,6 +385,24 @@ def normalise_subject_device(raw: torch.Tensor, cols, names, ref=None, stats: Op
     out = torch.empty((N, len(cols), T), dtype=torch.float32, device=raw.device)
     carr = (C.c_int32 * len(cols))(*[int(c) for c in cols])
     st = C.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)
+    if running is not None:
+        if ref is not None:
+            raise ValueError("a running reference takes no mask of reference windows")
+        if stats is None:
+            stats = torch.zeros((N, 2 * L.MAX_C + 1), dtype=torch.float64, device=raw.device)
+        elif (stats.dtype != torch.float64 or stats.device != raw.device or tuple(stats.shape) != (N, 2 * L.MAX_C + 1) or not stats.is_contiguous()):
+            raise ValueError(f"stats must be a contiguous float64 tensor of ({N}, {2 * L.MAX_C + 1}) on {raw.device}")
+        head = (raw.data_ptr(), N * T, C_all, carr, len(cols), mask, T, T)                      # L = N * T, S = T: window n is row n
+        sums = torch.empty((N, 2 * L.MAX_C), dtype=torch.float64, device=raw.device)
+        L.check(L.lib().msig_rn_sums(*head, 0, N, sums.data_ptr(), st), "msig_rn_sums")
+        if running.kind == "decayed":
+            L.check(L.lib().msig_rd_stats(*head, sums.data_ptr(), N, running.decay, stats.data_ptr(), st), "msig_rd_stats")
+        else:
+            L.check(L.lib().msig_rn_stats(*head, sums.data_ptr(), N, running.K, stats.data_ptr(), st), "msig_rn_stats")
+        for n0 in range(0, N, RUNNING_PIECE):
+            B = min(RUNNING_PIECE, N - n0)
+            L.check(L.lib().msig_rn_windows(*head, n0, B, stats[n0].data_ptr(), out[n0].data_ptr(), st), "msig_rn_windows")
+        return out
     if ref is not None:
         if not isinstance(ref, torch.Tensor):
             ref = torch.from_numpy(np.ascontiguousarray(np.asarray(ref) != 0))

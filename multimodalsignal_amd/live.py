@@ -6,9 +6,10 @@ that became complete across all sessions, and runs them through the ensemble as 
 msig_lv_windows_multi, one msig_st_forward_multi and one msig_en_reduce_multi per piece and member chunk, on `Ensemble`'s own
 forward and reduction code (`LiveEnsemble` overrides the filling of the arenas, as monitor.RecordingEnsemble does, and their size).  What a
 session reports equals, bit for bit, what `Monitor.run` reports for the same samples as one recording, under every causal reference:
-"head:K", and the running references "expanding" and "trailing:K" (include/msig_rn.h), whose statistics follow
-the wearer: a per-session state block on the device, one msig_rn_lv_step per piece that forms each new window's sums from the ring
-and its statistics record, and msig_rn_lv_windows_multi, which normalises every row with its own record.  A row's eval bits do not
+"head:K", and the running references "expanding", "trailing:K" (include/msig_rn.h) and "decayed:H"
+(include/msig_rd.h, section 37), whose statistics follow the wearer: a per-session state block on the device, one msig_rn_lv_step or
+msig_rd_lv_step per piece that forms each new window's sums from the ring and its statistics record, and msig_rn_lv_windows_multi,
+which normalises every row with its own record.  "decayed:H" keeps one carry per session whatever H is.  A row's eval bits do not
 depend on its batch, and the smoothing is `monitor.ema`'s recurrence continued.
 
 The offline state drops episodes shorter than `min_on` after the fact; a live system cannot take back an alarm.  So an `onset` alarm
@@ -19,12 +20,12 @@ so far.
 
 The host parts (`Smoother`, `AlarmMachine`, `RingBook`, the CLI's argument checks) need no GPU.  `LiveMonitor` has no CPU fallback.
 
-Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py), decayed (EMA) statistics, training
-under a matching causal normalisation (--norm-reference has no expanding or trailing form), and any network or serial front end —
-push() is the interface.
+Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py) and any network or serial front end —
+push() is the interface.  Training under the matching causal normalisation is --norm-reference expanding | trailing:K | decayed:H
+(dataset.py); --reference auto picks a run's counterpart (monitor.resolve_reference).
 
 CLI:  python -m multimodalsignal_amd.live --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]] --out DIR
+      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] --out DIR
 """
 from __future__ import annotations
 
@@ -40,7 +41,7 @@ import torch
 from . import _lib as L
 from .ensemble import Ensemble, load_members
 from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, ema, find_events, hysteresis,
-                      parse_recording_reference, phase_shares, running_reference)
+                      parse_recording_reference, phase_shares, resolve_reference, run_norm_reference, running_reference)
 
 FIELDS = ("mean_p", "std_p", "pred", "entropy", "mutual_info", "votes")      # what a session stores per window, as Ensemble.predict gives it
 
@@ -205,10 +206,11 @@ class LiveBatch:
         mon = self.monitor
         p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         nxt = np.ascontiguousarray([mon.rn_next[int(s)] for s in self.sess[i:i + b]], dtype=np.int64)
-        L.check(L.lib().msig_rn_lv_step(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, mon.running[0], mon.rn_state.data_ptr(),
-                                        mon.rn_state.shape[1] * 8, self.sess[i:].ctypes.data_as(p32), self.win[i:].ctypes.data_as(p64),
-                                        self.written[i:].ctypes.data_as(p64), nxt.ctypes.data_as(p64), int(b), self.table[i].data_ptr(),
-                                        mon._stream()), "msig_rn_lv_step")
+        decayed = mon.running.kind == "decayed"          # msig_rd_lv_step: the same call with the decay in K's place
+        step, name = (L.lib().msig_rd_lv_step, "msig_rd_lv_step") if decayed else (L.lib().msig_rn_lv_step, "msig_rn_lv_step")
+        L.check(step(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, mon.running.decay if decayed else mon.running[0],
+                     mon.rn_state.data_ptr(), mon.rn_state.shape[1] * 8, self.sess[i:].ctypes.data_as(p32), self.win[i:].ctypes.data_as(p64),
+                     self.written[i:].ctypes.data_as(p64), nxt.ctypes.data_as(p64), int(b), self.table[i].data_ptr(), mon._stream()), name)
         self.stepped.add(i)
         for r in range(i, i + b):
             mon.rn_next[int(self.sess[r])] += 1
@@ -261,14 +263,16 @@ class _Session:
         self.score: List[float] = []
         self.smoothed: List[float] = []
         self.alarms: List[Alarm] = []
+        self.counts: List[float] = []            # decayed: every window's c_n, read from its statistics record
 
 
 class LiveMonitor:
     """An ensemble of 1..256 trained models over up to `max_sessions` live sessions sampled at `fs` Hz: windows of `window_s` seconds
     every `stride_s`, a ring of `ring_s` seconds per session (None: the head span or one window, plus 8 strides), `eval_batch` rows
     per piece.  `reference`: "head:K" — a session's first K windows supply its statistics and are emitted together, flagged warmup,
-    when window K - 1 completes — "expanding[:W]" or "trailing:K[:W]" (monitor.running_reference) — window n is normalised with
-    windows 0..n or with the last K, emitted in the push that completes it, the first W flagged warmup — or a float64 statistics
+    when window K - 1 completes — "expanding[:W]", "trailing:K[:W]" or "decayed:H[:W]" (monitor.running_reference) — window n is
+    normalised with windows 0..n, with the last K or with all so far at a half-life of H windows, emitted in the push that completes
+    it, the first W flagged warmup — or a float64 statistics
     tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.  "recording" is refused: it is not causal; "expanding" is
     its causal counterpart.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.
 
@@ -292,7 +296,7 @@ class LiveMonitor:
         elif running_reference(reference) is not None:
             self.warm = 0                        # no delay: a window's statistics are complete with the window
         else:
-            raise ValueError("a live reference is 'head:K', 'expanding[:W]', 'trailing:K[:W]' or a statistics tensor (anything else is not "
+            raise ValueError("a live reference is 'head:K', 'expanding[:W]', 'trailing:K[:W]', 'decayed:H[:W]' or a statistics tensor (anything else is not "
                              f"causal; 'expanding' is the causal counterpart of 'recording'), got {reference!r}")
         self.running = running_reference(reference)
         if isinstance(max_sessions, bool) or not 1 <= int(max_sessions) <= L.LV_MAX_SESSIONS:
@@ -310,6 +314,7 @@ class LiveMonitor:
         if not 0 <= int(positive) < self.ensemble.K:
             raise ValueError(f"positive must be a class in 0..{self.ensemble.K - 1}, got {positive!r}")
         self.reference, self.positive, self.halflife, self.on, self.off, self.min_on = reference, int(positive), float(halflife), float(on), float(off), int(min_on)
+        self.reference_requested = None          # "auto" where from_run resolved the reference from the run
         self.channels = None if channels is None else list(channels)
         if self.channels is not None and len(self.channels) != self.ensemble.C:
             raise ValueError(f"the models take {self.ensemble.C} channels, got {len(self.channels)} names")
@@ -328,11 +333,16 @@ class LiveMonitor:
 
     @classmethod
     def from_run(cls, run_dir, subject: Optional[str] = None, config_name: Optional[str] = None, fs: float = 64.0, device="cuda", **kw) -> "LiveMonitor":
-        """The checkpoints Monitor.from_run loads (Monitor.run_files) and the run's channels (Monitor.run_channels)."""
+        """The checkpoints Monitor.from_run loads (Monitor.run_files) and the run's channels (Monitor.run_channels).  reference="auto":
+        the causal counterpart of the run's NORM_REFERENCE (monitor.resolve_reference), resolved before anything is loaded."""
+        auto = isinstance(kw.get("reference"), str) and kw["reference"] == "auto"
+        if auto:
+            kw["reference"] = resolve_reference(run_norm_reference(run_dir, config_name), live=True)
         files = Monitor.run_files(run_dir, subject, config_name)
         kw.setdefault("channels", Monitor.run_channels(run_dir, config_name))
         self = cls(load_members(files, device), fs, **kw)
         self.files = files
+        self.reference_requested = "auto" if auto else None
         return self
 
     # ---- sessions ---------------------------------------------------------------------------------------------------------------
@@ -449,10 +459,14 @@ class LiveMonitor:
         return out[next(iter(samples))] if single else out
 
     def _evaluate(self, rows, owners: List[_Session], out):
-        p = self.ensemble.predict(LiveBatch(self, rows))
+        batch = LiveBatch(self, rows)
+        p = self.ensemble.predict(batch)
         host = {k: getattr(p, k).cpu().numpy() for k in FIELDS}
+        counts = batch.table[:, 2 * L.MAX_C].cpu().numpy() if self.running is not None and self.running.kind == "decayed" else None
         for b, s in enumerate(owners):
             n = rows[b][1]
+            if counts is not None:
+                s.counts.append(float(counts[b]))
             for k in FIELDS:
                 s.rows[k].append(host[k][b].copy())
             score = float(host["mean_p"][b, self.positive].astype(np.float64))
@@ -494,7 +508,9 @@ class LiveMonitor:
                     reference="statistics" if s.given else self.reference, warmup_windows=int(s.flagged),
                     files=[str(p) for p in self.files])
         if self.running is not None:
-            meta["reference_window_counts"] = [k + 1 if self.running[0] == 0 else min(k + 1, self.running[0]) for k in range(n)]
+            meta["reference_window_counts"] = list(s.counts) if self.running.kind == "decayed" else self.running.counts(n)
+        if self.reference_requested is not None:
+            meta["reference_requested"] = self.reference_requested
         return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.flagged,
                         events=find_events(state, smoothed, t_end), meta=meta, **f)
 
@@ -537,9 +553,11 @@ def parse_args(argv=None):
     if not 1 <= a.sessions <= L.LV_MAX_SESSIONS:
         ap.error(f"--sessions must be in 1..{L.LV_MAX_SESSIONS}")
     try:
+        if a.reference == "auto":
+            return a
         if not (isinstance(a.reference, str) and a.reference.startswith("head:")) and running_reference(a.reference) is None:
-            ap.error("a live --reference is head:K, expanding[:W] or trailing:K[:W] ('recording' is not causal; 'expanding' is its causal "
-                     "counterpart)")
+            ap.error("a live --reference is head:K, expanding[:W], trailing:K[:W], decayed:H[:W] or auto ('recording' is not causal; "
+                     "'expanding' is its causal counterpart)")
         parse_recording_reference(a.reference, 1 << 62)
     except ValueError as e:
         ap.error(str(e))
@@ -569,7 +587,7 @@ def main(argv=None) -> Timeline:
     for t in range(ticks + a.sessions - 1):          # session k is k chunks behind session 0
         live.push({k: sig[(t - k) * chunk:(t - k + 1) * chunk] for k in range(a.sessions) if 0 <= t - k < ticks})
     tl = live.timeline(0)
-    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, channels=live.channels)
+    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=live.reference, channels=live.channels)
     equal = timelines_equal(tl, offline.run(sig, names))
     if table is not None:
         tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, live.T, live.S))

@@ -34,7 +34,7 @@ from . import adversary as adversary_mod
 from . import dro as dro_mod
 from . import supcon as supcon_mod
 from . import averaging as averaging_mod
-from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask
+from .dataset import DeviceLoader, SubjectStore, WesadDataset, parse_reference, reference_mask, running_norm_reference
 from . import distill as distill_mod
 from . import sam as sam_mod
 from . import ensemble as ensemble_mod
@@ -927,6 +927,9 @@ def normalisation(results, references, data_path, subjects):
             if not fy.exists():
                 continue
             y_raw = np.load(fy)
+            if running_norm_reference(ref) is not None:           # window n is normalised with the windows up to n: no one count
+                windows[ref][sid] = {"n_windows": int(len(y_raw)), "reference_windows": "per window", "fallback": False}
+                continue
             n = int(reference_mask(y_raw, ref).sum())
             fallback = n == 0
             windows[ref][sid] = {"n_windows": int(len(y_raw)), "reference_windows": int(len(y_raw)) if fallback else n, "fallback": fallback}
@@ -984,7 +987,8 @@ def write_normalisation(run_output_dir, table, synthetic=False):
         lines.append("")
     lines.append("reference windows used per subject (fallback: no baseline window, the statistics of all windows):")
     for r in refs:
-        lines.append(f"  {r}: " + ", ".join(f"{sid} {w['reference_windows']}/{w['n_windows']}" + (" fallback" if w["fallback"] else "")
+        lines.append(f"  {r}: " + ", ".join((f"{sid} per window" if w["reference_windows"] == "per window" else
+                                             f"{sid} {w['reference_windows']}/{w['n_windows']}") + (" fallback" if w["fallback"] else "")
                                             for sid, w in table["reference_windows"][r].items()))
     path = run_output_dir / "normalisation.txt"
     path.write_text("\n".join(lines) + "\n", encoding="utf-8")
@@ -1395,7 +1399,10 @@ def build_parser():
                     help="which windows supply each subject's normalisation mean and std (all of its windows are then transformed with "
                          "them): subject = every window (the default, transductive for the test subject), baseline = the windows of the "
                          "baseline phase (raw protocol label 1), baseline:K = the first K of those (60 + 10 (K - 1) seconds of rest).  A "
-                         "subject without a baseline window keeps the subject rule, with a warning.  One value: that reference in every "
+                         "subject without a baseline window keeps the subject rule, with a warning.  expanding | trailing:K | "
+                         "decayed:H = causal: window n is normalised with the windows up to n in file order — all of them, the last K, "
+                         "or all at a half-life of H windows — the rows monitor.py / live.py feed the model under the same --reference "
+                         "(--reference auto picks it).  One value: that reference in every "
                          "driver and with every option.  Several: one job with one LOSO per reference on shared splits, seeds and fold "
                          "batches, and normalisation.txt / normalisation.json with the paired differences (one --model kind, not "
                          "--hierarchical, no post-LOSO option)")

@@ -13,11 +13,12 @@ Out of scope: sharing the front end between overlapping windows (not exact: the 
 convolutions pad at ITS edges) and the hand-crafted feature branch.  The live push(samples) interface is live.py.
 
 Causal running references (include/msig_rn.h): "expanding" normalises window n with windows 0..n, "trailing:K"
-with the last K — a statistics record per window (one msig_rn_sums, one msig_rn_stats) and batches whose every row has its own
-record (msig_rn_windows[_multi]).
+with the last K, "decayed:H" (include/msig_rd.h, section 37) with every window so far, window n - k weighted 2^(-k / H) — a
+statistics record per window (one msig_rn_sums, one msig_rn_stats or msig_rd_stats) and batches whose every row has its own record
+(msig_rn_windows[_multi]).  "auto" takes the counterpart of the reference the run was trained under (resolve_reference).
 
 CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K|expanding[:W]|trailing:K[:W]] [--stride-s 10] --out DIR
+      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] --out DIR
 """
 from __future__ import annotations
 
@@ -35,6 +36,7 @@ import torch
 
 from . import _lib as L
 from .ensemble import Ensemble, load_members, member_files
+from .reference import RUNNING_WARMUP, Running, parse_running      # noqa: F401  (RUNNING_WARMUP is part of this module's interface)
 
 SYNTHETIC_NOTE = ("synthetic recording: the stress phases are planted and easy, so the timeline shows that the recording-to-events "
                   "machinery works, not what detection is worth on WESAD")
@@ -50,33 +52,60 @@ def count_windows(L_: int, T: int, S: int) -> int:
     return n
 
 
-REFERENCE_FORMS = ("'recording', 'head:K' with K >= 1, 'expanding[:W]', 'trailing:K[:W]' with K in 1..%d and W >= 0, a (w0, w1) pair or a "
-                   "statistics tensor" % L.RN_MAX_K)
-RUNNING_WARMUP = 6          # windows a running reference flags `warmup` by default: head:6's count
+REFERENCE_FORMS = ("'recording', 'head:K' with K >= 1, 'expanding[:W]', 'trailing:K[:W]' with K in 1..%d, 'decayed:H[:W]' with H in 1..%d and "
+                   "W >= 0, a (w0, w1) pair or a statistics tensor" % (L.RN_MAX_K, L.RD_MAX_H))
 
 
-def running_reference(reference) -> Optional[Tuple[int, int]]:
-    """(K, W) of a causal running reference — "expanding" / "expanding:W" (K = 0: window n is normalised with windows 0..n) or
-    "trailing:K" / "trailing:K:W" (with the last K, 1 <= K <= RN_MAX_K); W >= 0 leading windows are flagged `warmup` (default 6).
-    None for anything that is not spelled as one; ValueError for one that is spelled wrongly."""
-    if not isinstance(reference, str) or reference.split(":")[0] not in ("expanding", "trailing"):
-        return None
-    kind, *rest = reference.split(":")
-    want = 0 if kind == "expanding" else 1
-    ok = want <= len(rest) <= want + 1 and all(v.isascii() and v.isdigit() for v in rest)
-    if ok:
-        K = int(rest[0]) if want else 0
-        W = int(rest[want]) if len(rest) > want else RUNNING_WARMUP
-        if not want or 1 <= K <= L.RN_MAX_K:
-            return K, W
-    raise ValueError(f"reference must be {REFERENCE_FORMS}, got {reference!r}")
+def running_reference(reference) -> Optional[Running]:
+    """The reference.Running — as a tuple (K, W) — of a causal running reference: "expanding[:W]" (K = 0: window n is normalised with
+    windows 0..n), "trailing:K[:W]" (with the last K, 1 <= K <= RN_MAX_K) or "decayed:H[:W]" (K = 0, .H = H, .decay = exp2(-1 / H):
+    every window so far, a half-life of H windows, 1 <= H <= RD_MAX_H); W >= 0 leading windows are flagged `warmup` (default 6).
+    None for anything that is not spelled as one; ValueError for one that is spelled wrongly.  The grammar is reference.parse_running."""
+    try:
+        return parse_running(reference)
+    except ValueError:
+        raise ValueError(f"reference must be {REFERENCE_FORMS}, got {reference!r}") from None
+
+
+def run_norm_reference(run_dir, config_name: Optional[str] = None) -> str:
+    """NORM_REFERENCE of the run's cv_summary.txt (the file run_channels reads); "subject" where the line is absent."""
+    base = Path(run_dir) / config_name if config_name else Path(run_dir)
+    for path in (base / "cv_summary.txt", Path(run_dir) / "cv_summary.txt"):
+        if path.exists():
+            for line in path.read_text(encoding="utf-8").splitlines():
+                if line.startswith("NORM_REFERENCE:"):
+                    return line.split(":", 1)[1].strip()
+            return "subject"
+    return "subject"
+
+
+def resolve_reference(trained: str, live: bool = False) -> str:
+    """--reference auto: the monitor's counterpart of the --norm-reference a run was trained under.  subject -> recording (live:
+    refused, it is not causal), baseline:K -> head:K, a running reference -> itself with the default warm-up; baseline (every
+    baseline window, wherever it lies) has no counterpart on a recording."""
+    from .dataset import parse_reference as parse_norm_reference          # training's grammar: None, 0, K or a Running
+    try:
+        k = parse_norm_reference(trained)
+    except ValueError as e:
+        raise ValueError(f"--reference auto: the run's NORM_REFERENCE is not one this monitor knows: {e}") from None
+    if k is None:
+        if live:
+            raise ValueError("--reference auto: the run was trained under 'subject', whose counterpart 'recording' is not causal; a live "
+                             "monitor can take 'expanding', best with a run trained under --norm-reference expanding")
+        return "recording"
+    if isinstance(k, Running):
+        return f"{k.spelling}:{RUNNING_WARMUP}"
+    if k == 0:
+        raise ValueError("--reference auto: the run was trained under 'baseline' (every baseline window of a subject), which no reference "
+                         "of a recording matches; train under baseline:K and monitor under 'head:K'")
+    return f"head:{k}"
 
 
 def parse_recording_reference(reference, n: int):
     """Which windows supply a recording's mean and std: "recording" (all of them: the counterpart of training's --norm-reference
     subject), "head:K" (the first K >= 1: the counterpart of baseline:K, 60 + 10 (K - 1) seconds at the default window and
     stride) or a pair (w0, w1) of window indices, 0 <= w0 < w1 <= n.  Returns (w0, w1, warm-up windows) — the warm-up count is K
-    for "head:K" and 0 otherwise.  A running reference (running_reference: "expanding[:W]", "trailing:K[:W]") has statistics per
+    for "head:K" and 0 otherwise.  A running reference (running_reference: "expanding[:W]", "trailing:K[:W]", "decayed:H[:W]") has statistics per
     window: it returns (0, n, W), the windows any row may draw on and the number flagged.  A tensor of statistics is not parsed here
     (RecordingWindows takes it as it is)."""
     if reference == "recording":
@@ -158,7 +187,8 @@ class Timeline:
     std_p (N, K), pred, entropy, mutual_info (N,), votes (N, K), score = mean_p[:, positive], smoothed (float64), state (bool),
     warmup (bool: the window supplied the statistics of a "head:K" reference, or is one of a running reference's first W); `events`
     as find_events lists them; `meta` the settings (under a running reference also reference_window_counts: per window the number
-    of windows its statistics were taken over)."""
+    of windows its statistics were taken over — integers, under "decayed:H" the real effective counts c_n; where the reference was
+    resolved from the run, reference_requested = "auto" beside the resolved `reference`)."""
     t_end: np.ndarray
     mean_p: np.ndarray
     std_p: np.ndarray
@@ -240,8 +270,12 @@ class RecordingWindows:
             sums = torch.empty((self.n, 2 * L.MAX_C), dtype=torch.float64, device=self.device)
             self.stats = torch.zeros((self.n, 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
             L.check(L.lib().msig_rn_sums(*self._head(), 0, self.n, sums.data_ptr(), self._stream()), "msig_rn_sums")
-            L.check(L.lib().msig_rn_stats(*self._head(), sums.data_ptr(), self.n, self.running[0], self.stats.data_ptr(), self._stream()),
-                    "msig_rn_stats")
+            if self.running.kind == "decayed":
+                L.check(L.lib().msig_rd_stats(*self._head(), sums.data_ptr(), self.n, self.running.decay, self.stats.data_ptr(), self._stream()),
+                        "msig_rd_stats")
+            else:
+                L.check(L.lib().msig_rn_stats(*self._head(), sums.data_ptr(), self.n, self.running[0], self.stats.data_ptr(), self._stream()),
+                        "msig_rn_stats")
         elif isinstance(reference, torch.Tensor):
             if reference.dtype != torch.float64 or reference.numel() < 2 * L.MAX_C + 1:
                 raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
@@ -331,6 +365,7 @@ class Monitor:
         if not 0 <= int(positive) < self.ensemble.K:
             raise ValueError(f"positive must be a class in 0..{self.ensemble.K - 1}, got {positive!r}")
         self.reference, self.positive, self.halflife, self.on, self.off, self.min_on = reference, int(positive), float(halflife), float(on), float(off), int(min_on)
+        self.reference_requested = None          # "auto" where from_run resolved the reference from the run
         self.channels = None if channels is None else list(channels)
         if self.channels is not None and len(self.channels) != self.ensemble.C:
             raise ValueError(f"the models take {self.ensemble.C} channels, got {len(self.channels)} names")
@@ -362,10 +397,15 @@ class Monitor:
 
     @classmethod
     def from_run(cls, run_dir, subject: Optional[str] = None, config_name: Optional[str] = None, fs: float = 64.0, device="cuda", **kw) -> "Monitor":
+        """reference="auto": the counterpart of the run's NORM_REFERENCE (resolve_reference), resolved before anything is loaded."""
+        auto = isinstance(kw.get("reference"), str) and kw["reference"] == "auto"
+        if auto:
+            kw["reference"] = resolve_reference(run_norm_reference(run_dir, config_name))
         files = cls.run_files(run_dir, subject, config_name)
         kw.setdefault("channels", cls.run_channels(run_dir, config_name))
         self = cls(load_members(files, device), fs, **kw)
         self.files = files
+        self.reference_requested = "auto" if auto else None
         return self
 
     def windows(self, sig, names: Sequence[str]) -> RecordingWindows:
@@ -390,7 +430,10 @@ class Monitor:
                                                                                       else list(rw.reference_windows)),
                     warmup_windows=int(rw.warmup), files=[str(f) for f in self.files])
         if rw.running is not None:
-            meta["reference_window_counts"] = [int(v) for v in rw.stats[:, 2 * L.MAX_C].cpu().numpy()]
+            counts = rw.stats[:, 2 * L.MAX_C].cpu().numpy()          # decayed: c_n, the effective number of windows, a real number
+            meta["reference_window_counts"] = [float(v) if rw.running.kind == "decayed" else int(v) for v in counts]
+        if self.reference_requested is not None:
+            meta["reference_requested"] = self.reference_requested
         return Timeline(t_end=t_end, mean_p=mean_p, std_p=host(p.std_p), pred=host(p.pred), entropy=host(p.entropy),
                         mutual_info=host(p.mutual_info), votes=host(p.votes), score=score, smoothed=smoothed, state=state, warmup=warmup,
                         events=find_events(state, smoothed, t_end), meta=meta)
@@ -408,7 +451,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--synthetic-recording", action="store_true", help="a seeded 40-minute recording with planted stress phases")
     ap.add_argument("--fs", type=float, default=64.0, help="sampling rate the models were trained at")
     ap.add_argument("--resample-from", type=float, default=None, help="the recording's own sampling rate: it is resampled to --fs first")
-    ap.add_argument("--reference", default="recording", help="recording | head:K | expanding[:W] | trailing:K[:W]")
+    ap.add_argument("--reference", default="recording", help="recording | head:K | expanding[:W] | trailing:K[:W] | decayed:H[:W] | auto (the counterpart of the run's NORM_REFERENCE)")
     ap.add_argument("--window-s", type=float, default=60.0)
     ap.add_argument("--stride-s", type=float, default=10.0)
     ap.add_argument("--seed", type=int, default=42, help="seed of --synthetic-recording")
@@ -432,7 +475,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     if not a.window_s > 0 or not a.stride_s > 0:
         ap.error("--window-s and --stride-s must be > 0")
     try:
-        parse_recording_reference(a.reference, 1 << 62)
+        if a.reference != "auto":
+            parse_recording_reference(a.reference, 1 << 62)
     except ValueError as e:
         ap.error(str(e))
     return a
