@@ -125,6 +125,8 @@ LV_MAX_SESSIONS = 4096        # MSIG_LV_MAX_SESSIONS
 RN_ABI_VERSION = 1    # include/msig_rn.h MSIG_RN_ABI_VERSION (causal running references: a statistics record per window, offline and live)
 RN_MAX_K = 4096               # MSIG_RN_MAX_K
 RD_ABI_VERSION = 1    # include/msig_rd.h MSIG_RD_ABI_VERSION (the exponentially decayed running reference, offline and live)
+GP_ABI_VERSION = 1    # include/msig_gp.h MSIG_GP_ABI_VERSION (gap-tolerant running references: missing samples, offline and live)
+GP_EXPANDING, GP_TRAILING, GP_DECAYED = 0, 1, 2      # msig_gp_mode.kind
 RD_MAX_H = 1 << 20            # half-life of a decayed reference in windows at most (the host's limit: the library takes any decay in [0, 1])
 
 
@@ -141,6 +143,12 @@ class Multi(C.Structure):
     _fields_ = [("n", C.c_int32), ("slot", C.c_int32 * MAX_FOLDS), ("stride_bytes", C.c_int64),
                 ("key_gru", C.c_uint32 * MAX_FOLDS), ("key_head", C.c_uint32 * MAX_FOLDS), ("lr", C.c_float * MAX_FOLDS),
                 ("form_folds", C.c_int32), ("step", C.c_int64 * MAX_FOLDS)]
+
+
+class GpMode(C.Structure):
+    """msig_gp_mode (include/msig_gp.h): the running reference of a gap-tolerant call — kind GP_EXPANDING, GP_TRAILING (K windows) or
+    GP_DECAYED (decay = lambda)."""
+    _fields_ = [("kind", C.c_int32), ("K", C.c_int32), ("decay", C.c_double)]
 
 
 class FtHead(C.Structure):
@@ -519,6 +527,24 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} has msig_rd.h ABI {L.msig_rd_abi_version()}; this binding is {RD_ABI_VERSION}: rebuild the library")
         L.msig_rd_stats.argtypes = rec + [vp, i64, C.c_double, vp, vp]
         L.msig_rd_lv_step.argtypes = pool + rows + [C.c_double, vp, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
+        # include/msig_gp.h, exported by the same library: pivot, window records, statistics and coverage tables, rows and the live step
+        # of recordings and sessions with missing samples
+        L.msig_gp_abi_version.restype = C.c_int
+        L.msig_gp_struct_bytes.restype = C.c_int64
+        if L.msig_gp_abi_version() != GP_ABI_VERSION or L.msig_gp_struct_bytes() != C.sizeof(GpMode):
+            raise RuntimeError(f"{LIB_PATH} has msig_gp.h ABI {L.msig_gp_abi_version()} with msig_gp_mode of {L.msig_gp_struct_bytes()} bytes; "
+                               f"this binding is {GP_ABI_VERSION} with {C.sizeof(GpMode)}: rebuild the library")
+        L.msig_gp_state_bytes.argtypes = [i32]
+        L.msig_gp_state_bytes.restype = C.c_int64
+        L.msig_gp_pivot.argtypes = rec + [i64, vp, vp]
+        L.msig_gp_sums.argtypes = rec + [vp, i64, i64, vp, vp]
+        L.msig_gp_stats.argtypes = rec + [vp, vp, i64, C.POINTER(GpMode), vp, vp, vp]
+        L.msig_gp_windows.argtypes = rec + [i64, i32, vp, vp, vp]
+        L.msig_gp_windows_multi.argtypes = rec + [i64, i32, vp, vp, C.POINTER(Multi), vp]
+        L.msig_gp_lv_step.argtypes = pool + rows + [C.POINTER(GpMode), vp, i64, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, vp,
+                                                    vp, vp]
+        L.msig_gp_lv_windows_multi.argtypes = pool + rows + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp, C.POINTER(Multi), vp]
+        L.msig_gp_lv_skip.argtypes = pool + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp]
         _lib = L
     return _lib
 

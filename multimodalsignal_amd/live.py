@@ -12,6 +12,13 @@ msig_rd_lv_step per piece that forms each new window's sums from the ring and it
 which normalises every row with its own record.  "decayed:H" keeps one carry per session whatever H is.  A row's eval bits do not
 depend on its batch, and the smoothing is `monitor.ema`'s recurrence continued.
 
+Missing samples (include/msig_gp.h): with `gaps=Gaps(...)`, under a running reference, a chunk may hold NaN and
+`skip({sid: n_samples})` stands for a stretch in which nothing arrived at all — it completes windows exactly as a push of n NaN rows
+would (msig_gp_lv_skip writes them into the ring without a staging buffer).  The per-session state, the step and the row fill are
+msig_gp_lv_step's and msig_gp_lv_windows_multi's; an update carries the window's coverage and validity, the smoother and the alarm
+machine hold through invalid windows (GapSmoother, GapAlarmMachine) and raise `lost` / `back`.  `timeline(sid)` equals `Monitor.run`
+with the same `gaps` on the same samples, the skipped stretches as NaN rows, in every field.
+
 The offline state drops episodes shorter than `min_on` after the fact; a live system cannot take back an alarm.  So an `onset` alarm
 is raised at the window where a run of the raw hysteresis state reaches `min_on` windows (it carries the run's first window), and an
 `offset` alarm at the window where such a run ends: every offline event (a, b) yields one onset at window a + min_on - 1 and one
@@ -25,7 +32,8 @@ push() is the interface.  Training under the matching causal normalisation is --
 (dataset.py); --reference auto picks a run's counterpart (monitor.resolve_reference).
 
 CLI:  python -m multimodalsignal_amd.live --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] --out DIR
+      --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto]
+      [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
 """
 from __future__ import annotations
 
@@ -40,8 +48,10 @@ import torch
 
 from . import _lib as L
 from .ensemble import Ensemble, load_members
-from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, ema, find_events, hysteresis,
-                      parse_recording_reference, phase_shares, resolve_reference, run_norm_reference, running_reference)
+from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, check_gap_args, ema, ema_gaps,
+                      find_events, hysteresis, hysteresis_gaps, lost_windows, parse_recording_reference, phase_shares, resolve_reference,
+                      run_norm_reference, running_reference)
+from .reference import Gaps, gp_mode_fields
 
 FIELDS = ("mean_p", "std_p", "pred", "entropy", "mutual_info", "votes")      # what a session stores per window, as Ensemble.predict gives it
 
@@ -96,6 +106,89 @@ class AlarmMachine:
             alarm = Alarm("onset", n, self.start)
         self.n += 1
         return self.raw and n - self.start + 1 >= self.min_on, alarm
+
+
+class GapSmoother:
+    """monitor.ema_gaps one (score, valid) at a time: the same float64 operations in the same order, so after n windows `value`
+    holds ema_gaps(scores, valid, halflife, lost_after)[n - 1] bit for bit."""
+
+    def __init__(self, halflife: float, lost_after: int):
+        ema([], halflife)
+        lost_windows([], lost_after)
+        self.a = 1.0 if halflife == 0 else 1.0 - 2.0 ** (-1.0 / float(halflife))
+        self.lost_after, self.run, self.fresh, self.value = int(lost_after), 0, True, 0.0
+
+    def push(self, score, valid) -> float:
+        if valid:
+            v = float(score)
+            self.value = v if self.fresh else self.value + self.a * (v - self.value)
+            self.fresh, self.run = False, 0
+        else:
+            self.run += 1
+            if self.run >= self.lost_after:
+                self.fresh = True
+        return self.value
+
+
+class GapAlarmMachine:
+    """monitor.hysteresis_gaps one (smoothed, valid) at a time, with AlarmMachine's live min_on rule.  step(v, valid) returns (on,
+    alarms): `alarms` — the Alarms raised at this window, in order.  Beside onset and offset: "lost" at the window where a run of
+    invalid windows reaches lost_after (start_window: the run's first window) — preceded by an "offset" where an alarm was active,
+    since the state is forced off there — and "back" at the next valid window (start_window: the same run's first window)."""
+
+    def __init__(self, on: float, off: float, min_on: int = 1, lost_after: int = 6):
+        hysteresis([], on, off, min_on)
+        lost_windows([], lost_after)
+        self.on, self.off, self.min_on, self.lost_after = float(on), float(off), int(min_on), int(lost_after)
+        self.n, self.raw, self.start = 0, False, 0
+        self.run, self.gap_start, self.lost = 0, 0, False
+
+    def step(self, v, valid) -> Tuple[bool, List[Alarm]]:
+        v, n, alarms = float(v), self.n, []
+        if valid:
+            if self.lost:
+                alarms.append(Alarm("back", n, self.gap_start))
+            self.run, self.lost = 0, False
+            if not self.raw and v >= self.on:
+                self.raw, self.start = True, n
+            elif self.raw and v <= self.off:
+                self.raw = False
+                if n - self.start >= self.min_on:
+                    alarms.append(Alarm("offset", n, self.start))
+        else:
+            if self.run == 0:
+                self.gap_start = n
+            self.run += 1
+            if self.run >= self.lost_after:
+                if self.raw:
+                    self.raw = False
+                    if n - self.start >= self.min_on:
+                        alarms.append(Alarm("offset", n, self.start))
+                if not self.lost:
+                    alarms.append(Alarm("lost", n, self.gap_start))
+                self.lost = True
+        if self.raw and n - self.start + 1 == self.min_on:
+            alarms.append(Alarm("onset", n, self.start))
+        self.n += 1
+        return self.raw and n - self.start + 1 >= self.min_on, alarms
+
+
+def alarms_of_gaps(state, valid, lost_after: int, min_on: int) -> List[Tuple[str, int, int]]:
+    """(kind, window, start_window) of the alarms the offline state and validity vectors imply: alarms_of_events' onsets and offsets,
+    a "lost" at the first lost window of every invalid run that reaches lost_after and a "back" at the valid window that ends it —
+    in window order, at one window back before offset before lost before onset (GapAlarmMachine's order)."""
+    ok, lost = np.asarray(valid, dtype=bool), lost_windows(valid, lost_after)
+    out = list(alarms_of_events(state, min_on))
+    for n in range(len(ok)):
+        if lost[n] and not (n > 0 and lost[n - 1]):
+            out.append(("lost", n, n - int(lost_after) + 1))
+        if n > 0 and lost[n - 1] and ok[n]:
+            k = n - 1
+            while k > 0 and not ok[k - 1]:
+                k -= 1
+            out.append(("back", n, k))
+    rank = {"back": 0, "offset": 1, "lost": 2, "onset": 3}
+    return sorted(out, key=lambda e: (e[1], rank[e[0]]))
 
 
 def alarms_of_events(state, min_on: int) -> List[Tuple[str, int, int]]:
@@ -168,7 +261,8 @@ class RingBook:
 class LiveUpdate:
     """One new window of one session: its index, t_end = (window S + T) / fs, the timeline's row (score = mean_p[positive], std =
     std_p[positive], entropy, mutual_info, pred, smoothed, warmup), `on` (AlarmMachine: an alarm is active) and the Alarm raised at
-    this window, if any."""
+    this window, if any.  A monitor with `gaps` also fills `coverage` (per selected channel the share of valid samples) and `valid`,
+    and `alarms` with every Alarm of this window in order (a forced offset comes before its `lost`); `alarm` is the last of them."""
     sid: object
     window: int
     t_end: float
@@ -181,6 +275,9 @@ class LiveUpdate:
     warmup: bool
     on: bool
     alarm: Optional[Alarm] = None
+    valid: bool = True
+    coverage: Optional[Tuple[float, ...]] = None
+    alarms: Tuple[Alarm, ...] = ()
 
 
 # ---- the sessions on the GPU -------------------------------------------------------------------------------------------------------
@@ -194,9 +291,11 @@ class LiveBatch:
         self.written = np.ascontiguousarray([r[2] for r in rows], dtype=np.int64)
         self.C, self.T = monitor.ensemble.C, monitor.T
         self.shape = (len(rows), self.C, self.T)
-        self.table, self.stepped = None, set()
+        self.table, self.coverage, self.stepped = None, None, set()
         if monitor.running is not None:          # a statistics record per row, written by msig_rn_lv_step piece by piece
             self.table = torch.zeros((len(rows), 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
+        if monitor.gaps is not None:             # and a coverage record per row (msig_gp_lv_step)
+            self.coverage = torch.zeros((len(rows), L.MAX_C), dtype=torch.float64, device=self.device)
 
     def _step(self, i: int, b: int):
         """msig_rn_lv_step for rows i .. i + b - 1, once: the sessions' states advance in row order (a piece is filled once per
@@ -206,11 +305,23 @@ class LiveBatch:
         mon = self.monitor
         p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         nxt = np.ascontiguousarray([mon.rn_next[int(s)] for s in self.sess[i:i + b]], dtype=np.int64)
+        if mon.gaps is not None:
+            mode = L.GpMode(*gp_mode_fields(mon.running))
+            L.check(L.lib().msig_gp_lv_step(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, C.byref(mode), mon.rn_state.data_ptr(),
+                                            mon.rn_state.shape[1] * 8, self.sess[i:].ctypes.data_as(p32), self.win[i:].ctypes.data_as(p64),
+                                            self.written[i:].ctypes.data_as(p64), nxt.ctypes.data_as(p64), int(b), self.table[i].data_ptr(),
+                                            self.coverage[i].data_ptr(), mon._stream()), "msig_gp_lv_step")
+            self._stepped(i, b)
+            return
         decayed = mon.running.kind == "decayed"          # msig_rd_lv_step: the same call with the decay in K's place
         step, name = (L.lib().msig_rd_lv_step, "msig_rd_lv_step") if decayed else (L.lib().msig_rn_lv_step, "msig_rn_lv_step")
         L.check(step(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, mon.running.decay if decayed else mon.running[0],
                      mon.rn_state.data_ptr(), mon.rn_state.shape[1] * 8, self.sess[i:].ctypes.data_as(p32), self.win[i:].ctypes.data_as(p64),
                      self.written[i:].ctypes.data_as(p64), nxt.ctypes.data_as(p64), int(b), self.table[i].data_ptr(), mon._stream()), name)
+        self._stepped(i, b)
+
+    def _stepped(self, i: int, b: int):
+        mon = self.monitor
         self.stepped.add(i)
         for r in range(i, i + b):
             mon.rn_next[int(self.sess[r])] += 1
@@ -223,9 +334,11 @@ class LiveBatch:
         p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         if self.table is not None:
             self._step(i, b)
-            L.check(L.lib().msig_rn_lv_windows_multi(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, self.sess[i:].ctypes.data_as(p32),
+            rows = L.lib().msig_gp_lv_windows_multi if mon.gaps is not None else L.lib().msig_rn_lv_windows_multi
+            L.check(rows(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, self.sess[i:].ctypes.data_as(p32),
                                                      self.win[i:].ctypes.data_as(p64), self.written[i:].ctypes.data_as(p64), int(b),
-                                                     self.table[i].data_ptr(), x0, C.byref(multi), mon._stream()), "msig_rn_lv_windows_multi")
+                                                     self.table[i].data_ptr(), x0, C.byref(multi), mon._stream()),
+                    "msig_gp_lv_windows_multi" if mon.gaps is not None else "msig_rn_lv_windows_multi")
             return
         L.check(L.lib().msig_lv_windows_multi(*mon._pool_args(), mon.cols, self.C, mon.mask, mon.T, mon.S, self.sess[i:].ctypes.data_as(p32),
                                               self.win[i:].ctypes.data_as(p64), self.written[i:].ctypes.data_as(p64), int(b),
@@ -257,6 +370,11 @@ class _Session:
     def __init__(self, sid, slot: int, book: RingBook, mon: "LiveMonitor"):
         self.sid, self.slot, self.book = sid, slot, book
         self.smoother, self.machine = Smoother(mon.halflife), AlarmMachine(mon.on, mon.off, mon.min_on)
+        if mon.gaps is not None:
+            self.smoother = GapSmoother(mon.halflife, mon.gaps.lost_after)
+            self.machine = GapAlarmMachine(mon.on, mon.off, mon.min_on, mon.gaps.lost_after)
+        self.coverage: List[np.ndarray] = []     # gaps: every window's coverage of the selected channels, and its validity
+        self.valid: List[bool] = []
         self.given = book.warm == 0 and mon.running is None
         self.flagged = mon.running[1] if mon.running is not None else book.warm      # leading windows flagged warmup
         self.rows: Dict[str, list] = {k: [] for k in FIELDS}
@@ -274,19 +392,27 @@ class LiveMonitor:
     normalised with windows 0..n, with the last K or with all so far at a half-life of H windows, emitted in the push that completes
     it, the first W flagged warmup — or a float64 statistics
     tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.  "recording" is refused: it is not causal; "expanding" is
-    its causal counterpart.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.
+    its causal counterpart.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.  `gaps` (a Gaps, with a running
+    reference only): samples may be NaN and stretches may be skipped (module docstring).
 
-    open(sid, names, stats=None) / close(sid); push({sid: samples}) or push(sid, samples); timeline(sid); alarms(sid)."""
+    open(sid, names, stats=None) / close(sid); push({sid: samples}) or push(sid, samples); skip({sid: n}) or skip(sid, n);
+    timeline(sid); alarms(sid)."""
 
     def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="head:6", max_sessions: int = 64,
                  ring_s: Optional[float] = None, eval_batch: int = 256, positive: int = 1, halflife: float = 3, on: float = 0.6,
-                 off: float = 0.4, min_on: int = 2, channels: Optional[Sequence[str]] = None):
+                 off: float = 0.4, min_on: int = 2, channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None):
         if not float(fs) > 0:
             raise ValueError(f"fs must be > 0, got {fs!r}")
         self.fs = float(fs)
         self.T, self.S = int(round(float(window_s) * self.fs)), int(round(float(stride_s) * self.fs))
         if self.T < 16 or self.S < 1:
             raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
+        if gaps is not None and not isinstance(gaps, Gaps):
+            raise ValueError(f"gaps is a Gaps(min_coverage, lost_after) or None, got {gaps!r}")
+        if gaps is not None and (isinstance(reference, torch.Tensor) or running_reference(reference) is None):
+            raise ValueError("a live monitor with gaps takes a running reference ('expanding', 'trailing:K', 'decayed:H'): 'head:K' statistics "
+                             f"weight samples and have no per-channel count of valid ones, and given statistics have no live coverage; got {reference!r}")
+        self.gaps = gaps
         if isinstance(reference, torch.Tensor):
             if reference.dtype != torch.float64 or reference.numel() < 2 * L.MAX_C + 1:
                 raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
@@ -327,7 +453,8 @@ class LiveMonitor:
         self.scratch = torch.empty(L.lib().msig_rec_scratch_bytes(), dtype=torch.uint8, device=self.device)
         self.pool = None
         if self.running is not None:             # per session: the pivot, the expanding carry and the ring of the last K window sums
-            self.rn_state = torch.zeros((self.max_sessions, L.lib().msig_rn_state_bytes(self.running[0]) // 8), dtype=torch.float64, device=self.device)
+            state_bytes = L.lib().msig_rn_state_bytes(self.running[0]) if gaps is None else L.lib().msig_gp_state_bytes(self.running[0])
+            self.rn_state = torch.zeros((self.max_sessions, state_bytes // 8), dtype=torch.float64, device=self.device)
             self.rn_next = [0] * self.max_sessions               # the host's mirror of every state's next expected window
             self.rn_latest: Dict[int, torch.Tensor] = {}         # slot -> the session's latest statistics record
 
@@ -428,22 +555,52 @@ class LiveMonitor:
                 raise ValueError("push takes {sid: samples} or (sid, samples)")
             samples = {samples: chunk}
         todo = [(self._session(sid), self._samples(x)) for sid, x in samples.items()]
-        out: Dict[object, List[LiveUpdate]] = {sid: [] for sid in samples}
+        out = self._feed(todo, {sid: [] for sid in samples})
+        return out[next(iter(samples))] if single else out
+
+    @torch.no_grad()
+    def skip(self, counts, n=None) -> Union[Dict[object, List[LiveUpdate]], List[LiveUpdate]]:
+        """skip({sid: n_samples, ...}) -> {sid: [LiveUpdate, ...]}; skip(sid, n_samples) -> [LiveUpdate, ...].  Nothing arrived from
+        these sessions for n samples' time: the stretch is appended as missing rows (msig_gp_lv_skip, no staging buffer) and
+        completes windows exactly as a push of n NaN rows would.  Needs a monitor with `gaps`."""
+        if self.gaps is None:
+            raise ValueError("skip needs a monitor with gaps=Gaps(...): without it a stretch without samples has no representation")
+        single = n is not None or not isinstance(counts, dict)
+        if single:
+            if n is None:
+                raise ValueError("skip takes {sid: n_samples} or (sid, n_samples)")
+            counts = {counts: n}
+        for k in counts.values():
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 0:
+                raise ValueError(f"skip takes a number of samples >= 0 per session, got {k!r}")
+        todo = [(self._session(sid), int(k)) for sid, k in counts.items()]
+        out = self._feed(todo, {sid: [] for sid in counts})
+        return out[next(iter(counts))] if single else out
+
+    def _feed(self, todo, out: Dict[object, List[LiveUpdate]]):
+        """Appends every session's samples — an array, or a count of missing rows — segment by segment (RingBook) and evaluates the
+        windows that became complete after each round."""
         at = [0] * len(todo)
+        size = lambda x: x if isinstance(x, int) else x.shape[0]      # noqa: E731
         lib = L.lib()
         while True:
-            seg = [(j, s, s.book.segment(x.shape[0] - at[j])) for j, (s, x) in enumerate(todo) if x.shape[0] > at[j]]
+            seg = [(j, s, s.book.segment(size(x) - at[j])) for j, (s, x) in enumerate(todo) if size(x) > at[j]]
             if not seg:
                 break
-            parts = [todo[j][1][at[j]:at[j] + a] for j, _s, a in seg]
-            if all(isinstance(p, np.ndarray) for p in parts):                  # one upload of the round's chunks, back to back
-                staging = torch.from_numpy(np.concatenate(parts) if len(parts) > 1 else parts[0]).to(self.device)
-            else:
-                staging = torch.cat([torch.from_numpy(p).to(self.device) if isinstance(p, np.ndarray) else p for p in parts]).contiguous()
-            n = len(seg)
-            L.check(lib.msig_lv_push(*self._pool_args(), (C.c_int32 * n)(*[s.slot for _j, s, _a in seg]),
-                                     (C.c_int64 * n)(*[s.book.written for _j, s, _a in seg]), (C.c_int64 * n)(*[a for _j, _s, a in seg]), n,
-                                     staging.data_ptr(), self._stream()), "msig_lv_push")
+            args = lambda part: ((C.c_int32 * len(part))(*[s.slot for _j, s, _a in part]),      # noqa: E731
+                                 (C.c_int64 * len(part))(*[s.book.written for _j, s, _a in part]),
+                                 (C.c_int64 * len(part))(*[a for _j, _s, a in part]), len(part))
+            data = [e for e in seg if not isinstance(todo[e[0]][1], int)]
+            gone = [e for e in seg if isinstance(todo[e[0]][1], int)]
+            if data:
+                parts = [todo[j][1][at[j]:at[j] + a] for j, _s, a in data]
+                if all(isinstance(p, np.ndarray) for p in parts):                  # one upload of the round's chunks, back to back
+                    staging = torch.from_numpy(np.concatenate(parts) if len(parts) > 1 else parts[0]).to(self.device)
+                else:
+                    staging = torch.cat([torch.from_numpy(p).to(self.device) if isinstance(p, np.ndarray) else p for p in parts]).contiguous()
+                L.check(lib.msig_lv_push(*self._pool_args(), *args(data), staging.data_ptr(), self._stream()), "msig_lv_push")
+            if gone:
+                L.check(lib.msig_gp_lv_skip(*self._pool_args(), *args(gone), self._stream()), "msig_gp_lv_skip")
             rows, owners = [], []
             for j, s, a in seg:
                 at[j] += a
@@ -456,13 +613,16 @@ class LiveMonitor:
                 owners += [s] * len(windows)
             if rows:
                 self._evaluate(rows, owners, out)
-        return out[next(iter(samples))] if single else out
+        return out
 
     def _evaluate(self, rows, owners: List[_Session], out):
         batch = LiveBatch(self, rows)
         p = self.ensemble.predict(batch)
         host = {k: getattr(p, k).cpu().numpy() for k in FIELDS}
         counts = batch.table[:, 2 * L.MAX_C].cpu().numpy() if self.running is not None and self.running.kind == "decayed" else None
+        if self.gaps is not None:
+            coverage = np.ascontiguousarray(batch.coverage.cpu().numpy()[:, :self.ensemble.C])
+            valid = self.gaps.valid(coverage)
         for b, s in enumerate(owners):
             n = rows[b][1]
             if counts is not None:
@@ -470,17 +630,30 @@ class LiveMonitor:
             for k in FIELDS:
                 s.rows[k].append(host[k][b].copy())
             score = float(host["mean_p"][b, self.positive].astype(np.float64))
-            smoothed = s.smoother.push(score)
-            on, alarm = s.machine.step(smoothed)
             t_end = lambda w: (float(w) * self.S + self.T) / self.fs      # noqa: E731
-            if alarm is not None:
-                alarm = Alarm(alarm.kind, alarm.window, alarm.start_window, t_end(alarm.window), t_end(alarm.start_window))
-                s.alarms.append(alarm)
+            clocked = lambda al: Alarm(al.kind, al.window, al.start_window, t_end(al.window), t_end(al.start_window))      # noqa: E731
+            extra = {}
+            if self.gaps is None:
+                smoothed = s.smoother.push(score)
+                on, alarm = s.machine.step(smoothed)
+                if alarm is not None:
+                    alarm = clocked(alarm)
+                    s.alarms.append(alarm)
+            else:
+                ok = bool(valid[b])
+                smoothed = s.smoother.push(score, ok)
+                on, raised = s.machine.step(smoothed, ok)
+                raised = tuple(clocked(al) for al in raised)
+                s.alarms.extend(raised)
+                s.coverage.append(coverage[b].copy())
+                s.valid.append(ok)
+                alarm = raised[-1] if raised else None
+                extra = dict(valid=ok, coverage=tuple(float(v) for v in coverage[b]), alarms=raised)
             s.score.append(score)
             s.smoothed.append(smoothed)
             out[s.sid].append(LiveUpdate(sid=s.sid, window=int(n), t_end=t_end(n), score=score, std=float(host["std_p"][b, self.positive]),
                                          entropy=float(host["entropy"][b]), mutual_info=float(host["mutual_info"][b]), pred=int(host["pred"][b]),
-                                         smoothed=smoothed, warmup=n < s.flagged, on=on, alarm=alarm))
+                                         smoothed=smoothed, warmup=n < s.flagged, on=on, alarm=alarm, **extra))
 
     # ---- what a session has reported so far -------------------------------------------------------------------------------------
     def alarms(self, sid) -> List[Alarm]:
@@ -502,7 +675,14 @@ class LiveMonitor:
         f = {k: np.stack(s.rows[k]) if n else np.zeros(*empty[k]) for k in FIELDS}
         score, smoothed = np.array(s.score, dtype=np.float64), np.array(s.smoothed, dtype=np.float64)
         t_end = (np.arange(n, dtype=np.float64) * self.S + self.T) / self.fs
-        state = hysteresis(smoothed, self.on, self.off, self.min_on)
+        extra = {}
+        if self.gaps is None:
+            state = hysteresis(smoothed, self.on, self.off, self.min_on)
+        else:
+            valid = np.array(s.valid, dtype=bool)
+            state = hysteresis_gaps(smoothed, valid, self.on, self.off, self.min_on, self.gaps.lost_after)
+            extra = dict(coverage=np.stack(s.coverage) if n else np.zeros((0, self.ensemble.C)), valid=valid,
+                         lost=lost_windows(valid, self.gaps.lost_after))
         meta = dict(fs=self.fs, window_samples=self.T, stride_samples=self.S, members=M, positive=self.positive, halflife=self.halflife,
                     on=self.on, off=self.off, min_on=self.min_on, samples=s.book.written,
                     reference="statistics" if s.given else self.reference, warmup_windows=int(s.flagged),
@@ -511,8 +691,10 @@ class LiveMonitor:
             meta["reference_window_counts"] = list(s.counts) if self.running.kind == "decayed" else self.running.counts(n)
         if self.reference_requested is not None:
             meta["reference_requested"] = self.reference_requested
+        if self.gaps is not None:
+            meta.update(gaps=self.gaps.spelling, invalid_windows=int((~extra["valid"]).sum()), lost_windows=int(extra["lost"].sum()))
         return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.flagged,
-                        events=find_events(state, smoothed, t_end), meta=meta, **f)
+                        events=find_events(state, smoothed, t_end), meta=meta, **f, **extra)
 
 
 def timelines_equal(a: Timeline, b: Timeline) -> bool:
@@ -520,6 +702,10 @@ def timelines_equal(a: Timeline, b: Timeline) -> bool:
     for k in ("t_end", "mean_p", "std_p", "pred", "entropy", "mutual_info", "votes", "score", "smoothed", "state", "warmup"):
         x, y = getattr(a, k), getattr(b, k)
         if x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes():
+            return False
+    for k in ("coverage", "valid", "lost"):          # filled by a monitor with gaps: in both or in neither
+        x, y = getattr(a, k), getattr(b, k)
+        if (x is None) != (y is None) or (x is not None and (x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes())):
             return False
     return a.events == b.events
 
@@ -552,6 +738,7 @@ def parse_args(argv=None):
         ap.error("--window-s, --stride-s and --chunk-s must be > 0")
     if not 1 <= a.sessions <= L.LV_MAX_SESSIONS:
         ap.error(f"--sessions must be in 1..{L.LV_MAX_SESSIONS}")
+    check_gap_args(ap, a)
     try:
         if a.reference == "auto":
             return a
@@ -564,15 +751,34 @@ def parse_args(argv=None):
     return a
 
 
+def replay_pieces(lo: int, hi: int, spans) -> List[Tuple[int, int, bool]]:
+    """The samples [lo, hi) cut at the all-channel gap spans: (first, one past last, skipped) pieces in order."""
+    out, at = [], lo
+    for a, b in spans:
+        a, b = max(a, lo), min(b, hi)
+        if a >= b:
+            continue
+        if a > at:
+            out.append((at, a, False))
+        out.append((a, b, True))
+        at = b
+    if hi > at:
+        out.append((at, hi, False))
+    return out
+
+
 def main(argv=None) -> Timeline:
     a = parse_args(argv)
     live = LiveMonitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference,
-                                max_sessions=a.sessions)
-    table = None
+                                max_sessions=a.sessions, gaps=a.gaps)
+    table, spans = None, []
     if a.synthetic_recording:
-        from .synth import CHANNELS6, make_synthetic_recording
+        from .synth import CHANNELS6, gap_spans, make_synthetic_recording
         names = list(CHANNELS6)
-        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty)
+        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty,
+                                              gaps=a.synthetic_gaps)
+        if a.gaps is not None and a.synthetic_gaps is not None:      # the stretches in which every channel is off are not pushed but skipped
+            spans = gap_spans(a.synthetic_gaps, a.fs, int(sig.shape[0]))
     else:
         sig = np.load(a.recording)
         names = [ln.strip() for ln in a.names.read_text().splitlines() if ln.strip()]
@@ -584,10 +790,22 @@ def main(argv=None) -> Timeline:
     ticks = -(-int(sig.shape[0]) // chunk)
     for k in range(a.sessions):
         live.open(k, names)
+    skipped = 0
     for t in range(ticks + a.sessions - 1):          # session k is k chunks behind session 0
-        live.push({k: sig[(t - k) * chunk:(t - k + 1) * chunk] for k in range(a.sessions) if 0 <= t - k < ticks})
+        if not spans:
+            live.push({k: sig[(t - k) * chunk:(t - k + 1) * chunk] for k in range(a.sessions) if 0 <= t - k < ticks})
+            continue
+        pieces = {k: replay_pieces((t - k) * chunk, min((t - k + 1) * chunk, int(sig.shape[0])), spans) for k in range(a.sessions) if 0 <= t - k < ticks}
+        for r in range(max(len(v) for v in pieces.values())):      # a session's pieces in their order, the sessions side by side
+            data = {k: sig[v[r][0]:v[r][1]] for k, v in pieces.items() if r < len(v) and not v[r][2]}
+            gone = {k: v[r][1] - v[r][0] for k, v in pieces.items() if r < len(v) and v[r][2]}
+            if data:
+                live.push(data)
+            if gone:
+                live.skip(gone)
+                skipped += gone.get(0, 0)
     tl = live.timeline(0)
-    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=live.reference, channels=live.channels)
+    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=live.reference, channels=live.channels, gaps=a.gaps)
     equal = timelines_equal(tl, offline.run(sig, names))
     if table is not None:
         tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, live.T, live.S))
@@ -598,6 +816,9 @@ def main(argv=None) -> Timeline:
     print(f"{a.sessions} sessions, {ticks} pushes of {chunk} samples each; session 0: {len(tl.t_end)} windows, {int(tl.state.sum())} flagged, "
           f"{len(tl.events)} events, {len(live.alarms(0))} alarms; timeline written to: {path}")
     print(f"session 0's timeline and Monitor.run's for the same recording: {'equal' if equal else 'NOT EQUAL'} bit for bit")
+    if a.gaps is not None:
+        print(f"gaps {a.gaps.spelling}: {tl.meta['invalid_windows']} invalid windows, {tl.meta['lost_windows']} lost; {skipped} of session 0's "
+              f"samples were skipped, not pushed; {int((~np.isfinite(tl.score)).sum())} of {len(tl.score)} scores are not finite")
     if table is not None:
         print("NOTE: " + SYNTHETIC_NOTE + ".")
     return tl

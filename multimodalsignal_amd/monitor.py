@@ -17,8 +17,14 @@ with the last K, "decayed:H" (include/msig_rd.h, section 37) with every window s
 statistics record per window (one msig_rn_sums, one msig_rn_stats or msig_rd_stats) and batches whose every row has its own record
 (msig_rn_windows[_multi]).  "auto" takes the counterpart of the reference the run was trained under (resolve_reference).
 
+Missing samples (include/msig_gp.h): `gaps=Gaps(...)` / --gaps [MIN_COVERAGE[:LOST_AFTER]].  A sample that is
+NaN or +-Inf (after log1p) is missing: it enters no statistic and is the reference mean, +0.0, in its window's rows; every window has
+a coverage per channel, a window below MIN_COVERAGE is invalid — scored, but the smoother and the hysteresis hold (ema_gaps,
+hysteresis_gaps) — and after LOST_AFTER invalid windows in a row the state is off until the next valid one.  Under a running
+reference or a statistics tensor; without `gaps` nothing here differs from what it was.
+
 CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] --out DIR
+      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
 """
 from __future__ import annotations
 
@@ -36,7 +42,8 @@ import torch
 
 from . import _lib as L
 from .ensemble import Ensemble, load_members, member_files
-from .reference import RUNNING_WARMUP, Running, parse_running      # noqa: F401  (RUNNING_WARMUP is part of this module's interface)
+from .reference import (GAPS_REFERENCES, RUNNING_WARMUP, Gaps, Running, gp_mode_fields, parse_gaps,      # noqa: F401  (RUNNING_WARMUP and Gaps
+                        parse_running)                                                                  # are part of this module's interface)
 
 SYNTHETIC_NOTE = ("synthetic recording: the stress phases are planted and easy, so the timeline shows that the recording-to-events "
                   "machinery works, not what detection is worth on WESAD")
@@ -167,6 +174,74 @@ def hysteresis(smoothed, on: float, off: float, min_on: int = 1) -> np.ndarray:
     return state
 
 
+def lost_windows(valid, lost_after: int) -> np.ndarray:
+    """(N,) bool: window n is lost when it is invalid and the run of invalid windows it belongs to has reached `lost_after` windows
+    at n — from the lost_after-th window of the run to its last."""
+    if isinstance(lost_after, bool) or int(lost_after) < 1:
+        raise ValueError(f"lost_after must be an integer >= 1, got {lost_after!r}")
+    ok = np.asarray(valid, dtype=bool).reshape(-1)
+    out = np.zeros(ok.size, dtype=bool)
+    run = 0
+    for n, v in enumerate(ok):
+        run = 0 if v else run + 1
+        out[n] = run >= int(lost_after)
+    return out
+
+
+def ema_gaps(score, valid, halflife: float, lost_after: int) -> np.ndarray:
+    """`ema` over the valid windows only: an invalid window leaves s where it is (its own score is reported, it does not move the
+    smoother), and after a lost stretch (lost_windows) the smoother restarts, s = score, at the next valid window, as at window 0.
+    Before the first valid window s = 0.0.  With every window valid these are ema's operations in ema's order: the same bits."""
+    x = np.asarray(score, dtype=np.float64).reshape(-1)
+    ok = np.asarray(valid, dtype=bool).reshape(-1)
+    if ok.size != x.size:
+        raise ValueError(f"{x.size} scores and {ok.size} validity flags")
+    if not halflife >= 0:
+        raise ValueError(f"halflife must be >= 0 windows, got {halflife!r}")
+    lost = lost_windows(ok, lost_after)
+    a = 1.0 if halflife == 0 else 1.0 - 2.0 ** (-1.0 / float(halflife))
+    out = np.empty_like(x)
+    s, fresh = 0.0, True
+    for n, v in enumerate(x):
+        if ok[n]:
+            s = float(v) if fresh else s + a * (float(v) - s)
+            fresh = False
+        elif lost[n]:
+            fresh = True
+        out[n] = s
+    return out
+
+
+def hysteresis_gaps(smoothed, valid, on: float, off: float, min_on: int = 1, lost_after: int = 6) -> np.ndarray:
+    """`hysteresis` that an invalid window does not move: the state holds through it, and from the window where a run of invalid
+    windows reaches `lost_after` (lost_windows) it is forced off until a valid window raises it again.  min_on acts on the resulting
+    state sequence.  With every window valid this is hysteresis' array."""
+    if not off < on:
+        raise ValueError(f"hysteresis needs off < on, got off = {off!r}, on = {on!r}")
+    if isinstance(min_on, bool) or int(min_on) < 1:
+        raise ValueError(f"min_on must be an integer >= 1, got {min_on!r}")
+    x = np.asarray(smoothed, dtype=np.float64).reshape(-1)
+    ok = np.asarray(valid, dtype=bool).reshape(-1)
+    if ok.size != x.size:
+        raise ValueError(f"{x.size} smoothed scores and {ok.size} validity flags")
+    lost = lost_windows(ok, lost_after)
+    state = np.zeros(x.size, dtype=bool)
+    cur = False
+    for n, v in enumerate(x):
+        if ok[n]:
+            if not cur and v >= on:
+                cur = True
+            elif cur and v <= off:
+                cur = False
+        elif lost[n]:
+            cur = False
+        state[n] = cur
+    for a, b in _runs(state):
+        if b - a < int(min_on):
+            state[a:b] = False
+    return state
+
+
 def _runs(state) -> List[Tuple[int, int]]:
     """The maximal runs of True in a bool vector as (first, one past last)."""
     s = np.concatenate(([False], np.asarray(state, dtype=bool), [False]))
@@ -188,7 +263,9 @@ class Timeline:
     warmup (bool: the window supplied the statistics of a "head:K" reference, or is one of a running reference's first W); `events`
     as find_events lists them; `meta` the settings (under a running reference also reference_window_counts: per window the number
     of windows its statistics were taken over — integers, under "decayed:H" the real effective counts c_n; where the reference was
-    resolved from the run, reference_requested = "auto" beside the resolved `reference`)."""
+    resolved from the run, reference_requested = "auto" beside the resolved `reference`).  Only a monitor with `gaps` fills coverage
+    (N, C) float64 — per selected channel the share of the window's samples that were valid —, valid and lost (N,) bool; its meta
+    holds gaps = "MIN_COVERAGE:LOST_AFTER", invalid_windows and lost_windows, and its CSV the columns valid, coverage_min, lost."""
     t_end: np.ndarray
     mean_p: np.ndarray
     std_p: np.ndarray
@@ -202,14 +279,19 @@ class Timeline:
     warmup: np.ndarray
     events: List[Tuple[float, float, float, float]]
     meta: dict = field(default_factory=dict)
+    coverage: Optional[np.ndarray] = None
+    valid: Optional[np.ndarray] = None
+    lost: Optional[np.ndarray] = None
 
     def to_csv(self, path) -> Path:
         path = Path(path)
-        lines = ["window,t_end_s,score,std,smoothed,state,pred,entropy,mutual_info,warmup"]
+        gaps = "gaps" in self.meta and self.coverage is not None
+        lines = ["window,t_end_s,score,std,smoothed,state,pred,entropy,mutual_info,warmup" + (",valid,coverage_min,lost" if gaps else "")]
         pos = int(self.meta.get("positive", 1))
         for n in range(len(self.t_end)):
             lines.append(f"{n},{self.t_end[n]:.6f},{self.score[n]:.9g},{self.std_p[n, pos]:.9g},{self.smoothed[n]:.9g},{int(self.state[n])},"
-                         f"{int(self.pred[n])},{self.entropy[n]:.9g},{self.mutual_info[n]:.9g},{int(self.warmup[n])}")
+                         f"{int(self.pred[n])},{self.entropy[n]:.9g},{self.mutual_info[n]:.9g},{int(self.warmup[n])}"
+                         + (f",{int(self.valid[n])},{float(self.coverage[n].min()):.9g},{int(self.lost[n])}" if gaps else ""))
         path.write_text("\n".join(lines) + "\n")
         return path
 
@@ -239,10 +321,13 @@ class RecordingWindows:
     in dataset.normalise_subject_device.  `reference`: parse_recording_reference, or a float64 tensor of 2 * MAX_C + 1 statistics
     (msig_nr.h's layout) taken as it is.  `.n` windows, `.shape` = (n, C, T), `.stats` the statistics on the device, `.warmup` the
     number of leading windows that supplied them ("head:K").  Under a running reference (running_reference) `.stats` is the
-    (n, 2 * MAX_C + 1) table of one record per window, `.running` = (K, W) and `.warmup` = W, the windows flagged."""
+    (n, 2 * MAX_C + 1) table of one record per window, `.running` = (K, W) and `.warmup` = W, the windows flagged.
+    `gaps` (a reference.Gaps; include/msig_gp.h): samples may be missing.  pivot -> window records -> statistics and coverage -> rows
+    go through msig_gp_*; `.stats` is a table of one record per window also for a statistics tensor (the one record, broadcast) and
+    `.coverage` the (n, MAX_C) table of every window's share of valid samples per selected channel.  Any other reference is refused."""
 
     def __init__(self, sig, names: Sequence[str], channels: Sequence[str], T: int, stride: int,
-                 reference: Union[str, tuple, torch.Tensor] = "recording", device="cuda"):
+                 reference: Union[str, tuple, torch.Tensor] = "recording", device="cuda", gaps: Optional[Gaps] = None):
         if isinstance(sig, np.ndarray):
             sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float64)).to(device)
         if not isinstance(sig, torch.Tensor) or not sig.is_cuda or sig.dtype != torch.float64 or sig.dim() != 2:
@@ -265,7 +350,10 @@ class RecordingWindows:
         self.cols = (C.c_int32 * self.C)(*[names.index(c) for c in channels])
         self.mask = sum(1 << c for c, name in enumerate(channels) if name == "chest_EDA")
         self.running = running_reference(reference)
-        if self.running is not None:            # a record per window: the windows' own sums, then their ordered sums (msig_rn.h)
+        self.gaps, self.coverage = gaps, None
+        if gaps is not None:
+            self._gap_tables(reference)
+        elif self.running is not None:            # a record per window: the windows' own sums, then their ordered sums (msig_rn.h)
             self.reference_windows, self.warmup = None, self.running[1]
             sums = torch.empty((self.n, 2 * L.MAX_C), dtype=torch.float64, device=self.device)
             self.stats = torch.zeros((self.n, 2 * L.MAX_C + 1), dtype=torch.float64, device=self.device)
@@ -287,6 +375,29 @@ class RecordingWindows:
             scratch = torch.empty(L.lib().msig_rec_scratch_bytes(), dtype=torch.uint8, device=self.device)
             L.check(L.lib().msig_rec_stats(*self._head(), w0, w1, self.stats.data_ptr(), scratch.data_ptr(), self._stream()), "msig_rec_stats")
 
+    def _gap_tables(self, reference):
+        """The gap-tolerant tables (msig_gp.h): the pivot record, the window records, then a statistics and a coverage record per window."""
+        if not isinstance(self.gaps, Gaps):
+            raise ValueError(f"gaps is a Gaps(min_coverage, lost_after) or None, got {self.gaps!r}")
+        given = isinstance(reference, torch.Tensor)
+        if self.running is None and not given:
+            raise ValueError(f"{GAPS_REFERENCES}; got {reference!r}")
+        if given and (reference.dtype != torch.float64 or reference.numel() < 2 * L.MAX_C + 1):
+            raise ValueError(f"a statistics tensor holds 2 * {L.MAX_C} + 1 float64 values")
+        self.reference_windows, self.warmup = None, (0 if given else self.running[1])
+        lib, z = L.lib(), dict(dtype=torch.float64, device=self.device)
+        self.pivot = torch.zeros(2 * L.MAX_C, **z)
+        self.sums = torch.zeros((self.n, 3 * L.MAX_C), **z)
+        self.stats = torch.zeros((self.n, 2 * L.MAX_C + 1), **z)
+        self.coverage = torch.zeros((self.n, L.MAX_C), **z)
+        mode = L.GpMode(*gp_mode_fields(self.running))
+        L.check(lib.msig_gp_pivot(*self._head(), self.n, self.pivot.data_ptr(), self._stream()), "msig_gp_pivot")
+        L.check(lib.msig_gp_sums(*self._head(), self.pivot.data_ptr(), 0, self.n, self.sums.data_ptr(), self._stream()), "msig_gp_sums")
+        L.check(lib.msig_gp_stats(*self._head(), self.pivot.data_ptr(), self.sums.data_ptr(), self.n, C.byref(mode), self.stats.data_ptr(),
+                                  self.coverage.data_ptr(), self._stream()), "msig_gp_stats")
+        if given:                                # the coverage is the windows' own; every row takes the one given record
+            self.stats = reference.to(self.device).reshape(-1)[:2 * L.MAX_C + 1][None, :].repeat(self.n, 1).contiguous()
+
     def _head(self):
         return self.sig.data_ptr(), self.L, self.C_all, self.cols, self.C, self.mask, self.T, self.S
 
@@ -303,6 +414,11 @@ class RecordingWindows:
             out = torch.empty((int(B), self.C, self.T), dtype=torch.float32, device=self.device)
         elif out.dtype != torch.float32 or tuple(out.shape) != (int(B), self.C, self.T) or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"out must be a contiguous float32 ({B}, {self.C}, {self.T}) tensor on {self.device}")
+        if self.gaps is not None:
+            self._rows(n0, B)
+            L.check(L.lib().msig_gp_windows(*self._head(), int(n0), int(B), self.stats[int(n0)].data_ptr(), out.data_ptr(), self._stream()),
+                    "msig_gp_windows")
+            return out
         if self.running is not None:
             self._rows(n0, B)
             L.check(L.lib().msig_rn_windows(*self._head(), int(n0), int(B), self.stats[int(n0)].data_ptr(), out.data_ptr(), self._stream()),
@@ -314,6 +430,11 @@ class RecordingWindows:
 
     def fill(self, x0: int, multi: L.Multi, n0: int, B: int):
         """Windows n0 .. n0 + B - 1 into the x buffer of every arena slot of `multi`; x0 is arena 0's (msig_rec_windows_multi)."""
+        if self.gaps is not None:
+            self._rows(n0, B)
+            L.check(L.lib().msig_gp_windows_multi(*self._head(), int(n0), int(B), self.stats[int(n0)].data_ptr(), x0, C.byref(multi),
+                                                  self._stream()), "msig_gp_windows_multi")
+            return
         if self.running is not None:
             self._rows(n0, B)
             L.check(L.lib().msig_rn_windows_multi(*self._head(), int(n0), int(B), self.stats[int(n0)].data_ptr(), x0, C.byref(multi),
@@ -348,11 +469,13 @@ class Monitor:
     """An ensemble of 1..256 trained models (M = 1: one model) over continuous recordings sampled at `fs` Hz: windows of `window_s`
     seconds every `stride_s`, normalised by `reference` (parse_recording_reference), `eval_batch` windows per piece.  `channels`: the
     names of the models' input channels in their order (None: the recording's columns as they come).  score = the probability of
-    class `positive`; smoothed = ema(score, halflife) (in windows); state = hysteresis(smoothed, on, off, min_on)."""
+    class `positive`; smoothed = ema(score, halflife) (in windows); state = hysteresis(smoothed, on, off, min_on).
+    `gaps` (a Gaps; None: every sample is taken as a number, as ever): samples may be missing (module docstring) — the timeline
+    gains coverage, valid and lost, and smoothed and state are ema_gaps' and hysteresis_gaps'."""
 
     def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="recording", eval_batch: int = 256,
                  positive: int = 1, halflife: float = 3, on: float = 0.6, off: float = 0.4, min_on: int = 2,
-                 channels: Optional[Sequence[str]] = None):
+                 channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None):
         if not float(fs) > 0:
             raise ValueError(f"fs must be > 0, got {fs!r}")
         self.fs = float(fs)
@@ -361,6 +484,11 @@ class Monitor:
             raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
         hysteresis([], on, off, min_on)
         ema([], halflife)
+        if gaps is not None and not isinstance(gaps, Gaps):
+            raise ValueError(f"gaps is a Gaps(min_coverage, lost_after) or None, got {gaps!r}")
+        if gaps is not None and running_reference(reference) is None and not isinstance(reference, torch.Tensor):
+            raise ValueError(f"{GAPS_REFERENCES}; got {reference!r}")
+        self.gaps = gaps
         self.ensemble = RecordingEnsemble(models, eval_batch=eval_batch)
         if not 0 <= int(positive) < self.ensemble.K:
             raise ValueError(f"positive must be a class in 0..{self.ensemble.K - 1}, got {positive!r}")
@@ -411,7 +539,7 @@ class Monitor:
     def windows(self, sig, names: Sequence[str]) -> RecordingWindows:
         names = list(names)
         return RecordingWindows(sig, names, self.channels if self.channels is not None else names, self.T, self.S, self.reference,
-                                device=self.ensemble.device)
+                                device=self.ensemble.device, gaps=self.gaps)
 
     @torch.no_grad()
     def run(self, sig, names: Sequence[str]) -> Timeline:
@@ -421,8 +549,16 @@ class Monitor:
         mean_p = host(p.mean_p)
         score = mean_p[:, self.positive].astype(np.float64)
         t_end = (np.arange(rw.n, dtype=np.float64) * self.S + self.T) / self.fs
-        smoothed = ema(score, self.halflife)
-        state = hysteresis(smoothed, self.on, self.off, self.min_on)
+        extra = {}
+        if self.gaps is None:
+            smoothed = ema(score, self.halflife)
+            state = hysteresis(smoothed, self.on, self.off, self.min_on)
+        else:
+            coverage = np.ascontiguousarray(host(rw.coverage)[:, :rw.C])
+            valid = self.gaps.valid(coverage)
+            smoothed = ema_gaps(score, valid, self.halflife, self.gaps.lost_after)
+            state = hysteresis_gaps(smoothed, valid, self.on, self.off, self.min_on, self.gaps.lost_after)
+            extra = dict(coverage=coverage, valid=valid, lost=lost_windows(valid, self.gaps.lost_after))
         warmup = np.arange(rw.n) < rw.warmup
         meta = dict(fs=self.fs, window_samples=self.T, stride_samples=self.S, members=self.ensemble.M, positive=self.positive,
                     halflife=self.halflife, on=self.on, off=self.off, min_on=self.min_on, samples=rw.L,
@@ -434,9 +570,11 @@ class Monitor:
             meta["reference_window_counts"] = [float(v) if rw.running.kind == "decayed" else int(v) for v in counts]
         if self.reference_requested is not None:
             meta["reference_requested"] = self.reference_requested
+        if self.gaps is not None:
+            meta.update(gaps=self.gaps.spelling, invalid_windows=int((~extra["valid"]).sum()), lost_windows=int(extra["lost"].sum()))
         return Timeline(t_end=t_end, mean_p=mean_p, std_p=host(p.std_p), pred=host(p.pred), entropy=host(p.entropy),
                         mutual_info=host(p.mutual_info), votes=host(p.votes), score=score, smoothed=smoothed, state=state, warmup=warmup,
-                        events=find_events(state, smoothed, t_end), meta=meta)
+                        events=find_events(state, smoothed, t_end), meta=meta, **extra)
 
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------------
@@ -456,8 +594,28 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--stride-s", type=float, default=10.0)
     ap.add_argument("--seed", type=int, default=42, help="seed of --synthetic-recording")
     ap.add_argument("--difficulty", type=float, default=1.0, help="difficulty of --synthetic-recording")
+    ap.add_argument("--gaps", nargs="?", const="", default=None, metavar="MIN_COVERAGE[:LOST_AFTER]",
+                    help="samples may be missing (NaN, +-Inf): a window whose smallest channel coverage is below MIN_COVERAGE (0.75) is "
+                         "invalid and holds the smoother and the state; after LOST_AFTER (6) invalid windows in a row the state is off")
+    ap.add_argument("--synthetic-gaps", default=None, metavar="SPEC",
+                    help="plant gaps into --synthetic-recording: drop=RATE,channel=INDEX:START_S:SECONDS,all=START_S:SECONDS")
     ap.add_argument("--out", type=Path, required=True)
     return ap
+
+
+def check_gap_args(ap, a):
+    """--gaps and --synthetic-gaps, checked before anything touches the GPU; a.gaps becomes a Gaps or None."""
+    try:
+        a.gaps = None if a.gaps is None else parse_gaps(a.gaps)
+        if a.synthetic_gaps is not None:
+            if not a.synthetic_recording:
+                ap.error("--synthetic-gaps goes with --synthetic-recording")
+            from .synth import parse_synthetic_gaps
+            parse_synthetic_gaps(a.synthetic_gaps)
+        if a.gaps is not None and a.reference != "auto" and running_reference(a.reference) is None:
+            ap.error(GAPS_REFERENCES + f"; got {a.reference!r}")
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -479,17 +637,19 @@ def parse_args(argv=None) -> argparse.Namespace:
             parse_recording_reference(a.reference, 1 << 62)
     except ValueError as e:
         ap.error(str(e))
+    check_gap_args(ap, a)
     return a
 
 
 def main(argv=None) -> Timeline:
     a = parse_args(argv)
-    mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference)
+    mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, gaps=a.gaps)
     table = None
     if a.synthetic_recording:
         from .synth import CHANNELS6, make_synthetic_recording
         names = list(CHANNELS6)
-        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty)
+        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty,
+                                              gaps=a.synthetic_gaps)
     else:
         sig = np.load(a.recording)
         names = [ln.strip() for ln in a.names.read_text().splitlines() if ln.strip()]
@@ -504,6 +664,9 @@ def main(argv=None) -> Timeline:
     tl.to_csv(a.out / "timeline.csv")
     path = tl.to_json(a.out / "timeline.json")
     print(f"{len(tl.t_end)} windows, {int(tl.state.sum())} flagged, {len(tl.events)} events; timeline written to: {path}")
+    if a.gaps is not None:
+        print(f"gaps {a.gaps.spelling}: {tl.meta['invalid_windows']} invalid windows, {tl.meta['lost_windows']} lost; "
+              f"{int((~np.isfinite(tl.score)).sum())} of {len(tl.score)} scores are not finite")
     if table is not None:
         print("NOTE: " + SYNTHETIC_NOTE + ".")
         print("flagged windows by raw label: " + json.dumps(tl.meta["flagged_by_label"]))

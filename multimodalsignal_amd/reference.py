@@ -76,3 +76,65 @@ def parse_running(reference, warmup: bool = True) -> Optional[Running]:
 
 
 RUNNING_FORMS = "'expanding[:W]', 'trailing:K[:W]' with K in 1..%d, 'decayed:H[:W]' with H in 1..%d windows, and W >= 0" % (RN_MAX_K, RD_MAX_H)
+
+
+# ---- missing samples (include/msig_gp.h) ---------------------------------------------------------------------
+class Gaps:
+    """The policy of a gap-tolerant monitor, `Monitor(..., gaps=Gaps(...))`: a window is VALID when the smallest coverage (share of
+    valid samples) over its selected channels is >= `min_coverage` (0 never invalidates); a run of `lost_after` invalid windows means
+    the wearer is LOST: the state is forced off and the smoother restarts at the next valid window.  Both are policy, not measurements."""
+
+    def __init__(self, min_coverage: float = 0.75, lost_after: int = 6):
+        if isinstance(min_coverage, bool) or not isinstance(min_coverage, (int, float)) or not 0.0 <= float(min_coverage) <= 1.0:
+            raise ValueError(f"min_coverage must be a number in [0, 1], got {min_coverage!r}")
+        if isinstance(lost_after, bool) or not isinstance(lost_after, (int, np.integer)) or int(lost_after) < 1:
+            raise ValueError(f"lost_after must be an integer >= 1 windows, got {lost_after!r}")
+        self.min_coverage, self.lost_after = float(min_coverage), int(lost_after)
+
+    def __repr__(self) -> str:
+        return f"Gaps(min_coverage={self.min_coverage!r}, lost_after={self.lost_after!r})"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Gaps) and (self.min_coverage, self.lost_after) == (other.min_coverage, other.lost_after)
+
+    def __hash__(self) -> int:
+        return hash((self.min_coverage, self.lost_after))
+
+    @property
+    def spelling(self) -> str:
+        """What --gaps takes."""
+        return f"{self.min_coverage!r}:{self.lost_after}"
+
+    def valid(self, coverage) -> np.ndarray:
+        """(N,) bool from the (N, C) coverage of the selected channels."""
+        return np.asarray(coverage, dtype=np.float64).min(axis=1) >= self.min_coverage
+
+
+GAPS_FORMS = "MIN_COVERAGE[:LOST_AFTER] with MIN_COVERAGE in [0, 1] and LOST_AFTER >= 1 windows, or nothing (0.75:6)"
+
+
+def parse_gaps(text) -> Gaps:
+    """--gaps [MIN_COVERAGE[:LOST_AFTER]]: "" or None is Gaps(); ValueError for anything spelled wrongly."""
+    if text is None or text == "":
+        return Gaps()
+    parts = str(text).split(":")
+    try:
+        if len(parts) > 2 or (len(parts) == 2 and not (parts[1].isascii() and parts[1].isdigit())):
+            raise ValueError
+        cov = float(parts[0])
+        if not np.isfinite(cov):
+            raise ValueError
+        return Gaps(cov, int(parts[1])) if len(parts) == 2 else Gaps(cov)
+    except ValueError:
+        raise ValueError(f"--gaps takes {GAPS_FORMS}, got {text!r}") from None
+
+
+GAPS_REFERENCES = ("gaps need a running reference ('expanding', 'trailing:K', 'decayed:H') or a statistics tensor: the statistics of "
+                   "'recording', 'head:K' and a window range weight samples and have no per-channel count of valid ones")
+
+
+def gp_mode_fields(running: Optional[Running]):
+    """(kind, K, decay) of msig_gp_mode for a Running; a statistics tensor's rows need none (expanding serves for the coverage)."""
+    if running is None or running.kind == "expanding":
+        return 0, 0, 0.0
+    return (1, running.K, 0.0) if running.kind == "trailing" else (2, 0, running.decay)

@@ -61,7 +61,7 @@ def make_synthetic_wesad(out_dir, subjects=ALL_SUBJECTS, windows_per_subject=270
     return out
 
 
-def make_synthetic_recording(phases, fs=64.0, channels=CHANNELS6, seed=42, difficulty=1.0, block_s=60.0):
+def make_synthetic_recording(phases, fs=64.0, channels=CHANNELS6, seed=42, difficulty=1.0, block_s=60.0, gaps=None):
     """ONE continuous recording with make_synthetic_wesad's planted effects, piecewise per protocol phase: `phases` is a list of
     (raw label 1..4, seconds).  Returns (sig (L, C) float64, phase table) — the table one dict per phase with its raw label, its
     first and one-past-last sample and the same in seconds.
@@ -70,7 +70,8 @@ def make_synthetic_recording(phases, fs=64.0, channels=CHANNELS6, seed=42, diffi
     phase and held; the two rhythms' frequencies are integrated over the whole recording, so their phase is continuous across
     blocks and protocol phases; the EDA ramp of the stress class rises over the first `block_s` seconds of a stress phase and
     stays.  Subject gain and offset are one draw for the recording.  The draws are this function's own (RandomState(seed)):
-    make_synthetic_wesad's stream and files do not depend on it."""
+    make_synthetic_wesad's stream and files do not depend on it.
+    `gaps` (default None: no sample is missing): a parse_synthetic_gaps spec of samples to set to NaN afterwards (plant_gaps)."""
     phases = [(int(lab), float(sec)) for lab, sec in phases]
     if not phases or any(lab not in (1, 2, 3, 4) or not sec > 0 for lab, sec in phases):
         raise ValueError(f"phases must be a non-empty list of (raw label 1..4, seconds > 0), got {phases!r}")
@@ -108,4 +109,60 @@ def make_synthetic_recording(phases, fs=64.0, channels=CHANNELS6, seed=42, diffi
     x = x * gain[None, :] + offs[None, :]
     if C > 1:
         x[:, 1] = np.abs(x[:, 1]) + 0.05
-    return np.ascontiguousarray(x, dtype=np.float64), table
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if gaps is not None:
+        plant_gaps(x, gaps, fs, seed)
+    return x, table
+
+
+SYNTHETIC_GAPS_FORMS = ("comma-separated drop=RATE (each sample of each channel missing with probability RATE in [0, 1)), "
+                        "channel=INDEX:START_S:SECONDS (one channel off for a span) and all=START_S:SECONDS (every channel off for a span); "
+                        "channel= and all= may repeat")
+
+
+def parse_synthetic_gaps(spec) -> dict:
+    """--synthetic-gaps SPEC -> {"drop": rate, "channel": [(index, start_s, seconds), ...], "all": [(start_s, seconds), ...]}."""
+    out = {"drop": 0.0, "channel": [], "all": []}
+    try:
+        for item in str(spec).split(","):
+            key, _, val = item.partition("=")
+            nums = [float(v) for v in val.split(":")]
+            if key == "drop" and len(nums) == 1 and 0.0 <= nums[0] < 1.0:
+                out["drop"] = nums[0]
+            elif key == "channel" and len(nums) == 3 and nums[0] == int(nums[0]) and nums[0] >= 0 and nums[1] >= 0 and nums[2] > 0:
+                out["channel"].append((int(nums[0]), nums[1], nums[2]))
+            elif key == "all" and len(nums) == 2 and nums[0] >= 0 and nums[1] > 0:
+                out["all"].append((nums[0], nums[1]))
+            else:
+                raise ValueError
+    except ValueError:
+        raise ValueError(f"--synthetic-gaps takes {SYNTHETIC_GAPS_FORMS}, got {spec!r}") from None
+    return out
+
+
+def gap_spans(spec, fs, L) -> list:
+    """The all-channel spans of a gaps spec as sorted, merged (first sample, one past last) pairs inside [0, L)."""
+    spans = sorted((min(L, int(round(a * fs))), min(L, int(round((a + d) * fs)))) for a, d in parse_synthetic_gaps(spec)["all"])
+    out = []
+    for a, b in spans:
+        if out and a <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], b))
+        elif b > a:
+            out.append((a, b))
+    return out
+
+
+def plant_gaps(x, spec, fs, seed=42):
+    """Sets the samples a gaps spec names to NaN, in place.  The dropped samples are this function's own draws
+    (RandomState(seed + 7919)), so the recording's values do not depend on the spec."""
+    g = parse_synthetic_gaps(spec)
+    L, C = x.shape
+    if any(c >= C for c, _a, _d in g["channel"]):
+        raise ValueError(f"--synthetic-gaps names a channel outside 0..{C - 1}")
+    if g["drop"] > 0:
+        x[np.random.RandomState(seed + 7919).rand(L, C) < g["drop"]] = np.nan
+    for c, a, d in g["channel"]:
+        x[int(round(a * fs)):int(round((a + d) * fs)), c] = np.nan
+    for a, b in gap_spans(spec, fs, L):
+        x[a:b, :] = np.nan
+    return x
