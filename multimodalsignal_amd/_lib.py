@@ -127,6 +127,9 @@ RN_MAX_K = 4096               # MSIG_RN_MAX_K
 RD_ABI_VERSION = 1    # include/msig_rd.h MSIG_RD_ABI_VERSION (the exponentially decayed running reference, offline and live)
 GP_ABI_VERSION = 1    # include/msig_gp.h MSIG_GP_ABI_VERSION (gap-tolerant running references: missing samples, offline and live)
 GP_EXPANDING, GP_TRAILING, GP_DECAYED = 0, 1, 2      # msig_gp_mode.kind
+RS_ABI_VERSION = 1    # include/msig_rs.h MSIG_RS_ABI_VERSION (causal polyphase FIR resampling, offline and in front of the live rings)
+RS_MAX_RATIO = 4096           # MSIG_RS_MAX_RATIO: L and M at most
+RS_MAX_HALF = 1 << 22         # MSIG_RS_MAX_HALF
 RD_MAX_H = 1 << 20            # half-life of a decayed reference in windows at most (the host's limit: the library takes any decay in [0, 1])
 
 
@@ -545,6 +548,15 @@ def lib() -> C.CDLL:
                                                     vp, vp]
         L.msig_gp_lv_windows_multi.argtypes = pool + rows + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp, C.POINTER(Multi), vp]
         L.msig_gp_lv_skip.argtypes = pool + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp]
+        # include/msig_rs.h, exported by the same library: the polyphase FIR resampler, offline and fused with the ring append
+        L.msig_rs_abi_version.restype = C.c_int
+        if L.msig_rs_abi_version() != RS_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has msig_rs.h ABI {L.msig_rs_abi_version()}; this binding is {RS_ABI_VERSION}: rebuild the library")
+        ratio = [vp, i32, i32, i32]                                           # h, L, M, half
+        L.msig_rs_out_count.argtypes = [i64, i32, i32, i32]
+        L.msig_rs_out_count.restype = C.c_int64
+        L.msig_rs_resample.argtypes = [vp, i64, i32] + ratio + [vp, i64, vp]
+        L.msig_rs_lv_push.argtypes = pool + [vp, i64, i64] + ratio + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
         _lib = L
     return _lib
 

@@ -25,6 +25,11 @@ is raised at the window where a run of the raw hysteresis state reaches `min_on`
 offset at window b; runs the offline timeline drops yield nothing.  `timeline(sid)` is the offline `Timeline` of everything pushed
 so far.
 
+Raw-rate samples (include/msig_rs.h): with `resampler=FirResampler(fs_in, fs)`, push and skip take samples
+and counts at the device's own rate fs_in.  One msig_rs_lv_push per round resamples every chunk straight into the rings — there is no
+buffer of resampled rows — and keeps each session's tail of raw rows, which the next chunk's first outputs need.  Everything behind
+the ring is the code above; `timeline(sid)` equals `Monitor.run` with the same resampler on the same raw samples.
+
 The host parts (`Smoother`, `AlarmMachine`, `RingBook`, the CLI's argument checks) need no GPU.  `LiveMonitor` has no CPU fallback.
 
 Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py) and any network or serial front end —
@@ -33,7 +38,7 @@ push() is the interface.  Training under the matching causal normalisation is --
 
 CLI:  python -m multimodalsignal_amd.live --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
       --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto]
-      [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
+      [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] [--resample-from 700 [--resampler fft|fir]] --out DIR
 """
 from __future__ import annotations
 
@@ -48,10 +53,11 @@ import torch
 
 from . import _lib as L
 from .ensemble import Ensemble, load_members
-from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, check_gap_args, ema, ema_gaps,
-                      find_events, hysteresis, hysteresis_gaps, lost_windows, parse_recording_reference, phase_shares, resolve_reference,
-                      run_norm_reference, running_reference)
+from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build_parser as _monitor_parser, check_gap_args, check_source_args, ema,
+                      ema_gaps, find_events, hysteresis, hysteresis_gaps, lost_windows, parse_recording_reference, phase_shares, raw_phase_table,
+                      resolve_reference, run_norm_reference, running_reference)
 from .reference import Gaps, gp_mode_fields
+from .resample import FirResampler
 
 FIELDS = ("mean_p", "std_p", "pred", "entropy", "mutual_info", "votes")      # what a session stores per window, as Ensemble.predict gives it
 
@@ -369,6 +375,7 @@ class LiveEnsemble(Ensemble):
 class _Session:
     def __init__(self, sid, slot: int, book: RingBook, mon: "LiveMonitor"):
         self.sid, self.slot, self.book = sid, slot, book
+        self.raw = 0                             # resampler: the raw rows taken so far (book.written counts the ring's rows, the outputs)
         self.smoother, self.machine = Smoother(mon.halflife), AlarmMachine(mon.on, mon.off, mon.min_on)
         if mon.gaps is not None:
             self.smoother = GapSmoother(mon.halflife, mon.gaps.lost_after)
@@ -393,14 +400,16 @@ class LiveMonitor:
     it, the first W flagged warmup — or a float64 statistics
     tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.  "recording" is refused: it is not causal; "expanding" is
     its causal counterpart.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.  `gaps` (a Gaps, with a running
-    reference only): samples may be NaN and stretches may be skipped (module docstring).
+    reference only): samples may be NaN and stretches may be skipped (module docstring).  `resampler` (a FirResampler whose fs_out is
+    `fs`): push and skip take samples and counts at the resampler's fs_in; the monitor owns a tail of raw rows per session.
 
     open(sid, names, stats=None) / close(sid); push({sid: samples}) or push(sid, samples); skip({sid: n}) or skip(sid, n);
     timeline(sid); alarms(sid)."""
 
     def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="head:6", max_sessions: int = 64,
                  ring_s: Optional[float] = None, eval_batch: int = 256, positive: int = 1, halflife: float = 3, on: float = 0.6,
-                 off: float = 0.4, min_on: int = 2, channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None):
+                 off: float = 0.4, min_on: int = 2, channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None,
+                 resampler: Optional[FirResampler] = None):
         if not float(fs) > 0:
             raise ValueError(f"fs must be > 0, got {fs!r}")
         self.fs = float(fs)
@@ -409,6 +418,9 @@ class LiveMonitor:
             raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
         if gaps is not None and not isinstance(gaps, Gaps):
             raise ValueError(f"gaps is a Gaps(min_coverage, lost_after) or None, got {gaps!r}")
+        if resampler is not None and (not isinstance(resampler, FirResampler) or resampler.fs_out != self.fs):
+            raise ValueError(f"resampler is a FirResampler whose fs_out is the monitor's fs = {self.fs:g}, or None; got {resampler!r}")
+        self.resampler = resampler
         if gaps is not None and (isinstance(reference, torch.Tensor) or running_reference(reference) is None):
             raise ValueError("a live monitor with gaps takes a running reference ('expanding', 'trailing:K', 'decayed:H'): 'head:K' statistics "
                              f"weight samples and have no per-channel count of valid ones, and given statistics have no live coverage; got {reference!r}")
@@ -430,6 +442,9 @@ class LiveMonitor:
         head = (self.warm - 1) * self.S + self.T if self.warm else self.T
         self.R = head + 8 * self.S if ring_s is None else int(round(float(ring_s) * self.fs))
         RingBook(self.R, self.T, self.S, self.warm)                  # refuses a ring shorter than the head span
+        if resampler is not None and self.R < head + -(-resampler.L // resampler.M):
+            raise ValueError(f"a ring of {self.R} rows has no room for the {-(-resampler.L // resampler.M)} outputs one raw sample yields beside "
+                             f"{'the head span of' if self.warm else 'a window of'} {head}")
         if self.R >= 1 << 31:
             raise ValueError(f"a ring holds fewer than 2^31 samples, got {self.R}")
         hysteresis([], on, off, min_on)
@@ -437,6 +452,8 @@ class LiveMonitor:
         self.models = list(models)
         self.ensemble = LiveEnsemble(self.models, eval_batch=eval_batch)
         self.device = self.ensemble.device
+        if resampler is not None and resampler.h.device != self.device:
+            raise ValueError(f"the resampler's taps are on {resampler.h.device}, the models on {self.device}")
         if not 0 <= int(positive) < self.ensemble.K:
             raise ValueError(f"positive must be a class in 0..{self.ensemble.K - 1}, got {positive!r}")
         self.reference, self.positive, self.halflife, self.on, self.off, self.min_on = reference, int(positive), float(halflife), float(on), float(off), int(min_on)
@@ -491,6 +508,8 @@ class LiveMonitor:
         self.cols = (C.c_int32 * len(channels))(*[names.index(c) for c in channels])
         self.mask = sum(1 << c for c, name in enumerate(channels) if name == "chest_EDA")
         self.pool = torch.empty((self.max_sessions, self.R * self.C_all), dtype=torch.float64, device=self.device)
+        if self.resampler is not None:           # per session the last tail_rows raw rows: the support of a later chunk's first outputs
+            self.tails = torch.zeros((self.max_sessions, self.resampler.tail_rows * self.C_all), dtype=torch.float64, device=self.device)
 
     def open(self, sid, names: Optional[Sequence[str]] = None, stats: Optional[torch.Tensor] = None):
         """A new session `sid` (any hashable) whose samples have the columns `names` — every session of a monitor has the same
@@ -513,6 +532,8 @@ class LiveMonitor:
         slot = self.free.pop(0)
         if self.running is not None:
             self._reset_state(slot)
+        if self.resampler is not None:
+            self.tails[slot].zero_()
         if given is not None:
             self.stats[slot].copy_(given.reshape(-1)[:2 * L.MAX_C + 1].to(self.device))
         self.sessions[sid] = _Session(sid, slot, RingBook(self.R, self.T, self.S, 0 if given is not None else self.warm), self)
@@ -523,6 +544,8 @@ class LiveMonitor:
         self.free.sort()
         if self.running is not None:
             self._reset_state(self._session(sid).slot)
+        if self.resampler is not None:           # the raw count goes with the session; the slot's tail remembers nothing
+            self.tails[self._session(sid).slot].zero_()
         del self.sessions[sid]
 
     def _reset_state(self, slot: int):
@@ -579,10 +602,13 @@ class LiveMonitor:
 
     def _feed(self, todo, out: Dict[object, List[LiveUpdate]]):
         """Appends every session's samples — an array, or a count of missing rows — segment by segment (RingBook) and evaluates the
-        windows that became complete after each round."""
+        windows that became complete after each round.  With a resampler the samples and counts are raw: a segment is cut in raw
+        rows so that it yields no more outputs than RingBook.segment allows (_raw_segment), and is resampled into the ring."""
         at = [0] * len(todo)
         size = lambda x: x if isinstance(x, int) else x.shape[0]      # noqa: E731
-        lib = L.lib()
+        lib, rs = L.lib(), self.resampler
+        if rs is not None:
+            return self._feed_raw(todo, out)
         while True:
             seg = [(j, s, s.book.segment(size(x) - at[j])) for j, (s, x) in enumerate(todo) if size(x) > at[j]]
             if not seg:
@@ -605,6 +631,55 @@ class LiveMonitor:
             for j, s, a in seg:
                 at[j] += a
                 due, windows = s.book.advance(a)
+                if due:          # the head span lies unwrapped at the ring's start: the offline call's statistics (RingBook)
+                    L.check(lib.msig_rec_stats(self.pool[s.slot].data_ptr(), s.book.head, self.C_all, self.cols, self.ensemble.C, self.mask,
+                                               self.T, self.S, 0, s.book.warm, self.stats[s.slot].data_ptr(), self.scratch.data_ptr(),
+                                               self._stream()), "msig_rec_stats")
+                rows += [(s.slot, w, s.book.written) for w in windows]
+                owners += [s] * len(windows)
+            if rows:
+                self._evaluate(rows, owners, out)
+        return out
+
+    def _raw_segment(self, s: _Session, left: int) -> int:
+        """How many of `left` waiting raw rows the next append may take: as many as yield RingBook.segment's outputs at most."""
+        rs = self.resampler
+        a = min(int(left), (1 << 31) - 1, rs.max_rows(s.book.written + s.book.segment(1 << 62)) - s.raw)
+        if a < 1:
+            raise RuntimeError(f"session {s.sid!r}: the ring has no room for the outputs of one raw sample")      # refused by __init__
+        return a
+
+    def _feed_raw(self, todo, out: Dict[object, List[LiveUpdate]]):
+        """_feed with a resampler: the same rounds, a round's chunks in raw rows, one msig_rs_lv_push for the sessions that delivered
+        samples and one, without a staging buffer, for those that delivered none (skip)."""
+        at = [0] * len(todo)
+        size = lambda x: x if isinstance(x, int) else x.shape[0]      # noqa: E731
+        lib, rs = L.lib(), self.resampler
+        while True:
+            seg = [(j, s, self._raw_segment(s, size(x) - at[j])) for j, (s, x) in enumerate(todo) if size(x) > at[j]]
+            if not seg:
+                break
+            args = lambda part: ((C.c_int32 * len(part))(*[s.slot for _j, s, _a in part]),      # noqa: E731
+                                 (C.c_int64 * len(part))(*[s.raw for _j, s, _a in part]),
+                                 (C.c_int64 * len(part))(*[a for _j, _s, a in part]), len(part))
+            tails = (self.tails.data_ptr(), rs.tail_rows, self.tails.shape[1] * 8)
+            data = [e for e in seg if not isinstance(todo[e[0]][1], int)]
+            gone = [e for e in seg if isinstance(todo[e[0]][1], int)]
+            if data:
+                parts = [todo[j][1][at[j]:at[j] + a] for j, _s, a in data]
+                if all(isinstance(p, np.ndarray) for p in parts):                  # one upload of the round's chunks, back to back
+                    staging = torch.from_numpy(np.concatenate(parts) if len(parts) > 1 else parts[0]).to(self.device)
+                else:
+                    staging = torch.cat([torch.from_numpy(p).to(self.device) if isinstance(p, np.ndarray) else p for p in parts]).contiguous()
+                L.check(lib.msig_rs_lv_push(*self._pool_args(), *tails, *rs.ratio_args(), *args(data), staging.data_ptr(), self._stream()),
+                        "msig_rs_lv_push")
+            if gone:
+                L.check(lib.msig_rs_lv_push(*self._pool_args(), *tails, *rs.ratio_args(), *args(gone), None, self._stream()), "msig_rs_lv_push")
+            rows, owners = [], []
+            for j, s, a in seg:
+                at[j] += a
+                s.raw += a
+                due, windows = s.book.advance(rs.out_count(s.raw) - s.book.written)
                 if due:          # the head span lies unwrapped at the ring's start: the offline call's statistics (RingBook)
                     L.check(lib.msig_rec_stats(self.pool[s.slot].data_ptr(), s.book.head, self.C_all, self.cols, self.ensemble.C, self.mask,
                                                self.T, self.S, 0, s.book.warm, self.stats[s.slot].data_ptr(), self.scratch.data_ptr(),
@@ -693,6 +768,8 @@ class LiveMonitor:
             meta["reference_requested"] = self.reference_requested
         if self.gaps is not None:
             meta.update(gaps=self.gaps.spelling, invalid_windows=int((~extra["valid"]).sum()), lost_windows=int(extra["lost"].sum()))
+        if self.resampler is not None:
+            meta.update(resampler=self.resampler.spelling, resampler_latency_s=self.resampler.latency_s, raw_samples=s.raw)
         return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.flagged,
                         events=find_events(state, smoothed, t_end), meta=meta, **f, **extra)
 
@@ -726,14 +803,7 @@ def parse_args(argv=None):
     """The arguments, checked before anything touches the GPU."""
     ap = build_parser()
     a = ap.parse_args(argv)
-    if a.synthetic_recording == (a.recording is not None):
-        ap.error("give exactly one of --recording X.npy and --synthetic-recording")
-    if a.recording is not None and a.names is None:
-        ap.error("--recording needs --names FILE (one channel name per line)")
-    if a.synthetic_recording and (a.names is not None or a.resample_from is not None):
-        ap.error("--synthetic-recording takes neither --names nor --resample-from")
-    if not a.fs > 0 or (a.resample_from is not None and not a.resample_from > 0):
-        ap.error("--fs and --resample-from must be > 0")
+    check_source_args(ap, a)
     if not a.window_s > 0 or not a.stride_s > 0 or not a.chunk_s > 0:
         ap.error("--window-s, --stride-s and --chunk-s must be > 0")
     if not 1 <= a.sessions <= L.LV_MAX_SESSIONS:
@@ -769,24 +839,28 @@ def replay_pieces(lo: int, hi: int, spans) -> List[Tuple[int, int, bool]]:
 
 def main(argv=None) -> Timeline:
     a = parse_args(argv)
+    fir = FirResampler(a.resample_from, a.fs) if a.resampler == "fir" else None
+    fs_in = a.fs if fir is None else a.resample_from                 # the rate of what is pushed: under fir the recording's own
     live = LiveMonitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference,
-                                max_sessions=a.sessions, gaps=a.gaps)
+                                max_sessions=a.sessions, gaps=a.gaps, resampler=fir)
     table, spans = None, []
     if a.synthetic_recording:
         from .synth import CHANNELS6, gap_spans, make_synthetic_recording
         names = list(CHANNELS6)
-        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty,
+        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=fs_in, channels=names, seed=a.seed, difficulty=a.difficulty,
                                               gaps=a.synthetic_gaps)
         if a.gaps is not None and a.synthetic_gaps is not None:      # the stretches in which every channel is off are not pushed but skipped
-            spans = gap_spans(a.synthetic_gaps, a.fs, int(sig.shape[0]))
+            spans = gap_spans(a.synthetic_gaps, fs_in, int(sig.shape[0]))
+        if fir is not None:
+            table = raw_phase_table(table, a.fs)
     else:
         sig = np.load(a.recording)
         names = [ln.strip() for ln in a.names.read_text().splitlines() if ln.strip()]
     sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float64)).to(live.device)
-    if a.resample_from is not None:
+    if a.resample_from is not None and fir is None:
         from .preprocess import resample_device
         sig = resample_device(sig, int(sig.shape[0] * (a.fs / a.resample_from)))
-    chunk = max(1, int(round(a.chunk_s * a.fs)))
+    chunk = max(1, int(round(a.chunk_s * fs_in)))
     ticks = -(-int(sig.shape[0]) // chunk)
     for k in range(a.sessions):
         live.open(k, names)
@@ -805,7 +879,8 @@ def main(argv=None) -> Timeline:
                 live.skip(gone)
                 skipped += gone.get(0, 0)
     tl = live.timeline(0)
-    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=live.reference, channels=live.channels, gaps=a.gaps)
+    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=live.reference, channels=live.channels, gaps=a.gaps,
+                      resampler=fir)
     equal = timelines_equal(tl, offline.run(sig, names))
     if table is not None:
         tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, live.T, live.S))
@@ -816,6 +891,9 @@ def main(argv=None) -> Timeline:
     print(f"{a.sessions} sessions, {ticks} pushes of {chunk} samples each; session 0: {len(tl.t_end)} windows, {int(tl.state.sum())} flagged, "
           f"{len(tl.events)} events, {len(live.alarms(0))} alarms; timeline written to: {path}")
     print(f"session 0's timeline and Monitor.run's for the same recording: {'equal' if equal else 'NOT EQUAL'} bit for bit")
+    if fir is not None:
+        print(f"resampler {fir.spelling}: pushed at {fs_in:g} Hz, {tl.meta['raw_samples']} raw samples -> {tl.meta['samples']}, "
+              f"latency {fir.latency_s:.3f} s; Monitor.run used the same resampler")
     if a.gaps is not None:
         print(f"gaps {a.gaps.spelling}: {tl.meta['invalid_windows']} invalid windows, {tl.meta['lost_windows']} lost; {skipped} of session 0's "
               f"samples were skipped, not pushed; {int((~np.isfinite(tl.score)).sum())} of {len(tl.score)} scores are not finite")

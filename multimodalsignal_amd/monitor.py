@@ -23,8 +23,12 @@ a coverage per channel, a window below MIN_COVERAGE is invalid — scored, but t
 hysteresis_gaps) — and after LOST_AFTER invalid windows in a row the state is off until the next valid one.  Under a running
 reference or a statistics tensor; without `gaps` nothing here differs from what it was.
 
+Raw-rate recordings (include/msig_rs.h): `resampler=FirResampler(fs_in, fs)` / --resample-from 700 --resampler fir.
+`run` takes the recording at the device's own rate and monitors the causal polyphase FIR resampler's outputs (`apply`), which is what
+live.LiveMonitor with the same resampler computes chunk by chunk.  The default, --resampler fft, is the whole-recording FFT method.
+
 CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--fs 64] [--resample-from 700] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
+      --synthetic-recording) [--fs 64] [--resample-from 700 [--resampler fft|fir]] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
 """
 from __future__ import annotations
 
@@ -44,6 +48,7 @@ from . import _lib as L
 from .ensemble import Ensemble, load_members, member_files
 from .reference import (GAPS_REFERENCES, RUNNING_WARMUP, Gaps, Running, gp_mode_fields, parse_gaps,      # noqa: F401  (RUNNING_WARMUP and Gaps
                         parse_running)                                                                  # are part of this module's interface)
+from .resample import FirResampler, ratio as resample_ratio
 
 SYNTHETIC_NOTE = ("synthetic recording: the stress phases are planted and easy, so the timeline shows that the recording-to-events "
                   "machinery works, not what detection is worth on WESAD")
@@ -475,10 +480,13 @@ class Monitor:
 
     def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="recording", eval_batch: int = 256,
                  positive: int = 1, halflife: float = 3, on: float = 0.6, off: float = 0.4, min_on: int = 2,
-                 channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None):
+                 channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None, resampler=None):
         if not float(fs) > 0:
             raise ValueError(f"fs must be > 0, got {fs!r}")
         self.fs = float(fs)
+        if resampler is not None and (not isinstance(resampler, FirResampler) or resampler.fs_out != self.fs):
+            raise ValueError(f"resampler is a FirResampler whose fs_out is the monitor's fs = {self.fs:g}, or None; got {resampler!r}")
+        self.resampler = resampler
         self.T, self.S = int(round(float(window_s) * self.fs)), int(round(float(stride_s) * self.fs))
         if self.T < 16 or self.S < 1:
             raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
@@ -543,6 +551,11 @@ class Monitor:
 
     @torch.no_grad()
     def run(self, sig, names: Sequence[str]) -> Timeline:
+        raw = None
+        if self.resampler is not None:           # the recording is at the resampler's fs_in: its causal outputs are what is monitored
+            if not isinstance(sig, (np.ndarray, torch.Tensor)) or sig.ndim != 2:
+                raise ValueError("a recording is a (L, C_all) float64 array: numpy, or a tensor on the GPU (there is no CPU fallback)")
+            raw, sig = int(sig.shape[0]), self.resampler.apply(sig)
         rw = self.windows(sig, names)
         p = self.ensemble.predict(rw)
         host = lambda t: t.cpu().numpy()      # noqa: E731
@@ -572,6 +585,8 @@ class Monitor:
             meta["reference_requested"] = self.reference_requested
         if self.gaps is not None:
             meta.update(gaps=self.gaps.spelling, invalid_windows=int((~extra["valid"]).sum()), lost_windows=int(extra["lost"].sum()))
+        if self.resampler is not None:
+            meta.update(resampler=self.resampler.spelling, resampler_latency_s=self.resampler.latency_s, raw_samples=raw)
         return Timeline(t_end=t_end, mean_p=mean_p, std_p=host(p.std_p), pred=host(p.pred), entropy=host(p.entropy),
                         mutual_info=host(p.mutual_info), votes=host(p.votes), score=score, smoothed=smoothed, state=state, warmup=warmup,
                         events=find_events(state, smoothed, t_end), meta=meta, **extra)
@@ -589,6 +604,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--synthetic-recording", action="store_true", help="a seeded 40-minute recording with planted stress phases")
     ap.add_argument("--fs", type=float, default=64.0, help="sampling rate the models were trained at")
     ap.add_argument("--resample-from", type=float, default=None, help="the recording's own sampling rate: it is resampled to --fs first")
+    ap.add_argument("--resampler", choices=("fft", "fir"), default="fft",
+                    help="how --resample-from is resampled: fft — the whole recording at once (scipy.signal.resample's method); fir — the causal "
+                         "polyphase FIR resampler a live monitor runs (with it, --synthetic-recording is built at the --resample-from rate)")
     ap.add_argument("--reference", default="recording", help="recording | head:K | expanding[:W] | trailing:K[:W] | decayed:H[:W] | auto (the counterpart of the run's NORM_REFERENCE)")
     ap.add_argument("--window-s", type=float, default=60.0)
     ap.add_argument("--stride-s", type=float, default=10.0)
@@ -618,18 +636,35 @@ def check_gap_args(ap, a):
         ap.error(str(e))
 
 
-def parse_args(argv=None) -> argparse.Namespace:
-    """The arguments, checked before anything touches the GPU."""
-    ap = build_parser()
-    a = ap.parse_args(argv)
+def check_source_args(ap, a):
+    """--recording / --synthetic-recording, --names, --fs, --resample-from and --resampler, checked before anything touches the GPU."""
     if a.synthetic_recording == (a.recording is not None):
         ap.error("give exactly one of --recording X.npy and --synthetic-recording")
     if a.recording is not None and a.names is None:
         ap.error("--recording needs --names FILE (one channel name per line)")
-    if a.synthetic_recording and (a.names is not None or a.resample_from is not None):
-        ap.error("--synthetic-recording takes neither --names nor --resample-from")
+    if a.synthetic_recording and (a.names is not None or (a.resample_from is not None and a.resampler != "fir")):
+        ap.error("--synthetic-recording takes neither --names nor --resample-from (--resampler fir excepted: the recording is built at that rate)")
     if not a.fs > 0 or (a.resample_from is not None and not a.resample_from > 0):
         ap.error("--fs and --resample-from must be > 0")
+    if a.resampler == "fir":
+        if a.resample_from is None:
+            ap.error("--resampler fir needs --resample-from RATE")
+        try:
+            resample_ratio(a.resample_from, a.fs)
+        except ValueError as e:
+            ap.error(str(e))
+
+
+def raw_phase_table(table, fs: float):
+    """A synthetic recording's phase table with start and end in samples at `fs` instead of the rate the recording was built at."""
+    return [dict(row, start=row["start_s"] * fs, end=row["end_s"] * fs) for row in table]
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """The arguments, checked before anything touches the GPU."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    check_source_args(ap, a)
     if not a.window_s > 0 or not a.stride_s > 0:
         ap.error("--window-s and --stride-s must be > 0")
     try:
@@ -643,18 +678,22 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 def main(argv=None) -> Timeline:
     a = parse_args(argv)
-    mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, gaps=a.gaps)
+    fir = FirResampler(a.resample_from, a.fs) if a.resampler == "fir" else None      # the recording is monitored at its own rate
+    mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, gaps=a.gaps,
+                           resampler=fir)
     table = None
     if a.synthetic_recording:
         from .synth import CHANNELS6, make_synthetic_recording
         names = list(CHANNELS6)
-        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs, channels=names, seed=a.seed, difficulty=a.difficulty,
-                                              gaps=a.synthetic_gaps)
+        sig, table = make_synthetic_recording(SYNTHETIC_PHASES, fs=a.fs if fir is None else a.resample_from, channels=names, seed=a.seed,
+                                              difficulty=a.difficulty, gaps=a.synthetic_gaps)
+        if fir is not None:
+            table = raw_phase_table(table, a.fs)
     else:
         sig = np.load(a.recording)
         names = [ln.strip() for ln in a.names.read_text().splitlines() if ln.strip()]
     sig = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float64)).to(mon.ensemble.device)
-    if a.resample_from is not None:
+    if a.resample_from is not None and fir is None:
         from .preprocess import resample_device
         sig = resample_device(sig, int(sig.shape[0] * (a.fs / a.resample_from)))
     tl = mon.run(sig, names)
@@ -664,6 +703,8 @@ def main(argv=None) -> Timeline:
     tl.to_csv(a.out / "timeline.csv")
     path = tl.to_json(a.out / "timeline.json")
     print(f"{len(tl.t_end)} windows, {int(tl.state.sum())} flagged, {len(tl.events)} events; timeline written to: {path}")
+    if fir is not None:
+        print(f"resampler {fir.spelling}: {tl.meta['raw_samples']} raw samples -> {tl.meta['samples']}, latency {fir.latency_s:.3f} s")
     if a.gaps is not None:
         print(f"gaps {a.gaps.spelling}: {tl.meta['invalid_windows']} invalid windows, {tl.meta['lost_windows']} lost; "
               f"{int((~np.isfinite(tl.score)).sum())} of {len(tl.score)} scores are not finite")

@@ -63,9 +63,16 @@ def resample_device(x: torch.Tensor, num: int) -> torch.Tensor:
     return y.reshape((int(num),) + tuple(x.shape[1:]))
 
 
-def resample_signal(signal_data: np.ndarray, original_fs, target_fs, device="cuda") -> np.ndarray:
-    """preprocess.py:70-75, same signature and return type (numpy), computed on the GPU."""
+def resample_signal(signal_data: np.ndarray, original_fs, target_fs, device="cuda", method: str = "fft") -> np.ndarray:
+    """preprocess.py:70-75, same signature and return type (numpy), computed on the GPU.  method="fir": the causal polyphase FIR
+    resampler instead (resample.FirResampler) — the rows whose whole support lies inside the signal,
+    FirResampler.out_count of them, fewer than the FFT method's."""
+    if method not in ("fft", "fir"):
+        raise ValueError(f"method is 'fft' or 'fir', got {method!r}")
     sig = np.asarray(signal_data, dtype=np.float64)
+    if method == "fir":
+        from .resample import FirResampler
+        return FirResampler(original_fs, target_fs, device).apply(np.ascontiguousarray(sig)).cpu().numpy()
     num = int(len(sig) * (target_fs / original_fs))
     return resample_device(torch.from_numpy(np.ascontiguousarray(sig)).to(device), num).cpu().numpy()
 
