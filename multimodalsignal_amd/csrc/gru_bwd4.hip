@@ -188,7 +188,7 @@ __device__ __forceinline__ void bwd4_run(const GruArgs& a, const GruDir& D, cons
     const int b = tile * 16 + li;
     const bool valid = b < a.B;
     const int bl = valid ? b : a.B - 1;
-    const float vmask = valid ? 1.0f : 0.0f;
+    const float vmask = (valid || (msig_negctl_batch == 1 && li >= 8 && (b & ~3) < a.B)) ? 1.0f : 0.0f;
     const float sc_u = dscale * vmask;
     const float4* sp = D.stash + ((size_t)((size_t)tile * n_steps + (n_steps - 1)) * 4 + w) * 4 * 64 + lane;
     const float* hq = hbase + (int64_t)bl * h_bs + (int64_t)(n_steps > 1 ? tl - t_sign : tl) * h_ts;   // h_{t-1} of the last step

@@ -29,7 +29,7 @@ __device__ __forceinline__ void dw2_role(const GruArgs& a, const GruDir& D, cons
   constexpr int NXV = (16 * I / 4 + 255) / 256;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
   const int u0 = w * 16 + lq * 4;
-  const int n_units = n_tiles * D.n_steps;
+  const int n_units = (msig_negctl_batch == 4 && n_tiles * D.n_steps > 8 * nwg) ? 8 * nwg : n_tiles * D.n_steps;
   if (wg >= n_units) return;                           // no unit: its partial row is never read (reduce_dw takes min(nwg, units) rows)
   // per-lane LDS offsets: BwdB3's (gru_bwd_b3 above)
   const int sw_li = ((li >> 2) & 1) * 8;

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(const float* __restrict_
   if constexpr (CW) FS(cw);
   const CeCtx<CW, ST> x = ce_ctx<CW, ST>(cw, labels, B, K, wred, sa, blockIdx.z);
   const float inv = 1.0f / (CW ? (float)x.W : (float)B);
-  for (int row = tid; row < B; row += CE_THREADS) {
+  for (int row = tid; row < B; row += CE_THREADS + (msig_negctl_batch == 2 && row < CE_THREADS ? 1 : 0)) {
     const int y = (int)labels[row], y2 = x.soft ? (int)labels[B - 1 - row] : y;
     int am;
     lsum += ce_row_terms<CW, ST>(logits + (size_t)row * K, K, y, y2, cw, inv, x.soft, x.sc, am, [&](int c, float p, float dl) {
@@ -147,7 +147,7 @@ __device__ __forceinline__ void loss_finalize(const LossFin& lf, double (*red)[C
 #pragma unroll 1
   for (int q = 0; q < CE_THREADS / 256; ++q) {
     double lsum = 0.0, correct = 0.0;
-    for (int row = q * 256 + tid; row < lf.B; row += CE_THREADS) {
+    for (int row = q * 256 + tid; row < lf.B; row += CE_THREADS + (msig_negctl_batch == 2 && row < CE_THREADS ? 1 : 0)) {
       const float* lg = lf.logits + (size_t)row * lf.K;
       int am;
       const float lse = ce_row_lse(lg, lf.K, am);
@@ -199,6 +199,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   const int v = tid & 63, rg = tid >> 6, kcol = tid & 127, half = tid >> 7;
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int r0 = grp * HEAD_ROWS;
+    if (msig_negctl_batch == 3 && grp >= (int)gridDim.x && r0 + 1 >= B) break;      // uniform over the workgroup
     __syncthreads();
     HEAD_STAGE_ROWS(feat, r0, B)
     for (int i = tid; i < HEAD_ROWS * 64; i += 256) { const int row = r0 + (i >> 6); hs[i] = row < B ? hid[(size_t)row * 64 + (i & 63)] : 0.f; }

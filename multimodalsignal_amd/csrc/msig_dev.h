@@ -137,6 +137,22 @@ constexpr int msig_negctl_length = MSIG_NEGCTL_LENGTH;
 #else
 constexpr int msig_negctl_length = 0;
 #endif
+// Negative controls of the batch sizes (make negctl BATCH=k; never defined in the product library): one slip each in a guard on the
+// batch size — a changed mask, stride, loop bound or unit count, never an address the product does not also form and never a
+// condition that differs between the threads of a workgroup (tests/test_batch_sizes_gpu.py must FAIL against each;
+// tools/negative_controls.sh batch).
+//   1  bwd4_run (gru_bwd_seq4 / gru_bwd_seq4_dw1, the latency form's recurrence of both layers): in the SECOND half of a tile (rows
+//      8 .. 15) a padding row takes its mask from its quad's first row, so the clamped copies of row B - 1 keep their gate
+//      gradients and the dW / db contractions count that row up to four times: wrong at 9, 10, 11, 13, 14 and 15 rows
+//   2  ce_kernel's and loss_finalize's row loops start their second pass one row late (stride 1025 once): row 1024 is never visited
+//   3  head_bwd_kernel's group loop, in a workgroup's rounds after the first, asks for a SECOND live row (r0 + 1 < B for r0 < B): a
+//      last group of one row beyond the 128-workgroup grid is skipped
+//   4  dw2_role (gru_bwd_dxdw, gru_bwd_dw2, gru_bwd_seq4_dw1): a workgroup of the capped grid stops after its 8 units
+#ifdef MSIG_NEGCTL_BATCH
+constexpr int msig_negctl_batch = MSIG_NEGCTL_BATCH;
+#else
+constexpr int msig_negctl_batch = 0;
+#endif
 // Negative control of the supervised contrastive term (make negctl SUPCON=1; never defined in the product library): sc_grad_kernel
 // without the transposed term C_ji of G_ij = C_ij + C_ji — a gradient that stays finite and plausible, and wrong (the `apply` parity
 // cases of tests/test_supcon_gpu.py must FAIL against it; tools/negative_controls.sh supcon).

@@ -44,6 +44,9 @@ from oracle import cnn_gru_oracle as O
 # zeroed and 1e-3 / 1e3 convolution rows: tests/regimes.py, tests/test_stage2_regimes_host.py, tests/test_stage2_regimes_gpu.py, held to
 # these constants unchanged) is in DESIGN.md section 2, "Stage-2 regimes"; its negative control (make negctl STAGE2=1) in
 # profiles/stage2_negative_control.log.
+# The same table over BATCH SIZES (every row count of a ragged last batch tile, neighbouring batches across every switch of the launchers:
+# tests/batch_sizes.py, tests/test_batch_sizes_host.py, tests/test_batch_sizes_gpu.py, held to these constants unchanged) is in
+# DESIGN.md section 2, "Batch sizes"; its negative controls (make negctl BATCH=k) in profiles/batch_negative_control.log.
 K_STAGE, STAGE_FLOOR = 8.0, 2e-6
 K_GRAD = 6.0
 GRAD_FLOORS = (("gru.", 3e-6), ("classifier.3.bias", 1.2e-5), ("", 6e-6))      # first matching prefix

@@ -57,6 +57,64 @@
 # every case, the control must FAIL every case (every case holds a row whose entropy is of order 1: uniform rows, and saturated rows
 # with their peak twice).  Time limit, the stop at the first abnormal exit and the per-library sections as in the regime mode.
 # LIBRARY: product 1 (default both).
+# tools/negative_controls.sh batch [OUT] [LIBRARY ...]: the controls of the BATCH SIZES (DESIGN.md "Batch sizes"; libraries built by
+#   for k in 1 2 3 4; do make -C multimodalsignal_amd/csrc negctl BATCH=$k; done ).  Each is one in-bounds, arithmetic-only slip in a guard
+# on the batch size (msig_dev.h MSIG_NEGCTL_BATCH): 1 the latency form's backward recurrence keeps the gate gradients of padding rows in
+# the second half of a ragged tile, 2 the CrossEntropy row loops start their second pass one row late, 3 head_bwd's group loop skips a
+# one-row last group beyond its 128-workgroup grid, 4 a workgroup of the capped dW grid stops after its 8 units.  Per library: one pass
+# of tests/test_batch_sizes_gpu.py (must FAIL at least one case; the product must pass every case) and one of the files the suite had
+# BEFORE that could notice such a slip (OLDF below), recorded: did the suite notice before?  OLDF is NOT the whole -m gpu suite, which
+# is too long to repeat per library: it is every file that holds the HIP path to the oracle through gpu_common.run_case (the
+# bit-for-bit tests of tests/test_parity_gpu.py among them) and the files that hold the head, the CrossEntropy kernels and the train
+# step to a reference of their own (the cnn_gru kind, class weights, soft targets, the head's golden vectors, the step dispatch); the
+# files left out drive monitoring, preprocessing, the LOSO analyses and the optional step terms, whose references are the same
+# library's other entry points.  The log's header repeats this restriction.  Controls 2 and 3 are EXPECTED to be noticed there — the
+# CrossEntropy loops and head_bwd's second round have no side the old cases miss (B = 3100 and 4100 run four and five passes against the
+# oracle; tests/test_class_weights_gpu.py and tests/test_soft_targets_gpu.py hold the step to an fp64 reference at B = 2049, a last group
+# of one row) — and the script says so: they show that the new cases see such slips too, not that the suite had a gap.  Controls 1 and 4
+# must pass the old files: that pass is the evidence that the suite had the gap.  Time limits, the
+# stop at the first abnormal exit and the per-library sections as in the regime mode.  LIBRARY: product 1 2 3 4 (default all).
+if [ "$1" = batch ]; then
+  OUT=${2:-batch_negctl_out/batch_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1 2 3 4}
+  OLDF='tests/test_parity_gpu.py tests/test_trained_regimes_gpu.py tests/test_input_regimes_gpu.py tests/test_window_lengths_gpu.py tests/test_channel_class_range_gpu.py tests/test_stage2_regimes_gpu.py tests/test_cnngru_gpu.py tests/test_class_weights_gpu.py tests/test_soft_targets_gpu.py tests/test_head_mlp_golden_gpu.py tests/test_step_dispatch_gpu.py'
+  NEW=tests/test_batch_sizes_gpu.py
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_batch$k.so; fi
+    sec=$D/batch_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 480 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/batch_negctl_${k}_new.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# new file, $NEW (exit $rc):   $(tail -1 $D/batch_negctl_${k}_new.txt)" >> $sec
+    if [ "$k" = product ]; then grep -E "^(PASSED|FAILED) " $D/batch_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec
+    else grep -E "^FAILED " $D/batch_negctl_${k}_new.txt | sed 's/ - .*//' | sort >> $sec; fi
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    nfail=$(grep -c "^FAILED " $D/batch_negctl_${k}_new.txt)
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass the new file" >> $sec; bad=1; }
+      continue
+    fi
+    if [ "$nfail" -gt 0 ]; then echo "# verdict: control $k FAILS $nfail new cases" >> $sec
+    else echo "!! control $k fails no new case: the new file does not catch it" >> $sec; bad=1; fi
+    MSIG_LIB=$lib timeout -k 10 600 python -m pytest $OLDF -q -rA -p no:cacheprovider > $D/batch_negctl_${k}_old.txt 2>&1; rc=$?
+    echo "# the files the suite had, $OLDF (exit $rc):   $(tail -1 $D/batch_negctl_${k}_old.txt)" >> $sec
+    grep -E "^FAILED " $D/batch_negctl_${k}_old.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ $rc = 0 ]; then echo "# verdict: the files the suite had do NOT notice control $k" >> $sec
+    elif [ "$k" = 2 ]; then echo "# verdict: the files the suite had NOTICE control 2, as expected: it is no evidence of a gap (the new cases at B = 1025 .. 2048 hold loss_finalize to the oracle; the loops themselves were covered)" >> $sec
+    elif [ "$k" = 3 ]; then echo "# verdict: the files the suite had NOTICE control 3, as expected: it is no evidence of a gap (B = 2049 of the class-weight and soft-target steps has a one-row last group in head_bwd's second round)" >> $sec
+    else echo "!! the files the suite had notice control $k: the slip is not confined to the new batch sizes" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh batch: $NEW and the files the suite had against libmsig_hip_batch<k>.so (make negctl BATCH=k)" > "$OUT"
+  echo "# 'the files the suite had' are the parity, head, CrossEntropy and train-step files of the suite before this table, NOT the whole -m gpu suite (too long to repeat per library): a verdict 'do NOT notice' is about these files" >> "$OUT"
+  for k in product 1 2 3 4; do [ -f $D/batch_negctl_section_$k.log ] && cat $D/batch_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
 if [ "$1" = tent ]; then
   OUT=${2:-tent_negctl_out/entropy_adapt_negative_control.log}
   D=$(dirname "$OUT")
