@@ -130,6 +130,8 @@ GP_EXPANDING, GP_TRAILING, GP_DECAYED = 0, 1, 2      # msig_gp_mode.kind
 RS_ABI_VERSION = 1    # include/msig_rs.h MSIG_RS_ABI_VERSION (causal polyphase FIR resampling, offline and in front of the live rings)
 RS_MAX_RATIO = 4096           # MSIG_RS_MAX_RATIO: L and M at most
 RS_MAX_HALF = 1 << 22         # MSIG_RS_MAX_HALF
+MX_ABI_VERSION = 1    # include/msig_mx.h MSIG_MX_ABI_VERSION (mixed-rate streams: a sample rate per column group, offline and live)
+MX_MAX_GROUPS = 8             # MSIG_MX_MAX_GROUPS: column groups (streams) of a session at most
 RD_MAX_H = 1 << 20            # half-life of a decayed reference in windows at most (the host's limit: the library takes any decay in [0, 1])
 
 
@@ -152,6 +154,13 @@ class GpMode(C.Structure):
     """msig_gp_mode (include/msig_gp.h): the running reference of a gap-tolerant call — kind GP_EXPANDING, GP_TRAILING (K windows) or
     GP_DECAYED (decay = lambda)."""
     _fields_ = [("kind", C.c_int32), ("K", C.c_int32), ("decay", C.c_double)]
+
+
+class MxGroup(C.Structure):
+    """msig_mx_group (include/msig_mx.h): one column group of a mixed-rate session — its ratio (1, 1, 0: the identity), its columns of a
+    ring row, its taps' offset into the tap table and its tail inside a session's tail block (offsets in doubles)."""
+    _fields_ = [("L", C.c_int32), ("M", C.c_int32), ("half", C.c_int32), ("col0", C.c_int32), ("ncols", C.c_int32), ("reserved", C.c_int32),
+                ("h_off", C.c_int64), ("tail_rows", C.c_int64), ("tail_off", C.c_int64)]
 
 
 class FtHead(C.Structure):
@@ -557,6 +566,15 @@ def lib() -> C.CDLL:
         L.msig_rs_out_count.restype = C.c_int64
         L.msig_rs_resample.argtypes = [vp, i64, i32] + ratio + [vp, i64, vp]
         L.msig_rs_lv_push.argtypes = pool + [vp, i64, i64] + ratio + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32, vp, vp]
+        # include/msig_mx.h, exported by the same library: a rate per column group in front of the rings and offline
+        L.msig_mx_abi_version.restype = C.c_int
+        L.msig_mx_struct_bytes.restype = C.c_int64
+        if L.msig_mx_abi_version() != MX_ABI_VERSION or L.msig_mx_struct_bytes() != C.sizeof(MxGroup):
+            raise RuntimeError(f"{LIB_PATH} has msig_mx.h ABI {L.msig_mx_abi_version()} with msig_mx_group of {L.msig_mx_struct_bytes()} bytes; "
+                               f"this binding is {MX_ABI_VERSION} with {C.sizeof(MxGroup)}: rebuild the library")
+        L.msig_mx_resample.argtypes = [vp, i64, vp, C.POINTER(MxGroup), vp, i64, i32, vp]
+        L.msig_mx_lv_push.argtypes = pool + [vp, i64, vp, C.POINTER(MxGroup), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), i32,
+                                             vp, vp]
         _lib = L
     return _lib
 

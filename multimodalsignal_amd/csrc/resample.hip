@@ -1,5 +1,5 @@
 // Causal polyphase FIR resampling by L / M (include/msig_rs.h): the offline call over a whole recording and the
-// live call that resamples raw-rate chunks straight into the msig_lv.h rings.  One device function, rs_output, forms an output
+// live call that resamples raw-rate chunks straight into the msig_lv.h rings.  One device function, rs_output (rs_dev.h), forms an output
 // sample for both: the taps in ascending raw row j, acc = fma(h, x, acc) in float64 — the two calls differ only in where x[j] comes
 // from (the recording; or the chunk in the staging buffer and, for rows older than the chunk, the session's tail ring), so their bits
 // are the same.  Both kernels are streaming kernels in live.hip's shape: a thread owns one output value, consecutive lanes are the
@@ -8,31 +8,11 @@
 // crossings a side); those re-reads are served by the caches, nothing is staged in LDS: the tile of raw rows an output tile needs is
 // tile * M / L + 2 * half / L rows, which has no bound that holds over the ratios the header admits.  The per-session table travels as
 // kernel arguments, MSIG_LV_GROUP entries a launch: nothing is uploaded, allocated or kept.
-#include "msig_dev.h"
-#include "../../include/msig_rs.h"
+#include "rs_dev.h"
 
-struct RsRatio { int32_t L, M, half; };
 struct RsChunk { int64_t src0, w; int32_t len, session; };      // staging row of the chunk's first row; raw rows the session had before it
 struct RsChunks { RsChunk e[MSIG_LV_GROUP]; };
 static_assert(sizeof(RsChunks) + 128 <= 4096, "the table is a kernel argument");
-
-// msig_rs_out_count without its checks
-__host__ __device__ __forceinline__ int64_t rs_count(int64_t n_in, RsRatio r) {
-  const int64_t v = n_in * r.L - r.half - 1;
-  return v < 0 ? 0 : v / r.M + 1;
-}
-
-// Output m: x(j) is raw row j of the thread's column, asked for j = max(0, ceil((m M - half) / L)) .. floor((m M + half) / L) in
-// ascending order.  The tap index half + m M - j L runs from at most 2 half down to at least 0.
-template <class Fetch>
-__device__ __forceinline__ double rs_output(int64_t m, RsRatio r, const double* __restrict__ h, Fetch x) {
-  const int64_t c = m * r.M, lo = c - r.half;
-  const int64_t j0 = lo <= 0 ? 0 : (lo + r.L - 1) / r.L, j1 = (c + r.half) / r.L;
-  const double* tap = h + (r.half + c - j0 * r.L);
-  double acc = 0.0;
-  for (int64_t j = j0; j <= j1; ++j, tap -= r.L) acc = fma(*tap, x(j), acc);
-  return acc;
-}
 
 __global__ __launch_bounds__(256) void rs_resample_kernel(const double* __restrict__ x, int C_all, const double* __restrict__ h, RsRatio r,
                                                           double* __restrict__ y, int64_t n_out) {
@@ -78,14 +58,6 @@ __global__ __launch_bounds__(256) void rs_lv_tail_kernel(double* __restrict__ ta
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static int rs_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
-
-static int rs_ratio_check(int32_t L, int32_t M, int32_t half) {
-  if (L < 1 || L > MSIG_RS_MAX_RATIO || M < 1 || M > MSIG_RS_MAX_RATIO || L == M || rs_gcd(L, M) != 1) return MSIG_E_SHAPE;
-  if (half < (L > M ? L : M) || half > MSIG_RS_MAX_HALF) return MSIG_E_SHAPE;
-  return 0;
-}
-
 extern "C" int msig_rs_abi_version(void) { return MSIG_RS_ABI_VERSION; }
 
 extern "C" int64_t msig_rs_out_count(int64_t n_in, int32_t L, int32_t M, int32_t half) {

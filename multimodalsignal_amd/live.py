@@ -30,7 +30,15 @@ and counts at the device's own rate fs_in.  One msig_rs_lv_push per round resamp
 buffer of resampled rows — and keeps each session's tail of raw rows, which the next chunk's first outputs need.  Everything behind
 the ring is the code above; `timeline(sid)` equals `Monitor.run` with the same resampler on the same raw samples.
 
-The host parts (`Smoother`, `AlarmMachine`, `RingBook`, the CLI's argument checks) need no GPU.  `LiveMonitor` has no CPU fallback.
+Mixed rates (include/msig_mx.h): with `resampler=MixedResampler([Stream(...), ...], fs)` the columns of a session
+arrive as streams, each at its own rate: push({sid: {stream: samples}}), skip({sid: {stream: n_raw}}), room(sid).  A session keeps one
+raw count per stream; its ring rows are complete up to the slowest stream's output count, which is the `written` every window call
+receives (`MixedBook`).  A round costs one msig_mx_lv_push for the chunks of every (session, stream) that delivered samples and one for
+those that delivered none.  A stream may run ahead of the slowest one by what the ring holds beyond the windows still to be handed
+out; a push that would need more is refused before anything is launched.  `timeline(sid)` equals `Monitor.run` with the same resampler
+on the same streams.
+
+The host parts (`Smoother`, `AlarmMachine`, `RingBook`, `MixedBook`, the CLI's argument checks) need no GPU.  `LiveMonitor` has no CPU fallback.
 
 Out of scope: sharing the front end between overlapping windows (not exact, see monitor.py) and any network or serial front end —
 push() is the interface.  Training under the matching causal normalisation is --norm-reference expanding | trailing:K | decayed:H
@@ -38,7 +46,7 @@ push() is the interface.  Training under the matching causal normalisation is --
 
 CLI:  python -m multimodalsignal_amd.live --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
       --synthetic-recording) [--sessions N] [--chunk-s 2.5] [--reference head:6|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto]
-      [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] [--resample-from 700 [--resampler fft|fir]] --out DIR
+      [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] [--resample-from 700 [--resampler fft|fir] | --streams SPEC] --out DIR
 """
 from __future__ import annotations
 
@@ -57,7 +65,7 @@ from .monitor import (SYNTHETIC_NOTE, SYNTHETIC_PHASES, Monitor, Timeline, build
                       ema_gaps, find_events, hysteresis, hysteresis_gaps, lost_windows, parse_recording_reference, phase_shares, raw_phase_table,
                       resolve_reference, run_norm_reference, running_reference)
 from .reference import Gaps, gp_mode_fields
-from .resample import FirResampler
+from .resample import FirResampler, MixedResampler, out_count as rs_out_count
 
 FIELDS = ("mean_p", "std_p", "pred", "entropy", "mutual_info", "votes")      # what a session stores per window, as Ensemble.predict gives it
 
@@ -263,6 +271,95 @@ class RingBook:
         return out
 
 
+class MixedStuck(ValueError):
+    """MixedBook.plan: stream `ahead` cannot take its waiting rows — its outputs would lie `lead_rows` rows ahead of what the slowest
+    stream, `slowest`, can reach in this call; a ring of `need_rows` rows would hold them."""
+
+    def __init__(self, ahead: int, slowest: int, lead_rows: int, need_rows: int):
+        super().__init__(f"stream {ahead} is {lead_rows} rows ahead of stream {slowest}; a ring of {need_rows} rows would hold it")
+        self.ahead, self.slowest, self.lead_rows, self.need_rows = ahead, slowest, lead_rows, need_rows
+
+
+class MixedBook:
+    """The bookkeeping of one session whose columns arrive as streams with the ratios `ratios` = [(L, M, half), ...] ((1, 1, 0): a
+    stream at the ring's rate), on integers only.  `raw[g]` raw rows of stream g so far; `book` is the session's RingBook, whose
+    `written` is the minimum of the streams' output counts: the rows every stream has delivered.  A stream that is ahead has its rows
+    in the ring already; nothing reads them until the slowest stream reaches them.
+
+    A call's waiting rows are taken in rounds.  With bound = book.written + book.segment(1 << 62) — the first row whose ring slot a
+    window not yet handed out (or, while the statistics are pending, the unwrapped head) still needs — every stream with waiting rows
+    takes as many as keep its output count at or below the bound, at most max_rows_g(bound) - raw[g]; then the book advances to the
+    new minimum, which may hand out windows and raise the bound.  `plan` runs this on copies and raises MixedStuck where a round can
+    take nothing: rows are still waiting and no stream can move — the slowest stream has nothing waiting.  Nothing has changed then."""
+
+    def __init__(self, book: RingBook, ratios: Sequence[Tuple[int, int, int]]):
+        self.book, self.ratios = book, [(int(a), int(b), int(h)) for a, b, h in ratios]
+        if not self.ratios:
+            raise ValueError("a mixed book has at least one stream")
+        self.raw = [0] * len(self.ratios)
+
+    def count(self, g: int, n: int) -> int:
+        return rs_out_count(n, *self.ratios[g])
+
+    def max_rows(self, g: int, k: int) -> int:
+        """The largest raw count of stream g with count(g, n) <= k."""
+        up, down, half = self.ratios[g]
+        return (int(k) * down + half) // up
+
+    def counts(self) -> List[int]:
+        return [self.count(g, n) for g, n in enumerate(self.raw)]
+
+    def _rounds(self, waiting: Sequence[int]):
+        """(rounds, stuck): rounds = [(rows taken per stream, statistics due, windows handed out)], on copies; stuck is None or the
+        MixedStuck of the round that could take nothing."""
+        G = len(self.ratios)
+        if len(waiting) != G or any(int(n) < 0 for n in waiting):
+            raise ValueError(f"waiting rows are {G} counts >= 0, got {list(waiting)}")
+        b = RingBook(self.book.R, self.book.T, self.book.S, self.book.warm)
+        b.written, b.next_window, b.pending = self.book.written, self.book.next_window, self.book.pending
+        raw, left, rounds = list(self.raw), [int(n) for n in waiting], []
+        while any(left):
+            bound = b.written + b.segment(1 << 62)
+            take = [max(0, min(left[g], (1 << 31) - 1, self.max_rows(g, bound) - raw[g])) for g in range(G)]
+            if not any(take):
+                final = [self.count(g, raw[g] + left[g]) for g in range(G)]
+                ahead = max((g for g in range(G) if left[g]), key=lambda g: final[g])
+                slowest = min(range(G), key=lambda g: final[g])
+                return rounds, MixedStuck(ahead, slowest, final[ahead] - final[slowest], final[ahead] - b.next_window * b.S)
+            raw = [raw[g] + take[g] for g in range(G)]
+            left = [left[g] - take[g] for g in range(G)]
+            due, wins = b.advance(min(self.count(g, raw[g]) for g in range(G)) - b.written)
+            rounds.append((take, due, wins))
+        return rounds, None
+
+    def plan(self, waiting: Sequence[int]) -> List[Tuple[List[int], bool, range]]:
+        """The rounds of a call that delivers waiting[g] raw rows of stream g; changes nothing.  MixedStuck where it cannot finish."""
+        rounds, stuck = self._rounds(waiting)
+        if stuck is not None:
+            raise stuck
+        return rounds
+
+    def apply(self, take: Sequence[int]) -> Tuple[bool, range]:
+        """One planned round has been appended: (the statistics are due now, the windows to hand out now)."""
+        self.raw = [n + int(a) for n, a in zip(self.raw, take)]
+        return self.book.advance(min(self.counts()) - self.book.written)
+
+    def push(self, waiting: Sequence[int]) -> List[Tuple[List[int], bool, range]]:
+        """plan and apply: the call as a whole."""
+        rounds = self.plan(waiting)
+        for take, _due, _wins in rounds:
+            self.apply(take)
+        return rounds
+
+    def room(self, g: int) -> int:
+        """The raw rows stream g can take now, the others delivering nothing."""
+        if len(self.ratios) == 1:
+            return (1 << 31) - 1
+        waiting = [0] * len(self.ratios)
+        waiting[g] = 1 << 40
+        return sum(take[g] for take, _due, _wins in self._rounds(waiting)[0])
+
+
 @dataclass
 class LiveUpdate:
     """One new window of one session: its index, t_end = (window S + T) / fs, the timeline's row (score = mean_p[positive], std =
@@ -376,6 +473,7 @@ class _Session:
     def __init__(self, sid, slot: int, book: RingBook, mon: "LiveMonitor"):
         self.sid, self.slot, self.book = sid, slot, book
         self.raw = 0                             # resampler: the raw rows taken so far (book.written counts the ring's rows, the outputs)
+        self.mx = MixedBook(book, [(g.L, g.M, g.half) for g in mon.resampler.streams]) if mon.mixed else None      # a raw count per stream
         self.smoother, self.machine = Smoother(mon.halflife), AlarmMachine(mon.on, mon.off, mon.min_on)
         if mon.gaps is not None:
             self.smoother = GapSmoother(mon.halflife, mon.gaps.lost_after)
@@ -401,15 +499,18 @@ class LiveMonitor:
     tensor (msig_nr.h's layout): wearers enrolled earlier, no warm-up.  "recording" is refused: it is not causal; "expanding" is
     its causal counterpart.  positive, halflife, on, off, min_on, channels: as for monitor.Monitor.  `gaps` (a Gaps, with a running
     reference only): samples may be NaN and stretches may be skipped (module docstring).  `resampler` (a FirResampler whose fs_out is
-    `fs`): push and skip take samples and counts at the resampler's fs_in; the monitor owns a tail of raw rows per session.
+    `fs`): push and skip take samples and counts at the resampler's fs_in; the monitor owns a tail of raw rows per session.  Or a
+    MixedResampler: the columns are the resampler's `.names`, push and skip take {stream: samples} and {stream: n_raw} per session, and
+    the default ring is longer by the resampler's latency_spread_rows (an explicit ring must hold the head span, that spread and the
+    outputs of one raw sample).
 
     open(sid, names, stats=None) / close(sid); push({sid: samples}) or push(sid, samples); skip({sid: n}) or skip(sid, n);
-    timeline(sid); alarms(sid)."""
+    timeline(sid); alarms(sid); room(sid) (mixed rates)."""
 
     def __init__(self, models: Sequence, fs: float, window_s: float = 60, stride_s: float = 10, reference="head:6", max_sessions: int = 64,
                  ring_s: Optional[float] = None, eval_batch: int = 256, positive: int = 1, halflife: float = 3, on: float = 0.6,
                  off: float = 0.4, min_on: int = 2, channels: Optional[Sequence[str]] = None, gaps: Optional[Gaps] = None,
-                 resampler: Optional[FirResampler] = None):
+                 resampler: Union[FirResampler, MixedResampler, None] = None):
         if not float(fs) > 0:
             raise ValueError(f"fs must be > 0, got {fs!r}")
         self.fs = float(fs)
@@ -418,9 +519,9 @@ class LiveMonitor:
             raise ValueError(f"a window needs >= 16 samples and a stride >= 1, got {self.T} and {self.S}")
         if gaps is not None and not isinstance(gaps, Gaps):
             raise ValueError(f"gaps is a Gaps(min_coverage, lost_after) or None, got {gaps!r}")
-        if resampler is not None and (not isinstance(resampler, FirResampler) or resampler.fs_out != self.fs):
-            raise ValueError(f"resampler is a FirResampler whose fs_out is the monitor's fs = {self.fs:g}, or None; got {resampler!r}")
-        self.resampler = resampler
+        if resampler is not None and (not isinstance(resampler, (FirResampler, MixedResampler)) or resampler.fs_out != self.fs):
+            raise ValueError(f"resampler is a FirResampler or a MixedResampler whose fs_out is the monitor's fs = {self.fs:g}, or None; got {resampler!r}")
+        self.resampler, self.mixed = resampler, isinstance(resampler, MixedResampler)
         if gaps is not None and (isinstance(reference, torch.Tensor) or running_reference(reference) is None):
             raise ValueError("a live monitor with gaps takes a running reference ('expanding', 'trailing:K', 'decayed:H'): 'head:K' statistics "
                              f"weight samples and have no per-channel count of valid ones, and given statistics have no live coverage; got {reference!r}")
@@ -440,9 +541,16 @@ class LiveMonitor:
         if isinstance(max_sessions, bool) or not 1 <= int(max_sessions) <= L.LV_MAX_SESSIONS:
             raise ValueError(f"max_sessions must be an integer in 1..{L.LV_MAX_SESSIONS}, got {max_sessions!r}")
         head = (self.warm - 1) * self.S + self.T if self.warm else self.T
-        self.R = head + 8 * self.S if ring_s is None else int(round(float(ring_s) * self.fs))
+        spread = resampler.latency_spread_rows if self.mixed else 0      # a low-rate stream's outputs trail the others' by that many rows
+        self.R = head + 8 * self.S + spread if ring_s is None else int(round(float(ring_s) * self.fs))
         RingBook(self.R, self.T, self.S, self.warm)                  # refuses a ring shorter than the head span
-        if resampler is not None and self.R < head + -(-resampler.L // resampler.M):
+        if self.mixed:
+            most = max(-(-g.L // g.M) for g in resampler.streams)
+            if self.R < head + spread + most:
+                raise ValueError(f"a ring of {self.R} rows has no room for the streams' latency spread of {spread} rows and the {most} outputs one "
+                                 f"raw sample yields beside {'the head span of' if self.warm else 'a window of'} {head}: ring_s >= "
+                                 f"{(head + spread + most) / self.fs:g}")
+        elif resampler is not None and self.R < head + -(-resampler.L // resampler.M):
             raise ValueError(f"a ring of {self.R} rows has no room for the {-(-resampler.L // resampler.M)} outputs one raw sample yields beside "
                              f"{'the head span of' if self.warm else 'a window of'} {head}")
         if self.R >= 1 << 31:
@@ -474,6 +582,8 @@ class LiveMonitor:
             self.rn_state = torch.zeros((self.max_sessions, state_bytes // 8), dtype=torch.float64, device=self.device)
             self.rn_next = [0] * self.max_sessions               # the host's mirror of every state's next expected window
             self.rn_latest: Dict[int, torch.Tensor] = {}         # slot -> the session's latest statistics record
+        if self.mixed:                           # the resampler defines the sessions' columns
+            self._bind(resampler.names)
 
     @classmethod
     def from_run(cls, run_dir, subject: Optional[str] = None, config_name: Optional[str] = None, fs: float = 64.0, device="cuda", **kw) -> "LiveMonitor":
@@ -508,7 +618,10 @@ class LiveMonitor:
         self.cols = (C.c_int32 * len(channels))(*[names.index(c) for c in channels])
         self.mask = sum(1 << c for c, name in enumerate(channels) if name == "chest_EDA")
         self.pool = torch.empty((self.max_sessions, self.R * self.C_all), dtype=torch.float64, device=self.device)
-        if self.resampler is not None:           # per session the last tail_rows raw rows: the support of a later chunk's first outputs
+        if self.mixed:                           # per session every stream's last tail_rows raw rows, side by side (msig_mx.h)
+            self.tails = torch.zeros((self.max_sessions, self.resampler.tail_doubles), dtype=torch.float64, device=self.device)
+            self.groups = self.resampler.groups()
+        elif self.resampler is not None:         # per session the last tail_rows raw rows: the support of a later chunk's first outputs
             self.tails = torch.zeros((self.max_sessions, self.resampler.tail_rows * self.C_all), dtype=torch.float64, device=self.device)
 
     def open(self, sid, names: Optional[Sequence[str]] = None, stats: Optional[torch.Tensor] = None):
@@ -568,6 +681,20 @@ class LiveMonitor:
             raise ValueError(f"samples are (n, {self.C_all}) — the columns {self.names} — got {tuple(x.shape)}")
         return x
 
+    def _stream_dict(self, sid, d, what: str) -> dict:
+        rs = self.resampler
+        if not isinstance(d, dict) or not set(d) <= set(rs.stream):
+            raise ValueError(f"session {sid!r}: {what} takes {{stream: ...}} with streams among {[g.name for g in rs.streams]}, got "
+                             f"{sorted(d, key=str) if isinstance(d, dict) else d!r}")
+        return d
+
+    def room(self, sid) -> Dict[str, int]:
+        """Mixed rates: per stream the raw rows it can take now (the other streams delivering nothing)."""
+        if not self.mixed:
+            raise ValueError("room(sid) belongs to a monitor with a MixedResampler")
+        s = self._session(sid)
+        return {g.name: s.mx.room(i) for i, g in enumerate(self.resampler.streams)}
+
     @torch.no_grad()
     def push(self, samples, chunk=None) -> Union[Dict[object, List[LiveUpdate]], List[LiveUpdate]]:
         """push({sid: samples, ...}) -> {sid: [LiveUpdate, ...]}; push(sid, samples) -> [LiveUpdate, ...].  Everything is checked
@@ -577,7 +704,12 @@ class LiveMonitor:
             if chunk is None:
                 raise ValueError("push takes {sid: samples} or (sid, samples)")
             samples = {samples: chunk}
-        todo = [(self._session(sid), self._samples(x)) for sid, x in samples.items()]
+        if self.mixed:
+            rs = self.resampler
+            todo = [(self._session(sid), {rs.streams.index(rs.stream[k]): rs.samples(rs.stream[k], x, self.device)
+                                          for k, x in self._stream_dict(sid, d, "push").items()}) for sid, d in samples.items()]
+        else:
+            todo = [(self._session(sid), self._samples(x)) for sid, x in samples.items()]
         out = self._feed(todo, {sid: [] for sid in samples})
         return out[next(iter(samples))] if single else out
 
@@ -593,10 +725,15 @@ class LiveMonitor:
             if n is None:
                 raise ValueError("skip takes {sid: n_samples} or (sid, n_samples)")
             counts = {counts: n}
-        for k in counts.values():
+        per = [k for sid, d in counts.items() for k in self._stream_dict(sid, d, "skip").values()] if self.mixed else list(counts.values())
+        for k in per:
             if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 0:
                 raise ValueError(f"skip takes a number of samples >= 0 per session, got {k!r}")
-        todo = [(self._session(sid), int(k)) for sid, k in counts.items()]
+        if self.mixed:
+            rs = self.resampler
+            todo = [(self._session(sid), {rs.streams.index(rs.stream[k]): int(n) for k, n in d.items()}) for sid, d in counts.items()]
+        else:
+            todo = [(self._session(sid), int(k)) for sid, k in counts.items()]
         out = self._feed(todo, {sid: [] for sid in counts})
         return out[next(iter(counts))] if single else out
 
@@ -607,6 +744,8 @@ class LiveMonitor:
         at = [0] * len(todo)
         size = lambda x: x if isinstance(x, int) else x.shape[0]      # noqa: E731
         lib, rs = L.lib(), self.resampler
+        if self.mixed:
+            return self._feed_mixed(todo, out)
         if rs is not None:
             return self._feed_raw(todo, out)
         while True:
@@ -681,6 +820,58 @@ class LiveMonitor:
                 s.raw += a
                 due, windows = s.book.advance(rs.out_count(s.raw) - s.book.written)
                 if due:          # the head span lies unwrapped at the ring's start: the offline call's statistics (RingBook)
+                    L.check(lib.msig_rec_stats(self.pool[s.slot].data_ptr(), s.book.head, self.C_all, self.cols, self.ensemble.C, self.mask,
+                                               self.T, self.S, 0, s.book.warm, self.stats[s.slot].data_ptr(), self.scratch.data_ptr(),
+                                               self._stream()), "msig_rec_stats")
+                rows += [(s.slot, w, s.book.written) for w in windows]
+                owners += [s] * len(windows)
+            if rows:
+                self._evaluate(rows, owners, out)
+        return out
+
+    def _feed_mixed(self, todo, out: Dict[object, List[LiveUpdate]]):
+        """_feed_raw with a chunk per (session, stream): every session's rounds are planned on integers first (MixedBook.plan), so a
+        call that cannot finish is refused before anything is launched or changed; then round r of every session goes into one
+        msig_mx_lv_push for the chunks with samples and one, without a staging buffer, for the missing ones."""
+        size = lambda x: x if isinstance(x, int) else x.shape[0]      # noqa: E731
+        lib, rs = L.lib(), self.resampler
+        G = len(rs.streams)
+        plans = []
+        for s, d in todo:
+            try:
+                plans.append(s.mx.plan([size(d[g]) if g in d else 0 for g in range(G)]))
+            except MixedStuck as e:
+                raise ValueError(f"session {s.sid!r}: stream {rs.streams[e.ahead].name!r} would be {e.lead_rows / self.fs:.3f} s ahead of stream "
+                                 f"{rs.streams[e.slowest].name!r}, more than the ring of {self.R / self.fs:g} s holds beside the windows still to be "
+                                 f"handed out; push the lagging streams first, or build the monitor with ring_s >= {e.need_rows / self.fs:g}") from None
+        at = [[0] * G for _ in todo]
+        tails = (self.tails.data_ptr(), self.tails.shape[1] * 8, rs.h.data_ptr(), self.groups, G)
+        for r in range(max((len(p) for p in plans), default=0)):
+            seg = [(j, g, a) for j, p in enumerate(plans) if r < len(p) for g, a in enumerate(p[r][0]) if a > 0]
+            args = lambda part: ((C.c_int32 * len(part))(*[todo[j][0].slot for j, _g, _a in part]),      # noqa: E731
+                                 (C.c_int32 * len(part))(*[g for _j, g, _a in part]),
+                                 (C.c_int64 * len(part))(*[todo[j][0].mx.raw[g] for j, g, _a in part]),
+                                 (C.c_int64 * len(part))(*[a for _j, _g, a in part]), len(part))
+            data = [e for e in seg if not isinstance(todo[e[0]][1][e[1]], int)]
+            gone = [e for e in seg if isinstance(todo[e[0]][1][e[1]], int)]
+            if data:
+                parts = [todo[j][1][g][at[j][g]:at[j][g] + a].reshape(-1) for j, g, a in data]      # the chunks' rows differ in width: back to back
+                if all(isinstance(p, np.ndarray) for p in parts):                  # one upload of the round's chunks
+                    staging = torch.from_numpy(np.concatenate(parts) if len(parts) > 1 else np.ascontiguousarray(parts[0])).to(self.device)
+                else:
+                    staging = torch.cat([torch.from_numpy(p).to(self.device) if isinstance(p, np.ndarray) else p for p in parts]).contiguous()
+                L.check(lib.msig_mx_lv_push(*self._pool_args(), *tails, *args(data), staging.data_ptr(), self._stream()), "msig_mx_lv_push")
+            if gone:
+                L.check(lib.msig_mx_lv_push(*self._pool_args(), *tails, *args(gone), None, self._stream()), "msig_mx_lv_push")
+            rows, owners = [], []
+            for j, p in enumerate(plans):
+                if r >= len(p):
+                    continue
+                s, take = todo[j][0], p[r][0]
+                for g in range(G):
+                    at[j][g] += take[g]
+                due, windows = s.mx.apply(take)
+                if due:          # the head span lies unwrapped at the ring's start, complete in every stream's columns
                     L.check(lib.msig_rec_stats(self.pool[s.slot].data_ptr(), s.book.head, self.C_all, self.cols, self.ensemble.C, self.mask,
                                                self.T, self.S, 0, s.book.warm, self.stats[s.slot].data_ptr(), self.scratch.data_ptr(),
                                                self._stream()), "msig_rec_stats")
@@ -769,7 +960,8 @@ class LiveMonitor:
         if self.gaps is not None:
             meta.update(gaps=self.gaps.spelling, invalid_windows=int((~extra["valid"]).sum()), lost_windows=int(extra["lost"].sum()))
         if self.resampler is not None:
-            meta.update(resampler=self.resampler.spelling, resampler_latency_s=self.resampler.latency_s, raw_samples=s.raw)
+            raw = {g.name: s.mx.raw[i] for i, g in enumerate(self.resampler.streams)} if self.mixed else s.raw
+            meta.update(resampler=self.resampler.spelling, resampler_latency_s=self.resampler.latency_s, raw_samples=raw)
         return Timeline(t_end=t_end, score=score, smoothed=smoothed, state=state, warmup=np.arange(n) < s.flagged,
                         events=find_events(state, smoothed, t_end), meta=meta, **f, **extra)
 
@@ -837,8 +1029,74 @@ def replay_pieces(lo: int, hi: int, spans) -> List[Tuple[int, int, bool]]:
     return out
 
 
+def main_streams(a) -> Timeline:
+    """main with --streams: every session is fed stream by stream at the streams' own rates, chunk_s seconds of each per tick; the
+    spans in which a stream is off (--synthetic-gaps all= and stream=) are not pushed but skipped on that stream."""
+    from .monitor import load_streams
+    mx = MixedResampler(a.streams, a.fs)
+    live = LiveMonitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference,
+                                max_sessions=a.sessions, gaps=a.gaps, resampler=mx)
+    sig, table = load_streams(a, mx)
+    sig = {k: torch.from_numpy(v.reshape(v.shape[0], -1)).to(live.device) for k, v in sig.items()}
+    chunk = {g.name: max(1, int(round(a.chunk_s * g.fs))) for g in mx.streams}
+    ticks = max(-(-int(sig[g.name].shape[0]) // chunk[g.name]) for g in mx.streams)
+    spans = {g.name: [] for g in mx.streams}
+    if a.gaps is not None and a.synthetic_gaps is not None:
+        from .synth import gap_spans
+        spans = {g.name: gap_spans(a.synthetic_gaps, g.fs, int(sig[g.name].shape[0]), stream=g.name) for g in mx.streams}
+    for k in range(a.sessions):
+        live.open(k)
+    skipped = {g.name: 0 for g in mx.streams}
+    for t in range(ticks + a.sessions - 1):          # session k is k chunks behind session 0
+        pieces = {}
+        for k in range(a.sessions):
+            if 0 <= t - k < ticks:
+                for g in mx.streams:
+                    lo, hi = (t - k) * chunk[g.name], min((t - k + 1) * chunk[g.name], int(sig[g.name].shape[0]))
+                    if hi > lo:
+                        pieces[k, g.name] = replay_pieces(lo, hi, spans[g.name])
+        for r in range(max((len(v) for v in pieces.values()), default=0)):      # a stream's pieces in their order, streams and sessions side by side
+            data: Dict[int, dict] = {}
+            gone: Dict[int, dict] = {}
+            for (k, name), v in pieces.items():
+                if r < len(v):
+                    lo, hi, off = v[r]
+                    if off:
+                        gone.setdefault(k, {})[name] = hi - lo
+                        skipped[name] += (hi - lo) if k == 0 else 0
+                    else:
+                        data.setdefault(k, {})[name] = sig[name][lo:hi]
+            if data:
+                live.push(data)
+            if gone:
+                live.skip(gone)
+    tl = live.timeline(0)
+    offline = Monitor(live.models, a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=live.reference, channels=live.channels, gaps=a.gaps,
+                      resampler=mx)
+    equal = timelines_equal(tl, offline.run(sig))
+    if table is not None:
+        tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, live.T, live.S))
+    a.out.mkdir(parents=True, exist_ok=True)
+    tl.to_csv(a.out / "timeline.csv")
+    path = tl.to_json(a.out / "timeline.json")
+    (a.out / "alarms.json").write_text(json.dumps({str(k): [asdict(al) for al in live.alarms(k)] for k in range(a.sessions)}, indent=1))
+    print(f"{a.sessions} sessions, {ticks} ticks of {a.chunk_s:g} s — {chunk} raw rows per stream; session 0: {len(tl.t_end)} windows, "
+          f"{int(tl.state.sum())} flagged, {len(tl.events)} events, {len(live.alarms(0))} alarms; timeline written to: {path}")
+    print(f"session 0's timeline and Monitor.run's for the same recording: {'equal' if equal else 'NOT EQUAL'} bit for bit")
+    print(f"resampler {mx.spelling}: {tl.meta['raw_samples']} raw samples -> {tl.meta['samples']}, latency {mx.latency_s:.3f} s, a ring of "
+          f"{live.R} rows; Monitor.run used the same resampler")
+    if a.gaps is not None:
+        print(f"gaps {a.gaps.spelling}: {tl.meta['invalid_windows']} invalid windows, {tl.meta['lost_windows']} lost; {skipped} of session 0's "
+              f"raw samples were skipped, not pushed; {int((~np.isfinite(tl.score)).sum())} of {len(tl.score)} scores are not finite")
+    if table is not None:
+        print("NOTE: " + SYNTHETIC_NOTE + ".")
+    return tl
+
+
 def main(argv=None) -> Timeline:
     a = parse_args(argv)
+    if a.streams is not None:
+        return main_streams(a)
     fir = FirResampler(a.resample_from, a.fs) if a.resampler == "fir" else None
     fs_in = a.fs if fir is None else a.resample_from                 # the rate of what is pushed: under fir the recording's own
     live = LiveMonitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference,

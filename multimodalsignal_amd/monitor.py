@@ -26,9 +26,11 @@ reference or a statistics tensor; without `gaps` nothing here differs from what 
 Raw-rate recordings (include/msig_rs.h): `resampler=FirResampler(fs_in, fs)` / --resample-from 700 --resampler fir.
 `run` takes the recording at the device's own rate and monitors the causal polyphase FIR resampler's outputs (`apply`), which is what
 live.LiveMonitor with the same resampler computes chunk by chunk.  The default, --resampler fft, is the whole-recording FFT method.
+Mixed rates (include/msig_mx.h): `resampler=MixedResampler([Stream(...), ...], fs)` / --streams SPEC.  `run` takes
+{stream: array}, each at its stream's rate (--recording X.npz keyed by stream name), and monitors the rows every stream has delivered.
 
 CLI:  python -m multimodalsignal_amd.monitor --run RUN [--subject S5] [--config NAME] (--recording X.npy --names FILE |
-      --synthetic-recording) [--fs 64] [--resample-from 700 [--resampler fft|fir]] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
+      --synthetic-recording) [--fs 64] [--resample-from 700 [--resampler fft|fir] | --streams SPEC] [--reference recording|head:K|expanding[:W]|trailing:K[:W]|decayed:H[:W]|auto] [--stride-s 10] [--gaps [MIN_COVERAGE[:LOST_AFTER]]] [--synthetic-gaps SPEC] --out DIR
 """
 from __future__ import annotations
 
@@ -48,7 +50,7 @@ from . import _lib as L
 from .ensemble import Ensemble, load_members, member_files
 from .reference import (GAPS_REFERENCES, RUNNING_WARMUP, Gaps, Running, gp_mode_fields, parse_gaps,      # noqa: F401  (RUNNING_WARMUP and Gaps
                         parse_running)                                                                  # are part of this module's interface)
-from .resample import FirResampler, ratio as resample_ratio
+from .resample import FirResampler, MixedResampler, parse_streams, ratio as resample_ratio
 
 SYNTHETIC_NOTE = ("synthetic recording: the stress phases are planted and easy, so the timeline shows that the recording-to-events "
                   "machinery works, not what detection is worth on WESAD")
@@ -484,8 +486,8 @@ class Monitor:
         if not float(fs) > 0:
             raise ValueError(f"fs must be > 0, got {fs!r}")
         self.fs = float(fs)
-        if resampler is not None and (not isinstance(resampler, FirResampler) or resampler.fs_out != self.fs):
-            raise ValueError(f"resampler is a FirResampler whose fs_out is the monitor's fs = {self.fs:g}, or None; got {resampler!r}")
+        if resampler is not None and (not isinstance(resampler, (FirResampler, MixedResampler)) or resampler.fs_out != self.fs):
+            raise ValueError(f"resampler is a FirResampler or a MixedResampler whose fs_out is the monitor's fs = {self.fs:g}, or None; got {resampler!r}")
         self.resampler = resampler
         self.T, self.S = int(round(float(window_s) * self.fs)), int(round(float(stride_s) * self.fs))
         if self.T < 16 or self.S < 1:
@@ -550,9 +552,20 @@ class Monitor:
                                 device=self.ensemble.device, gaps=self.gaps)
 
     @torch.no_grad()
-    def run(self, sig, names: Sequence[str]) -> Timeline:
+    def run(self, sig, names: Optional[Sequence[str]] = None) -> Timeline:
+        """The timeline of the recording `sig` with the columns `names`.  With a MixedResampler `sig` is {stream: array}, each at its
+        stream's rate, and the columns are the resampler's (`names`, if given, must equal them)."""
         raw = None
-        if self.resampler is not None:           # the recording is at the resampler's fs_in: its causal outputs are what is monitored
+        if isinstance(self.resampler, MixedResampler):      # every stream at its own rate: the rows all of them have delivered are monitored
+            if names is not None and list(names) != self.resampler.names:
+                raise ValueError(f"the resampler's streams have the columns {self.resampler.names}, got {list(names)}")
+            if not isinstance(sig, dict):
+                raise ValueError("with a MixedResampler a recording is {stream: array}, each array at its stream's rate")
+            names, y = self.resampler.names, self.resampler.apply(sig)
+            raw, sig = {g.name: int(sig[g.name].shape[0]) for g in self.resampler.streams}, y
+        elif names is None:
+            raise ValueError("run(sig, names) takes the names of the recording's columns")
+        elif self.resampler is not None:           # the recording is at the resampler's fs_in: its causal outputs are what is monitored
             if not isinstance(sig, (np.ndarray, torch.Tensor)) or sig.ndim != 2:
                 raise ValueError("a recording is a (L, C_all) float64 array: numpy, or a tensor on the GPU (there is no CPU fallback)")
             raw, sig = int(sig.shape[0]), self.resampler.apply(sig)
@@ -607,6 +620,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--resampler", choices=("fft", "fir"), default="fft",
                     help="how --resample-from is resampled: fft — the whole recording at once (scipy.signal.resample's method); fir — the causal "
                          "polyphase FIR resampler a live monitor runs (with it, --synthetic-recording is built at the --resample-from rate)")
+    ap.add_argument("--streams", default=None, metavar="SPEC",
+                    help="mixed-rate streams, NAME=RATE:COLUMN,...;NAME=RATE:COLUMN,... — every stream is resampled to --fs by the causal FIR "
+                         "resampler (a stream at --fs is copied); --recording is then an .npz keyed by stream name, --synthetic-recording is "
+                         "built per stream at its rate; excludes --resample-from")
     ap.add_argument("--reference", default="recording", help="recording | head:K | expanding[:W] | trailing:K[:W] | decayed:H[:W] | auto (the counterpart of the run's NORM_REFERENCE)")
     ap.add_argument("--window-s", type=float, default=60.0)
     ap.add_argument("--stride-s", type=float, default=10.0)
@@ -629,7 +646,10 @@ def check_gap_args(ap, a):
             if not a.synthetic_recording:
                 ap.error("--synthetic-gaps goes with --synthetic-recording")
             from .synth import parse_synthetic_gaps
-            parse_synthetic_gaps(a.synthetic_gaps)
+            spec = parse_synthetic_gaps(a.synthetic_gaps)
+            known = [st.name for st in a.streams] if getattr(a, "streams", None) else []
+            if any(name not in known for name, _a, _d in spec["stream"]):
+                ap.error(f"--synthetic-gaps stream=NAME:START_S:SECONDS names one of the --streams {known}")
         if a.gaps is not None and a.reference != "auto" and running_reference(a.reference) is None:
             ap.error(GAPS_REFERENCES + f"; got {a.reference!r}")
     except ValueError as e:
@@ -637,9 +657,28 @@ def check_gap_args(ap, a):
 
 
 def check_source_args(ap, a):
-    """--recording / --synthetic-recording, --names, --fs, --resample-from and --resampler, checked before anything touches the GPU."""
+    """--recording / --synthetic-recording, --names, --fs, --resample-from, --resampler and --streams, checked before anything touches
+    the GPU; a.streams becomes a list of Stream or None."""
     if a.synthetic_recording == (a.recording is not None):
         ap.error("give exactly one of --recording X.npy and --synthetic-recording")
+    if a.streams is not None:
+        if a.resample_from is not None:
+            ap.error("--streams excludes --resample-from: every stream has its own rate")
+        if a.names is not None:
+            ap.error("--streams names the columns itself: it takes no --names")
+        if not a.fs > 0:
+            ap.error("--fs must be > 0")
+        try:
+            a.streams = parse_streams(a.streams)
+            MixedResampler(a.streams, a.fs, device="cpu")          # the ratios and the column sets, on the host
+            if a.synthetic_recording:
+                from .synth import CHANNELS6
+                unknown = [c for st in a.streams for c in st.columns if c not in CHANNELS6]
+                if unknown:
+                    raise ValueError(f"--synthetic-recording has the channels {CHANNELS6}; --streams names {unknown}")
+        except ValueError as e:
+            ap.error(str(e))
+        return
     if a.recording is not None and a.names is None:
         ap.error("--recording needs --names FILE (one channel name per line)")
     if a.synthetic_recording and (a.names is not None or (a.resample_from is not None and a.resampler != "fir")):
@@ -676,8 +715,45 @@ def parse_args(argv=None) -> argparse.Namespace:
     return a
 
 
+def load_streams(a, resampler: MixedResampler):
+    """--streams: ({stream: (n, ncols) float64 numpy array}, phase table or None) of --recording X.npz or --synthetic-recording."""
+    if a.synthetic_recording:
+        from .synth import make_synthetic_streams
+        return make_synthetic_streams(SYNTHETIC_PHASES, a.streams, fs=a.fs, seed=a.seed, difficulty=a.difficulty, gaps=a.synthetic_gaps)
+    with np.load(a.recording) as z:
+        missing = [g.name for g in resampler.streams if g.name not in z.files]
+        if missing:
+            raise ValueError(f"{a.recording} holds the arrays {z.files}; --streams names {missing} too")
+        return {g.name: np.ascontiguousarray(z[g.name], dtype=np.float64) for g in resampler.streams}, None
+
+
+def main_streams(a) -> Timeline:
+    """main with --streams: the recording is a dict of arrays, each at its stream's rate."""
+    mx = MixedResampler(a.streams, a.fs)
+    mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, gaps=a.gaps,
+                           resampler=mx)
+    sig, table = load_streams(a, mx)
+    tl = mon.run(sig)
+    if table is not None:
+        tl.meta.update(note=SYNTHETIC_NOTE, phases=table, flagged_by_label=phase_shares(tl, table, mon.T, mon.S))
+    a.out.mkdir(parents=True, exist_ok=True)
+    tl.to_csv(a.out / "timeline.csv")
+    path = tl.to_json(a.out / "timeline.json")
+    print(f"{len(tl.t_end)} windows, {int(tl.state.sum())} flagged, {len(tl.events)} events; timeline written to: {path}")
+    print(f"resampler {mx.spelling}: {tl.meta['raw_samples']} raw samples -> {tl.meta['samples']}, latency {mx.latency_s:.3f} s")
+    if a.gaps is not None:
+        print(f"gaps {a.gaps.spelling}: {tl.meta['invalid_windows']} invalid windows, {tl.meta['lost_windows']} lost; "
+              f"{int((~np.isfinite(tl.score)).sum())} of {len(tl.score)} scores are not finite")
+    if table is not None:
+        print("NOTE: " + SYNTHETIC_NOTE + ".")
+        print("flagged windows by raw label: " + json.dumps(tl.meta["flagged_by_label"]))
+    return tl
+
+
 def main(argv=None) -> Timeline:
     a = parse_args(argv)
+    if a.streams is not None:
+        return main_streams(a)
     fir = FirResampler(a.resample_from, a.fs) if a.resampler == "fir" else None      # the recording is monitored at its own rate
     mon = Monitor.from_run(a.run, a.subject, a.config, fs=a.fs, window_s=a.window_s, stride_s=a.stride_s, reference=a.reference, gaps=a.gaps,
                            resampler=fir)

@@ -116,16 +116,24 @@ def make_synthetic_recording(phases, fs=64.0, channels=CHANNELS6, seed=42, diffi
 
 
 SYNTHETIC_GAPS_FORMS = ("comma-separated drop=RATE (each sample of each channel missing with probability RATE in [0, 1)), "
-                        "channel=INDEX:START_S:SECONDS (one channel off for a span) and all=START_S:SECONDS (every channel off for a span); "
-                        "channel= and all= may repeat")
+                        "channel=INDEX:START_S:SECONDS (one channel off for a span), all=START_S:SECONDS (every channel off for a span) and, "
+                        "with mixed-rate streams, stream=NAME:START_S:SECONDS (one stream off for a span); channel=, all= and stream= may repeat")
 
 
 def parse_synthetic_gaps(spec) -> dict:
-    """--synthetic-gaps SPEC -> {"drop": rate, "channel": [(index, start_s, seconds), ...], "all": [(start_s, seconds), ...]}."""
-    out = {"drop": 0.0, "channel": [], "all": []}
+    """--synthetic-gaps SPEC -> {"drop": rate, "channel": [(index, start_s, seconds), ...], "all": [(start_s, seconds), ...],
+    "stream": [(name, start_s, seconds), ...]}."""
+    out = {"drop": 0.0, "channel": [], "all": [], "stream": []}
     try:
         for item in str(spec).split(","):
             key, _, val = item.partition("=")
+            if key == "stream":
+                name, _, span = val.partition(":")
+                nums = [float(v) for v in span.split(":")]
+                if not name or len(nums) != 2 or not (nums[0] >= 0 and nums[1] > 0):
+                    raise ValueError
+                out["stream"].append((name, nums[0], nums[1]))
+                continue
             nums = [float(v) for v in val.split(":")]
             if key == "drop" and len(nums) == 1 and 0.0 <= nums[0] < 1.0:
                 out["drop"] = nums[0]
@@ -140,9 +148,12 @@ def parse_synthetic_gaps(spec) -> dict:
     return out
 
 
-def gap_spans(spec, fs, L) -> list:
-    """The all-channel spans of a gaps spec as sorted, merged (first sample, one past last) pairs inside [0, L)."""
-    spans = sorted((min(L, int(round(a * fs))), min(L, int(round((a + d) * fs)))) for a, d in parse_synthetic_gaps(spec)["all"])
+def gap_spans(spec, fs, L, stream=None) -> list:
+    """The all-channel spans of a gaps spec as sorted, merged (first sample, one past last) pairs inside [0, L); with `stream`, a
+    stream's name, the spans in which that stream is off: the all-channel spans and its own stream= spans."""
+    g = parse_synthetic_gaps(spec)
+    both = g["all"] + [(a, d) for name, a, d in g["stream"] if stream is not None and name == stream]
+    spans = sorted((min(L, int(round(a * fs))), min(L, int(round((a + d) * fs)))) for a, d in both)
     out = []
     for a, b in spans:
         if out and a <= out[-1][1]:
@@ -152,11 +163,14 @@ def gap_spans(spec, fs, L) -> list:
     return out
 
 
-def plant_gaps(x, spec, fs, seed=42):
+def plant_gaps(x, spec, fs, seed=42, streams=False):
     """Sets the samples a gaps spec names to NaN, in place.  The dropped samples are this function's own draws
-    (RandomState(seed + 7919)), so the recording's values do not depend on the spec."""
+    (RandomState(seed + 7919)), so the recording's values do not depend on the spec.  stream= spans belong to mixed-rate streams
+    (make_synthetic_streams plants them, with streams=True here): a single-rate recording has no streams and refuses them."""
     g = parse_synthetic_gaps(spec)
     L, C = x.shape
+    if g["stream"] and not streams:
+        raise ValueError("--synthetic-gaps stream=NAME:START_S:SECONDS goes with mixed-rate streams (--streams)")
     if any(c >= C for c, _a, _d in g["channel"]):
         raise ValueError(f"--synthetic-gaps names a channel outside 0..{C - 1}")
     if g["drop"] > 0:
@@ -166,3 +180,39 @@ def plant_gaps(x, spec, fs, seed=42):
     for a, b in gap_spans(spec, fs, L):
         x[a:b, :] = np.nan
     return x
+
+
+def make_synthetic_streams(phases, streams, fs=64.0, channels=CHANNELS6, seed=42, difficulty=1.0, block_s=60.0, gaps=None):
+    """make_synthetic_recording as mixed-rate streams: `streams` is a list of resample.Stream (name, fs, columns — each column one
+    of `channels`).  Returns ({name: (n, ncols) float64 at the stream's rate}, phase table in samples at `fs`, the monitor's rate).
+
+    make_synthetic_recording is called once per distinct rate with the same seed, and each stream keeps its columns of the
+    recording at its rate.  The planted phase effects — the stress terms of the rhythms' rates, of the EDA level and ramp and of the
+    modulation, in seconds, and the subject's gain and offset — are the same at every rate.  The NOISE draws differ between rates:
+    the generator draws a recording's per-sample noise first, so the per-block draws that follow it (a block's own heart rate, level
+    and breathing rate around the planted ones) differ too, and a column at 4 Hz is not the 700 Hz column decimated.
+    `gaps`: drop=, channel= (an index into `channels`) and all= are planted at every rate; stream=NAME:START_S:SECONDS sets that
+    stream's rows of the span to NaN."""
+    channels = list(channels)
+    unknown = [c for st in streams for c in st.columns if c not in channels]
+    if unknown:
+        raise ValueError(f"the synthetic recording has the channels {channels}; the streams name {unknown}")
+    spec = parse_synthetic_gaps(gaps) if gaps is not None else None
+    if spec is not None and any(name not in [st.name for st in streams] for name, _a, _d in spec["stream"]):
+        raise ValueError(f"--synthetic-gaps names a stream outside {[st.name for st in streams]}")
+    at_rate, table = {}, None
+    for st in streams:
+        if st.fs not in at_rate:
+            x, t = make_synthetic_recording(phases, fs=st.fs, channels=channels, seed=seed, difficulty=difficulty, block_s=block_s)
+            if gaps is not None:
+                plant_gaps(x, gaps, st.fs, seed, streams=True)
+            at_rate[st.fs] = x
+            table = t if table is None else table
+    out = {}
+    for st in streams:
+        x = np.ascontiguousarray(at_rate[st.fs][:, [channels.index(c) for c in st.columns]])
+        if gaps is not None:
+            for a, b in gap_spans(gaps, st.fs, x.shape[0], stream=st.name):
+                x[a:b, :] = np.nan
+        out[st.name] = x
+    return out, [dict(row, start=row["start_s"] * fs, end=row["end_s"] * fs) for row in table]

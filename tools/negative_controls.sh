@@ -57,6 +57,12 @@
 # every case, the control must FAIL every case (every case holds a row whose entropy is of order 1: uniform rows, and saturated rows
 # with their peak twice).  Time limit, the stop at the first abnormal exit and the per-library sections as in the regime mode.
 # LIBRARY: product 1 (default both).
+# tools/negative_controls.sh mixed [OUT] [LIBRARY ...]: the control of the MIXED-RATE push (library built by
+#   make -C multimodalsignal_amd/csrc negctl MIXED=1 ): mx_lv_push_kernel reads tail row (j + 1) % tail_rows for raw row j (mixed.hip
+# MSIG_NEGCTL_MIXED), in bounds by construction.  Per library: one pass of the single-group test and of the chunking cases of
+# tests/test_mixed_rate_gpu.py — the product must pass every case, the control must FAIL every one (each pushes chunks whose first
+# outputs reach behind the chunk).  Time limit, the stop at the first abnormal exit and the per-library sections as in the regime mode.
+# LIBRARY: product 1 (default both).
 # tools/negative_controls.sh batch [OUT] [LIBRARY ...]: the controls of the BATCH SIZES (DESIGN.md "Batch sizes"; libraries built by
 #   for k in 1 2 3 4; do make -C multimodalsignal_amd/csrc negctl BATCH=$k; done ).  Each is one in-bounds, arithmetic-only slip in a guard
 # on the batch size (msig_dev.h MSIG_NEGCTL_BATCH): 1 the latency form's backward recurrence keeps the gate gradients of padding rows in
@@ -181,6 +187,37 @@ if [ "$1" = stage2 ]; then
   done
   echo "# tools/negative_controls.sh stage2: $NEW and $OLDF against libmsig_hip_stage21.so (make negctl STAGE2=1)" > "$OUT"
   for k in product 1; do [ -f $D/stage2_negctl_section_$k.log ] && cat $D/stage2_negctl_section_$k.log >> "$OUT"; done
+  tail -n +1 "$OUT"
+  exit $bad
+fi
+if [ "$1" = mixed ]; then
+  OUT=${2:-mixed_negctl_out/mixed_negative_control.log}
+  D=$(dirname "$OUT")
+  shift; shift
+  LIBS=${*:-product 1}
+  NEW="tests/test_mixed_rate_gpu.py::test_one_group_of_all_columns_is_the_single_rate_call tests/test_mixed_rate_gpu.py::test_every_way_of_chunking_gives_the_offline_bits"
+  mkdir -p "$D"
+  bad=0
+  for k in $LIBS; do
+    if [ "$k" = product ]; then lib=$PWD/multimodalsignal_amd/libmsig_hip.so; else lib=$PWD/multimodalsignal_amd/csrc/build/libmsig_hip_mixed$k.so; fi
+    sec=$D/mixed_negctl_section_$k.log
+    [ -f "$lib" ] || { echo "## library: $(basename $lib): missing" > $sec; bad=1; continue; }
+    MSIG_LIB=$lib timeout -k 10 300 python -m pytest $NEW -q -rA -p no:cacheprovider > $D/mixed_negctl_${k}.txt 2>&1; rc=$?
+    echo "## library: $(basename $lib)" > $sec
+    echo "# $NEW (exit $rc):   $(tail -1 $D/mixed_negctl_${k}.txt)" >> $sec
+    grep -E "^(PASSED|FAILED) " $D/mixed_negctl_${k}.txt | sed 's/ - .*//' | sort >> $sec
+    if [ $rc != 0 ] && [ $rc != 1 ]; then echo "!! abnormal exit $rc: stopped here" >> $sec; bad=2; break; fi
+    if [ "$k" = product ]; then
+      [ $rc = 0 ] || { echo "!! the product library must pass every case" >> $sec; bad=1; }
+      continue
+    fi
+    npass=$(grep -c "^PASSED " $D/mixed_negctl_${k}.txt)
+    nfail=$(grep -c "^FAILED " $D/mixed_negctl_${k}.txt)
+    if [ "$npass" = 0 ] && [ "$nfail" -gt 0 ]; then echo "# verdict: control $k FAILS all $nfail cases" >> $sec
+    else echo "!! control $k passes $npass cases: the tests do not catch it there" >> $sec; bad=1; fi
+  done
+  echo "# tools/negative_controls.sh mixed: the single-group and chunking cases of tests/test_mixed_rate_gpu.py against libmsig_hip_mixed1.so (make negctl MIXED=1)" > "$OUT"
+  for k in product 1; do [ -f $D/mixed_negctl_section_$k.log ] && cat $D/mixed_negctl_section_$k.log >> "$OUT"; done
   tail -n +1 "$OUT"
   exit $bad
 fi
